@@ -2,7 +2,7 @@
 """Self-play throughput benchmark (BASELINE.json metric: self-play games/sec at 800 sims/move,
 ResNet-24 "53M" (R24-320), 1/2/4/8 MI355X).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -22,18 +22,32 @@ MEASURED plies/sec (searched and played plies counted by the engine) divided by 
 profiles/game_length.json (measured by running whole generations of games to completion with this engine/config;
 the basis is named in the JSON line).
 
+A plain run sets up, warms up, times the K plies, writes the outputs when `--dump-outputs DIR` is given and prints the JSON line;
+`--full` adds the supplementary measurements below (CPU baseline, the evaluation-cache and half-split regions).
+
 `value` is measured with every leaf going through the network (`engine.eval_cache` off).  The drop-in worker's default has the
 cache on -- a leaf reached more than once in a pass shares one batch row and a per-game cache serves positions evaluated in
 earlier passes, ~5 % of the leaf evaluations; every simulation is still played and the games are bit-identical
-(tests/test_eval_cache_gpu.py) -- so the same K plies are timed a second time with it on and reported in `eval_cache`
+(tests/test_eval_cache_gpu.py) -- so with `--full` the same K plies are timed a second time with it on and reported in `eval_cache`
 (`value_with_eval_cache`); `--no-eval-cache` skips that region, `--eval-cache-in-value` measures `value` itself with it on.
-A third, supplementary region times the same K plies with `engine.tail_split = "halves"` (opt-in: every pass as two half batches
-side by side; `half_split.value_with_half_split`; `--no-half-split-region` skips it).  Neither extra region enters `value` or `roofline`.
+A third, supplementary region (`--full`) times the same K plies with `engine.tail_split = "halves"` (opt-in: every pass as two half
+batches side by side; `half_split.value_with_half_split`; `--no-half-split-region` skips it).  Neither extra region enters `value`
+or `roofline`.
+
+--dump-outputs DIR: after the timed region of `value`, the state its last step left is written as .npy files (fixed seeds, so
+the same arguments give the same inputs on every run and two builds can be compared file for file): the leaves the resident
+trees select next and the network's answer to them, through the split-step seam that is bit-identical to the fused step
+(tests/test_timed_path_gpu.py).  Rows are put in a canonical order (the select kernel hands out batch rows in arrival order).
+  leaf_values.npy         f32 [rows]             value head, every row
+  leaf_planes.npy         f32 [S,19,8,8]         input planes of a seeded sample of S = min(rows, 2048) rows
+  leaf_policy_logits.npy  f32 [S,4672]           policy logits of the same rows
+  timed_counters.npy      f64 [5]                evaluations, simulations, plies, games finished, passes of the timed region
+With several ranks every file name carries `_rank<r>`.
 
 Extra objects in the JSON line:
   roofline      dominant kernel = 3x3 320->320 implicit-GEMM conv (MFMA-bound); achieved = algorithmic FLOP /
                 launch time from HIP events around every launch on the launch stream, summed over the timed region
-  cpu_baseline  BASELINE configs[0] on this box's host cores: W = cores / threads worker processes, each playing one
+  cpu_baseline  (--full) BASELINE configs[0] on the host cores: W = cores / threads worker processes, each playing one
                 self-play game at 64 sims/move with the CPU oracle (oracle/selfplay_ref.py + oracle/mcts_ref.py, reference
                 search semantics: batches of <= 96 leaves, no virtual loss) and the torch-CPU fp32 R24-320 forward, for a
                 bounded time; rank 0 at N=1 only, run BEFORE the GPU is touched so the two do not share the host
@@ -214,6 +228,11 @@ def main():
                          "on the whole chip; the default bench keeps one forward per pass")
     ap.add_argument("--cu-split", action="store_true",
                     help="experiment (with --streams 2): the two engines' streams run on complementary CU halves of every XCD")
+    ap.add_argument("--full", action="store_true",
+                    help="also the supplementary measurements: the CPU baseline and the second (eval_cache) and third (half_split) "
+                         "timed regions; a plain run times `value` only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region of `value`, write what its last step left as DIR/<name>.npy (module docstring)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -224,7 +243,7 @@ def main():
 
     # CPU baseline first (rank 0, N=1): its worker processes are started before this process touches the GPU
     cpu = None
-    if rank == 0 and world == 1 and args.gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and args.gpus == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_seconds, game_length_basis()[0], args.cpu_threads)
 
     import numpy as np
@@ -277,7 +296,31 @@ def main():
 
     substeps = -(-args.sims // args.leaves)          # passes of the hot path per searched ply (all games in step)
 
-    def measure(eval_cache: bool, split=None):
+    def dump_outputs(engines, backends, counters):
+        """--dump-outputs: the leaves the trees select after the last timed step and the network's answer to them (the split-step
+        seam: ext_select -> infer_np, bit-identical to the fused step), rows in a canonical order, plus the timed counters."""
+        planes, logits, values = [], [], []
+        for x, b_ in zip(engines, backends):
+            pl = x.ext_select()
+            if pl.shape[0]:
+                lg, vv = b_.infer_np(pl)
+                planes.append(pl); logits.append(lg); values.append(vv)
+        planes = np.concatenate(planes) if planes else np.zeros((0, 19, 8, 8), np.float32)
+        logits = np.concatenate(logits) if logits else np.zeros((0, 4672), np.float32)
+        values = np.concatenate(values) if values else np.zeros((0,), np.float32)
+        flat = planes.reshape(planes.shape[0], -1)
+        order = np.array(sorted(range(flat.shape[0]), key=lambda i: flat[i].tobytes()), dtype=np.int64)
+        sample = np.sort(np.random.default_rng(0).choice(order.size, size=min(order.size, 2048), replace=False))
+        rows = order[sample]
+        suffix = f"_rank{rank}" if world > 1 else ""
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("leaf_values", values[order].astype(np.float32)),
+                        ("leaf_planes", planes[rows].astype(np.float32)),
+                        ("leaf_policy_logits", logits[rows].astype(np.float32)),
+                        ("timed_counters", np.asarray(counters, dtype=np.float64))):
+            np.save(os.path.join(args.dump_outputs, f"{name}{suffix}.npy"), a)
+
+    def measure(eval_cache: bool, split=None, dump=False):
         """One engine, warm-up, then the timed region of exactly `--steps` searched plies per resident game."""
         if split is None:
             split = "halves" if args.half_split else args.tail_split
@@ -316,6 +359,9 @@ def main():
         conv_ms, conv_flop, conv_launches = be.profile_get(reset=True)
         tail = getattr(be, "last_tail_profile", (0.0, 0))
         be.profile_enable(False)
+        if dump:
+            dump_outputs(e.engines if args.streams > 1 else [e], e.backends if args.streams > 1 else [be],
+                         [s1[k] - s0[k] for k in ("evals", "sims", "plies", "games_finished")] + [passes_timed])
         if args.streams > 1:
             for x in e.engines:
                 x.close()                                   # the first backend is `be`: it stays open for the next measurement
@@ -336,18 +382,18 @@ def main():
     # The product default (drop-in worker) has engine.eval_cache on; the same K plies are then timed a second time with it on
     # and reported beside `value` in `eval_cache` (--no-eval-cache: skip that; --eval-cache-in-value: `value` itself with it on)
     primary_cache = bool(args.eval_cache_in_value)
-    dt_max, tot, tail_prof = measure(primary_cache)
+    dt_max, tot, tail_prof = measure(primary_cache, dump=args.dump_outputs is not None)
     evals, plies, gfin, conv_ms, conv_flop, conv_launches, ms_net, ms_tree, ms_host, sims, passes_all, cached, rows_tail = tot
     passes = max(1.0, passes_all / args.gpus)           # passes per rank in the timed region
     second = None
-    if not args.no_eval_cache and not primary_cache:
+    if args.full and not args.no_eval_cache and not primary_cache:
         dt2, tot2, _ = measure(True)
         second = {"dt": dt2, "evals": tot2[0], "plies": tot2[1], "gfin": tot2[2], "sims": tot2[9], "passes": tot2[10], "cached": tot2[11]}
     # third region (supplementary, like the second): the same K plies with engine.tail_split = "halves" -- every pass as two half
     # batches side by side (bit-identical games, tests/test_selfplay_gpu.py).  Kept OUT of `value` and of `roofline`: with two
     # forwards in flight a launch shares the chip with the other half's kernels and its event-bracketed time describes no kernel
     third = None
-    if not args.no_half_split_region and not args.half_split and not args.tail_split and args.streams == 1:
+    if args.full and not args.no_half_split_region and not args.half_split and not args.tail_split and args.streams == 1:
         dt3, tot3, _ = measure(primary_cache, split="halves")
         third = {"dt": dt3, "evals": tot3[0], "plies": tot3[1], "gfin": tot3[2], "rows_tail": tot3[12]}
 

@@ -1,12 +1,7 @@
-"""Training-side reader (matrix0_amd/npz_dataset.py) over shards written by this package, and -- in the build container,
-where /root/reference exists -- the REFERENCE's own DataManager reading the same shards (the drop-in direction that matters:
-the reference trainer consumes what the engine writes)."""
-import os
+"""Training-side reader (matrix0_amd/npz_dataset.py) over shards written by this package."""
 import sqlite3
-import sys
 
 import numpy as np
-import pytest
 
 from matrix0_amd.data_writer import ReplayShardWriter
 from matrix0_amd.npz_dataset import NPZBatchIterableDataset, ReplayReader
@@ -61,26 +56,3 @@ def test_bad_shards_are_marked_corrupted_and_skipped(tmp_path):
     assert conn.execute("SELECT corrupted FROM shards WHERE path = ?", (bad,)).fetchone()[0] == 1
     conn.close()
     assert bad not in ReplayReader(str(tmp_path)).valid_shards()
-
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/azchess"), reason="the reference exists in the build container only")
-def test_reference_datamanager_reads_our_shards(tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path.insert(0, os.path.join(root, "tools"))
-    import refshim
-    refshim.install()
-    import logging
-    logging.disable(logging.CRITICAL)
-    from azchess.data_manager import DataManager
-    rng = np.random.default_rng(3)
-    _write(tmp_path, rng, games=5, n=64, shard_size=64)
-    dm = DataManager(base_dir=str(tmp_path), expected_planes=19)
-    it = dm.get_training_batch(64, "cpu")
-    seen = []
-    for _ in range(5):
-        b = next(it)
-        assert len(b) == 4 and b[0].shape == (64, 19, 8, 8) and b[1].shape == (64, 4672) and b[3].shape == (64, 4672)
-        seen.append(b[0][:, 0, 0, 0])
-    assert set(np.unique(np.concatenate(seen))) <= {1.0, 2.0, 3.0, 4.0, 5.0}
-    stats = [s for s in dm._get_all_shards() if not s.corrupted]
-    assert len(stats) == 5 and all(s.sample_count == 64 for s in stats)
