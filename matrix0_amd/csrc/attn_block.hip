@@ -44,10 +44,6 @@ constexpr int AB_PAR = AB_RING + 4 * AB_PIECE;            // 156160: LayerNorm g
 constexpr int AB_LDS = AB_PAR + 4 * 320 * 4;              // 161280
 }
 
-__device__ __forceinline__ void ab_dma16(const void* gsrc, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 // 64 bytes per lane from global memory that the compiler does not track (the caller waits: vmcnt)
 __device__ __forceinline__ void ab_load64(half8& b0, half8& b1, half8& b2, half8& b3, const half8* p) {
     asm volatile("global_load_dwordx4 %0, %4, off\n\tglobal_load_dwordx4 %1, %4, off offset:16\n\t"
@@ -123,7 +119,7 @@ __global__ __launch_bounds__(512) void attn_block_kernel(AttnBlockArgs a) {
         const int q = idx * 64 + lane;
         const int row = q / 40, pos = q - row * 40;
         const int src = (pos & ~7) | ((pos ^ (row >> 1)) & 7);
-        ab_dma16(xg + row * 640 + src * 16, smem + AB_X + idx * 1024);
+        glds16(xg + row * 640 + src * 16, smem + AB_X + idx * 1024);
     }
     // a piece is 12 x 1 KB: every wave issues one full 16-byte DMA and one with its upper 32 lanes masked off (1.5 KB per
     // wave), so the count of outstanding vector-memory operations is the same in all 8 waves.  (global_load_lds_dwordx3
@@ -134,8 +130,8 @@ __global__ __launch_bounds__(512) void attn_block_kernel(AttnBlockArgs a) {
     auto issue = [&](int t) __attribute__((always_inline)) {
         const char* s = wsrc + (size_t)t * AB_PIECE;
         char* d = ring_w + (t & 3) * AB_PIECE;
-        ab_dma16(s, d);
-        if (lane < 32) ab_dma16(s + 1024, d + 1024);
+        glds16(s, d);
+        if (lane < 32) glds16(s + 1024, d + 1024);
     };
     // AB_WAIT(4) = all but this wave's two youngest pieces have landed.  Only LDS-DMA operations may be outstanding at a
     // counted wait: loads into registers and loads into LDS do not retire in one order (measured: a later DMA retired

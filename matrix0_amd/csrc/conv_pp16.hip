@@ -17,10 +17,6 @@
 #include "conv_epilogue16.h"
 #include "conv_tail16.h"
 
-__device__ __forceinline__ void p16_glds16(const void* gsrc, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 #define P16_FENCE() asm volatile("" ::: "memory")
 
 #ifdef SW_STAMP
@@ -64,15 +60,15 @@ __global__ __launch_bounds__(512) void conv_pp16_kernel(GemmArgs a) {
         const int p = 8 * qq + (lane >> 3);             // 1-KiB piece: squares 8qq..8qq+7 of the 256-row tile
         const int cl = lane & 7;                        // LDS 16-byte chunk this lane fills
         const char* src = in_bytes + ((size_t)(m0 + p) * Cin + (size_t)chunk * 64) * 2 + 16 * (cl ^ ((p >> 1) & 7));
-        p16_glds16(src, A_lds + (chunk & 1) * A_BYTES + qq * 1024);
+        glds16(src, A_lds + (chunk & 1) * A_BYTES + qq * 1024);
     };
     auto issue_half = [&](int y) __attribute__((always_inline)) {      // prologue only
         const char* src = w_blk + (size_t)(y >> 1) * w_kt_stride + (size_t)(y & 1) * WH_BYTES;
         char* dst = W_lds + (y & 3) * WH_BYTES;
-        p16_glds16(src + wave * 1024, dst + wave * 1024);
-        p16_glds16(src + (8 + wave) * 1024, dst + (8 + wave) * 1024);
-        if (wave < 4) p16_glds16(src + (16 + wave) * 1024, dst + (16 + wave) * 1024);
-        else p16_glds16(w_blk, D_lds + (wave - 4) * 1024);  // filler: keeps 3 pieces per wave and half-tile (vmcnt)
+        glds16(src + wave * 1024, dst + wave * 1024);
+        glds16(src + (8 + wave) * 1024, dst + (8 + wave) * 1024);
+        if (wave < 4) glds16(src + (16 + wave) * 1024, dst + (16 + wave) * 1024);
+        else glds16(w_blk, D_lds + (wave - 4) * 1024);  // filler: keeps 3 pieces per wave and half-tile (vmcnt)
     };
 
     float4v acc[MT][NG];
@@ -119,13 +115,13 @@ __global__ __launch_bounds__(512) void conv_pp16_kernel(GemmArgs a) {
     auto issue_next = [&](auto G_) __attribute__((always_inline)) {
         constexpr int G = decltype(G_)::value;
         char* dst = W_lds + w_slot + wave * 1024;
-        p16_glds16(w_ptr + w_lane, dst);
-        p16_glds16(w_ptr + 8192 + w_lane, dst + 8192);
+        glds16(w_ptr + w_lane, dst);
+        glds16(w_ptr + 8192 + w_lane, dst + 8192);
         if constexpr (G == 0) {
-            p16_glds16(w_ptr + 16384 + w_lane, dst + 16384);
+            glds16(w_ptr + 16384 + w_lane, dst + 16384);
         } else {
             const bool have = a_left > 0;
-            p16_glds16((have ? a_ptr : in_bytes) + a_lane, have ? A_lds + a_dst : D_lds + (wave - 4) * 1024);
+            glds16((have ? a_ptr : in_bytes) + a_lane, have ? A_lds + a_dst : D_lds + (wave - 4) * 1024);
             a_ptr += have ? (size_t)32 * Cin * 2 : 0;
             a_dst += have ? 4096 : 0;
             a_left -= have ? 1 : 0;
@@ -222,16 +218,9 @@ __global__ __launch_bounds__(512) void conv_pp16_kernel(GemmArgs a) {
         o[0] = st_entry; o[1] = __builtin_amdgcn_s_memrealtime(); o[2] = hw; o[3] = xcc;
     }
 #endif
-#ifdef PP_NO_EPILOGUE
-#pragma unroll
-    for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NG; ++ni) asm volatile("" :: "v"(acc[mi][ni]));
-#else
     if constexpr (EPI == 3) conv_tail_epilogue16<ACT, false>(acc, a, smem, m0, wm, wn, wave, lane);
     else if constexpr (EPI == 5) conv_tail_epilogue16<ACT, true>(acc, a, smem, m0, wm, wn, wave, lane);
     else conv_tile_epilogue16<EPI, ACT>(acc, a, smem + wave * (5 * 64 * 64), m0, n0, wm, wn, lane);
-#endif
 }
 
 template <int EPI, int ACT>

@@ -1,19 +1,22 @@
-// Residual-block tail fused into conv2's epilogue (conv_pp_kernel, EPI 3):
-//   t      = conv2 output (this workgroup holds 4 whole boards x all 320 channels in its accumulators)
+// Residual-block tails fused into a conv's epilogue (the workgroup holds 4 whole boards x all 320 channels in its
+// accumulators):
+//   t      = conv output
 //   gate   = sigmoid(W2 act(W1 mean_squares(t) + b1) + b2)            squeeze-excite, resnet.py:59-68 (optional)
+//   or PRE: t <- act(GroupNorm16(t; a.pre_gamma, a.pre_beta))          the chess-feature convs, resnet.py:229-244
 //   y      = x + gate * t                                             the residual stream          -> a.out
 //   y2     = act(GroupNorm16(y; next block's bn1))                    the next conv1's operand     -> a.y2 (optional)
 // i.e. what conv2's plain epilogue + se_gate_kernel + ew_board_kernel did with three launches and two more trips of
 // the tensor through HBM.  Everything a board needs is inside the workgroup, so the only new global traffic is the
-// read of x.  The phases, all 8 waves together (LDS is free once the main loop is over):
-//   A  per-board channel means of t from the accumulators                         -> LDS pool[4][C]
-//   B  W1 (C x Hd f32) by global_load_lds -> LDS, hidden = act(W1 pool + b1);  W2 likewise, gate -> LDS; each lane
-//      picks up the 5 gate values of its accumulator columns
-//   C  gate * t staged as fp16 in the wave's private LDS image [64 rows][160 ch]   (conv_stage_tile)
-//   D  lane = (16-byte channel chunk, row mod 3): add x (global, 16-byte loads issued up front), store y, write y back
-//      to the image, per-channel sums -> GroupNorm statistics of the wave's 10 groups by shuffles
-//   E  second pass over the image: y2 = act(y * scale + shift), 16-byte stores
-// Phases C-E touch only the wave's own image: no workgroup barrier after B.
+// read of x.  Each accumulator layout has its own tail: conv_tail_epilogue below (conv_big_kernel, PRE only),
+// conv_tail16.h (conv_pp16_kernel) and conv_zs_tail.h (conv_zs_kernel).  Each reads its accumulators (channel means,
+// squeeze-excite gate, PRE statistics) and stages gate * t as fp16 in the wave's private LDS image, 64 rows of 20
+// 16-byte chunks, issuing the loads of x between the tile columns.  The rest works on that image and is shared:
+//   tail_gn_params  the second GroupNorm's parameters of the lane's 8 channels (fetched first: a late load is an
+//                   exposed global-memory latency in a kernel with one workgroup per CU)
+//   tail_residual   lane = (16-byte chunk, row mod 3): y = x + image, store y, write y back to the image, GroupNorm sums
+//   tail_gn_stats   the GroupNorm statistics of the lane's group by shuffles
+//   tail_y2         second pass over the image: y2 = act(y * scale + shift), 16-byte stores
+// None of them needs a workgroup barrier.
 //
 // (The attention block's tail -- residual + LayerNorm over C + next GroupNorm -- was fused into the proj conv the same
 //  way, in the accumulator layout with DPP row reductions: correct, but 374 us against 92 + 228 us for proj +
@@ -22,191 +25,33 @@
 #pragma once
 #include "conv_epilogue.h"
 
-__device__ __forceinline__ void tail_glds16(const void* gsrc, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+constexpr int TAIL_NCH = 20;         // 16-byte chunks per image row (160 channels)
+constexpr int TAIL_NIT = 22;         // image rows per lane: ceil(64 / 3)
+
+__device__ __forceinline__ void tail_gn_params(const GemmArgs& a, int c0, float (&gg)[8], float (&bb)[8]) {
+    const float4 g0 = *reinterpret_cast<const float4*>(a.gn_gamma + c0), g1 = *reinterpret_cast<const float4*>(a.gn_gamma + c0 + 4);
+    const float4 b0 = *reinterpret_cast<const float4*>(a.gn_beta + c0), b1 = *reinterpret_cast<const float4*>(a.gn_beta + c0 + 4);
+    gg[0] = g0.x; gg[1] = g0.y; gg[2] = g0.z; gg[3] = g0.w; gg[4] = g1.x; gg[5] = g1.y; gg[6] = g1.z; gg[7] = g1.w;
+    bb[0] = b0.x; bb[1] = b0.y; bb[2] = b0.z; bb[3] = b0.w; bb[4] = b1.x; bb[5] = b1.y; bb[6] = b1.z; bb[7] = b1.w;
 }
 
-// C == 320 (one N block), 8 waves: wave = (board wm, channel half wn), NT == 5.
-// PRE: t is first normalised and activated, t <- act(GroupNorm16(t; a.pre_gamma, a.pre_beta)) -- the chess-feature
-// convs (resnet.py:229-244: x += act(norm(conv(x)))); no squeeze-excite in that case.
-template <int ACT, bool PRE = false>
-__device__ __forceinline__ void conv_tail_epilogue(float16v (&acc)[2][5], const GemmArgs& a, char* smem, int m0, int wm,
-                                                   int wn, int wave, int lane) {
-    constexpr int NT = 5, C = 320;
-    const int tid = wave * 64 + lane;
-    const int r31 = lane & 31, half = lane >> 5;
-    float* pool = reinterpret_cast<float*>(smem);              // [C][4 boards]   5120 B (one 16-byte read per channel)
-    float* gate = pool + 4 * C;                                // [4][C]          5120 B
-    float* hid = gate + 4 * C;                                 // [Hd<=128][4]    2048 B
-    float* part = hid + 4 * 128;                               // [parts<=8][4][Hd<=128] 16384 B
-    float* wst = reinterpret_cast<float*>(smem + 32768);       // staged W1 / W2: C*Hd*4 <= 131072 B - 32768
-    const int Hd = a.se_hidden;
-    const bool se = a.se_w1 != nullptr;
-    // phase D/E lane mapping and the second output's GroupNorm parameters (fetched now: a late load is an exposed
-    // global-memory latency in a kernel with one workgroup per CU)
-    constexpr int NCH = NT * 4;                                  // 20 chunks per 160-channel row
-    constexpr int NIT = 22;                                      // ceil(64 / 3)
-    const int chunk = lane % NCH, rsub = lane / NCH;
+// y = x + image; lane = (chunk = lane % 20, rsub = lane / 20), rows rsub, rsub+3, ...; lanes 60..63 idle.  Row `row` of
+// the lane is at img + lane_loff + row * 320 and at global offset lane_goff + row * ldo2 of yout (stored below rows_valid).
+// The sum of two fp16 numbers rounded to fp16 is what the fp32 add + conversion gives, so y is computed with packed
+// fp16 adds (4 instructions per 8 channels); the GroupNorm sums (this lane's 8 channels x its rows) use the
+// 2-element fp16 dot product with fp32 accumulation, on the rounded y (the tensor that is actually stored).
+__device__ __forceinline__ void tail_residual(char* img, uint32_t lane_loff, char* yout, uint32_t lane_goff, uint32_t ldo2,
+                                              int rows_valid, const half8 (&xv)[TAIL_NIT], int lane, float& gs, float& gss) {
+    const int rsub = lane / TAIL_NCH;
     const bool lane_on = rsub < 3;
-    float gg[8], bb[8];
-    if (a.y2 != nullptr) {
-        const int c0 = wn * 160 + chunk * 8;
-        const float4 g0 = *reinterpret_cast<const float4*>(a.gn_gamma + c0), g1 = *reinterpret_cast<const float4*>(a.gn_gamma + c0 + 4);
-        const float4 b0 = *reinterpret_cast<const float4*>(a.gn_beta + c0), b1 = *reinterpret_cast<const float4*>(a.gn_beta + c0 + 4);
-        gg[0] = g0.x; gg[1] = g0.y; gg[2] = g0.z; gg[3] = g0.w; gg[4] = g1.x; gg[5] = g1.y; gg[6] = g1.z; gg[7] = g1.w;
-        bb[0] = b0.x; bb[1] = b0.y; bb[2] = b0.z; bb[3] = b0.w; bb[4] = b1.x; bb[5] = b1.y; bb[6] = b1.z; bb[7] = b1.w;
-    }
-    float gv[NT];
-#ifdef TAIL_NO_SE
-    if (false) {
-#else
-    if (se && !PRE) {
-#endif
-        const int wbytes = C * Hd * 4;                          // multiple of 1024 (C = 320)
-        const int npieces = wbytes >> 10;
-        // B1 (issued first, lands while phase A runs): W1 -> LDS
-        for (int p = wave; p < npieces; p += 8)
-            tail_glds16(reinterpret_cast<const char*>(a.se_w1) + p * 1024 + lane * 16, reinterpret_cast<char*>(wst) + p * 1024);
-        // A: channel means of this wave's board / channel half
-        static_for<0, NT>([&](auto ni_) __attribute__((always_inline)) {
-            constexpr int ni = decltype(ni_)::value;
-            float s = 0.f;
-            static_for<0, 2>([&](auto mi_) __attribute__((always_inline)) {
-                static_for<0, 16>([&](auto r_) __attribute__((always_inline)) { s += acc[decltype(mi_)::value][ni][decltype(r_)::value]; });
-            });
-            s += __shfl_xor(s, 32);
-            if (lane < 32) pool[(wn * 160 + ni * 32 + r31) * 4 + wm] = s * (1.f / 64.f);
-        });
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        // B2: hidden = act(W1 pool + b1); thread = (hidden unit j, channel part), the 4 boards at once; w1 is [C][Hd]
-        const int parts = 512 / Hd > 8 ? 8 : 512 / Hd;
-        {
-            const int j = tid % Hd, p = tid / Hd;
-            if (p < parts) {
-                const int cpp = (C + parts - 1) / parts;
-                const int cbeg = p * cpp, cend = cbeg + cpp < C ? cbeg + cpp : C;
-                float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll 6
-                for (int c = cbeg; c < cend; ++c) {
-                    const float w = wst[c * Hd + j];
-                    const float4 pv = *reinterpret_cast<const float4*>(pool + c * 4);
-                    s0 = __builtin_fmaf(w, pv.x, s0); s1 = __builtin_fmaf(w, pv.y, s1); s2 = __builtin_fmaf(w, pv.z, s2); s3 = __builtin_fmaf(w, pv.w, s3);   // explicit: all four boards alike (se_gate_kernel's header)
-                }
-                float* pp = part + (p * 4) * 128 + j;
-                pp[0] = s0; pp[128] = s1; pp[256] = s2; pp[384] = s3;
-            }
-        }
-        __syncthreads();
-        // B3: W2 -> LDS (W1 is dead), meanwhile the hidden units
-        for (int p = wave; p < npieces; p += 8)
-            tail_glds16(reinterpret_cast<const char*>(a.se_w2) + p * 1024 + lane * 16, reinterpret_cast<char*>(wst) + p * 1024);
-        for (int i = tid; i < 4 * Hd; i += 512) {
-            const int b = i / Hd, j = i - b * Hd;
-            float s = a.se_b1[j];
-            for (int p = 0; p < parts; ++p) s += part[(p * 4 + b) * 128 + j];
-            hid[j * 4 + b] = act_fast<ACT>(s);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        // B4: gate = sigmoid(W2 hidden + b2); thread = channel (first 320 threads), the 4 boards at once; w2 is [Hd][C]
-        if (tid < C) {
-            const float b2 = a.se_b2[tid];
-            float s0 = b2, s1 = b2, s2 = b2, s3 = b2;
-#pragma unroll 8
-            for (int j = 0; j < Hd; ++j) {
-                const float w = wst[j * C + tid];
-                const float4 hv = *reinterpret_cast<const float4*>(hid + j * 4);
-                s0 = __builtin_fmaf(w, hv.x, s0); s1 = __builtin_fmaf(w, hv.y, s1); s2 = __builtin_fmaf(w, hv.z, s2); s3 = __builtin_fmaf(w, hv.w, s3);
-            }
-            gate[tid] = __builtin_amdgcn_rcpf(1.f + __expf(-s0));
-            gate[C + tid] = __builtin_amdgcn_rcpf(1.f + __expf(-s1));
-            gate[2 * C + tid] = __builtin_amdgcn_rcpf(1.f + __expf(-s2));
-            gate[3 * C + tid] = __builtin_amdgcn_rcpf(1.f + __expf(-s3));
-        }
-        __syncthreads();
-        // B5: the gate values of this lane's accumulator columns
-        static_for<0, NT>([&](auto ni_) __attribute__((always_inline)) {
-            constexpr int ni = decltype(ni_)::value;
-            gv[ni] = gate[wm * C + wn * 160 + ni * 32 + r31];
-        });
-        __syncthreads();                                          // the images below overwrite pool / gate / wst
-    } else {
-        static_for<0, NT>([&](auto ni_) __attribute__((always_inline)) { gv[decltype(ni_)::value] = 1.f; });
-    }
-    float pv[NT];                                                 // PRE: per-column shift (gv = scale)
-    if constexpr (PRE) {
-        // GroupNorm(16 channels x 64 squares) of t on the accumulators: the wave owns whole groups (as EPI 1)
-        static_for<0, NT>([&](auto ni_) __attribute__((always_inline)) {
-            constexpr int ni = decltype(ni_)::value;
-            const int col = wn * 160 + ni * 32 + r31;
-            float s = 0.f, ss = 0.f;
-            static_for<0, 2>([&](auto mi_) __attribute__((always_inline)) {
-                const float16v av = acc[decltype(mi_)::value][ni];
-                static_for<0, 16>([&](auto r_) __attribute__((always_inline)) { const float v = av[decltype(r_)::value]; s += v; ss += v * v; });
-            });
-#pragma unroll
-            for (int o = 1; o <= 8; o <<= 1) { s += __shfl_xor(s, o); ss += __shfl_xor(ss, o); }
-            s += __shfl_xor(s, 32); ss += __shfl_xor(ss, 32);
-            const float mean = s * (1.f / 1024.f);
-            float var = ss * (1.f / 1024.f) - mean * mean;
-            var = var > 0.f ? var : 0.f;
-            gv[ni] = rsqrtf(var + 1e-5f) * a.pre_gamma[col];
-            pv[ni] = a.pre_beta[col] - mean * gv[ni];
-        });
-    }
-
-    // C: gate * t -> the wave's fp16 image; the loads of x are issued between the tile columns, into the registers
-    // the staged accumulators free (x is 2-3 us away and nothing else runs on this CU)
-    char* img = smem + wave * (NT * 64 * 64);
-    char* wbase = conv_stage_base<NT>(img, lane);
-    const uint32_t ldo2 = (uint32_t)a.ldo * 2u;
-    const size_t tile_off = ((size_t)(m0 + wm * 64) * a.ldo + wn * 160) * 2;      // wave-uniform
-    const char* xin = reinterpret_cast<const char*>(a.res) + tile_off;
-    char* yout = reinterpret_cast<char*>(a.out) + tile_off;
-    const int rows_valid = a.Mvalid - (m0 + wm * 64);
-    const uint32_t lane_goff = (uint32_t)rsub * ldo2 + (uint32_t)chunk * 16u;
-    const uint32_t lane_loff = (uint32_t)(rsub * NCH + chunk) * 16u;
-    half8 xv[NIT];
-    static_for<0, NT>([&](auto ni_) __attribute__((always_inline)) {
-        constexpr int ni = decltype(ni_)::value;
-        static_for<0, 2>([&](auto mi_) __attribute__((always_inline)) {
-            constexpr int mi = decltype(mi_)::value;
-            float v[16];
-            static_for<0, 16>([&](auto r_) __attribute__((always_inline)) {
-                constexpr int r = decltype(r_)::value;
-                if constexpr (PRE) v[r] = act_fast<ACT>(acc[mi][ni][r] * gv[ni] + pv[ni]);
-                else v[r] = acc[mi][ni][r] * gv[ni];
-            });
-            conv_stage_tile<NT, mi, ni>(v, wbase, lane);
-        });
-        __builtin_amdgcn_sched_barrier(0);
-        static_for<ni * 5, (ni * 5 + 5 < NIT ? ni * 5 + 5 : NIT)>([&](auto it_) __attribute__((always_inline)) {
-            constexpr int it = decltype(it_)::value;
-            const int row = rsub + 3 * it;
-#ifdef TAIL_NO_XLOAD
-            xv[it] = half8{0, 0, 0, 0, 0, 0, 0, 0};
-#else
-            xv[it] = (lane_on && row < 64) ? *reinterpret_cast<const half8*>(xin + (lane_goff + (uint32_t)(3 * it) * ldo2))
-                                           : half8{0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-        });
-        __builtin_amdgcn_sched_barrier(0);
-    });
-
-    // D: y = x + image; lane = (chunk of 8 channels, row mod 3), rows rsub, rsub+3, ...; lanes 60..63 idle
-    // The sum of two fp16 numbers rounded to fp16 is what the fp32 add + conversion gives, so y is computed with packed
-    // fp16 adds (4 instructions per 8 channels); the GroupNorm sums (this lane's 8 channels x its rows) use the
-    // 2-element fp16 dot product with fp32 accumulation, on the rounded y (the tensor that is actually stored).
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     const h2 ones = {(_Float16)1.f, (_Float16)1.f};
-    float gs = 0.f, gss = 0.f;
+    gs = 0.f; gss = 0.f;
 #pragma unroll
-    for (int it = 0; it < NIT; ++it) {
+    for (int it = 0; it < TAIL_NIT; ++it) {
         const int row = rsub + 3 * it;
         if (lane_on && row < 64) {
-            half8* ip = reinterpret_cast<half8*>(img + lane_loff + (uint32_t)(3 * it * NCH) * 16u);
+            half8* ip = reinterpret_cast<half8*>(img + lane_loff + (uint32_t)(3 * it * TAIL_NCH) * 16u);
             const half8 yv = *ip + xv[it];
             static_for<0, 4>([&](auto i_) __attribute__((always_inline)) {
                 constexpr int i = decltype(i_)::value;
@@ -218,23 +63,28 @@ __device__ __forceinline__ void conv_tail_epilogue(float16v (&acc)[2][5], const 
             if (row < rows_valid) *reinterpret_cast<half8*>(yout + (lane_goff + (uint32_t)(3 * it) * ldo2)) = yv;
         }
     }
-#ifdef TAIL_NO_Y2
-    return;
-#endif
-    if (a.y2 == nullptr) return;
+}
 
-    // GroupNorm statistics of y: over the 3 row classes (lanes chunk, chunk+20, chunk+40), then over the group's 16
-    // channels = this lane's 8 + the neighbour chunk's 8
-    {
-        const float s1 = __shfl(gs, chunk + NCH), s2 = __shfl(gs, chunk + 2 * NCH);
-        const float q1 = __shfl(gss, chunk + NCH), q2 = __shfl(gss, chunk + 2 * NCH);
-        gs = __shfl(gs, chunk) + s1 + s2;                        // every lane: totals of its chunk (same order everywhere)
-        gss = __shfl(gss, chunk) + q1 + q2;
-        const float so = __shfl_xor(gs, 1), qo = __shfl_xor(gss, 1);      // partner chunk (chunk ^ 1 is lane ^ 1 for lanes < 60)
-        const float lo_s = (chunk & 1) ? so : gs, hi_s = (chunk & 1) ? gs : so;
-        const float lo_q = (chunk & 1) ? qo : gss, hi_q = (chunk & 1) ? gss : qo;
-        gs = lo_s + hi_s; gss = lo_q + hi_q;
-    }
+// GroupNorm statistics of y: over the 3 row classes (lanes chunk, chunk+20, chunk+40), then over the group's 16
+// channels = this lane's 8 + the neighbour chunk's 8 (chunk ^ 1: the same group, a group is 2 chunks)
+__device__ __forceinline__ void tail_gn_stats(float& gs, float& gss, int lane) {
+    const int chunk = lane % TAIL_NCH;
+    const float s1 = __shfl(gs, chunk + TAIL_NCH), s2 = __shfl(gs, chunk + 2 * TAIL_NCH);
+    const float q1 = __shfl(gss, chunk + TAIL_NCH), q2 = __shfl(gss, chunk + 2 * TAIL_NCH);
+    gs = __shfl(gs, chunk) + s1 + s2;                        // every lane: totals of its chunk (same order everywhere)
+    gss = __shfl(gss, chunk) + q1 + q2;
+    const float so = __shfl_xor(gs, 1), qo = __shfl_xor(gss, 1);      // partner chunk (chunk ^ 1 is lane ^ 1 for lanes < 60)
+    const float lo_s = (chunk & 1) ? so : gs, hi_s = (chunk & 1) ? gs : so;
+    const float lo_q = (chunk & 1) ? qo : gss, hi_q = (chunk & 1) ? gss : qo;
+    gs = lo_s + hi_s; gss = lo_q + hi_q;
+}
+
+// y2 = act(GroupNorm(y)) from the image (same rows and offsets as tail_residual); gs / gss from tail_gn_stats
+template <int ACT>
+__device__ __forceinline__ void tail_y2(const char* img, uint32_t lane_loff, char* y2out, uint32_t lane_goff, uint32_t ldo2,
+                                        int rows_valid, float gs, float gss, const float (&gg)[8], const float (&bb)[8], int lane) {
+    const int rsub = lane / TAIL_NCH;
+    const bool lane_on = rsub < 3;
     const float mean = gs * (1.f / 1024.f);
     float var = gss * (1.f / 1024.f) - mean * mean;
     var = var > 0.f ? var : 0.f;
@@ -244,13 +94,11 @@ __device__ __forceinline__ void conv_tail_epilogue(float16v (&acc)[2][5], const 
         constexpr int i = decltype(i_)::value;
         scl[i] = gg[i] * rstd; shl[i] = bb[i] - mean * scl[i];
     });
-    // E: y2 = act(GroupNorm(y)) from the image
-    char* y2out = reinterpret_cast<char*>(a.y2) + tile_off;
 #pragma unroll
-    for (int it = 0; it < NIT; ++it) {
+    for (int it = 0; it < TAIL_NIT; ++it) {
         const int row = rsub + 3 * it;
         if (lane_on && row < 64 && row < rows_valid) {
-            const half8 yv = *reinterpret_cast<const half8*>(img + lane_loff + (uint32_t)(3 * it * NCH) * 16u);
+            const half8 yv = *reinterpret_cast<const half8*>(img + lane_loff + (uint32_t)(3 * it * TAIL_NCH) * 16u);
             half8 ov;
             static_for<0, 8>([&](auto i_) __attribute__((always_inline)) {
                 constexpr int i = decltype(i_)::value;
@@ -261,3 +109,73 @@ __device__ __forceinline__ void conv_tail_epilogue(float16v (&acc)[2][5], const 
     }
 }
 
+// conv_big_kernel's layout (2 x 5 tiles of 32x32, conv_epilogue.h), PRE form: out = res + act(GroupNorm16(t)) (+ y2).
+// C == 320 (one N block), 8 waves: wave = (board wm, channel half wn), NT == 5.
+template <int ACT>
+__device__ __forceinline__ void conv_tail_epilogue(float16v (&acc)[2][5], const GemmArgs& a, char* smem, int m0, int wm,
+                                                   int wn, int wave, int lane) {
+    constexpr int NT = 5;
+    const int r31 = lane & 31;
+    const int chunk = lane % TAIL_NCH, rsub = lane / TAIL_NCH;
+    const bool lane_on = rsub < 3;
+    float gg[8], bb[8];
+    if (a.y2 != nullptr) tail_gn_params(a, wn * 160 + chunk * 8, gg, bb);
+    // GroupNorm(16 channels x 64 squares) of t on the accumulators: the wave owns whole groups (as EPI 1)
+    float gv[NT], pv[NT];                                         // per-column scale and shift
+    static_for<0, NT>([&](auto ni_) __attribute__((always_inline)) {
+        constexpr int ni = decltype(ni_)::value;
+        const int col = wn * 160 + ni * 32 + r31;
+        float s = 0.f, ss = 0.f;
+        static_for<0, 2>([&](auto mi_) __attribute__((always_inline)) {
+            const float16v av = acc[decltype(mi_)::value][ni];
+            static_for<0, 16>([&](auto r_) __attribute__((always_inline)) { const float v = av[decltype(r_)::value]; s += v; ss += v * v; });
+        });
+#pragma unroll
+        for (int o = 1; o <= 8; o <<= 1) { s += __shfl_xor(s, o); ss += __shfl_xor(ss, o); }
+        s += __shfl_xor(s, 32); ss += __shfl_xor(ss, 32);
+        const float mean = s * (1.f / 1024.f);
+        float var = ss * (1.f / 1024.f) - mean * mean;
+        var = var > 0.f ? var : 0.f;
+        gv[ni] = rsqrtf(var + 1e-5f) * a.pre_gamma[col];
+        pv[ni] = a.pre_beta[col] - mean * gv[ni];
+    });
+
+    // act(t * scale + shift) -> the wave's fp16 image; the loads of x are issued between the tile columns, into the
+    // registers the staged accumulators free (x is 2-3 us away and nothing else runs on this CU)
+    char* img = smem + wave * (NT * 64 * 64);
+    char* wbase = conv_stage_base<NT>(img, lane);
+    const uint32_t ldo2 = (uint32_t)a.ldo * 2u;
+    const size_t tile_off = ((size_t)(m0 + wm * 64) * a.ldo + wn * 160) * 2;      // wave-uniform
+    const char* xin = reinterpret_cast<const char*>(a.res) + tile_off;
+    char* yout = reinterpret_cast<char*>(a.out) + tile_off;
+    const int rows_valid = a.Mvalid - (m0 + wm * 64);
+    const uint32_t lane_goff = (uint32_t)rsub * ldo2 + (uint32_t)chunk * 16u;
+    const uint32_t lane_loff = (uint32_t)(rsub * TAIL_NCH + chunk) * 16u;
+    half8 xv[TAIL_NIT];
+    static_for<0, NT>([&](auto ni_) __attribute__((always_inline)) {
+        constexpr int ni = decltype(ni_)::value;
+        static_for<0, 2>([&](auto mi_) __attribute__((always_inline)) {
+            constexpr int mi = decltype(mi_)::value;
+            float v[16];
+            static_for<0, 16>([&](auto r_) __attribute__((always_inline)) {
+                constexpr int r = decltype(r_)::value;
+                v[r] = act_fast<ACT>(acc[mi][ni][r] * gv[ni] + pv[ni]);
+            });
+            conv_stage_tile<NT, mi, ni>(v, wbase, lane);
+        });
+        __builtin_amdgcn_sched_barrier(0);
+        static_for<ni * 5, (ni * 5 + 5 < TAIL_NIT ? ni * 5 + 5 : TAIL_NIT)>([&](auto it_) __attribute__((always_inline)) {
+            constexpr int it = decltype(it_)::value;
+            const int row = rsub + 3 * it;
+            xv[it] = (lane_on && row < 64) ? *reinterpret_cast<const half8*>(xin + (lane_goff + (uint32_t)(3 * it) * ldo2))
+                                           : half8{0, 0, 0, 0, 0, 0, 0, 0};
+        });
+        __builtin_amdgcn_sched_barrier(0);
+    });
+
+    float gs, gss;
+    tail_residual(img, lane_loff, yout, lane_goff, ldo2, rows_valid, xv, lane, gs, gss);
+    if (a.y2 == nullptr) return;
+    tail_gn_stats(gs, gss, lane);
+    tail_y2<ACT>(img, lane_loff, reinterpret_cast<char*>(a.y2) + tile_off, lane_goff, ldo2, rows_valid, gs, gss, gg, bb, lane);
+}

@@ -30,20 +30,6 @@ constexpr int ZS_OFF_D = ZS_OFF_Z + 8192;             // [4][1024] sink of the f
 constexpr int ZS_LDS_MAIN = ZS_OFF_D + 4096;          // 159,744 B
 }
 
-__device__ __forceinline__ void zs_glds16(const void* gsrc, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-// activation pieces: every byte is read once, by one workgroup.  ZS_A_AUX = 2 (nt) asks the caches not to keep them, so that the
-// 1.84 MB of weights every workgroup of an XCD streams stay in that XCD's 4 MB L2 instead of being evicted by the ~10 MB of
-// activations a round of 32 workgroups moves through it (measured: profiles/r04_exp_conv_activation_loads_nt.log)
-#ifndef ZS_A_AUX
-#define ZS_A_AUX 0
-#endif
-__device__ __forceinline__ void zs_glds16_act(const void* gsrc, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, ZS_A_AUX);
-}
 #define ZS_FENCE() asm volatile("" ::: "memory")
 
 #ifdef SW_STAMP
@@ -85,15 +71,15 @@ __global__ __launch_bounds__(512) void conv_zs_kernel(GemmArgs a) {
         const int p = 8 * qq + (lane >> 3);             // 1-KiB piece: rows 8qq..8qq+7 of the 256-row tile
         const int key = (p & 2) | (((p >> 6) & 1) << 2);
         const char* src = in_bytes + ((size_t)(m0 + p) * Cin + (size_t)chunk * 64) * 2 + 16 * ((lane & 7) ^ key);
-        zs_glds16_act(src, A_lds + (chunk & 1) * ZS_A_BYTES + qq * 1024);
+        glds16(src, A_lds + (chunk & 1) * ZS_A_BYTES + qq * 1024);
     };
     auto issue_half = [&](int y) __attribute__((always_inline)) {      // prologue only
         const char* src = w_blk + (size_t)(y >> 1) * w_kt_stride + (size_t)(y & 1) * ZS_WH_BYTES;
         char* dst = W_lds + (y & 3) * ZS_WH_BYTES;
-        zs_glds16(src + wave * 1024, dst + wave * 1024);
-        zs_glds16(src + (8 + wave) * 1024, dst + (8 + wave) * 1024);
-        if (wave < 4) zs_glds16(src + (16 + wave) * 1024, dst + (16 + wave) * 1024);
-        else zs_glds16(w_blk, D_lds + (wave - 4) * 1024);   // filler: keeps 3 pieces per wave and half-tile (vmcnt)
+        glds16(src + wave * 1024, dst + wave * 1024);
+        glds16(src + (8 + wave) * 1024, dst + (8 + wave) * 1024);
+        if (wave < 4) glds16(src + (16 + wave) * 1024, dst + (16 + wave) * 1024);
+        else glds16(w_blk, D_lds + (wave - 4) * 1024);   // filler: keeps 3 pieces per wave and half-tile (vmcnt)
     };
 
     float4v acc[MT][NG];
@@ -136,41 +122,21 @@ __global__ __launch_bounds__(512) void conv_zs_kernel(GemmArgs a) {
     auto issue_next = [&](auto G_) __attribute__((always_inline)) {
         constexpr int G = decltype(G_)::value;
         char* dst = W_lds + w_slot + wave * 1024;
-#ifdef ZS_EMU8          // timing experiment: the DMA volume of an 8-board x 160-channel tile (half the weight pieces, twice the activation
-                        // pieces): group 0 two weight pieces, group 1 its activation piece (+ one weight piece with ZS_EMU8 = 2); results wrong
-        if constexpr (G == 0) { zs_glds16(w_ptr + w_lane, dst); zs_glds16(w_ptr + 8192 + w_lane, dst + 8192); }
-        else if (ZS_EMU8 == 2) zs_glds16(w_ptr + w_lane, dst);
-#else
-        zs_glds16(w_ptr + w_lane, dst);
-        zs_glds16(w_ptr + 8192 + w_lane, dst + 8192);
-#endif
-#if defined(ZS_SKIP_DMA) || defined(ZS_EMU8)      // timing experiments: fewer DMA pieces per wave and half-tile (results wrong)
-        if constexpr (G == 2) {
-#else
+        glds16(w_ptr + w_lane, dst);
+        glds16(w_ptr + 8192 + w_lane, dst + 8192);
         if constexpr (G == 0) {
-#endif
-            zs_glds16(w_ptr + 16384 + w_lane, dst + 16384);
-#if defined(ZS_SKIP_DMA)
-        } else if constexpr (G == 3) {
-#elif defined(ZS_EMU8)
-        } else if constexpr (G == 1) {
-#else
+            glds16(w_ptr + 16384 + w_lane, dst + 16384);
         } else {
-#endif
             const bool have = a_left > 0;
             const uint32_t al = ((8 - a_left) & 2) ? a_lane1 : a_lane0;     // pieces 2, 3, 6, 7 of this wave: odd boards
-            zs_glds16_act((have ? a_ptr : in_bytes) + al, have ? A_lds + a_dst : D_lds + (wave - 4) * 1024);
+            glds16((have ? a_ptr : in_bytes) + al, have ? A_lds + a_dst : D_lds + (wave - 4) * 1024);
             a_ptr += have ? (size_t)32 * Cin * 2 : 0;
             a_dst += have ? 4096 : 0;
             a_left -= have ? 1 : 0;
         }
         const bool more = t_next + 1 < NH;
         const size_t inc = (t_next & 1) ? (w_kt_stride - ZS_WH_BYTES) : (size_t)ZS_WH_BYTES;   // odd -> even: next K-tile
-#ifndef ZS_W_SAME      // timing experiment: every half-tile re-reads the same 20 KB of weights (L1 / L2 hits; results wrong)
         w_ptr += more ? inc : 0;
-#else
-        (void)more; (void)inc;
-#endif
         t_next += 1;
         w_slot = (t_next & 3) * ZS_WH_BYTES;
     };
@@ -227,14 +193,7 @@ __global__ __launch_bounds__(512) void conv_zs_kernel(GemmArgs a) {
                     // half-tile before this one) was read into registers by both wave groups at least a phase ago.
                     ZS_FENCE(); issue_next(G_); ZS_FENCE();
                     // all but this wave's three youngest pieces (the ones just issued) have landed
-#if defined(ZS_EMU8)
-                    if constexpr (G == 0 || ZS_EMU8 == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-                    else asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-#elif defined(ZS_SKIP_DMA)
-                    asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-#else
                     asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-#endif
                     ZS_FENCE();
                     __builtin_amdgcn_s_barrier();
                     ZS_FENCE();
@@ -273,30 +232,9 @@ __global__ __launch_bounds__(512) void conv_zs_kernel(GemmArgs a) {
     if (wp == 0) __builtin_amdgcn_s_barrier();          // matches group 1's extra barrier
     __builtin_amdgcn_s_barrier();                       // every wave's DMA has landed before anyone stages output (tools/ubench/conv_pp.hip)
 
-#ifdef ZS_PREFETCH
-    // L2 prefetch of the first activation chunk of the tile that the XCD's NEXT round of workgroups brings (workgroup ids go to the
-    // XCDs round-robin, so tile blockIdx.x + 256 k lands on this XCD): one 4-byte load per row = one per 128-byte line of the
-    // chunk, issued before the epilogue, retired (by the compiler's own wait) at the very end.
-    float zs_pf = 0.f;
-    {
-        const int nrow = m0 + 256 * ZS_PREFETCH + (tid & 255);
-        if (tid < 256 && nrow < a.Mrows)
-            zs_pf = *reinterpret_cast<const volatile float*>(in_bytes + (size_t)nrow * Cin * 2);
-    }
-#endif
-#ifdef PP_NO_EPILOGUE
-#pragma unroll
-    for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NG; ++ni) asm volatile("" :: "v"(acc[mi][ni]));
-#else
     if constexpr (EPI == 3) zs_tail_epilogue<ACT, false>(acc, a, smem, m0, wp, wn, wave, lane);
     else if constexpr (EPI == 5) zs_tail_epilogue<ACT, true>(acc, a, smem, m0, wp, wn, wave, lane);
     else zs_tile_epilogue<EPI, ACT>(acc, a, smem + wave * 20480, m0, n0, wp, wn, lane);
-#endif
-#ifdef ZS_PREFETCH
-    asm volatile("" :: "v"(zs_pf));
-#endif
 #ifdef SW_STAMP     // timeline of the workgroup (10-ns ticks, wave 0) and where it ran: [blocks][4] behind the main-loop stamps
     if (tid == 0) {
         unsigned long long* o = g_zs_stamp + (size_t)gridDim.x * 4 + (size_t)blockIdx.x * 4;

@@ -20,11 +20,12 @@
 //
 // D  gate * t staged as fp16 in the wave's private image [64 squares][2 boards][80 ch]; the loads of x are issued between
 //    the tile columns into the registers the staged accumulators free
-// E  lane = (16-byte channel chunk of a board, square mod 3): add x, store y, write y back to the image, per-channel sums ->
-//    GroupNorm statistics by shuffles;  F  second pass over the image: y2 = act(y * scale + shift), 16-byte stores.
+// E, F  conv_tail.h: tail_residual (lane = (16-byte channel chunk of a board, square mod 3)), tail_gn_stats (a board has
+//    an even number of chunks, so chunk ^ 1 is in the same board), tail_y2.
 // D-F touch only the wave's own image: no workgroup barrier after C.
 #pragma once
 #include "conv_zs_epilogue.h"
+#include "conv_tail.h"
 
 constexpr int ZS_SE_HMAX = 96;            // squeeze-excite hidden units the fused tail takes (LDS: 60 + 60 pieces)
 constexpr int ZS_SE_WOFF = 8192;          // LDS offset of the weight pieces during the squeeze-excite phase
@@ -32,11 +33,6 @@ constexpr int ZS_SE_WOFF = 8192;          // LDS offset of the weight pieces dur
 // number of 1-KiB pieces of GemmArgs::se_wf for Hd hidden units (net.hip packs them, pack_se_fragments)
 __host__ __device__ inline int zs_se_pieces_w1(int Hd) { return 10 * ((Hd + 15) >> 4); }
 __host__ __device__ inline int zs_se_pieces_w2(int Hd) { return 20 * ((Hd + 31) >> 5); }
-
-__device__ __forceinline__ void zs_tail_glds16(const void* gsrc, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 #ifdef SW_STAMP
 __device__ unsigned long long* g_zs_tail_stamp;    // [blocks][8] realtime stamps of the tail's phases (tools/ubench)
@@ -56,26 +52,14 @@ __device__ __forceinline__ void zs_tail_epilogue(float4v (&acc)[8][5], const Gem
     const bool se = a.se_w1 != nullptr;
     // phase E/F lane mapping and the second output's GroupNorm parameters (fetched now: a late load is an exposed
     // global-memory latency in a kernel with one workgroup per CU)
-    constexpr int NCH = 20;                                      // 16-byte chunks per image row: 2 boards x 10
-    constexpr int NIT = 22;                                      // ceil(64 / 3)
-    const int c20 = lane % NCH, rsub = lane / NCH;
+    const int c20 = lane % TAIL_NCH, rsub = lane / TAIL_NCH;
     const bool lane_on = rsub < 3;
     const int bd = c20 >= 10 ? 1 : 0, ch = c20 - 10 * bd;        // board of the pair, chunk of its 80 channels
     float gg[8], bb[8];
-    if (a.y2 != nullptr) {
-        const int c0 = wn * 80 + ch * 8;
-        const float4 g0 = *reinterpret_cast<const float4*>(a.gn_gamma + c0), g1 = *reinterpret_cast<const float4*>(a.gn_gamma + c0 + 4);
-        const float4 b0 = *reinterpret_cast<const float4*>(a.gn_beta + c0), b1 = *reinterpret_cast<const float4*>(a.gn_beta + c0 + 4);
-        gg[0] = g0.x; gg[1] = g0.y; gg[2] = g0.z; gg[3] = g0.w; gg[4] = g1.x; gg[5] = g1.y; gg[6] = g1.z; gg[7] = g1.w;
-        bb[0] = b0.x; bb[1] = b0.y; bb[2] = b0.z; bb[3] = b0.w; bb[4] = b1.x; bb[5] = b1.y; bb[6] = b1.z; bb[7] = b1.w;
-    }
+    if (a.y2 != nullptr) tail_gn_params(a, wn * 80 + ch * 8, gg, bb);
     float gv[NG];
     ZS_TAIL_STAMP(0);
-#ifdef TAIL_NO_SE
-    if (false) {
-#else
     if (se && !PRE) {
-#endif
         const int Hd = a.se_hidden;
         const int NT1 = (Hd + 15) >> 4, KS2 = (Hd + 31) >> 5;
         const int n1 = 10 * NT1, npieces = n1 + 20 * KS2;
@@ -83,7 +67,7 @@ __device__ __forceinline__ void zs_tail_epilogue(float4v (&acc)[8][5], const Gem
         _Float16* hidA = reinterpret_cast<_Float16*>(smem + 5120);     // [2][4][128]  2048 B, zero beyond the hidden units
         const char* wf = smem + ZS_SE_WOFF;
         for (int p = wave; p < npieces; p += 8)
-            zs_tail_glds16(reinterpret_cast<const char*>(a.se_wf) + (size_t)p * 1024 + lane * 16, smem + ZS_SE_WOFF + p * 1024);
+            glds16(reinterpret_cast<const char*>(a.se_wf) + (size_t)p * 1024 + lane * 16, smem + ZS_SE_WOFF + p * 1024);
         if (tid < 128) reinterpret_cast<uint4*>(hidA)[tid] = make_uint4(0, 0, 0, 0);
         const int j1 = 16 * wave + c15;
         const float b1v = (wave < NT1 && j1 < Hd) ? a.se_b1[j1] : 0.f;
@@ -191,8 +175,8 @@ __device__ __forceinline__ void zs_tail_epilogue(float4v (&acc)[8][5], const Gem
     char* yout = reinterpret_cast<char*>(a.out) + tile_off;
     const int rows_valid = a.Mvalid - (m0 + wp * 128 + bd * 64);                  // of this lane's board
     const uint32_t lane_goff = (uint32_t)(bd * 64 + rsub) * ldo2 + (uint32_t)ch * 16u;
-    const uint32_t lane_loff = (uint32_t)(rsub * NCH + c20) * 16u;
-    half8 xv[NIT];
+    const uint32_t lane_loff = (uint32_t)(rsub * TAIL_NCH + c20) * 16u;
+    half8 xv[TAIL_NIT];
     static_for<0, NG>([&](auto ni_) __attribute__((always_inline)) {
         constexpr int ni = decltype(ni_)::value;
         static_for<0, MT>([&](auto mi_) __attribute__((always_inline)) {
@@ -210,81 +194,18 @@ __device__ __forceinline__ void zs_tail_epilogue(float4v (&acc)[8][5], const Gem
         static_for<(ni < 2 ? ni * 5 : 10 + (ni - 2) * 4), (ni < 2 ? ni * 5 + 5 : 10 + (ni - 1) * 4)>([&](auto it_) __attribute__((always_inline)) {
             constexpr int it = decltype(it_)::value;
             const int row = rsub + 3 * it;
-#ifdef TAIL_NO_XLOAD
-            xv[it] = half8{0, 0, 0, 0, 0, 0, 0, 0};
-#else
             xv[it] = (lane_on && row < 64) ? *reinterpret_cast<const half8*>(xin + (lane_goff + (uint32_t)(3 * it) * ldo2))
                                            : half8{0, 0, 0, 0, 0, 0, 0, 0};
-#endif
         });
         __builtin_amdgcn_sched_barrier(0);
     });
 
     ZS_TAIL_STAMP(2);
-    // E: y = x + image; lane = (chunk of 8 channels of a board, square mod 3), squares rsub, rsub+3, ...; lanes 60..63 idle.
-    // The sum of two fp16 numbers rounded to fp16 is what the fp32 add + conversion gives, so y is computed with packed
-    // fp16 adds (4 instructions per 8 channels); the GroupNorm sums (this lane's 8 channels x its squares) use the
-    // 2-element fp16 dot product with fp32 accumulation, on the rounded y (the tensor that is actually stored).
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    const h2 ones = {(_Float16)1.f, (_Float16)1.f};
-    float gs = 0.f, gss = 0.f;
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int row = rsub + 3 * it;
-        if (lane_on && row < 64) {
-            half8* ip = reinterpret_cast<half8*>(img + lane_loff + (uint32_t)(3 * it * NCH) * 16u);
-            const half8 yv = *ip + xv[it];
-            static_for<0, 4>([&](auto i_) __attribute__((always_inline)) {
-                constexpr int i = decltype(i_)::value;
-                const h2 p = {yv[2 * i], yv[2 * i + 1]};
-                gs = __builtin_amdgcn_fdot2(p, ones, gs, false);
-                gss = __builtin_amdgcn_fdot2(p, p, gss, false);
-            });
-            *ip = yv;
-            if (row < rows_valid) *reinterpret_cast<half8*>(yout + (lane_goff + (uint32_t)(3 * it) * ldo2)) = yv;
-        }
-    }
+    float gs, gss;
+    tail_residual(img, lane_loff, yout, lane_goff, ldo2, rows_valid, xv, lane, gs, gss);
     ZS_TAIL_STAMP(3);
-#ifdef TAIL_NO_Y2
-    return;
-#endif
     if (a.y2 == nullptr) return;
-
-    // GroupNorm statistics of y: over the 3 square classes (lanes c20, c20+20, c20+40), then over the group's 16
-    // channels = this lane's 8 + the neighbour chunk's 8 (c20 ^ 1: same board, since a board has an even number of chunks)
-    {
-        const float s1 = __shfl(gs, c20 + NCH), s2 = __shfl(gs, c20 + 2 * NCH);
-        const float q1 = __shfl(gss, c20 + NCH), q2 = __shfl(gss, c20 + 2 * NCH);
-        gs = __shfl(gs, c20) + s1 + s2;                          // every lane: totals of its chunk (same order everywhere)
-        gss = __shfl(gss, c20) + q1 + q2;
-        const float so = __shfl_xor(gs, 1), qo = __shfl_xor(gss, 1);      // partner chunk (c20 ^ 1 is lane ^ 1 for lanes < 60)
-        const float lo_s = (c20 & 1) ? so : gs, hi_s = (c20 & 1) ? gs : so;
-        const float lo_q = (c20 & 1) ? qo : gss, hi_q = (c20 & 1) ? gss : qo;
-        gs = lo_s + hi_s; gss = lo_q + hi_q;
-    }
-    const float mean = gs * (1.f / 1024.f);
-    float var = gss * (1.f / 1024.f) - mean * mean;
-    var = var > 0.f ? var : 0.f;
-    const float rstd = rsqrtf(var + 1e-5f);
-    float scl[8], shl[8];
-    static_for<0, 8>([&](auto i_) __attribute__((always_inline)) {
-        constexpr int i = decltype(i_)::value;
-        scl[i] = gg[i] * rstd; shl[i] = bb[i] - mean * scl[i];
-    });
-    // F: y2 = act(GroupNorm(y)) from the image
-    char* y2out = reinterpret_cast<char*>(a.y2) + tile_off;
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int row = rsub + 3 * it;
-        if (lane_on && row < 64 && row < rows_valid) {
-            const half8 yv = *reinterpret_cast<const half8*>(img + lane_loff + (uint32_t)(3 * it * NCH) * 16u);
-            half8 ov;
-            static_for<0, 8>([&](auto i_) __attribute__((always_inline)) {
-                constexpr int i = decltype(i_)::value;
-                ov[i] = (_Float16)act_fast<ACT>((float)yv[i] * scl[i] + shl[i]);
-            });
-            *reinterpret_cast<half8*>(y2out + (lane_goff + (uint32_t)(3 * it) * ldo2)) = ov;
-        }
-    }
+    tail_gn_stats(gs, gss, lane);
+    tail_y2<ACT>(img, lane_loff, reinterpret_cast<char*>(a.y2) + tile_off, lane_goff, ldo2, rows_valid, gs, gss, gg, bb, lane);
     ZS_TAIL_STAMP(4);
 }

@@ -34,6 +34,12 @@ struct DeviceOnce {
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float float16v __attribute__((ext_vector_type(16)));
 
+// One LDS-DMA piece: 16 bytes per lane from `gsrc` (per lane) to LDS at the wave-uniform `lds_wave_base` + lane * 16 (hardware).
+__device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
+                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+}
+
 // Compile-time loop: the body sees its index as an integral_constant, so every accumulator index is a
 // constant in the AST (a runtime- or late-unrolled index keeps the MFMA accumulators in scratch memory).
 template <int I, int N, typename F>

@@ -23,7 +23,7 @@ struct GemmArgs {
     int epi_act;
     int out_f32;
     float out_scale;
-    int ksplit;              // conv_big_kernel<1>: > 1 = split K over gridDim.y, workgroup z writes its fp32 partial tile to
+    int ksplit;              // conv_big_kernel: > 1 = split K over gridDim.y, workgroup z writes its fp32 partial tile to
                              // out + z * Mrows * ldo floats (out_f32 = 1, no bias / act); reduced by launch_splitk_reduce
     int w_pp;                // 3x3 big tile: w is in the half-tile layout of conv_zs_kernel / conv_pp16_kernel (pack_gemm)
     // residual-block tail fused into the epilogue (conv_tail.h), when res != null: out = res + gate * conv,

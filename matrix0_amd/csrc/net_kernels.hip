@@ -8,15 +8,14 @@
 // wave-local.
 //
 // Kernels:
-//   conv_big_kernel<TAPS>  the hot kernel: implicit-GEMM 3x3 / 1x1 conv (and wide FC layers) on
-//       v_mfma_f32_32x32x16_f16, fp32 accumulate.  WG = 8 waves, tile = 256 rows (4 boards) x 320
-//       output channels, K stepped as (64-channel chunk, tap).  Both operands go global -> LDS by
-//       global_load_lds (16 B/lane, no VGPR staging): the 64-channel slice of the 4 boards once per
-//       chunk (double-buffered, reused by all 9 taps through shifted reads; out-of-board taps read a
-//       shared zero pixel) and one 320x64 weight stage per step (double-buffered, pre-swizzled on the
-//       host).  128-byte LDS rows, 16-byte chunk index XOR (row>>1)&7 -> conflict-free ds_read_b128.
-//       Epilogue: bias/act/mul/scale + per-(board,channel) sums, or a fused GroupNorm16+activation
-//       over the wave's own board (a wave holds all 64 rows of one board x 10 whole groups).
+//   conv_big_kernel (conv_big.hip)  the 1x1 big-tile GEMM: the piece-square-table conv with the PRE block
+//       tail (conv_tail.h), the split-K FCs and the unfused qkv / proj path, on v_mfma_f32_32x32x16_f16, fp32
+//       accumulate.  WG = 8 waves, tile = 256 rows (4 boards) x 320 output channels, K stepped in 64-channel
+//       chunks.  Both operands go global -> LDS by global_load_lds (16 B/lane, no VGPR staging), double-
+//       buffered: the 64-channel slice of the 4 boards and one 320x64 weight stage per chunk (pre-swizzled on
+//       the host).  128-byte LDS rows, 16-byte chunk index XOR (row>>1)&7 -> conflict-free ds_read_b128.
+//       Epilogue: bias/act/mul/scale + per-(board,channel) sums, per element, or the PRE block tail.
+//       (The 3x3 tower convs: conv_zs_kernel / conv_pp16_kernel.)
 //   conv_gemm_kernel<TAPS,1,1,32>  generic small-tile variant (any N%32==0, Cin%32==0): stem, heads, FCs.
 //   ew_board_kernel   per-board elementwise glue: GN+act, SE gate, residual add,
 //       positional encoding, LayerNorm over C, output statistics.

@@ -17,7 +17,6 @@
 //      the last reads of y-1 (waves 4-7, L(y-1,1)) are retired by the lgkmcnt wait of C(y-1,1), before barrier 4y.
 #include "../../matrix0_amd/csrc/kernel_common.h"
 #include "../../matrix0_amd/csrc/conv_epilogue.h"
-#include "../../matrix0_amd/csrc/conv_tail.h"
 
 __device__ __forceinline__ void pp_glds16(const void* gsrc, void* lds_wave_base) {
     // LDS destination = wave-uniform base + lane*16 (hardware); the global source is per lane
@@ -413,9 +412,7 @@ __global__ __launch_bounds__(512) void conv_pp_kernel(GemmArgs a) {
     asm volatile("" :: "v"(acc[1][0]), "v"(acc[1][1]), "v"(acc[1][2]), "v"(acc[1][3]), "v"(acc[1][4]));
 #else
     // every wave is past its last LDS read and DMA wait here (the barrier just above / the loop's final one)
-    if constexpr (EPI == 3) conv_tail_epilogue<ACT, false>(acc, a, smem, m0, wm, wn, wave, lane);
-    else if constexpr (EPI == 5) conv_tail_epilogue<ACT, true>(acc, a, smem, m0, wm, wn, wave, lane);
-    else conv_tile_epilogue<EPI, ACT, NT>(acc, a, smem + wave * (NT * 64 * 64), m0, n0, wm, wn, lane);
+    conv_tile_epilogue<EPI, ACT, NT>(acc, a, smem + wave * (NT * 64 * 64), m0, n0, wm, wn, lane);
 #endif
 }
 
@@ -439,20 +436,8 @@ hipError_t launch_conv_pp(const GemmArgs& a, hipStream_t st) {
     if (a.Cin % 64 != 0 || a.Npad % 320 != 0 || a.Mrows % 256 != 0) return hipErrorInvalidValue;
     if (a.mul != nullptr || a.out_f32 != 0) return hipErrorInvalidValue;      // 3x3 convs never use these
     if ((size_t)a.Mrows * a.ldo * 2 >= ((size_t)1 << 32)) return hipErrorInvalidValue;   // 32-bit store offsets
-    if (a.res != nullptr) {                     // conv2 of a block with the block's tail fused (conv_tail.h)
-        if (a.N != 320 || a.Npad != 320 || a.ldo != 320 || a.bias != nullptr || a.out_stats != nullptr) return hipErrorInvalidValue;
-        if (a.y2 != nullptr && a.gn_gamma == nullptr) return hipErrorInvalidValue;
-        if (a.se_w1 != nullptr && (a.se_hidden < 4 || a.se_hidden > 128 || a.se_hidden % 4 != 0)) return hipErrorInvalidValue;
-        if (a.pre_gamma != nullptr) {               // x += act(norm(conv(x))) (chess-feature conv) + next GroupNorm
-            if (a.se_w1 != nullptr) return hipErrorInvalidValue;
-            if (a.epi_act == ACT_SILU) return launch_conv_pp_e<5, ACT_SILU>(a, st);
-            if (a.epi_act == ACT_RELU) return launch_conv_pp_e<5, ACT_RELU>(a, st);
-            return hipErrorInvalidValue;
-        }
-        if (a.epi_act == ACT_SILU) return launch_conv_pp_e<3, ACT_SILU>(a, st);
-        if (a.epi_act == ACT_RELU) return launch_conv_pp_e<3, ACT_RELU>(a, st);
-        return hipErrorInvalidValue;
-    }
+    // the fused block tail of this layout went with conv_tail.h's squeeze-excite form: conv_pp16 / conv_zs have their own
+    if (a.res != nullptr) return hipErrorInvalidValue;
     if (a.gn_gamma != nullptr) {                // conv1 of a block: GroupNorm + the network activation
         if (a.epi_act == ACT_SILU) return launch_conv_pp_e<1, ACT_SILU>(a, st);
         if (a.epi_act == ACT_RELU) return launch_conv_pp_e<1, ACT_RELU>(a, st);

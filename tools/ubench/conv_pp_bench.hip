@@ -59,6 +59,9 @@ int main(int argc, char** argv) {
         (void)dtb;
     }
 #endif
+#if defined(BENCH_TAIL) && !defined(BENCH_ZS) && !defined(BENCH_P16)
+#error "BENCH_TAIL needs BENCH_ZS or BENCH_P16 (conv_pp_kernel has no fused tail)"
+#endif
 #ifdef BENCH_TAIL   // conv2 with the residual-block tail fused (EPI 3): x, squeeze-excite weights, next GroupNorm, y2
     {
         const int Hd = 80;
