@@ -199,7 +199,7 @@ static hipError_t launch_conv_big_e(const GemmArgs& a, hipStream_t st) {
 }
 
 hipError_t launch_conv_big(const GemmArgs& a, int taps, hipStream_t st) {
-    // 1x1 convs whose N is a multiple of 320 (qkv, proj).  3x3: conv_zs_kernel / conv_pp16_kernel.
+    // 1x1 convs whose N is a multiple of 320 (qkv, proj).  3x3: conv_zs_kernel.
     if (taps != 1) return hipErrorInvalidValue;
     if (a.res != nullptr) {   // x + act(GroupNorm16(conv1x1(x))) in the epilogue (piece-square-table conv of the chess features)
         if (a.pre_gamma == nullptr || a.se_w1 != nullptr || a.N != 320 || a.Npad != 320 || a.ldo != 320 || a.bias != nullptr ||

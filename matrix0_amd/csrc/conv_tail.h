@@ -7,9 +7,9 @@
 //   y2     = act(GroupNorm16(y; next block's bn1))                    the next conv1's operand     -> a.y2 (optional)
 // i.e. what conv2's plain epilogue + se_gate_kernel + ew_board_kernel did with three launches and two more trips of
 // the tensor through HBM.  Everything a board needs is inside the workgroup, so the only new global traffic is the
-// read of x.  Each accumulator layout has its own tail: conv_tail_epilogue below (conv_big_kernel, PRE only),
-// conv_tail16.h (conv_pp16_kernel) and conv_zs_tail.h (conv_zs_kernel).  Each reads its accumulators (channel means,
-// squeeze-excite gate, PRE statistics) and stages gate * t as fp16 in the wave's private LDS image, 64 rows of 20
+// read of x.  Each accumulator layout has its own tail: conv_tail_epilogue below (conv_big_kernel, PRE only) and
+// conv_zs_tail.h (conv_zs_kernel).  Each reads its accumulators (channel means, squeeze-excite gate, PRE statistics)
+// and stages gate * t as fp16 in the wave's private LDS image, 64 rows of 20
 // 16-byte chunks, issuing the loads of x between the tile columns.  The rest works on that image and is shared:
 //   tail_gn_params  the second GroupNorm's parameters of the lane's 8 channels (fetched first: a late load is an
 //                   exposed global-memory latency in a kernel with one workgroup per CU)

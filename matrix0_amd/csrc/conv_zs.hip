@@ -1,14 +1,21 @@
-// conv_zs_kernel: the 3x3 320->320 implicit-GEMM conv of the tower with the zero padding SKIPPED.
+// conv_zs_kernel: the 3x3 320->320 implicit-GEMM conv of the tower with the zero padding SKIPPED (DESIGN.md section 5).
 //
-// conv_pp16_kernel (read its header and tools/ubench/conv_pp.hip's: same workgroup tile of 4 boards x 320 channels, LDS images, DMA ring,
-// ping-pong groups and barrier protocol) gives a wave one board x 160 channels, M-tile = 16 consecutive squares.  A 3x3 conv
-// on an 8x8 board multiplies 92 of its 576 (square, tap) pairs by the zero padding; the main loop is POWER-bound (DESIGN.md
-// section 5), so those MFMAs cost wall time.  Here a wave owns TWO boards x 80 channels and M-tile mi = board row y = mi of
-// both boards (lanes c15 < 8: board a, squares 8 mi .. 8 mi + 7; c15 >= 8: board b).  For the three taps with dy = -1 the
-// operand of tile 0 is the padding row above both boards, for dy = +1 that of tile 7 the row below: those tiles' MFMAs and
-// fragment reads are simply not issued -- 6 of the 72 (tap, tile) pairs, 8.3 % of the matrix work, results bit-identical
-// (the skipped products are exact zeros).  Only the left / right padding column (one lane in eight) is still read from a zero
-// region.  Per half-tile (32 k) a wave reads 8 (7) activation fragments and 5 weight fragments and issues 40 (35) MFMAs.
+// Workgroup: 8 waves, tile = 4 boards (256 rows) x 320 output channels, K walked as (64-channel chunk, tap) in half-tiles of 32 k.
+// Wave (wp = wave >> 2, wn = wave & 3) owns the board PAIR wp x channels 80 wn .. 80 wn + 79: 8 x 5 accumulator tiles of
+// v_mfma_f32_16x16x32_f16.  Why that shape: the main loop is POWER-bound, not issue-bound.  In-kernel stamps (tools/ubench,
+// -DSW_STAMP, random operands, round 2, before the padding skip) showed this loop on 32x32x16 at 87.7 % of the MFMA issue rate but
+// at 1.52-1.57 GHz; on 16x16x32 it spent more cycles (82 %) at 1.75-1.82 GHz and finished 5.6-7 % sooner: the chip holds a higher
+// clock on this shape.
+//
+// M-tile mi = board row mi of both boards of the pair.  A 3x3 conv on an 8x8 board multiplies 92 of its 576 (square, tap)
+// pairs by the zero padding; for the three taps with dy = -1 the operand of tile 0 is the padding row above both boards, for
+// dy = +1 that of tile 7 the row below: those tiles' MFMAs and fragment reads are simply not issued -- 6 of the 72 (tap, tile)
+// pairs, 8.3 % of the matrix work, results bit-identical (the skipped products are exact zeros).  Only the left / right padding
+// column (one lane in eight) is still read from a zero region.  Per half-tile a wave reads 8 (7) activation fragments and 5 weight
+// fragments and issues 40 (35) MFMAs.
+//
+// Fragments: lane l = (c15 = l & 15, q = l >> 4) holds k 8q .. 8q + 7 of the half-tile.  Activation fragment of tile mi: board
+// c15 >> 3 of the pair, square 8 mi + (c15 & 7) shifted by the tap; weight fragment ni: output channel 80 wn + 16 ni + c15.
 //
 // LDS activation image: [256 rows = board * 64 + square][64 channels] fp16, 128-byte rows, 16-byte chunk index XOR
 // key(row) = (column & 2) | (board parity << 2).  A ds_read_b128 is served in the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19,
@@ -17,6 +24,23 @@
 // three column shifts of a tap row (searched exhaustively; round 2's key ((column >> 1) & 3) was built for lanes 0-15 as one group
 // and was 2-way conflicted for dx = -1 / +1: 31 % of the main loop's LDS cycles).  key does not change with the board row, so
 // the 8 tiles of a tap are ONE base address plus immediate offsets mi * 1024.
+// LDS weight half-tile: [320 channels][32 k] fp16, 64-byte rows, 16-byte chunk index XOR ((4 - (row >> 2)) & 3) (pack_gemm in
+// net.hip): conflict-free for the weight fragment reads.
+//
+// DMA ring and barriers.  Half-tile y (NH = 18 Cin / 64 of them) lives in weight slot y & 3 of a four-slot ring; chunk c's
+// activations in buffer c & 1.  Everything arrives by LDS-DMA (glds16) in 1-KiB pieces, wave-uniform addresses advanced
+// incrementally.  In every half-tile every wave issues exactly THREE pieces of the half-tile three ahead: weight pieces wave and
+// 8 + wave, then group 0 (waves 0-3) piece 16 + wave and group 1 (waves 4-7) one piece of the next chunk's activations (eight per
+// wave and chunk) or, once those are out, a filler into the D region (past the last half-tile the weight pieces re-fetch it).
+// The ring slot it fills held half-tile y - 1, which both groups have read.  Equal counts make one counted wait exact:
+// `s_waitcnt vmcnt(3)` right after the issue leaves only those three pieces in flight, so the wave's pieces of half-tiles up to
+// y + 2 have landed; a group reads half-tile y + 1 only after a barrier that the other group reaches after its own wait in
+// half-tile y.  The prologue issues chunk 0 and half-tiles 0 .. 2 and waits with vmcnt(6).  Group 1 runs one barrier behind
+// group 0 (an extra barrier after the prologue, matched by group 0 after the loop), so the two barriers of a half-tile (after
+// the load section, after the MFMAs) alternate the groups: on every SIMD one wave issues its MFMAs while its partner (wave ^ 4)
+// reads fragments and issues its DMA.  After the loop every wave drains its DMA (vmcnt(0)) and a last barrier frees the LDS for
+// the epilogue's staging.
+// (History: the 32x32x16 conv_pp_kernel of round 1 with the same ring is tools/ubench/conv_pp.hip.)
 #include "kernel_common.h"
 #include "conv_zs_epilogue.h"
 #include "conv_zs_tail.h"
@@ -108,7 +132,7 @@ __global__ __launch_bounds__(512) void conv_zs_kernel(GemmArgs a) {
     __builtin_amdgcn_s_barrier();
     if (wp == 1) __builtin_amdgcn_s_barrier();          // group 1 runs one barrier behind group 0
 
-    // ---- steady-state DMA (wave-uniform state, advanced incrementally; see tools/ubench/conv_pp.hip) ----
+    // ---- steady-state DMA (wave-uniform state, advanced incrementally; the ring is described in the header) ----
     const uint32_t w_lane = (uint32_t)lane * 16u;
     // activation piece qq = 4 xi + wave - 4 (xi = 0..7): rows 32 xi + 8 (wave - 4) + (lane >> 3); key = ((lane >> 3) & 2) | (xi & 2) << 1
     const uint32_t a_lane0 = (uint32_t)(lane >> 3) * (uint32_t)Cin * 2u + 16u * (uint32_t)((lane & 7) ^ ((lane >> 3) & 2));
@@ -230,7 +254,7 @@ __global__ __launch_bounds__(512) void conv_zs_kernel(GemmArgs a) {
 #endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // this wave's tail refetches / fillers have landed
     if (wp == 0) __builtin_amdgcn_s_barrier();          // matches group 1's extra barrier
-    __builtin_amdgcn_s_barrier();                       // every wave's DMA has landed before anyone stages output (tools/ubench/conv_pp.hip)
+    __builtin_amdgcn_s_barrier();                       // every wave's DMA has landed before anyone stages output (header)
 
     if constexpr (EPI == 3) zs_tail_epilogue<ACT, false>(acc, a, smem, m0, wp, wn, wave, lane);
     else if constexpr (EPI == 5) zs_tail_epilogue<ACT, true>(acc, a, smem, m0, wp, wn, wave, lane);
@@ -259,21 +283,15 @@ static hipError_t launch_conv_zs_e(const GemmArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-// true: launch_conv_zs takes these arguments (the dispatcher falls back to conv_pp16_kernel otherwise)
-bool conv_zs_supports(const GemmArgs& a) {
-    if (a.res != nullptr && a.se_w1 != nullptr && (a.se_wf == nullptr || a.se_hidden > ZS_SE_HMAX)) return false;   // fragment-order weights
-    return true;
-}
-
-// 3x3 only; a.w must be in the half-tile layout (GemmArgs::w_pp).  Same contract as launch_conv_pp16.
+// 3x3 only; a.w must be in the half-tile layout (GemmArgs::w_pp).
 hipError_t launch_conv_zs(const GemmArgs& a, hipStream_t st) {
     if (a.Cin % 64 != 0 || a.Npad % 320 != 0 || a.Mrows % 256 != 0) return hipErrorInvalidValue;
-    if (a.mul != nullptr || a.out_f32 != 0 || !conv_zs_supports(a)) return hipErrorInvalidValue;
+    if (a.mul != nullptr || a.out_f32 != 0) return hipErrorInvalidValue;      // 3x3 convs never use these
     if ((size_t)a.Mrows * a.ldo * 2 >= ((size_t)1 << 32)) return hipErrorInvalidValue;   // 32-bit store offsets
     if (a.res != nullptr) {                     // conv2 of a block with the block's tail fused (conv_zs_tail.h)
         if (a.N != 320 || a.Npad != 320 || a.ldo != 320 || a.bias != nullptr || a.out_stats != nullptr) return hipErrorInvalidValue;
         if (a.y2 != nullptr && a.gn_gamma == nullptr) return hipErrorInvalidValue;
-        if (a.se_w1 != nullptr && (a.se_hidden < 1 || a.se_hidden > ZS_SE_HMAX)) return hipErrorInvalidValue;
+        if (a.se_w1 != nullptr && (a.se_wf == nullptr || a.se_hidden < 1 || a.se_hidden > TAIL_SE_HMAX)) return hipErrorInvalidValue;
         if (a.pre_gamma != nullptr) {               // x += act(norm(conv(x))) (chess-feature conv) + next GroupNorm
             if (a.se_w1 != nullptr) return hipErrorInvalidValue;
             if (a.epi_act == ACT_SILU) return launch_conv_zs_e<5, ACT_SILU>(a, st);

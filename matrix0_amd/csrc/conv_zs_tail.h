@@ -16,7 +16,7 @@
 //   C  FC2 per wave for its own 80 channels: rows = boards ordered so that accumulator row 4q + r is board q >> 1 of the
 //      wave's pair -- the gate of (board, channel) comes out in exactly the lane that scales that accumulator column.
 // Three workgroup barriers.  The weight pieces are one stream of 1-KiB DMA pieces (se_wf): 10 x ceil(Hd/16) of W1, then
-// 20 x ceil(Hd/32) of W2.
+// 20 x ceil(Hd/32) of W2, at most 60 + 60 for Hd <= TAIL_SE_HMAX (net_kernels.h).
 //
 // D  gate * t staged as fp16 in the wave's private image [64 squares][2 boards][80 ch]; the loads of x are issued between
 //    the tile columns into the registers the staged accumulators free
@@ -27,7 +27,6 @@
 #include "conv_zs_epilogue.h"
 #include "conv_tail.h"
 
-constexpr int ZS_SE_HMAX = 96;            // squeeze-excite hidden units the fused tail takes (LDS: 60 + 60 pieces)
 constexpr int ZS_SE_WOFF = 8192;          // LDS offset of the weight pieces during the squeeze-excite phase
 
 // number of 1-KiB pieces of GemmArgs::se_wf for Hd hidden units (net.hip packs them, pack_se_fragments)

@@ -25,7 +25,7 @@ struct DeviceOnce {
     }
 };
 
-// RULE for every kernel that stages through LDS-DMA (__builtin_amdgcn_global_load_lds: conv_zs / conv_pp16 / attn_block /
+// RULE for every kernel that stages through LDS-DMA (__builtin_amdgcn_global_load_lds: conv_zs / attn_block /
 // conv_big): a COUNTED `s_waitcnt vmcnt(N)` (N > 0) may only be used while nothing but LDS-DMA operations of this wave is
 // outstanding.  vmcnt counts loads into registers, stores and LDS-DMA together, but a later LDS-DMA can retire before an
 // earlier load into registers (measured on gfx950, round 3: `vmcnt(1)` meant as "the bias load, not the DMA after it" let

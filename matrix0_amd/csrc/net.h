@@ -20,7 +20,7 @@ struct PackedGemm {
     _Float16* w = nullptr;   // [taps][Cin/KC][N][KC]
     float* bias = nullptr;   // [N] or null
     int taps = 1, Cin = 0, N = 0;
-    bool pp = false;         // 3x3 big tile in the half-tile layout of conv_zs_kernel / conv_pp16_kernel [chunk*9+tap][N/320][k half][320][32]
+    bool pp = false;         // 3x3 big tile in the half-tile layout of conv_zs_kernel [chunk*9+tap][N/320][k half][320][32]
 };
 
 struct NormParams {
@@ -32,7 +32,6 @@ struct ResBlockW {
     PackedGemm conv1, conv2;
     NormParams bn1, bn2;
     float *se_w1 = nullptr, *se_b1 = nullptr, *se_w2 = nullptr, *se_b2 = nullptr;
-    _Float16 *se_w1h = nullptr, *se_w2h = nullptr;   // fp16 copies for the fused tail (conv_tail16.h)
     void* se_wf = nullptr;                           // fp16 MFMA fragment pieces for conv_zs_kernel's tail (conv_zs_tail.h)
     int se_hidden = 0;
 };
@@ -104,7 +103,7 @@ private:
     m0_net_cfg cfg_;
     int device_;
     hipStream_t stream_ = nullptr;
-    struct Switches { bool fuse_tail = true, fuse_attn = true, splitk = true, conv_zs = true, fuse_small = true; } sw_;   // read once (constructor)
+    struct Switches { bool fuse_tail = true, fuse_attn = true, splitk = true, fuse_small = true; } sw_;   // read once (constructor)
     bool finalized_ = false;
     size_t nparams_ = 0;
     std::map<std::string, HostTensor> sd_;

@@ -41,7 +41,6 @@ Net::Net(const m0_net_cfg& cfg, int device, hipStream_t stream) : cfg_(cfg), dev
     sw_.fuse_small = !off("M0_FUSE_SMALL");   // =0: stem / head convs write raw tensors + statistics for ew_board passes (rounds 1-3)
     sw_.fuse_attn = !off("M0_FUSE_ATTN");     // =0: qkv GEMM + attn_core + proj GEMM + ew_board as separate kernels
     sw_.splitk = !off("M0_SPLITK");           // =0: value_fc1 never splits K
-    sw_.conv_zs = !off("M0_CONV_ZS");         // =0: conv_pp16_kernel instead of conv_zs_kernel
     C_ = cfg.channels;
     Cp_ = (C_ > 256 && C_ < 320) ? 320 : C_;
     Cs_ = ceil_to(std::max(16, C_ / 2), 32);
@@ -130,7 +129,7 @@ int Net::pack_gemm(PackedGemm& g, const std::string& wkey, const std::string& bk
     nparams_ += expect;
     const int KC = conv_gemm_kc(Cin_pad, N_pad);
     const int nchunk = Cin_pad / KC;
-    const bool pp = KC == 64 && taps == 9;       // 3x3 big tile: the half-tile layout of conv_zs_kernel / conv_pp16_kernel
+    const bool pp = KC == 64 && taps == 9;       // 3x3 big tile: the half-tile layout of conv_zs_kernel
     const int nblk = N_pad / 320;
     std::vector<_Float16> p((size_t)taps * Cin_pad * N_pad, (_Float16)0.f);
     for (int nr = 0; nr < N_real; ++nr)
@@ -148,8 +147,8 @@ int Net::pack_gemm(PackedGemm& g, const std::string& wkey, const std::string& bk
                     kk = sq * k_perm_ch + c;
                 }
                 int chunk = kk / KC, kc = kk % KC;
-                if (pp) {       // conv_pp16 / conv_pp kernels: half-K-tiles of 320 x 32 k, 64-byte rows, 16-byte chunk index
-                                // ^ ((4 - (row >> 2)) & 3): conflict-free for the 16x16x32 and the 32x32x16 fragment reads
+                if (pp) {       // conv_zs_kernel: half-K-tiles of 320 x 32 k, 64-byte rows, 16-byte chunk index
+                                // ^ ((4 - (row >> 2)) & 3): conflict-free for its 16x16x32 fragment reads
                     const int kt = chunk * 9 + t, by = n / 320, nl = n % 320, h = kc >> 5, k32 = kc & 31;
                     const int kx = (((k32 >> 3) ^ ((4 - ((nl >> 2) & 3)) & 3)) << 3) | (k32 & 7);
                     p[((((size_t)kt * nblk + by) * 2 + h) * 320 + nl) * 32 + kx] = (_Float16)v;
@@ -304,17 +303,7 @@ int Net::finalize(std::string& err) {
                 for (int c = 0; c < C; ++c)
                     for (int j = 0; j < hd; ++j) w2t[(size_t)j * P + c] = w2->data[(size_t)c * hd + j];
                 r.se_w2 = upload_f32(w2t);
-                {   // fp16 copies for the fused tail
-                    std::vector<_Float16> h1(w1t.size()), h2(w2t.size());
-                    for (size_t i = 0; i < w1t.size(); ++i) h1[i] = (_Float16)w1t[i];
-                    for (size_t i = 0; i < w2t.size(); ++i) h2[i] = (_Float16)w2t[i];
-                    r.se_w1h = (_Float16*)dalloc(h1.size() * 2, false);
-                    r.se_w2h = (_Float16*)dalloc(h2.size() * 2, false);
-                    if (!r.se_w1h || !r.se_w2h) { err = "hipMalloc failed"; return M0_ERR_HIP; }
-                    (void)hipMemcpy(r.se_w1h, h1.data(), h1.size() * 2, hipMemcpyHostToDevice);
-                    (void)hipMemcpy(r.se_w2h, h2.data(), h2.size() * 2, hipMemcpyHostToDevice);
-                }
-                if (P == 320 && hd <= 96) {
+                if (P == 320 && hd <= TAIL_SE_HMAX) {
                     // conv_zs_kernel's tail runs the two FCs on the matrix cores: B-fragment pieces of v_mfma_f32_16x16x32_f16,
                     // lane (c15 = lane & 15, q = lane >> 4) holds column c15, k = 8q..8q+7 of its tile (conv_zs_tail.h):
                     //   W1 piece (nt, ks):   W1[channel 32 ks + 8 q + e][hidden 16 nt + c15]     nt < ceil(hd/16), ks < 10
@@ -534,7 +523,6 @@ hipError_t Net::run_gemm(const PackedGemm& g, const _Float16* in, void* out, int
     a.bias = g.bias; a.mul = mul; a.out_stats = out_stats;
     a.Mrows = Mrows; a.Mvalid = Mvalid; a.Cin = g.Cin; a.N = g.N; a.Npad = g.N; a.ldo = g.N;
     a.epi_act = epi_act; a.out_f32 = out_f32 ? 1 : 0; a.out_scale = out_scale; a.w_pp = g.pp ? 1 : 0;
-    a.no_zs = sw_.conv_zs ? 0 : 1;
     const bool timed = profile_ && g.taps == 9 && conv_gemm_tile_n(g.Cin, g.N) == 320;
     if (timed) {
         if (pev_used_ + 2 > pev_.size()) {
@@ -573,11 +561,11 @@ hipError_t Net::run_conv_tail(const ResBlockW& r, const _Float16* in, const _Flo
     memset(&a, 0, sizeof(a));
     a.in = in; a.w = g.w; a.out = y;
     a.Mrows = Mrows; a.Mvalid = Mrows; a.Cin = g.Cin; a.N = g.N; a.Npad = g.N; a.ldo = g.N;
-    a.epi_act = act; a.out_scale = 1.f; a.w_pp = g.pp ? 1 : 0; a.no_zs = sw_.conv_zs ? 0 : 1;
+    a.epi_act = act; a.out_scale = 1.f; a.w_pp = g.pp ? 1 : 0;
     a.res = x;
     if (next_bn1 && y2) { a.y2 = y2; a.gn_gamma = next_bn1->gamma; a.gn_beta = next_bn1->beta; }
     if (cfg_.se) { a.se_w1 = r.se_w1; a.se_b1 = r.se_b1; a.se_w2 = r.se_w2; a.se_b2 = r.se_b2; a.se_hidden = r.se_hidden;
-                   a.se_w1h = r.se_w1h; a.se_w2h = r.se_w2h; a.se_wf = r.se_wf; }
+                   a.se_wf = r.se_wf; }
     const bool timed = profile_;
     if (timed) {
         if (pev_used_ + 2 > pev_.size()) {
@@ -636,8 +624,9 @@ int Net::forward(const float* planes_dev, const _Float16* nhwc_dev, int B, float
         x0 = X0_;
     }
     const bool big = conv_gemm_tile_n(C, C) == 320;     // fused GN epilogue available (C % 320 == 0)
+    // a squeeze-excite wider than the fused tail takes runs conv2 + se_gate + ew_board instead, as M0_FUSE_TAIL=0 does
     const bool fuse_tail = big && C == 320 && sw_.fuse_tail &&
-                           (!cfg_.se || (res_[0].se_hidden >= 4 && res_[0].se_hidden <= 128 && res_[0].se_hidden % 4 == 0));
+                           (!cfg_.se || (res_[0].se_hidden <= TAIL_SE_HMAX && res_[0].se_hidden % 4 == 0));
     const bool fuse_attn = C == 320 && sw_.fuse_attn;
     // ew: elementwise glue; y2/gn2 = pre-activated input of the NEXT residual block (its bn1), or null
     auto ew = [&](const _Float16* t, const float* tst, const NormParams* gn, const ResBlockW* se, const _Float16* res,
@@ -716,7 +705,7 @@ int Net::forward(const float* planes_dev, const _Float16* nhwc_dev, int B, float
             memset(&ia, 0, sizeof(ia));
             ia.in = xa; ia.w = inter_.w; ia.out = xb;
             ia.Mrows = Mc; ia.Mvalid = Mc; ia.Cin = inter_.Cin; ia.N = inter_.N; ia.Npad = inter_.N; ia.ldo = inter_.N;
-            ia.epi_act = act; ia.out_scale = 1.f; ia.w_pp = inter_.pp ? 1 : 0; ia.no_zs = sw_.conv_zs ? 0 : 1;
+            ia.epi_act = act; ia.out_scale = 1.f; ia.w_pp = inter_.pp ? 1 : 0;
             ia.res = xa; ia.pre_gamma = inter_n_.gamma; ia.pre_beta = inter_n_.beta;
             if (first_bn1) { ia.y2 = AA_; ia.gn_gamma = first_bn1->gamma; ia.gn_beta = first_bn1->beta; }
             KCHK(launch_conv_gemm(ia, 9, st));

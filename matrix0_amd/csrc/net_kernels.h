@@ -5,6 +5,10 @@
 
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2, ACT_LEAKY = 3, ACT_SIGMOID = 4, ACT_TANH = 5 };
 
+// Most squeeze-excite hidden units the fused residual-block tail takes (conv_zs_tail.h; its LDS holds 60 + 60 weight
+// pieces).  A network with a wider squeeze-excite runs conv2, se_gate_kernel and ew_board_kernel instead (net.hip).
+constexpr int TAIL_SE_HMAX = 96;
+
 struct GemmArgs {
     const _Float16* in;      // [Mrows][Cin]
     const _Float16* w;       // packed [taps][Cin/KC][Npad][KC] (big tile: 16-byte chunks XOR-swizzled, see pack_gemm)
@@ -25,7 +29,7 @@ struct GemmArgs {
     float out_scale;
     int ksplit;              // conv_big_kernel: > 1 = split K over gridDim.y, workgroup z writes its fp32 partial tile to
                              // out + z * Mrows * ldo floats (out_f32 = 1, no bias / act); reduced by launch_splitk_reduce
-    int w_pp;                // 3x3 big tile: w is in the half-tile layout of conv_zs_kernel / conv_pp16_kernel (pack_gemm)
+    int w_pp;                // 3x3 big tile: w is in the half-tile layout of conv_zs_kernel (pack_gemm)
     // residual-block tail fused into the epilogue (conv_tail.h), when res != null: out = res + gate * conv,
     // y2 = epi_act(GroupNorm16(out; gn_gamma, gn_beta)) when y2 != null, gate from se_* when se_w1 != null
     const _Float16* res;     // [Mrows][ldo]
@@ -36,10 +40,7 @@ struct GemmArgs {
     const float* se_b1;
     const float* se_w2;      // [Hd][C] (transposed)
     const float* se_b2;
-    int se_hidden;
-    const _Float16* se_w1h;  // fp16 copies of se_w1 / se_w2 (same layouts): conv_pp16's tail stages BOTH in LDS with one DMA
-    const _Float16* se_w2h;  //   wave (half the bytes of the f32 matrices, which it brought in one after the other)
-    int no_zs;               // 3x3 big tile: 1 = conv_pp16_kernel instead of conv_zs_kernel (M0_CONV_ZS=0, read once per network)
+    int se_hidden;           // at most TAIL_SE_HMAX
     const void* se_wf;       // conv_zs_kernel's tail: W1 and W2 as fp16 MFMA B-fragment pieces of 1 KiB (conv_zs_tail.h; net.hip packs)
     // small tile with gn_gamma != null (conv_gemm_kernel, EPI 1): out = epi_act(GroupNorm16(conv)) [+ posenc], fp16, through the
     // LDS-staged 16-byte-store epilogue.  Two consumers of one input in ONE launch (policy-head and value-head 1x1 convs over the

@@ -15,7 +15,7 @@
 //       buffered: the 64-channel slice of the 4 boards and one 320x64 weight stage per chunk (pre-swizzled on
 //       the host).  128-byte LDS rows, 16-byte chunk index XOR (row>>1)&7 -> conflict-free ds_read_b128.
 //       Epilogue: bias/act/mul/scale + per-(board,channel) sums, per element, or the PRE block tail.
-//       (The 3x3 tower convs: conv_zs_kernel / conv_pp16_kernel.)
+//       (The 3x3 tower convs: conv_zs_kernel, conv_zs.hip.)
 //   conv_gemm_kernel<TAPS,1,1,32>  generic small-tile variant (any N%32==0, Cin%32==0): stem, heads, FCs.
 //   ew_board_kernel   per-board elementwise glue: GN+act, SE gate, residual add,
 //       positional encoding, LayerNorm over C, output statistics.
@@ -298,9 +298,7 @@ static hipError_t launch_conv_gemm_gn(const GemmArgs& a, int taps, hipStream_t s
 }
 
 hipError_t launch_conv_big(const GemmArgs& a, int taps, hipStream_t st);   // conv_big.hip
-hipError_t launch_conv_pp16(const GemmArgs& a, hipStream_t st);            // conv_pp16.hip
 hipError_t launch_conv_zs(const GemmArgs& a, hipStream_t st);              // conv_zs.hip
-bool conv_zs_supports(const GemmArgs& a);
 
 int conv_gemm_tile_n(int Cin, int Npad) {
     return (Npad % 320 == 0 && Cin % 64 == 0) ? 320 : 32;
@@ -321,11 +319,8 @@ hipError_t launch_conv_gemm(const GemmArgs& a, int taps, hipStream_t st) {
         if (big) {
             if (!a.w_pp) return hipErrorInvalidValue;
             // conv_zs_kernel: the v_mfma_f32_16x16x32_f16 loop with the wave tile laid out so that the M-tiles that only see the
-            // zero padding above / below the board are skipped (8.3 % of the MFMAs).  conv_pp16_kernel (the same loop without the
-            // skipping) takes the shapes conv_zs does not (squeeze-excite wider than 96 hidden units) and A/B runs
-            // (GemmArgs::no_zs, set from M0_CONV_ZS=0 when the network is created).
-            if (!a.no_zs && conv_zs_supports(a)) return launch_conv_zs(a, st);
-            return launch_conv_pp16(a, st);
+            // zero padding above / below the board are skipped (8.3 % of the MFMAs)
+            return launch_conv_zs(a, st);
         }
         return launch_conv_gemm_t<9, 1, 1, 32>(a, st);
     } else if (taps == 1) {

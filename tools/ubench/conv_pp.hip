@@ -436,7 +436,7 @@ hipError_t launch_conv_pp(const GemmArgs& a, hipStream_t st) {
     if (a.Cin % 64 != 0 || a.Npad % 320 != 0 || a.Mrows % 256 != 0) return hipErrorInvalidValue;
     if (a.mul != nullptr || a.out_f32 != 0) return hipErrorInvalidValue;      // 3x3 convs never use these
     if ((size_t)a.Mrows * a.ldo * 2 >= ((size_t)1 << 32)) return hipErrorInvalidValue;   // 32-bit store offsets
-    // the fused block tail of this layout went with conv_tail.h's squeeze-excite form: conv_pp16 / conv_zs have their own
+    // the fused block tail of this layout went with conv_tail.h's squeeze-excite form: conv_zs has its own (conv_zs_tail.h)
     if (a.res != nullptr) return hipErrorInvalidValue;
     if (a.gn_gamma != nullptr) {                // conv1 of a block: GroupNorm + the network activation
         if (a.epi_act == ACT_SILU) return launch_conv_pp_e<1, ACT_SILU>(a, st);

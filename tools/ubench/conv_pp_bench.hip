@@ -5,7 +5,6 @@
 // L-start / L-end(before barrier) / C-start(after barrier) / C-end(MFMAs issued) of each phase.
 #include "conv_pp.hip"
 #include "conv_sw.hip"
-#include "../../matrix0_amd/csrc/conv_pp16.hip"
 #include "../../matrix0_amd/csrc/conv_zs.hip"
 #include "conv_z2.hip"
 #include "conv_zd.hip"
@@ -20,9 +19,6 @@
 #endif
 #ifdef BENCH_SW
 #define launch_conv_pp launch_conv_sw
-#endif
-#ifdef BENCH_P16
-#define launch_conv_pp launch_conv_pp16
 #endif
 #include <stdio.h>
 #include <string.h>
@@ -59,8 +55,8 @@ int main(int argc, char** argv) {
         (void)dtb;
     }
 #endif
-#if defined(BENCH_TAIL) && !defined(BENCH_ZS) && !defined(BENCH_P16)
-#error "BENCH_TAIL needs BENCH_ZS or BENCH_P16 (conv_pp_kernel has no fused tail)"
+#if defined(BENCH_TAIL) && !defined(BENCH_ZS)
+#error "BENCH_TAIL needs BENCH_ZS (conv_pp_kernel has no fused tail)"
 #endif
 #ifdef BENCH_TAIL   // conv2 with the residual-block tail fused (EPI 3): x, squeeze-excite weights, next GroupNorm, y2
     {
@@ -77,14 +73,7 @@ int main(int argc, char** argv) {
         hipMemcpy(dres, din, (size_t)M * C * 2, hipMemcpyDeviceToDevice);
         a.out_stats = nullptr; a.res = dres; a.y2 = dy2; a.gn_gamma = dg; a.gn_beta = dbt; a.epi_act = ACT_SILU;
         a.se_w1 = dw1; a.se_b1 = db1; a.se_w2 = dw2; a.se_b2 = db2; a.se_hidden = Hd;
-        {
-            std::vector<_Float16> h1(w1.size()), h2(w2.size());
-            for (size_t i = 0; i < w1.size(); ++i) h1[i] = (_Float16)w1[i];
-            for (size_t i = 0; i < w2.size(); ++i) h2[i] = (_Float16)w2[i];
-            _Float16 *dh1, *dh2; hipMalloc(&dh1, h1.size() * 2); hipMalloc(&dh2, h2.size() * 2);
-            hipMemcpy(dh1, h1.data(), h1.size() * 2, hipMemcpyHostToDevice); hipMemcpy(dh2, h2.data(), h2.size() * 2, hipMemcpyHostToDevice);
-            a.se_w1h = dh1; a.se_w2h = dh2;
-            // conv_zs_kernel: MFMA B-fragment pieces (net.hip)
+        {   // conv_zs_kernel: MFMA B-fragment pieces (net.hip)
             const int NT1 = (Hd + 15) / 16, KS2 = (Hd + 31) / 32;
             std::vector<_Float16> wf((size_t)(10 * NT1 + 20 * KS2) * 512, (_Float16)0.f);
             for (int nt = 0; nt < NT1; ++nt) for (int ks = 0; ks < 10; ++ks) for (int l = 0; l < 64; ++l) for (int e = 0; e < 8; ++e) {
@@ -118,8 +107,6 @@ int main(int argc, char** argv) {
     }
 #elif defined(BENCH_ZS)
     hipMemcpyToSymbol(HIP_SYMBOL(g_zs_stamp), &dst_, sizeof(dst_));
-#elif defined(BENCH_P16)
-    hipMemcpyToSymbol(HIP_SYMBOL(g_p16_stamp), &dst_, sizeof(dst_));
 #else
     hipMemcpyToSymbol(HIP_SYMBOL(g_pp_stamp), &dst_, sizeof(dst_));
 #endif
@@ -127,10 +114,6 @@ int main(int argc, char** argv) {
 #if defined(SW_STAMP) && defined(BENCH_ZS) && defined(BENCH_TAIL)
     unsigned long long* dztail_; hipMalloc(&dztail_, (size_t)(M / 256) * 8 * 8); hipMemset(dztail_, 0, (size_t)(M / 256) * 8 * 8);
     hipMemcpyToSymbol(HIP_SYMBOL(g_zs_tail_stamp), &dztail_, sizeof(dztail_));
-#endif
-#if defined(SW_STAMP) && defined(BENCH_P16) && defined(BENCH_TAIL)
-    unsigned long long* dtail_; hipMalloc(&dtail_, (size_t)(M / 256) * 8 * 8); hipMemset(dtail_, 0, (size_t)(M / 256) * 8 * 8);
-    hipMemcpyToSymbol(HIP_SYMBOL(g_tail_stamp), &dtail_, sizeof(dtail_));
 #endif
     hipStream_t st; hipStreamCreate(&st);
 #ifdef BENCH_CMPZD   // conv_zd_kernel (square tiles of 16 boards, all padding skipped) against conv_zs_kernel: same sums in another order
@@ -180,27 +163,6 @@ int main(int argc, char** argv) {
                hipGetErrorString(e1), hipGetErrorString(e2), bad, o1.size(), md, ms, (double)o2[0], (double)o2[1], (double)o2[2], (double)o2[3]);
     }
 #endif
-#ifdef BENCH_CMP   // conv_zs_kernel against conv_pp16_kernel on the same operands: outputs must agree bit for bit (stats / gate: closely)
-    {
-        const size_t nb = (size_t)M * C * 2;
-        std::vector<_Float16> o1((size_t)M * C), o2((size_t)M * C), p1((size_t)M * C), p2((size_t)M * C);
-        hipMemset(dout, 0, nb); if (a.y2) hipMemset(a.y2, 0, nb);
-        hipError_t e1 = launch_conv_pp16(a, st); hipStreamSynchronize(st);
-        hipMemcpy(o1.data(), dout, nb, hipMemcpyDeviceToHost); if (a.y2) hipMemcpy(p1.data(), a.y2, nb, hipMemcpyDeviceToHost);
-        std::vector<float> s1, s2;
-        if (a.out_stats) { s1.resize((size_t)boards * C * 2); hipMemcpy(s1.data(), dstats, s1.size() * 4, hipMemcpyDeviceToHost); }
-        hipMemset(dout, 0, nb); if (a.y2) hipMemset(a.y2, 0, nb);
-        hipError_t e2 = launch_conv_zs(a, st); hipStreamSynchronize(st);
-        hipMemcpy(o2.data(), dout, nb, hipMemcpyDeviceToHost); if (a.y2) hipMemcpy(p2.data(), a.y2, nb, hipMemcpyDeviceToHost);
-        if (a.out_stats) { s2.resize(s1.size()); hipMemcpy(s2.data(), dstats, s2.size() * 4, hipMemcpyDeviceToHost); }
-        size_t bad = 0, bad2 = 0; double md = 0, md2 = 0, ms = 0;
-        for (size_t i = 0; i < o1.size(); ++i) { const double d = fabs((double)o1[i] - (double)o2[i]); if (d != 0) ++bad; if (d > md) md = d; }
-        if (a.y2) for (size_t i = 0; i < p1.size(); ++i) { const double d = fabs((double)p1[i] - (double)p2[i]); if (d != 0) ++bad2; if (d > md2) md2 = d; }
-        for (size_t i = 0; i < s1.size(); ++i) { const double d = fabs((double)s1[i] - (double)s2[i]) / (1.0 + fabs((double)s1[i])); if (d > ms) ms = d; }
-        printf("compare conv_pp16 (%s) vs conv_zs (%s): out %zu differing elements (max |d| %.3g), y2 %zu (max %.3g), stats max rel %.3g; out[0..3] = %g %g %g %g\n",
-               hipGetErrorString(e1), hipGetErrorString(e2), bad, md, bad2, md2, ms, (double)o2[0], (double)o2[1], (double)o2[2], (double)o2[3]);
-    }
-#endif
 #ifdef BENCH_Z2     // argv[3] = start delay of the second workgroup of every CU in us
     if (argc > 3) { const int d = (int)(atof(argv[3]) * 100.0); hipMemcpyToSymbol(HIP_SYMBOL(g_z2_delay), &d, sizeof(int)); }
 #endif
@@ -235,17 +197,6 @@ int main(int argc, char** argv) {
         double d[4] = {0, 0, 0, 0};
         for (int b = 0; b < nb; ++b) for (int k = 0; k < 4; ++k) d[k] += (double)(ht[b * 8 + k + 1] - ht[b * 8 + k]);
         printf("zs tail phases per workgroup (wave 0): SE gate %.2f us, stage + x loads %.2f us, y = x + t / store / stats %.2f us, y2 %.2f us\n",
-               d[0] / nb * 0.01, d[1] / nb * 0.01, d[2] / nb * 0.01, d[3] / nb * 0.01);
-    }
-#endif
-#if defined(SW_STAMP) && defined(BENCH_P16) && defined(BENCH_TAIL)
-    {
-        const int nb = M / 256;
-        std::vector<unsigned long long> ht((size_t)nb * 8);
-        hipMemcpy(ht.data(), dtail_, ht.size() * 8, hipMemcpyDeviceToHost);
-        double d[4] = {0, 0, 0, 0};
-        for (int b = 0; b < nb; ++b) for (int k = 0; k < 4; ++k) d[k] += (double)(ht[b * 8 + k + 1] - ht[b * 8 + k]);
-        printf("tail phases per workgroup (wave 0): SE gate %.2f us, stage + x loads %.2f us, y = x + t / store / stats %.2f us, y2 %.2f us\n",
                d[0] / nb * 0.01, d[1] / nb * 0.01, d[2] / nb * 0.01, d[3] / nb * 0.01);
     }
 #endif
@@ -299,46 +250,6 @@ int main(int argc, char** argv) {
         std::sort(cyc.begin(), cyc.end());
         if (n) printf("conv_zd per workgroup (n=%d): prologue %.2f us, main loop %.2f us (median %.0f cycles -> %.0f MHz), epilogue %.2f us\n",
                       n, pro / n * 0.01, loop / n * 0.01, cyc[cyc.size() / 2], cyc[cyc.size() / 2] / (loop / n * 0.01), epi / n * 0.01);
-    }
-#endif
-#if defined(SW_STAMP) && defined(BENCH_P16)
-    {   // per-CU timeline of the last launch: entry -> loop start -> loop end -> (before epilogue), realtime ticks of 10 ns
-        const int nb = M / 256;
-        std::vector<unsigned long long> hs((size_t)nb * 8);
-        hipMemcpy(hs.data(), dst_, hs.size() * 8, hipMemcpyDeviceToHost);
-        struct Ev { unsigned long long entry, ls, le, x; };
-        std::map<unsigned long long, std::vector<Ev>> bycu;
-        unsigned long long t0 = ~0ull, t1 = 0;
-        for (int b = 0; b < nb; ++b) {
-            Ev e{hs[(size_t)nb * 4 + b * 4 + 0], hs[b * 4 + 1], hs[b * 4 + 3], hs[(size_t)nb * 4 + b * 4 + 1]};
-            const unsigned long long id = (hs[(size_t)nb * 4 + b * 4 + 3] << 32) | (hs[(size_t)nb * 4 + b * 4 + 2] & 0xffffff00ull);
-            bycu[id].push_back(e);
-            t0 = std::min(t0, e.entry); t1 = std::max(t1, e.x);
-        }
-        double pro = 0, loop = 0, gap = 0; int ng = 0, n = 0;
-        for (auto& kv : bycu) {
-            auto& v = kv.second;
-            std::sort(v.begin(), v.end(), [](const Ev& a, const Ev& b) { return a.entry < b.entry; });
-            for (size_t i = 0; i < v.size(); ++i) {
-                pro += (double)(v[i].ls - v[i].entry); loop += (double)(v[i].le - v[i].ls); ++n;
-                if (i) { gap += (double)(v[i].entry - v[i - 1].x); ++ng; }
-            }
-        }
-        {   // idle time between the last two launches on the device's own clock
-            std::vector<unsigned long long> h2((size_t)nb * 16);
-            hipMemcpy(h2.data(), dst_, h2.size() * 8, hipMemcpyDeviceToHost);
-            unsigned long long ent[2] = {~0ull, ~0ull}, ex[2] = {0, 0};
-            for (int par = 0; par < 2; ++par)
-                for (int b = 0; b < nb; ++b) {
-                    const unsigned long long* o = h2.data() + (size_t)nb * 4 + (size_t)par * nb * 8 + b * 4;
-                    ent[par] = std::min(ent[par], o[0]); ex[par] = std::max(ex[par], o[1]);
-                }
-            const int last = (iters - 1) & 1, prev = last ^ 1;
-            printf("between the last two launches: previous exit -> last first entry %.2f us; previous span %.1f us, last span %.1f us\n",
-                   ((double)ent[last] - (double)ex[prev]) * 0.01, (ex[prev] - ent[prev]) * 0.01, (ex[last] - ent[last]) * 0.01);
-        }
-        printf("timeline: %zu CU ids, span %.1f us; per workgroup: prologue %.2f us, main loop %.2f us; gap end->next entry %.2f us (n=%d); first entry spread -> see span\n",
-               bycu.size(), (t1 - t0) * 0.01, pro / n * 0.01, loop / n * 0.01, ng ? gap / ng * 0.01 : 0.0, ng);
     }
 #endif
 #ifdef PP_TRACE
