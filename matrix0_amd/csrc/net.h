@@ -48,14 +48,22 @@ struct TowerLayer {
     int kind;    // 0 = residual block, 1 = attention
     int index;   // into res / att vectors
     bool skip;   // inference attention stride (resnet.py:678-687)
+    // res_ index of the residual block that consumes the stream right after this layer: its bn1 + activation is applied by
+    // whatever writes the stream here.  -1: the next executed layer is attention, or the tower ends (finalize fills it in)
+    int next_bn1 = -1;
 };
 
 struct SslHeadW {
-    std::string task;
     PackedGemm c0, c1;
     NormParams n;
     int out_ch = 0;
-    int hidden = 0;
+};
+
+// Optional operands of Net::conv_norm_act, set by name at the call site.
+struct ConvNormOpts {
+    const float* posenc = nullptr;          // [64][N] added after the activation (stem)
+    const _Float16* res = nullptr;          // residual added after the activation
+    const NormParams* next_bn1 = nullptr;   // with it AA_ also receives act(GroupNorm16(out; next_bn1)), the next block's conv1 input
 };
 
 class Net {
@@ -89,8 +97,6 @@ public:
     // Dominant-kernel timing (roofline): when enabled every 3x3 C->C conv launch is bracketed by HIP events on
     // the launch stream; harvest after the stream has been synchronised.
     void set_profile(bool on) { profile_ = on; }
-    hipError_t run_conv_tail(const ResBlockW& r, const _Float16* in, const _Float16* x, _Float16* y,
-                             const NormParams* next_bn1, _Float16* y2, int act, int Mrows, hipStream_t st);
     void harvest_profile();
     double prof_conv_ms() const { return prof_ms_; }
     double prof_conv_flop() const { return prof_flop_; }
@@ -103,7 +109,17 @@ private:
     m0_net_cfg cfg_;
     int device_;
     hipStream_t stream_ = nullptr;
-    struct Switches { bool fuse_tail = true, fuse_attn = true, splitk = true, fuse_small = true; } sw_;   // read once (constructor)
+    struct Switches { bool fuse_tail = true, fuse_attn = true; } sw_;   // read once (constructor)
+    // What forward() would otherwise derive again on every call: fixed by the configuration, the switches and the squeeze-excite
+    // width, filled in at the end of finalize().  Layers are named by index into res_ (TowerLayer::next_bn1, first_bn1), not by
+    // pointer: shared_view() copies the vectors, and an index stays valid in the copy.
+    struct Plan {
+        bool fuse_tail = false;   // conv2 + squeeze-excite + residual (+ next GroupNorm) and the chess-feature convs' tails in one kernel
+        bool fuse_attn = false;   // attn_block_kernel
+        bool gn_small = false;    // small-tile convs (stem, heads) take GroupNorm + activation in their epilogue: trunk % 64 == 0
+        int act = 0, vact = 0;    // ACT_* of the network / of the value FCs
+        int first_bn1 = -1;       // res_ index of the block that consumes the stem / chess-feature output, or -1
+    } plan_;
     bool finalized_ = false;
     size_t nparams_ = 0;
     std::map<std::string, HostTensor> sd_;
@@ -122,7 +138,7 @@ private:
     std::vector<AttnW> att_;
     std::vector<TowerLayer> tower_;
     PackedGemm ph_conv_, pfc1_, pfc2_;
-    PackedGemm hv_;          // policy_head.0 and value_head.0 as ONE 1x1 GEMM over the trunk (N = 64 + 128), round 4
+    PackedGemm hv_;          // policy_head.0 and value_head.0 as ONE 1x1 GEMM over the trunk (N = 64 + 128)
     NormParams hv_n_;        // their GroupNorm parameters, concatenated
     NormParams ph_n_;
     float logit_scale_ = 1.f;
@@ -143,21 +159,36 @@ private:
     int wsB_ = 0, wsM_ = 0;
     _Float16 *X0_ = nullptr, *XA_ = nullptr, *XB_ = nullptr, *T1_ = nullptr, *T2_ = nullptr, *QKV_ = nullptr,
              *O_ = nullptr, *AA_ = nullptr;
-    float *SX_ = nullptr, *S1_ = nullptr, *S2_ = nullptr, *G_ = nullptr;   // G_: squeeze-excite gates [B][C]
+    float *S1_ = nullptr, *S2_ = nullptr, *G_ = nullptr;   // G_: squeeze-excite gates [B][C]
     _Float16 *PH_ = nullptr, *PH2_ = nullptr, *VH_ = nullptr, *VH2_ = nullptr, *F1_ = nullptr, *F2_ = nullptr,
              *F3_ = nullptr, *F4_ = nullptr, *SH_ = nullptr, *SH2_ = nullptr, *SO_ = nullptr;
     float* VAL_ = nullptr;
+    float* SPK_ = nullptr;      // split-K partial tiles [8][Mfc][2C] f32 (value_fc1)
 
     const HostTensor* get(const std::string& k, std::string& err);
     int pack_gemm(PackedGemm& g, const std::string& wkey, const std::string& bkey, int taps, int Cin_real,
                   int Cin_pad, int N_real, int N_pad, int k_perm_ch, std::string& err, int qkv_heads = 0,
                   int qkv_heads_pad = 0);
-    float* SPK_ = nullptr;      // split-K partial tiles [8][Mfc][2C] f32 (value_fc1)
     int pack_attn_block(AttnW& a, const std::string& prefix, std::string& err);
+    int pack_chess_features(std::string& err);
+    int pack_se(ResBlockW& r, const std::string& prefix, std::string& err);
+    int pack_attn(AttnW& a, bool skip, const std::string& prefix, std::string& err);
+    void upload_attn_mask();
+    int pack_joint_head(std::string& err);
+    int pack_ssl_heads(std::string& err);
+    void make_plan();
     int upload_norm(NormParams& n, const std::string& prefix, int C_real, int C_pad, std::string& err);
     float* upload_f32(const std::vector<float>& v);
     void* dalloc(size_t bytes, bool ws);
-    hipError_t run_gemm(const PackedGemm& g, const _Float16* in, void* out, int Mrows, int Mvalid,
-                        const NormParams* out_norm, int epi_act, const _Float16* mul, float* out_stats,
-                        bool out_f32, float out_scale, hipStream_t st);
+    const NormParams* bn1(int res_index) const { return res_index < 0 ? nullptr : &res_[res_index].bn1; }
+    // roofline bracket: `launch()` between two events on `st` when `on`, with its FLOP count and whether it carries a fused tail
+    template <class Launch>
+    hipError_t profiled(bool on, hipStream_t st, double flop, bool tail, Launch&& launch);
+    // one conv / FC launch from filled-in arguments (gemm_args + named fields); splits K for value_fc1
+    hipError_t run_gemm(const PackedGemm& g, GemmArgs a, hipStream_t st);
+    // out = act(GroupNorm16(conv(in); n)) [+ posenc] [+ res], in the conv's epilogue where a kernel has one, else the raw conv
+    // into `scratch` + ew_board_kernel
+    hipError_t conv_norm_act(const PackedGemm& g, const NormParams& n, const _Float16* in, _Float16* out, _Float16* scratch,
+                             int Mrows, hipStream_t st, const ConvNormOpts& o = ConvNormOpts());
+    hipError_t se_gate(const ResBlockW& r, const float* stats, int boards, hipStream_t st);   // G_ <- the block's gates
 };

@@ -1,18 +1,31 @@
-// Host side of the network forward (see net.h).
+// Host side of the network forward (see net.h): state-dict intake and repacking (finalize and its pack_* / upload_* helpers),
+// the workspace, and the schedule of one forward.
+//
+// The forward, step by step, with the kernel each step launches.  "fused" is what a 320-wide trunk runs by default; "unfused" is
+// what a kernel-less width, M0_FUSE_TAIL=0 / M0_FUSE_ATTN=0 or a wide squeeze-excite falls back to: the raw conv with
+// per-(board, channel) statistics, then ew_board_kernel.  Every "conv -> GroupNorm + act" step goes through conv_norm_act, which
+// picks the form; Plan (net.h) holds the choices that do not depend on the step.
+//
+//   step                                   fused                                            unfused
+//   input planes -> NHWC fp16              planes_to_nhwc (skipped when the engine encoded into X0_)
+//   stem + positional encoding             conv_gemm_kernel<9> GN epilogue (trunk % 64 == 0) conv_gemm_kernel<9> + ew_board
+//   stem without chess features            --                                               conv_gemm_kernel<9> + ew_board (+ next bn1)
+//   piece-square-table 1x1 + residual      conv_big_kernel, pre_gamma tail                  conv + ew_board
+//   interaction 3x3 + residual + next bn1  conv_zs_kernel, pre_gamma tail                   conv + ew_board
+//   block conv1 + bn2                      conv_zs_kernel GN epilogue                       conv_gemm_kernel<9> + ew_board
+//   block conv2 + SE + residual + next bn1 conv_zs_kernel tail (conv_zs_tail.h)             conv + se_gate + ew_board
+//   attention block                        attn_block_kernel                                qkv GEMM + attn_core + proj GEMM + ew_board
+//   policy_head.0 and value_head.0         one conv_gemm_kernel<1>, N = 64 + 128, two outputs  two convs, each + ew_board
+//   policy FCs                             conv_gemm_kernel<1> (bias, ReLU; f32 logits * logit scale)
+//   value_head.3                           conv_gemm_kernel<1> GN epilogue                  conv + ew_board
+//   value_fc1                              conv_big_kernel split-K + splitk_reduce (widths 160, 320), else conv_gemm_kernel<1>
+//   value_fc2, gate, fc3                   conv_gemm_kernel<1>
+//   SSL head: conv + GN, conv, transpose   conv_gemm_kernel<1> GN epilogue (N in 32/64/128/160), conv, nhwc_to_nchw_f32
 #include "net.h"
 #include <math.h>
 #include <string.h>
 #include <algorithm>
 #include <stdlib.h>
-
-#define HIPCHK(x)                                                                         \
-    do {                                                                                  \
-        hipError_t e_ = (x);                                                              \
-        if (e_ != hipSuccess) {                                                           \
-            err = std::string(#x) + ": " + hipGetErrorString(e_);                         \
-            return M0_ERR_HIP;                                                            \
-        }                                                                                 \
-    } while (0)
 
 static inline int ceil_to(int v, int m) { return (v + m - 1) / m * m; }
 
@@ -35,12 +48,11 @@ const char* Net::check_supported(const m0_net_cfg& c) {
 }
 
 Net::Net(const m0_net_cfg& cfg, int device, hipStream_t stream) : cfg_(cfg), device_(device), stream_(stream) {
-    // kernel-variant switches (A/B runs): read ONCE, here, so that the layout decisions of forward() and the dispatcher agree
+    // kernel-variant switches (A/B runs, and the tests' reference for the fused kernels): read ONCE, here, so that the layout
+    // decisions of finalize() and forward() agree
     auto off = [](const char* name) { const char* e = getenv(name); return e && e[0] == '0'; };
     sw_.fuse_tail = !off("M0_FUSE_TAIL");     // =0: conv2 + se_gate + ew_board as separate kernels
-    sw_.fuse_small = !off("M0_FUSE_SMALL");   // =0: stem / head convs write raw tensors + statistics for ew_board passes (rounds 1-3)
     sw_.fuse_attn = !off("M0_FUSE_ATTN");     // =0: qkv GEMM + attn_core + proj GEMM + ew_board as separate kernels
-    sw_.splitk = !off("M0_SPLITK");           // =0: value_fc1 never splits K
     C_ = cfg.channels;
     Cp_ = (C_ > 256 && C_ < 320) ? 320 : C_;
     Cs_ = ceil_to(std::max(16, C_ / 2), 32);
@@ -252,6 +264,178 @@ int Net::upload_norm(NormParams& n, const std::string& prefix, int C_real, int C
 
 #define TRY(x) do { int rc_ = (x); if (rc_ != M0_OK) return rc_; } while (0)
 
+// positional encoding [64][P] and the two feature convs (resnet.py:229-244)
+int Net::pack_chess_features(std::string& err) {
+    const int C = C_, P = Cp_;
+    const HostTensor* pe = get("chess_features.position_encoding", err);
+    if (!pe) return M0_ERR_INVALID;
+    if ((int)pe->data.size() != C * 64) { err = "shape mismatch for position_encoding"; return M0_ERR_INVALID; }
+    nparams_ += pe->data.size();
+    std::vector<float> t((size_t)64 * P, 0.f);
+    for (int c = 0; c < C; ++c)
+        for (int n = 0; n < 64; ++n) t[(size_t)n * P + c] = pe->data[(size_t)c * 64 + n];
+    posenc_ = upload_f32(t);
+    if (cfg_.piece_square_tables) {
+        TRY(pack_gemm(pst_, "chess_features.pst_conv.weight", "", 1, C, P, C, P, 0, err));
+        TRY(upload_norm(pst_n_, "chess_features.pst_norm", C, P, err));
+    }
+    TRY(pack_gemm(inter_, "chess_features.interaction_conv.weight", "", 9, C, P, C, P, 0, err));
+    return upload_norm(inter_n_, "chess_features.interaction_norm", C, P, err);
+}
+
+// squeeze-excite of one block: both FCs transposed for se_gate_kernel and, where the fused tail can take them, as fp16 MFMA
+// fragment pieces for conv_zs_kernel
+int Net::pack_se(ResBlockW& r, const std::string& p, std::string& err) {
+    const int C = C_, P = Cp_;
+    const int hd = std::max(8, (int)(C * cfg_.se_ratio));
+    r.se_hidden = hd;
+    const HostTensor* w1 = get(p + ".se_fc1.weight", err); if (!w1) return M0_ERR_INVALID;
+    const HostTensor* b1 = get(p + ".se_fc1.bias", err); if (!b1) return M0_ERR_INVALID;
+    const HostTensor* w2 = get(p + ".se_fc2.weight", err); if (!w2) return M0_ERR_INVALID;
+    const HostTensor* b2 = get(p + ".se_fc2.bias", err); if (!b2) return M0_ERR_INVALID;
+    if ((int)w1->data.size() != hd * C || (int)w2->data.size() != hd * C || (int)b1->data.size() != hd ||
+        (int)b2->data.size() != C) { err = "shape mismatch for " + p + ".se_*"; return M0_ERR_INVALID; }
+    nparams_ += (size_t)2 * hd * C + hd + C;
+    std::vector<float> w1t((size_t)P * hd, 0.f);  // [P][hd] from [hd][C]
+    for (int j = 0; j < hd; ++j)
+        for (int c = 0; c < C; ++c) w1t[(size_t)c * hd + j] = w1->data[(size_t)j * C + c];
+    r.se_w1 = upload_f32(w1t);
+    r.se_b1 = upload_f32(b1->data);
+    std::vector<float> w2t((size_t)hd * P, 0.f);  // [hd][P] from [C][hd]: coalesced across channels
+    for (int c = 0; c < C; ++c)
+        for (int j = 0; j < hd; ++j) w2t[(size_t)j * P + c] = w2->data[(size_t)c * hd + j];
+    r.se_w2 = upload_f32(w2t);
+    if (P == 320 && hd <= TAIL_SE_HMAX) {
+        // conv_zs_kernel's tail runs the two FCs on the matrix cores: B-fragment pieces of v_mfma_f32_16x16x32_f16,
+        // lane (c15 = lane & 15, q = lane >> 4) holds column c15, k = 8q..8q+7 of its tile (conv_zs_tail.h):
+        //   W1 piece (nt, ks):   W1[channel 32 ks + 8 q + e][hidden 16 nt + c15]     nt < ceil(hd/16), ks < 10
+        //   W2 piece (nt, ks):   W2[hidden 32 ks + 8 q + e][channel 16 nt + c15]     nt < 20, ks < ceil(hd/32)
+        const int NT1 = (hd + 15) / 16, KS2 = (hd + 31) / 32;
+        std::vector<_Float16> wf((size_t)(10 * NT1 + 20 * KS2) * 512, (_Float16)0.f);
+        for (int nt = 0; nt < NT1; ++nt)
+            for (int ks = 0; ks < 10; ++ks)
+                for (int l = 0; l < 64; ++l)
+                    for (int e = 0; e < 8; ++e) {
+                        const int c = 32 * ks + 8 * (l >> 4) + e, j = 16 * nt + (l & 15);
+                        if (j < hd) wf[((size_t)(nt * 10 + ks) * 64 + l) * 8 + e] = (_Float16)w1t[(size_t)c * hd + j];
+                    }
+        for (int nt = 0; nt < 20; ++nt)
+            for (int ks = 0; ks < KS2; ++ks)
+                for (int l = 0; l < 64; ++l)
+                    for (int e = 0; e < 8; ++e) {
+                        const int j = 32 * ks + 8 * (l >> 4) + e, c = 16 * nt + (l & 15);
+                        if (j < hd) wf[((size_t)(10 * NT1 + nt * KS2 + ks) * 64 + l) * 8 + e] = (_Float16)w2t[(size_t)j * P + c];
+                    }
+        r.se_wf = dalloc(wf.size() * 2, false);
+        if (!r.se_wf) { err = "hipMalloc failed"; return M0_ERR_HIP; }
+        (void)hipMemcpy(r.se_wf, wf.data(), wf.size() * 2, hipMemcpyHostToDevice);
+    }
+    std::vector<float> b2p(P, 0.f);
+    std::copy(b2->data.begin(), b2->data.end(), b2p.begin());
+    r.se_b2 = upload_f32(b2p);
+    return M0_OK;
+}
+
+int Net::pack_attn(AttnW& a, bool skip, const std::string& p, std::string& err) {
+    const int C = C_, P = Cp_;
+    if (skip) {   // never executed at inference; count parameters, keep nothing resident
+        for (const char* k : {".qkv.weight", ".proj.weight", ".norm.weight", ".norm.bias", ".rel_bias"}) {
+            auto it = sd_.find(p + k);
+            if (it != sd_.end()) nparams_ += it->second.data.size();
+        }
+        return M0_OK;
+    }
+    TRY(pack_gemm(a.qkv, p + ".qkv.weight", "", 1, C, P, 3 * C, 3 * P, 0, err, P != C ? cfg_.attention_heads : 0, P / 16));
+    TRY(pack_gemm(a.proj, p + ".proj.weight", "", 1, C, P, C, P, 0, err));
+    TRY(upload_norm(a.ln, p + ".norm", C, P, err));
+    if (P == 320) TRY(pack_attn_block(a, p, err));
+    if (cfg_.attention_relbias) {
+        const HostTensor* rb = get(p + ".rel_bias", err); if (!rb) return M0_ERR_INVALID;
+        if ((int)rb->data.size() != cfg_.attention_heads * 4096) { err = "shape mismatch for rel_bias"; return M0_ERR_INVALID; }
+        nparams_ += rb->data.size();
+        // stored pre-multiplied by log2(e): the attention kernel exponentiates with exp2
+        std::vector<float> rbs((size_t)(P / 16) * 4096, 0.f);      // padded heads: zero bias
+        for (size_t i = 0; i < rb->data.size(); ++i) rbs[i] = rb->data[i] * 1.44269504088896f;
+        a.rel_bias = upload_f32(rbs);
+    }
+    return M0_OK;
+}
+
+// attention visibility mask, resnet.py:104-130
+void Net::upload_attn_mask() {
+    std::vector<uint64_t> m(64, 0);
+    for (int i = 0; i < 64; ++i)
+        for (int j = 0; j < 64; ++j) {
+            int dr = i / 8 - j / 8, dc = i % 8 - j % 8;
+            int adr = abs(dr), adc = abs(dc);
+            bool vis = dr == 0 || dc == 0 || adr == adc || (adr == 2 && adc == 1) || (adr == 1 && adc == 2) ||
+                       (adr <= 1 && adc <= 1);
+            if (vis) m[i] |= (1ull << j);
+        }
+    mask_dev_ = (uint64_t*)dalloc(64 * 8, false);
+    (void)hipMemcpy(mask_dev_, m.data(), 64 * 8, hipMemcpyHostToDevice);
+}
+
+// policy_head.0 (64 channels) and value_head.0 (128) read the same trunk: one GEMM with N = 192, columns [policy | value], both
+// in the small-tile layout [Cin / 32][N][32]; GroupNorm parameters concatenated the same way.  Built from the two packed
+// convs and their norms as they were uploaded.
+int Net::pack_joint_head(std::string& err) {
+    const int nch = Cp_ / 32;
+    std::vector<_Float16> a((size_t)nch * 64 * 32), b((size_t)nch * 128 * 32), c((size_t)nch * 192 * 32);
+    (void)hipMemcpy(a.data(), ph_conv_.w, a.size() * 2, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(b.data(), vh0_.w, b.size() * 2, hipMemcpyDeviceToHost);
+    for (int ch = 0; ch < nch; ++ch) {
+        std::copy(a.begin() + (size_t)ch * 64 * 32, a.begin() + (size_t)(ch + 1) * 64 * 32, c.begin() + (size_t)ch * 192 * 32);
+        std::copy(b.begin() + (size_t)ch * 128 * 32, b.begin() + (size_t)(ch + 1) * 128 * 32, c.begin() + ((size_t)ch * 192 + 64) * 32);
+    }
+    hv_.w = (_Float16*)dalloc(c.size() * 2, false);
+    if (!hv_.w) { err = "hipMalloc failed"; return M0_ERR_HIP; }
+    (void)hipMemcpy(hv_.w, c.data(), c.size() * 2, hipMemcpyHostToDevice);
+    hv_.taps = 1; hv_.Cin = Cp_; hv_.N = 192; hv_.pp = false; hv_.bias = nullptr;
+    std::vector<float> g(192), be(192);
+    (void)hipMemcpy(g.data(), ph_n_.gamma, 64 * 4, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(g.data() + 64, vh1_n_.gamma, 128 * 4, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(be.data(), ph_n_.beta, 64 * 4, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(be.data() + 64, vh1_n_.beta, 128 * 4, hipMemcpyDeviceToHost);
+    hv_n_.gamma = upload_f32(g); hv_n_.beta = upload_f32(be);
+    if (!hv_n_.gamma || !hv_n_.beta) { err = "hipMalloc failed"; return M0_ERR_HIP; }
+    return M0_OK;
+}
+
+int Net::pack_ssl_heads(std::string& err) {
+    for (int t = 0; t < 5; ++t) {
+        if (!(cfg_.ssl_tasks & (1 << t))) continue;
+        SslHeadW h;
+        h.out_ch = kSslOut[t];
+        std::string p = std::string("ssl_heads.") + kSslNames[t];
+        TRY(pack_gemm(h.c0, p + ".0.weight", "", 1, C_, Cp_, C_ / 2, Cs_, 0, err));
+        TRY(upload_norm(h.n, p + ".1", C_ / 2, Cs_, err));
+        TRY(pack_gemm(h.c1, p + ".3.weight", "", 1, C_ / 2, Cs_, h.out_ch, 32, 0, err));
+        ssl_.push_back(h);
+    }
+    return M0_OK;
+}
+
+// The schedule choices that do not depend on the batch (Plan, TowerLayer::next_bn1): see net.h.
+void Net::make_plan() {
+    const bool big = conv_gemm_tile_n(Cp_, Cp_) == 320;     // 320-wide trunk: conv_zs_kernel / conv_big_kernel with their epilogues
+    // a squeeze-excite wider than the fused tail takes runs conv2 + se_gate + ew_board instead, as M0_FUSE_TAIL=0 does
+    plan_.fuse_tail = big && sw_.fuse_tail &&
+                      (!cfg_.se || (res_[0].se_hidden <= TAIL_SE_HMAX && res_[0].se_hidden % 4 == 0));
+    plan_.fuse_attn = big && sw_.fuse_attn;
+    plan_.gn_small = Cp_ % 64 == 0;
+    plan_.act = cfg_.activation == M0_ACT_SILU ? ACT_SILU : ACT_RELU;
+    plan_.vact = cfg_.value_activation == M0_ACT_SILU ? ACT_SILU : (cfg_.value_activation == M0_ACT_LEAKY ? ACT_LEAKY : ACT_RELU);
+    int next = -1;                      // walking up from the end: the residual block that follows position i
+    for (size_t i = tower_.size(); i-- > 0;) {
+        TowerLayer& L = tower_[i];
+        if (L.kind == 1 && L.skip) continue;
+        L.next_bn1 = next;
+        next = L.kind == 0 ? L.index : -1;
+    }
+    plan_.first_bn1 = next;
+}
+
 int Net::finalize(std::string& err) {
     if (finalized_) return M0_OK;
     if (hipSetDevice(device_) != hipSuccess) { err = "hipSetDevice failed"; return M0_ERR_HIP; }
@@ -259,22 +443,7 @@ int Net::finalize(std::string& err) {
     nparams_ = 0;
     TRY(pack_gemm(stem_, "stem.0.weight", "", 9, cfg_.planes, 32, C, P, 0, err));
     TRY(upload_norm(stem_n_, "stem.1", C, P, err));
-    if (cfg_.chess_features) {
-        const HostTensor* pe = get("chess_features.position_encoding", err);
-        if (!pe) return M0_ERR_INVALID;
-        if ((int)pe->data.size() != C * 64) { err = "shape mismatch for position_encoding"; return M0_ERR_INVALID; }
-        nparams_ += pe->data.size();
-        std::vector<float> t((size_t)64 * P, 0.f);
-        for (int c = 0; c < C; ++c)
-            for (int n = 0; n < 64; ++n) t[(size_t)n * P + c] = pe->data[(size_t)c * 64 + n];
-        posenc_ = upload_f32(t);
-        if (cfg_.piece_square_tables) {
-            TRY(pack_gemm(pst_, "chess_features.pst_conv.weight", "", 1, C, P, C, P, 0, err));
-            TRY(upload_norm(pst_n_, "chess_features.pst_norm", C, P, err));
-        }
-        TRY(pack_gemm(inter_, "chess_features.interaction_conv.weight", "", 9, C, P, C, P, 0, err));
-        TRY(upload_norm(inter_n_, "chess_features.interaction_norm", C, P, err));
-    }
+    if (cfg_.chess_features) TRY(pack_chess_features(err));
     int ti = 0;
     for (auto& L : tower_) {
         std::string p = "tower." + std::to_string(ti++);
@@ -284,95 +453,14 @@ int Net::finalize(std::string& err) {
             TRY(pack_gemm(r.conv2, p + ".conv2.weight", "", 9, C, P, C, P, 0, err));
             TRY(upload_norm(r.bn1, p + ".bn1", C, P, err));
             TRY(upload_norm(r.bn2, p + ".bn2", C, P, err));
-            if (cfg_.se) {
-                int hd = std::max(8, (int)(C * cfg_.se_ratio));
-                r.se_hidden = hd;
-                const HostTensor* w1 = get(p + ".se_fc1.weight", err); if (!w1) return M0_ERR_INVALID;
-                const HostTensor* b1 = get(p + ".se_fc1.bias", err); if (!b1) return M0_ERR_INVALID;
-                const HostTensor* w2 = get(p + ".se_fc2.weight", err); if (!w2) return M0_ERR_INVALID;
-                const HostTensor* b2 = get(p + ".se_fc2.bias", err); if (!b2) return M0_ERR_INVALID;
-                if ((int)w1->data.size() != hd * C || (int)w2->data.size() != hd * C || (int)b1->data.size() != hd ||
-                    (int)b2->data.size() != C) { err = "shape mismatch for " + p + ".se_*"; return M0_ERR_INVALID; }
-                nparams_ += (size_t)2 * hd * C + hd + C;
-                std::vector<float> w1t((size_t)P * hd, 0.f);  // [P][hd] from [hd][C]
-                for (int j = 0; j < hd; ++j)
-                    for (int c = 0; c < C; ++c) w1t[(size_t)c * hd + j] = w1->data[(size_t)j * C + c];
-                r.se_w1 = upload_f32(w1t);
-                r.se_b1 = upload_f32(b1->data);
-                std::vector<float> w2t((size_t)hd * P, 0.f);  // [hd][P] from [C][hd]: coalesced across channels
-                for (int c = 0; c < C; ++c)
-                    for (int j = 0; j < hd; ++j) w2t[(size_t)j * P + c] = w2->data[(size_t)c * hd + j];
-                r.se_w2 = upload_f32(w2t);
-                if (P == 320 && hd <= TAIL_SE_HMAX) {
-                    // conv_zs_kernel's tail runs the two FCs on the matrix cores: B-fragment pieces of v_mfma_f32_16x16x32_f16,
-                    // lane (c15 = lane & 15, q = lane >> 4) holds column c15, k = 8q..8q+7 of its tile (conv_zs_tail.h):
-                    //   W1 piece (nt, ks):   W1[channel 32 ks + 8 q + e][hidden 16 nt + c15]     nt < ceil(hd/16), ks < 10
-                    //   W2 piece (nt, ks):   W2[hidden 32 ks + 8 q + e][channel 16 nt + c15]     nt < 20, ks < ceil(hd/32)
-                    const int NT1 = (hd + 15) / 16, KS2 = (hd + 31) / 32;
-                    std::vector<_Float16> wf((size_t)(10 * NT1 + 20 * KS2) * 512, (_Float16)0.f);
-                    for (int nt = 0; nt < NT1; ++nt)
-                        for (int ks = 0; ks < 10; ++ks)
-                            for (int l = 0; l < 64; ++l)
-                                for (int e = 0; e < 8; ++e) {
-                                    const int c = 32 * ks + 8 * (l >> 4) + e, j = 16 * nt + (l & 15);
-                                    if (j < hd) wf[((size_t)(nt * 10 + ks) * 64 + l) * 8 + e] = (_Float16)w1t[(size_t)c * hd + j];
-                                }
-                    for (int nt = 0; nt < 20; ++nt)
-                        for (int ks = 0; ks < KS2; ++ks)
-                            for (int l = 0; l < 64; ++l)
-                                for (int e = 0; e < 8; ++e) {
-                                    const int j = 32 * ks + 8 * (l >> 4) + e, c = 16 * nt + (l & 15);
-                                    if (j < hd) wf[((size_t)(10 * NT1 + nt * KS2 + ks) * 64 + l) * 8 + e] = (_Float16)w2t[(size_t)j * P + c];
-                                }
-                    r.se_wf = dalloc(wf.size() * 2, false);
-                    if (!r.se_wf) { err = "hipMalloc failed"; return M0_ERR_HIP; }
-                    (void)hipMemcpy(r.se_wf, wf.data(), wf.size() * 2, hipMemcpyHostToDevice);
-                }
-                std::vector<float> b2p(P, 0.f);
-                std::copy(b2->data.begin(), b2->data.end(), b2p.begin());
-                r.se_b2 = upload_f32(b2p);
-            }
+            if (cfg_.se) TRY(pack_se(r, p, err));
         } else {
-            AttnW& a = att_[L.index];
-            if (L.skip) {   // never executed at inference; count parameters, keep nothing resident
-                for (const char* k : {".qkv.weight", ".proj.weight", ".norm.weight", ".norm.bias", ".rel_bias"}) {
-                    auto it = sd_.find(p + k);
-                    if (it != sd_.end()) nparams_ += it->second.data.size();
-                }
-                continue;
-            }
-            TRY(pack_gemm(a.qkv, p + ".qkv.weight", "", 1, C, P, 3 * C, 3 * P, 0, err, P != C ? cfg_.attention_heads : 0, P / 16));
-            TRY(pack_gemm(a.proj, p + ".proj.weight", "", 1, C, P, C, P, 0, err));
-            TRY(upload_norm(a.ln, p + ".norm", C, P, err));
-            if (P == 320) TRY(pack_attn_block(a, p, err));
-            if (cfg_.attention_relbias) {
-                const HostTensor* rb = get(p + ".rel_bias", err); if (!rb) return M0_ERR_INVALID;
-                if ((int)rb->data.size() != cfg_.attention_heads * 4096) { err = "shape mismatch for rel_bias"; return M0_ERR_INVALID; }
-                nparams_ += rb->data.size();
-                {   // stored pre-multiplied by log2(e): the attention kernel exponentiates with exp2
-                    std::vector<float> rbs((size_t)(P / 16) * 4096, 0.f);      // padded heads: zero bias
-                    for (size_t i = 0; i < rb->data.size(); ++i) rbs[i] = rb->data[i] * 1.44269504088896f;
-                    a.rel_bias = upload_f32(rbs);
-                }
-            }
+            TRY(pack_attn(att_[L.index], L.skip, p, err));
         }
     }
-    // attention visibility mask, resnet.py:104-130
-    {
-        std::vector<uint64_t> m(64, 0);
-        for (int i = 0; i < 64; ++i)
-            for (int j = 0; j < 64; ++j) {
-                int dr = i / 8 - j / 8, dc = i % 8 - j % 8;
-                int adr = abs(dr), adc = abs(dc);
-                bool vis = dr == 0 || dc == 0 || adr == adc || (adr == 2 && adc == 1) || (adr == 1 && adc == 2) ||
-                           (adr <= 1 && adc <= 1);
-                if (vis) m[i] |= (1ull << j);
-            }
-        mask_dev_ = (uint64_t*)dalloc(64 * 8, false);
-        (void)hipMemcpy(mask_dev_, m.data(), 64 * 8, hipMemcpyHostToDevice);
-    }
+    upload_attn_mask();
     // policy head
-    TRY(pack_gemm(ph_conv_, "policy_head.0.weight", "", 1, C_, Cp_, 64, 64, 0, err));
+    TRY(pack_gemm(ph_conv_, "policy_head.0.weight", "", 1, C, P, 64, 64, 0, err));
     TRY(upload_norm(ph_n_, "policy_head.1", 64, 64, err));
     if (cfg_.policy_factor_rank > 0) {
         int r = cfg_.policy_factor_rank, rp = ceil_to(r, 32);
@@ -389,54 +477,20 @@ int Net::finalize(std::string& err) {
         logit_scale_ = (float)std::min(5.0, sp + 1e-3);
     }
     // value head
-    TRY(pack_gemm(vh0_, "value_head.0.weight", "", 1, C_, Cp_, 128, 128, 0, err));
+    TRY(pack_gemm(vh0_, "value_head.0.weight", "", 1, C, P, 128, 128, 0, err));
     TRY(upload_norm(vh1_n_, "value_head.1", 128, 128, err));
     TRY(pack_gemm(vh3_, "value_head.3.weight", "", 1, 128, 128, 128, 128, 0, err));
     TRY(upload_norm(vh4_n_, "value_head.4", 128, 128, err));
-    {   // policy_head.0 (64 channels) and value_head.0 (128) read the same trunk: one GEMM with N = 192, columns [policy | value], both
-        // in the small-tile layout [Cin / 32][N][32]; GroupNorm parameters concatenated the same way
-        const int nch = Cp_ / 32;
-        std::vector<_Float16> a((size_t)nch * 64 * 32), b((size_t)nch * 128 * 32), c((size_t)nch * 192 * 32);
-        (void)hipMemcpy(a.data(), ph_conv_.w, a.size() * 2, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(b.data(), vh0_.w, b.size() * 2, hipMemcpyDeviceToHost);
-        for (int ch = 0; ch < nch; ++ch) {
-            std::copy(a.begin() + (size_t)ch * 64 * 32, a.begin() + (size_t)(ch + 1) * 64 * 32, c.begin() + (size_t)ch * 192 * 32);
-            std::copy(b.begin() + (size_t)ch * 128 * 32, b.begin() + (size_t)(ch + 1) * 128 * 32, c.begin() + ((size_t)ch * 192 + 64) * 32);
-        }
-        hv_.w = (_Float16*)dalloc(c.size() * 2, false);
-        if (!hv_.w) { err = "hipMalloc failed"; return M0_ERR_HIP; }
-        (void)hipMemcpy(hv_.w, c.data(), c.size() * 2, hipMemcpyHostToDevice);
-        hv_.taps = 1; hv_.Cin = Cp_; hv_.N = 192; hv_.pp = false; hv_.bias = nullptr;
-        std::vector<float> g(192), be(192);
-        (void)hipMemcpy(g.data(), ph_n_.gamma, 64 * 4, hipMemcpyDeviceToHost); (void)hipMemcpy(g.data() + 64, vh1_n_.gamma, 128 * 4, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(be.data(), ph_n_.beta, 64 * 4, hipMemcpyDeviceToHost); (void)hipMemcpy(be.data() + 64, vh1_n_.beta, 128 * 4, hipMemcpyDeviceToHost);
-        hv_n_.gamma = upload_f32(g); hv_n_.beta = upload_f32(be);
-        if (!hv_n_.gamma || !hv_n_.beta) { err = "hipMalloc failed"; return M0_ERR_HIP; }
-    }
-    {
-        int h1 = 2 * C, h1p = ceil_to(h1, 32), h2 = C, h2p = ceil_to(C, 32);
-        TRY(pack_gemm(vfc1_, "value_fc1.weight", "value_fc1.bias", 1, 8192, 8192, h1, h1p, 128, err));
-        TRY(pack_gemm(vfc2_, "value_fc2.weight", "value_fc2.bias", 1, h1, h1p, h2, h2p, 0, err));
-        TRY(pack_gemm(vgate_, "value_gate.0.weight", "value_gate.0.bias", 1, h2, h2p, h2, h2p, 0, err));
-        TRY(pack_gemm(vfc3_, "value_fc3.weight", "value_fc3.bias", 1, h2, h2p, 1, 32, 0, err));
-    }
-    // ssl heads
-    if (cfg_.self_supervised) {
-        for (int t = 0; t < 5; ++t) {
-            if (!(cfg_.ssl_tasks & (1 << t))) continue;
-            SslHeadW h;
-            h.task = kSslNames[t];
-            h.out_ch = kSslOut[t];
-            h.hidden = C / 2;
-            std::string p = std::string("ssl_heads.") + kSslNames[t];
-            TRY(pack_gemm(h.c0, p + ".0.weight", "", 1, C_, Cp_, C / 2, Cs_, 0, err));
-            TRY(upload_norm(h.n, p + ".1", C / 2, Cs_, err));
-            TRY(pack_gemm(h.c1, p + ".3.weight", "", 1, C / 2, Cs_, h.out_ch, 32, 0, err));
-            ssl_.push_back(h);
-        }
-    }
+    TRY(pack_joint_head(err));
+    const int h1 = 2 * C, h1p = ceil_to(h1, 32), h2 = C, h2p = ceil_to(C, 32);
+    TRY(pack_gemm(vfc1_, "value_fc1.weight", "value_fc1.bias", 1, 8192, 8192, h1, h1p, 128, err));
+    TRY(pack_gemm(vfc2_, "value_fc2.weight", "value_fc2.bias", 1, h1, h1p, h2, h2p, 0, err));
+    TRY(pack_gemm(vgate_, "value_gate.0.weight", "value_gate.0.bias", 1, h2, h2p, h2, h2p, 0, err));
+    TRY(pack_gemm(vfc3_, "value_fc3.weight", "value_fc3.bias", 1, h2, h2p, 1, 32, 0, err));
+    if (cfg_.self_supervised) TRY(pack_ssl_heads(err));
     sd_.clear();
     (void)hipDeviceSynchronize();       // uploads (blocking NULL-stream copies) have landed before any non-blocking stream reads them
+    make_plan();
     finalized_ = true;
     return M0_OK;
 }
@@ -486,7 +540,7 @@ int Net::ensure_workspace(int B, std::string& err) {
     X0_ = H(nb * 64 * 32);
     XA_ = H(nb * 64 * C); XB_ = H(nb * 64 * C); T1_ = H(nb * 64 * C); T2_ = H(nb * 64 * C); AA_ = H(nb * 64 * C);
     QKV_ = H(nb * 64 * 3 * C); O_ = H(nb * 64 * C);
-    SX_ = F(nb * Cst * 2); S1_ = F(nb * Cst * 2); S2_ = F(nb * Cst * 2); G_ = F(nb * Cst);
+    S1_ = F(nb * Cst * 2); S2_ = F(nb * Cst * 2); G_ = F(nb * Cst);
     PH_ = H(nh * 64 * 64); PH2_ = H(nh * 64 * 64);
     VH_ = H(nh * 64 * 128); VH2_ = H(nh * 64 * 128);
     const size_t rp = cfg_.policy_factor_rank > 0 ? ceil_to(cfg_.policy_factor_rank, 32) : 32;
@@ -495,7 +549,7 @@ int Net::ensure_workspace(int B, std::string& err) {
     SH_ = H(nb * 64 * Cs_); SH2_ = H(nb * 64 * Cs_); SO_ = H(nb * 64 * 32);
     VAL_ = F((size_t)Mfc * 32);
     SPK_ = F((size_t)8 * Mfc * ceil_to(2 * C_, 32));
-    if (!X0_ || !XA_ || !XB_ || !AA_ || !T1_ || !T2_ || !QKV_ || !O_ || !SX_ || !S1_ || !S2_ || !PH_ || !PH2_ || !VH_ ||
+    if (!X0_ || !XA_ || !XB_ || !AA_ || !T1_ || !T2_ || !QKV_ || !O_ || !S1_ || !S2_ || !PH_ || !PH2_ || !VH_ ||
         !VH2_ || !F1_ || !F2_ || !F3_ || !F4_ || !SH_ || !SH2_ || !SO_ || !VAL_ || !SPK_) {
         err = "workspace hipMalloc failed";
         wsB_ = wsM_ = 0;
@@ -512,75 +566,99 @@ int Net::ensure_workspace(int B, std::string& err) {
     return M0_OK;
 }
 
-hipError_t Net::run_gemm(const PackedGemm& g, const _Float16* in, void* out, int Mrows, int Mvalid,
-                         const NormParams* out_norm, int epi_act, const _Float16* mul, float* out_stats,
-                         bool out_f32, float out_scale, hipStream_t st) {
+// The arguments every conv / FC launch starts from; a call site then sets what is special about it, by field name.
+static GemmArgs gemm_args(const PackedGemm& g, const _Float16* in, void* out, int Mrows, int epi_act = ACT_NONE) {
     GemmArgs a;
     memset(&a, 0, sizeof(a));
-    a.in = in; a.w = g.w; a.out = out;
-    a.gn_gamma = out_norm ? out_norm->gamma : nullptr;
-    a.gn_beta = out_norm ? out_norm->beta : nullptr;
-    a.bias = g.bias; a.mul = mul; a.out_stats = out_stats;
-    a.Mrows = Mrows; a.Mvalid = Mvalid; a.Cin = g.Cin; a.N = g.N; a.Npad = g.N; a.ldo = g.N;
-    a.epi_act = epi_act; a.out_f32 = out_f32 ? 1 : 0; a.out_scale = out_scale; a.w_pp = g.pp ? 1 : 0;
-    const bool timed = profile_ && g.taps == 9 && conv_gemm_tile_n(g.Cin, g.N) == 320;
-    if (timed) {
-        if (pev_used_ + 2 > pev_.size()) {
-            for (int i = 0; i < 2; ++i) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return hipErrorOutOfMemory; pev_.push_back(e); }
-        }
-        (void)hipEventRecord(pev_[pev_used_], st);
+    a.in = in; a.w = g.w; a.out = out; a.bias = g.bias;
+    a.Mrows = Mrows; a.Mvalid = Mrows; a.Cin = g.Cin; a.N = g.N; a.Npad = g.N; a.ldo = g.N;
+    a.epi_act = epi_act; a.out_scale = 1.f; a.w_pp = g.pp ? 1 : 0;
+    return a;
+}
+
+// The same for ew_board_kernel: y = t, then whatever the call site names.
+static EwArgs ew_args(const _Float16* t, _Float16* y, int C, int act) {
+    EwArgs e;
+    memset(&e, 0, sizeof(e));
+    e.t = t; e.y = y; e.C = C; e.act = act;
+    return e;
+}
+static void ew_next_bn1(EwArgs& e, const NormParams* next_bn1, _Float16* y2) {
+    if (next_bn1) { e.y2 = y2; e.gn2_gamma = next_bn1->gamma; e.gn2_beta = next_bn1->beta; }
+}
+
+static double conv3x3_flop(const PackedGemm& g, int rows) { return 2.0 * (double)rows * (double)g.N * (double)g.Cin * 9.0; }
+
+template <class Launch>
+hipError_t Net::profiled(bool on, hipStream_t st, double flop, bool tail, Launch&& launch) {
+    if (!on) return launch();
+    if (pev_used_ + 2 > pev_.size()) {
+        for (int i = 0; i < 2; ++i) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return hipErrorOutOfMemory; pev_.push_back(e); }
     }
-    hipError_t rc;
+    (void)hipEventRecord(pev_[pev_used_], st);
+    hipError_t rc = launch();
+    (void)hipEventRecord(pev_[pev_used_ + 1], st);
+    pev_used_ += 2;
+    pflop_.push_back(flop);
+    ptail_.push_back(tail ? 1 : 0);
+    return rc;
+}
+
+hipError_t Net::run_gemm(const PackedGemm& g, GemmArgs a, hipStream_t st) {
+    const bool big = conv_gemm_tile_n(g.Cin, g.N) == 320;
     // a long-K 1x1 GEMM (value_fc1: K = 8192; 32 tiles on 256 CUs at 4096 boards): split K eight ways into fp32 partial
     // tiles, then a fixed-order reduction with the bias and the activation.  Taken at EVERY batch size: the summation order of a
     // board's value must not depend on how many other boards share the launch (tests/test_net_gpu.py: bitwise batch invariance up
     // to the 24 832 boards of a self-play pass); at large batches the partial tiles cost ~0.1 % of the forward.
-    const bool splitk = sw_.splitk && g.taps == 1 && conv_gemm_tile_n(g.Cin, g.N) == 320 && g.Cin >= 4096 &&
-                        (g.Cin >> 6) % 8 == 0 && !out_norm && !mul && !out_stats && !out_f32 && out_scale == 1.f && SPK_ != nullptr &&
-                        (size_t)g.N <= (size_t)ceil_to(2 * C_, 32) && Mrows <= wsM_;
-    if (splitk) {
+    const bool splitk = g.taps == 1 && big && g.Cin >= 4096 && (g.Cin >> 6) % 8 == 0 && !a.gn_gamma && !a.mul && !a.out_stats &&
+                        !a.out_f32 && a.out_scale == 1.f && SPK_ != nullptr && (size_t)g.N <= (size_t)ceil_to(2 * C_, 32) &&
+                        a.Mrows <= wsM_;
+    // the roofline profile counts the 3x3 big-tile convs launched from here (and the fused block tails, forward())
+    return profiled(profile_ && g.taps == 9 && big, st, conv3x3_flop(g, a.Mvalid), false, [&]() -> hipError_t {
+        if (!splitk) return launch_conv_gemm(a, g.taps, st);
+        _Float16* out = (_Float16*)a.out;
+        const int act = a.epi_act;
         a.out = SPK_; a.bias = nullptr; a.epi_act = ACT_NONE; a.out_f32 = 1; a.ksplit = 8;
-        rc = launch_conv_gemm(a, g.taps, st);
-        if (rc == hipSuccess) rc = launch_splitk_reduce(SPK_, 8, Mrows, g.N, g.bias, epi_act, (_Float16*)out, st);
-    } else {
-        rc = launch_conv_gemm(a, g.taps, st);
-    }
-    if (timed) {
-        (void)hipEventRecord(pev_[pev_used_ + 1], st);
-        pev_used_ += 2;
-        pflop_.push_back(2.0 * (double)Mvalid * (double)g.N * (double)g.Cin * 9.0);
-        ptail_.push_back(0);
-    }
-    return rc;
+        hipError_t rc = launch_conv_gemm(a, g.taps, st);
+        return rc != hipSuccess ? rc : launch_splitk_reduce(SPK_, 8, a.Mrows, g.N, g.bias, act, out, st);
+    });
 }
 
-hipError_t Net::run_conv_tail(const ResBlockW& r, const _Float16* in, const _Float16* x, _Float16* y,
-                              const NormParams* next_bn1, _Float16* y2, int act, int Mrows, hipStream_t st) {
-    const PackedGemm& g = r.conv2;
-    GemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.in = in; a.w = g.w; a.out = y;
-    a.Mrows = Mrows; a.Mvalid = Mrows; a.Cin = g.Cin; a.N = g.N; a.Npad = g.N; a.ldo = g.N;
-    a.epi_act = act; a.out_scale = 1.f; a.w_pp = g.pp ? 1 : 0;
-    a.res = x;
-    if (next_bn1 && y2) { a.y2 = y2; a.gn_gamma = next_bn1->gamma; a.gn_beta = next_bn1->beta; }
-    if (cfg_.se) { a.se_w1 = r.se_w1; a.se_b1 = r.se_b1; a.se_w2 = r.se_w2; a.se_b2 = r.se_b2; a.se_hidden = r.se_hidden;
-                   a.se_wf = r.se_wf; }
-    const bool timed = profile_;
-    if (timed) {
-        if (pev_used_ + 2 > pev_.size()) {
-            for (int i = 0; i < 2; ++i) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return hipErrorOutOfMemory; pev_.push_back(e); }
-        }
-        (void)hipEventRecord(pev_[pev_used_], st);
+hipError_t Net::se_gate(const ResBlockW& r, const float* stats, int boards, hipStream_t st) {
+    SeGateArgs g;
+    g.t_stats = stats; g.w1 = r.se_w1; g.b1 = r.se_b1; g.w2 = r.se_w2; g.b2 = r.se_b2;
+    g.gate = G_; g.B = boards; g.C = Cp_; g.hidden = r.se_hidden; g.act = plan_.act;
+    return launch_se_gate(g, st);
+}
+
+hipError_t Net::conv_norm_act(const PackedGemm& g, const NormParams& n, const _Float16* in, _Float16* out, _Float16* scratch,
+                              int Mrows, hipStream_t st, const ConvNormOpts& o) {
+    const bool big = conv_gemm_tile_n(g.Cin, g.N) == 320;
+    GemmArgs a = gemm_args(g, in, out, Mrows);
+    if (big && o.res && plan_.fuse_tail) {
+        // big tile, tail form: out = res + act(GroupNorm16(conv)), then the next block's GroupNorm + act into AA_.  Launched
+        // outside the roofline bracket: the profile's "tail" launches are the residual blocks' conv2 only.
+        a.epi_act = plan_.act; a.res = o.res; a.pre_gamma = n.gamma; a.pre_beta = n.beta;
+        if (o.next_bn1) { a.y2 = AA_; a.gn_gamma = o.next_bn1->gamma; a.gn_beta = o.next_bn1->beta; }
+        return launch_conv_gemm(a, g.taps, st);
     }
-    hipError_t rc = launch_conv_gemm(a, 9, st);
-    if (timed) {
-        (void)hipEventRecord(pev_[pev_used_ + 1], st);
-        pev_used_ += 2;
-        pflop_.push_back(2.0 * (double)Mrows * (double)g.N * (double)g.Cin * 9.0);
-        ptail_.push_back(1);
+    // GroupNorm + act (+ posenc) epilogues, neither with a residual nor a second output: conv_zs_kernel's (3x3 big tile), and
+    // conv_gemm_kernel's for a trunk that is a multiple of 64 wide: 3x3 over the stem's 32 input planes, 1x1 with all of
+    // N = 32 / 64 / 128 / 160 in one workgroup
+    const bool epilogue = big ? g.taps == 9
+                              : plan_.gn_small && (g.taps == 9 ? g.Cin == 32 : g.N == 32 || g.N == 64 || g.N == 128 || g.N == 160);
+    if (epilogue && !o.res && !o.next_bn1) {
+        a.gn_gamma = n.gamma; a.gn_beta = n.beta; a.epi_act = plan_.act; a.posenc = o.posenc;
+        return run_gemm(g, a, st);
     }
-    return rc;
+    // unfused: the raw conv with per-(board, channel) statistics, then ew_board_kernel
+    a.out = scratch; a.out_stats = S1_;
+    hipError_t rc = run_gemm(g, a, st);
+    if (rc != hipSuccess) return rc;
+    EwArgs e = ew_args(scratch, out, g.N, plan_.act);
+    e.t_stats = S1_; e.gn_gamma = n.gamma; e.gn_beta = n.beta; e.res = o.res; e.posenc = o.posenc;
+    ew_next_bn1(e, o.next_bn1, AA_);
+    return launch_ew_board(e, Mrows / 64, st);
 }
 
 void Net::harvest_profile() {
@@ -613,8 +691,7 @@ int Net::forward(const float* planes_dev, const _Float16* nhwc_dev, int B, float
     const int Bp = ceil_to(B, 4);
     const int Mc = Bp * 64;
     const int Mfc = ceil_to(B, 256);
-    const int act = cfg_.activation == M0_ACT_SILU ? ACT_SILU : ACT_RELU;
-    const int vact = cfg_.value_activation == M0_ACT_SILU ? ACT_SILU : (cfg_.value_activation == M0_ACT_LEAKY ? ACT_LEAKY : ACT_RELU);
+    const int act = plan_.act, vact = plan_.vact;
     const int C = Cp_;                 // in-memory trunk width
 
     const _Float16* x0 = nhwc_dev;
@@ -623,192 +700,121 @@ int Net::forward(const float* planes_dev, const _Float16* nhwc_dev, int B, float
         KCHK(launch_planes_to_nhwc(planes_dev, X0_, B, cfg_.planes, st));
         x0 = X0_;
     }
-    const bool big = conv_gemm_tile_n(C, C) == 320;     // fused GN epilogue available (C % 320 == 0)
-    // a squeeze-excite wider than the fused tail takes runs conv2 + se_gate + ew_board instead, as M0_FUSE_TAIL=0 does
-    const bool fuse_tail = big && C == 320 && sw_.fuse_tail &&
-                           (!cfg_.se || (res_[0].se_hidden <= TAIL_SE_HMAX && res_[0].se_hidden % 4 == 0));
-    const bool fuse_attn = C == 320 && sw_.fuse_attn;
-    // ew: elementwise glue; y2/gn2 = pre-activated input of the NEXT residual block (its bn1), or null
-    auto ew = [&](const _Float16* t, const float* tst, const NormParams* gn, const ResBlockW* se, const _Float16* res,
-                  const float* pos, const NormParams* ln, _Float16* y, float* ost, const NormParams* next_bn1,
-                  _Float16* y2, int Cc, int boards) -> hipError_t {
-        EwArgs e;
-        memset(&e, 0, sizeof(e));
-        e.t = t; e.t_stats = tst;
-        if (gn) { e.gn_gamma = gn->gamma; e.gn_beta = gn->beta; }
-        if (se) {
-            SeGateArgs g;
-            g.t_stats = tst; g.w1 = se->se_w1; g.b1 = se->se_b1; g.w2 = se->se_w2; g.b2 = se->se_b2;
-            g.gate = G_; g.B = boards; g.C = Cc; g.hidden = se->se_hidden; g.act = act;
-            hipError_t ge = launch_se_gate(g, st);
-            if (ge != hipSuccess) return ge;
-            e.gate = G_;
-        }
-        e.res = res; e.posenc = pos;
-        if (ln) { e.ln_g = ln->gamma; e.ln_b = ln->beta; e.ln_count = C_; }
-        e.y = y; e.out_stats = ost; e.C = Cc; e.act = act; e.stats_from_rounded = 0;
-        if (next_bn1 && y2) { e.y2 = y2; e.gn2_gamma = next_bn1->gamma; e.gn2_beta = next_bn1->beta; }
-        return launch_ew_board(e, boards, st);
-    };
-    // bn1 of the residual block that consumes the stream right after tower position `pos` (null if the
-    // next executed layer is attention or the tower ends there)
-    auto next_bn1_after = [&](size_t pos) -> const NormParams* {
-        for (size_t j = pos + 1; j < tower_.size(); ++j) {
-            if (tower_[j].kind == 1) { if (tower_[j].skip) continue; return nullptr; }
-            return &res_[tower_[j].index].bn1;
-        }
-        return nullptr;
-    };
-    const NormParams* first_bn1 = nullptr;
-    for (size_t j = 0; j < tower_.size(); ++j) {
-        if (tower_[j].kind == 1) { if (tower_[j].skip) continue; break; }
-        first_bn1 = &res_[tower_[j].index].bn1; break;
-    }
-
-    // stem (resnet.py:314-318) + chess features (229-244)
-    // fused small kernels (round 4): GroupNorm + activation (+ positional encoding) in the conv's own epilogue
-    const bool fuse_small = sw_.fuse_small && C % 64 == 0 && (act == ACT_SILU || act == ACT_RELU);
-    auto gn_gemm = [&](const PackedGemm& g, int taps, const _Float16* in, _Float16* out, int ldo, const NormParams& n, const float* pos,
-                       _Float16* out2, int ldo2, int nsplit) -> hipError_t {
-        GemmArgs ga;
-        memset(&ga, 0, sizeof(ga));
-        ga.in = in; ga.w = g.w; ga.out = out; ga.gn_gamma = n.gamma; ga.gn_beta = n.beta; ga.posenc = pos;
-        ga.Mrows = Mc; ga.Mvalid = Mc; ga.Cin = g.Cin; ga.N = g.N; ga.Npad = g.N; ga.ldo = ldo; ga.epi_act = act; ga.out_scale = 1.f;
-        ga.out2 = out2; ga.ldo2 = ldo2; ga.nsplit = nsplit;
-        return launch_conv_gemm(ga, taps, st);
-    };
+    // The residual stream alternates between xa (current) and xb; AA_ holds act(bn1(stream)) for the next residual block's
+    // conv1, written by whichever step wrote the stream (next_bn1).
     _Float16* xa = XA_;
     _Float16* xb = XB_;
-    if (!(fuse_small && cfg_.chess_features)) KCHK(run_gemm(stem_, x0, T1_, Mc, Mc, nullptr, 0, nullptr, S1_, false, 1.f, st));
+    const NormParams* first_bn1 = bn1(plan_.first_bn1);
+    // stem (resnet.py:314-318) + chess features (229-244)
+    ConvNormOpts so;
+    if (cfg_.chess_features) so.posenc = posenc_; else so.next_bn1 = first_bn1;
+    KCHK(conv_norm_act(stem_, stem_n_, x0, xa, T1_, Mc, st, so));
     if (cfg_.chess_features) {
-        if (fuse_small) KCHK(gn_gemm(stem_, 9, x0, xa, C, stem_n_, posenc_, nullptr, 0, 0));
-        else KCHK(ew(T1_, S1_, &stem_n_, nullptr, nullptr, posenc_, nullptr, xa, nullptr, nullptr, nullptr, C, Bp));
         if (cfg_.piece_square_tables) {
-            if (fuse_tail) {
-                // piece-square-table 1x1 conv + GroupNorm/act + residual add in one kernel
-                GemmArgs pa;
-                memset(&pa, 0, sizeof(pa));
-                pa.in = xa; pa.w = pst_.w; pa.out = xb;
-                pa.Mrows = Mc; pa.Mvalid = Mc; pa.Cin = pst_.Cin; pa.N = pst_.N; pa.Npad = pst_.N; pa.ldo = pst_.N;
-                pa.epi_act = act; pa.out_scale = 1.f;
-                pa.res = xa; pa.pre_gamma = pst_n_.gamma; pa.pre_beta = pst_n_.beta;
-                KCHK(launch_conv_gemm(pa, 1, st));
-            } else {
-                KCHK(run_gemm(pst_, xa, T1_, Mc, Mc, nullptr, 0, nullptr, S1_, false, 1.f, st));
-                KCHK(ew(T1_, S1_, &pst_n_, nullptr, xa, nullptr, nullptr, xb, nullptr, nullptr, nullptr, C, Bp));
-            }
+            ConvNormOpts po;
+            po.res = xa;
+            KCHK(conv_norm_act(pst_, pst_n_, xa, xb, T1_, Mc, st, po));
             std::swap(xa, xb);
         }
-        if (fuse_tail) {
-            // interaction conv + GroupNorm/act + residual add + the first block's GroupNorm/act in one kernel
-            GemmArgs ia;
-            memset(&ia, 0, sizeof(ia));
-            ia.in = xa; ia.w = inter_.w; ia.out = xb;
-            ia.Mrows = Mc; ia.Mvalid = Mc; ia.Cin = inter_.Cin; ia.N = inter_.N; ia.Npad = inter_.N; ia.ldo = inter_.N;
-            ia.epi_act = act; ia.out_scale = 1.f; ia.w_pp = inter_.pp ? 1 : 0;
-            ia.res = xa; ia.pre_gamma = inter_n_.gamma; ia.pre_beta = inter_n_.beta;
-            if (first_bn1) { ia.y2 = AA_; ia.gn_gamma = first_bn1->gamma; ia.gn_beta = first_bn1->beta; }
-            KCHK(launch_conv_gemm(ia, 9, st));
-        } else {
-            KCHK(run_gemm(inter_, xa, T1_, Mc, Mc, nullptr, 0, nullptr, S1_, false, 1.f, st));
-            KCHK(ew(T1_, S1_, &inter_n_, nullptr, xa, nullptr, nullptr, xb, nullptr, first_bn1, AA_, C, Bp));
-        }
+        ConvNormOpts io;
+        io.res = xa; io.next_bn1 = first_bn1;
+        KCHK(conv_norm_act(inter_, inter_n_, xa, xb, T1_, Mc, st, io));
         std::swap(xa, xb);
-    } else {
-        KCHK(ew(T1_, S1_, &stem_n_, nullptr, nullptr, nullptr, nullptr, xa, nullptr, first_bn1, AA_, C, Bp));
     }
     // tower
-    for (size_t li = 0; li < tower_.size(); ++li) {
-        const TowerLayer& L = tower_[li];
+    for (const TowerLayer& L : tower_) {
+        const NormParams* next_bn1 = bn1(L.next_bn1);
         if (L.kind == 0) {
             const ResBlockW& r = res_[L.index];
-            // pre-activation block (resnet.py:45-51): AA_ = act(GN1(x)) comes from the previous ew; conv1's
-            // epilogue applies GN2+act in registers (big tile) so conv2 also reads a ready operand
-            if (big) {
-                KCHK(run_gemm(r.conv1, AA_, T1_, Mc, Mc, &r.bn2, act, nullptr, nullptr, false, 1.f, st));
-            } else {
-                KCHK(run_gemm(r.conv1, AA_, T2_, Mc, Mc, nullptr, 0, nullptr, S1_, false, 1.f, st));
-                KCHK(ew(T2_, S1_, &r.bn2, nullptr, nullptr, nullptr, nullptr, T1_, nullptr, nullptr, nullptr, C, Bp));
-            }
-            if (fuse_tail) {
+            // pre-activation block (resnet.py:45-51): conv1 reads AA_ = act(bn1(x)) and leaves T1_ = act(bn2(conv1)), so conv2
+            // also reads a ready operand
+            KCHK(conv_norm_act(r.conv1, r.bn2, AA_, T1_, T2_, Mc, st));
+            if (plan_.fuse_tail) {
                 // conv2 + squeeze-excite + residual add + the next block's GroupNorm/activation in one kernel
-                KCHK(run_conv_tail(r, T1_, xa, xb, next_bn1_after(li), AA_, act, Mc, st));
+                GemmArgs a = gemm_args(r.conv2, T1_, xb, Mc, act);
+                a.res = xa;
+                if (next_bn1) { a.y2 = AA_; a.gn_gamma = next_bn1->gamma; a.gn_beta = next_bn1->beta; }
+                if (cfg_.se) { a.se_w1 = r.se_w1; a.se_b1 = r.se_b1; a.se_w2 = r.se_w2; a.se_b2 = r.se_b2; a.se_hidden = r.se_hidden;
+                               a.se_wf = r.se_wf; }
+                KCHK(profiled(profile_, st, conv3x3_flop(r.conv2, Mc), true, [&] { return launch_conv_gemm(a, 9, st); }));
             } else {
-                KCHK(run_gemm(r.conv2, T1_, T2_, Mc, Mc, nullptr, 0, nullptr, S2_, false, 1.f, st));
-                KCHK(ew(T2_, S2_, nullptr, cfg_.se ? &r : nullptr, xa, nullptr, nullptr, xb, nullptr, next_bn1_after(li), AA_, C, Bp));
+                GemmArgs a = gemm_args(r.conv2, T1_, T2_, Mc);
+                a.out_stats = S2_;
+                KCHK(run_gemm(r.conv2, a, st));
+                EwArgs e = ew_args(T2_, xb, C, act);
+                e.t_stats = S2_; e.res = xa;
+                if (cfg_.se) { KCHK(se_gate(r, S2_, Bp, st)); e.gate = G_; }
+                ew_next_bn1(e, next_bn1, AA_);
+                KCHK(launch_ew_board(e, Bp, st));
             }
-            std::swap(xa, xb);
         } else {
             if (L.skip) continue;
             const AttnW& w = att_[L.index];
-            if (fuse_attn && w.blk_w != nullptr) {
+            const float inv_sqrt_d = 1.f / sqrtf((float)(C_ / cfg_.attention_heads));
+            if (plan_.fuse_attn && w.blk_w != nullptr) {
                 // the whole block (qkv, attention, proj, residual, LayerNorm, next block's GroupNorm/act) in one kernel
                 AttnBlockArgs ab;
                 memset(&ab, 0, sizeof(ab));
                 ab.x = xa; ab.wpack = w.blk_w; ab.bias = w.blk_bias; ab.mask = mask_dev_;
                 ab.ln_g = w.ln.gamma; ab.ln_b = w.ln.beta; ab.y = xb;
-                if (const NormParams* nb = next_bn1_after(li)) {
-                    ab.y2 = AA_; ab.gn2_gamma = nb->gamma; ab.gn2_beta = nb->beta;
-                }
-                ab.B = Bp; ab.ln_count = C_; ab.act = act; ab.mix = cfg_.attention_unmasked_mix;
-                ab.inv_sqrt_d = 1.f / sqrtf((float)(C_ / cfg_.attention_heads));
+                if (next_bn1) { ab.y2 = AA_; ab.gn2_gamma = next_bn1->gamma; ab.gn2_beta = next_bn1->beta; }
+                ab.B = Bp; ab.ln_count = C_; ab.act = act; ab.mix = cfg_.attention_unmasked_mix; ab.inv_sqrt_d = inv_sqrt_d;
                 KCHK(launch_attn_block(ab, st));
-                std::swap(xa, xb);
-                continue;
+            } else {
+                KCHK(run_gemm(w.qkv, gemm_args(w.qkv, xa, QKV_, Mc), st));
+                AttnArgs aa;
+                aa.qkv = QKV_; aa.rel_bias = w.rel_bias; aa.mask = mask_dev_; aa.o = O_;
+                aa.B = Bp; aa.H = C / 16; aa.C = C; aa.mix = cfg_.attention_unmasked_mix;      // head_dim 16; padded heads are all-zero
+                aa.inv_sqrt_d = inv_sqrt_d;
+                KCHK(launch_attn_core(aa, st));
+                KCHK(run_gemm(w.proj, gemm_args(w.proj, O_, T1_, Mc), st));
+                EwArgs e = ew_args(T1_, xb, C, act);
+                e.res = xa; e.ln_g = w.ln.gamma; e.ln_b = w.ln.beta; e.ln_count = C_;
+                ew_next_bn1(e, next_bn1, AA_);
+                KCHK(launch_ew_board(e, Bp, st));
             }
-            KCHK(run_gemm(w.qkv, xa, QKV_, Mc, Mc, nullptr, 0, nullptr, nullptr, false, 1.f, st));
-            AttnArgs aa;
-            aa.qkv = QKV_; aa.rel_bias = w.rel_bias; aa.mask = mask_dev_; aa.o = O_;
-            aa.B = Bp; aa.H = C / 16; aa.C = C; aa.mix = cfg_.attention_unmasked_mix;      // head_dim 16; padded heads are all-zero
-            aa.inv_sqrt_d = 1.f / sqrtf((float)(C_ / cfg_.attention_heads));
-            KCHK(launch_attn_core(aa, st));
-            KCHK(run_gemm(w.proj, O_, T1_, Mc, Mc, nullptr, 0, nullptr, nullptr, false, 1.f, st));
-            KCHK(ew(T1_, nullptr, nullptr, nullptr, xa, nullptr, &w.ln, xb, nullptr, next_bn1_after(li), AA_, C, Bp));
-            std::swap(xa, xb);
         }
+        std::swap(xa, xb);
     }
-    // policy head (resnet.py:699-711); fused: its conv and the value head's first conv read the trunk ONCE, GroupNorm + activation in
-    // the epilogue (PH2_ <- policy, VH2_ <- value)
-    if (fuse_small) KCHK(gn_gemm(hv_, 1, xa, PH2_, 64, hv_n_, nullptr, VH2_, 128, 64));
-    else {
-        KCHK(run_gemm(ph_conv_, xa, PH_, Mc, Mc, nullptr, 0, nullptr, S1_, false, 1.f, st));
-        KCHK(ew(PH_, S1_, &ph_n_, nullptr, nullptr, nullptr, nullptr, PH2_, nullptr, nullptr, nullptr, 64, Bp));
-    }
-    if (cfg_.policy_factor_rank > 0) {
-        KCHK(run_gemm(pfc1_, PH2_, F1_, Mfc, Mfc, nullptr, ACT_RELU, nullptr, nullptr, false, 1.f, st));
-        KCHK(run_gemm(pfc2_, F1_, logits_dev, Mfc, B, nullptr, 0, nullptr, nullptr, true, logit_scale_, st));
+    // policy head (resnet.py:699-711).  Its first conv and the value head's read the same trunk: where the small-tile GroupNorm
+    // epilogue is in use they are ONE launch over the joint weights hv_ (PH2_ <- policy columns, VH2_ <- value columns), the
+    // fused form of the two conv_norm_act steps below.
+    const bool joint = plan_.gn_small;
+    if (joint) {
+        GemmArgs a = gemm_args(hv_, xa, PH2_, Mc, act);
+        a.gn_gamma = hv_n_.gamma; a.gn_beta = hv_n_.beta;
+        a.ldo = 64; a.out2 = VH2_; a.ldo2 = 128; a.nsplit = 64;
+        KCHK(launch_conv_gemm(a, 1, st));
     } else {
-        KCHK(run_gemm(pfc1_, PH2_, logits_dev, Mfc, B, nullptr, 0, nullptr, nullptr, true, logit_scale_, st));
+        KCHK(conv_norm_act(ph_conv_, ph_n_, xa, PH2_, PH_, Mc, st));
     }
+    const bool factored = cfg_.policy_factor_rank > 0;
+    if (factored) KCHK(run_gemm(pfc1_, gemm_args(pfc1_, PH2_, F1_, Mfc, ACT_RELU), st));
+    const PackedGemm& plast = factored ? pfc2_ : pfc1_;
+    GemmArgs pl = gemm_args(plast, factored ? F1_ : PH2_, logits_dev, Mfc);
+    pl.Mvalid = B; pl.out_f32 = 1; pl.out_scale = logit_scale_;
+    KCHK(run_gemm(plast, pl, st));
     // value head (resnet.py:721-734)
-    const _Float16* vflat = VH2_;
-    if (fuse_small) {
-        KCHK(gn_gemm(vh3_, 1, VH2_, VH_, 128, vh4_n_, nullptr, nullptr, 0, 0));
-        vflat = VH_;
-    } else {
-        KCHK(run_gemm(vh0_, xa, VH_, Mc, Mc, nullptr, 0, nullptr, S1_, false, 1.f, st));
-        KCHK(ew(VH_, S1_, &vh1_n_, nullptr, nullptr, nullptr, nullptr, VH2_, nullptr, nullptr, nullptr, 128, Bp));
-        KCHK(run_gemm(vh3_, VH2_, VH_, Mc, Mc, nullptr, 0, nullptr, S1_, false, 1.f, st));
-        KCHK(ew(VH_, S1_, &vh4_n_, nullptr, nullptr, nullptr, nullptr, VH2_, nullptr, nullptr, nullptr, 128, Bp));
-    }
-    KCHK(run_gemm(vfc1_, vflat, F2_, Mfc, Mfc, nullptr, vact, nullptr, nullptr, false, 1.f, st));
-    KCHK(run_gemm(vfc2_, F2_, F3_, Mfc, Mfc, nullptr, vact, nullptr, nullptr, false, 1.f, st));
-    KCHK(run_gemm(vgate_, F3_, F4_, Mfc, Mfc, nullptr, ACT_SIGMOID, F3_, nullptr, false, 1.f, st));
-    KCHK(run_gemm(vfc3_, F4_, VAL_, Mfc, Mfc, nullptr, ACT_TANH, nullptr, nullptr, true, 1.f, st));
+    if (!joint) KCHK(conv_norm_act(vh0_, vh1_n_, xa, VH2_, VH_, Mc, st));
+    // value_head.3 reads VH2_: its epilogue form writes VH_, the unfused form passes through VH_ and lands in VH2_ again
+    _Float16* vflat = joint ? VH_ : VH2_;
+    KCHK(conv_norm_act(vh3_, vh4_n_, VH2_, vflat, VH_, Mc, st));
+    KCHK(run_gemm(vfc1_, gemm_args(vfc1_, vflat, F2_, Mfc, vact), st));
+    KCHK(run_gemm(vfc2_, gemm_args(vfc2_, F2_, F3_, Mfc, vact), st));
+    GemmArgs vg = gemm_args(vgate_, F3_, F4_, Mfc, ACT_SIGMOID);
+    vg.mul = F3_;
+    KCHK(run_gemm(vgate_, vg, st));
+    GemmArgs v3 = gemm_args(vfc3_, F4_, VAL_, Mfc, ACT_TANH);
+    v3.out_f32 = 1;
+    KCHK(run_gemm(vfc3_, v3, st));
     KCHK(hipMemcpy2DAsync(value_dev, 4, VAL_, 32 * 4, 4, B, hipMemcpyDeviceToDevice, st));
     // ssl heads (resnet.py:738-745)
     if (ssl_dev && !ssl_.empty()) {
         const int ctot = ssl_channels_total();
         int coff = 0;
-        const bool ssl_fused = fuse_small && (Cs_ == 160 || Cs_ == 128 || Cs_ == 64 || Cs_ == 32);
         for (auto& h : ssl_) {
-            if (ssl_fused) {        // the head's first conv with GroupNorm + activation in its epilogue, all its channels in one workgroup
-                KCHK(gn_gemm(h.c0, 1, xa, SH2_, Cs_, h.n, nullptr, nullptr, 0, 0));
-            } else {
-                KCHK(run_gemm(h.c0, xa, SH_, Mc, Mc, nullptr, 0, nullptr, S1_, false, 1.f, st));
-                KCHK(ew(SH_, S1_, &h.n, nullptr, nullptr, nullptr, nullptr, SH2_, nullptr, nullptr, nullptr, Cs_, Bp));
-            }
-            KCHK(run_gemm(h.c1, SH2_, SO_, Mc, Mc, nullptr, 0, nullptr, nullptr, false, 1.f, st));
+            KCHK(conv_norm_act(h.c0, h.n, xa, SH2_, SH_, Mc, st));
+            KCHK(run_gemm(h.c1, gemm_args(h.c1, SH2_, SO_, Mc), st));
             KCHK(launch_nhwc_to_nchw_f32(SO_, ssl_dev, B, 32, h.out_ch, ctot, coff, st));
             coff += h.out_ch;
         }

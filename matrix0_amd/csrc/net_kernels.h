@@ -69,7 +69,6 @@ struct EwArgs {
     const float* gn2_beta;
     int C;
     int act;
-    int stats_from_rounded;
 };
 
 struct SeGateArgs {
