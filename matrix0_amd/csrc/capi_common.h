@@ -13,3 +13,6 @@ int m0_net_device(m0_net* n);
 // the workspace and the stream belong to the handle.
 void m0_net_lock(m0_net* n);
 void m0_net_unlock(m0_net* n);
+// A non-blocking stream; when the environment variable env_name holds w0,w1,...,w7 (hex words, bit b = CU b in the driver's
+// numbering) the stream runs on those CUs only (hipExtStreamCreateWithCUMask).  Measurement switch; read at every call.
+hipError_t create_stream_cu_mask_env(const char* env_name, hipStream_t* stream);

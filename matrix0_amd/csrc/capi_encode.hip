@@ -1,0 +1,153 @@
+// extern "C" device hooks that take FEN strings and need no engine (include/m0_engine.h): encoding.py on the device and the
+// SSL target maps.
+#include <hip/hip_runtime.h>
+#include <string.h>
+#include <string>
+#include <vector>
+#include "../../include/m0_engine.h"
+#include "capi_common.h"
+#include "chess_core.h"
+#include "tree.h"
+
+using namespace m0;
+
+namespace {
+
+// device memory for the length of one call
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    DevBuf() {}
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    bool alloc(size_t count) { return hipMalloc((void**)&p, count * sizeof(T)) == hipSuccess; }
+    void download(T* host, size_t count) const { (void)hipMemcpy(host, p, count * sizeof(T), hipMemcpyDeviceToHost); }
+};
+
+// selects the device, parses the n FENs and puts the positions on it
+int upload_fens(int hip_device, const char* const* fens, int n, DevBuf<Pos>& dp) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { m0_set_error("no HIP device available (no CPU fallback)"); return M0_ERR_HIP; }
+    if (hipSetDevice(hip_device) != hipSuccess) { m0_set_error("hipSetDevice failed"); return M0_ERR_HIP; }
+    std::vector<Pos> hp(n);
+    for (int i = 0; i < n; ++i)
+        if (!fens[i] || parse_fen(fens[i], hp[i]) != 0) { m0_set_error(std::string("bad FEN at index ") + std::to_string(i)); return M0_ERR_INVALID; }
+    if (!dp.alloc(n)) { m0_set_error("hipMalloc failed"); return M0_ERR_HIP; }
+    (void)hipMemcpy(dp.p, hp.data(), sizeof(Pos) * n, hipMemcpyHostToDevice);
+    return M0_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int m0_encode_fens(int hip_device, const char* const* fens, int n, float* planes, uint8_t* mask, int32_t* nlegal,
+                   uint16_t* moves, int32_t* idx) {
+    if (!fens || n <= 0) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
+    DevBuf<Pos> dp;
+    const int rc = upload_fens(hip_device, fens, n, dp);
+    if (rc != M0_OK) return rc;
+    const size_t N = (size_t)n;
+    DevBuf<float> dpl; DevBuf<uint8_t> dm; DevBuf<int32_t> dn; DevBuf<uint16_t> dmv; DevBuf<int32_t> di;
+    if ((planes && !dpl.alloc(N * 19 * 64)) || (mask && !dm.alloc(N * 4672)) || (nlegal && !dn.alloc(N)) ||
+        (moves && !dmv.alloc(N * M0_MAX_MOVES)) || (idx && !di.alloc(N * M0_MAX_MOVES))) { m0_set_error("hipMalloc failed"); return M0_ERR_HIP; }
+    if (launch_encode_positions(dp.p, n, dpl.p, nullptr, dm.p, dn.p, dmv.p, di.p, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        m0_set_error("encode kernel failed");
+        return M0_ERR_HIP;
+    }
+    if (planes) dpl.download(planes, N * 19 * 64);
+    if (mask) dm.download(mask, N * 4672);
+    if (nlegal) dn.download(nlegal, N);
+    if (moves) dmv.download(moves, N * M0_MAX_MOVES);
+    if (idx) di.download(idx, N * M0_MAX_MOVES);
+    return M0_OK;
+}
+
+int m0_encode_fens_nhwc(int hip_device, const char* const* fens, int n, uint16_t* out) {
+    if (!fens || n <= 0 || !out) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
+    DevBuf<Pos> dp;
+    const int rc = upload_fens(hip_device, fens, n, dp);
+    if (rc != M0_OK) return rc;
+    DevBuf<_Float16> dx;
+    if (!dx.alloc((size_t)n * 64 * 32)) { m0_set_error("hipMalloc failed"); return M0_ERR_HIP; }
+    if (launch_encode_positions(dp.p, n, nullptr, dx.p, nullptr, nullptr, nullptr, nullptr, nullptr) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) { m0_set_error("encode kernel failed"); return M0_ERR_HIP; }
+    dx.download((_Float16*)out, (size_t)n * 64 * 32);
+    return M0_OK;
+}
+
+int m0_ssl_targets_fens(int hip_device, const char* const* fens, int n, float* out) {
+    if (!fens || n <= 0 || !out) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
+    DevBuf<Pos> dp;
+    const int rc = upload_fens(hip_device, fens, n, dp);
+    if (rc != M0_OK) return rc;
+    DevBuf<float> dout;
+    if (!dout.alloc((size_t)n * 17 * 64)) { m0_set_error("hipMalloc failed"); return M0_ERR_HIP; }
+    if (launch_ssl_targets(dp.p, n, dout.p, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { m0_set_error("ssl kernel failed"); return M0_ERR_HIP; }
+    dout.download(out, (size_t)n * 17 * 64);
+    return M0_OK;
+}
+
+int m0_move_to_index_fen(int hip_device, const char* fen, const char* uci, int32_t* out) {
+    if (!fen || !uci || !out) { m0_set_error("null argument"); return M0_ERR_INVALID; }
+    const Move want = parse_uci(uci);
+    if (want == 0xFFFF) { m0_set_error(std::string("Illegal move: ") + uci); return M0_ERR_INVALID; }
+    std::vector<uint16_t> mv(M0_MAX_MOVES);
+    std::vector<int32_t> id(M0_MAX_MOVES);
+    int32_t n = 0;
+    const char* fens[1] = {fen};
+    int rc = m0_encode_fens(hip_device, fens, 1, nullptr, nullptr, &n, mv.data(), id.data());
+    if (rc != M0_OK) return rc;
+    for (int i = 0; i < n; ++i)
+        if (mv[i] == want) { *out = id[i]; return M0_OK; }
+    m0_set_error(std::string("Illegal move: ") + uci);     // encoding.py:120-121 raises ValueError
+    return M0_ERR_INVALID;
+}
+
+int m0_decode_move_fen(int hip_device, const char* fen, int action_idx, char* uci_out) {
+    if (!fen || !uci_out) { m0_set_error("null argument"); return M0_ERR_INVALID; }
+    if (action_idx < 0 || action_idx >= M0_POLICY_SIZE) { m0_set_error("action_idx out of range"); return M0_ERR_INVALID; }
+    Pos p;
+    if (parse_fen(fen, p) != 0) { m0_set_error("bad FEN"); return M0_ERR_INVALID; }
+    std::vector<uint16_t> mv(M0_MAX_MOVES);
+    int32_t n = 0;
+    const char* fens[1] = {fen};
+    int rc = m0_encode_fens(hip_device, fens, 1, nullptr, nullptr, &n, mv.data(), nullptr);   // legal moves from the device
+    if (rc != M0_OK) return rc;
+    static const int RAY[8][2] = {{1, 0}, {-1, 0}, {0, 1}, {0, -1}, {1, 1}, {1, -1}, {-1, 1}, {-1, -1}};
+    static const int KN[8][2] = {{-2, -1}, {-2, 1}, {-1, -2}, {-1, 2}, {1, -2}, {1, 2}, {2, -1}, {2, 1}};
+    const int from = action_idx / 73, off = action_idx % 73;
+    const int fr = from >> 3, ff = from & 7;
+    int dr, df, steps = 1, promo = 0;
+    bool under = false;
+    if (off < 56) { dr = RAY[off / 7][0]; df = RAY[off / 7][1]; steps = off % 7 + 1; }
+    else if (off < 64) { dr = KN[off - 56][0]; df = KN[off - 56][1]; }
+    else {
+        const int u = off - 64, d = u % 3;
+        static const int DW[3][2] = {{1, 0}, {1, -1}, {1, 1}}, DB[3][2] = {{-1, 0}, {-1, 1}, {-1, -1}};
+        dr = p.turn == WHITE ? DW[d][0] : DB[d][0]; df = p.turn == WHITE ? DW[d][1] : DB[d][1];
+        promo = u / 3 + 1; under = true;
+    }
+    const int tr = fr + dr * steps, tf = ff + df * steps;
+    int to = -1;
+    Move want = 0xFFFF;
+    if (tr >= 0 && tr < 8 && tf >= 0 && tf < 8) {
+        to = tr * 8 + tf;
+        if (!under && piece_type_at(p, from) == PAWN && (p.occ[0] | p.occ[1]) & bit(from) && (tr == 0 || tr == 7)) promo = 4;
+        want = mk_move(from, to, promo);
+    }
+    Move pick = 0xFFFF;
+    for (int i = 0; i < n && pick == 0xFFFF; ++i) if (mv[i] == want) pick = mv[i];
+    if (to >= 0) for (int i = 0; i < n && pick == 0xFFFF; ++i) if (mv_from(mv[i]) == from && mv_to(mv[i]) == to) pick = mv[i];
+    if (to < 0) for (int i = 0; i < n && pick == 0xFFFF; ++i) if (mv_from(mv[i]) == from && mv_to(mv[i]) == 0) pick = mv[i];   // null move target a1 (python Move.null().to_square == 0)
+    for (int i = 0; i < n && pick == 0xFFFF; ++i) if (mv_from(mv[i]) == from) pick = mv[i];
+    if (pick == 0xFFFF) { strcpy(uci_out, "0000"); return M0_OK; }
+    const int f = mv_from(pick), t = mv_to(pick), pr = mv_promo(pick);
+    uci_out[0] = (char)('a' + (f & 7)); uci_out[1] = (char)('1' + (f >> 3));
+    uci_out[2] = (char)('a' + (t & 7)); uci_out[3] = (char)('1' + (t >> 3));
+    uci_out[4] = pr ? " nbrq"[pr] : '\0'; uci_out[5] = '\0';
+    return M0_OK;
+}
+
+}  // extern "C"

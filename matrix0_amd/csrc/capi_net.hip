@@ -32,6 +32,20 @@ int m0_net_device(m0_net* n) { return n ? n->device : 0; }
 void m0_net_lock(m0_net* n) { if (n) n->mu.lock(); }
 void m0_net_unlock(m0_net* n) { if (n) n->mu.unlock(); }
 
+hipError_t create_stream_cu_mask_env(const char* env_name, hipStream_t* stream) {
+    const char* mk = getenv(env_name);
+    if (!mk || !*mk) return hipStreamCreateWithFlags(stream, hipStreamNonBlocking);
+    uint32_t words[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int nw = 0;
+    for (const char* q = mk; *q && nw < 8; ++nw) {
+        char* end = nullptr;
+        words[nw] = (uint32_t)strtoul(q, &end, 16);
+        if (end == q) break;
+        q = (*end == ',') ? end + 1 : end;
+    }
+    return hipExtStreamCreateWithCUMask(stream, 8, words);
+}
+
 extern "C" {
 
 const char* m0_last_error(void) { return g_m0_last_error.c_str(); }
@@ -55,23 +69,9 @@ m0_net* m0_net_create(const m0_net_cfg* cfg, int hip_device) {
     if (hipSetDevice(hip_device) != hipSuccess) { m0_set_error("hipSetDevice failed"); return nullptr; }
     m0_net* h = new m0_net();
     h->device = hip_device;
-    // M0_NET_CU_MASK=w0,w1,...,w7 (hex words, bit b = CU b in the driver's numbering): the network's stream runs on those CUs
-    // only (hipExtStreamCreateWithCUMask).  Measurement switch of tools/exp_cumask.py (two networks on complementary halves
-    // of the chip); read at creation, so two networks of one process can get different masks.
-    hipError_t se;
-    if (const char* mk = getenv("M0_NET_CU_MASK"); mk && *mk) {
-        uint32_t words[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        int nw = 0;
-        for (const char* q = mk; *q && nw < 8; ++nw) {
-            char* end = nullptr;
-            words[nw] = (uint32_t)strtoul(q, &end, 16);
-            if (end == q) break;
-            q = (*end == ',') ? end + 1 : end;
-        }
-        se = hipExtStreamCreateWithCUMask(&h->stream, 8, words);
-    } else {
-        se = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    }
+    // M0_NET_CU_MASK: the network's stream runs on those CUs only.  Measurement switch of tools/exp_cumask.py (two networks on
+    // complementary halves of the chip); read at creation, so two networks of one process can get different masks.
+    const hipError_t se = create_stream_cu_mask_env("M0_NET_CU_MASK", &h->stream);
     if (se != hipSuccess) {
         m0_set_error("hipStreamCreate failed");
         delete h;

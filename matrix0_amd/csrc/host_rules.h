@@ -60,6 +60,28 @@ struct RepWindow {
     }
 };
 
+constexpr const char* START_FEN = "rnbqkbnr/pppppppp/8/8/8/8/PPPPPPPP/RNBQKBNR w KQkq - 0 1";
+
+// A game as the host follows it: the position, its repetition window and every move played.
+struct Line {
+    Pos pos;
+    RepWindow win;
+    std::vector<Move> history;
+    void play(Move m) {
+        win.push(pos, m);
+        make_move(pos, m);
+        history.push_back(m);
+    }
+    // Plays m only when it is legal.  legal[0..n) are the legal moves of the position BEFORE the move, either way.
+    bool play_if_legal(Move m, Move* legal, int& n) {
+        n = gen_legal(pos, legal);
+        bool ok = false;
+        for (int j = 0; j < n; ++j) if (legal[j] == m) ok = true;
+        if (ok) play(m);
+        return ok;
+    }
+};
+
 inline bool is_fifty(const Pos& p) { return p.halfmove >= 100 && any_legal(p); }
 inline bool can_claim_fifty(const Pos& p) {
     if (is_fifty(p)) return true;

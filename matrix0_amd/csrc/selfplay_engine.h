@@ -1,0 +1,124 @@
+// The self-play engine object and the functions of its game loop (selfplay.hip) that the C-ABI unit (capi_selfplay.hip)
+// calls.  Internal: the public face is include/m0_engine.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <chrono>
+#include <deque>
+#include <list>
+#include <mutex>
+#include <string>
+#include <unordered_map>
+#include <vector>
+#include "../../include/m0_engine.h"
+#include "capi_common.h"
+#include "chess_core.h"
+#include "host_rules.h"
+#include "net.h"
+#include "tree.h"
+
+namespace m0 {
+
+inline double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+struct GameRecordOwner {
+    std::vector<float> s, pi, z, search_values, ssl;
+    std::vector<uint8_t> legal_mask;
+    std::vector<uint16_t> played;
+};
+
+struct HostGame : Line {                  // pos, win, history (all moves incl. opening plies)
+    bool in_use = false;
+    int game_index = 0;
+    std::vector<Pos> rec_pos;             // position of every recorded ply (SSL targets)
+    // records
+    std::vector<float> states, pis, search_values;
+    std::vector<int8_t> turns;
+    std::vector<uint8_t> masks;
+    std::vector<int> sims_used;
+    int nstates = 0;
+    double entropy_sum = 0.0;
+    int entropy_count = 0;
+    ResignState resign;
+    HStream rng;                          // PURPOSE_GAME stream: opening plies, playout cap, move sampling
+    double t0 = 0.0;
+    int cur_sims = 0;
+    bool a_is_white = true;               // arena
+};
+
+}  // namespace m0
+
+struct m0_selfplay {
+    m0_selfplay_cfg cfg;
+    TreeCfg tc;
+    m0_net* nethandle = nullptr;
+    m0_net* nethandle_b = nullptr;
+    Net* net = nullptr;
+    Net* net_b = nullptr;                 // arena: the second network (games with an odd index play it as White)
+    Net* net_tail = nullptr;              // cfg.tail_split: a view of `net` (same weights, own stream + workspace) for the partial last round
+    hipStream_t stream_tail = nullptr;
+    hipEvent_t ev_sel = nullptr, ev_tail = nullptr;
+    bool half_split = false;              // cfg.tail_split == 2: two halves instead of main + tail
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    int G = 0, L = 0, cap = 0, rows_max = 0;
+    TreeDev d;
+    std::vector<void*> allocs;
+    bool alloc_failed = false;            // a dalloc returned null (read by the creation path)
+    std::vector<GameDev> hg;
+    std::vector<m0::HostGame> games;
+    std::vector<RootResult> hres;
+    float* logits_dev = nullptr;
+    float* values_dev = nullptr;
+    float* ssl_dev = nullptr;
+    m0::Pos* ssl_pos_dev = nullptr;        // staging of one finished game's positions / SSL target maps (ssl_targets)
+    float* ssl_out_dev = nullptr;
+    int ssl_cap = 0;
+    int* ids_dev = nullptr;
+    int* slots_dev = nullptr;
+    std::deque<m0_game_record> done_meta;
+    m0_selfplay_stats stats;
+    int next_game = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
+    std::mutex mu;
+    std::vector<Sample> hsamples;
+    std::vector<int> prev_done;           // per slot: simulations already credited to stats.sims
+    int last_rows = 0, last_rows_b = 0;
+    int rows2[2] = {0, 0};                // rows of the last select per network
+    std::vector<m0::Pos> book;            // opening positions (m0_selfplay_set_openings)
+    // LRUCache nn_cache of the reference (mcts.py:44-59, 303, 360-371): positions whose root was re-evaluated; 10 000 entries
+    std::list<uint64_t> nn_lru;
+    std::unordered_map<uint64_t, std::list<uint64_t>::iterator> nn_map;
+    bool ext_pending = false;             // ext_select done, ext_expand outstanding
+    bool counted = false;                 // registered with the forward gate
+};
+
+namespace m0 {
+
+// Zeroed device memory that lives as long as the engine; null (and sp->alloc_failed) when hipMalloc fails.
+template <typename T>
+T* dalloc(m0_selfplay* sp, size_t count) {
+    void* p = nullptr;
+    size_t bytes = count * sizeof(T);
+    if (bytes == 0) bytes = 16;
+    if (hipMalloc(&p, bytes) != hipSuccess) { sp->alloc_failed = true; return nullptr; }
+    (void)hipMemsetAsync(p, 0, bytes, sp->stream);          // on the engine's own stream: ordered before every kernel that uses it
+    sp->allocs.push_back(p);
+    return (T*)p;
+}
+
+// selfplay.hip
+void forward_gate_join(m0_selfplay* sp);        // an engine that owns a network takes part in M0_FORWARD_GATE
+void forward_gate_leave(m0_selfplay* sp);
+void seed_game_dev(GameDev& g, uint64_t base, int uid);
+int sync_games_d2h(m0_selfplay* sp);
+void arm_search(m0_selfplay* sp, int slot, const Pos& pos, const RepWindow& win, int sims, bool dirichlet, bool fresh);
+int apply_advances(m0_selfplay* sp, std::vector<int>& ids, std::vector<int>& slots);
+int start_first_games(m0_selfplay* sp);         // lazily, at the first step; sets the error string itself
+int run_select(m0_selfplay* sp, int* rows_out);
+int one_step(m0_selfplay* sp, std::string& err);
+int step_back(m0_selfplay* sp, int rows, double t0, std::string& err);
+
+}  // namespace m0
