@@ -132,7 +132,7 @@ int m0_encode_fens(int hip_device, const char* const* fens, int n, float* planes
                    uint16_t* moves, int32_t* idx);
 /* The network's own input image of the same positions: fp16 bits, NHWC [n][64 squares][32 channels] (19 used, square
  * n = row*8+col of the reference tensor), written by the device function the search's select kernel calls for every
- * leaf (csrc/tree.hip encode_nhwc) -- i.e. encode_board (encoding.py:11-46) as the timed path evaluates it. */
+ * leaf (csrc/movegen_wave.h encode_nhwc) -- i.e. encode_board (encoding.py:11-46) as the timed path evaluates it. */
 int m0_encode_fens_nhwc(int hip_device, const char* const* fens, int n, uint16_t* nhwc);
 /* MoveEncoder.decode_move (encoding.py:174-229): policy index -> UCI (auto-queen, legal fallbacks); "0000" = null move.
  * uci_out: at least 6 bytes. */

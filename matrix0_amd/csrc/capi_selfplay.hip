@@ -242,7 +242,7 @@ static int leaf_planes(m0_selfplay* sp, int rows_a, float* planes_a, int rows_b,
         if (!sp->hg[g].active) continue;
         for (int s = 0; s < sp->hg[g].nsamples; ++s) {
             const Sample& smp = sp->hsamples[(size_t)g * (sp->L + 1) + s];
-            if (!(smp.kind == 1 || smp.kind == 2 || smp.kind == 4) || smp.row < 0) continue;
+            if (!sample_owns_row(smp.kind) || smp.row < 0) continue;
             if (smp.row < rows_a) encode_planes_f32(smp.pos, planes_a + (size_t)smp.row * 19 * 64);
             else if (smp.row >= base && smp.row < base + rows_b) encode_planes_f32(smp.pos, planes_b + (size_t)(smp.row - base) * 19 * 64);
         }

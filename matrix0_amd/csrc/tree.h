@@ -6,10 +6,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "chess_core.h"
+// deliberate: the C ABI already fixes M0_POLICY_SIZE (logits per batch row) and M0_PLANES (input planes); one definition
+#include "../../include/m0_engine.h"
 
 #define M0_MAX_DEPTH 256      // path length cap (nodes)
 #define M0_HIST_CAP 192       // reversible-move history window (<= 150 by the 75-move rule)
 #define M0_MAX_CHILDREN 256
+constexpr int M0_NHWC_C = 32;          // channel stride of the fp16 NHWC network input (M0_PLANES used, the rest zero)
 
 struct TreeCfg {              // MCTSConfig fields the kernels read (mcts.py:61-107)
     double fpu_reduction;
@@ -84,17 +87,30 @@ struct GameDev {
     int root_found;           // advance_kernel: this search's root was found in the side's table (mcts.py:343, 359-371)
 };
 
+enum SampleKind : int {
+    SK_NONE = 0,
+    SK_EVAL = 1,              // leaf: network evaluation, expansion, backup
+    SK_ROOT_INIT = 2,         // unexpanded root: evaluation + expansion, no backup
+    SK_TERMINAL = 3,          // terminal leaf, already backed up by select
+    SK_ROOT_VALUE = 4,        // value only: re-evaluation of a reused root
+    SK_CACHED = 5,            // leaf whose evaluation the evaluation cache served
+    SK_SHARED = 6,            // the same leaf as an earlier sample of this pass (shares its batch row)
+};
+// the sample reserved a batch row of its own (its planes go to the network)
+M0_HD bool sample_owns_row(int kind) { return kind == SK_EVAL || kind == SK_ROOT_INIT || kind == SK_ROOT_VALUE; }
+// the sample's descent left in-flight counts on its path, released after the batch
+M0_HD bool sample_holds_inflight(int kind) { return kind == SK_EVAL || kind == SK_TERMINAL || kind == SK_CACHED || kind == SK_SHARED; }
+
 struct Sample {
     m0::Pos pos;              // leaf position
-    int kind;                 // 0 none, 1 eval+backup, 2 root init (expand only), 3 terminal (already backed up),
-                              // 4 root value only (re-evaluation of a reused root), 5 eval served by the evaluation cache,
-                              // 6 the same leaf as an earlier sample of this pass (shares its batch row)
+    int kind;                 // SampleKind
     uint64_t ckey;            // evaluation-cache key of the leaf (0: not cacheable / cache off)
     int leaf;
     int depth;                // path has depth+1 nodes
     int row;                  // network batch row
     int nlegal;               // legal moves of the leaf (list in TreeDev::leaf_moves), filled by select
 };
+static_assert(sizeof(Sample) == 104, "the host copies Sample arrays device-to-host: the layout must not move");
 
 struct TreeArrays {           // each [G][2*cap]
     double* prior;
@@ -140,8 +156,8 @@ struct TreeDev {
     RootResult* results;      // [G]
     int* row_counter;         // [2]: rows reserved for network 0 / network 1 (arena); row index = net_row_base*net + count
     int net_row_base;         // first batch row of network 1's region (self-play: unused)
-    _Float16* x0;             // network input NHWC [rows][64][32]
-    const float* logits;      // [rows][4672]
+    _Float16* x0;             // network input NHWC [rows][64][M0_NHWC_C]
+    const float* logits;      // [rows][M0_POLICY_SIZE]
     const float* values;      // [rows]
     int G;
     int L;
@@ -154,11 +170,8 @@ hipError_t launch_expand(const TreeDev& d, const TreeCfg& c, hipStream_t st);
 hipError_t launch_advance(const TreeDev& d, const int* game_ids_dev, const int* child_slots_dev, int count, hipStream_t st);
 
 // test hooks: position-wise encode / legal move / index kernels (encoding.py on device)
-struct PosQuery {
-    m0::Pos pos;
-};
-hipError_t launch_encode_positions(const m0::Pos* pos_dev, int n, float* planes_f32_dev /*[n][19][64]*/,
-                                   _Float16* nhwc_dev /*[n][64][32] or null*/, uint8_t* mask_dev /*[n][4672]*/,
+hipError_t launch_encode_positions(const m0::Pos* pos_dev, int n, float* planes_f32_dev /*[n][M0_PLANES][64]*/,
+                                   _Float16* nhwc_dev /*[n][64][M0_NHWC_C] or null*/, uint8_t* mask_dev /*[n][M0_POLICY_SIZE]*/,
                                    int32_t* nlegal_dev, uint16_t* moves_dev /*[n][256]*/, int32_t* idx_dev /*[n][256]*/,
                                    hipStream_t st);
 

@@ -1,0 +1,95 @@
+// advance_kernel: re-root a game's tree on the played move, one wavefront per game.
+//   child_slot >= 0  keep that child's subtree, compacted breadth-first into the other arena half
+//   child_slot == -1 fresh tree (and an empty position table)
+//   child_slot <= -2 match engine with per-side tables (tt_sides == 2): the root is looked up in the side's table
+#include "tree_device.h"
+
+// Per-side tables: side = the network that searches now.  Nothing is compacted or cleared between the searches of a game; the
+// root is whatever node the side's table holds for the position (MCTS.run: root = self._tt_get(key), mcts.py:343), else a new
+// node.  slot -3 = first search of a game: both tables are cleared first.
+__device__ __forceinline__ void reroot_from_table(const TreeDev& d, GameDev* gd, int g, int slot, int lane) {
+    const int s = gd->net_id & 1;
+    const int prev_side = gd->arena & 1, prev_next = gd->next;
+    if (slot == -3) tt_clear(d.tt_keys + (size_t)g * 2 * d.tt_cap, 2 * d.tt_cap, lane);
+    __syncthreads();
+    int nxt = slot == -3 ? 0 : (s == prev_side ? prev_next : gd->side_next[s]);
+    const Arena A = arena_of(d.t, g, s);
+    uint64_t* TK = d.tt_keys + ((size_t)g * 2 + s) * d.tt_cap;
+    const int* TN = d.tt_nodes + ((size_t)g * 2 + s) * d.tt_cap;
+    int node = slot == -3 ? -1 : tt_lookup(TK, TN, d.tt_cap, tt_key_of(gd->root_pos), lane);
+    // a half that cannot take another search's worth of nodes starts over: its table is dropped and the search begins from a
+    // fresh root (what the reference's _cleanup_memory does to an over-full table); engine.arena_nodes sizes it for a game
+    if (nxt + (d.search_nodes > 4 * M0_MAX_CHILDREN ? d.search_nodes : 4 * M0_MAX_CHILDREN) >= d.t.cap) {
+        tt_clear(TK, d.tt_cap, lane);
+        nxt = 0; node = -1;
+        __syncthreads();
+    }
+    const bool found = node >= 0;
+    if (lane == 0) {
+        if (slot != -3) gd->side_next[prev_side] = prev_next;
+        else { gd->side_next[0] = 0; gd->side_next[1] = 0; }
+        if (!found) {
+            node = nxt;
+            node_reset(A, node, 0.0, 0, 0);
+            nxt = node + 1;
+        }
+        gd->arena = s; gd->root = node; gd->next = nxt; gd->overflow = 0;
+        gd->root_fresh = found ? 0 : 1; gd->root_found = found ? 1 : 0;
+    }
+}
+
+__device__ __forceinline__ void reroot_fresh(const TreeDev& d, GameDev* gd, int g, int lane) {
+    const Arena D = arena_of(d.t, g, 0);
+    // a fresh root starts with an empty position table
+    if (d.tt_keys) tt_clear(d.tt_keys + (size_t)g * d.tt_sides * d.tt_cap, d.tt_sides * d.tt_cap, lane);
+    if (lane == 0) {
+        node_reset(D, 0, 0.0, 0, 0);
+        gd->arena = 0; gd->root = 0; gd->next = 1; gd->overflow = 0;
+    }
+}
+
+// The subtree of the root's child `slot` -> the other arena half, breadth-first: node 0 is the new root, then its children,
+// their children ... (select_kernel's LDS copy of the tree top relies on this order).
+__device__ __forceinline__ void reroot_keep_subtree(const TreeDev& d, GameDev* gd, int g, int slot, int lane) {
+    const int a = gd->arena;
+    const Arena Sx = arena_of(d.t, g, a), D = arena_of(d.t, g, a ^ 1);
+    const int r = Sx.cbase[gd->root] + slot;
+    if (lane == 0) node_copy(D, 0, Sx, r);
+    __syncthreads();
+    int head = 0, tail = 1;
+    while (head < tail) {
+        const int lim = tail < head + 64 ? tail : head + 64;
+        const int i = head + lane;
+        const int nc_i = i < lim ? (int)D.nch[i] : -1;
+        const int cb_i = i < lim ? D.cbase[i] : -1;     // still the OLD child base
+        unsigned long long mask = __ballot(nc_i > 0);
+        while (mask) {
+            const int b = __builtin_ctzll(mask);
+            mask &= mask - 1;
+            const int nc = __shfl(nc_i, b), ocb = __shfl(cb_i, b);
+            const int ncb = tail;
+            for (int k = lane; k < nc; k += 64) node_copy(D, ncb + k, Sx, ocb + k);
+            if (lane == 0) D.cbase[head + b] = ncb;
+            tail += nc;
+        }
+        __syncthreads();
+        head = lim;
+    }
+    if (lane == 0) { gd->arena = a ^ 1; gd->root = 0; gd->next = tail; gd->overflow = 0; }
+}
+
+__global__ __launch_bounds__(64) void advance_kernel(TreeDev d, const int* game_ids, const int* child_slots, int count) {
+    const int j = blockIdx.x, lane = threadIdx.x;
+    if (j >= count) return;
+    const int g = game_ids[j], slot = child_slots[j];
+    GameDev* gd = &d.games[g];
+    if (slot <= -2) reroot_from_table(d, gd, g, slot, lane);
+    else if (slot < 0) reroot_fresh(d, gd, g, lane);
+    else reroot_keep_subtree(d, gd, g, slot, lane);
+}
+
+hipError_t launch_advance(const TreeDev& d, const int* game_ids_dev, const int* child_slots_dev, int count, hipStream_t st) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(advance_kernel, dim3(count), dim3(64), 0, st, d, game_ids_dev, child_slots_dev, count);
+    return hipGetLastError();
+}

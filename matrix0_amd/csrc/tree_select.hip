@@ -1,0 +1,313 @@
+// select_kernel: L descents per game and step, one wavefront per game tree: children scored one per lane from coalesced SoA
+// loads (PUCT + FPU + virtual loss + jitter in fp64, mcts.py:851-925), wave arg-max with first-max tie-break, leaf board by
+// make_move, terminal test, immediate terminal backup, evaluation-cache probe, M0_PLANES-plane encode written straight into
+// the network input (lane = square).
+#include "tree_device.h"
+#include "eval_cache.h"
+#include "movegen_wave.h"
+#include "kernel_common.h"   // DeviceOnce
+
+__device__ __forceinline__ double cpuct_at(const TreeCfg& c, int ply) {    // mcts.py:927-944
+    if (c.use_c_base) {
+        double N = fmax(1.0, (double)(ply + 1));
+        return c.cpuct_c_init + log((N + c.cpuct_c_base) / c.cpuct_c_base);
+    }
+    if (c.cpuct_plies <= 0) return c.cpuct;
+    int p = ply < 0 ? 0 : (ply > c.cpuct_plies ? c.cpuct_plies : ply);
+    double t = (double)p / (double)c.cpuct_plies;
+    return c.cpuct_start + (c.cpuct_end - c.cpuct_start) * t;
+}
+static __device__ void apply_dirichlet(const Arena& A, int root, GameDev* gd, const TreeCfg& c, double* sg, int lane) {
+    const int k = A.nch[root];
+    if (k <= 0 || c.dirichlet_frac <= 0.0) return;
+    const int cb = A.cbase[root];
+    uint64_t ctr = gd->ctr_dir;
+    double sum = 0.0;
+    for (int i = 0; i < k; ++i) {                 // sequential draws, uniform across lanes
+        double gmm = gamma_draw(gd->seed_dir, ctr, c.dirichlet_alpha);
+        if (lane == 0) sg[i] = gmm;
+        sum += gmm;
+    }
+    __syncthreads();
+    for (int i = lane; i < k; i += 64) {
+        double nv = A.prior[cb + i] * (1.0 - c.dirichlet_frac) + (sg[i] / sum) * c.dirichlet_frac;
+        A.prior[cb + i] = fmax(1e-8, fmin(1.0 - 1e-8, nv));
+    }
+    if (lane == 0) gd->ctr_dir = ctr;
+    __syncthreads();
+}
+
+__device__ __forceinline__ Sample make_sample(const Pos& pos, SampleKind kind, int leaf, int depth, int row, int nlegal, uint64_t ckey) {
+    Sample s; s.pos = pos; s.kind = kind; s.leaf = leaf; s.depth = depth; s.row = row; s.nlegal = nlegal; s.ckey = ckey;
+    return s;
+}
+
+// is_game_over() (checkmate, stalemate, insufficient, 75-move, fivefold) -> _terminal_value in `tv`
+__device__ __forceinline__ bool leaf_terminal(const TreeCfg& c, const Pos& pos, int nlegal, int depth, const uint64_t* pkey,
+                                              const uint8_t* pirr, const uint64_t* H, int hist_len, int lane, double& tv) {
+    const bool chk = in_check(pos);
+    bool term = false;
+    tv = 0.0;
+    if (nlegal == 0) { term = true; tv = chk ? -1.0 : c.draw_penalty; }
+    else if (is_insufficient(pos)) { term = true; tv = c.draw_penalty; }
+    else if (pos.halfmove >= 150) { term = true; tv = c.draw_penalty; }
+    else {
+        const uint64_t lk = tkey(pos);
+        int cnt = 1;
+        bool broke = false;
+        for (int dd = depth - 1; dd >= 0; --dd) {
+            if (pirr[dd]) { broke = true; break; }
+            if (pkey[dd] == lk) ++cnt;
+        }
+        if (!broke)                                   // the game's reversible-move window: one entry per lane
+            for (int i0 = 0; i0 < hist_len; i0 += 64) {
+                const int i = i0 + lane;
+                cnt += __popcll(__ballot(i < hist_len && H[i] == lk));
+            }
+        if (cnt >= 5) { term = true; tv = c.draw_penalty; }
+    }
+    return term;
+}
+
+// The same unexpanded node reached again in this pass (a batch of 96 descents over a young tree lands on the same leaf
+// many times; the virtual loss only spreads them): it shares the batch row of its first occurrence instead of being
+// evaluated twice in one forward.  The pending row sits in the node's child-base field, which means nothing until the
+// node is expanded: cbase <= -2  <=>  row -(cbase + 2) of this pass (expand_kernel resets it).
+__device__ __forceinline__ bool pending_row(const Arena& A, int node, int& row) {
+    const int pend = A.cbase[node];
+    if (A.nch[node] < 0 && pend <= -2) { row = -(pend + 2); return true; }
+    return false;
+}
+__device__ __forceinline__ void mark_pending_row(const Arena& A, int node, int row) { A.cbase[node] = -(row + 2); }
+
+// mcts.py:359-371: a root taken over from the previous search is evaluated once more (value only)
+__device__ __forceinline__ void emit_root_value(const TreeDev& d, GameDev* gd, Sample* S, int at, int root, int lane) {
+    const int row = reserve_row(d, gd, lane);
+    if (lane == 0) {
+        S[at] = make_sample(gd->root_pos, SK_ROOT_VALUE, root, 0, row, 0, 0); gd->reinfer = 0;
+    }
+    encode_nhwc(gd->root_pos, nhwc_row(d.x0, row), lane);
+}
+
+// root not expanded: one network evaluation, no simulation
+__device__ __forceinline__ void emit_root_init(const TreeDev& d, GameDev* gd, Sample* S, int* P, uint16_t* LM, int root, bool reinfer,
+                                               Move* smoves, Move* spseudo, int lane) {
+    if (lane == 0 && !gd->root_fresh) {
+        // reused but never expanded child: run() applies Dirichlet BEFORE expanding it (a no-op on a
+        // childless node, mcts.py:374-376 vs 398-413) and then sets root.q = v
+        gd->need_dirichlet = 0;
+        gd->root_q_from_v = 1;
+    }
+    const int row = reserve_row(d, gd, lane);
+    const Pos rp = gd->root_pos;
+    const int nl = gen_legal_wave(rp, smoves, spseudo, lane);
+    for (int i = lane; i < nl; i += 64) LM[i] = smoves[i];
+    if (lane == 0) {
+        S[0] = make_sample(rp, SK_ROOT_INIT, root, 0, row, nl, 0); P[0] = root; gd->nsamples = reinfer ? 2 : 1;
+    }
+    encode_nhwc(rp, nhwc_row(d.x0, row), lane);
+    if (reinfer) emit_root_value(d, gd, S, 1, root, lane);
+}
+
+// The sample of a leaf: a terminal or cache-served leaf needs no batch row; one that an earlier sample of this pass already
+// sent to the network shares that row (pending_row); any other reserves a row and writes its planes there.
+__device__ __forceinline__ void emit_leaf(const TreeDev& d, const TreeCfg& c, const Arena& A, GameDev* gd, Sample* smp, uint16_t* lm,
+                                          const Pos& pos, int node, int depth, const Move* smoves, int nlegal, bool term, bool cached,
+                                          uint64_t ckey, int lane) {
+    int row = -1;
+    bool shared = false;
+    if (!term && !cached && c.eval_cache) shared = pending_row(A, node, row);
+    if (!term && !cached && !shared) {
+        row = reserve_row(d, gd, lane);
+        encode_nhwc(pos, nhwc_row(d.x0, row), lane);
+        if (c.eval_cache && lane == 0 && A.nch[node] < 0) mark_pending_row(A, node, row);
+    }
+    if (!term && !shared) for (int i = lane; i < nlegal; i += 64) lm[i] = smoves[i];
+    if (lane == 0) {
+        *smp = make_sample(pos, term ? SK_TERMINAL : (cached ? SK_CACHED : (shared ? SK_SHARED : SK_EVAL)), node, depth, row, nlegal,
+                           cached ? 0ull : ckey);
+    }
+}
+
+// The top of a game's tree lives in LDS for the duration of a select launch (north star: "tree walk over LDS-resident node
+// arrays"): after every played move the kept subtree is compacted BREADTH-FIRST (advance_kernel), so the nodes with the lowest
+// indices are the root, its children, their children ... -- the levels every one of the pass's 96 descents walks through.  The
+// first M0_SEL_CACHE nodes' select fields are copied once per launch; the children scan reads them from LDS instead of paying a
+// global round trip per level, and the two things a select launch writes to such nodes (in-flight counts, the statistics of a
+// terminal leaf's path) are written through.  Deeper nodes -- and everything in the table modes, whose arenas are not
+// compacted -- are read from the arenas in HBM as before.
+constexpr int M0_SEL_CACHE = 2048;
+struct TopCache {
+    double prior[M0_SEL_CACHE];
+    double q[M0_SEL_CACHE];
+    int n[M0_SEL_CACHE];
+    int vl[M0_SEL_CACHE];
+    int cbase[M0_SEL_CACHE];
+    int16_t nch[M0_SEL_CACHE];
+    uint16_t mv[M0_SEL_CACHE];
+};
+constexpr int M0_SEL_CACHE_BYTES = M0_SEL_CACHE * 32;     // the launch's dynamic LDS
+static_assert(sizeof(TopCache) == M0_SEL_CACHE_BYTES, "32 bytes of select fields per cached node");
+// Select field f of node i: from the LDS copy `TC` where the node is cached (`hit`), else from the arena `A`.  A macro on
+// purpose: as written here the compiler folds a node's reads into one branch on `hit` (LDS loads | global loads); behind a
+// function or lambda, however inlined, each read becomes a select between an LDS and a global address and a flat load, and
+// select_kernel measured 25 us (1.5 %) slower per call.
+#define TOP(f, hit, i) ((hit) ? TC->f[i] : A.f[i])
+
+__global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
+    extern __shared__ __attribute__((aligned(16))) char sel_cache[];
+    TopCache* const TC = reinterpret_cast<TopCache*>(sel_cache);
+    __shared__ uint64_t pkey[M0_MAX_DEPTH];
+    __shared__ uint8_t pirr[M0_MAX_DEPTH];
+    __shared__ Move smoves[M0_MAX_MOVES];
+    __shared__ Move spseudo[M0_MAX_MOVES];
+    __shared__ double sg[M0_MAX_CHILDREN];
+    const int g = blockIdx.x, lane = threadIdx.x;
+    GameDev* gd = &d.games[g];
+    if (!gd->active) { if (lane == 0) gd->nsamples = 0; return; }
+    uint16_t* LM = d.leaf_moves + (size_t)g * (d.L + 1) * M0_MAX_CHILDREN;
+    const Arena A = arena_of(d.t, g, gd->arena);
+    const int root = gd->root;
+    Sample* S = d.samples + (size_t)g * (d.L + 1);
+    int* P = d.paths + (size_t)g * (d.L + 1) * M0_MAX_DEPTH;
+    int* EP = c.tt_merge ? d.epaths + (size_t)g * (d.L + 1) * M0_MAX_DEPTH : nullptr;
+    const uint64_t* TK = c.tt_merge ? d.tt_keys + tt_table_of(d, g, gd) : nullptr;
+    const int* TN = c.tt_merge ? d.tt_nodes + tt_table_of(d, g, gd) : nullptr;
+    const bool reinfer = gd->reinfer != 0;
+
+    if (A.nch[root] < 0) { emit_root_init(d, gd, S, P, LM, root, reinfer, smoves, spseudo, lane); return; }
+    if (gd->need_dirichlet) {
+        apply_dirichlet(A, root, gd, c, sg, lane);
+        if (lane == 0) gd->need_dirichlet = 0;
+    }
+    int nleaf = gd->sims_target - gd->sims_done;
+    if (nleaf > d.L) nleaf = d.L;
+    if (nleaf < 0) nleaf = 0;
+    // the top of the tree -> LDS (after the Dirichlet noise, which rewrites the root's priors)
+    int ncached = 0;
+    if (!c.tt_merge && nleaf > 0) {
+        ncached = gd->next < M0_SEL_CACHE ? gd->next : M0_SEL_CACHE;
+        for (int i = lane; i < ncached; i += 64) {
+            TC->prior[i] = A.prior[i]; TC->q[i] = A.q[i]; TC->n[i] = A.n[i]; TC->vl[i] = A.vl[i]; TC->cbase[i] = A.cbase[i];
+            TC->nch[i] = A.nch[i]; TC->mv[i] = A.mv[i];
+        }
+        __syncthreads();
+    }
+    uint64_t ctrj = gd->ctr_jitter;
+    const uint64_t seedj = gd->seed_jitter;
+    const double jit = c.selection_jitter > 0.0 ? c.selection_jitter : 0.001;
+    const int hist_len = gd->hist_len;
+    const uint64_t* H = d.hist + (size_t)g * M0_HIST_CAP;
+
+    for (int s = 0; s < nleaf; ++s) {
+        Pos pos = gd->root_pos;
+        int* path = P + (size_t)s * M0_MAX_DEPTH;
+        int* epath = c.tt_merge ? EP + (size_t)s * M0_MAX_DEPTH : nullptr;
+        int node = root, depth = 0;
+        int prev_from = -1, prev_to = -1;
+        if (lane == 0) { path[0] = root; if (epath) epath[0] = root; }
+        // One round of dependent loads per level: the children scan also fetches every candidate's own node fields
+        // (children ARE nodes), and the winner's are broadcast -- the next level starts without loading its node.
+        const bool rh = node < ncached;
+        int nc = TOP(nch, rh, node), cb = TOP(cbase, rh, node), nn = TOP(n, rh, node);
+        double nq = TOP(q, rh, node);
+        while (true) {
+            if (nc <= 0 || depth >= M0_MAX_DEPTH - 1) break;
+            const double sq = sqrt((double)(nn > 1 ? nn : 1));
+            const double eff = cpuct_at(c, depth);
+            double best = -1e9;
+            int bi = -1;
+            int b_nch = 0, b_cb = 0, b_n = 0, b_vl = 0;
+            double b_q = 0.0;
+            Move b_mv = 0;
+            for (int i = lane; i < nc; i += 64) {
+                const int ci = cb + i;
+                const bool hit = ci < ncached;                  // the children of a node are one block: all lanes agree but at the edge
+                const int cn = TOP(n, hit, ci);
+                const double cq = TOP(q, hit, ci);
+                const int c_nch = TOP(nch, hit, ci), c_cb = TOP(cbase, hit, ci);
+                const Move m = TOP(mv, hit, ci);
+                const double cprior = TOP(prior, hit, ci);
+                const double qq = cn == 0 ? nq - c.fpu_reduction : cq;
+                const double u = eff * cprior * (sq / (1.0 + (double)cn));
+                double sc = qq + u;
+                if (c.no_instant_backtrack && depth >= 1) {
+                    if (mv_from(m) == prev_to && mv_to(m) == prev_from) sc -= 0.01;
+                }
+                const int cvl = c.virtual_loss_active ? TOP(vl, hit, ci) : 0;
+                if (c.virtual_loss_active && c.virtual_loss > 0.0) sc -= (double)cvl * c.virtual_loss;
+                sc += (u01(seedj, ctrj + (uint64_t)i) - 0.5) * jit;
+                if (sc > best) { best = sc; bi = i; b_nch = c_nch; b_cb = c_cb; b_n = cn; b_q = cq; b_mv = m; b_vl = cvl; }
+            }
+            for (int off = 32; off > 0; off >>= 1) {
+                const double ob = __shfl_xor(best, off);
+                const int oi = __shfl_xor(bi, off);
+                if (oi >= 0 && (bi < 0 || ob > best || (ob == best && oi < bi))) { best = ob; bi = oi; }
+            }
+            ctrj += (uint64_t)nc;
+            if (bi < 0) bi = 0;
+            const int child = cb + bi;
+            // the lane that scanned child bi (i = lane + 64 k) holds its fields iff its own best is bi
+            const int wl = bi & 63;
+            nc = __shfl(b_nch, wl); cb = __shfl(b_cb, wl); nn = __shfl(b_n, wl); nq = __shfl(b_q, wl);
+            const Move m = (Move)__shfl((int)b_mv, wl);
+            const uint64_t k = tkey(pos);
+            const bool irr = irreversible(pos, m);
+            if (lane == 0) { pkey[depth] = k; pirr[depth] = irr ? 1 : 0; }
+            make_move(pos, m);
+            // the scanned in-flight count + 1 (no second load), and no barrier per level: nothing a level stores
+            // (in-flight count, path, position keys) is read before the walk has ended
+            const int vlw = __shfl(b_vl, wl);
+            if (lane == 0 && c.virtual_loss_active) { A.vl[child] = vlw + 1; if (child < ncached) TC->vl[child] = vlw + 1; }
+            prev_from = mv_from(m); prev_to = mv_to(m);
+            node = child; ++depth;
+            if (c.tt_merge) {
+                // mcts.py:919: node = self._tt_get(board._transposition_key()) or best_child -- the walk continues from
+                // the node registered LAST for this position; the edge child keeps the statistics its parent scores
+                const int tn = tt_lookup(TK, TN, d.tt_cap, tt_key_of(pos), lane);
+                if (tn >= 0 && tn != child) {
+                    node = tn;
+                    nc = A.nch[node]; cb = A.cbase[node]; nn = A.n[node]; nq = A.q[node];
+                }
+                if (lane == 0) epath[depth] = child;
+            }
+            if (lane == 0) path[depth] = node;
+        }
+        __syncthreads();
+        const int nlegal = gen_legal_wave(pos, smoves, spseudo, lane);
+        double tv;
+        const bool term = leaf_terminal(c, pos, nlegal, depth, pkey, pirr, H, hist_len, lane, tv);
+        uint64_t ckey = 0;
+        bool cached = false;
+        if (!term && c.eval_cache && d.ec.sets > 0 && nlegal <= M0_EC_MAXLEGAL) {
+            ckey = ec_key_of(pos);
+            cached = ec_probe(d, gd, g, s, ckey, smoves, nlegal, lane);
+        }
+        emit_leaf(d, c, A, gd, S + s, LM + (size_t)s * M0_MAX_CHILDREN, pos, node, depth, smoves, nlegal, term, cached, ckey, lane);
+        __syncthreads();                                 // path[] (lane 0) before the wave reads it
+        if (term) {                                      // mcts.py:747-751: terminal leaves back up immediately
+            // (the cached copies of the path's statistics follow)
+            backprop(A, path, depth, tv, lane, c.tt_merge != 0, [&](int nd, int nn, double qq) {
+                if (nd < ncached) { TC->n[nd] = nn; TC->q[nd] = qq; }
+            });
+            __syncthreads();
+            // Later descents of this launch read these nodes' statistics again, the uncached ones from the arena: drop this CU's
+            // vector-L1 lines so that they come from L2, where the stores above are.  (Round 4: a load of the same addresses
+            // issued right after the barrier returned the OLD values from time to time -- the lines were resident from the
+            // children scan and a store does not refresh them at once; seen as run-to-run differences in whole games.)
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        }
+    }
+    if (reinfer) emit_root_value(d, gd, S, nleaf, root, lane);
+    if (lane == 0) { gd->ctr_jitter = ctrj; gd->nsamples = nleaf + (reinfer ? 1 : 0); }
+}
+
+hipError_t launch_select(const TreeDev& d, const TreeCfg& c, hipStream_t st) {
+    static DeviceOnce once;
+    hipError_t e = once.run([] {
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(&select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, M0_SEL_CACHE_BYTES);
+    });
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(select_kernel, dim3(d.G), dim3(64), M0_SEL_CACHE_BYTES, st, d, c);
+    return hipGetLastError();
+}

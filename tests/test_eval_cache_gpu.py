@@ -1,7 +1,7 @@
 """`engine.eval_cache`: (a) a leaf reached more than once in one pass (96 descents over a young tree land on the same
-unexpanded node many times) shares ONE batch row, (b) per-game evaluation cache (csrc/tree.h EvalCache): a leaf whose position
-the game evaluated in an earlier pass is expanded from the stored value + legal logits.  The 320-wide forward is bitwise batch invariant, so a fresh evaluation would return the very same
-numbers: the games must be identical, bit for bit, with the cache on and off -- moves, visit distributions, values -- and every
+unexpanded node many times) shares ONE batch row, (b) per-game evaluation cache (csrc/tree.h EvalCache,
+csrc/eval_cache.h): a leaf whose position the game evaluated in an earlier pass is expanded from the stored value + legal
+logits.  The 320-wide forward is bitwise batch invariant, so a fresh evaluation would return the very same numbers: the games must be identical, bit for bit, with the cache on and off -- moves, visit distributions, values -- and every
 simulation that was a network evaluation without the cache is either an evaluation or a cache hit with it."""
 import numpy as np
 import pytest

@@ -94,7 +94,7 @@ def test_device_encoding_matches_reference_outputs(gold):
 
 @pytest.mark.gpu
 def test_network_input_of_the_search_matches_reference_outputs(gold):
-    """The network input of the TIMED path: csrc/tree.hip::encode_nhwc, the device function select_kernel calls for every
+    """The network input of the TIMED path: csrc/movegen_wave.h::encode_nhwc, the device function select_kernel calls for every
     leaf (fp16, NHWC [64 squares][32 channels]), run on every position of the golden file through m0_encode_fens_nhwc and
     compared with fp16(encode_board of the reference) bit for bit -- channels 19..31 must be zero."""
     from matrix0_amd import engine as eng
