@@ -194,9 +194,10 @@ typedef struct m0_selfplay_cfg {
     /* per-game evaluation cache (csrc/tree.h EvalCache): a leaf whose position was evaluated before -- a transposition inside
      * the search, a position of a discarded subtree -- is expanded from the stored value + legal logits instead of going
      * through the network again.  Games are unchanged (the forward is bitwise batch invariant on the 320-wide path).  Active
-     * only with legal_softmax = 1 and without tt_merge / raw_legal_priors, and never in a match engine (m0_arena_create*:
-     * two networks alternate in one game slot and the key carries no network id -- the field is ignored there).  A hit must
-     * also match the stored legal-move count and a checksum of the legal moves; otherwise it is served as a miss.  0 = off. */
+     * only with legal_softmax = 1 and without tt_merge / raw_legal_priors.  A hit must also match the stored legal-move count
+     * and a checksum of the legal moves; otherwise it is served as a miss.  0 = off.  This field is for self-play engines: a
+     * match engine (m0_arena_create*) ignores it -- two networks alternate in one game slot and the key carries no network
+     * id -- and has a switch of its own, arena_eval_cache below, which gives every network its own cache. */
     int eval_cache;
     int eval_cache_entries;       /* entries per game (rounded up to a power of two, 4-way sets); 0 = 16384 */
     /* 1 = a pass of >= 2048 rows on the 320-wide network is evaluated as a main part that is a whole number of rounds of
@@ -207,6 +208,18 @@ typedef struct m0_selfplay_cfg {
      * half's attention blocks then run beside the other half's power-bound convs instead of behind them (+1.3 % games/s
      * measured); per-launch kernel timings of the two halves overlap.  0 = off (default). */
     int tail_split;
+    /* Match engines only (ignored by self-play engines).  1 = every game slot owns TWO evaluation caches of eval_cache_entries
+     * entries each, one per network, addressed by the network that evaluates the current search: a position evaluated by
+     * network A is never served to a search of network B.  A side's cache lives for the whole game, across that side's
+     * fresh-tree searches (its new root's subtree was evaluated by the same network two plies earlier), and both are emptied
+     * when the slot starts a new game (colours, hence networks, swap).  Same conditions and hit criteria as eval_cache;
+     * outside them the switch is ignored.  Games are unchanged on the bitwise batch-invariant 320-wide path.  0 = off. */
+    int arena_eval_cache;
+    /* Match engines only.  1 = with an opening book (m0_selfplay_set_openings) games 2k and 2k+1 start from the SAME book
+     * position, so every opening is played once with each network as White.  The position is drawn from the counter stream
+     * keyed by (seed, k, a purpose of its own), not from either game's stream: the pairing does not depend on the slot or the
+     * order in which games start.  0 = every game draws its opening from its own stream, as a self-play engine does. */
+    int arena_paired_openings;
 } m0_selfplay_cfg;
 
 typedef struct m0_selfplay m0_selfplay;
@@ -236,6 +249,8 @@ typedef struct m0_game_record {
     const uint16_t* played;       /* [total_plies] moves incl. opening plies */
     const float* ssl;             /* [T,17,8,8] piece(13) threat pin fork control, or NULL */
     void* owner;
+    const char* start_fen;        /* the opening-book position the game started from, as given to m0_selfplay_set_openings;
+                                     NULL = the initial position.  `played` holds the moves from there on */
 } m0_game_record;
 
 m0_selfplay* m0_selfplay_create(m0_net* net, const m0_selfplay_cfg* cfg);
@@ -251,7 +266,9 @@ void m0_game_record_free(m0_game_record* rec);
 int m0_selfplay_running(m0_selfplay* sp);
 /* Opening book (selfplay/internal.py:34-69 load_opening_book / get_opening_position): every new game starts from one of
  * these positions, chosen with the game's own stream as random.choice(OPENING_BOOK) would; n = 0 clears the book
- * (games start from the initial position).  Call before the first step. */
+ * (games start from the initial position).  Call before the first step.  A match engine takes a book too (the reference's
+ * eval.openings_pgn): cfg->max_game_len then counts the plies played from the book position, and with
+ * cfg->arena_paired_openings the two games of a pair share their position. */
 int m0_selfplay_set_openings(m0_selfplay* sp, const char* const* fens, int n);
 /* The self-play step split at the network, for an external evaluator behind the reference's infer_np seam (net may be
  * NULL): ext_select runs select for all resident games and returns the leaf planes f32 [rows,19,8,8]; ext_expand takes
@@ -267,7 +284,11 @@ int m0_selfplay_last_batch_nhwc(m0_selfplay* sp, uint16_t* nhwc, int max_rows, i
 /* Evaluation match between two networks (azchess/arena.py:59-126 _arena_run_one_game, :305 play_match): game i is played
  * with net_a as White when i is even.  Every search of a game is evaluated by the network of the side to move; each
  * move starts a fresh tree, unless cfg->tt_merge asks for the reference's own structure: one transposition table per side
- * kept for the whole game (arena.py:157-158 keeps one MCTS object per side), roots looked up in it.  The game ends on board.is_game_over(claim_draw=True), on
+ * kept for the whole game (arena.py:157-158 keeps one MCTS object per side), roots looked up in it.  With
+ * cfg->arena_eval_cache a fresh-tree match engine keeps one evaluation cache per network and game, so what a side's previous
+ * search evaluated is not evaluated again (cfg->eval_cache itself stays ignored here); m0_selfplay_stats.evals_cached counts
+ * the hits.  Games start from the initial position or from an opening book (m0_selfplay_set_openings,
+ * cfg->arena_paired_openings).  The game ends on board.is_game_over(claim_draw=True), on
  * cfg->max_game_len plies or on draw adjudication (draw.py); no resignation.  Step / poll / stats / destroy with the
  * m0_selfplay_* functions; a record's `played` holds the moves, `result` the outcome from White's point of view
  * (0 for unfinished or adjudicated games, as the reference scores them 1/2-1/2). */
@@ -275,7 +296,8 @@ m0_selfplay* m0_arena_create(m0_net* net_a, m0_net* net_b, const m0_selfplay_cfg
 /* The same match engine without networks, for external evaluators behind the reference's infer_np seam (golden tests replay
  * the reference's arena games this way): m0_arena_ext_select returns the leaves of network A's searches and of network B's
  * separately (planes f32 [rows,19,8,8] each; max_rows >= concurrent_games * (inference_batch_size + 1) for both buffers),
- * m0_arena_ext_expand takes the two evaluators' answers and finishes the step exactly as m0_selfplay_step does. */
+ * m0_arena_ext_expand takes the two evaluators' answers and finishes the step exactly as m0_selfplay_step does.  Leaves
+ * served by cfg->arena_eval_cache are not handed to the evaluators. */
 m0_selfplay* m0_arena_create_ext(const m0_selfplay_cfg* cfg);
 int m0_arena_ext_select(m0_selfplay* sp, int* rows_a, int* rows_b, float* planes_a, float* planes_b, int max_rows);
 int m0_arena_ext_expand(m0_selfplay* sp, const float* logits_a, const float* values_a, int rows_a, const float* logits_b,
@@ -283,11 +305,14 @@ int m0_arena_ext_expand(m0_selfplay* sp, const float* logits_a, const float* val
 /* PGN output of arena games (arena.py:281-303 uses chess.pgn): standard algebraic notation, python-chess Board.san().
  * m0_san_legal_fen: the legal moves of `fen` in legal_moves order (moves u16[256]) with their SAN (san char[256][8],
  * NUL-padded).  m0_san_game: movetext "1. e4 e5 2. Nf3 ..." of a game from the start position (moves as in
- * m0_game_record.played); returns its length. */
+ * m0_game_record.played); returns its length.  m0_san_game_fen: the same for a game that starts from `fen`
+ * (m0_game_record.start_fen), move numbers following the FEN as python-chess writes them: "12... Nf6 13. e4" when Black
+ * moves first. */
 /* arena.py:73-106 move choice over a visit list in move order; u = the uniform np.random.choice would draw. */
 int m0_arena_choose_move(const int32_t* visits, int n, double temp, int ply, int temp_plies, double u);
 int m0_san_legal_fen(const char* fen, uint16_t* moves, char* san, int* nlegal);
 int m0_san_game(const uint16_t* moves, int n, char* out, int cap);
+int m0_san_game_fen(const char* fen, const uint16_t* moves, int n, char* out, int cap);
 /* Board.fen() after pushing `n` legal moves (UCI) on the position `fen` (python-chess semantics: cleaned castling rights, the
  * en-passant square only when such a capture is legal); M0_ERR_INVALID for an illegal move.  Host function (no GPU): the PGN
  * opening-book reader (selfplay/internal.py:39-63) and FEN-addressed callers are built on it. */

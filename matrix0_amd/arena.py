@@ -13,12 +13,21 @@ Search structure: by default every move starts a fresh tree.  The reference keep
 table -- per side for the whole game (:157-158): `engine.compat.tt_merge: true` gives the match engine exactly that (one
 device table per side and game, roots looked up in it, later searches merging into the nodes earlier ones left there; size
 `engine.arena_nodes` for all nodes a side creates in a game).  Both modes replay the reference's own arena games move for move
-(tests/golden/ref_arena.json.gz, tests/test_golden_selfplay_gpu.py)."""
+(tests/golden/ref_arena.json.gz, tests/test_golden_selfplay_gpu.py).
+
+Two opt-in additions the reference has no code for.  `engine.arena_eval_cache: true` (entries: `engine.eval_cache_entries`)
+gives every network an evaluation cache per game: a side's fresh tree re-expands what its own search of two plies earlier
+evaluated, and those leaves are served from the cache instead of the network -- the same games, fewer evaluations
+(`last_match_stats["evals_cached"]`).  `eval.openings_pgn` (the key of the reference's config.yaml, which nothing there reads) or
+the `openings=` argument starts the games from an opening book, paired by colour: games 2k and 2k+1 share one book position, so
+each opening is played once with A as White and once with B.  Without a book every game starts from the initial position, and
+with no temperature and no noise a match is then two distinct games played over and over."""
 from __future__ import annotations
 
 import json
 import os
 import time
+import warnings
 from datetime import datetime
 from typing import Dict, List, Optional, Tuple
 
@@ -59,13 +68,16 @@ def game_score(result: str, a_is_white: bool) -> float:
     return 0.5
 
 
-def save_pgn(moves_raw, result: str, headers: Dict[str, str], out_dir: str, idx: int) -> str:
-    """game_{idx:04d}.pgn with the seven-tag roster + caller headers and SAN movetext (lines wrapped at 80 columns)."""
+def save_pgn(moves_raw, result: str, headers: Dict[str, str], out_dir: str, idx: int, start_fen: Optional[str] = None) -> str:
+    """game_{idx:04d}.pgn with the seven-tag roster + caller headers and SAN movetext (lines wrapped at 80 columns).  A game
+    from an opening-book position (`start_fen`) also carries [SetUp "1"] and [FEN "..."], and its move numbers follow the FEN."""
     os.makedirs(out_dir, exist_ok=True)
     tags = {"Event": "?", "Site": "?", "Date": "????.??.??", "Round": "?", "White": "?", "Black": "?", "Result": result}
     tags.update({k: str(v) for k, v in headers.items()})
     tags["Result"] = result
-    words = (eng.san_game(moves_raw).split() if len(moves_raw) else []) + [result]
+    if start_fen:
+        tags["SetUp"], tags["FEN"] = "1", start_fen
+    words = (eng.san_game(moves_raw, start_fen).split() if len(moves_raw) else []) + [result]
     lines, cur = [], ""
     for w in words:
         if cur and len(cur) + 1 + len(w) > 80:
@@ -102,7 +114,25 @@ def arena_cfg_from_dict(cfg: dict, *, games: int, num_sims: int, max_moves: int,
                                    record_games=False, arena_nodes=int(ecfg.get("arena_nodes", 0) or 0))
     c.arena_temp = float(temp)
     c.arena_temp_plies = int(temp_plies)
+    # one evaluation cache per network and game (`engine.eval_cache` is the self-play switch; a match engine ignores it)
+    c.arena_eval_cache = int(bool(ecfg.get("arena_eval_cache", False)))
+    c.eval_cache_entries = int(ecfg.get("eval_cache_entries", 0) or 0)
     return c
+
+
+def match_openings(cfg: dict, openings: Optional[List[str]] = None) -> List[str]:
+    """The opening book of a match as FEN strings: the `openings` argument, else the PGN file `eval.openings_pgn` names (read by
+    pgn_book.load_opening_book), else [] = every game starts from the initial position."""
+    if openings is not None:
+        return [str(f) for f in openings]
+    path = (cfg.get("eval", {}) or {}).get("openings_pgn")
+    if not path:
+        return []
+    from .pgn_book import load_opening_book
+    book = load_opening_book(str(path))
+    if not book:
+        warnings.warn(f"eval.openings_pgn: no opening positions in {path!r}; the games start from the initial position")
+    return book
 
 
 last_match_stats: Dict[str, float] = {}
@@ -111,11 +141,14 @@ last_match_stats: Dict[str, float] = {}
 def play_match(backend_a, backend_b, games: int, cfg: dict, seed: Optional[int] = None, pgn_out: Optional[str] = None,
                pgn_sample: int = 0, num_sims: int = 500, max_moves_override: Optional[int] = None, temp: float = 0.0,
                temp_plies: int = 0, concurrent_games: Optional[int] = None, leaves_per_step: Optional[int] = 16,
-               elo_book: Optional[str] = None, log_dir: Optional[str] = None, progress=None) -> float:
+               elo_book: Optional[str] = None, log_dir: Optional[str] = None, progress=None,
+               openings: Optional[List[str]] = None) -> float:
     """A vs B over `games` games; returns the summed score of A (1 / 0.5 / 0 per game), as arena.play_match does.
     `backend_a` / `backend_b` are M0Backend objects on the same device (the reference takes checkpoint paths:
-    M0Backend.from_checkpoint).  Details of the last match (W/L/D, win rate, Wilson interval, Elo) are left in
-    `last_match_stats`."""
+    M0Backend.from_checkpoint).  `openings` (FEN strings) or `eval.openings_pgn` in `cfg`: the games start from book positions,
+    games 2k and 2k+1 from the same one; `max_moves` then counts the plies played from there.  Details of the last match
+    (W/L/D, win rate, Wilson interval, Elo, evaluations made and served from the cache, the records with their `start_fen`) are
+    left in `last_match_stats`."""
     global last_match_stats
     if games <= 0:
         return 0.0
@@ -135,12 +168,16 @@ def play_match(backend_a, backend_b, games: int, cfg: dict, seed: Optional[int] 
         cfg = dict(cfg, engine=dict(ecfg, arena_nodes=nodes))
     c = arena_cfg_from_dict(cfg, games=games, num_sims=num_sims, max_moves=max_moves, temp=temp, temp_plies=temp_plies,
                             concurrent_games=min(conc, games), leaves_per_step=leaves_per_step, seed=seed)
+    book = match_openings(cfg, openings)
+    c.arena_paired_openings = 1 if book else 0
     e = eng.ArenaEngine(backend_a, backend_b, c)
     score = 0.0
     a_wins = b_wins = draws = 0
     done: List[dict] = []
     t0 = time.perf_counter()
     try:
+        if book:
+            e.set_openings(book)
         while e.running():
             e.step(8)
             while (r := e.poll()) is not None:
@@ -161,7 +198,8 @@ def play_match(backend_a, backend_b, games: int, cfg: dict, seed: Optional[int] 
                 if pgn_out and (pgn_sample <= 0 or len(done) <= pgn_sample):
                     save_pgn(r["played_raw"], res, {"Event": "Matrix0 arena", "Round": r["game_index"] + 1,
                                                     "White": "A" if a_white else "B", "Black": "B" if a_white else "A",
-                                                    "Date": datetime.now().strftime("%Y.%m.%d")}, pgn_out, r["game_index"])
+                                                    "Date": datetime.now().strftime("%Y.%m.%d")}, pgn_out, r["game_index"],
+                             start_fen=r.get("start_fen"))
                 if progress is not None:
                     progress(len(done), games, a_wins, b_wins, draws)
     finally:
@@ -171,7 +209,7 @@ def play_match(backend_a, backend_b, games: int, cfg: dict, seed: Optional[int] 
     lo, hi = wilson_interval(win_rate, games)
     stats = {"games": games, "a_wins": a_wins, "b_wins": b_wins, "draws": draws, "score": score, "win_rate": win_rate,
              "wilson_low": lo, "wilson_high": hi, "seconds": time.perf_counter() - t0, "evals": float(st["evals"]),
-             "plies": float(st["plies"]), "records": done}
+             "evals_cached": float(st["evals_cached"]), "plies": float(st["plies"]), "records": done}
     if elo_book:
         book = {"best": 1500.0, "enhanced_best": 1500.0, "candidate": 1500.0, "baseline": 1500.0, "history": []}
         if os.path.exists(elo_book):

@@ -161,17 +161,22 @@ int m0_fen_after(const char* fen, const char* const* ucis, int n, char* fen_out,
     return M0_OK;
 }
 
-int m0_san_game(const uint16_t* moves, int n, char* out, int cap) {
-    if ((!moves && n > 0) || !out || cap <= 0) { m0_set_error("null argument"); return M0_ERR_INVALID; }
+int m0_san_game(const uint16_t* moves, int n, char* out, int cap) { return m0_san_game_fen(START_FEN, moves, n, out, cap); }
+
+int m0_san_game_fen(const char* fen, const uint16_t* moves, int n, char* out, int cap) {
+    if (!fen || (!moves && n > 0) || !out || cap <= 0) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     Line ln;
-    parse_fen(START_FEN, ln.pos);
+    if (parse_fen(fen, ln.pos) != 0) { m0_set_error("bad FEN"); return M0_ERR_INVALID; }
     std::string text;
     for (int i = 0; i < n; ++i) {
         const Pos before = ln.pos;
         Move mv[M0_MAX_MOVES];
         int k;
         if (!ln.play_if_legal(moves[i], mv, k)) { m0_set_error("illegal move in game"); return M0_ERR_INVALID; }
+        // the number in front of every White move and, as python-chess writes a line that Black opens, "12..." in front of
+        // the first move
         if (before.turn == WHITE) text += std::to_string(before.fullmove) + ". ";
+        else if (i == 0) text += std::to_string(before.fullmove) + "... ";
         text += san_of(before, moves[i], mv, k);
         text += ' ';
     }

@@ -7,7 +7,8 @@
 
 using namespace m0;
 
-static void fill_tree_cfg(const m0_selfplay_cfg& c, TreeCfg& t) {
+// `arena`: a match engine, whose cache switch is arena_eval_cache (eval_cache is ignored there: m0_engine.h)
+static void fill_tree_cfg(const m0_selfplay_cfg& c, bool arena, TreeCfg& t) {
     t.fpu_reduction = c.fpu_reduction; t.draw_penalty = c.draw_penalty; t.virtual_loss = c.virtual_loss;
     t.selection_jitter = c.selection_jitter; t.cpuct = c.cpuct; t.cpuct_start = c.cpuct_start; t.cpuct_end = c.cpuct_end;
     t.cpuct_plies = c.cpuct_plies; t.use_c_base = c.use_c_base; t.cpuct_c_base = c.cpuct_c_base; t.cpuct_c_init = c.cpuct_c_init;
@@ -17,7 +18,7 @@ static void fill_tree_cfg(const m0_selfplay_cfg& c, TreeCfg& t) {
     t.tt_merge = c.tt_merge; t.raw_legal_priors = c.raw_legal_priors; t.max_children = c.max_children;
     t.min_child_prior = c.min_child_prior;
     // the cached payload is the LEGAL logits: only the legal-softmax expansion can be served from it
-    t.eval_cache = (c.eval_cache && c.legal_softmax && !c.raw_legal_priors && !c.tt_merge) ? 1 : 0;
+    t.eval_cache = ((arena ? c.arena_eval_cache : c.eval_cache) && c.legal_softmax && !c.raw_legal_priors && !c.tt_merge) ? 1 : 0;
 }
 
 static void alloc_tree_arenas(m0_selfplay* sp) {
@@ -68,9 +69,11 @@ static bool alloc_eval_cache(m0_selfplay* sp) {
     while (sets * 4 < entries) sets <<= 1;
     EvalCache& ec = sp->d.ec;
     ec.sets = sets;
-    ec.keys = dalloc<uint64_t>(sp, (size_t)sp->G * sets * 4);
-    ec.stamps = dalloc<uint32_t>(sp, (size_t)sp->G * sets * 4);
-    ec.payload = dalloc<float>(sp, (size_t)sp->G * sets * 4 * M0_EC_WORDS);
+    ec.sides = sp->cfg.arena_mode ? 2 : 1;              // match engine: one instance per network
+    const size_t entries_all = (size_t)sp->G * ec.sides * sets * 4;
+    ec.keys = dalloc<uint64_t>(sp, entries_all);
+    ec.stamps = dalloc<uint32_t>(sp, entries_all);
+    ec.payload = dalloc<float>(sp, entries_all * M0_EC_WORDS);
     ec.hit_stage = dalloc<float>(sp, (size_t)sp->G * LS * M0_EC_WORDS);
     if (ec.keys && ec.stamps && ec.payload && ec.hit_stage) return true;
     m0_set_error("hipMalloc failed for the evaluation cache: lower eval_cache_entries or concurrent_games");
@@ -168,15 +171,17 @@ static m0_selfplay* selfplay_create_impl(m0_net* nh, m0_net* nh_b, const m0_self
     std::unique_ptr<m0_selfplay, decltype(&m0_selfplay_destroy)> owner(new m0_selfplay(), &m0_selfplay_destroy);
     m0_selfplay* sp = owner.get();
     sp->cfg = *cfg;
-    fill_tree_cfg(*cfg, sp->tc);
     sp->nethandle = nh;
     sp->nethandle_b = nh_b;
     sp->net = m0_net_impl(nh);
     sp->net_b = m0_net_impl(nh_b);
     sp->cfg.arena_mode = (nh_b || arena) ? 1 : 0;
     // A match engine alternates two networks in one game slot and the cache key covers the position only (no network id):
-    // side B's leaves would be expanded from side A's cached value and logits.  Off, whatever the caller asked for.
-    if (sp->cfg.arena_mode) { sp->cfg.eval_cache = 0; sp->tc.eval_cache = 0; }
+    // with ONE cache side B's leaves would be expanded from side A's cached value and logits.  eval_cache is therefore ignored
+    // there, whatever the caller asked for; arena_eval_cache gives each network a cache of its own (EvalCache::sides).
+    if (sp->cfg.arena_mode) sp->cfg.eval_cache = 0;
+    else { sp->cfg.arena_eval_cache = 0; sp->cfg.arena_paired_openings = 0; }
+    fill_tree_cfg(sp->cfg, sp->cfg.arena_mode != 0, sp->tc);
     sp->device = nh ? m0_net_device(nh) : 0;
     if (nh) forward_gate_join(sp);
     (void)hipSetDevice(sp->device);
@@ -229,6 +234,7 @@ int m0_selfplay_set_openings(m0_selfplay* sp, const char* const* fens, int n) {
     for (int i = 0; i < n; ++i)
         if (!fens[i] || parse_fen(fens[i], book[i]) != 0) { m0_set_error(std::string("bad FEN at index ") + std::to_string(i)); return M0_ERR_INVALID; }
     sp->book.swap(book);
+    sp->book_fens.assign(fens, fens + n);
     return M0_OK;
 }
 

@@ -1,5 +1,6 @@
-// Device side of the per-game evaluation cache (tree.h EvalCache describes what it holds and why): key, set address,
-// payload layout, probe (select_kernel), victim choice and publish (expand_kernel).  All functions are whole-wave.
+// Device side of the per-game evaluation cache (tree.h EvalCache describes what it holds and why): key, instance and set
+// address, payload layout, probe (select_kernel), victim choice and publish (expand_kernel), clear (advance_kernel).  All
+// functions are whole-wave.
 #pragma once
 #include "tree_device.h"
 
@@ -17,9 +18,19 @@ __device__ __forceinline__ uint64_t ec_key_of(const Pos& pos) {
     const uint64_t hm = pos.halfmove < 99 ? pos.halfmove : 99, fm = pos.fullmove < 199 ? pos.fullmove : 199;
     return mix64(tkey(pos) ^ ((hm << 8 | fm) * GOLDEN64)) | 1ull;
 }
-// first way of the key's set in game g's cache
-__device__ __forceinline__ size_t ec_set_of(const EvalCache& ec, int g, uint64_t ckey) {
-    return ((size_t)g * ec.sets + (size_t)((ckey >> 1) & (uint64_t)(ec.sets - 1))) * EC_WAYS;
+// The cache instance a search of game g works on: the game's own, or in a match engine (two per game) the one of the
+// network that evaluates the search.  Also the index of the instance's clock in GameDev::cache_clock.
+__device__ __forceinline__ int ec_side_of(const EvalCache& ec, const GameDev* gd) { return ec.sides == 2 ? (gd->net_id & 1) : 0; }
+// first way of the key's set in instance `side` of game g
+__device__ __forceinline__ size_t ec_set_of(const EvalCache& ec, int g, int side, uint64_t ckey) {
+    return (((size_t)g * ec.sides + side) * ec.sets + (size_t)((ckey >> 1) & (uint64_t)(ec.sets - 1))) * EC_WAYS;
+}
+// whole-wave: empty every instance of game g (a new game in a match engine's slot: the colours, hence the networks, swap)
+__device__ __forceinline__ void ec_clear_game(const EvalCache& ec, GameDev* gd, int g, int lane) {
+    const size_t n = (size_t)ec.sides * ec.sets * EC_WAYS;               // a multiple of 256 keys; the block is 16-byte aligned
+    uint4* k4 = reinterpret_cast<uint4*>(ec.keys + (size_t)g * n);
+    for (size_t i = lane; i < n / 2; i += 64) k4[i] = make_uint4(0, 0, 0, 0);
+    if (lane == 0) { gd->cache_clock[0] = 0; gd->cache_clock[1] = 0; }
 }
 // where select stages the payload of sample s's hit for expand (an insert of the same pass may evict the entry)
 __device__ __forceinline__ float* ec_hit_stage(const TreeDev& d, int g, int s) {
@@ -42,7 +53,8 @@ __device__ __forceinline__ int legal_sig(const Move* mv, int n, int lane) {
 __device__ __forceinline__ bool ec_probe(const TreeDev& d, GameDev* gd, int g, int s, uint64_t ckey, const Move* legal, int nlegal,
                                          int lane) {
     bool cached = false;
-    const size_t eb = ec_set_of(d.ec, g, ckey);
+    const int side = ec_side_of(d.ec, gd);
+    const size_t eb = ec_set_of(d.ec, g, side, ckey);
     const uint64_t k = lane < EC_WAYS ? d.ec.keys[eb + lane] : 0ull;
     const unsigned long long hit = __ballot(lane < EC_WAYS && k == ckey);
     if (hit) {
@@ -51,15 +63,15 @@ __device__ __forceinline__ bool ec_probe(const TreeDev& d, GameDev* gd, int g, i
         float* dst = ec_hit_stage(d, g, s);
         for (int i = lane; i < M0_EC_WORDS; i += 64) dst[i] = src[i];
         cached = __float_as_int(src[EC_SIG]) == legal_sig(legal, nlegal, lane);
-        if (cached && lane == 0) { d.ec.stamps[eb + way] = ++gd->cache_clock; }
+        if (cached && lane == 0) { d.ec.stamps[eb + way] = ++gd->cache_clock[side]; }
     }
     return cached;
 }
 
 // The entry an evaluation under `ckey` goes to: the way that holds the key already, else an empty way, else the least
 // recently used one (lowest way on a tie).
-__device__ __forceinline__ size_t ec_choose_victim(const EvalCache& ec, int g, uint64_t ckey, int lane) {
-    const size_t eb = ec_set_of(ec, g, ckey);
+__device__ __forceinline__ size_t ec_choose_victim(const EvalCache& ec, const GameDev* gd, int g, uint64_t ckey, int lane) {
+    const size_t eb = ec_set_of(ec, g, ec_side_of(ec, gd), ckey);
     const uint64_t k = lane < EC_WAYS ? ec.keys[eb + lane] : 0ull;
     const uint32_t st = lane < EC_WAYS ? ec.stamps[eb + lane] : 0xffffffffu;
     const unsigned long long same = __ballot(lane < EC_WAYS && k == ckey), empty = __ballot(lane < EC_WAYS && k == 0ull);
@@ -82,5 +94,5 @@ __device__ __forceinline__ void ec_publish(const EvalCache& ec, GameDev* gd, siz
     float* cw = ec_payload(ec, ce);
     cw[EC_VALUE] = v; cw[EC_SIG] = __int_as_float(sig);
     __threadfence_block();
-    ec.keys[ce] = ckey; ec.stamps[ce] = ++gd->cache_clock;
+    ec.keys[ce] = ckey; ec.stamps[ce] = ++gd->cache_clock[ec_side_of(ec, gd)];
 }

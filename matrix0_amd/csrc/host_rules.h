@@ -12,7 +12,8 @@
 
 namespace m0 {
 
-enum { PURPOSE_JITTER = 1, PURPOSE_NOISE = 2, PURPOSE_DIRICHLET = 3, PURPOSE_GAME = 4 };
+// PURPOSE_PAIR_OPENING is keyed by a PAIR of match games (index k = games 2k and 2k+1), the others by a game
+enum { PURPOSE_JITTER = 1, PURPOSE_NOISE = 2, PURPOSE_DIRICHLET = 3, PURPOSE_GAME = 4, PURPOSE_PAIR_OPENING = 5 };
 
 inline uint64_t derive_seed(uint64_t base, int game, int purpose) {
     const uint64_t G = 0x9E3779B97F4A7C15ull;

@@ -79,6 +79,7 @@ static void finish_game(m0_selfplay* sp, int slot, bool resigned, int resigner, 
         o->z.resize(hgm.nstates);
         for (int i = 0; i < hgm.nstates; ++i) o->z[i] = z * (float)hgm.turns[i];
         o->played.assign(hgm.history.begin(), hgm.history.end());
+        if (hgm.book_index >= 0) o->start_fen = sp->book_fens[hgm.book_index];
         if (c.ssl_targets && (int)hgm.rec_pos.size() == hgm.nstates) {
             // targets for all plies of the game in one launch on the engine stream
             const int T = hgm.nstates;
@@ -107,6 +108,7 @@ static void finish_game(m0_selfplay* sp, int slot, bool resigned, int resigner, 
         r.s = o->s.data(); r.pi = o->pi.data(); r.z = o->z.data(); r.legal_mask = o->legal_mask.data();
         r.search_values = o->search_values.data(); r.played = o->played.data(); r.owner = o;
         r.ssl = o->ssl.empty() ? nullptr : o->ssl.data();
+        r.start_fen = hgm.book_index >= 0 ? o->start_fen.c_str() : nullptr;
         sp->done_meta.push_back(r);
     }
     hgm.in_use = false;
@@ -152,14 +154,21 @@ static void start_game(m0_selfplay* sp, int slot, std::vector<int>& adv_ids, std
     parse_fen(START_FEN, hgm.pos);
     hgm.rng = HStream(derive_seed(sp->cfg.seed, hgm.game_index, PURPOSE_GAME));
     if (!sp->book.empty()) {               // get_opening_position (internal.py:65-69): random.choice(OPENING_BOOK)
-        size_t k = (size_t)(hgm.rng.next() * (double)sp->book.size());
+        // a paired match: games 2k and 2k+1 share the draw of pair k's own stream (and leave their own streams alone), so each
+        // opening is played with both colours whichever slot takes the games and whenever they start
+        const bool paired = sp->cfg.arena_mode && sp->cfg.arena_paired_openings;
+        const double u = paired ? HStream(derive_seed(sp->cfg.seed, hgm.game_index / 2, PURPOSE_PAIR_OPENING)).next() : hgm.rng.next();
+        size_t k = (size_t)(u * (double)sp->book.size());
         if (k >= sp->book.size()) k = sp->book.size() - 1;
         hgm.pos = sp->book[k];
+        hgm.book_index = (int)k;
     }
     hgm.t0 = now_ms();
     hgm.a_is_white = (hgm.game_index % 2) == 0;               // arena.py:66
     seed_game_dev(sp->hg[slot], sp->cfg.seed, hgm.game_index);
     sp->hg[slot].evals = 0;
+    // a match engine's caches hold what each NETWORK said; the next game of the slot swaps the colours (advance_kernel clears)
+    if (sp->cfg.arena_mode && sp->tc.eval_cache) sp->hg[slot].ec_clear = 1;
     // opening diversity: uniform random legal plies (internal.py:366-379; random.choice -> injected stream)
     for (int i = 0; i < sp->cfg.opening_random_plies; ++i) {
         if (is_game_over(hgm.pos, hgm.win, false)) break;

@@ -26,6 +26,7 @@ struct GameRecordOwner {
     std::vector<float> s, pi, z, search_values, ssl;
     std::vector<uint8_t> legal_mask;
     std::vector<uint16_t> played;
+    std::string start_fen;
 };
 
 struct HostGame : Line {                  // pos, win, history (all moves incl. opening plies)
@@ -45,6 +46,7 @@ struct HostGame : Line {                  // pos, win, history (all moves incl. 
     double t0 = 0.0;
     int cur_sims = 0;
     bool a_is_white = true;               // arena
+    int book_index = -1;                  // the opening-book position the game started from, -1 = the initial position
 };
 
 }  // namespace m0
@@ -88,6 +90,7 @@ struct m0_selfplay {
     int last_rows = 0, last_rows_b = 0;
     int rows2[2] = {0, 0};                // rows of the last select per network
     std::vector<m0::Pos> book;            // opening positions (m0_selfplay_set_openings)
+    std::vector<std::string> book_fens;   // ... as the caller wrote them (m0_game_record::start_fen)
     // LRUCache nn_cache of the reference (mcts.py:44-59, 303, 360-371): positions whose root was re-evaluated; 10 000 entries
     std::list<uint64_t> nn_lru;
     std::unordered_map<uint64_t, std::list<uint64_t>::iterator> nn_map;

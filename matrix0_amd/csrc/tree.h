@@ -46,14 +46,17 @@ struct TreeCfg {              // MCTSConfig fields the kernels read (mcts.py:61-
 // network evaluation.  Same role as the reference's position table, which never evaluates a transposed node twice
 // (mcts.py:919), and its nn_cache (mcts.py:44-59); results are unchanged because the 320-wide forward is bitwise batch
 // invariant (a fresh evaluation would return the very same numbers).  4-way set associative, least recently used way replaced.
+// A match engine (cfg.arena_eval_cache) keeps `sides` = 2 instances per game, one per network, each with its own clock:
+// instance (game, GameDev::net_id) holds only what that network said, and the search it evaluates sees no other.
 #define M0_EC_MAXLEGAL 64     // positions with more legal moves are not cached
 #define M0_EC_WORDS 66        // payload floats per entry: value, nlegal (as int bits), 64 logits
 struct EvalCache {
-    uint64_t* keys;           // [G][sets * 4], 0 = empty
-    uint32_t* stamps;         // [G][sets * 4] last use (per-game clock)
-    float* payload;           // [G][sets * 4][M0_EC_WORDS]
+    uint64_t* keys;           // [G][sides][sets * 4], 0 = empty
+    uint32_t* stamps;         // [G][sides][sets * 4] last use (the instance's clock, GameDev::cache_clock)
+    float* payload;           // [G][sides][sets * 4][M0_EC_WORDS]
     float* hit_stage;         // [G][L + 1][M0_EC_WORDS] payload of this pass's hits (an insert of the same pass may evict the entry)
-    int sets;                 // per game, a power of two; 0 = cache off
+    int sets;                 // per instance, a power of two; 0 = cache off
+    int sides;                // instances per game: 1, or 2 in a match engine (one per network)
 };
 
 // Per-game control block (host writes between steps, kernels update counters).
@@ -82,7 +85,8 @@ struct GameDev {
     int reinfer;              // evaluate the (reused) root once more at the first select of this search (mcts.py:359-371)
     // match engine with compat.tt_merge (TreeDev::tt_sides == 2): arena half s and table s belong to side s for the WHOLE game
     uint64_t cache_hits;      // leaf evaluations served by the evaluation cache
-    uint32_t cache_clock;
+    uint32_t cache_clock[2];  // per cache instance (self-play: [0] only)
+    int ec_clear;             // match engine: this slot starts a new game -- advance_kernel empties both of its caches
     int side_next[2];         // bump allocator of each side's half while the other side searches
     int root_found;           // advance_kernel: this search's root was found in the side's table (mcts.py:343, 359-371)
 };

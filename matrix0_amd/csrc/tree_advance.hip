@@ -2,7 +2,9 @@
 //   child_slot >= 0  keep that child's subtree, compacted breadth-first into the other arena half
 //   child_slot == -1 fresh tree (and an empty position table)
 //   child_slot <= -2 match engine with per-side tables (tt_sides == 2): the root is looked up in the side's table
+// and, before any of these, the slot's evaluation caches are emptied when the host flagged a new game (GameDev::ec_clear).
 #include "tree_device.h"
+#include "eval_cache.h"
 
 // Per-side tables: side = the network that searches now.  Nothing is compacted or cleared between the searches of a game; the
 // root is whatever node the side's table holds for the position (MCTS.run: root = self._tt_get(key), mcts.py:343), else a new
@@ -83,6 +85,13 @@ __global__ __launch_bounds__(64) void advance_kernel(TreeDev d, const int* game_
     if (j >= count) return;
     const int g = game_ids[j], slot = child_slots[j];
     GameDev* gd = &d.games[g];
+    // a match engine's slot starts a new game: what its two networks said about the last game's positions goes.  (Nothing of
+    // this launch reads the keys again: select_kernel's probes are a later launch.)
+    const bool new_game = gd->ec_clear != 0;
+    if (new_game) {
+        if (d.ec.sets > 0) ec_clear_game(d.ec, gd, g, lane);
+        if (lane == 0) gd->ec_clear = 0;
+    }
     if (slot <= -2) reroot_from_table(d, gd, g, slot, lane);
     else if (slot < 0) reroot_fresh(d, gd, g, lane);
     else reroot_keep_subtree(d, gd, g, slot, lane);

@@ -294,7 +294,7 @@ __device__ __forceinline__ void expand_evaluated(const TreeDev& d, const TreeCfg
     size_t ce = 0;
     const uint64_t ckey = kind == SK_EVAL ? smp.ckey : 0ull;
     if (ckey != 0 && isfinite(v)) {
-        ce = ec_choose_victim(d.ec, g, ckey, lane);
+        ce = ec_choose_victim(d.ec, gd, g, ckey, lane);
         cw = ec_payload(d.ec, ce);
         ec_invalidate(d.ec, ce, lane);                  // invalid while it is being rewritten
     }

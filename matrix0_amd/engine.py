@@ -31,7 +31,7 @@ class SelfplayCfg(C.Structure):
         ("arena_mode", c_int), ("arena_temp", c_double), ("arena_temp_plies", c_int),
         ("fresh_tree_per_move", c_int), ("tt_merge", c_int), ("raw_legal_priors", c_int), ("max_children", c_int),
         ("min_child_prior", c_double), ("root_reinfer", c_int), ("eval_cache", c_int), ("eval_cache_entries", c_int),
-        ("tail_split", c_int),
+        ("tail_split", c_int), ("arena_eval_cache", c_int), ("arena_paired_openings", c_int),
     ]
 
 
@@ -47,7 +47,8 @@ class GameRecord(C.Structure):
                 ("total_plies", c_int), ("result", C.c_float), ("avg_policy_entropy", C.c_float), ("avg_sims", C.c_float),
                 ("secs", c_double), ("s", C.POINTER(C.c_float)), ("pi", C.POINTER(C.c_float)), ("z", C.POINTER(C.c_float)),
                 ("legal_mask", C.POINTER(C.c_uint8)), ("search_values", C.POINTER(C.c_float)),
-                ("played", C.POINTER(C.c_uint16)), ("ssl", C.POINTER(C.c_float)), ("owner", C.c_void_p)]
+                ("played", C.POINTER(C.c_uint16)), ("ssl", C.POINTER(C.c_float)), ("owner", C.c_void_p),
+                ("start_fen", C.c_char_p)]
 
 
 _bound = False
@@ -68,6 +69,7 @@ def _bind():
     L.m0_arena_ext_expand.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, c_int, C.c_void_p, C.c_void_p, c_int]
     L.m0_san_legal_fen.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.POINTER(c_int)]
     L.m0_san_game.argtypes = [C.c_void_p, c_int, C.c_char_p, c_int]
+    L.m0_san_game_fen.argtypes = [C.c_char_p, C.c_void_p, c_int, C.c_char_p, c_int]
     L.m0_fen_after.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), c_int, C.c_char_p, c_int]
     L.m0_selfplay_destroy.argtypes = [C.c_void_p]
     L.m0_selfplay_destroy.restype = None
@@ -246,6 +248,8 @@ class SelfplayEngine:
                 "played_raw": (np.ctypeslib.as_array(r.played, shape=(r.total_plies,)).copy()
                                if r.total_plies > 0 else np.zeros(0, np.uint16)),
             }
+            if r.start_fen:                                    # the game started from an opening-book position
+                out["start_fen"] = r.start_fen.decode()
             if r.s and T > 0:                                  # arena records carry only the moves and the result
                 out["s"] = np.ctypeslib.as_array(r.s, shape=(T, 19, 8, 8)).copy()
                 out["pi"] = np.ctypeslib.as_array(r.pi, shape=(T, 4672)).copy()
@@ -481,7 +485,9 @@ def ssl_targets_fens(fens, device_index: int = 0) -> dict:
 
 class ArenaEngine(SelfplayEngine):
     """Evaluation match engine (m0_arena_create): game i has `backend_a` as White when i is even; step / poll / stats as
-    SelfplayEngine.  Records carry `played`, `result` (White's point of view) and `moves`."""
+    SelfplayEngine.  Records carry `played`, `result` (White's point of view) and `moves`, and `start_fen` when the game began
+    from an opening-book position (`set_openings`; `cfg.arena_paired_openings` pairs games 2k and 2k+1 on one position).
+    `cfg.arena_eval_cache` gives each network an evaluation cache per game (`cfg.eval_cache` is ignored here)."""
 
     def __init__(self, backend_a, backend_b, cfg: SelfplayCfg):
         self._L = _bind()
@@ -552,12 +558,16 @@ def fen_after(fen: str, ucis) -> str:
     return buf.value.decode()
 
 
-def san_game(moves_raw) -> str:
-    """Movetext '1. e4 e5 2. Nf3 ...' of a game from the start position (moves as in a record's `played_raw`)."""
+def san_game(moves_raw, fen: Optional[str] = None) -> str:
+    """Movetext '1. e4 e5 2. Nf3 ...' of a game (moves as in a record's `played_raw`) from the start position or from `fen`
+    (a record's `start_fen`); the move numbers follow the FEN, '12... Nf6 13. e4' when Black moves first."""
     L = _bind()
     mv = np.ascontiguousarray(moves_raw, dtype=np.uint16)
     buf = C.create_string_buffer(16 * (len(mv) + 4))
-    rc = L.m0_san_game(mv.ctypes.data_as(C.c_void_p), int(len(mv)), buf, len(buf))
+    if fen is None:
+        rc = L.m0_san_game(mv.ctypes.data_as(C.c_void_p), int(len(mv)), buf, len(buf))
+    else:
+        rc = L.m0_san_game_fen(fen.encode(), mv.ctypes.data_as(C.c_void_p), int(len(mv)), buf, len(buf))
     if rc < 0:
         _lib.check(rc, "m0_san_game")
     return buf.value.decode().strip()
