@@ -20,6 +20,7 @@
 #ifndef M0_ENGINE_H
 #define M0_ENGINE_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -330,6 +331,54 @@ int m0_search_result(m0_selfplay* sp, int g, int* nchild, int32_t* child_n, uint
                      double* child_prior, double* child_q, double* root_q, int* root_n, int* finished);
 /* play child slot `slot` of the finished search in g and keep its subtree (tree reuse across moves) */
 int m0_search_advance(m0_selfplay* sp, int g, int slot, int sims, int dirichlet);
+
+/* ---- batched position analysis (the reference's MCTS.run(board) for a list of arbitrary positions) ----
+ * An analysis engine plays no games: positions are submitted with an id, searched in the engine's tree slots on the device
+ * (select -> network -> expand, the kernels of m0_selfplay_step) and answered with the best root moves, the principal
+ * variation behind each and the evaluation.  Every analysis is a fresh tree whose random streams are keyed by (cfg->seed, id):
+ * a result does not depend on the slot, the number of slots or what else is in flight.  (The streams take the low 32 bits
+ * of id.)
+ * cfg: concurrent_games = tree slots, inference_batch_size and the MCTS fields as a self-play engine reads them;
+ * num_simulations sizes the node arenas (a submission with more simulations may report `overflow`).  The self-play, draw and
+ * arena fields, eval_cache and tail_split are ignored; tt_merge / raw_legal_priors are refused (NULL, the message starts with
+ * "M0_ERR_UNSUPPORTED").  Destroy and stats with m0_selfplay_destroy / m0_selfplay_stats_get.  m0_selfplay_step, _poll,
+ * _ext_*, _set_openings and m0_search_* on an analysis engine return M0_ERR_STATE, as m0_analysis_* do on any other engine. */
+#define M0_AN_MAX_LINES 8
+#define M0_AN_MAX_PV    16
+typedef struct m0_analysis_opts { int multipv, pv_len, dirichlet; } m0_analysis_opts;   /* 1..8, 1..16, bool */
+typedef struct m0_analysis_line {
+    uint16_t move; int32_t policy_index; int32_t visits; float prior; double q;   /* the root child */
+    int32_t pv_len; uint16_t pv[M0_AN_MAX_PV];                                    /* pv[0] == move; unused entries 0 */
+} m0_analysis_line;
+typedef struct m0_analysis_result {
+    int64_t id; int32_t status;      /* 0 searched/evaluated, 1 side to move is checkmated, 2 stalemate */
+    int32_t nlegal, overflow, sims, root_n; uint64_t evals;
+    float value;                     /* network value of the root evaluation (side to move) */
+    double root_q; int32_t nlines; m0_analysis_line lines[M0_AN_MAX_LINES];
+} m0_analysis_result;
+m0_selfplay* m0_analysis_create(m0_net* net, const m0_selfplay_cfg* cfg, const m0_analysis_opts* opts);
+m0_selfplay* m0_analysis_create_ext(const m0_selfplay_cfg* cfg, const m0_analysis_opts* opts);   /* external evaluator */
+/* Queue the position `fen` after the n_moves legal moves `ucis` (nullable when n_moves = 0): the moves go through the
+ * repetition window of a game, so the search sees repetitions with the positions before it.  The queue is unbounded.
+ * A bad FEN or an illegal move: M0_ERR_INVALID, nothing queued.  A root without legal moves is answered at once (status 1 / 2,
+ * nlines 0, no evaluation) and never takes a slot.
+ * sims > 0: a search of that many simulations; lines are the root children by visits (ties: move order), each with the
+ *           most-visited line behind it (first maximum in move order; it ends at an unexpanded or terminal node, at a node
+ *           without visited children, or at opts->pv_len).
+ * sims = 0: policy mode, no tree: one network evaluation; lines are the legal moves by legal-softmax prior (ties: move order),
+ *           visits 0, pv_len 1, root_n 0, evals 1, value the network's raw value.  Engines with a network only
+ *           (m0_analysis_create_ext: M0_ERR_UNSUPPORTED). */
+int m0_analysis_submit(m0_selfplay* sp, const char* fen, const char* const* ucis, int n_moves, int sims, int64_t id);
+/* `steps` times: evaluate up to concurrent_games * (inference_batch_size + 1) queued policy-mode positions, fill free slots
+ * from the queue, run one select -> network -> expand pass, harvest the finished searches (only the compact results cross
+ * to the host).  Stops early when nothing is pending. */
+int m0_analysis_step(m0_selfplay* sp, int steps);
+/* The step split at the network, as m0_selfplay_ext_select / _expand (same buffer rule for max_rows). */
+int m0_analysis_ext_select(m0_selfplay* sp, int* rows, float* planes, int max_rows);
+int m0_analysis_ext_expand(m0_selfplay* sp, const float* logits, const float* values, int rows);
+int m0_analysis_poll(m0_selfplay* sp, m0_analysis_result* out);   /* 1 written, 0 none; completion order */
+int m0_analysis_pending(m0_selfplay* sp);                         /* queued + in flight (answered ones not counted) */
+size_t m0_analysis_result_size(void);                             /* sizeof(m0_analysis_result), for foreign mirrors */
 
 /* ---- host decision functions (selfplay/internal.py), exposed for parity tests ---- */
 int m0_sample_move_index(const int32_t* visits, int n, double temperature, double u);

@@ -1,0 +1,261 @@
+// extern "C" entry points of the analysis engine (include/m0_engine.h): a list of arbitrary positions in, the best moves, the
+// lines behind them and the evaluation out.  The engine is a self-play engine object that plays no games: its tree slots are
+// filled from a host queue (analysis_refill), searched by the pass of m0_selfplay_step (one_step / the external-evaluator
+// pair) and emptied by the result kernel (analysis_harvest); positions that ask for no search go through the position
+// encoder, one forward and the policy kernel (policy_pass).
+#include <string.h>
+#include <algorithm>
+#include <memory>
+#include "selfplay_engine.h"
+
+using namespace m0;
+
+namespace m0 {
+
+static int pending_count(const m0_selfplay* sp) {
+    int n = (int)(sp->an->queue.size() + sp->an->policy_queue.size());
+    for (const HostGame& hgm : sp->games) n += hgm.in_use ? 1 : 0;
+    return n;
+}
+
+static m0_analysis_result blank_result(const AnalysisJob& job) {
+    m0_analysis_result r;
+    memset(&r, 0, sizeof(r));
+    r.id = job.id; r.nlegal = job.nlegal; r.sims = job.sims;
+    return r;
+}
+
+// Free slots take the next queued searches: a fresh tree each, random streams keyed by the submission's id (not by the slot).
+int analysis_refill(m0_selfplay* sp, std::string& err) {
+    Analysis& a = *sp->an;
+    std::vector<int> ids, slots;
+    for (int s = 0; s < sp->G && !a.queue.empty(); ++s) {
+        HostGame& hgm = sp->games[s];
+        if (hgm.in_use) continue;
+        AnalysisJob& job = a.queue.front();
+        hgm = HostGame();
+        hgm.in_use = true;
+        hgm.game_index = (int)job.id;
+        static_cast<Line&>(hgm) = std::move(job.line);
+        a.slot_job[s] = AnalysisJob{Line(), job.sims, job.nlegal, job.id};
+        a.queue.pop_front();
+        GameDev& g = sp->hg[s];
+        seed_game_dev(g, sp->cfg.seed, hgm.game_index);
+        g.evals = 0; g.net_id = 0;
+        arm_search(sp, s, hgm.pos, hgm.win, a.slot_job[s].sims, a.opts.dirichlet != 0, true);
+        ids.push_back(s);
+        slots.push_back(-1);
+    }
+    if (!ids.empty() && apply_advances(sp, ids, slots) != 0) { err = "advance failed"; return M0_ERR_HIP; }
+    return M0_OK;
+}
+
+// The searches that the last expand finished: their lines from the result kernel (the trees stay on the device), the rest
+// from the slots' control blocks, which the step has just mirrored.  The slots are free afterwards.
+int analysis_harvest(m0_selfplay* sp, std::string& err) {
+    Analysis& a = *sp->an;
+    a.finished.clear();
+    for (int s = 0; s < sp->G; ++s)
+        if (sp->hg[s].active && sp->hg[s].finished) a.finished.push_back(s);
+    const int nf = (int)a.finished.size();
+    if (nf == 0) return M0_OK;
+    if (hipMemcpyAsync(sp->ids_dev, a.finished.data(), (size_t)nf * 4, hipMemcpyHostToDevice, sp->stream) != hipSuccess ||
+        launch_analysis_lines(sp->d, sp->ids_dev, nf, a.opts.multipv, a.opts.pv_len, a.lines_dev, a.nlines_dev, sp->stream) != hipSuccess ||
+        hipMemcpyAsync(a.hlines.data(), a.lines_dev, sizeof(m0_analysis_line) * M0_AN_MAX_LINES * nf, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
+        hipMemcpyAsync(a.hnlines.data(), a.nlines_dev, (size_t)nf * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
+        hipStreamSynchronize(sp->stream) != hipSuccess) {
+        err = std::string("analysis harvest failed: ") + hipGetErrorString(hipGetLastError());
+        return M0_ERR_HIP;
+    }
+    for (int j = 0; j < nf; ++j) {
+        const int s = a.finished[j];
+        GameDev& g = sp->hg[s];
+        m0_analysis_result r = blank_result(a.slot_job[s]);
+        r.overflow = g.overflow; r.root_n = g.root_n; r.evals = g.evals;
+        r.value = (float)g.root_v;
+        r.root_q = g.root_n > 0 ? g.root_q : g.root_v;
+        r.nlines = a.hnlines[j] < 0 ? 0 : (a.hnlines[j] > M0_AN_MAX_LINES ? M0_AN_MAX_LINES : a.hnlines[j]);
+        for (int l = 0; l < r.nlines; ++l) r.lines[l] = a.hlines[(size_t)j * M0_AN_MAX_LINES + l];
+        if (g.overflow) sp->stats.arena_overflows++;
+        a.done.push_back(r);
+        g.active = 0; g.finished = 0;
+        sp->games[s].in_use = false;
+    }
+    std::vector<int> none;
+    if (apply_advances(sp, none, none) != 0) { err = "releasing the slots failed"; return M0_ERR_HIP; }   // the control blocks -> device
+    return M0_OK;
+}
+
+// Policy mode: up to rows_max queued positions -> network input, legal moves and policy indices (the position encoder), one
+// forward, the policy kernel; the compact lines come back.
+static int policy_pass(m0_selfplay* sp, std::string& err) {
+    Analysis& a = *sp->an;
+    const int n = (int)std::min<size_t>(a.policy_queue.size(), (size_t)sp->rows_max);
+    if (n <= 0) return M0_OK;
+    const double t0 = now_ms();
+    for (int i = 0; i < n; ++i) a.hpos[i] = a.policy_queue[i].line.pos;
+    if (hipMemcpyAsync(a.pos_dev, a.hpos.data(), sizeof(Pos) * n, hipMemcpyHostToDevice, sp->stream) != hipSuccess ||
+        launch_encode_positions(a.pos_dev, n, nullptr, sp->d.x0, nullptr, a.nlegal_dev, a.moves_dev, a.idx_dev, sp->stream) != hipSuccess) {
+        err = "position encode failed";
+        return M0_ERR_HIP;
+    }
+    m0_net_lock(sp->nethandle);
+    const int rc = sp->net->forward(nullptr, sp->d.x0, n, sp->logits_dev, sp->values_dev, nullptr, sp->stream, err);
+    m0_net_unlock(sp->nethandle);
+    if (rc != M0_OK) return rc;
+    if (launch_policy_lines(sp->logits_dev, sp->values_dev, a.nlegal_dev, a.moves_dev, a.idx_dev, n, a.opts.multipv, a.lines_dev,
+                            a.nlines_dev, a.value_out_dev, sp->stream) != hipSuccess ||
+        hipMemcpyAsync(a.hlines.data(), a.lines_dev, sizeof(m0_analysis_line) * M0_AN_MAX_LINES * n, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
+        hipMemcpyAsync(a.hnlines.data(), a.nlines_dev, (size_t)n * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
+        hipMemcpyAsync(a.hvalues.data(), a.value_out_dev, (size_t)n * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
+        hipStreamSynchronize(sp->stream) != hipSuccess) {
+        err = std::string("policy pass failed: ") + hipGetErrorString(hipGetLastError());
+        return M0_ERR_HIP;
+    }
+    for (int i = 0; i < n; ++i) {
+        m0_analysis_result r = blank_result(a.policy_queue.front());
+        r.evals = 1;
+        r.value = a.hvalues[i];
+        r.root_q = (double)r.value;
+        r.nlines = a.hnlines[i] < 0 ? 0 : (a.hnlines[i] > M0_AN_MAX_LINES ? M0_AN_MAX_LINES : a.hnlines[i]);
+        for (int l = 0; l < r.nlines; ++l) r.lines[l] = a.hlines[(size_t)i * M0_AN_MAX_LINES + l];
+        a.done.push_back(r);
+        a.policy_queue.pop_front();
+    }
+    sp->stats.evals += (uint64_t)n;
+    sp->stats.ms_total += now_ms() - t0;
+    return M0_OK;
+}
+
+static m0_selfplay* analysis_create_impl(m0_net* nh, const m0_selfplay_cfg* cfg, const m0_analysis_opts* opts) {
+    if (!cfg || !opts) { m0_set_error("cfg / opts is null"); return nullptr; }
+    if (opts->multipv < 1 || opts->multipv > M0_AN_MAX_LINES || opts->pv_len < 1 || opts->pv_len > M0_AN_MAX_PV) {
+        m0_set_error("multipv must be in [1, 8] and pv_len in [1, 16]");
+        return nullptr;
+    }
+    if (cfg->tt_merge || cfg->raw_legal_priors) {
+        m0_set_error("M0_ERR_UNSUPPORTED: an analysis engine searches plain trees (tt_merge / raw_legal_priors are refused)");
+        return nullptr;
+    }
+    m0_selfplay_cfg c = *cfg;
+    // no games are played: every analysis is a fresh tree of exactly the simulations it asks for
+    c.total_games = 0; c.record_games = 0; c.ssl_in_forward = 0; c.ssl_targets = 0; c.opening_random_plies = 0;
+    c.playout_random_frac = 0.0; c.fresh_tree_per_move = 1; c.root_reinfer = 0;
+    c.arena_mode = 0; c.arena_eval_cache = 0; c.arena_paired_openings = 0; c.eval_cache = 0; c.tail_split = 0;
+    std::unique_ptr<m0_selfplay, decltype(&m0_selfplay_destroy)> owner(engine_create(nh, nullptr, &c, false), &m0_selfplay_destroy);
+    m0_selfplay* sp = owner.get();
+    if (!sp) return nullptr;
+    Analysis* a = sp->an = new Analysis();
+    a->opts = *opts;
+    const size_t R = (size_t)sp->rows_max;
+    a->slot_job.resize(sp->G);
+    a->hlines.resize(R * M0_AN_MAX_LINES);
+    a->hnlines.resize(R);
+    a->hvalues.resize(R);
+    a->hpos.resize(R);
+    a->lines_dev = dalloc<m0_analysis_line>(sp, R * M0_AN_MAX_LINES);
+    a->nlines_dev = dalloc<int>(sp, R);
+    a->value_out_dev = dalloc<float>(sp, R);
+    if (sp->net) {                         // policy mode needs the engine's own network
+        a->pos_dev = dalloc<Pos>(sp, R);
+        a->nlegal_dev = dalloc<int32_t>(sp, R);
+        a->moves_dev = dalloc<uint16_t>(sp, R * M0_MAX_MOVES);
+        a->idx_dev = dalloc<int32_t>(sp, R * M0_MAX_MOVES);
+    }
+    if (sp->alloc_failed || hipStreamSynchronize(sp->stream) != hipSuccess) {
+        m0_set_error("hipMalloc failed for the analysis result buffers");
+        return nullptr;
+    }
+    return owner.release();
+}
+
+}  // namespace m0
+
+extern "C" {
+
+m0_selfplay* m0_analysis_create(m0_net* net, const m0_selfplay_cfg* cfg, const m0_analysis_opts* opts) {
+    if (!net) { m0_set_error("m0_analysis_create needs a network (m0_analysis_create_ext takes an external evaluator)"); return nullptr; }
+    return analysis_create_impl(net, cfg, opts);
+}
+
+m0_selfplay* m0_analysis_create_ext(const m0_selfplay_cfg* cfg, const m0_analysis_opts* opts) {
+    return analysis_create_impl(nullptr, cfg, opts);
+}
+
+// Head of every m0_analysis_* call: the engine's lock and device; any other engine is refused with M0_ERR_STATE.
+#define M0_ANALYSIS_ENGINE(sp, what)                                                          \
+    if (!(sp)) { m0_set_error("sp is null"); return M0_ERR_INVALID; }                         \
+    std::lock_guard<std::mutex> lk((sp)->mu);                                                 \
+    if (!(sp)->an) { m0_set_error(what ": not an analysis engine"); return M0_ERR_STATE; }    \
+    (void)hipSetDevice((sp)->device)
+
+int m0_analysis_submit(m0_selfplay* sp, const char* fen, const char* const* ucis, int n_moves, int sims, int64_t id) {
+    M0_ANALYSIS_ENGINE(sp, "m0_analysis_submit");
+    if (!fen || sims < 0 || n_moves < 0 || (n_moves > 0 && !ucis)) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
+    if (sims == 0 && !sp->net) { m0_set_error("policy mode (sims = 0) needs an engine with a network"); return M0_ERR_UNSUPPORTED; }
+    AnalysisJob job;
+    job.sims = sims; job.id = id;
+    if (parse_fen(fen, job.line.pos) != 0) { m0_set_error("bad FEN"); return M0_ERR_INVALID; }
+    Move legal[M0_MAX_MOVES];
+    int n = 0;
+    for (int i = 0; i < n_moves; ++i) {
+        if (!job.line.play_if_legal(ucis[i] ? parse_uci(ucis[i]) : (Move)0xFFFF, legal, n)) {
+            m0_set_error(std::string("Illegal move: ") + (ucis[i] ? ucis[i] : "(null)"));
+            return M0_ERR_INVALID;
+        }
+    }
+    job.nlegal = gen_legal(job.line.pos, legal);
+    if (job.nlegal == 0) {                 // no search, no evaluation, no slot
+        m0_analysis_result r = blank_result(job);
+        r.status = in_check(job.line.pos) ? 1 : 2;
+        sp->an->done.push_back(r);
+        return M0_OK;
+    }
+    (sims == 0 ? sp->an->policy_queue : sp->an->queue).push_back(std::move(job));
+    return M0_OK;
+}
+
+int m0_analysis_step(m0_selfplay* sp, int steps) {
+    M0_ANALYSIS_ENGINE(sp, "m0_analysis_step");
+    if (!sp->net) { m0_set_error("m0_analysis_step needs a network (use m0_analysis_ext_select / _expand without one)"); return M0_ERR_STATE; }
+    if (sp->ext_pending) { m0_set_error("m0_analysis_ext_expand outstanding"); return M0_ERR_STATE; }
+    std::string err;
+    for (int i = 0; i < steps && pending_count(sp) > 0; ++i) {
+        int rc = policy_pass(sp, err);
+        if (rc == M0_OK) rc = analysis_refill(sp, err);
+        bool searching = false;
+        for (const HostGame& hgm : sp->games) searching = searching || hgm.in_use;
+        if (rc == M0_OK && searching) rc = one_step(sp, err);
+        if (rc != M0_OK) { m0_set_error(err); return rc; }
+    }
+    return M0_OK;
+}
+
+int m0_analysis_ext_select(m0_selfplay* sp, int* rows, float* planes, int max_rows) {
+    M0_ANALYSIS_ENGINE(sp, "m0_analysis_ext_select");
+    if (!rows) { m0_set_error("null argument"); return M0_ERR_INVALID; }
+    return ext_select_impl(sp, rows, nullptr, planes, nullptr, max_rows);
+}
+
+int m0_analysis_ext_expand(m0_selfplay* sp, const float* logits, const float* values, int rows) {
+    M0_ANALYSIS_ENGINE(sp, "m0_analysis_ext_expand");
+    return ext_expand_impl(sp, logits, values, rows, nullptr, nullptr, 0);
+}
+
+int m0_analysis_poll(m0_selfplay* sp, m0_analysis_result* out) {
+    M0_ANALYSIS_ENGINE(sp, "m0_analysis_poll");
+    if (!out) { m0_set_error("null argument"); return M0_ERR_INVALID; }
+    if (sp->an->done.empty()) return 0;
+    *out = sp->an->done.front();
+    sp->an->done.pop_front();
+    return 1;
+}
+
+int m0_analysis_pending(m0_selfplay* sp) {
+    M0_ANALYSIS_ENGINE(sp, "m0_analysis_pending");
+    return pending_count(sp);
+}
+
+size_t m0_analysis_result_size(void) { return sizeof(m0_analysis_result); }
+
+}  // extern "C"

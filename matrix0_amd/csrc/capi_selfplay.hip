@@ -157,9 +157,7 @@ static bool build_engine(m0_selfplay* sp) {
     return true;
 }
 
-extern "C" {
-
-static m0_selfplay* selfplay_create_impl(m0_net* nh, m0_net* nh_b, const m0_selfplay_cfg* cfg, bool arena = false) {
+m0_selfplay* m0::engine_create(m0_net* nh, m0_net* nh_b, const m0_selfplay_cfg* cfg, bool arena) {
     if (!cfg) { m0_set_error("cfg is null"); return nullptr; }
     if (cfg->concurrent_games <= 0 || cfg->inference_batch_size <= 0 || cfg->num_simulations <= 0) {
         m0_set_error("concurrent_games, inference_batch_size and num_simulations must be positive");
@@ -195,49 +193,6 @@ static m0_selfplay* selfplay_create_impl(m0_net* nh, m0_net* nh_b, const m0_self
     return build_engine(sp) ? owner.release() : nullptr;
 }
 
-m0_selfplay* m0_selfplay_create(m0_net* nh, const m0_selfplay_cfg* cfg) { return selfplay_create_impl(nh, nullptr, cfg); }
-
-m0_selfplay* m0_arena_create(m0_net* net_a, m0_net* net_b, const m0_selfplay_cfg* cfg) {
-    if (!net_a || !net_b) { m0_set_error("m0_arena_create needs two networks"); return nullptr; }
-    if (m0_net_device(net_a) != m0_net_device(net_b)) { m0_set_error("both networks must live on the same HIP device"); return nullptr; }
-    if (cfg && (cfg->ssl_in_forward || cfg->ssl_targets)) { m0_set_error("arena games carry no SSL outputs"); return nullptr; }
-    return selfplay_create_impl(net_a, net_b, cfg);
-}
-
-m0_selfplay* m0_arena_create_ext(const m0_selfplay_cfg* cfg) {
-    if (cfg && (cfg->ssl_in_forward || cfg->ssl_targets)) { m0_set_error("arena games carry no SSL outputs"); return nullptr; }
-    return selfplay_create_impl(nullptr, nullptr, cfg, true);
-}
-
-void m0_selfplay_destroy(m0_selfplay* sp) {
-    if (!sp) return;
-    forward_gate_leave(sp);
-    (void)hipSetDevice(sp->device);
-    if (sp->stream) (void)hipStreamSynchronize(sp->stream);
-    if (sp->stream_tail) (void)hipStreamSynchronize(sp->stream_tail);
-    delete sp->net_tail;
-    if (sp->ev_sel) (void)hipEventDestroy(sp->ev_sel);
-    if (sp->ev_tail) (void)hipEventDestroy(sp->ev_tail);
-    if (sp->stream_tail) (void)hipStreamDestroy(sp->stream_tail);
-    for (void* p : sp->allocs) (void)hipFree(p);
-    for (auto& r : sp->done_meta) delete (GameRecordOwner*)r.owner;
-    if (sp->ev0) { (void)hipEventDestroy(sp->ev0); (void)hipEventDestroy(sp->ev1); (void)hipEventDestroy(sp->ev2); (void)hipEventDestroy(sp->ev3); }
-    if (sp->own_stream && sp->stream) (void)hipStreamDestroy(sp->stream);
-    delete sp;
-}
-
-int m0_selfplay_set_openings(m0_selfplay* sp, const char* const* fens, int n) {
-    if (!sp || n < 0 || (n > 0 && !fens)) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(sp->mu);
-    if (sp->stats.games_started != 0) { m0_set_error("set the opening book before the first step"); return M0_ERR_STATE; }
-    std::vector<Pos> book(n);
-    for (int i = 0; i < n; ++i)
-        if (!fens[i] || parse_fen(fens[i], book[i]) != 0) { m0_set_error(std::string("bad FEN at index ") + std::to_string(i)); return M0_ERR_INVALID; }
-    sp->book.swap(book);
-    sp->book_fens.assign(fens, fens + n);
-    return M0_OK;
-}
-
 // The leaves of the last select as f32 planes for an external evaluator: rows [0, rows_a) into planes_a and, for a match
 // engine, rows [net_row_base, net_row_base + rows_b) into planes_b (rows_b = 0 with one network).
 static int leaf_planes(m0_selfplay* sp, int rows_a, float* planes_a, int rows_b, float* planes_b) {
@@ -265,7 +220,7 @@ static void upload_eval(m0_selfplay* sp, size_t row_base, const float* logits, c
 
 // first half of a step for an external evaluator: select, then the leaves' planes on the host (region 0 = network A / the only
 // network, region 1 = network B of a match engine, whose rows start at d.net_row_base on the device)
-static int ext_select_impl(m0_selfplay* sp, int* rows_a, int* rows_b, float* planes_a, float* planes_b, int max_rows) {
+int m0::ext_select_impl(m0_selfplay* sp, int* rows_a, int* rows_b, float* planes_a, float* planes_b, int max_rows) {
     (void)hipSetDevice(sp->device);
     if (sp->ext_pending) { m0_set_error("m0_selfplay_ext_expand outstanding"); return M0_ERR_STATE; }
     // select applies virtual losses and reserves batch rows: refuse a buffer that cannot take the worst case BEFORE it runs
@@ -274,7 +229,12 @@ static int ext_select_impl(m0_selfplay* sp, int* rows_a, int* rows_b, float* pla
         m0_set_error("planes buffer too small: concurrent_games * (inference_batch_size + 1) rows are required");
         return M0_ERR_INVALID;
     }
-    int rc = start_first_games(sp);
+    int rc = M0_OK;
+    if (sp->an) {                                   // an analysis engine fills its free slots from its queue instead
+        std::string err;
+        rc = analysis_refill(sp, err);
+        if (rc != M0_OK) m0_set_error(err);
+    } else rc = start_first_games(sp);
     if (rc != M0_OK) return rc;
     int r = 0;
     if (run_select(sp, &r) != 0) { m0_set_error(std::string("select failed: ") + hipGetErrorString(hipGetLastError())); return M0_ERR_HIP; }
@@ -289,7 +249,7 @@ static int ext_select_impl(m0_selfplay* sp, int* rows_a, int* rows_b, float* pla
     return M0_OK;
 }
 
-static int ext_expand_impl(m0_selfplay* sp, const float* logits_a, const float* values_a, int rows_a, const float* logits_b,
+int m0::ext_expand_impl(m0_selfplay* sp, const float* logits_a, const float* values_a, int rows_a, const float* logits_b,
                            const float* values_b, int rows_b) {
     (void)hipSetDevice(sp->device);
     if (!sp->ext_pending) { m0_set_error("no m0_selfplay_ext_select outstanding"); return M0_ERR_STATE; }
@@ -305,9 +265,63 @@ static int ext_expand_impl(m0_selfplay* sp, const float* logits_a, const float* 
     return rc;
 }
 
+bool m0::refuse_analysis(m0_selfplay* sp, const char* what) {
+    if (!sp->an) return false;
+    m0_set_error(std::string(what) + ": this is an analysis engine (use the m0_analysis_* functions)");
+    return true;
+}
+
+extern "C" {
+
+m0_selfplay* m0_selfplay_create(m0_net* nh, const m0_selfplay_cfg* cfg) { return engine_create(nh, nullptr, cfg, false); }
+
+m0_selfplay* m0_arena_create(m0_net* net_a, m0_net* net_b, const m0_selfplay_cfg* cfg) {
+    if (!net_a || !net_b) { m0_set_error("m0_arena_create needs two networks"); return nullptr; }
+    if (m0_net_device(net_a) != m0_net_device(net_b)) { m0_set_error("both networks must live on the same HIP device"); return nullptr; }
+    if (cfg && (cfg->ssl_in_forward || cfg->ssl_targets)) { m0_set_error("arena games carry no SSL outputs"); return nullptr; }
+    return engine_create(net_a, net_b, cfg, false);
+}
+
+m0_selfplay* m0_arena_create_ext(const m0_selfplay_cfg* cfg) {
+    if (cfg && (cfg->ssl_in_forward || cfg->ssl_targets)) { m0_set_error("arena games carry no SSL outputs"); return nullptr; }
+    return engine_create(nullptr, nullptr, cfg, true);
+}
+
+void m0_selfplay_destroy(m0_selfplay* sp) {
+    if (!sp) return;
+    forward_gate_leave(sp);
+    (void)hipSetDevice(sp->device);
+    if (sp->stream) (void)hipStreamSynchronize(sp->stream);
+    if (sp->stream_tail) (void)hipStreamSynchronize(sp->stream_tail);
+    delete sp->net_tail;
+    if (sp->ev_sel) (void)hipEventDestroy(sp->ev_sel);
+    if (sp->ev_tail) (void)hipEventDestroy(sp->ev_tail);
+    if (sp->stream_tail) (void)hipStreamDestroy(sp->stream_tail);
+    for (void* p : sp->allocs) (void)hipFree(p);
+    for (auto& r : sp->done_meta) delete (GameRecordOwner*)r.owner;
+    delete sp->an;
+    if (sp->ev0) { (void)hipEventDestroy(sp->ev0); (void)hipEventDestroy(sp->ev1); (void)hipEventDestroy(sp->ev2); (void)hipEventDestroy(sp->ev3); }
+    if (sp->own_stream && sp->stream) (void)hipStreamDestroy(sp->stream);
+    delete sp;
+}
+
+int m0_selfplay_set_openings(m0_selfplay* sp, const char* const* fens, int n) {
+    if (!sp || n < 0 || (n > 0 && !fens)) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (refuse_analysis(sp, "m0_selfplay_set_openings")) return M0_ERR_STATE;
+    if (sp->stats.games_started != 0) { m0_set_error("set the opening book before the first step"); return M0_ERR_STATE; }
+    std::vector<Pos> book(n);
+    for (int i = 0; i < n; ++i)
+        if (!fens[i] || parse_fen(fens[i], book[i]) != 0) { m0_set_error(std::string("bad FEN at index ") + std::to_string(i)); return M0_ERR_INVALID; }
+    sp->book.swap(book);
+    sp->book_fens.assign(fens, fens + n);
+    return M0_OK;
+}
+
 int m0_selfplay_ext_select(m0_selfplay* sp, int* rows, float* planes, int max_rows) {
     if (!sp || !rows) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     std::lock_guard<std::mutex> lk(sp->mu);
+    if (refuse_analysis(sp, "m0_selfplay_ext_select")) return M0_ERR_STATE;
     if (sp->cfg.arena_mode) { m0_set_error("a match engine has two evaluators: use m0_arena_ext_select"); return M0_ERR_STATE; }
     return ext_select_impl(sp, rows, nullptr, planes, nullptr, max_rows);
 }
@@ -315,6 +329,7 @@ int m0_selfplay_ext_select(m0_selfplay* sp, int* rows, float* planes, int max_ro
 int m0_selfplay_ext_expand(m0_selfplay* sp, const float* logits, const float* values, int rows) {
     if (!sp) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     std::lock_guard<std::mutex> lk(sp->mu);
+    if (refuse_analysis(sp, "m0_selfplay_ext_expand")) return M0_ERR_STATE;
     if (sp->cfg.arena_mode) { m0_set_error("a match engine has two evaluators: use m0_arena_ext_expand"); return M0_ERR_STATE; }
     return ext_expand_impl(sp, logits, values, rows, nullptr, nullptr, 0);
 }
@@ -322,6 +337,7 @@ int m0_selfplay_ext_expand(m0_selfplay* sp, const float* logits, const float* va
 int m0_arena_ext_select(m0_selfplay* sp, int* rows_a, int* rows_b, float* planes_a, float* planes_b, int max_rows) {
     if (!sp || !rows_a || !rows_b) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     std::lock_guard<std::mutex> lk(sp->mu);
+    if (refuse_analysis(sp, "m0_arena_ext_select")) return M0_ERR_STATE;
     if (!sp->cfg.arena_mode) { m0_set_error("not a match engine"); return M0_ERR_STATE; }
     return ext_select_impl(sp, rows_a, rows_b, planes_a, planes_b, max_rows);
 }
@@ -330,6 +346,7 @@ int m0_arena_ext_expand(m0_selfplay* sp, const float* logits_a, const float* val
                         const float* values_b, int rows_b) {
     if (!sp) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     std::lock_guard<std::mutex> lk(sp->mu);
+    if (refuse_analysis(sp, "m0_arena_ext_expand")) return M0_ERR_STATE;
     if (!sp->cfg.arena_mode) { m0_set_error("not a match engine"); return M0_ERR_STATE; }
     return ext_expand_impl(sp, logits_a, values_a, rows_a, logits_b, values_b, rows_b);
 }
@@ -337,6 +354,7 @@ int m0_arena_ext_expand(m0_selfplay* sp, const float* logits_a, const float* val
 int m0_selfplay_step(m0_selfplay* sp, int steps) {
     if (!sp) { m0_set_error("sp is null"); return M0_ERR_INVALID; }
     std::lock_guard<std::mutex> lk(sp->mu);
+    if (refuse_analysis(sp, "m0_selfplay_step")) return M0_ERR_STATE;
     (void)hipSetDevice(sp->device);
     std::string err;
     if (sp->ext_pending) { m0_set_error("m0_selfplay_ext_expand outstanding"); return M0_ERR_STATE; }
@@ -359,6 +377,7 @@ int m0_selfplay_stats_get(m0_selfplay* sp, m0_selfplay_stats* out) {
 int m0_selfplay_poll(m0_selfplay* sp, m0_game_record* out) {
     if (!sp || !out) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     std::lock_guard<std::mutex> lk(sp->mu);
+    if (refuse_analysis(sp, "m0_selfplay_poll")) return M0_ERR_STATE;
     if (sp->done_meta.empty()) return 0;
     *out = sp->done_meta.front();
     sp->done_meta.pop_front();
@@ -381,6 +400,7 @@ int m0_selfplay_running(m0_selfplay* sp) {
 int m0_search_begin(m0_selfplay* sp, int g, const char* fen, int sims, int dirichlet, int game_uid) {
     if (!sp || !fen || g < 0 || g >= sp->G || sims <= 0) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
     std::lock_guard<std::mutex> lk(sp->mu);
+    if (refuse_analysis(sp, "m0_search_begin")) return M0_ERR_STATE;
     (void)hipSetDevice(sp->device);
     Pos p;
     if (parse_fen(fen, p) != 0) { m0_set_error("bad FEN"); return M0_ERR_INVALID; }
@@ -399,6 +419,7 @@ int m0_search_begin(m0_selfplay* sp, int g, const char* fen, int sims, int diric
 int m0_search_select(m0_selfplay* sp, int* rows, float* planes, int max_rows) {
     if (!sp || !rows) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     std::lock_guard<std::mutex> lk(sp->mu);
+    if (refuse_analysis(sp, "m0_search_select")) return M0_ERR_STATE;
     (void)hipSetDevice(sp->device);
     int r = 0;
     if (run_select(sp, &r) != 0) { m0_set_error(std::string("select failed: ") + hipGetErrorString(hipGetLastError())); return M0_ERR_HIP; }
@@ -414,6 +435,7 @@ int m0_search_select(m0_selfplay* sp, int* rows, float* planes, int max_rows) {
 int m0_search_expand(m0_selfplay* sp, const float* logits, const float* values, int rows) {
     if (!sp) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     std::lock_guard<std::mutex> lk(sp->mu);
+    if (refuse_analysis(sp, "m0_search_expand")) return M0_ERR_STATE;
     (void)hipSetDevice(sp->device);
     if (rows != sp->last_rows || rows > sp->rows_max) { m0_set_error("rows does not match the last select"); return M0_ERR_INVALID; }
     if (rows > 0 && (!logits || !values)) { m0_set_error("null argument"); return M0_ERR_INVALID; }
@@ -428,6 +450,7 @@ int m0_search_result(m0_selfplay* sp, int g, int* nchild, int32_t* child_n, uint
                      double* child_prior, double* child_q, double* root_q, int* root_n, int* finished) {
     if (!sp || g < 0 || g >= sp->G) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
     std::lock_guard<std::mutex> lk(sp->mu);
+    if (refuse_analysis(sp, "m0_search_result")) return M0_ERR_STATE;
     (void)hipSetDevice(sp->device);
     if (finished) *finished = sp->hg[g].finished;
     if (!sp->hg[g].finished) { if (nchild) *nchild = 0; return M0_OK; }
@@ -449,6 +472,7 @@ int m0_search_result(m0_selfplay* sp, int g, int* nchild, int32_t* child_n, uint
 int m0_search_advance(m0_selfplay* sp, int g, int slot, int sims, int dirichlet) {
     if (!sp || g < 0 || g >= sp->G || sims <= 0) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
     std::lock_guard<std::mutex> lk(sp->mu);
+    if (refuse_analysis(sp, "m0_search_advance")) return M0_ERR_STATE;
     (void)hipSetDevice(sp->device);
     // refresh the mirror first: an earlier advance changed root/next/arena on the device only
     if (sync_games_d2h(sp) != 0) { m0_set_error("device sync failed"); return M0_ERR_HIP; }

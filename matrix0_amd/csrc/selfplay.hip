@@ -380,7 +380,9 @@ int step_back(m0_selfplay* sp, int rows, double t0, std::string& err) {
         if (sp->hg[s].finished) any = true;
     }
     std::vector<int> ids, slots;
-    if (any) {
+    if (sp->an) {                          // an analysis engine: no games, the finished searches become results
+        if (any) { const int rc = analysis_harvest(sp, err); if (rc != M0_OK) return rc; }
+    } else if (any) {
         (void)hipMemcpy(sp->hres.data(), sp->d.results, sizeof(RootResult) * sp->G, hipMemcpyDeviceToHost);
         for (int s = 0; s < sp->G; ++s) {
             if (!(sp->hg[s].active && sp->hg[s].finished)) continue;

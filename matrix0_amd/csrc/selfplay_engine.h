@@ -49,6 +49,29 @@ struct HostGame : Line {                  // pos, win, history (all moves incl. 
     int book_index = -1;                  // the opening-book position the game started from, -1 = the initial position
 };
 
+// What an analysis engine (capi_analysis.hip) keeps beside the tree slots.  A slot that searches holds its position and
+// repetition window in m0_selfplay::games[slot] (in_use) and its search in hg[slot], as a game does.
+struct AnalysisJob { Line line; int sims; int nlegal; int64_t id; };
+struct Analysis {
+    m0_analysis_opts opts;
+    std::deque<AnalysisJob> queue;         // submitted searches that wait for a slot
+    std::deque<AnalysisJob> policy_queue;  // submitted policy-mode positions (sims = 0)
+    std::deque<m0_analysis_result> done;   // answered, not yet polled
+    std::vector<AnalysisJob> slot_job;     // per slot: what it searches (the Line lives in games[slot])
+    std::vector<int> finished;             // scratch: slots harvested by this step
+    std::vector<m0_analysis_line> hlines;  // host copies of the result kernels' output
+    std::vector<int> hnlines;
+    std::vector<float> hvalues;
+    std::vector<Pos> hpos;
+    m0_analysis_line* lines_dev = nullptr; // [rows_max][M0_AN_MAX_LINES] (searches use the first G entries)
+    int* nlines_dev = nullptr;             // [rows_max]
+    float* value_out_dev = nullptr;        // [rows_max]
+    Pos* pos_dev = nullptr;                // policy mode: [rows_max] positions, their legal moves and policy indices
+    int32_t* nlegal_dev = nullptr;
+    uint16_t* moves_dev = nullptr;
+    int32_t* idx_dev = nullptr;
+};
+
 }  // namespace m0
 
 struct m0_selfplay {
@@ -96,6 +119,7 @@ struct m0_selfplay {
     std::unordered_map<uint64_t, std::list<uint64_t>::iterator> nn_map;
     bool ext_pending = false;             // ext_select done, ext_expand outstanding
     bool counted = false;                 // registered with the forward gate
+    m0::Analysis* an = nullptr;           // set: an analysis engine (m0_analysis_create*); it plays no games
 };
 
 namespace m0 {
@@ -123,5 +147,17 @@ int start_first_games(m0_selfplay* sp);         // lazily, at the first step; se
 int run_select(m0_selfplay* sp, int* rows_out);
 int one_step(m0_selfplay* sp, std::string& err);
 int step_back(m0_selfplay* sp, int rows, double t0, std::string& err);
+
+// capi_selfplay.hip
+m0_selfplay* engine_create(m0_net* nh, m0_net* nh_b, const m0_selfplay_cfg* cfg, bool arena);
+int ext_select_impl(m0_selfplay* sp, int* rows_a, int* rows_b, float* planes_a, float* planes_b, int max_rows);
+int ext_expand_impl(m0_selfplay* sp, const float* logits_a, const float* values_a, int rows_a, const float* logits_b,
+                    const float* values_b, int rows_b);
+// true (error string set) when sp is an analysis engine: the game and split-search entry points refuse it
+bool refuse_analysis(m0_selfplay* sp, const char* what);
+
+// capi_analysis.hip: the two ends of an analysis engine's step, around the select -> network -> expand pass
+int analysis_refill(m0_selfplay* sp, std::string& err);      // free slots <- queued searches
+int analysis_harvest(m0_selfplay* sp, std::string& err);     // finished searches -> results, slots freed
 
 }  // namespace m0

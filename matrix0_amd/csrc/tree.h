@@ -179,5 +179,16 @@ hipError_t launch_encode_positions(const m0::Pos* pos_dev, int n, float* planes_
                                    int32_t* nlegal_dev, uint16_t* moves_dev /*[n][256]*/, int32_t* idx_dev /*[n][256]*/,
                                    hipStream_t st);
 
+// Results of the analysis engine (analysis_kernels.hip).  lines: M0_AN_MAX_LINES per entry, nlines: lines written per entry.
+// launch_analysis_lines: entry j = the finished search of slot slots_dev[j]: its root children by visits (ties by move order)
+// with the most-visited line behind each, at most pv_len moves.
+hipError_t launch_analysis_lines(const TreeDev& d, const int* slots_dev, int count, int multipv, int pv_len,
+                                 m0_analysis_line* lines_dev, int* nlines_dev, hipStream_t st);
+// launch_policy_lines: entry r = batch row r of a forward over positions that launch_encode_positions prepared (nlegal, moves,
+// idx): the legal moves by legal-softmax prior (ties by move order) and the row's value.
+hipError_t launch_policy_lines(const float* logits_dev, const float* values_dev, const int32_t* nlegal_dev, const uint16_t* moves_dev,
+                               const int32_t* idx_dev, int rows, int multipv, m0_analysis_line* lines_dev, int* nlines_dev,
+                               float* value_out_dev, hipStream_t st);
+
 // SSL training targets for recorded positions: out f32 [n][17][64] (piece 13, threat, pin, fork, control)
 hipError_t launch_ssl_targets(const m0::Pos* pos_dev, int n, float* out_dev, hipStream_t st);

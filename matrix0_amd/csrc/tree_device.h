@@ -73,6 +73,44 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return v;
 }
 
+// A lane's share of a leaf's children: child i = lane + 64 k, k < 4 (M0_MAX_CHILDREN = 256).
+constexpr int CPL = M0_MAX_CHILDREN / 64;
+static_assert(M0_POLICY_SIZE % 4 == 0, "logit rows are read as 16-byte pieces");
+
+// This lane's part of "the row holds a non-finite logit" (mcts.py:147-149).
+// (16-byte loads, all of a lane's 19 in flight together: one memory latency instead of 73 dependent-looking ones)
+__device__ __forceinline__ bool row_nonfinite(const float* lg, int lane) {
+    constexpr int N4 = M0_POLICY_SIZE / 4, PER_LANE = (N4 + 63) / 64;
+    const uint4* lg4 = reinterpret_cast<const uint4*>(lg);         // rows are 16-byte aligned
+    uint4 v[PER_LANE];
+#pragma unroll
+    for (int k = 0; k < PER_LANE; ++k) { const int j = lane + 64 * k; v[k] = lg4[j < N4 ? j : N4 - 1]; }   // unconditional loads
+    uint32_t acc = 0;                                               // all-ones exponent = inf or nan; no short-circuit
+#pragma unroll
+    for (int k = 0; k < PER_LANE; ++k) {
+        acc |= (uint32_t)((v[k].x & 0x7f800000u) == 0x7f800000u) | (uint32_t)((v[k].y & 0x7f800000u) == 0x7f800000u) |
+               (uint32_t)((v[k].z & 0x7f800000u) == 0x7f800000u) | (uint32_t)((v[k].w & 0x7f800000u) == 0x7f800000u);
+    }
+    return acc != 0;
+}
+
+// Softmax over the n <= M0_MAX_CHILDREN values l (CPL per lane, entries >= n hold -3.0e38f), whole-wave.
+// Numerics: (logit - max) in float32 as torch does, exp/sum/divide in float64, result rounded to float32.  Within one
+// float32 ulp of the reference's torch.softmax (mcts.py:158-168) and reproducible bit-for-bit on the host (oracle mode
+// "engine").  Shared by the expansion (expand_kernel) and the policy mode of the analysis engine (policy_lines_kernel).
+__device__ __forceinline__ void wave_softmax(const float (&l)[CPL], int n, int lane, float (&pr)[CPL]) {
+    float mx = -3.0e38f;
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) mx = fmaxf(mx, l[k]);
+    mx = wave_max_f(mx);
+    double e[CPL], sum = 0.0;
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) { const int i = lane + 64 * k; e[k] = i < n ? exp((double)(l[k] - mx)) : 0.0; sum += e[k]; }
+    sum = wave_sum_d(sum);
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) pr[k] = (float)(e[k] / sum);
+}
+
 // The next batch row of the game's network, reserved by lane 0 and known to the whole wave.
 __device__ __forceinline__ int reserve_row(const TreeDev& d, const GameDev* gd, int lane) {
     int row = 0;

@@ -29,9 +29,6 @@ struct LeafLogits {
 __device__ __forceinline__ LeafLogits logits_of_row(const float* row, float* store) { return LeafLogits{row, nullptr, store}; }
 // (row is null: the cache is only used with legal_softmax on and raw_legal_priors off, the two paths that never read it)
 __device__ __forceinline__ LeafLogits logits_of_cache(const float* payload) { return LeafLogits{nullptr, payload + EC_LOGITS, nullptr}; }
-// A lane's share of a leaf's children: child i = lane + 64 k, k < 4 (M0_MAX_CHILDREN = 256).
-constexpr int CPL = M0_MAX_CHILDREN / 64;
-static_assert(M0_POLICY_SIZE % 4 == 0, "logit rows are read as 16-byte pieces");
 
 // numpy float32 add.reduce over a[0..n): pairwise with an 8-way unrolled base case (blocks of <= 128), n <= 256
 static __device__ float np_sum_f32_dev(const float* a, int n) {
@@ -50,23 +47,6 @@ static __device__ float np_sum_f32_dev(const float* a, int n) {
     int n2 = n / 2;
     n2 -= n2 % 8;
     return block(a, n2) + block(a + n2, n - n2);
-}
-
-// This lane's part of "the row holds a non-finite logit" (mcts.py:147-149).
-// (16-byte loads, all of a lane's 19 in flight together: one memory latency instead of 73 dependent-looking ones)
-__device__ __forceinline__ bool row_nonfinite(const float* lg, int lane) {
-    constexpr int N4 = M0_POLICY_SIZE / 4, PER_LANE = (N4 + 63) / 64;
-    const uint4* lg4 = reinterpret_cast<const uint4*>(lg);         // rows are 16-byte aligned
-    uint4 v[PER_LANE];
-#pragma unroll
-    for (int k = 0; k < PER_LANE; ++k) { const int j = lane + 64 * k; v[k] = lg4[j < N4 ? j : N4 - 1]; }   // unconditional loads
-    uint32_t acc = 0;                                               // all-ones exponent = inf or nan; no short-circuit
-#pragma unroll
-    for (int k = 0; k < PER_LANE; ++k) {
-        acc |= (uint32_t)((v[k].x & 0x7f800000u) == 0x7f800000u) | (uint32_t)((v[k].y & 0x7f800000u) == 0x7f800000u) |
-               (uint32_t)((v[k].z & 0x7f800000u) == 0x7f800000u) | (uint32_t)((v[k].w & 0x7f800000u) == 0x7f800000u);
-    }
-    return acc != 0;
 }
 
 // Node._expand_with_legal_priors (mcts.py:227-256), the reference's in-process-model branch (mcts.py:697-703):
@@ -90,31 +70,22 @@ __device__ __forceinline__ void priors_uniform(int n, float (&pr)[CPL]) {
     for (int k = 0; k < CPL; ++k) pr[k] = 1.0f / (float)n;
 }
 
-// Softmax numerics: (logit - max) in float32 as torch does, exp/sum/divide in float64, result rounded
-// to float32.  Within one float32 ulp of the reference's torch.softmax (mcts.py:158-168) and
-// reproducible bit-for-bit on the host (oracle mode "engine"); entropy in float64.
+// Softmax numerics: wave_softmax (tree_device.h); entropy in float64.
 // Softmax over the legal moves only, entropy noise when the distribution is flat; the logits also go to src.store.
 __device__ __forceinline__ void priors_legal_softmax(const LeafLogits& src, const int (&idx)[CPL], int n, int lane, GameDev* gd,
                                                      const TreeCfg& c, float (&pr)[CPL]) {
-    float mx = -3.0e38f;
     double ent = 0.0;
     float l[CPL];
 #pragma unroll
     for (int k = 0; k < CPL; ++k) {
         const int i = lane + 64 * k;
         l[k] = i < n ? (src.legal ? src.legal[i] : src.row[idx[k]]) : -3.0e38f;
-        mx = fmaxf(mx, l[k]);
         if (src.store && i < n && i < M0_EC_MAXLEGAL) src.store[EC_LOGITS + i] = l[k];
     }
-    mx = wave_max_f(mx);
-    double e[CPL], sum = 0.0;
-#pragma unroll
-    for (int k = 0; k < CPL; ++k) { const int i = lane + 64 * k; e[k] = i < n ? exp((double)(l[k] - mx)) : 0.0; sum += e[k]; }
-    sum = wave_sum_d(sum);
+    wave_softmax(l, n, lane, pr);
 #pragma unroll
     for (int k = 0; k < CPL; ++k) {
         const int i = lane + 64 * k;
-        pr[k] = (float)(e[k] / sum);
         if (i < n) ent -= (double)pr[k] * log((double)pr[k] + 1e-8);
     }
     ent = wave_sum_d(ent);

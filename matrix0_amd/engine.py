@@ -51,6 +51,24 @@ class GameRecord(C.Structure):
                 ("start_fen", C.c_char_p)]
 
 
+AN_MAX_LINES, AN_MAX_PV = 8, 16
+
+
+class AnalysisOpts(C.Structure):
+    _fields_ = [("multipv", c_int), ("pv_len", c_int), ("dirichlet", c_int)]
+
+
+class AnalysisLine(C.Structure):
+    _fields_ = [("move", C.c_uint16), ("policy_index", C.c_int32), ("visits", C.c_int32), ("prior", C.c_float),
+                ("q", c_double), ("pv_len", C.c_int32), ("pv", C.c_uint16 * AN_MAX_PV)]
+
+
+class AnalysisResult(C.Structure):
+    _fields_ = [("id", C.c_int64), ("status", C.c_int32), ("nlegal", C.c_int32), ("overflow", C.c_int32),
+                ("sims", C.c_int32), ("root_n", C.c_int32), ("evals", c_u64), ("value", C.c_float), ("root_q", c_double),
+                ("nlines", C.c_int32), ("lines", AnalysisLine * AN_MAX_LINES)]
+
+
 _bound = False
 
 
@@ -101,6 +119,21 @@ def _bind():
     L.m0_rules_probe.argtypes = [C.POINTER(SelfplayCfg), C.c_char_p, C.POINTER(C.c_char_p), c_int, C.POINTER(c_int),
                                  C.POINTER(C.c_float)]
     L.m0_arena_choose_move.argtypes = [C.c_void_p, c_int, c_double, c_int, c_int, c_double]
+    L.m0_analysis_create.restype = C.c_void_p
+    L.m0_analysis_create.argtypes = [C.c_void_p, C.POINTER(SelfplayCfg), C.POINTER(AnalysisOpts)]
+    L.m0_analysis_create_ext.restype = C.c_void_p
+    L.m0_analysis_create_ext.argtypes = [C.POINTER(SelfplayCfg), C.POINTER(AnalysisOpts)]
+    L.m0_analysis_submit.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_char_p), c_int, c_int, C.c_int64]
+    L.m0_analysis_step.argtypes = [C.c_void_p, c_int]
+    L.m0_analysis_ext_select.argtypes = [C.c_void_p, C.POINTER(c_int), C.c_void_p, c_int]
+    L.m0_analysis_ext_expand.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, c_int]
+    L.m0_analysis_poll.argtypes = [C.c_void_p, C.POINTER(AnalysisResult)]
+    L.m0_analysis_pending.argtypes = [C.c_void_p]
+    L.m0_analysis_result_size.restype = C.c_size_t
+    L.m0_analysis_result_size.argtypes = []
+    # the mirror above against the library's own struct
+    assert C.sizeof(AnalysisResult) == L.m0_analysis_result_size(), \
+        (C.sizeof(AnalysisResult), L.m0_analysis_result_size())
     _bound = True
     return L
 
@@ -525,6 +558,91 @@ class ArenaExtEngine(SelfplayEngine):
         _lib.check(self._L.m0_arena_ext_expand(self._h, la.ctypes.data_as(C.c_void_p), va.ctypes.data_as(C.c_void_p), int(la.shape[0]),
                                                lb.ctypes.data_as(C.c_void_p), vb.ctypes.data_as(C.c_void_p), int(lb.shape[0])),
                    "m0_arena_ext_expand")
+
+
+ANALYSIS_STATUS = {0: "ok", 1: "checkmate", 2: "stalemate"}
+
+
+def analysis_result_to_dict(r: AnalysisResult) -> dict:
+    """One m0_analysis_result as plain Python: moves and principal variations as UCI strings."""
+    lines = []
+    for i in range(r.nlines):
+        ln = r.lines[i]
+        lines.append({"move": move_to_uci(int(ln.move)), "policy_index": int(ln.policy_index), "visits": int(ln.visits),
+                      "prior": float(ln.prior), "q": float(ln.q),
+                      "pv": [move_to_uci(int(ln.pv[k])) for k in range(ln.pv_len)]})
+    return {"id": int(r.id), "status": ANALYSIS_STATUS.get(int(r.status), str(int(r.status))), "nlegal": int(r.nlegal),
+            "overflow": bool(r.overflow), "sims": int(r.sims), "root_n": int(r.root_n), "evals": int(r.evals),
+            "value": float(r.value), "root_q": float(r.root_q), "lines": lines}
+
+
+class AnalysisEngine(SelfplayEngine):
+    """Batched position analysis on the engine's own network (m0_analysis_create): `submit` positions, `step`, `poll` the
+    results (completion order).  stats / close as SelfplayEngine; the game and split-search methods are refused by the library.
+    matrix0_amd.analysis.Analyzer is the interface built on it."""
+
+    def __init__(self, backend, cfg: SelfplayCfg, *, multipv: int = 1, pv_len: int = 8, dirichlet: bool = False):
+        self._L = _bind()
+        self.backend = backend
+        self.cfg = cfg
+        self.opts = AnalysisOpts(int(multipv), int(pv_len), int(bool(dirichlet)))
+        self._h = self._create()
+        if not self._h:
+            raise RuntimeError(f"m0_analysis_create failed: {_lib.last_error()}")
+
+    def _create(self):
+        return self._L.m0_analysis_create(self.backend.handle, C.byref(self.cfg), C.byref(self.opts))
+
+    def submit(self, fen: str, ucis=(), sims: int = 0, id: int = 0) -> None:
+        ucis = list(ucis)
+        arr = (C.c_char_p * max(1, len(ucis)))(*[u.encode() for u in ucis])
+        _lib.check(self._L.m0_analysis_submit(self._h, fen.encode(), arr, len(ucis), int(sims), int(id)), "m0_analysis_submit")
+
+    def step(self, steps: int = 1) -> None:
+        _lib.check(self._L.m0_analysis_step(self._h, int(steps)), "m0_analysis_step")
+
+    def pending(self) -> int:
+        n = int(self._L.m0_analysis_pending(self._h))
+        if n < 0:
+            _lib.check(n, "m0_analysis_pending")
+        return n
+
+    def poll(self) -> Optional[dict]:
+        r = AnalysisResult()
+        rc = self._L.m0_analysis_poll(self._h, C.byref(r))
+        if rc < 0:
+            _lib.check(rc, "m0_analysis_poll")
+        return analysis_result_to_dict(r) if rc == 1 else None
+
+
+class AnalysisExtEngine(AnalysisEngine):
+    """The same engine without a network (m0_analysis_create_ext): `step(infer_np)` runs select, the caller's evaluator on the
+    leaf planes and expand.  Search only (no policy mode)."""
+
+    def __init__(self, cfg: SelfplayCfg, **opts):
+        super().__init__(None, cfg, **opts)
+
+    def _create(self):
+        return self._L.m0_analysis_create_ext(C.byref(self.cfg), C.byref(self.opts))
+
+    def step(self, infer_np, steps: int = 1) -> None:
+        cap = self.cfg.concurrent_games * (self.cfg.inference_batch_size + 1)
+        planes = np.zeros((cap, 19, 8, 8), dtype=np.float32)
+        rows = c_int(0)
+        for _ in range(int(steps)):
+            if self.pending() == 0:
+                break
+            _lib.check(self._L.m0_analysis_ext_select(self._h, C.byref(rows), planes.ctypes.data_as(C.c_void_p), cap),
+                       "m0_analysis_ext_select")
+            n = rows.value
+            if n:
+                lg, v = infer_np(planes[:n])
+                lg = np.ascontiguousarray(lg, dtype=np.float32)
+                v = np.ascontiguousarray(v, dtype=np.float32)
+            else:
+                lg, v = np.zeros((0, 4672), np.float32), np.zeros((0,), np.float32)
+            _lib.check(self._L.m0_analysis_ext_expand(self._h, lg.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), n),
+                       "m0_analysis_ext_expand")
 
 
 def arena_choose_move(visits, temp: float, ply: int, temp_plies: int, u: float) -> int:
