@@ -22,6 +22,7 @@
 //   value_fc2, gate, fc3                   conv_gemm_kernel<1>
 //   SSL head: conv + GN, conv, transpose   conv_gemm_kernel<1> GN epilogue (N in 32/64/128/160), conv, nhwc_to_nchw_f32
 #include "net.h"
+#include "attn_math.h"
 #include <math.h>
 #include <string.h>
 #include <algorithm>
@@ -238,7 +239,7 @@ int Net::pack_attn_block(AttnW& a, const std::string& prefix, std::string& err) 
                         const int kt = e >> 4, r = e & 15;
                         const int q = qt * 32 + (lane & 31), key = kt * 32 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
                         bb[(((size_t)h * 2 + qt) * 64 + lane) * 32 + e] =
-                            (_Float16)(rb->data[((size_t)h * 64 + q) * 64 + key] * 1.44269504088896f);
+                            (_Float16)(rb->data[((size_t)h * 64 + q) * 64 + key] * kLog2e);
                     }
     }
     a.blk_bias = (_Float16*)dalloc(bb.size() * 2, false);
@@ -355,7 +356,7 @@ int Net::pack_attn(AttnW& a, bool skip, const std::string& p, std::string& err) 
         nparams_ += rb->data.size();
         // stored pre-multiplied by log2(e): the attention kernel exponentiates with exp2
         std::vector<float> rbs((size_t)(P / 16) * 4096, 0.f);      // padded heads: zero bias
-        for (size_t i = 0; i < rb->data.size(); ++i) rbs[i] = rb->data[i] * 1.44269504088896f;
+        for (size_t i = 0; i < rb->data.size(); ++i) rbs[i] = rb->data[i] * kLog2e;
         a.rel_bias = upload_f32(rbs);
     }
     return M0_OK;

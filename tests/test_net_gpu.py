@@ -212,6 +212,12 @@ def test_fused_attention_block_matches_split_kernels(monkeypatch):
         p_ref, v_ref = net_ref.forward(sd, cfg, x, return_ssl=False)[:2]
         for tag, p, v in (("split", p_split, v_split), ("fused", p_fused, v_fused)):
             _check(f"attn_{tag}:{sorted(extra.items())}", p, v, p_ref.numpy(), v_ref.numpy())
+        if extra is variants[0]:
+            # a workgroup owns a board pair and every wave's role follows from its index: a board's result must not depend
+            # on its seat in the pair -- rotate the batch by one board
+            perm = np.roll(np.arange(B), 1)
+            pr, vr = be.infer_np(x.numpy()[perm])
+            assert np.array_equal(pr, p_fused[perm]) and np.array_equal(vr, v_fused[perm])
         be.close()
 
 
