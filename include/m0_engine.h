@@ -380,6 +380,45 @@ int m0_analysis_poll(m0_selfplay* sp, m0_analysis_result* out);   /* 1 written, 
 int m0_analysis_pending(m0_selfplay* sp);                         /* queued + in flight (answered ones not counted) */
 size_t m0_analysis_result_size(void);                             /* sizeof(m0_analysis_result), for foreign mirrors */
 
+/* ---- generated 3- and 4-man endgame tablebases (the reference's tablebases.enabled: selfplay/internal.py:250-260, 559-581) ----
+ * The reference ends a self-play game as soon as the position after a move is found in a Syzygy table and takes the sign of
+ * its WDL as the result.  Here the tables are computed instead of read: distance-to-mate tables by retrograde analysis on the
+ * GPU, ignoring the 50-move rule as Syzygy's WDL does (the reference scores cursed wins as wins), so the verdict is the same.
+ * Scope: KK, the five 3-man signatures and every 4-man signature except KPKP (the only one with en passant); a KPKP position
+ * is no hit.  Signatures are strings such as "KQK", "KRPK", "KQKR": the greater side first (it is White in the table; a
+ * position with the greater side Black is probed through its colour flip), men ordered Q > R > B > N > P.  One byte per entry
+ * and 2 * 64^n entries per table: 0 draw, 255 invalid, 1 + d decided in d plies (d even: the side to move is mated in d, d odd:
+ * it mates in d); index and encoding are specified in csrc/tb_core.h.  A handle is immutable once made and may be shared by
+ * any number of engines and threads; it must outlive the engines it is attached to. */
+typedef struct m0_tb m0_tb;
+/* Build on the device: every signature in scope with at most max_men (3 or 4) men / the given signatures plus everything
+ * their captures and promotions lead into.  NULL on failure (no HIP device, an unknown signature). */
+m0_tb* m0_tb_build(int hip_device, int max_men);
+m0_tb* m0_tb_build_signatures(int hip_device, const char* const* sigs, int n);
+/* Cache file: magic, format version, the list of signatures with a checksum per table, then the tables.  Load needs no GPU and
+ * refuses (NULL, message in the last error) a file that is truncated, has another magic or version, or fails a checksum.
+ * Save writes a temporary file of a unique name beside `path` and renames it: several processes may save the same tables to
+ * the same path at the same time, and a reader never sees a partial file. */
+m0_tb* m0_tb_load(const char* path);
+int m0_tb_save(const m0_tb* tb, const char* path);
+void m0_tb_destroy(m0_tb* tb);
+int m0_tb_max_men(const m0_tb* tb);                   /* men of the largest table in the handle */
+/* The raw table of a signature (valid while the handle lives); M0_ERR_INVALID when the handle has no such table. */
+int m0_tb_table(const m0_tb* tb, const char* sig, const uint8_t** bytes, size_t* n);
+/* Table i in build order: signature (sig8: 8 bytes, NUL-padded), largest d (-1: no decided entry), sweeps and milliseconds of
+ * its build (0 for a loaded handle's time).  Returns 1, 0 when i is past the last table, M0_ERR_INVALID for a null handle.
+ * Not in the reference's interface: tools/bench_tablebase.py and the tests report sweeps and largest d through it. */
+int m0_tb_table_info(const m0_tb* tb, int i, char* sig8, int* maxd, int* sweeps, double* build_ms);
+/* Per FEN: hit 0/1, wdl -1/0/+1 for the side to move, dtm in plies (0 for draws); outputs nullable.  No hit: more men than the
+ * handle covers, a signature it does not hold (KPKP), any castling right left, an illegal placement. */
+int m0_tb_probe_fens(const m0_tb* tb, const char* const* fens, int n, uint8_t* hit, int8_t* wdl, int16_t* dtm);
+/* Attach to a self-play engine before its first step (tb = NULL detaches): after every played move a position with at most
+ * min(max_pieces, m0_tb_max_men) men is probed; on a hit the game ends there with that result (White's point of view,
+ * resigned = 0).  Without a tablebase the game loop is unchanged.  Match and analysis engines: M0_ERR_STATE (the reference's
+ * arena does not probe). */
+int m0_selfplay_set_tablebase(m0_selfplay* sp, const m0_tb* tb, int max_pieces);
+uint64_t m0_selfplay_tb_adjudications(m0_selfplay* sp);      /* games ended by a tablebase hit */
+
 /* ---- host decision functions (selfplay/internal.py), exposed for parity tests ---- */
 int m0_sample_move_index(const int32_t* visits, int n, double temperature, double u);
 int m0_playout_cap(int sims, double frac, double u);

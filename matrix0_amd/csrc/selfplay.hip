@@ -7,6 +7,7 @@
 #include <string.h>
 #include <atomic>
 #include "selfplay_engine.h"
+#include "tb.h"
 
 namespace m0 {
 
@@ -257,6 +258,15 @@ static void finish_search(m0_selfplay* sp, int slot, std::vector<int>& adv_ids, 
         return;
     }
     hgm.play(mv);
+    // tablebase hit after the move (internal.py:559-581): the game ends with the table's verdict, from White's point of view
+    if (sp->tb) {
+        int wdl = 0, dtm = 0;
+        if (tb_probe(sp->tb->set, hgm.pos, sp->tb_max_pieces, wdl, dtm)) {
+            sp->tb_adjudications++;
+            finish_game(sp, slot, false, 0, true, (float)(hgm.pos.turn == WHITE ? wdl : -wdl));
+            return;
+        }
+    }
     begin_move(sp, slot, pick, adv_ids, adv_slots);
 }
 

@@ -304,6 +304,22 @@ class SelfplayEngine:
         arr = (C.c_char_p * max(1, len(fens)))(*[f.encode() for f in fens])
         _lib.check(self._L.m0_selfplay_set_openings(self._h, arr, len(fens)), "m0_selfplay_set_openings")
 
+    def set_tablebase(self, tb, max_pieces: int = 4) -> None:
+        """Attach a matrix0_amd.tablebase.Tablebase (None detaches); call before the first step.  After every played move a
+        position with at most `max_pieces` men is probed and a hit ends the game with the table's verdict
+        (selfplay/internal.py:559-581).  The engine keeps a reference: the tables live as long as it does."""
+        from . import tablebase as _tb
+        _tb._bind()
+        _lib.check(self._L.m0_selfplay_set_tablebase(self._h, tb.handle if tb is not None else None, int(max_pieces)),
+                   "m0_selfplay_set_tablebase")
+        self._tablebase = tb
+
+    def tb_adjudications(self) -> int:
+        """Games ended by a tablebase hit."""
+        from . import tablebase as _tb
+        _tb._bind()
+        return int(self._L.m0_selfplay_tb_adjudications(self._h))
+
     def ext_select(self) -> np.ndarray:
         """First half of a self-play step for an external evaluator: the leaf planes f32 [rows,19,8,8]."""
         rows = c_int(0)

@@ -10,7 +10,12 @@ Instead of one game at a time with a Python MCTS, the games of this worker run c
 libm0engine.so; `shared_memory_resource` (the reference's inference-server handle) is accepted and ignored: leaf
 batching happens in the engine.  New keys live under an `engine:` section only:
     engine: {device_index: int, concurrent_games: int, leaves_per_step: int, virtual_loss_active: bool,
-             first_game_index: int, compat: {fresh_tree_per_move, tt_merge, raw_legal_priors, root_reinfer}}
+             first_game_index: int, compat: {fresh_tree_per_move, tt_merge, raw_legal_priors, root_reinfer},
+             tablebase: {max_pieces: 3 | 4, cache: <path or null>}}
+
+`engine.tablebase` stands in for the reference's Syzygy files (internal.py:250-260, 559-581): the 3- and 4-man tables are
+generated on the GPU (matrix0_amd/tablebase.py), or loaded from `cache`, and a game ends as soon as the position after a move
+is found in them.  `tablebases.enabled: true` is accepted only together with this key.
 
 The orchestrator hands the SAME cfg_dict to every worker (orchestrator.py:490-496), so what tells workers apart is
 proc_id alone: worker i runs on GPU  i % (visible MI355X)  and plays the global game indices [i*games, (i+1)*games) --
@@ -31,6 +36,7 @@ from . import encoding
 from .backend import M0Backend
 from .data_writer import ReplayShardWriter, SelfplayShardWriter
 from .engine import SelfplayEngine, SelfplayPool, selfplay_cfg_from_dict
+from .tablebase import Tablebase, probe_limit, tablebase_cfg
 from .weights import random_state_dict
 
 START_W = "rnbqkbnr/pppppppp/8/8/8/8/PPPPPPPP/RNBQKBNR w KQkq - 0 1"
@@ -62,9 +68,10 @@ def check_unsupported_sections(cfg_dict: dict) -> None:
         raise NotImplementedError("openings.polyglot (selfplay/internal.py:71-91, 328-333: python-chess polyglot reader) is not "
                                   "implemented by the MI355X engine; use selfplay.opening_random_plies or engine.opening_fens")
     tb = cfg_dict.get("tablebases", {}) or {}
-    if tb.get("enabled", False):
+    if tb.get("enabled", False) and tablebase_cfg(cfg_dict) is None:
         raise NotImplementedError("tablebases.enabled (selfplay/internal.py:250-260, 560-581: Syzygy probing through python-chess) "
-                                  "is not implemented by the MI355X engine; set tablebases.enabled: false")
+                                  "is not implemented by the MI355X engine, which generates its own 3- and 4-man tables instead: "
+                                  "set engine.tablebase: {max_pieces: 3 | 4, cache: <path>} or tablebases.enabled: false")
 
 
 def selfplay_worker(proc_id: int, cfg_dict: dict, ckpt_path: Optional[str], games: int, q=None,
@@ -121,9 +128,19 @@ def selfplay_worker(proc_id: int, cfg_dict: dict, ckpt_path: Optional[str], game
         from .pgn_book import load_opening_book
         book = load_opening_book(sp_book)
         logger.debug("worker %d: %d positions from opening book %s", proc_id, len(book), sp_book)
+    engines = engine.engines if hasattr(engine, "engines") else [engine]
     if book:
-        for e in (engine.engines if hasattr(engine, "engines") else [engine]):
+        for e in engines:
             e.set_openings(book)
+    # endgame tables (internal.py:250-260): engine.tablebase, built on this worker's GPU or loaded from its cache file
+    tb_cfg = tablebase_cfg(cfg_dict)
+    tablebase = None
+    if tb_cfg is not None:
+        tablebase = Tablebase.cached(tb_cfg["cache"], tb_cfg["max_pieces"], device_index)
+        for e in engines:
+            e.set_tablebase(tablebase, probe_limit(cfg_dict))
+        logger.info("worker %d: endgame tables up to %d men attached (probing up to %d)", proc_id, tablebase.max_men,
+                    probe_limit(cfg_dict))
     # engine.replay_shards: emit replay-buffer shards directly (ReplayShardWriter: what the orchestrator's
     # compact_selfplay_to_replay would make of the per-game files) instead of one NPZ per game
     direct_replay = bool(eng_cfg.get("replay_shards", False))
@@ -135,6 +152,7 @@ def selfplay_worker(proc_id: int, cfg_dict: dict, ckpt_path: Optional[str], game
     last_hb = time.perf_counter()
     done = 0
     overflows = 0
+    tb_hits = 0
     ssl_dropped = 0
     try:
         while engine.running():
@@ -174,6 +192,11 @@ def selfplay_worker(proc_id: int, cfg_dict: dict, ckpt_path: Optional[str], game
                 overflows = int(st["arena_overflows"])
                 logger.warning("worker %d: %d searches hit the node-arena limit or ended without visits; raise engine.arena_nodes",
                                proc_id, overflows)
+            if tablebase is not None:
+                hits = sum(e.tb_adjudications() for e in engines)
+                if hits > tb_hits:
+                    tb_hits = hits
+                    logger.info("worker %d: %d games adjudicated by the endgame tables", proc_id, tb_hits)
             if int(st.get("ssl_dropped", 0)) > ssl_dropped:
                 ssl_dropped = int(st["ssl_dropped"])
                 logger.warning("worker %d: %d games were written without ssl_* targets (staging buffers could not grow)",
