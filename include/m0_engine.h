@@ -351,17 +351,22 @@ typedef struct m0_analysis_line {
     int32_t pv_len; uint16_t pv[M0_AN_MAX_PV];                                    /* pv[0] == move; unused entries 0 */
 } m0_analysis_line;
 typedef struct m0_analysis_result {
-    int64_t id; int32_t status;      /* 0 searched/evaluated, 1 side to move is checkmated, 2 stalemate */
+    int64_t id; int32_t status;      /* 0 searched/evaluated, 1 side to move is checkmated, 2 stalemate, 3 answered from the
+                                        endgame tablebases (m0_selfplay_set_search_tablebase, m0_tb_root_lines) */
     int32_t nlegal, overflow, sims, root_n; uint64_t evals;
     float value;                     /* network value of the root evaluation (side to move) */
     double root_q; int32_t nlines; m0_analysis_line lines[M0_AN_MAX_LINES];
+    /* status 3 only (0 otherwise); appended, every field above keeps its offset */
+    int32_t tb_dtm;                  /* distance to mate of the root in plies, 0 for a draw */
+    int32_t line_dtm[M0_AN_MAX_LINES];   /* ... of the position after each line's move */
 } m0_analysis_result;
 m0_selfplay* m0_analysis_create(m0_net* net, const m0_selfplay_cfg* cfg, const m0_analysis_opts* opts);
 m0_selfplay* m0_analysis_create_ext(const m0_selfplay_cfg* cfg, const m0_analysis_opts* opts);   /* external evaluator */
 /* Queue the position `fen` after the n_moves legal moves `ucis` (nullable when n_moves = 0): the moves go through the
  * repetition window of a game, so the search sees repetitions with the positions before it.  The queue is unbounded.
  * A bad FEN or an illegal move: M0_ERR_INVALID, nothing queued.  A root without legal moves is answered at once (status 1 / 2,
- * nlines 0, no evaluation) and never takes a slot.
+ * nlines 0, no evaluation) and never takes a slot; so is, with tables attached (m0_selfplay_set_search_tablebase), a root inside
+ * them (status 3, the lines of m0_tb_root_lines).
  * sims > 0: a search of that many simulations; lines are the root children by visits (ties: move order), each with the
  *           most-visited line behind it (first maximum in move order; it ends at an unexpanded or terminal node, at a node
  *           without visited children, or at opts->pv_len).
@@ -418,6 +423,31 @@ int m0_tb_probe_fens(const m0_tb* tb, const char* const* fens, int n, uint8_t* h
  * arena does not probe). */
 int m0_selfplay_set_tablebase(m0_selfplay* sp, const m0_tb* tb, int max_pieces);
 uint64_t m0_selfplay_tb_adjudications(m0_selfplay* sp);      /* games ended by a tablebase hit */
+/* The tables inside the search (no counterpart in the reference).  Accepted by every engine kind before its first step; tb =
+ * NULL detaches.  The handle's tables are copied to the engine's HIP device at the first attach on that device (one copy per
+ * handle and device, shared by every engine there, complete before this call returns, freed by m0_tb_destroy: 2.6 MiB for the
+ * 3-man set, about 930 MiB for the 4-man set).  From then on select_kernel probes every leaf with at most
+ * min(max_pieces, m0_tb_max_men) men after the game-over tests: a hit is a terminal leaf worth +1 / -1 for the side to move
+ * (draw_penalty for a table draw), backed up at once, never expanded and never evaluated.  A position with a castling right
+ * left is no hit; the half-move clock is ignored, as in adjudication.  A root inside the tables is handled per engine kind:
+ *   self-play engines   also adjudicate after every played move, exactly as m0_selfplay_set_tablebase does (same counter);
+ *   match engines       adjudicate the same way: the game ends with the table's verdict from White's point of view;
+ *   analysis engines    answer a submission whose root is a hit at once from the tables (m0_tb_root_lines): status 3, no slot,
+ *                       no evaluation;
+ *   m0_search_*         searches whatever root it is given: only leaves are probed.
+ * Without an attached handle every engine computes bit for bit what it computed before. */
+int m0_selfplay_set_search_tablebase(m0_selfplay* sp, const m0_tb* tb, int max_pieces);
+uint64_t m0_selfplay_tb_leaves(m0_selfplay* sp);             /* leaves the search took from the tables */
+/* The analysis of a root inside the tables, on the host (no GPU).  1: the root is a hit and `out` is filled (every field but
+ * id): status 3, nlegal, root_q = wdl for the side to move, tb_dtm, evals = root_n = sims = 0, value 0 and min(multipv, nlegal)
+ * lines.  0: no hit (or a successor without a table), `out` untouched.  M0_ERR_INVALID: a bad FEN, multipv outside [1, 8],
+ * pv_len outside [1, 16].
+ * Line order: moves whose successor is lost for the opponent first, smallest successor dtm first; then moves to a drawn
+ * successor; then moves to a successor won for the opponent, largest dtm first; ties keep the legal-move order.  Per line: q
+ * the exact +1 / 0 / -1 from the root mover's view, visits 0, prior 0, policy_index as usual, line_dtm the successor's dtm.
+ * A decided line's pv continues with the first-ranked move of each following position and ends at checkmate or at pv_len; a
+ * drawn line's pv is the move alone. */
+int m0_tb_root_lines(const m0_tb* tb, const char* fen, int multipv, int pv_len, m0_analysis_result* out);
 
 /* ---- host decision functions (selfplay/internal.py), exposed for parity tests ---- */
 int m0_sample_move_index(const int32_t* visits, int n, double temperature, double u);

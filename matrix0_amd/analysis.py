@@ -13,12 +13,19 @@ ranked by legal-softmax prior.
     for r in an.analyse([fen, (fen2, ["e2e4", "e7e5"])], sims=800):
         print(r["lines"][0]["move"], r["lines"][0]["pv"], r["root_q"])
 
+With `tablebase=` (a matrix0_amd.tablebase.Tablebase or the path of its cache file) the generated endgame tables take part: a
+position inside them is answered from them alone (status "tablebase": exact root_q, `dtm` in plies, lines ranked shortest
+win first with the `dtm` behind each move, no evaluation), and every other search takes the exact value of each leaf it finds
+in them.
+
 Command line: python -m matrix0_amd.analysis --config config.yaml --checkpoint CKPT --fens FILE [--sims N] [--multipv K]
-prints one JSON object per position (FILE: one FEN per line, optionally followed by `moves` and UCI moves)."""
+[--tablebase PATH [--tb-men N]] prints one JSON object per position (FILE: one FEN per line, optionally followed by `moves` and
+UCI moves)."""
 from __future__ import annotations
 
 import argparse
 import json
+import os
 import sys
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
@@ -40,7 +47,8 @@ class Analyzer:
     num_simulations) sizes their node arenas."""
 
     def __init__(self, backend, cfg_dict: dict, *, slots: int = 256, multipv: int = 1, pv_len: int = 8, dirichlet: bool = False,
-                 leaves_per_step: Optional[int] = None, max_sims: Optional[int] = None, seed: Optional[int] = None):
+                 leaves_per_step: Optional[int] = None, max_sims: Optional[int] = None, seed: Optional[int] = None,
+                 tablebase=None, tb_men: int = 4):
         if not 1 <= int(multipv) <= eng.AN_MAX_LINES or not 1 <= int(pv_len) <= eng.AN_MAX_PV:
             raise ValueError(f"multipv must be in [1, {eng.AN_MAX_LINES}] and pv_len in [1, {eng.AN_MAX_PV}]")
         self.multipv = int(multipv)
@@ -50,6 +58,16 @@ class Analyzer:
             cfg.num_simulations = int(max_sims)
         self.cfg = cfg
         self.engine = self._make_engine(backend, cfg, multipv=self.multipv, pv_len=int(pv_len), dirichlet=bool(dirichlet))
+        self._tb_owned = None
+        if tablebase is not None:
+            try:
+                if isinstance(tablebase, (str, os.PathLike)):        # a cache file: loaded here, closed with the analyzer
+                    from .tablebase import Tablebase
+                    tablebase = self._tb_owned = Tablebase.load(tablebase)
+                self.engine.set_search_tablebase(tablebase, int(tb_men))
+            except Exception:
+                self.close()
+                raise
 
     def _make_engine(self, backend, cfg, **opts):
         return eng.AnalysisEngine(backend, cfg, **opts)
@@ -88,7 +106,7 @@ class Analyzer:
         """Search every position with `sims` simulations (default: the configured number).  `positions`: FENs or
         (fen, [uci, ...]) pairs -- the position after the moves, which count for repetitions.  `ids` (default 0, 1, ...)
         key the random streams.  Returns one dict per position, in submission order: status ("ok" | "checkmate" |
-        "stalemate"), nlegal, sims, root_n, root_q, value, evals, overflow and `lines`: [{move, pv, visits, prior, q,
+        "stalemate" | "tablebase"), nlegal, sims, root_n, root_q, value, evals, overflow and `lines`: [{move, pv, visits, prior, q,
         policy_index}], best first."""
         sims = int(self.cfg.num_simulations if sims is None else sims)
         if sims < 1:
@@ -112,7 +130,10 @@ class Analyzer:
         return self.engine.stats()
 
     def close(self) -> None:
-        self.engine.close()
+        self.engine.close()                # the engine first: the tables outlive it
+        if self._tb_owned is not None:
+            self._tb_owned.close()
+            self._tb_owned = None
 
     def __enter__(self):
         return self
@@ -175,6 +196,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--pv-len", type=int, default=8)
     ap.add_argument("--slots", type=int, default=256)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--tablebase", default=None, metavar="PATH", help="cache file of generated endgame tables (matrix0_amd.tablebase)")
+    ap.add_argument("--tb-men", type=int, default=4, help="probe positions with at most this many men (default 4)")
     return ap
 
 
@@ -201,6 +224,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     kw = dict(slots=args.slots, multipv=args.multipv, pv_len=args.pv_len)
     if args.sims:
         kw["max_sims"] = args.sims
+    if args.tablebase:
+        kw.update(tablebase=args.tablebase, tb_men=args.tb_men)
     with Analyzer(be, cfg, **kw) as an:
         results = an.evaluate(positions) if args.sims == 0 else an.analyse(positions, args.sims)
     for r in results:

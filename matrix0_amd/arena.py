@@ -21,7 +21,12 @@ evaluated, and those leaves are served from the cache instead of the network -- 
 (`last_match_stats["evals_cached"]`).  `eval.openings_pgn` (the key of the reference's config.yaml, which nothing there reads) or
 the `openings=` argument starts the games from an opening book, paired by colour: games 2k and 2k+1 share one book position, so
 each opening is played once with A as White and once with B.  Without a book every game starts from the initial position, and
-with no temperature and no noise a match is then two distinct games played over and over."""
+with no temperature and no noise a match is then two distinct games played over and over.
+
+A third: `engine.tablebase: {max_pieces, cache, in_search: true}` (matrix0_amd/tablebase.py) or the `tablebase=` argument puts
+the generated endgame tables into the match: the searches of both sides take the exact value of every leaf found in them, and
+a game ends with the table's verdict as soon as the position after a move is inside them
+(`last_match_stats["tb_adjudications"]`, `["tb_leaves"]`).  Without `in_search` the key is ignored here, as before."""
 from __future__ import annotations
 
 import json
@@ -142,13 +147,14 @@ def play_match(backend_a, backend_b, games: int, cfg: dict, seed: Optional[int] 
                pgn_sample: int = 0, num_sims: int = 500, max_moves_override: Optional[int] = None, temp: float = 0.0,
                temp_plies: int = 0, concurrent_games: Optional[int] = None, leaves_per_step: Optional[int] = 16,
                elo_book: Optional[str] = None, log_dir: Optional[str] = None, progress=None,
-               openings: Optional[List[str]] = None) -> float:
+               openings: Optional[List[str]] = None, tablebase=None) -> float:
     """A vs B over `games` games; returns the summed score of A (1 / 0.5 / 0 per game), as arena.play_match does.
     `backend_a` / `backend_b` are M0Backend objects on the same device (the reference takes checkpoint paths:
     M0Backend.from_checkpoint).  `openings` (FEN strings) or `eval.openings_pgn` in `cfg`: the games start from book positions,
     games 2k and 2k+1 from the same one; `max_moves` then counts the plies played from there.  Details of the last match
     (W/L/D, win rate, Wilson interval, Elo, evaluations made and served from the cache, the records with their `start_fen`) are
-    left in `last_match_stats`."""
+    left in `last_match_stats`.  `tablebase` (a Tablebase) or `engine.tablebase` with `in_search: true` in `cfg`: the endgame tables
+    are probed inside the searches and end a game that enters them, with their result."""
     global last_match_stats
     if games <= 0:
         return 0.0
@@ -170,7 +176,16 @@ def play_match(backend_a, backend_b, games: int, cfg: dict, seed: Optional[int] 
                             concurrent_games=min(conc, games), leaves_per_step=leaves_per_step, seed=seed)
     book = match_openings(cfg, openings)
     c.arena_paired_openings = 1 if book else 0
+    from . import tablebase as tbm
+    tb_cfg = tbm.tablebase_cfg(cfg)
+    tb, tb_limit, tb_owned = tablebase, 4, False
+    if tb is None and tb_cfg is not None and tb_cfg.get("in_search", False):
+        tb = tbm.Tablebase.cached(tb_cfg["cache"], tb_cfg["max_pieces"], int(ecfg.get("device_index", 0) or 0))
+        tb_owned = True
+    if tb is not None and tb_cfg is not None:
+        tb_limit = tbm.probe_limit(cfg)
     e = eng.ArenaEngine(backend_a, backend_b, c)
+    tb_stats = {"tb_adjudications": 0.0, "tb_leaves": 0.0}
     score = 0.0
     a_wins = b_wins = draws = 0
     done: List[dict] = []
@@ -178,6 +193,8 @@ def play_match(backend_a, backend_b, games: int, cfg: dict, seed: Optional[int] 
     try:
         if book:
             e.set_openings(book)
+        if tb is not None:
+            e.set_search_tablebase(tb, tb_limit)
         while e.running():
             e.step(8)
             while (r := e.poll()) is not None:
@@ -204,12 +221,16 @@ def play_match(backend_a, backend_b, games: int, cfg: dict, seed: Optional[int] 
                     progress(len(done), games, a_wins, b_wins, draws)
     finally:
         st = e.stats()
-        e.close()
+        if tb is not None:
+            tb_stats = {"tb_adjudications": float(e.tb_adjudications()), "tb_leaves": float(e.tb_leaves())}
+        e.close()                      # the engine first: the tables outlive it
+        if tb_owned:
+            tb.close()
     win_rate = score / float(max(1, games))
     lo, hi = wilson_interval(win_rate, games)
     stats = {"games": games, "a_wins": a_wins, "b_wins": b_wins, "draws": draws, "score": score, "win_rate": win_rate,
              "wilson_low": lo, "wilson_high": hi, "seconds": time.perf_counter() - t0, "evals": float(st["evals"]),
-             "evals_cached": float(st["evals_cached"]), "plies": float(st["plies"]), "records": done}
+             "evals_cached": float(st["evals_cached"]), "plies": float(st["plies"]), "records": done, **tb_stats}
     if elo_book:
         book = {"best": 1500.0, "enhanced_best": 1500.0, "candidate": 1500.0, "baseline": 1500.0, "history": []}
         if os.path.exists(elo_book):

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <memory>
 #include "selfplay_engine.h"
+#include "tb.h"
 
 using namespace m0;
 
@@ -210,6 +211,13 @@ int m0_analysis_submit(m0_selfplay* sp, const char* fen, const char* const* ucis
         r.status = in_check(job.line.pos) ? 1 : 2;
         sp->an->done.push_back(r);
         return M0_OK;
+    }
+    if (sp->tb) {                          // a root inside the attached tables: answered from them, as the two cases above
+        m0_analysis_result r = blank_result(job);
+        if (tb_root_lines(sp->tb, sp->tb_max_pieces, job.line.pos, sp->an->opts.multipv, sp->an->opts.pv_len, &r)) {
+            sp->an->done.push_back(r);
+            return M0_OK;
+        }
     }
     (sims == 0 ? sp->an->policy_queue : sp->an->queue).push_back(std::move(job));
     return M0_OK;

@@ -1,5 +1,7 @@
-// extern "C" entry points of the endgame tablebases (include/m0_engine.h, m0_tb_*): build, cache file, probing, and the
-// attachment to a self-play engine.  Only the build touches the GPU; a loaded handle probes on the host.
+// extern "C" entry points of the endgame tablebases (include/m0_engine.h, m0_tb_*): build, cache file, probing, the analysis
+// of a root inside the tables, and the two attachments to an engine: the host probe after a played move
+// (m0_selfplay_set_tablebase) and the probe inside the search (m0_selfplay_set_search_tablebase), for which the handle keeps
+// one copy of its tables per HIP device.  The build and that copy touch the GPU; everything else runs on the host.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -40,7 +42,104 @@ m0_tb* build(int hip_device, const std::vector<std::string>& sigs) {
     return tb.release();
 }
 
+// ---- the analysis of a root inside the tables ----
+struct RankedMove { Move mv; int wdl, dtm; };      // wdl / dtm of the successor, for the side to move there
+
+// The legal moves of p, best first for the mover: successors lost for the opponent by ascending dtm, drawn ones, successors
+// won for the opponent by descending dtm; ties in legal-move order.  false: a successor is not in the tables.
+bool rank_moves(const m0_tb* tb, int max_men, const Pos& p, std::vector<RankedMove>& out) {
+    Move mv[M0_MAX_MOVES];
+    const int n = gen_legal(p, mv);
+    out.clear();
+    for (int i = 0; i < n; ++i) {
+        Pos q = p;
+        make_move(q, mv[i]);
+        RankedMove r{mv[i], 0, 0};
+        if (!tb_probe(tb->set, q, max_men, r.wdl, r.dtm)) return false;
+        out.push_back(r);
+    }
+    auto cls = [](const RankedMove& r) { return r.wdl < 0 ? 0 : (r.wdl == 0 ? 1 : 2); };
+    std::stable_sort(out.begin(), out.end(), [&](const RankedMove& a, const RankedMove& b) {
+        if (cls(a) != cls(b)) return cls(a) < cls(b);
+        return cls(a) == 0 ? a.dtm < b.dtm : (cls(a) == 2 ? a.dtm > b.dtm : false);
+    });
+    return true;
+}
+
 }  // namespace
+
+bool m0::tb_root_lines(const m0_tb* tb, int max_men, const Pos& root, int multipv, int pv_len, m0_analysis_result* out) {
+    int wdl = 0, dtm = 0;
+    if (!tb_probe(tb->set, root, max_men, wdl, dtm)) return false;
+    std::vector<RankedMove> ranked, next;
+    if (!rank_moves(tb, max_men, root, ranked)) return false;
+    std::vector<m0_analysis_line> lines;
+    for (size_t l = 0; l < ranked.size() && (int)l < multipv; ++l) {
+        const RankedMove& r = ranked[l];
+        m0_analysis_line ln;
+        memset(&ln, 0, sizeof(ln));
+        ln.move = r.mv; ln.policy_index = move_to_index(root, r.mv); ln.q = (double)-r.wdl;
+        ln.pv[ln.pv_len++] = r.mv;
+        Pos p = root;
+        make_move(p, r.mv);
+        while (r.wdl != 0 && ln.pv_len < pv_len) {            // a decided line: the first-ranked move of every position on it
+            if (!rank_moves(tb, max_men, p, next)) return false;
+            if (next.empty()) break;                          // checkmate
+            ln.pv[ln.pv_len++] = next[0].mv;
+            make_move(p, next[0].mv);
+        }
+        lines.push_back(ln);
+    }
+    const int64_t id = out->id;
+    memset(out, 0, sizeof(*out));
+    out->id = id; out->status = 3; out->nlegal = (int32_t)ranked.size(); out->root_q = (double)wdl; out->tb_dtm = dtm;
+    out->nlines = (int32_t)lines.size();
+    for (size_t l = 0; l < lines.size(); ++l) { out->lines[l] = lines[l]; out->line_dtm[l] = ranked[l].dtm; }
+    return true;
+}
+
+// ---- the device copy ----
+int m0::tb_device_set(const m0_tb* tb, int hip_device, const TbSet** set_dev, std::string& err) {
+    std::lock_guard<std::mutex> lk(tb->dev_mu);
+    for (const auto& c : tb->dev_copies)
+        if (c.device == hip_device) { *set_dev = c.set; return M0_OK; }
+    m0_tb_device_copy c;
+    c.device = hip_device;
+    TbSet host;
+    for (auto& t : host.tab) t = nullptr;
+    hipError_t e = hipSetDevice(hip_device);
+    for (size_t i = 0; e == hipSuccess && i < tb->tables.size(); ++i) {
+        const TbTable& t = tb->tables[i];
+        void* p = nullptr;
+        e = hipMalloc(&p, t.bytes.size());
+        if (e != hipSuccess) break;
+        c.allocs.push_back(p);
+        host.tab[tb_material_code(t.sig)] = (const uint8_t*)p;
+        e = hipMemcpy(p, t.bytes.data(), t.bytes.size(), hipMemcpyHostToDevice);
+    }
+    void* sd = nullptr;
+    if (e == hipSuccess) e = hipMalloc(&sd, sizeof(TbSet));
+    if (e == hipSuccess) { c.allocs.push_back(sd); e = hipMemcpy(sd, &host, sizeof(TbSet), hipMemcpyHostToDevice); }
+    if (e == hipSuccess) e = hipDeviceSynchronize();          // nothing of the upload is left in flight when the caller goes on
+    if (e != hipSuccess) {
+        err = std::string("copying the tables to the device failed: ") + hipGetErrorString(e);
+        for (void* p : c.allocs) (void)hipFree(p);            // no kernel has seen them
+        return M0_ERR_HIP;
+    }
+    c.set = (const TbSet*)sd;
+    *set_dev = c.set;
+    tb->dev_copies.push_back(std::move(c));
+    return M0_OK;
+}
+
+void m0::tb_free_device_copies(m0_tb* tb) {
+    std::lock_guard<std::mutex> lk(tb->dev_mu);
+    for (auto& c : tb->dev_copies) {
+        if (hipSetDevice(c.device) != hipSuccess) continue;
+        for (void* p : c.allocs) (void)hipFree(p);
+    }
+    tb->dev_copies.clear();
+}
 
 extern "C" {
 
@@ -56,7 +155,11 @@ m0_tb* m0_tb_build_signatures(int hip_device, const char* const* sigs, int n) {
     return build(hip_device, v);
 }
 
-void m0_tb_destroy(m0_tb* tb) { delete tb; }
+void m0_tb_destroy(m0_tb* tb) {
+    if (!tb) return;
+    tb_free_device_copies(tb);
+    delete tb;
+}
 
 int m0_tb_max_men(const m0_tb* tb) { return tb ? tb->max_men : 0; }
 
@@ -165,6 +268,49 @@ int m0_selfplay_set_tablebase(m0_selfplay* sp, const m0_tb* tb, int max_pieces) 
     sp->tb = tb;
     sp->tb_max_pieces = tb ? std::min(max_pieces, tb->max_men) : 0;
     return M0_OK;
+}
+
+int m0_tb_root_lines(const m0_tb* tb, const char* fen, int multipv, int pv_len, m0_analysis_result* out) {
+    if (!tb || !fen || !out) { m0_set_error("null argument"); return M0_ERR_INVALID; }
+    if (multipv < 1 || multipv > M0_AN_MAX_LINES || pv_len < 1 || pv_len > M0_AN_MAX_PV) {
+        m0_set_error("multipv must be in [1, 8] and pv_len in [1, 16]");
+        return M0_ERR_INVALID;
+    }
+    Pos p;
+    if (parse_fen(fen, p) != 0) { m0_set_error("bad FEN"); return M0_ERR_INVALID; }
+    return tb_root_lines(tb, tb->max_men, p, multipv, pv_len, out) ? 1 : 0;
+}
+
+int m0_selfplay_set_search_tablebase(m0_selfplay* sp, const m0_tb* tb, int max_pieces) {
+    if (!sp) { m0_set_error("sp is null"); return M0_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(sp->mu);
+    const bool queued = sp->an && (!sp->an->queue.empty() || !sp->an->policy_queue.empty() || !sp->an->done.empty());
+    if (sp->stats.games_started != 0 || sp->stats.steps != 0 || sp->stats.evals != 0 || sp->ext_pending || queued) {
+        m0_set_error("attach the tablebase before the first step");
+        return M0_ERR_STATE;
+    }
+    if (tb && max_pieces < 2) { m0_set_error("max_pieces must be at least 2"); return M0_ERR_INVALID; }
+    const TbSet* set_dev = nullptr;
+    if (tb) {
+        std::string err;
+        const int rc = tb_device_set(tb, sp->device, &set_dev, err);
+        if (rc != M0_OK) { m0_set_error("m0_selfplay_set_search_tablebase: " + err); return rc; }
+        (void)hipSetDevice(sp->device);
+    }
+    // the host probe of a root (after a played move; of a submission) and the leaf probe of select_kernel read the same limit
+    sp->tb = tb;
+    sp->tb_max_pieces = tb ? std::min(max_pieces, tb->max_men) : 0;
+    sp->d.tb_set = set_dev;
+    sp->d.tb_max_pieces = sp->tb_max_pieces;
+    return M0_OK;
+}
+
+uint64_t m0_selfplay_tb_leaves(m0_selfplay* sp) {
+    if (!sp) return 0;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    uint64_t n = 0;
+    for (const GameDev& g : sp->hg) n += g.tb_leaves;         // the mirror the last step copied
+    return n;
 }
 
 uint64_t m0_selfplay_tb_adjudications(m0_selfplay* sp) {

@@ -259,6 +259,7 @@ static void finish_search(m0_selfplay* sp, int slot, std::vector<int>& adv_ids, 
     }
     hgm.play(mv);
     // tablebase hit after the move (internal.py:559-581): the game ends with the table's verdict, from White's point of view
+    // (a match engine too, once the tables are attached through m0_selfplay_set_search_tablebase)
     if (sp->tb) {
         int wdl = 0, dtm = 0;
         if (tb_probe(sp->tb->set, hgm.pos, sp->tb_max_pieces, wdl, dtm)) {

@@ -120,8 +120,9 @@ struct m0_selfplay {
     bool ext_pending = false;             // ext_select done, ext_expand outstanding
     bool counted = false;                 // registered with the forward gate
     m0::Analysis* an = nullptr;           // set: an analysis engine (m0_analysis_create*); it plays no games
-    const m0_tb* tb = nullptr;            // endgame tablebase probed after every played move (m0_selfplay_set_tablebase)
-    int tb_max_pieces = 0;                // ... for positions with at most this many men
+    const m0_tb* tb = nullptr;            // endgame tablebase probed on the host: after every played move (m0_selfplay_set_tablebase,
+                                          // m0_selfplay_set_search_tablebase), for a submitted root (analysis engines)
+    int tb_max_pieces = 0;                // ... for positions with at most this many men (d.tb_set: the probe inside the search)
     uint64_t tb_adjudications = 0;        // games it ended
 };
 

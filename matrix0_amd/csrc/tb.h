@@ -2,6 +2,7 @@
 // signature depends on, the build order, the GPU build (tb_build.hip).  Internal.
 #pragma once
 #include <algorithm>
+#include <mutex>
 #include <string>
 #include <vector>
 #include "../../include/m0_engine.h"
@@ -20,10 +21,21 @@ struct TbTable {
 
 }  // namespace m0
 
+// The tables once more in the memory of one HIP device, for the probe inside select_kernel (tree_select.hip): `set` is a
+// TbSet in device memory whose pointers are device pointers.  Made on first use (m0::tb_device_set), shared by every engine
+// on that device, freed with the handle and never before: a hipFree synchronises the whole device.
+struct m0_tb_device_copy {
+    int device = -1;
+    const m0::TbSet* set = nullptr;
+    std::vector<void*> allocs;          // the tables and the set
+};
+
 struct m0_tb {
     std::vector<m0::TbTable> tables;    // in build order
     m0::TbSet set;                      // host pointers into tables[i].bytes
     int max_men = 0;
+    mutable std::mutex dev_mu;          // guards dev_copies (the handle itself is immutable)
+    mutable std::vector<m0_tb_device_copy> dev_copies;
     void index_tables() {
         for (auto& t : set.tab) t = nullptr;
         max_men = 0;
@@ -131,6 +143,15 @@ inline std::vector<std::string> tb_all_signatures(int max_men) {
         }
     return out;
 }
+
+// capi_tb.hip: the device copy of tb's tables on `hip_device`, uploaded (and the upload waited for) at the first call.
+int tb_device_set(const m0_tb* tb, int hip_device, const TbSet** set_dev, std::string& err);
+// ... all of them freed (m0_tb_destroy)
+void tb_free_device_copies(m0_tb* tb);
+
+// capi_tb.hip: m0_tb_root_lines for a parsed position and a probe limit; false (out untouched) when the root is no hit.
+// out->id is kept.
+bool tb_root_lines(const m0_tb* tb, int max_men, const Pos& root, int multipv, int pv_len, m0_analysis_result* out);
 
 // tb_build.hip: builds the tables `order` (a tb_build_order result) on the device and leaves them in tb->tables.
 int tb_build_on_device(int hip_device, const std::vector<std::string>& order, m0_tb* tb, std::string& err);

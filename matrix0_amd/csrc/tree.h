@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "chess_core.h"
+namespace m0 { struct TbSet; }   // tb_core.h
 // deliberate: the C ABI already fixes M0_POLICY_SIZE (logits per batch row) and M0_PLANES (input planes); one definition
 #include "../../include/m0_engine.h"
 
@@ -89,6 +90,7 @@ struct GameDev {
     int ec_clear;             // match engine: this slot starts a new game -- advance_kernel empties both of its caches
     int side_next[2];         // bump allocator of each side's half while the other side searches
     int root_found;           // advance_kernel: this search's root was found in the side's table (mcts.py:343, 359-371)
+    uint64_t tb_leaves;       // leaves that select_kernel took from the endgame tablebases (TreeDev::tb_set), counted by lane 0
 };
 
 enum SampleKind : int {
@@ -165,6 +167,8 @@ struct TreeDev {
     const float* values;      // [rows]
     int G;
     int L;
+    const m0::TbSet* tb_set;  // endgame tablebases in device memory (m0_selfplay_set_search_tablebase); null = leaves are not probed
+    int tb_max_pieces;        // ... for leaves with at most this many men
 };
 
 hipError_t launch_select(const TreeDev& d, const TreeCfg& c, hipStream_t st);

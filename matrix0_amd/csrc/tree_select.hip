@@ -2,7 +2,11 @@
 // loads (PUCT + FPU + virtual loss + jitter in fp64, mcts.py:851-925), wave arg-max with first-max tie-break, leaf board by
 // make_move, terminal test, immediate terminal backup, evaluation-cache probe, M0_PLANES-plane encode written straight into
 // the network input (lane = square).
+// With endgame tablebases attached (TreeDev::tb_set) a leaf that survives the game-over tests is looked up there: a hit is a
+// terminal leaf with the table's value.  A position with a castling right left is no hit; the half-move clock is ignored,
+// as in adjudication (tb_core.h, tb_probe).
 #include "tree_device.h"
+#include "tb_core.h"
 #include "eval_cache.h"
 #include "movegen_wave.h"
 #include "kernel_common.h"   // DeviceOnce
@@ -42,9 +46,12 @@ __device__ __forceinline__ Sample make_sample(const Pos& pos, SampleKind kind, i
     return s;
 }
 
-// is_game_over() (checkmate, stalemate, insufficient, 75-move, fivefold) -> _terminal_value in `tv`
-__device__ __forceinline__ bool leaf_terminal(const TreeCfg& c, const Pos& pos, int nlegal, int depth, const uint64_t* pkey,
-                                              const uint8_t* pirr, const uint64_t* H, int hist_len, int lane, double& tv) {
+// is_game_over() (checkmate, stalemate, insufficient, 75-move, fivefold) -> _terminal_value in `tv`; then, with tables
+// attached, the table's verdict for the side to move (`tb_hit`).  pos is wave-uniform: the probe is scalar work and one
+// byte load, the same in every lane.
+__device__ __forceinline__ bool leaf_terminal(const TreeDev& d, const TreeCfg& c, const Pos& pos, int nlegal, int depth,
+                                              const uint64_t* pkey, const uint8_t* pirr, const uint64_t* H, int hist_len, int lane,
+                                              double& tv, bool& tb_hit) {
     const bool chk = in_check(pos);
     bool term = false;
     tv = 0.0;
@@ -65,6 +72,14 @@ __device__ __forceinline__ bool leaf_terminal(const TreeCfg& c, const Pos& pos, 
                 cnt += __popcll(__ballot(i < hist_len && H[i] == lk));
             }
         if (cnt >= 5) { term = true; tv = c.draw_penalty; }
+    }
+    tb_hit = false;
+    if (!term && d.tb_set) {
+        int wdl, dtm;
+        if (tb_probe(*d.tb_set, pos, d.tb_max_pieces, wdl, dtm)) {
+            term = tb_hit = true;
+            tv = wdl > 0 ? 1.0 : (wdl < 0 ? -1.0 : c.draw_penalty);
+        }
     }
     return term;
 }
@@ -276,7 +291,9 @@ __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
         __syncthreads();
         const int nlegal = gen_legal_wave(pos, smoves, spseudo, lane);
         double tv;
-        const bool term = leaf_terminal(c, pos, nlegal, depth, pkey, pirr, H, hist_len, lane, tv);
+        bool tb_hit;
+        const bool term = leaf_terminal(d, c, pos, nlegal, depth, pkey, pirr, H, hist_len, lane, tv, tb_hit);
+        if (tb_hit && lane == 0) gd->tb_leaves++;
         uint64_t ckey = 0;
         bool cached = false;
         if (!term && c.eval_cache && d.ec.sets > 0 && nlegal <= M0_EC_MAXLEGAL) {

@@ -66,7 +66,8 @@ class AnalysisLine(C.Structure):
 class AnalysisResult(C.Structure):
     _fields_ = [("id", C.c_int64), ("status", C.c_int32), ("nlegal", C.c_int32), ("overflow", C.c_int32),
                 ("sims", C.c_int32), ("root_n", C.c_int32), ("evals", c_u64), ("value", C.c_float), ("root_q", c_double),
-                ("nlines", C.c_int32), ("lines", AnalysisLine * AN_MAX_LINES)]
+                ("nlines", C.c_int32), ("lines", AnalysisLine * AN_MAX_LINES),
+                ("tb_dtm", C.c_int32), ("line_dtm", C.c_int32 * AN_MAX_LINES)]
 
 
 _bound = False
@@ -319,6 +320,24 @@ class SelfplayEngine:
         from . import tablebase as _tb
         _tb._bind()
         return int(self._L.m0_selfplay_tb_adjudications(self._h))
+
+    def set_search_tablebase(self, tb, max_pieces: int = 4) -> None:
+        """Attach a matrix0_amd.tablebase.Tablebase to the search itself (None detaches); every engine kind, before the first
+        step.  The tables are copied to the engine's GPU once per handle and device; from then on a leaf with at most
+        `max_pieces` men that is in the tables is a terminal leaf with the table's value and costs no evaluation.  A root inside
+        the tables: self-play and match engines end the game there with the table's verdict (as `set_tablebase`), an analysis
+        engine answers it from the tables (status "tablebase"), the split-step search searches it as given."""
+        from . import tablebase as _tb
+        _tb._bind()
+        _lib.check(self._L.m0_selfplay_set_search_tablebase(self._h, tb.handle if tb is not None else None, int(max_pieces)),
+                   "m0_selfplay_set_search_tablebase")
+        self._tablebase = tb
+
+    def tb_leaves(self) -> int:
+        """Leaves the search took from the tables instead of the network (as of the last step)."""
+        from . import tablebase as _tb
+        _tb._bind()
+        return int(self._L.m0_selfplay_tb_leaves(self._h))
 
     def ext_select(self) -> np.ndarray:
         """First half of a self-play step for an external evaluator: the leaf planes f32 [rows,19,8,8]."""
@@ -576,20 +595,28 @@ class ArenaExtEngine(SelfplayEngine):
                    "m0_arena_ext_expand")
 
 
-ANALYSIS_STATUS = {0: "ok", 1: "checkmate", 2: "stalemate"}
+ANALYSIS_STATUS = {0: "ok", 1: "checkmate", 2: "stalemate", 3: "tablebase"}
 
 
 def analysis_result_to_dict(r: AnalysisResult) -> dict:
-    """One m0_analysis_result as plain Python: moves and principal variations as UCI strings."""
+    """One m0_analysis_result as plain Python: moves and principal variations as UCI strings.  A result from the endgame
+    tablebases (status "tablebase") also carries `dtm`, the root's distance to mate in plies (0: a draw), and per line the
+    `dtm` of the position after its move; its root_q is the exact wdl."""
+    from_tb = int(r.status) == 3
     lines = []
     for i in range(r.nlines):
         ln = r.lines[i]
         lines.append({"move": move_to_uci(int(ln.move)), "policy_index": int(ln.policy_index), "visits": int(ln.visits),
                       "prior": float(ln.prior), "q": float(ln.q),
                       "pv": [move_to_uci(int(ln.pv[k])) for k in range(ln.pv_len)]})
-    return {"id": int(r.id), "status": ANALYSIS_STATUS.get(int(r.status), str(int(r.status))), "nlegal": int(r.nlegal),
-            "overflow": bool(r.overflow), "sims": int(r.sims), "root_n": int(r.root_n), "evals": int(r.evals),
-            "value": float(r.value), "root_q": float(r.root_q), "lines": lines}
+        if from_tb:
+            lines[-1]["dtm"] = int(r.line_dtm[i])
+    out = {"id": int(r.id), "status": ANALYSIS_STATUS.get(int(r.status), str(int(r.status))), "nlegal": int(r.nlegal),
+           "overflow": bool(r.overflow), "sims": int(r.sims), "root_n": int(r.root_n), "evals": int(r.evals),
+           "value": float(r.value), "root_q": float(r.root_q), "lines": lines}
+    if from_tb:
+        out["dtm"] = int(r.tb_dtm)
+    return out
 
 
 class AnalysisEngine(SelfplayEngine):

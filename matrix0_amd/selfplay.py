@@ -11,11 +11,12 @@ libm0engine.so; `shared_memory_resource` (the reference's inference-server handl
 batching happens in the engine.  New keys live under an `engine:` section only:
     engine: {device_index: int, concurrent_games: int, leaves_per_step: int, virtual_loss_active: bool,
              first_game_index: int, compat: {fresh_tree_per_move, tt_merge, raw_legal_priors, root_reinfer},
-             tablebase: {max_pieces: 3 | 4, cache: <path or null>}}
+             tablebase: {max_pieces: 3 | 4, cache: <path or null>, in_search: false | true}}
 
 `engine.tablebase` stands in for the reference's Syzygy files (internal.py:250-260, 559-581): the 3- and 4-man tables are
 generated on the GPU (matrix0_amd/tablebase.py), or loaded from `cache`, and a game ends as soon as the position after a move
-is found in them.  `tablebases.enabled: true` is accepted only together with this key.
+is found in them.  With `in_search: true` the tables also live on the GPU and the search takes the exact value of every leaf
+found in them instead of a network evaluation.  `tablebases.enabled: true` is accepted only together with this key.
 
 The orchestrator hands the SAME cfg_dict to every worker (orchestrator.py:490-496), so what tells workers apart is
 proc_id alone: worker i runs on GPU  i % (visible MI355X)  and plays the global game indices [i*games, (i+1)*games) --
@@ -137,10 +138,11 @@ def selfplay_worker(proc_id: int, cfg_dict: dict, ckpt_path: Optional[str], game
     tablebase = None
     if tb_cfg is not None:
         tablebase = Tablebase.cached(tb_cfg["cache"], tb_cfg["max_pieces"], device_index)
+        searched = bool(tb_cfg.get("in_search", False))
         for e in engines:
-            e.set_tablebase(tablebase, probe_limit(cfg_dict))
-        logger.info("worker %d: endgame tables up to %d men attached (probing up to %d)", proc_id, tablebase.max_men,
-                    probe_limit(cfg_dict))
+            (e.set_search_tablebase if searched else e.set_tablebase)(tablebase, probe_limit(cfg_dict))
+        logger.info("worker %d: endgame tables up to %d men attached (probing up to %d%s)", proc_id, tablebase.max_men,
+                    probe_limit(cfg_dict), ", inside the search too" if searched else "")
     # engine.replay_shards: emit replay-buffer shards directly (ReplayShardWriter: what the orchestrator's
     # compact_selfplay_to_replay would make of the per-game files) instead of one NPZ per game
     direct_replay = bool(eng_cfg.get("replay_shards", False))

@@ -3,9 +3,11 @@
 The reference's worker ends a game as soon as the position after a move is found in a Syzygy table
 (azchess/selfplay/internal.py:250-260, 559-581).  This engine computes the tables on the GPU instead of reading them
 (distance to mate, no 50-move rule -- the reference looks at the sign of the WDL only), keeps them in host memory, and the
-self-play engine probes them after every move (SelfplayEngine.set_tablebase).
+self-play engine probes them after every move (SelfplayEngine.set_tablebase).  With `in_search: true` they are also copied to
+the GPU and probed inside the search (SelfplayEngine.set_search_tablebase): a leaf found in a table takes its exact value and
+no network evaluation, in self-play, in matches (arena.play_match) and in analysis.
 
-    engine: {tablebase: {max_pieces: 3 | 4, cache: <path or null>}}
+    engine: {tablebase: {max_pieces: 3 | 4, cache: <path or null>, in_search: false | true}}
 
 in config.yaml makes the worker build (or load from `cache`) and attach them; `tablebases.enabled: true` of the reference's
 own section is accepted only together with it.
@@ -45,25 +47,41 @@ def _bind():
     L.m0_selfplay_set_tablebase.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.m0_selfplay_tb_adjudications.restype = C.c_uint64
     L.m0_selfplay_tb_adjudications.argtypes = [C.c_void_p]
+    L.m0_selfplay_set_search_tablebase.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.m0_selfplay_tb_leaves.restype = C.c_uint64
+    L.m0_selfplay_tb_leaves.argtypes = [C.c_void_p]
+    L.m0_tb_root_lines.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p]
     _bound = True
     return L
 
 
 def tablebase_cfg(cfg_dict: dict) -> Optional[dict]:
-    """`engine.tablebase` of config.yaml -> {"max_pieces": 3 | 4, "cache": path or None}; None when the key is absent."""
+    """`engine.tablebase` of config.yaml -> {"max_pieces": 3 | 4, "cache": path or None}; None when the key is absent.
+    `in_search` (a bool, default false: the tables adjudicate only) appears in the result when the config names it."""
     tb = (cfg_dict.get("engine", {}) or {}).get("tablebase")
     if not tb:
         return None
     if not isinstance(tb, dict):
-        raise ValueError("engine.tablebase must be a mapping {max_pieces: 3 | 4, cache: <path or null>}")
-    unknown = set(tb) - {"max_pieces", "cache"}
+        raise ValueError("engine.tablebase must be a mapping {max_pieces: 3 | 4, cache: <path or null>, in_search: <bool>}")
+    unknown = set(tb) - {"max_pieces", "cache", "in_search"}
     if unknown:
         raise ValueError(f"unknown engine.tablebase keys: {sorted(unknown)}")
     mp = tb.get("max_pieces", 4)
     if isinstance(mp, bool) or not isinstance(mp, int) or mp not in (3, 4):
         raise ValueError(f"engine.tablebase.max_pieces must be 3 or 4, not {mp!r}")
     cache = tb.get("cache")
-    return {"max_pieces": mp, "cache": str(cache) if cache else None}
+    out = {"max_pieces": mp, "cache": str(cache) if cache else None}
+    if "in_search" in tb:
+        if not isinstance(tb["in_search"], bool):
+            raise ValueError(f"engine.tablebase.in_search must be true or false, not {tb['in_search']!r}")
+        out["in_search"] = tb["in_search"]
+    return out
+
+
+def in_search(cfg_dict: dict) -> bool:
+    """`engine.tablebase.in_search`: the tables are probed inside the search, not only after a played move."""
+    tb = tablebase_cfg(cfg_dict)
+    return bool(tb and tb.get("in_search", False))
 
 
 def probe_limit(cfg_dict: dict) -> int:
@@ -155,6 +173,19 @@ class Tablebase:
         _lib.check(self._L.m0_tb_probe_fens(self.handle, arr, n, hit.ctypes.data_as(C.c_void_p), wdl.ctypes.data_as(C.c_void_p),
                                             dtm.ctypes.data_as(C.c_void_p)), "m0_tb_probe_fens")
         return hit.astype(bool), wdl, dtm
+
+    def root_lines(self, fen: str, multipv: int = 1, pv_len: int = 8) -> Optional[dict]:
+        """The analysis of a position inside the tables, on the host: the dict an Analyzer returns for it (status "tablebase",
+        root_q the wdl for the side to move, `dtm`, evals 0; lines best first -- shortest win, draws, longest loss -- each
+        with q, `dtm` of the position after the move and the principal variation under the same rule).  None when `fen` is
+        no hit."""
+        from . import engine as eng
+        eng._bind()
+        r = eng.AnalysisResult()
+        rc = self._L.m0_tb_root_lines(self.handle, fen.encode(), int(multipv), int(pv_len), C.byref(r))
+        if rc < 0:
+            _lib.check(rc, "m0_tb_root_lines")
+        return eng.analysis_result_to_dict(r) if rc == 1 else None
 
     def close(self) -> None:
         if getattr(self, "handle", None):
