@@ -167,7 +167,7 @@ def play_match(backend_a, backend_b, games: int, cfg: dict, seed: Optional[int] 
         # game (~40 per simulation and search).  Size it, and keep the resident games within ~96 GB of node storage.
         nodes = int(min(8_000_000, max(65536, num_sims * 40 * (max_moves // 2 + 2))))
         tcap = 1024
-        while tcap < 2 * nodes:                                        # selfplay_create_impl rounds a table up to a power of two
+        while tcap < 2 * nodes:                                        # alloc_position_tables rounds a table up to a power of two
             tcap <<= 1
         per_game = 2 * nodes * 46 + 2 * tcap * 12                      # two halves of SoA nodes + two tables (8-byte key + 4-byte node)
         conc = max(1, min(conc, int(96e9 // per_game)))

@@ -1,7 +1,7 @@
 // extern "C" entry points of the analysis engine (include/m0_engine.h): a list of arbitrary positions in, the best moves, the
 // lines behind them and the evaluation out.  The engine is a self-play engine object that plays no games: its tree slots are
-// filled from a host queue (analysis_refill), searched by the pass of m0_selfplay_step (one_step / the external-evaluator
-// pair) and emptied by the result kernel (analysis_harvest); positions that ask for no search go through the position
+// filled from a host queue (analysis_refill, the engine's `refill`), searched by the pass of m0_selfplay_step (one_step / the
+// external-evaluator pair) and emptied by the result kernel (analysis_harvest, its `harvest`); positions that ask for no search go through the position
 // encoder, one forward and the policy kernel (policy_pass).
 #include <string.h>
 #include <algorithm>
@@ -13,11 +13,12 @@ using namespace m0;
 
 namespace m0 {
 
-static int pending_count(const m0_selfplay* sp) {
-    int n = (int)(sp->an->queue.size() + sp->an->policy_queue.size());
+static int searches_pending(const m0_selfplay* sp) {          // queued or in a slot
+    int n = (int)sp->an->queue.size();
     for (const HostGame& hgm : sp->games) n += hgm.in_use ? 1 : 0;
     return n;
 }
+static int pending_count(const m0_selfplay* sp) { return searches_pending(sp) + (int)sp->an->policy_queue.size(); }
 
 static m0_analysis_result blank_result(const AnalysisJob& job) {
     m0_analysis_result r;
@@ -26,34 +27,30 @@ static m0_analysis_result blank_result(const AnalysisJob& job) {
     return r;
 }
 
+// entry j of what a result kernel wrote (hlines / hnlines) -> the lines of r
+static void copy_lines(const Analysis& a, int j, m0_analysis_result& r) {
+    r.nlines = a.hnlines[j] < 0 ? 0 : (a.hnlines[j] > M0_AN_MAX_LINES ? M0_AN_MAX_LINES : a.hnlines[j]);
+    for (int l = 0; l < r.nlines; ++l) r.lines[l] = a.hlines[(size_t)j * M0_AN_MAX_LINES + l];
+}
+
 // Free slots take the next queued searches: a fresh tree each, random streams keyed by the submission's id (not by the slot).
-int analysis_refill(m0_selfplay* sp, std::string& err) {
+int analysis_refill(m0_selfplay* sp) {
     Analysis& a = *sp->an;
-    std::vector<int> ids, slots;
     for (int s = 0; s < sp->G && !a.queue.empty(); ++s) {
-        HostGame& hgm = sp->games[s];
-        if (hgm.in_use) continue;
+        if (sp->games[s].in_use) continue;
         AnalysisJob& job = a.queue.front();
-        hgm = HostGame();
-        hgm.in_use = true;
-        hgm.game_index = (int)job.id;
-        static_cast<Line&>(hgm) = std::move(job.line);
+        occupy_slot(sp, s, std::move(job.line), (int)job.id);
         a.slot_job[s] = AnalysisJob{Line(), job.sims, job.nlegal, job.id};
         a.queue.pop_front();
-        GameDev& g = sp->hg[s];
-        seed_game_dev(g, sp->cfg.seed, hgm.game_index);
-        g.evals = 0; g.net_id = 0;
-        arm_search(sp, s, hgm.pos, hgm.win, a.slot_job[s].sims, a.opts.dirichlet != 0, true);
-        ids.push_back(s);
-        slots.push_back(-1);
+        sp->hg[s].net_id = 0;
+        begin_search(sp, s, a.slot_job[s].sims, a.opts.dirichlet != 0, ROOT_FRESH);
     }
-    if (!ids.empty() && apply_advances(sp, ids, slots) != 0) { err = "advance failed"; return M0_ERR_HIP; }
-    return M0_OK;
+    return sp->adv.empty() ? M0_OK : apply_advances(sp);
 }
 
 // The searches that the last expand finished: their lines from the result kernel (the trees stay on the device), the rest
 // from the slots' control blocks, which the step has just mirrored.  The slots are free afterwards.
-int analysis_harvest(m0_selfplay* sp, std::string& err) {
+int analysis_harvest(m0_selfplay* sp) {
     Analysis& a = *sp->an;
     a.finished.clear();
     for (int s = 0; s < sp->G; ++s)
@@ -65,7 +62,7 @@ int analysis_harvest(m0_selfplay* sp, std::string& err) {
         hipMemcpyAsync(a.hlines.data(), a.lines_dev, sizeof(m0_analysis_line) * M0_AN_MAX_LINES * nf, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
         hipMemcpyAsync(a.hnlines.data(), a.nlines_dev, (size_t)nf * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
         hipStreamSynchronize(sp->stream) != hipSuccess) {
-        err = std::string("analysis harvest failed: ") + hipGetErrorString(hipGetLastError());
+        m0_set_error(std::string("analysis harvest failed: ") + hipGetErrorString(hipGetLastError()));
         return M0_ERR_HIP;
     }
     for (int j = 0; j < nf; ++j) {
@@ -75,21 +72,19 @@ int analysis_harvest(m0_selfplay* sp, std::string& err) {
         r.overflow = g.overflow; r.root_n = g.root_n; r.evals = g.evals;
         r.value = (float)g.root_v;
         r.root_q = g.root_n > 0 ? g.root_q : g.root_v;
-        r.nlines = a.hnlines[j] < 0 ? 0 : (a.hnlines[j] > M0_AN_MAX_LINES ? M0_AN_MAX_LINES : a.hnlines[j]);
-        for (int l = 0; l < r.nlines; ++l) r.lines[l] = a.hlines[(size_t)j * M0_AN_MAX_LINES + l];
+        copy_lines(a, j, r);
         if (g.overflow) sp->stats.arena_overflows++;
         a.done.push_back(r);
         g.active = 0; g.finished = 0;
         sp->games[s].in_use = false;
     }
-    std::vector<int> none;
-    if (apply_advances(sp, none, none) != 0) { err = "releasing the slots failed"; return M0_ERR_HIP; }   // the control blocks -> device
+    if (sync_games_h2d(sp) != 0) { m0_set_error("releasing the slots failed"); return M0_ERR_HIP; }
     return M0_OK;
 }
 
 // Policy mode: up to rows_max queued positions -> network input, legal moves and policy indices (the position encoder), one
 // forward, the policy kernel; the compact lines come back.
-static int policy_pass(m0_selfplay* sp, std::string& err) {
+static int policy_pass(m0_selfplay* sp) {
     Analysis& a = *sp->an;
     const int n = (int)std::min<size_t>(a.policy_queue.size(), (size_t)sp->rows_max);
     if (n <= 0) return M0_OK;
@@ -97,20 +92,21 @@ static int policy_pass(m0_selfplay* sp, std::string& err) {
     for (int i = 0; i < n; ++i) a.hpos[i] = a.policy_queue[i].line.pos;
     if (hipMemcpyAsync(a.pos_dev, a.hpos.data(), sizeof(Pos) * n, hipMemcpyHostToDevice, sp->stream) != hipSuccess ||
         launch_encode_positions(a.pos_dev, n, nullptr, sp->d.x0, nullptr, a.nlegal_dev, a.moves_dev, a.idx_dev, sp->stream) != hipSuccess) {
-        err = "position encode failed";
+        m0_set_error("position encode failed");
         return M0_ERR_HIP;
     }
+    std::string err;
     m0_net_lock(sp->nethandle);
     const int rc = sp->net->forward(nullptr, sp->d.x0, n, sp->logits_dev, sp->values_dev, nullptr, sp->stream, err);
     m0_net_unlock(sp->nethandle);
-    if (rc != M0_OK) return rc;
+    if (rc != M0_OK) { m0_set_error(err); return rc; }
     if (launch_policy_lines(sp->logits_dev, sp->values_dev, a.nlegal_dev, a.moves_dev, a.idx_dev, n, a.opts.multipv, a.lines_dev,
                             a.nlines_dev, a.value_out_dev, sp->stream) != hipSuccess ||
         hipMemcpyAsync(a.hlines.data(), a.lines_dev, sizeof(m0_analysis_line) * M0_AN_MAX_LINES * n, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
         hipMemcpyAsync(a.hnlines.data(), a.nlines_dev, (size_t)n * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
         hipMemcpyAsync(a.hvalues.data(), a.value_out_dev, (size_t)n * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
         hipStreamSynchronize(sp->stream) != hipSuccess) {
-        err = std::string("policy pass failed: ") + hipGetErrorString(hipGetLastError());
+        m0_set_error(std::string("policy pass failed: ") + hipGetErrorString(hipGetLastError()));
         return M0_ERR_HIP;
     }
     for (int i = 0; i < n; ++i) {
@@ -118,8 +114,7 @@ static int policy_pass(m0_selfplay* sp, std::string& err) {
         r.evals = 1;
         r.value = a.hvalues[i];
         r.root_q = (double)r.value;
-        r.nlines = a.hnlines[i] < 0 ? 0 : (a.hnlines[i] > M0_AN_MAX_LINES ? M0_AN_MAX_LINES : a.hnlines[i]);
-        for (int l = 0; l < r.nlines; ++l) r.lines[l] = a.hlines[(size_t)i * M0_AN_MAX_LINES + l];
+        copy_lines(a, i, r);
         a.done.push_back(r);
         a.policy_queue.pop_front();
     }
@@ -143,7 +138,7 @@ static m0_selfplay* analysis_create_impl(m0_net* nh, const m0_selfplay_cfg* cfg,
     c.total_games = 0; c.record_games = 0; c.ssl_in_forward = 0; c.ssl_targets = 0; c.opening_random_plies = 0;
     c.playout_random_frac = 0.0; c.fresh_tree_per_move = 1; c.root_reinfer = 0;
     c.arena_mode = 0; c.arena_eval_cache = 0; c.arena_paired_openings = 0; c.eval_cache = 0; c.tail_split = 0;
-    std::unique_ptr<m0_selfplay, decltype(&m0_selfplay_destroy)> owner(engine_create(nh, nullptr, &c, false), &m0_selfplay_destroy);
+    std::unique_ptr<m0_selfplay, decltype(&m0_selfplay_destroy)> owner(engine_create(nh, nullptr, &c, EngineKind::Analysis), &m0_selfplay_destroy);
     m0_selfplay* sp = owner.get();
     if (!sp) return nullptr;
     Analysis* a = sp->an = new Analysis();
@@ -183,15 +178,8 @@ m0_selfplay* m0_analysis_create_ext(const m0_selfplay_cfg* cfg, const m0_analysi
     return analysis_create_impl(nullptr, cfg, opts);
 }
 
-// Head of every m0_analysis_* call: the engine's lock and device; any other engine is refused with M0_ERR_STATE.
-#define M0_ANALYSIS_ENGINE(sp, what)                                                          \
-    if (!(sp)) { m0_set_error("sp is null"); return M0_ERR_INVALID; }                         \
-    std::lock_guard<std::mutex> lk((sp)->mu);                                                 \
-    if (!(sp)->an) { m0_set_error(what ": not an analysis engine"); return M0_ERR_STATE; }    \
-    (void)hipSetDevice((sp)->device)
-
 int m0_analysis_submit(m0_selfplay* sp, const char* fen, const char* const* ucis, int n_moves, int sims, int64_t id) {
-    M0_ANALYSIS_ENGINE(sp, "m0_analysis_submit");
+    M0_ENGINE_CALL(sp, "m0_analysis_submit", KIND_ANALYSIS, true);
     if (!fen || sims < 0 || n_moves < 0 || (n_moves > 0 && !ucis)) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
     if (sims == 0 && !sp->net) { m0_set_error("policy mode (sims = 0) needs an engine with a network"); return M0_ERR_UNSUPPORTED; }
     AnalysisJob job;
@@ -224,34 +212,31 @@ int m0_analysis_submit(m0_selfplay* sp, const char* fen, const char* const* ucis
 }
 
 int m0_analysis_step(m0_selfplay* sp, int steps) {
-    M0_ANALYSIS_ENGINE(sp, "m0_analysis_step");
+    M0_ENGINE_CALL(sp, "m0_analysis_step", KIND_ANALYSIS, true);
     if (!sp->net) { m0_set_error("m0_analysis_step needs a network (use m0_analysis_ext_select / _expand without one)"); return M0_ERR_STATE; }
     if (sp->ext_pending) { m0_set_error("m0_analysis_ext_expand outstanding"); return M0_ERR_STATE; }
-    std::string err;
     for (int i = 0; i < steps && pending_count(sp) > 0; ++i) {
-        int rc = policy_pass(sp, err);
-        if (rc == M0_OK) rc = analysis_refill(sp, err);
-        bool searching = false;
-        for (const HostGame& hgm : sp->games) searching = searching || hgm.in_use;
-        if (rc == M0_OK && searching) rc = one_step(sp, err);
-        if (rc != M0_OK) { m0_set_error(err); return rc; }
+        int rc = policy_pass(sp);
+        if (rc == M0_OK) rc = refill(sp);
+        if (rc == M0_OK && searches_pending(sp) > 0) rc = one_step(sp);      // the pass and the harvest
+        if (rc != M0_OK) return rc;
     }
     return M0_OK;
 }
 
 int m0_analysis_ext_select(m0_selfplay* sp, int* rows, float* planes, int max_rows) {
-    M0_ANALYSIS_ENGINE(sp, "m0_analysis_ext_select");
+    M0_ENGINE_CALL(sp, "m0_analysis_ext_select", KIND_ANALYSIS, true);
     if (!rows) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     return ext_select_impl(sp, rows, nullptr, planes, nullptr, max_rows);
 }
 
 int m0_analysis_ext_expand(m0_selfplay* sp, const float* logits, const float* values, int rows) {
-    M0_ANALYSIS_ENGINE(sp, "m0_analysis_ext_expand");
+    M0_ENGINE_CALL(sp, "m0_analysis_ext_expand", KIND_ANALYSIS, true);
     return ext_expand_impl(sp, logits, values, rows, nullptr, nullptr, 0);
 }
 
 int m0_analysis_poll(m0_selfplay* sp, m0_analysis_result* out) {
-    M0_ANALYSIS_ENGINE(sp, "m0_analysis_poll");
+    M0_ENGINE_CALL(sp, "m0_analysis_poll", KIND_ANALYSIS, true);
     if (!out) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     if (sp->an->done.empty()) return 0;
     *out = sp->an->done.front();
@@ -260,7 +245,7 @@ int m0_analysis_poll(m0_selfplay* sp, m0_analysis_result* out) {
 }
 
 int m0_analysis_pending(m0_selfplay* sp) {
-    M0_ANALYSIS_ENGINE(sp, "m0_analysis_pending");
+    M0_ENGINE_CALL(sp, "m0_analysis_pending", KIND_ANALYSIS, true);
     return pending_count(sp);
 }
 

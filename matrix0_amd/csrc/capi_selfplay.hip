@@ -7,8 +7,8 @@
 
 using namespace m0;
 
-// `arena`: a match engine, whose cache switch is arena_eval_cache (eval_cache is ignored there: m0_engine.h)
-static void fill_tree_cfg(const m0_selfplay_cfg& c, bool arena, TreeCfg& t) {
+// `match`: a match engine, whose cache switch is arena_eval_cache (eval_cache is ignored there: m0_engine.h)
+static void fill_tree_cfg(const m0_selfplay_cfg& c, bool match, TreeCfg& t) {
     t.fpu_reduction = c.fpu_reduction; t.draw_penalty = c.draw_penalty; t.virtual_loss = c.virtual_loss;
     t.selection_jitter = c.selection_jitter; t.cpuct = c.cpuct; t.cpuct_start = c.cpuct_start; t.cpuct_end = c.cpuct_end;
     t.cpuct_plies = c.cpuct_plies; t.use_c_base = c.use_c_base; t.cpuct_c_base = c.cpuct_c_base; t.cpuct_c_init = c.cpuct_c_init;
@@ -18,7 +18,7 @@ static void fill_tree_cfg(const m0_selfplay_cfg& c, bool arena, TreeCfg& t) {
     t.tt_merge = c.tt_merge; t.raw_legal_priors = c.raw_legal_priors; t.max_children = c.max_children;
     t.min_child_prior = c.min_child_prior;
     // the cached payload is the LEGAL logits: only the legal-softmax expansion can be served from it
-    t.eval_cache = ((arena ? c.arena_eval_cache : c.eval_cache) && c.legal_softmax && !c.raw_legal_priors && !c.tt_merge) ? 1 : 0;
+    t.eval_cache = ((match ? c.arena_eval_cache : c.eval_cache) && c.legal_softmax && !c.raw_legal_priors && !c.tt_merge) ? 1 : 0;
 }
 
 static void alloc_tree_arenas(m0_selfplay* sp) {
@@ -49,7 +49,7 @@ static bool alloc_position_tables(m0_selfplay* sp) {
     while (tc < 2 * sp->cap) tc <<= 1;
     sp->d.tt_cap = tc;
     // match engine: one table per side, kept for the whole game (the reference keeps one MCTS object per side, arena.py:157-158)
-    sp->d.tt_sides = sp->cfg.arena_mode ? 2 : 1;
+    sp->d.tt_sides = sp->kind == EngineKind::Match ? 2 : 1;
     // a side's half that cannot hold one more search starts over BEFORE that search (advance_kernel), not in the middle of it:
     // ~35 children per expansion on average, 48 with margin, never more than half of the half
     sp->d.search_nodes = (int)std::min<long>((long)sp->cfg.num_simulations * 48 + 4 * M0_MAX_CHILDREN, (long)sp->cap / 2);
@@ -69,7 +69,7 @@ static bool alloc_eval_cache(m0_selfplay* sp) {
     while (sets * 4 < entries) sets <<= 1;
     EvalCache& ec = sp->d.ec;
     ec.sets = sets;
-    ec.sides = sp->cfg.arena_mode ? 2 : 1;              // match engine: one instance per network
+    ec.sides = sp->kind == EngineKind::Match ? 2 : 1;             // match engine: one instance per network
     const size_t entries_all = (size_t)sp->G * ec.sides * sets * 4;
     ec.keys = dalloc<uint64_t>(sp, entries_all);
     ec.stamps = dalloc<uint32_t>(sp, entries_all);
@@ -82,7 +82,7 @@ static bool alloc_eval_cache(m0_selfplay* sp) {
 
 // the batch (one region per network), the evaluator's outputs and the small staging buffers
 static bool alloc_batch_buffers(m0_selfplay* sp) {
-    const int nreg = sp->cfg.arena_mode ? 2 : 1;
+    const int nreg = sp->kind == EngineKind::Match ? 2 : 1;
     sp->d.hist = dalloc<uint64_t>(sp, (size_t)sp->G * M0_HIST_CAP);
     sp->d.results = dalloc<RootResult>(sp, sp->G);
     sp->d.row_counter = dalloc<int>(sp, 4);
@@ -102,7 +102,7 @@ static bool alloc_batch_buffers(m0_selfplay* sp) {
         }
     }
     sp->ids_dev = dalloc<int>(sp, sp->G);
-    sp->slots_dev = dalloc<int>(sp, sp->G);
+    sp->roots_dev = dalloc<int>(sp, sp->G);
     sp->d.logits = sp->logits_dev; sp->d.values = sp->values_dev;
     sp->d.G = sp->G; sp->d.L = sp->L;
     return true;
@@ -110,7 +110,7 @@ static bool alloc_batch_buffers(m0_selfplay* sp) {
 
 // cfg.tail_split: the second instance of the network on a stream of its own (one_step, split_rows)
 static bool make_tail_view(m0_selfplay* sp) {
-    if (!(sp->cfg.tail_split && sp->net && !sp->cfg.arena_mode && sp->net->cfg().channels > 256 && sp->net->cfg().channels <= 320 &&
+    if (!(sp->cfg.tail_split && sp->net && sp->kind != EngineKind::Match && sp->net->cfg().channels > 256 && sp->net->cfg().channels <= 320 &&
           sp->rows_max >= 2048)) return true;
     // M0_TAIL_CU_MASK=w0,...,w7 (measurement switch, like M0_NET_CU_MASK for the network's own stream): the second instance's
     // stream runs on those CUs only -- with complementary masks every launch of the two halves has a known share of the chip
@@ -157,7 +157,7 @@ static bool build_engine(m0_selfplay* sp) {
     return true;
 }
 
-m0_selfplay* m0::engine_create(m0_net* nh, m0_net* nh_b, const m0_selfplay_cfg* cfg, bool arena) {
+m0_selfplay* m0::engine_create(m0_net* nh, m0_net* nh_b, const m0_selfplay_cfg* cfg, EngineKind kind) {
     if (!cfg) { m0_set_error("cfg is null"); return nullptr; }
     if (cfg->concurrent_games <= 0 || cfg->inference_batch_size <= 0 || cfg->num_simulations <= 0) {
         m0_set_error("concurrent_games, inference_batch_size and num_simulations must be positive");
@@ -173,13 +173,15 @@ m0_selfplay* m0::engine_create(m0_net* nh, m0_net* nh_b, const m0_selfplay_cfg* 
     sp->nethandle_b = nh_b;
     sp->net = m0_net_impl(nh);
     sp->net_b = m0_net_impl(nh_b);
-    sp->cfg.arena_mode = (nh_b || arena) ? 1 : 0;
+    sp->kind = kind;
+    const bool match = kind == EngineKind::Match;
+    sp->cfg.arena_mode = match ? 1 : 0;
     // A match engine alternates two networks in one game slot and the cache key covers the position only (no network id):
     // with ONE cache side B's leaves would be expanded from side A's cached value and logits.  eval_cache is therefore ignored
     // there, whatever the caller asked for; arena_eval_cache gives each network a cache of its own (EvalCache::sides).
-    if (sp->cfg.arena_mode) sp->cfg.eval_cache = 0;
+    if (match) sp->cfg.eval_cache = 0;
     else { sp->cfg.arena_eval_cache = 0; sp->cfg.arena_paired_openings = 0; }
-    fill_tree_cfg(sp->cfg, sp->cfg.arena_mode != 0, sp->tc);
+    fill_tree_cfg(sp->cfg, match, sp->tc);
     sp->device = nh ? m0_net_device(nh) : 0;
     if (nh) forward_gate_join(sp);
     (void)hipSetDevice(sp->device);
@@ -221,24 +223,18 @@ static void upload_eval(m0_selfplay* sp, size_t row_base, const float* logits, c
 // first half of a step for an external evaluator: select, then the leaves' planes on the host (region 0 = network A / the only
 // network, region 1 = network B of a match engine, whose rows start at d.net_row_base on the device)
 int m0::ext_select_impl(m0_selfplay* sp, int* rows_a, int* rows_b, float* planes_a, float* planes_b, int max_rows) {
-    (void)hipSetDevice(sp->device);
     if (sp->ext_pending) { m0_set_error("m0_selfplay_ext_expand outstanding"); return M0_ERR_STATE; }
     // select applies virtual losses and reserves batch rows: refuse a buffer that cannot take the worst case BEFORE it runs
     // (an error after it would leave the engine waiting for an ext_expand the caller has no planes for)
-    if (!planes_a || (sp->cfg.arena_mode && !planes_b) || max_rows < sp->G * (sp->L + 1)) {
+    if (!planes_a || (sp->kind == EngineKind::Match && !planes_b) || max_rows < sp->G * (sp->L + 1)) {
         m0_set_error("planes buffer too small: concurrent_games * (inference_batch_size + 1) rows are required");
         return M0_ERR_INVALID;
     }
-    int rc = M0_OK;
-    if (sp->an) {                                   // an analysis engine fills its free slots from its queue instead
-        std::string err;
-        rc = analysis_refill(sp, err);
-        if (rc != M0_OK) m0_set_error(err);
-    } else rc = start_first_games(sp);
+    int rc = refill(sp);
     if (rc != M0_OK) return rc;
     int r = 0;
-    if (run_select(sp, &r) != 0) { m0_set_error(std::string("select failed: ") + hipGetErrorString(hipGetLastError())); return M0_ERR_HIP; }
-    const int rb = sp->cfg.arena_mode ? sp->rows2[1] : 0;
+    if ((rc = run_select(sp, &r)) != M0_OK) return rc;
+    const int rb = sp->kind == EngineKind::Match ? sp->rows2[1] : 0;
     if (r > sp->rows_max || rb > sp->rows_max) { m0_set_error("row counter overflow"); return M0_ERR_STATE; }
     *rows_a = r;
     if (rows_b) *rows_b = rb;
@@ -251,40 +247,39 @@ int m0::ext_select_impl(m0_selfplay* sp, int* rows_a, int* rows_b, float* planes
 
 int m0::ext_expand_impl(m0_selfplay* sp, const float* logits_a, const float* values_a, int rows_a, const float* logits_b,
                            const float* values_b, int rows_b) {
-    (void)hipSetDevice(sp->device);
     if (!sp->ext_pending) { m0_set_error("no m0_selfplay_ext_select outstanding"); return M0_ERR_STATE; }
     if (rows_a != sp->last_rows || rows_b != sp->last_rows_b) { m0_set_error("rows does not match the last select"); return M0_ERR_INVALID; }
     if ((rows_a > 0 && (!logits_a || !values_a)) || (rows_b > 0 && (!logits_b || !values_b))) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     upload_eval(sp, 0, logits_a, values_a, rows_a);
     upload_eval(sp, (size_t)sp->d.net_row_base, logits_b, values_b, rows_b);
     sp->ext_pending = false;
-    std::string err;
     (void)hipEventRecord(sp->ev0, sp->stream); (void)hipEventRecord(sp->ev1, sp->stream);
-    int rc = step_back(sp, rows_a + rows_b, now_ms(), err);
-    if (rc != M0_OK) m0_set_error(err);
-    return rc;
+    return finish_step(sp, rows_a + rows_b, now_ms());
 }
 
-bool m0::refuse_analysis(m0_selfplay* sp, const char* what) {
-    if (!sp->an) return false;
-    m0_set_error(std::string(what) + ": this is an analysis engine (use the m0_analysis_* functions)");
-    return true;
+bool m0::kind_accepted(const m0_selfplay* sp, const char* what, unsigned kinds) {
+    if (kinds & (1u << (int)sp->kind)) return true;
+    static const char* const is_a[] = {"a self-play engine", "a match engine", "an analysis engine"};
+    const char* only = kinds == KIND_SELFPLAY ? "self-play engines" : kinds == KIND_MATCH ? "match engines"
+                     : kinds == KIND_ANALYSIS ? "analysis engines" : "self-play and match engines";
+    m0_set_error(std::string(what) + ": " + only + " only, this is " + is_a[(int)sp->kind]);
+    return false;
 }
 
 extern "C" {
 
-m0_selfplay* m0_selfplay_create(m0_net* nh, const m0_selfplay_cfg* cfg) { return engine_create(nh, nullptr, cfg, false); }
+m0_selfplay* m0_selfplay_create(m0_net* nh, const m0_selfplay_cfg* cfg) { return engine_create(nh, nullptr, cfg, EngineKind::SelfPlay); }
 
 m0_selfplay* m0_arena_create(m0_net* net_a, m0_net* net_b, const m0_selfplay_cfg* cfg) {
     if (!net_a || !net_b) { m0_set_error("m0_arena_create needs two networks"); return nullptr; }
     if (m0_net_device(net_a) != m0_net_device(net_b)) { m0_set_error("both networks must live on the same HIP device"); return nullptr; }
     if (cfg && (cfg->ssl_in_forward || cfg->ssl_targets)) { m0_set_error("arena games carry no SSL outputs"); return nullptr; }
-    return engine_create(net_a, net_b, cfg, false);
+    return engine_create(net_a, net_b, cfg, EngineKind::Match);
 }
 
 m0_selfplay* m0_arena_create_ext(const m0_selfplay_cfg* cfg) {
     if (cfg && (cfg->ssl_in_forward || cfg->ssl_targets)) { m0_set_error("arena games carry no SSL outputs"); return nullptr; }
-    return engine_create(nullptr, nullptr, cfg, true);
+    return engine_create(nullptr, nullptr, cfg, EngineKind::Match);
 }
 
 void m0_selfplay_destroy(m0_selfplay* sp) {
@@ -307,8 +302,7 @@ void m0_selfplay_destroy(m0_selfplay* sp) {
 
 int m0_selfplay_set_openings(m0_selfplay* sp, const char* const* fens, int n) {
     if (!sp || n < 0 || (n > 0 && !fens)) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(sp->mu);
-    if (refuse_analysis(sp, "m0_selfplay_set_openings")) return M0_ERR_STATE;
+    M0_ENGINE_CALL(sp, "m0_selfplay_set_openings", KIND_GAMES, false);
     if (sp->stats.games_started != 0) { m0_set_error("set the opening book before the first step"); return M0_ERR_STATE; }
     std::vector<Pos> book(n);
     for (int i = 0; i < n; ++i)
@@ -320,64 +314,48 @@ int m0_selfplay_set_openings(m0_selfplay* sp, const char* const* fens, int n) {
 
 int m0_selfplay_ext_select(m0_selfplay* sp, int* rows, float* planes, int max_rows) {
     if (!sp || !rows) { m0_set_error("null argument"); return M0_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(sp->mu);
-    if (refuse_analysis(sp, "m0_selfplay_ext_select")) return M0_ERR_STATE;
-    if (sp->cfg.arena_mode) { m0_set_error("a match engine has two evaluators: use m0_arena_ext_select"); return M0_ERR_STATE; }
+    M0_ENGINE_CALL(sp, "m0_selfplay_ext_select", KIND_SELFPLAY, true);
     return ext_select_impl(sp, rows, nullptr, planes, nullptr, max_rows);
 }
 
 int m0_selfplay_ext_expand(m0_selfplay* sp, const float* logits, const float* values, int rows) {
-    if (!sp) { m0_set_error("null argument"); return M0_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(sp->mu);
-    if (refuse_analysis(sp, "m0_selfplay_ext_expand")) return M0_ERR_STATE;
-    if (sp->cfg.arena_mode) { m0_set_error("a match engine has two evaluators: use m0_arena_ext_expand"); return M0_ERR_STATE; }
+    M0_ENGINE_CALL(sp, "m0_selfplay_ext_expand", KIND_SELFPLAY, true);
     return ext_expand_impl(sp, logits, values, rows, nullptr, nullptr, 0);
 }
 
 int m0_arena_ext_select(m0_selfplay* sp, int* rows_a, int* rows_b, float* planes_a, float* planes_b, int max_rows) {
     if (!sp || !rows_a || !rows_b) { m0_set_error("null argument"); return M0_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(sp->mu);
-    if (refuse_analysis(sp, "m0_arena_ext_select")) return M0_ERR_STATE;
-    if (!sp->cfg.arena_mode) { m0_set_error("not a match engine"); return M0_ERR_STATE; }
+    M0_ENGINE_CALL(sp, "m0_arena_ext_select", KIND_MATCH, true);
     return ext_select_impl(sp, rows_a, rows_b, planes_a, planes_b, max_rows);
 }
 
 int m0_arena_ext_expand(m0_selfplay* sp, const float* logits_a, const float* values_a, int rows_a, const float* logits_b,
                         const float* values_b, int rows_b) {
-    if (!sp) { m0_set_error("null argument"); return M0_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(sp->mu);
-    if (refuse_analysis(sp, "m0_arena_ext_expand")) return M0_ERR_STATE;
-    if (!sp->cfg.arena_mode) { m0_set_error("not a match engine"); return M0_ERR_STATE; }
+    M0_ENGINE_CALL(sp, "m0_arena_ext_expand", KIND_MATCH, true);
     return ext_expand_impl(sp, logits_a, values_a, rows_a, logits_b, values_b, rows_b);
 }
 
 int m0_selfplay_step(m0_selfplay* sp, int steps) {
-    if (!sp) { m0_set_error("sp is null"); return M0_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(sp->mu);
-    if (refuse_analysis(sp, "m0_selfplay_step")) return M0_ERR_STATE;
-    (void)hipSetDevice(sp->device);
-    std::string err;
+    M0_ENGINE_CALL(sp, "m0_selfplay_step", KIND_GAMES, true);
     if (sp->ext_pending) { m0_set_error("m0_selfplay_ext_expand outstanding"); return M0_ERR_STATE; }
-    { int rc0 = start_first_games(sp); if (rc0 != M0_OK) return rc0; }
-    for (int i = 0; i < steps; ++i) {
+    int rc = refill(sp);
+    for (int i = 0; i < steps && rc == M0_OK; ++i) {
         if (sp->stats.active_games == 0 && sp->stats.steps > 0) break;
-        int rc = one_step(sp, err);
-        if (rc != M0_OK) { m0_set_error(err); return rc; }
+        rc = one_step(sp);
     }
-    return M0_OK;
+    return rc;
 }
 
 int m0_selfplay_stats_get(m0_selfplay* sp, m0_selfplay_stats* out) {
     if (!sp || !out) { m0_set_error("null argument"); return M0_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(sp->mu);
+    M0_ENGINE_CALL(sp, "m0_selfplay_stats_get", KIND_ANY, false);
     *out = sp->stats;
     return M0_OK;
 }
 
 int m0_selfplay_poll(m0_selfplay* sp, m0_game_record* out) {
     if (!sp || !out) { m0_set_error("null argument"); return M0_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(sp->mu);
-    if (refuse_analysis(sp, "m0_selfplay_poll")) return M0_ERR_STATE;
+    M0_ENGINE_CALL(sp, "m0_selfplay_poll", KIND_GAMES, false);
     if (sp->done_meta.empty()) return 0;
     *out = sp->done_meta.front();
     sp->done_meta.pop_front();
@@ -389,8 +367,7 @@ void m0_game_record_free(m0_game_record* rec) {
 }
 
 int m0_selfplay_running(m0_selfplay* sp) {
-    if (!sp) return 0;
-    std::lock_guard<std::mutex> lk(sp->mu);
+    M0_ENGINE_CALL_OR(0, sp, "m0_selfplay_running", KIND_ANY, false);
     if (sp->stats.games_started == 0) return 1;
     if (sp->stats.active_games > 0) return 1;
     return (sp->cfg.total_games <= 0 || sp->next_game < sp->cfg.total_games) ? 1 : 0;
@@ -399,30 +376,20 @@ int m0_selfplay_running(m0_selfplay* sp) {
 // ---------------- split-step search ----------------
 int m0_search_begin(m0_selfplay* sp, int g, const char* fen, int sims, int dirichlet, int game_uid) {
     if (!sp || !fen || g < 0 || g >= sp->G || sims <= 0) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(sp->mu);
-    if (refuse_analysis(sp, "m0_search_begin")) return M0_ERR_STATE;
-    (void)hipSetDevice(sp->device);
-    Pos p;
-    if (parse_fen(fen, p) != 0) { m0_set_error("bad FEN"); return M0_ERR_INVALID; }
+    M0_ENGINE_CALL(sp, "m0_search_begin", KIND_GAMES, true);
+    Line line;                             // history-less
+    if (parse_fen(fen, line.pos) != 0) { m0_set_error("bad FEN"); return M0_ERR_INVALID; }
     if (sync_games_d2h(sp) != 0) { m0_set_error("device sync failed"); return M0_ERR_HIP; }
-    HostGame& hgm = sp->games[g];
-    hgm = HostGame();
-    hgm.in_use = true; hgm.pos = p; hgm.game_index = game_uid;
-    seed_game_dev(sp->hg[g], sp->cfg.seed, game_uid);
-    sp->hg[g].evals = 0;
-    arm_search(sp, g, p, hgm.win, sims, dirichlet != 0, true);
-    std::vector<int> ids{g}, slots{-1};
-    if (apply_advances(sp, ids, slots) != 0) { m0_set_error("advance failed"); return M0_ERR_HIP; }
-    return M0_OK;
+    occupy_slot(sp, g, std::move(line), game_uid);
+    begin_search(sp, g, sims, dirichlet != 0, ROOT_FRESH);
+    return apply_advances(sp);
 }
 
 int m0_search_select(m0_selfplay* sp, int* rows, float* planes, int max_rows) {
     if (!sp || !rows) { m0_set_error("null argument"); return M0_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(sp->mu);
-    if (refuse_analysis(sp, "m0_search_select")) return M0_ERR_STATE;
-    (void)hipSetDevice(sp->device);
+    M0_ENGINE_CALL(sp, "m0_search_select", KIND_GAMES, true);
     int r = 0;
-    if (run_select(sp, &r) != 0) { m0_set_error(std::string("select failed: ") + hipGetErrorString(hipGetLastError())); return M0_ERR_HIP; }
+    { const int rc = run_select(sp, &r); if (rc != M0_OK) return rc; }
     *rows = r;
     sp->last_rows = r;
     if (planes && r > 0) {
@@ -434,9 +401,7 @@ int m0_search_select(m0_selfplay* sp, int* rows, float* planes, int max_rows) {
 
 int m0_search_expand(m0_selfplay* sp, const float* logits, const float* values, int rows) {
     if (!sp) { m0_set_error("null argument"); return M0_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(sp->mu);
-    if (refuse_analysis(sp, "m0_search_expand")) return M0_ERR_STATE;
-    (void)hipSetDevice(sp->device);
+    M0_ENGINE_CALL(sp, "m0_search_expand", KIND_GAMES, true);
     if (rows != sp->last_rows || rows > sp->rows_max) { m0_set_error("rows does not match the last select"); return M0_ERR_INVALID; }
     if (rows > 0 && (!logits || !values)) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     upload_eval(sp, 0, logits, values, rows);
@@ -449,9 +414,7 @@ int m0_search_expand(m0_selfplay* sp, const float* logits, const float* values, 
 int m0_search_result(m0_selfplay* sp, int g, int* nchild, int32_t* child_n, uint16_t* child_mv, int32_t* child_idx,
                      double* child_prior, double* child_q, double* root_q, int* root_n, int* finished) {
     if (!sp || g < 0 || g >= sp->G) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(sp->mu);
-    if (refuse_analysis(sp, "m0_search_result")) return M0_ERR_STATE;
-    (void)hipSetDevice(sp->device);
+    M0_ENGINE_CALL(sp, "m0_search_result", KIND_GAMES, true);
     if (finished) *finished = sp->hg[g].finished;
     if (!sp->hg[g].finished) { if (nchild) *nchild = 0; return M0_OK; }
     (void)hipMemcpy(&sp->hres[g], sp->d.results + g, sizeof(RootResult), hipMemcpyDeviceToHost);
@@ -471,28 +434,22 @@ int m0_search_result(m0_selfplay* sp, int g, int* nchild, int32_t* child_n, uint
 
 int m0_search_advance(m0_selfplay* sp, int g, int slot, int sims, int dirichlet) {
     if (!sp || g < 0 || g >= sp->G || sims <= 0) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(sp->mu);
-    if (refuse_analysis(sp, "m0_search_advance")) return M0_ERR_STATE;
-    (void)hipSetDevice(sp->device);
+    M0_ENGINE_CALL(sp, "m0_search_advance", KIND_GAMES, true);
     // refresh the mirror first: an earlier advance changed root/next/arena on the device only
     if (sync_games_d2h(sp) != 0) { m0_set_error("device sync failed"); return M0_ERR_HIP; }
     if (!sp->hg[g].finished) { m0_set_error("search not finished"); return M0_ERR_STATE; }
     (void)hipMemcpy(&sp->hres[g], sp->d.results + g, sizeof(RootResult), hipMemcpyDeviceToHost);
     const RootResult& R = sp->hres[g];
     if (slot < 0 || slot >= R.nchild) { m0_set_error("child slot out of range"); return M0_ERR_INVALID; }
-    HostGame& hgm = sp->games[g];
-    hgm.play(R.child_mv[slot]);
+    sp->games[g].play(R.child_mv[slot]);
     const bool fresh = sp->cfg.fresh_tree_per_move || sp->cfg.tt_merge;
-    arm_search(sp, g, hgm.pos, hgm.win, sims, dirichlet != 0, fresh);
-    std::vector<int> ids{g}, slots{fresh ? -1 : slot};
-    if (apply_advances(sp, ids, slots) != 0) { m0_set_error("advance failed"); return M0_ERR_HIP; }
-    return M0_OK;
+    begin_search(sp, g, sims, dirichlet != 0, fresh ? ROOT_FRESH : slot);
+    return apply_advances(sp);
 }
 
 int m0_selfplay_last_batch_nhwc(m0_selfplay* sp, uint16_t* out, int max_rows, int* rows) {
     if (!sp || !out || !rows) { m0_set_error("null argument"); return M0_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(sp->mu);
-    (void)hipSetDevice(sp->device);
+    M0_ENGINE_CALL(sp, "m0_selfplay_last_batch_nhwc", KIND_ANY, true);
     const int r = sp->last_rows;
     if (r > max_rows) { m0_set_error("output buffer too small"); return M0_ERR_INVALID; }
     *rows = r;

@@ -259,17 +259,6 @@ int m0_tb_probe_fens(const m0_tb* tb, const char* const* fens, int n, uint8_t* h
     return M0_OK;
 }
 
-int m0_selfplay_set_tablebase(m0_selfplay* sp, const m0_tb* tb, int max_pieces) {
-    if (!sp) { m0_set_error("sp is null"); return M0_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(sp->mu);
-    if (sp->an || sp->cfg.arena_mode) { m0_set_error("m0_selfplay_set_tablebase: self-play engines only (matches and analysis do not probe)"); return M0_ERR_STATE; }
-    if (sp->stats.games_started != 0) { m0_set_error("attach the tablebase before the first step"); return M0_ERR_STATE; }
-    if (tb && max_pieces < 2) { m0_set_error("max_pieces must be at least 2"); return M0_ERR_INVALID; }
-    sp->tb = tb;
-    sp->tb_max_pieces = tb ? std::min(max_pieces, tb->max_men) : 0;
-    return M0_OK;
-}
-
 int m0_tb_root_lines(const m0_tb* tb, const char* fen, int multipv, int pv_len, m0_analysis_result* out) {
     if (!tb || !fen || !out) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     if (multipv < 1 || multipv > M0_AN_MAX_LINES || pv_len < 1 || pv_len > M0_AN_MAX_PV) {
@@ -281,17 +270,17 @@ int m0_tb_root_lines(const m0_tb* tb, const char* fen, int multipv, int pv_len, 
     return tb_root_lines(tb, tb->max_men, p, multipv, pv_len, out) ? 1 : 0;
 }
 
-int m0_selfplay_set_search_tablebase(m0_selfplay* sp, const m0_tb* tb, int max_pieces) {
-    if (!sp) { m0_set_error("sp is null"); return M0_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(sp->mu);
-    const bool queued = sp->an && (!sp->an->queue.empty() || !sp->an->policy_queue.empty() || !sp->an->done.empty());
-    if (sp->stats.games_started != 0 || sp->stats.steps != 0 || sp->stats.evals != 0 || sp->ext_pending || queued) {
-        m0_set_error("attach the tablebase before the first step");
-        return M0_ERR_STATE;
+// Both attachments.  `in_search`: also the device copy that select_kernel probes, and the stricter rule for "nothing has run yet".
+static int attach_tablebase(m0_selfplay* sp, const m0_tb* tb, int max_pieces, bool in_search) {
+    bool started = sp->stats.games_started != 0;
+    if (in_search) {
+        const bool queued = sp->an && (!sp->an->queue.empty() || !sp->an->policy_queue.empty() || !sp->an->done.empty());
+        started = started || sp->stats.steps != 0 || sp->stats.evals != 0 || sp->ext_pending || queued;
     }
+    if (started) { m0_set_error("attach the tablebase before the first step"); return M0_ERR_STATE; }
     if (tb && max_pieces < 2) { m0_set_error("max_pieces must be at least 2"); return M0_ERR_INVALID; }
     const TbSet* set_dev = nullptr;
-    if (tb) {
+    if (tb && in_search) {
         std::string err;
         const int rc = tb_device_set(tb, sp->device, &set_dev, err);
         if (rc != M0_OK) { m0_set_error("m0_selfplay_set_search_tablebase: " + err); return rc; }
@@ -300,22 +289,29 @@ int m0_selfplay_set_search_tablebase(m0_selfplay* sp, const m0_tb* tb, int max_p
     // the host probe of a root (after a played move; of a submission) and the leaf probe of select_kernel read the same limit
     sp->tb = tb;
     sp->tb_max_pieces = tb ? std::min(max_pieces, tb->max_men) : 0;
-    sp->d.tb_set = set_dev;
-    sp->d.tb_max_pieces = sp->tb_max_pieces;
+    if (in_search) { sp->d.tb_set = set_dev; sp->d.tb_max_pieces = sp->tb_max_pieces; }
     return M0_OK;
 }
 
+int m0_selfplay_set_tablebase(m0_selfplay* sp, const m0_tb* tb, int max_pieces) {
+    M0_ENGINE_CALL(sp, "m0_selfplay_set_tablebase", KIND_SELFPLAY, false);      // matches and analysis do not probe after a move
+    return attach_tablebase(sp, tb, max_pieces, false);
+}
+
+int m0_selfplay_set_search_tablebase(m0_selfplay* sp, const m0_tb* tb, int max_pieces) {
+    M0_ENGINE_CALL(sp, "m0_selfplay_set_search_tablebase", KIND_ANY, false);
+    return attach_tablebase(sp, tb, max_pieces, true);
+}
+
 uint64_t m0_selfplay_tb_leaves(m0_selfplay* sp) {
-    if (!sp) return 0;
-    std::lock_guard<std::mutex> lk(sp->mu);
+    M0_ENGINE_CALL_OR(0, sp, "m0_selfplay_tb_leaves", KIND_ANY, false);
     uint64_t n = 0;
     for (const GameDev& g : sp->hg) n += g.tb_leaves;         // the mirror the last step copied
     return n;
 }
 
 uint64_t m0_selfplay_tb_adjudications(m0_selfplay* sp) {
-    if (!sp) return 0;
-    std::lock_guard<std::mutex> lk(sp->mu);
+    M0_ENGINE_CALL_OR(0, sp, "m0_selfplay_tb_adjudications", KIND_ANY, false);
     return sp->tb_adjudications;
 }
 

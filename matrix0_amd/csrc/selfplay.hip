@@ -25,7 +25,7 @@ static bool nn_cache_miss(m0_selfplay* sp, uint64_t key) {
     return true;
 }
 
-void seed_game_dev(GameDev& g, uint64_t base, int uid) {
+static void seed_game_dev(GameDev& g, uint64_t base, int uid) {
     g.seed_jitter = derive_seed(base, uid, PURPOSE_JITTER);
     g.seed_noise = derive_seed(base, uid, PURPOSE_NOISE);
     g.seed_dir = derive_seed(base, uid, PURPOSE_DIRICHLET);
@@ -36,7 +36,7 @@ int sync_games_d2h(m0_selfplay* sp) {
     if (hipMemcpyAsync(sp->hg.data(), sp->d.games, sizeof(GameDev) * sp->G, hipMemcpyDeviceToHost, sp->stream) != hipSuccess) return -1;
     return hipStreamSynchronize(sp->stream) == hipSuccess ? 0 : -1;
 }
-static int sync_games_h2d(m0_selfplay* sp) {
+int sync_games_h2d(m0_selfplay* sp) {
     return hipMemcpyAsync(sp->d.games, sp->hg.data(), sizeof(GameDev) * sp->G, hipMemcpyHostToDevice, sp->stream) == hipSuccess ? 0 : -1;
 }
 static void push_hist(m0_selfplay* sp, int slot, const RepWindow& w) {
@@ -48,7 +48,7 @@ static void push_hist(m0_selfplay* sp, int slot, const RepWindow& w) {
 }
 
 // configure a search on slot for the host position (MCTS.run prologue, mcts.py:342-396)
-void arm_search(m0_selfplay* sp, int slot, const Pos& pos, const RepWindow& win, int sims, bool dirichlet, bool fresh) {
+static void arm_search(m0_selfplay* sp, int slot, const Pos& pos, const RepWindow& win, int sims, bool dirichlet, bool fresh) {
     GameDev& g = sp->hg[slot];
     g.root_pos = pos;
     g.active = 1; g.sims_done = 0; g.sims_target = sims;
@@ -62,18 +62,36 @@ void arm_search(m0_selfplay* sp, int slot, const Pos& pos, const RepWindow& win,
     push_hist(sp, slot, win);
 }
 
+HostGame& occupy_slot(m0_selfplay* sp, int slot, Line&& line, int uid) {
+    HostGame& hgm = sp->games[slot];
+    hgm = HostGame();
+    static_cast<Line&>(hgm) = std::move(line);
+    hgm.in_use = true;
+    hgm.game_index = uid;
+    seed_game_dev(sp->hg[slot], sp->cfg.seed, uid);
+    sp->hg[slot].evals = 0;
+    return hgm;
+}
+
+void begin_search(m0_selfplay* sp, int slot, int sims, bool dirichlet, int root) {
+    const HostGame& hgm = sp->games[slot];
+    arm_search(sp, slot, hgm.pos, hgm.win, sims, dirichlet, root < 0);
+    sp->adv.push(slot, root);
+}
+
 static void finish_game(m0_selfplay* sp, int slot, bool resigned, int resigner, bool have_z, float z_in) {
     HostGame& hgm = sp->games[slot];
     const m0_selfplay_cfg& c = sp->cfg;
+    const bool match = sp->kind == EngineKind::Match;
     float z = z_in;
     if (!have_z) {
         // internal.py:587-599 computed per game (SURVEY B-8: the reference's stale-z reuse is not reproduced)
         if (is_game_over(hgm.pos, hgm.win, true)) z = game_result(hgm.pos);
-        else if (c.arena_mode) z = 0.f;                              // arena.py:121-123: unfinished = 1/2-1/2
+        else if (match) z = 0.f;                                     // arena.py:121-123: unfinished = 1/2-1/2
         else z = hgm.search_values.empty() ? 0.f : hgm.search_values.back();
     }
     sp->stats.games_finished++;
-    if ((c.record_games && hgm.nstates > 0) || c.arena_mode) {
+    if ((c.record_games && hgm.nstates > 0) || match) {
         GameRecordOwner* o = new GameRecordOwner();
         o->s.swap(hgm.states); o->pi.swap(hgm.pis); o->legal_mask.swap(hgm.masks);
         o->search_values = hgm.search_values;
@@ -117,47 +135,45 @@ static void finish_game(m0_selfplay* sp, int slot, bool resigned, int resigner, 
 }
 
 // top of the per-ply loop (internal.py:382-408): termination tests, then arm the search
-static void begin_move(m0_selfplay* sp, int slot, int child_slot, std::vector<int>& adv_ids, std::vector<int>& adv_slots) {
+static void begin_move(m0_selfplay* sp, int slot, int child_slot) {
     HostGame& hgm = sp->games[slot];
     const m0_selfplay_cfg& c = sp->cfg;
+    const bool match = sp->kind == EngineKind::Match;
     DrawCfg dc = draw_cfg_from(c);
     // self-play: internal.py:382-408; arena: `while not board.is_game_over(claim_draw=True) and moves < max_moves`
     // then the adjudication test (arena.py:68-72)
-    if (is_game_over(hgm.pos, hgm.win, c.arena_mode != 0) || hgm.nstates >= c.max_game_len ||
+    if (is_game_over(hgm.pos, hgm.win, match) || hgm.nstates >= c.max_game_len ||
         should_adjudicate_draw(hgm.pos, hgm.win, hgm.history, dc)) {
         finish_game(sp, slot, false, 0, false, 0.f);
         return;
     }
-    if (c.arena_mode) {
-        child_slot = -1;                                           // a fresh tree per move (see m0_arena_create)
+    int root = child_slot;
+    if (match) {
+        root = ROOT_FRESH;                                         // a fresh tree per move (see m0_arena_create)
         sp->hg[slot].net_id = ((hgm.pos.turn == WHITE) == hgm.a_is_white) ? 0 : 1;
     }
     // mcts.py:378-387 draws random.randint only when the cap is configured
     const bool cap_draws = c.playout_random_frac > 0.0 && c.num_simulations > 0;
     int sims = playout_cap(c.num_simulations, c.playout_random_frac, cap_draws ? hgm.rng.next() : 0.0);
     hgm.cur_sims = sims;
-    if (c.fresh_tree_per_move || c.tt_merge) child_slot = -1;   // tt_merge: the table lives for one search (see m0_engine.h)
-    // ... except in a match engine, where each side's table lives for the whole game: -3 = first search of the game (both
-    // tables cleared), -2 = any later one (root looked up in the side's table by advance_kernel)
-    if (c.arena_mode && c.tt_merge) child_slot = hgm.nstates == 0 ? -3 : -2;
+    if (c.fresh_tree_per_move || c.tt_merge) root = ROOT_FRESH;   // tt_merge: the table lives for one search (see m0_engine.h)
+    // ... except in a match engine, where each side's table lives for the whole game
+    if (match && c.tt_merge) root = hgm.nstates == 0 ? ROOT_FIRST_OF_GAME : ROOT_FROM_SIDE_TABLE;
     const bool dir = c.dirichlet_plies < 0 || hgm.nstates < c.dirichlet_plies;
-    arm_search(sp, slot, hgm.pos, hgm.win, sims, dir, child_slot < 0);
-    adv_ids.push_back(slot);
-    adv_slots.push_back(child_slot);
+    begin_search(sp, slot, sims, dir, root);
 }
 
-static void start_game(m0_selfplay* sp, int slot, std::vector<int>& adv_ids, std::vector<int>& adv_slots) {
-    HostGame& hgm = sp->games[slot];
-    hgm = HostGame();
-    hgm.in_use = true;
-    hgm.game_index = sp->cfg.first_game_index + sp->next_game++;
+static void start_game(m0_selfplay* sp, int slot) {
+    const bool match = sp->kind == EngineKind::Match;
+    Line start;
+    parse_fen(START_FEN, start.pos);
+    HostGame& hgm = occupy_slot(sp, slot, std::move(start), sp->cfg.first_game_index + sp->next_game++);
     sp->stats.games_started++;
-    parse_fen(START_FEN, hgm.pos);
     hgm.rng = HStream(derive_seed(sp->cfg.seed, hgm.game_index, PURPOSE_GAME));
     if (!sp->book.empty()) {               // get_opening_position (internal.py:65-69): random.choice(OPENING_BOOK)
         // a paired match: games 2k and 2k+1 share the draw of pair k's own stream (and leave their own streams alone), so each
         // opening is played with both colours whichever slot takes the games and whenever they start
-        const bool paired = sp->cfg.arena_mode && sp->cfg.arena_paired_openings;
+        const bool paired = match && sp->cfg.arena_paired_openings;
         const double u = paired ? HStream(derive_seed(sp->cfg.seed, hgm.game_index / 2, PURPOSE_PAIR_OPENING)).next() : hgm.rng.next();
         size_t k = (size_t)(u * (double)sp->book.size());
         if (k >= sp->book.size()) k = sp->book.size() - 1;
@@ -166,10 +182,8 @@ static void start_game(m0_selfplay* sp, int slot, std::vector<int>& adv_ids, std
     }
     hgm.t0 = now_ms();
     hgm.a_is_white = (hgm.game_index % 2) == 0;               // arena.py:66
-    seed_game_dev(sp->hg[slot], sp->cfg.seed, hgm.game_index);
-    sp->hg[slot].evals = 0;
     // a match engine's caches hold what each NETWORK said; the next game of the slot swaps the colours (advance_kernel clears)
-    if (sp->cfg.arena_mode && sp->tc.eval_cache) sp->hg[slot].ec_clear = 1;
+    if (match && sp->tc.eval_cache) sp->hg[slot].ec_clear = 1;
     // opening diversity: uniform random legal plies (internal.py:366-379; random.choice -> injected stream)
     for (int i = 0; i < sp->cfg.opening_random_plies; ++i) {
         if (is_game_over(hgm.pos, hgm.win, false)) break;
@@ -180,11 +194,11 @@ static void start_game(m0_selfplay* sp, int slot, std::vector<int>& adv_ids, std
         if (k >= n) k = n - 1;
         hgm.play(mv[k]);
     }
-    begin_move(sp, slot, -1, adv_ids, adv_slots);
+    begin_move(sp, slot, ROOT_FRESH);
 }
 
 // MCTS.run epilogue + the rest of the per-ply loop body (mcts.py:431-507, internal.py:408-539)
-static void finish_search(m0_selfplay* sp, int slot, std::vector<int>& adv_ids, std::vector<int>& adv_slots) {
+static void finish_search(m0_selfplay* sp, int slot) {
     HostGame& hgm = sp->games[slot];
     const m0_selfplay_cfg& c = sp->cfg;
     const RootResult& R = sp->hres[slot];
@@ -239,7 +253,7 @@ static void finish_search(m0_selfplay* sp, int slot, std::vector<int>& adv_ids, 
     if (c.low_visit_threshold > 0 && maxv < c.low_visit_threshold && temp < 0.8) temp = 0.8;
     std::vector<int32_t> visits(R.child_n, R.child_n + k);
     int pick;
-    if (c.arena_mode) {       // arena.py:73-106 (the uniform is drawn only on the sampling branch, as np.random.choice is)
+    if (sp->kind == EngineKind::Match) {       // arena.py:73-106 (the uniform is drawn only on the sampling branch, as np.random.choice is)
         const bool sampling = c.arena_temp > 1e-3 && hgm.nstates < c.arena_temp_plies;
         pick = arena_choose_move(visits.data(), k, c.arena_temp, hgm.nstates, c.arena_temp_plies, sampling ? hgm.rng.next() : 0.0);
     } else {
@@ -252,7 +266,7 @@ static void finish_search(m0_selfplay* sp, int slot, std::vector<int>& adv_ids, 
     hgm.nstates++;
     sp->stats.plies++;
     // resign (internal.py:507-536)
-    if (!c.arena_mode && resign_update(hgm.resign, root_q, hgm.nstates, c)) {
+    if (sp->kind != EngineKind::Match && resign_update(hgm.resign, root_q, hgm.nstates, c)) {
         const bool white = hgm.pos.turn == WHITE;
         finish_game(sp, slot, true, white ? 1 : 2, true, white ? -1.f : 1.f);
         return;
@@ -268,32 +282,36 @@ static void finish_search(m0_selfplay* sp, int slot, std::vector<int>& adv_ids, 
             return;
         }
     }
-    begin_move(sp, slot, pick, adv_ids, adv_slots);
+    begin_move(sp, slot, pick);
 }
 
 int run_select(m0_selfplay* sp, int* rows_out) {
-    if (hipMemsetAsync(sp->d.row_counter, 0, 8, sp->stream) != hipSuccess) return -1;
-    if (launch_select(sp->d, sp->tc, sp->stream) != hipSuccess) return -1;
-    if (hipMemcpyAsync(sp->rows2, sp->d.row_counter, 8, hipMemcpyDeviceToHost, sp->stream) != hipSuccess) return -1;
-    if (hipStreamSynchronize(sp->stream) != hipSuccess) return -1;
+    if (hipMemsetAsync(sp->d.row_counter, 0, 8, sp->stream) != hipSuccess || launch_select(sp->d, sp->tc, sp->stream) != hipSuccess ||
+        hipMemcpyAsync(sp->rows2, sp->d.row_counter, 8, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
+        hipStreamSynchronize(sp->stream) != hipSuccess) {
+        m0_set_error(std::string("select failed: ") + hipGetErrorString(hipGetLastError()));
+        return M0_ERR_HIP;
+    }
     *rows_out = sp->rows2[0];              // network 0's rows; network 1's (arena) start at d.net_row_base
-    return 0;
+    return M0_OK;
 }
 
-int apply_advances(m0_selfplay* sp, std::vector<int>& ids, std::vector<int>& slots) {
+static int launch_advances(m0_selfplay* sp) {
+    const std::vector<int>& ids = sp->adv.slots;
+    const std::vector<int>& roots = sp->adv.roots;
     if (sync_games_h2d(sp) != 0) return -1;
     if (!ids.empty()) {
         (void)hipMemcpyAsync(sp->ids_dev, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, sp->stream);
-        (void)hipMemcpyAsync(sp->slots_dev, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, sp->stream);
-        if (launch_advance(sp->d, sp->ids_dev, sp->slots_dev, (int)ids.size(), sp->stream) != hipSuccess) return -1;
-        if (hipStreamSynchronize(sp->stream) != hipSuccess) return -1;   // ids/slots vectors die with the caller
+        (void)hipMemcpyAsync(sp->roots_dev, roots.data(), roots.size() * 4, hipMemcpyHostToDevice, sp->stream);
+        if (launch_advance(sp->d, sp->ids_dev, sp->roots_dev, (int)ids.size(), sp->stream) != hipSuccess) return -1;
+        if (hipStreamSynchronize(sp->stream) != hipSuccess) return -1;   // the list is reused by the next step
         if (sp->d.tt_sides == 2) {
             // per-side tables: only the device knows whether a root was found in its side's table.  A found root is evaluated
             // once more unless nn_cache holds the position (mcts.py:359-371; the cache belongs to the side's MCTS object).
             if (sync_games_d2h(sp) != 0) return -1;
             bool any = false;
             for (size_t k = 0; k < ids.size(); ++k) {
-                if (slots[k] > -2) continue;
+                if (roots[k] > ROOT_FROM_SIDE_TABLE) continue;
                 GameDev& g = sp->hg[ids[k]];
                 const uint64_t salt = (g.net_id & 1) ? 0x9E3779B97F4A7C15ull : 0ull;
                 const uint64_t gsalt = (uint64_t)(uint32_t)sp->games[ids[k]].game_index * 0xD6E8FEB86659FD93ull;
@@ -306,23 +324,63 @@ int apply_advances(m0_selfplay* sp, std::vector<int>& ids, std::vector<int>& slo
     return 0;
 }
 
+int apply_advances(m0_selfplay* sp) {
+    const int rc = launch_advances(sp);
+    sp->adv.clear();
+    if (rc != 0) { m0_set_error("advance failed"); return M0_ERR_HIP; }
+    return M0_OK;
+}
+
 static void count_active_games(m0_selfplay* sp) {
     int act = 0;
     for (int s = 0; s < sp->G; ++s) act += sp->games[s].in_use ? 1 : 0;
     sp->stats.active_games = act;
 }
 
-int start_first_games(m0_selfplay* sp) {
-    if (sp->stats.games_started != 0) return M0_OK;
-    std::vector<int> ids, slots;
-    if (sync_games_d2h(sp) != 0) { m0_set_error("device sync failed"); return M0_ERR_HIP; }
+// a game in every free slot, as long as games remain to be played; their roots are queued in sp->adv
+static void start_games(m0_selfplay* sp) {
     for (int s = 0; s < sp->G; ++s) {
+        if (sp->games[s].in_use) continue;
         if (sp->cfg.total_games > 0 && sp->next_game >= sp->cfg.total_games) break;
-        start_game(sp, s, ids, slots);
+        start_game(sp, s);
     }
-    if (apply_advances(sp, ids, slots) != 0) { m0_set_error("advance failed"); return M0_ERR_HIP; }
+}
+
+static int start_first_games(m0_selfplay* sp) {         // lazily, at the first step
+    if (sp->stats.games_started != 0) return M0_OK;
+    if (sync_games_d2h(sp) != 0) { m0_set_error("device sync failed"); return M0_ERR_HIP; }
+    start_games(sp);
+    const int rc = apply_advances(sp);
+    if (rc != M0_OK) return rc;
     count_active_games(sp);
     return M0_OK;
+}
+
+int refill(m0_selfplay* sp) {
+    switch (sp->kind) {
+    case EngineKind::Analysis: return analysis_refill(sp);
+    default: return start_first_games(sp);
+    }
+}
+
+// The searches that the last expand finished become moves; games end, free slots start the next ones.
+static int harvest_games(m0_selfplay* sp) {
+    (void)hipMemcpy(sp->hres.data(), sp->d.results, sizeof(RootResult) * sp->G, hipMemcpyDeviceToHost);
+    for (int s = 0; s < sp->G; ++s) {
+        if (!(sp->hg[s].active && sp->hg[s].finished)) continue;
+        if (sp->hg[s].overflow) sp->stats.arena_overflows++;
+        finish_search(sp, s);
+    }
+    start_games(sp);
+    return apply_advances(sp);
+}
+
+// after expand, when a search has finished
+static int harvest(m0_selfplay* sp) {
+    switch (sp->kind) {
+    case EngineKind::Analysis: return analysis_harvest(sp);
+    default: return harvest_games(sp);
+    }
 }
 
 // Several engines on one GPU (engine.SelfplayPool).  By default their forwards simply overlap on the chip.  With
@@ -362,12 +420,12 @@ void forward_gate_leave(m0_selfplay* sp) {
     if (sp->counted) g_engines_with_net[sp->device].fetch_sub(1);
 }
 
-// second half of a step: expand / backup on the device, then the host part (finished searches -> moves, game ends, restarts)
-int step_back(m0_selfplay* sp, int rows, double t0, std::string& err) {
+// second half of a step: expand / backup on the device, then the host part (counters, the harvest of the finished searches)
+int finish_step(m0_selfplay* sp, int rows, double t0) {
     (void)hipEventRecord(sp->ev2, sp->stream);
-    if (launch_expand(sp->d, sp->tc, sp->stream) != hipSuccess) { err = "expand launch failed"; return M0_ERR_HIP; }
+    if (launch_expand(sp->d, sp->tc, sp->stream) != hipSuccess) { m0_set_error("expand launch failed"); return M0_ERR_HIP; }
     (void)hipEventRecord(sp->ev3, sp->stream);
-    if (sync_games_d2h(sp) != 0) { err = std::string("step failed: ") + hipGetErrorString(hipGetLastError()); return M0_ERR_HIP; }
+    if (sync_games_d2h(sp) != 0) { m0_set_error(std::string("step failed: ") + hipGetErrorString(hipGetLastError())); return M0_ERR_HIP; }
     if (sp->net) sp->net->harvest_profile();
     if (sp->net_b) sp->net_b->harvest_profile();
     float ms_sel = 0, ms_net = 0, ms_exp = 0;
@@ -377,8 +435,7 @@ int step_back(m0_selfplay* sp, int rows, double t0, std::string& err) {
     sp->stats.ms_net += ms_net; sp->stats.ms_tree += ms_sel + ms_exp;
     sp->stats.steps++; sp->stats.evals += (uint64_t)rows;
     const double t1 = now_ms();
-    // host: finished searches -> moves, game ends, restarts
-    bool any = false;
+    bool any = false;                      // a search has finished
     if (sp->tc.eval_cache) {
         uint64_t h = 0;
         for (int s = 0; s < sp->G; ++s) h += sp->hg[s].cache_hits;
@@ -390,24 +447,7 @@ int step_back(m0_selfplay* sp, int rows, double t0, std::string& err) {
         if (delta > 0) { sp->stats.sims += (uint64_t)delta; sp->prev_done[s] = sp->hg[s].sims_done; }
         if (sp->hg[s].finished) any = true;
     }
-    std::vector<int> ids, slots;
-    if (sp->an) {                          // an analysis engine: no games, the finished searches become results
-        if (any) { const int rc = analysis_harvest(sp, err); if (rc != M0_OK) return rc; }
-    } else if (any) {
-        (void)hipMemcpy(sp->hres.data(), sp->d.results, sizeof(RootResult) * sp->G, hipMemcpyDeviceToHost);
-        for (int s = 0; s < sp->G; ++s) {
-            if (!(sp->hg[s].active && sp->hg[s].finished)) continue;
-            if (sp->hg[s].overflow) sp->stats.arena_overflows++;
-            finish_search(sp, s, ids, slots);
-        }
-        // refill free slots
-        for (int s = 0; s < sp->G; ++s) {
-            if (sp->games[s].in_use) continue;
-            if (sp->cfg.total_games > 0 && sp->next_game >= sp->cfg.total_games) continue;
-            start_game(sp, s, ids, slots);
-        }
-        if (apply_advances(sp, ids, slots) != 0) { err = "advance failed"; return M0_ERR_HIP; }
-    }
+    if (any) { const int rc = harvest(sp); if (rc != M0_OK) return rc; }
     count_active_games(sp);
     const double t2 = now_ms();
     sp->stats.ms_host += t2 - t1;
@@ -430,16 +470,17 @@ static RowSplit split_rows(int rows, bool have_tail, bool half_split) {
     return {main_rows, rows - main_rows};
 }
 
-int one_step(m0_selfplay* sp, std::string& err) {
+int one_step(m0_selfplay* sp) {
+    std::string err;                         // Net::forward's
     const double t0 = now_ms();
     (void)hipEventRecord(sp->ev0, sp->stream);
     int rows = 0;
-    if (run_select(sp, &rows) != 0) { err = std::string("select failed: ") + hipGetErrorString(hipGetLastError()); return M0_ERR_HIP; }
+    if (run_select(sp, &rows) != M0_OK) return M0_ERR_HIP;
     (void)hipEventRecord(sp->ev1, sp->stream);
-    if (rows > sp->rows_max || sp->rows2[1] > sp->rows_max) { err = "row counter overflow"; return M0_ERR_STATE; }
+    if (rows > sp->rows_max || sp->rows2[1] > sp->rows_max) { m0_set_error("row counter overflow"); return M0_ERR_STATE; }
     ForwardGate gate(sp->device, sp->stream, rows > 0 || sp->rows2[1] > 0);
     if (rows > 0) {
-        if (!sp->net) { err = "m0_selfplay_step needs a network (use the split-step API without one)"; return M0_ERR_STATE; }
+        if (!sp->net) { m0_set_error("m0_selfplay_step needs a network (use the split-step API without one)"); return M0_ERR_STATE; }
         const auto [main_rows, tail_rows] = split_rows(rows, sp->net_tail != nullptr, sp->half_split);
         float* ssl = sp->cfg.ssl_in_forward ? sp->ssl_dev : nullptr;
         m0_net_lock(sp->nethandle);          // an infer_np on the same backend from another thread waits here
@@ -456,21 +497,21 @@ int one_step(m0_selfplay* sp, std::string& err) {
             (void)hipStreamWaitEvent(sp->stream, sp->ev_tail, 0);
         }
         m0_net_unlock(sp->nethandle);
-        if (rc != M0_OK) return rc;
+        if (rc != M0_OK) { m0_set_error(err); return rc; }
         sp->stats.rows_tail += (uint64_t)tail_rows;
     }
     if (sp->rows2[1] > 0) {                 // arena: the other network's leaves, in their own region of the batch
-        if (!sp->net_b) { err = "rows for a second network without one"; return M0_ERR_STATE; }
+        if (!sp->net_b) { m0_set_error("rows for a second network without one"); return M0_ERR_STATE; }
         const size_t b = (size_t)sp->d.net_row_base;
         m0_net_lock(sp->nethandle_b);
         int rc = sp->net_b->forward(nullptr, sp->d.x0 + b * 64 * 32, sp->rows2[1], sp->logits_dev + b * 4672,
                                     sp->values_dev + b, nullptr, sp->stream, err);
         m0_net_unlock(sp->nethandle_b);
-        if (rc != M0_OK) return rc;
+        if (rc != M0_OK) { m0_set_error(err); return rc; }
         rows += sp->rows2[1];
     }
     gate.release();
-    return step_back(sp, rows, t0, err);
+    return finish_step(sp, rows, t0);
 }
 
 }  // namespace m0

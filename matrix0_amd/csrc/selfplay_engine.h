@@ -49,6 +49,23 @@ struct HostGame : Line {                  // pos, win, history (all moves incl. 
     int book_index = -1;                  // the opening-book position the game started from, -1 = the initial position
 };
 
+// What one m0_selfplay object is: set once by engine_create and read wherever the three behave differently.  (cfg.arena_mode is
+// the same fact in the ABI struct; it is normalised at creation and not read afterwards.)
+enum class EngineKind { SelfPlay, Match, Analysis };
+// sets of kinds, for the call guard below
+constexpr unsigned KIND_SELFPLAY = 1u << (int)EngineKind::SelfPlay, KIND_MATCH = 1u << (int)EngineKind::Match,
+                   KIND_ANALYSIS = 1u << (int)EngineKind::Analysis, KIND_GAMES = KIND_SELFPLAY | KIND_MATCH,
+                   KIND_ANY = KIND_GAMES | KIND_ANALYSIS;
+
+// The new roots that the next advance_kernel launch sets: per entry a tree slot and either the child of its old root to keep
+// or a RootMode (tree.h).  Filled by the host part of a step, launched and emptied by apply_advances.
+struct AdvanceList {
+    std::vector<int> slots, roots;
+    void push(int slot, int root) { slots.push_back(slot); roots.push_back(root); }
+    void clear() { slots.clear(); roots.clear(); }
+    bool empty() const { return slots.empty(); }
+};
+
 // What an analysis engine (capi_analysis.hip) keeps beside the tree slots.  A slot that searches holds its position and
 // repetition window in m0_selfplay::games[slot] (in_use) and its search in hg[slot], as a game does.
 struct AnalysisJob { Line line; int sims; int nlegal; int64_t id; };
@@ -75,6 +92,7 @@ struct Analysis {
 }  // namespace m0
 
 struct m0_selfplay {
+    m0::EngineKind kind = m0::EngineKind::SelfPlay;
     m0_selfplay_cfg cfg;
     TreeCfg tc;
     m0_net* nethandle = nullptr;
@@ -101,8 +119,9 @@ struct m0_selfplay {
     m0::Pos* ssl_pos_dev = nullptr;        // staging of one finished game's positions / SSL target maps (ssl_targets)
     float* ssl_out_dev = nullptr;
     int ssl_cap = 0;
-    int* ids_dev = nullptr;
-    int* slots_dev = nullptr;
+    m0::AdvanceList adv;
+    int* ids_dev = nullptr;               // the device copy of adv (and of an analysis harvest's slot list)
+    int* roots_dev = nullptr;
     std::deque<m0_game_record> done_meta;
     m0_selfplay_stats stats;
     int next_game = 0;
@@ -119,7 +138,7 @@ struct m0_selfplay {
     std::unordered_map<uint64_t, std::list<uint64_t>::iterator> nn_map;
     bool ext_pending = false;             // ext_select done, ext_expand outstanding
     bool counted = false;                 // registered with the forward gate
-    m0::Analysis* an = nullptr;           // set: an analysis engine (m0_analysis_create*); it plays no games
+    m0::Analysis* an = nullptr;           // the state of an analysis engine (kind == Analysis), null otherwise
     const m0_tb* tb = nullptr;            // endgame tablebase probed on the host: after every played move (m0_selfplay_set_tablebase,
                                           // m0_selfplay_set_search_tablebase), for a submitted root (analysis engines)
     int tb_max_pieces = 0;                // ... for positions with at most this many men (d.tb_set: the probe inside the search)
@@ -140,28 +159,52 @@ T* dalloc(m0_selfplay* sp, size_t count) {
     return (T*)p;
 }
 
+// Head of every engine entry point, in this order: a null handle -> `null_result`; the engine's lock; an engine whose kind is
+// not in `kinds` -> M0_ERR_STATE with a message that names the call and the kind; the engine's device for the calls that touch
+// it (`on_device`; a host-only call must not move the calling thread's current device).
+//
+//   call                                                            accepted by
+//   m0_selfplay_step, _poll, _set_openings                          self-play, match
+//   m0_selfplay_ext_select, _ext_expand, m0_selfplay_set_tablebase  self-play
+//   m0_arena_ext_select, _ext_expand                                match
+//   m0_search_*                                                     self-play, match (a match engine is accepted as it always
+//                                                                   was, although nothing drives one this way)
+//   m0_analysis_*                                                   analysis
+//   m0_selfplay_stats_get, _running, _last_batch_nhwc,
+//   _set_search_tablebase, _tb_leaves, _tb_adjudications            every kind
+bool kind_accepted(const m0_selfplay* sp, const char* what, unsigned kinds);   // false: the error string is set
+#define M0_ENGINE_CALL_OR(null_result, sp, what, kinds, on_device)                    \
+    if (!(sp)) { m0_set_error(what ": sp is null"); return null_result; }             \
+    std::lock_guard<std::mutex> lk((sp)->mu);                                         \
+    if (!m0::kind_accepted(sp, what, kinds)) return M0_ERR_STATE;                     \
+    if (on_device) (void)hipSetDevice((sp)->device)
+#define M0_ENGINE_CALL(sp, what, kinds, on_device) M0_ENGINE_CALL_OR(M0_ERR_INVALID, sp, what, kinds, on_device)
+
+// Internal functions set the error string (m0_set_error) where the error happens and return the M0_ERR_* code.
 // selfplay.hip
 void forward_gate_join(m0_selfplay* sp);        // an engine that owns a network takes part in M0_FORWARD_GATE
 void forward_gate_leave(m0_selfplay* sp);
-void seed_game_dev(GameDev& g, uint64_t base, int uid);
-int sync_games_d2h(m0_selfplay* sp);
-void arm_search(m0_selfplay* sp, int slot, const Pos& pos, const RepWindow& win, int sims, bool dirichlet, bool fresh);
-int apply_advances(m0_selfplay* sp, std::vector<int>& ids, std::vector<int>& slots);
-int start_first_games(m0_selfplay* sp);         // lazily, at the first step; sets the error string itself
+int sync_games_d2h(m0_selfplay* sp);            // the slots' control blocks: device -> sp->hg, waited for
+int sync_games_h2d(m0_selfplay* sp);            // ... sp->hg -> device, on the engine's stream
+// Take tree slot `slot` for `line`: a new HostGame, random streams keyed by `uid`, no evaluations counted yet.
+HostGame& occupy_slot(m0_selfplay* sp, int slot, Line&& line, int uid);
+// Arm a search of the slot's position (MCTS.run prologue) and queue its root (a child of the old root or a RootMode) in sp->adv.
+void begin_search(m0_selfplay* sp, int slot, int sims, bool dirichlet, int root);
+int apply_advances(m0_selfplay* sp);            // control blocks -> device, advance_kernel over sp->adv, which is empty afterwards
 int run_select(m0_selfplay* sp, int* rows_out);
-int one_step(m0_selfplay* sp, std::string& err);
-int step_back(m0_selfplay* sp, int rows, double t0, std::string& err);
+int refill(m0_selfplay* sp);                    // before select: the first games (lazily, at the first step) / queued analyses
+int one_step(m0_selfplay* sp);                  // select -> network -> finish_step
+// second half of a step: expand / backup on the device, the counters, then the harvest of the finished searches
+int finish_step(m0_selfplay* sp, int rows, double t0);
 
 // capi_selfplay.hip
-m0_selfplay* engine_create(m0_net* nh, m0_net* nh_b, const m0_selfplay_cfg* cfg, bool arena);
+m0_selfplay* engine_create(m0_net* nh, m0_net* nh_b, const m0_selfplay_cfg* cfg, EngineKind kind);
 int ext_select_impl(m0_selfplay* sp, int* rows_a, int* rows_b, float* planes_a, float* planes_b, int max_rows);
 int ext_expand_impl(m0_selfplay* sp, const float* logits_a, const float* values_a, int rows_a, const float* logits_b,
                     const float* values_b, int rows_b);
-// true (error string set) when sp is an analysis engine: the game and split-search entry points refuse it
-bool refuse_analysis(m0_selfplay* sp, const char* what);
 
 // capi_analysis.hip: the two ends of an analysis engine's step, around the select -> network -> expand pass
-int analysis_refill(m0_selfplay* sp, std::string& err);      // free slots <- queued searches
-int analysis_harvest(m0_selfplay* sp, std::string& err);     // finished searches -> results, slots freed
+int analysis_refill(m0_selfplay* sp);       // free slots <- queued searches
+int analysis_harvest(m0_selfplay* sp);      // finished searches -> results, slots freed
 
 }  // namespace m0

@@ -173,8 +173,13 @@ struct TreeDev {
 
 hipError_t launch_select(const TreeDev& d, const TreeCfg& c, hipStream_t st);
 hipError_t launch_expand(const TreeDev& d, const TreeCfg& c, hipStream_t st);
-// child_slots: >= 0 keep that child's subtree; -1 fresh tree (and an empty table); tt_sides == 2 only: -2 next search of a
-// game (root looked up in the side's table), -3 first search of a game (both tables cleared first)
+// What advance_kernel makes the new root of a game: a value >= 0 keeps that child of the old root with its subtree, a negative
+// one is a RootMode.  The two table modes exist with tt_sides == 2 only.
+enum RootMode : int {
+    ROOT_FRESH = -1,            // a fresh tree (and an empty position table)
+    ROOT_FROM_SIDE_TABLE = -2,  // a later search of a game: the root is looked up in the side's table
+    ROOT_FIRST_OF_GAME = -3,    // the first search of a game: both tables are cleared first, then a new root
+};
 hipError_t launch_advance(const TreeDev& d, const int* game_ids_dev, const int* child_slots_dev, int count, hipStream_t st);
 
 // test hooks: position-wise encode / legal move / index kernels (encoding.py on device)

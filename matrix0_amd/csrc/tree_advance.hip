@@ -1,24 +1,25 @@
 // advance_kernel: re-root a game's tree on the played move, one wavefront per game.
-//   child_slot >= 0  keep that child's subtree, compacted breadth-first into the other arena half
-//   child_slot == -1 fresh tree (and an empty position table)
-//   child_slot <= -2 match engine with per-side tables (tt_sides == 2): the root is looked up in the side's table
+//   child_slot >= 0       keep that child's subtree, compacted breadth-first into the other arena half
+//   ROOT_FRESH            fresh tree (and an empty position table)
+//   ROOT_FROM_SIDE_TABLE  and below (RootMode, tree.h): match engine with per-side tables (tt_sides == 2), the root is looked
+//                         up in the side's table
 // and, before any of these, the slot's evaluation caches are emptied when the host flagged a new game (GameDev::ec_clear).
 #include "tree_device.h"
 #include "eval_cache.h"
 
 // Per-side tables: side = the network that searches now.  Nothing is compacted or cleared between the searches of a game; the
 // root is whatever node the side's table holds for the position (MCTS.run: root = self._tt_get(key), mcts.py:343), else a new
-// node.  slot -3 = first search of a game: both tables are cleared first.
+// node.  ROOT_FIRST_OF_GAME: both tables are cleared first.
 __device__ __forceinline__ void reroot_from_table(const TreeDev& d, GameDev* gd, int g, int slot, int lane) {
     const int s = gd->net_id & 1;
     const int prev_side = gd->arena & 1, prev_next = gd->next;
-    if (slot == -3) tt_clear(d.tt_keys + (size_t)g * 2 * d.tt_cap, 2 * d.tt_cap, lane);
+    if (slot == ROOT_FIRST_OF_GAME) tt_clear(d.tt_keys + (size_t)g * 2 * d.tt_cap, 2 * d.tt_cap, lane);
     __syncthreads();
-    int nxt = slot == -3 ? 0 : (s == prev_side ? prev_next : gd->side_next[s]);
+    int nxt = slot == ROOT_FIRST_OF_GAME ? 0 : (s == prev_side ? prev_next : gd->side_next[s]);
     const Arena A = arena_of(d.t, g, s);
     uint64_t* TK = d.tt_keys + ((size_t)g * 2 + s) * d.tt_cap;
     const int* TN = d.tt_nodes + ((size_t)g * 2 + s) * d.tt_cap;
-    int node = slot == -3 ? -1 : tt_lookup(TK, TN, d.tt_cap, tt_key_of(gd->root_pos), lane);
+    int node = slot == ROOT_FIRST_OF_GAME ? -1 : tt_lookup(TK, TN, d.tt_cap, tt_key_of(gd->root_pos), lane);
     // a half that cannot take another search's worth of nodes starts over: its table is dropped and the search begins from a
     // fresh root (what the reference's _cleanup_memory does to an over-full table); engine.arena_nodes sizes it for a game
     if (nxt + (d.search_nodes > 4 * M0_MAX_CHILDREN ? d.search_nodes : 4 * M0_MAX_CHILDREN) >= d.t.cap) {
@@ -28,7 +29,7 @@ __device__ __forceinline__ void reroot_from_table(const TreeDev& d, GameDev* gd,
     }
     const bool found = node >= 0;
     if (lane == 0) {
-        if (slot != -3) gd->side_next[prev_side] = prev_next;
+        if (slot != ROOT_FIRST_OF_GAME) gd->side_next[prev_side] = prev_next;
         else { gd->side_next[0] = 0; gd->side_next[1] = 0; }
         if (!found) {
             node = nxt;
@@ -92,7 +93,7 @@ __global__ __launch_bounds__(64) void advance_kernel(TreeDev d, const int* game_
         if (d.ec.sets > 0) ec_clear_game(d.ec, gd, g, lane);
         if (lane == 0) gd->ec_clear = 0;
     }
-    if (slot <= -2) reroot_from_table(d, gd, g, slot, lane);
+    if (slot <= ROOT_FROM_SIDE_TABLE) reroot_from_table(d, gd, g, slot, lane);
     else if (slot < 0) reroot_fresh(d, gd, g, lane);
     else reroot_keep_subtree(d, gd, g, slot, lane);
 }

@@ -130,6 +130,12 @@ def _bind():
     L.m0_analysis_ext_expand.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, c_int]
     L.m0_analysis_poll.argtypes = [C.c_void_p, C.POINTER(AnalysisResult)]
     L.m0_analysis_pending.argtypes = [C.c_void_p]
+    L.m0_selfplay_set_tablebase.argtypes = [C.c_void_p, C.c_void_p, c_int]
+    L.m0_selfplay_tb_adjudications.restype = c_u64
+    L.m0_selfplay_tb_adjudications.argtypes = [C.c_void_p]
+    L.m0_selfplay_set_search_tablebase.argtypes = [C.c_void_p, C.c_void_p, c_int]
+    L.m0_selfplay_tb_leaves.restype = c_u64
+    L.m0_selfplay_tb_leaves.argtypes = [C.c_void_p]
     L.m0_analysis_result_size.restype = C.c_size_t
     L.m0_analysis_result_size.argtypes = []
     # the mirror above against the library's own struct
@@ -234,6 +240,10 @@ def selfplay_cfg_from_dict(cfg: dict, *, concurrent_games: int, total_games: int
     return c
 
 
+def _ptr(a: np.ndarray):
+    return a.ctypes.data_as(C.c_void_p)
+
+
 def move_to_uci(m: int) -> str:
     f, t, p = m & 63, (m >> 6) & 63, (m >> 12) & 7
     s = "abcdefgh"[f & 7] + str((f >> 3) + 1) + "abcdefgh"[t & 7] + str((t >> 3) + 1)
@@ -245,12 +255,35 @@ class SelfplayEngine:
     in place); pass None for the split-step search API with an external evaluator."""
 
     def __init__(self, backend, cfg: SelfplayCfg):
+        self._open(backend, cfg, "m0_selfplay_create", backend.handle if backend is not None else None, C.byref(cfg))
+
+    def _open(self, backend, cfg: SelfplayCfg, create: str, *args) -> None:
+        """What every engine class constructs: the handle from its own create call."""
         self._L = _bind()
         self.backend = backend
         self.cfg = cfg
-        self._h = self._L.m0_selfplay_create(backend.handle if backend is not None else None, C.byref(cfg))
+        self._h = getattr(self._L, create)(*args)
         if not self._h:
-            raise RuntimeError(f"m0_selfplay_create failed: {_lib.last_error()}")
+            raise RuntimeError(f"{create} failed: {_lib.last_error()}")
+
+    def _select(self, fn, what: str, regions: int = 1) -> List[np.ndarray]:
+        """A select call of the library, `fn(handle, rows..., planes..., max_rows)` with one rows counter and one planes buffer of
+        concurrent_games * (inference_batch_size + 1) rows per region (network): the leaf planes f32 [rows,19,8,8] per region."""
+        cap = self.cfg.concurrent_games * (self.cfg.inference_batch_size + 1)
+        rows = [c_int(0) for _ in range(regions)]
+        planes = [np.zeros((cap, 19, 8, 8), dtype=np.float32) for _ in range(regions)]
+        _lib.check(fn(self._h, *[C.byref(r) for r in rows], *[_ptr(p) for p in planes], cap), what)
+        return [p[: r.value] for p, r in zip(planes, rows)]
+
+    def _expand(self, fn, what: str, *answers) -> None:
+        """An expand call of the library, `fn(handle, (logits, values, rows)...)`: one evaluator's answer (logits, values) per
+        region, handed over as contiguous float32."""
+        args = []
+        for logits, values in answers:
+            lg = np.ascontiguousarray(logits, dtype=np.float32)
+            vv = np.ascontiguousarray(values, dtype=np.float32)
+            args += [_ptr(lg), _ptr(vv), int(lg.shape[0])]         # the pointers keep their arrays alive
+        _lib.check(fn(self._h, *args), what)
 
     def step(self, steps: int = 1) -> None:
         _lib.check(self._L.m0_selfplay_step(self._h, int(steps)), "m0_selfplay_step")
@@ -309,16 +342,12 @@ class SelfplayEngine:
         """Attach a matrix0_amd.tablebase.Tablebase (None detaches); call before the first step.  After every played move a
         position with at most `max_pieces` men is probed and a hit ends the game with the table's verdict
         (selfplay/internal.py:559-581).  The engine keeps a reference: the tables live as long as it does."""
-        from . import tablebase as _tb
-        _tb._bind()
         _lib.check(self._L.m0_selfplay_set_tablebase(self._h, tb.handle if tb is not None else None, int(max_pieces)),
                    "m0_selfplay_set_tablebase")
         self._tablebase = tb
 
     def tb_adjudications(self) -> int:
         """Games ended by a tablebase hit."""
-        from . import tablebase as _tb
-        _tb._bind()
         return int(self._L.m0_selfplay_tb_adjudications(self._h))
 
     def set_search_tablebase(self, tb, max_pieces: int = 4) -> None:
@@ -327,31 +356,20 @@ class SelfplayEngine:
         `max_pieces` men that is in the tables is a terminal leaf with the table's value and costs no evaluation.  A root inside
         the tables: self-play and match engines end the game there with the table's verdict (as `set_tablebase`), an analysis
         engine answers it from the tables (status "tablebase"), the split-step search searches it as given."""
-        from . import tablebase as _tb
-        _tb._bind()
         _lib.check(self._L.m0_selfplay_set_search_tablebase(self._h, tb.handle if tb is not None else None, int(max_pieces)),
                    "m0_selfplay_set_search_tablebase")
         self._tablebase = tb
 
     def tb_leaves(self) -> int:
         """Leaves the search took from the tables instead of the network (as of the last step)."""
-        from . import tablebase as _tb
-        _tb._bind()
         return int(self._L.m0_selfplay_tb_leaves(self._h))
 
     def ext_select(self) -> np.ndarray:
         """First half of a self-play step for an external evaluator: the leaf planes f32 [rows,19,8,8]."""
-        rows = c_int(0)
-        cap = self.cfg.concurrent_games * (self.cfg.inference_batch_size + 1)
-        planes = np.zeros((cap, 19, 8, 8), dtype=np.float32)
-        _lib.check(self._L.m0_selfplay_ext_select(self._h, C.byref(rows), planes.ctypes.data_as(C.c_void_p), cap), "m0_selfplay_ext_select")
-        return planes[: rows.value]
+        return self._select(self._L.m0_selfplay_ext_select, "m0_selfplay_ext_select")[0]
 
     def ext_expand(self, logits: np.ndarray, values: np.ndarray) -> None:
-        lg = np.ascontiguousarray(logits, dtype=np.float32)
-        vv = np.ascontiguousarray(values, dtype=np.float32)
-        _lib.check(self._L.m0_selfplay_ext_expand(self._h, lg.ctypes.data_as(C.c_void_p), vv.ctypes.data_as(C.c_void_p),
-                                                  int(lg.shape[0])), "m0_selfplay_ext_expand")
+        self._expand(self._L.m0_selfplay_ext_expand, "m0_selfplay_ext_expand", (logits, values))
 
     def last_batch_nhwc(self) -> np.ndarray:
         """The network batch the last select wrote on the device (what `step()` feeds the network): f16 [rows,64,32],
@@ -359,7 +377,7 @@ class SelfplayEngine:
         cap = self.cfg.concurrent_games * (self.cfg.inference_batch_size + 1) + 4
         out = np.zeros((cap, 64, 32), dtype=np.float16)
         rows = c_int(0)
-        _lib.check(self._L.m0_selfplay_last_batch_nhwc(self._h, out.ctypes.data_as(C.c_void_p), cap, C.byref(rows)),
+        _lib.check(self._L.m0_selfplay_last_batch_nhwc(self._h, _ptr(out), cap, C.byref(rows)),
                    "m0_selfplay_last_batch_nhwc")
         return out[: rows.value]
 
@@ -368,25 +386,18 @@ class SelfplayEngine:
         _lib.check(self._L.m0_search_begin(self._h, g, fen.encode(), sims, int(dirichlet), game_uid), "m0_search_begin")
 
     def search_select(self) -> np.ndarray:
-        rows = c_int(0)
-        cap = self.cfg.concurrent_games * (self.cfg.inference_batch_size + 1)
-        planes = np.zeros((cap, 19, 8, 8), dtype=np.float32)
-        _lib.check(self._L.m0_search_select(self._h, C.byref(rows), planes.ctypes.data_as(C.c_void_p), cap), "m0_search_select")
-        return planes[: rows.value]
+        return self._select(self._L.m0_search_select, "m0_search_select")[0]
 
     def search_expand(self, logits: np.ndarray, values: np.ndarray) -> None:
-        lg = np.ascontiguousarray(logits, dtype=np.float32)
-        vv = np.ascontiguousarray(values, dtype=np.float32)
-        _lib.check(self._L.m0_search_expand(self._h, lg.ctypes.data_as(C.c_void_p), vv.ctypes.data_as(C.c_void_p),
-                                            int(lg.shape[0])), "m0_search_expand")
+        self._expand(self._L.m0_search_expand, "m0_search_expand", (logits, values))
 
     def search_result(self, g: int) -> dict:
         n = c_int(0); rn = c_int(0); fin = c_int(0); rq = c_double(0)
         cn = np.zeros(256, np.int32); mv = np.zeros(256, np.uint16); idx = np.zeros(256, np.int32)
         pr = np.zeros(256, np.float64); q = np.zeros(256, np.float64)
-        _lib.check(self._L.m0_search_result(self._h, g, C.byref(n), cn.ctypes.data_as(C.c_void_p), mv.ctypes.data_as(C.c_void_p),
-                                            idx.ctypes.data_as(C.c_void_p), pr.ctypes.data_as(C.c_void_p),
-                                            q.ctypes.data_as(C.c_void_p), C.byref(rq), C.byref(rn), C.byref(fin)),
+        _lib.check(self._L.m0_search_result(self._h, g, C.byref(n), _ptr(cn), _ptr(mv),
+                                            _ptr(idx), _ptr(pr),
+                                            _ptr(q), C.byref(rq), C.byref(rn), C.byref(fin)),
                    "m0_search_result")
         k = n.value
         return {"finished": bool(fin.value), "n": cn[:k].copy(), "moves": [move_to_uci(int(x)) for x in mv[:k]],
@@ -498,7 +509,7 @@ class SelfplayPool:
 def sample_move_index(visits, temperature: float, u: float) -> int:
     L = _bind()
     v = np.ascontiguousarray(visits, dtype=np.int32)
-    return int(L.m0_sample_move_index(v.ctypes.data_as(C.c_void_p), int(v.shape[0]), float(temperature), float(u)))
+    return int(L.m0_sample_move_index(_ptr(v), int(v.shape[0]), float(temperature), float(u)))
 
 
 def playout_cap(sims: int, frac: float, u: float) -> int:
@@ -529,7 +540,7 @@ def encode_fens_nhwc(fens, device_index: int = 0) -> np.ndarray:
     n = len(fens)
     arr = (C.c_char_p * n)(*[f.encode() for f in fens])
     out = np.empty((n, 64, 32), np.float16)
-    _lib.check(L.m0_encode_fens_nhwc(int(device_index), arr, n, out.ctypes.data_as(C.c_void_p)), "m0_encode_fens_nhwc")
+    _lib.check(L.m0_encode_fens_nhwc(int(device_index), arr, n, _ptr(out)), "m0_encode_fens_nhwc")
     return out
 
 
@@ -547,7 +558,7 @@ def ssl_targets_fens(fens, device_index: int = 0) -> dict:
     n = len(fens)
     arr = (C.c_char_p * n)(*[f.encode() for f in fens])
     out = np.empty((n, 17, 8, 8), np.float32)
-    _lib.check(L.m0_ssl_targets_fens(int(device_index), arr, n, out.ctypes.data_as(C.c_void_p)), "m0_ssl_targets_fens")
+    _lib.check(L.m0_ssl_targets_fens(int(device_index), arr, n, _ptr(out)), "m0_ssl_targets_fens")
     return {"piece": out[:, :13], "threat": out[:, 13], "pin": out[:, 14], "fork": out[:, 15], "control": out[:, 16]}
 
 
@@ -558,41 +569,22 @@ class ArenaEngine(SelfplayEngine):
     `cfg.arena_eval_cache` gives each network an evaluation cache per game (`cfg.eval_cache` is ignored here)."""
 
     def __init__(self, backend_a, backend_b, cfg: SelfplayCfg):
-        self._L = _bind()
-        self.backend = backend_a
         self.backend_b = backend_b
-        self.cfg = cfg
-        self._h = self._L.m0_arena_create(backend_a.handle, backend_b.handle, C.byref(cfg))
-        if not self._h:
-            raise RuntimeError(f"m0_arena_create failed: {_lib.last_error()}")
+        self._open(backend_a, cfg, "m0_arena_create", backend_a.handle, backend_b.handle, C.byref(cfg))
 
 
 class ArenaExtEngine(SelfplayEngine):
     """Match engine without networks (m0_arena_create_ext): two external evaluators behind the infer_np seam."""
 
     def __init__(self, cfg: SelfplayCfg):
-        self._L = _bind()
-        self.backend = None
-        self.cfg = cfg
-        self._h = self._L.m0_arena_create_ext(C.byref(cfg))
-        if not self._h:
-            raise RuntimeError(f"m0_arena_create_ext failed: {_lib.last_error()}")
+        self._open(None, cfg, "m0_arena_create_ext", C.byref(cfg))
 
     def arena_ext_select(self):
-        ra, rb = c_int(0), c_int(0)
-        cap = self.cfg.concurrent_games * (self.cfg.inference_batch_size + 1)
-        pa = np.zeros((cap, 19, 8, 8), dtype=np.float32)
-        pb = np.zeros((cap, 19, 8, 8), dtype=np.float32)
-        _lib.check(self._L.m0_arena_ext_select(self._h, C.byref(ra), C.byref(rb), pa.ctypes.data_as(C.c_void_p),
-                                               pb.ctypes.data_as(C.c_void_p), cap), "m0_arena_ext_select")
-        return pa[: ra.value], pb[: rb.value]
+        pa, pb = self._select(self._L.m0_arena_ext_select, "m0_arena_ext_select", regions=2)
+        return pa, pb
 
     def arena_ext_expand(self, lg_a, v_a, lg_b, v_b) -> None:
-        la = np.ascontiguousarray(lg_a, dtype=np.float32); va = np.ascontiguousarray(v_a, dtype=np.float32)
-        lb = np.ascontiguousarray(lg_b, dtype=np.float32); vb = np.ascontiguousarray(v_b, dtype=np.float32)
-        _lib.check(self._L.m0_arena_ext_expand(self._h, la.ctypes.data_as(C.c_void_p), va.ctypes.data_as(C.c_void_p), int(la.shape[0]),
-                                               lb.ctypes.data_as(C.c_void_p), vb.ctypes.data_as(C.c_void_p), int(lb.shape[0])),
-                   "m0_arena_ext_expand")
+        self._expand(self._L.m0_arena_ext_expand, "m0_arena_ext_expand", (lg_a, v_a), (lg_b, v_b))
 
 
 ANALYSIS_STATUS = {0: "ok", 1: "checkmate", 2: "stalemate", 3: "tablebase"}
@@ -625,16 +617,11 @@ class AnalysisEngine(SelfplayEngine):
     matrix0_amd.analysis.Analyzer is the interface built on it."""
 
     def __init__(self, backend, cfg: SelfplayCfg, *, multipv: int = 1, pv_len: int = 8, dirichlet: bool = False):
-        self._L = _bind()
-        self.backend = backend
-        self.cfg = cfg
         self.opts = AnalysisOpts(int(multipv), int(pv_len), int(bool(dirichlet)))
-        self._h = self._create()
-        if not self._h:
-            raise RuntimeError(f"m0_analysis_create failed: {_lib.last_error()}")
-
-    def _create(self):
-        return self._L.m0_analysis_create(self.backend.handle, C.byref(self.cfg), C.byref(self.opts))
+        if backend is not None:
+            self._open(backend, cfg, "m0_analysis_create", backend.handle, C.byref(cfg), C.byref(self.opts))
+        else:                                                  # AnalysisExtEngine
+            self._open(None, cfg, "m0_analysis_create_ext", C.byref(cfg), C.byref(self.opts))
 
     def submit(self, fen: str, ucis=(), sims: int = 0, id: int = 0) -> None:
         ucis = list(ucis)
@@ -665,34 +652,20 @@ class AnalysisExtEngine(AnalysisEngine):
     def __init__(self, cfg: SelfplayCfg, **opts):
         super().__init__(None, cfg, **opts)
 
-    def _create(self):
-        return self._L.m0_analysis_create_ext(C.byref(self.cfg), C.byref(self.opts))
-
     def step(self, infer_np, steps: int = 1) -> None:
-        cap = self.cfg.concurrent_games * (self.cfg.inference_batch_size + 1)
-        planes = np.zeros((cap, 19, 8, 8), dtype=np.float32)
-        rows = c_int(0)
         for _ in range(int(steps)):
             if self.pending() == 0:
                 break
-            _lib.check(self._L.m0_analysis_ext_select(self._h, C.byref(rows), planes.ctypes.data_as(C.c_void_p), cap),
-                       "m0_analysis_ext_select")
-            n = rows.value
-            if n:
-                lg, v = infer_np(planes[:n])
-                lg = np.ascontiguousarray(lg, dtype=np.float32)
-                v = np.ascontiguousarray(v, dtype=np.float32)
-            else:
-                lg, v = np.zeros((0, 4672), np.float32), np.zeros((0,), np.float32)
-            _lib.check(self._L.m0_analysis_ext_expand(self._h, lg.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), n),
-                       "m0_analysis_ext_expand")
+            planes = self._select(self._L.m0_analysis_ext_select, "m0_analysis_ext_select")[0]
+            answer = infer_np(planes) if len(planes) else (np.zeros((0, 4672), np.float32), np.zeros((0,), np.float32))
+            self._expand(self._L.m0_analysis_ext_expand, "m0_analysis_ext_expand", answer)
 
 
 def arena_choose_move(visits, temp: float, ply: int, temp_plies: int, u: float) -> int:
     """arena.py:73-106 (host_rules.h::arena_choose_move)."""
     L = _bind()
     v = np.ascontiguousarray(visits, dtype=np.int32)
-    return int(L.m0_arena_choose_move(v.ctypes.data_as(C.c_void_p), int(len(v)), float(temp), int(ply), int(temp_plies), float(u)))
+    return int(L.m0_arena_choose_move(_ptr(v), int(len(v)), float(temp), int(ply), int(temp_plies), float(u)))
 
 
 def san_legal(fen: str):
@@ -701,7 +674,7 @@ def san_legal(fen: str):
     mv = np.zeros(256, np.uint16)
     san = C.create_string_buffer(256 * 8)
     n = c_int(0)
-    _lib.check(L.m0_san_legal_fen(fen.encode(), mv.ctypes.data_as(C.c_void_p), san, C.byref(n)), "m0_san_legal_fen")
+    _lib.check(L.m0_san_legal_fen(fen.encode(), _ptr(mv), san, C.byref(n)), "m0_san_legal_fen")
     raw = san.raw
     return [(move_to_uci(int(mv[i])), raw[8 * i: 8 * i + 8].split(b"\0", 1)[0].decode()) for i in range(n.value)]
 
@@ -726,9 +699,9 @@ def san_game(moves_raw, fen: Optional[str] = None) -> str:
     mv = np.ascontiguousarray(moves_raw, dtype=np.uint16)
     buf = C.create_string_buffer(16 * (len(mv) + 4))
     if fen is None:
-        rc = L.m0_san_game(mv.ctypes.data_as(C.c_void_p), int(len(mv)), buf, len(buf))
+        rc = L.m0_san_game(_ptr(mv), int(len(mv)), buf, len(buf))
     else:
-        rc = L.m0_san_game_fen(fen.encode(), mv.ctypes.data_as(C.c_void_p), int(len(mv)), buf, len(buf))
+        rc = L.m0_san_game_fen(fen.encode(), _ptr(mv), int(len(mv)), buf, len(buf))
     if rc < 0:
         _lib.check(rc, "m0_san_game")
     return buf.value.decode().strip()

@@ -44,12 +44,6 @@ def _bind():
     L.m0_tb_table.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
     L.m0_tb_table_info.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)]
     L.m0_tb_probe_fens.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.m0_selfplay_set_tablebase.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    L.m0_selfplay_tb_adjudications.restype = C.c_uint64
-    L.m0_selfplay_tb_adjudications.argtypes = [C.c_void_p]
-    L.m0_selfplay_set_search_tablebase.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    L.m0_selfplay_tb_leaves.restype = C.c_uint64
-    L.m0_selfplay_tb_leaves.argtypes = [C.c_void_p]
     L.m0_tb_root_lines.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p]
     _bound = True
     return L

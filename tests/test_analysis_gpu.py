@@ -303,3 +303,74 @@ def test_mode_errors_leave_the_engine_usable():
     an.close()
     _check(got[0], _oracle_set(False)[1], "after the errors")
     assert got[1]["status"] == "ok" and got[1]["root_n"] == SIMS and got[1]["lines"][0]["visits"] > 0
+
+
+def test_every_entry_point_refuses_the_wrong_kind_of_engine():
+    """One engine of each kind without a network, in the smallest configuration, and every entry point with otherwise valid
+    arguments on the kinds that must refuse it: M0_ERR_STATE, no kernel launched, the engine untouched (stats unchanged, nothing
+    pending).  m0_search_* on a match engine is accepted, as it always was.  The calls every kind accepts are checked too."""
+    import ctypes as C
+    from matrix0_amd import _lib
+    from matrix0_amd import engine as eng
+    L = eng._bind()
+
+    def cfg():
+        return eng.selfplay_cfg_from_dict(_cfg(sims=4, leaves=2), concurrent_games=1)
+
+    engines = {"self-play": eng.SelfplayEngine(None, cfg()), "match": eng.ArenaExtEngine(cfg()),
+               "analysis": eng.AnalysisExtEngine(cfg())}
+    cap = 1 * (2 + 1)
+    pa, pb = np.zeros((cap, 19, 8, 8), np.float32), np.zeros((cap, 19, 8, 8), np.float32)
+    lg, v = np.zeros((cap, 4672), np.float32), np.zeros(cap, np.float32)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    rows, rows_b, n, rn, fin, rq = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_double(0)
+    rec, res, st = eng.GameRecord(), eng.AnalysisResult(), eng.SelfplayStats()
+    fen = ch.START_FEN.encode()
+    book = (C.c_char_p * 1)(fen)
+    games, not_analysis = {"analysis"}, {"self-play", "match"}
+    refused = [          # (call, the kinds that refuse it)
+        ("m0_selfplay_step", lambda h: L.m0_selfplay_step(h, 1), games),
+        ("m0_selfplay_poll", lambda h: L.m0_selfplay_poll(h, C.byref(rec)), games),
+        ("m0_selfplay_set_openings", lambda h: L.m0_selfplay_set_openings(h, book, 1), games),
+        ("m0_selfplay_ext_select", lambda h: L.m0_selfplay_ext_select(h, C.byref(rows), ptr(pa), cap), {"match", "analysis"}),
+        ("m0_selfplay_ext_expand", lambda h: L.m0_selfplay_ext_expand(h, ptr(lg), ptr(v), 0), {"match", "analysis"}),
+        ("m0_arena_ext_select", lambda h: L.m0_arena_ext_select(h, C.byref(rows), C.byref(rows_b), ptr(pa), ptr(pb), cap),
+         {"self-play", "analysis"}),
+        ("m0_arena_ext_expand", lambda h: L.m0_arena_ext_expand(h, ptr(lg), ptr(v), 0, ptr(lg), ptr(v), 0), {"self-play", "analysis"}),
+        ("m0_search_begin", lambda h: L.m0_search_begin(h, 0, fen, 4, 0, 1), games),
+        ("m0_search_select", lambda h: L.m0_search_select(h, C.byref(rows), ptr(pa), cap), games),
+        ("m0_search_expand", lambda h: L.m0_search_expand(h, ptr(lg), ptr(v), 0), games),
+        ("m0_search_result", lambda h: L.m0_search_result(h, 0, C.byref(n), None, None, None, None, None, C.byref(rq), C.byref(rn),
+                                                          C.byref(fin)), games),
+        ("m0_search_advance", lambda h: L.m0_search_advance(h, 0, 0, 4, 0), games),
+        ("m0_analysis_submit", lambda h: L.m0_analysis_submit(h, fen, None, 0, 4, 1), not_analysis),
+        ("m0_analysis_step", lambda h: L.m0_analysis_step(h, 1), not_analysis),
+        ("m0_analysis_ext_select", lambda h: L.m0_analysis_ext_select(h, C.byref(rows), ptr(pa), cap), not_analysis),
+        ("m0_analysis_ext_expand", lambda h: L.m0_analysis_ext_expand(h, ptr(lg), ptr(v), 0), not_analysis),
+        ("m0_analysis_poll", lambda h: L.m0_analysis_poll(h, C.byref(res)), not_analysis),
+        ("m0_analysis_pending", lambda h: L.m0_analysis_pending(h), not_analysis),
+        ("m0_selfplay_set_tablebase", lambda h: L.m0_selfplay_set_tablebase(h, None, 0), {"match", "analysis"}),
+    ]
+    try:
+        for kind, e in engines.items():
+            before = e.stats()
+            for name, call, kinds in refused:
+                if kind not in kinds:
+                    continue
+                assert call(e._h) == _lib.M0_ERR_STATE, (name, kind)
+                assert e.stats() == before, (name, kind)
+                if kind == "analysis":
+                    assert e.pending() == 0, name
+            # what every kind accepts
+            assert L.m0_selfplay_set_search_tablebase(e._h, None, 0) == _lib.M0_OK, kind
+            assert L.m0_selfplay_stats_get(e._h, C.byref(st)) == _lib.M0_OK, kind
+            assert L.m0_selfplay_running(e._h) in (0, 1), kind
+            assert e.tb_leaves() == 0 and e.tb_adjudications() == 0, kind
+            assert e.stats() == before, kind
+        sp = engines["self-play"]
+        assert L.m0_selfplay_set_tablebase(sp._h, None, 0) == _lib.M0_OK
+        sp.search_begin(0, ch.START_FEN, 4, False, 1)             # and it still plays
+        assert sp.search_select().shape[0] >= 1
+    finally:
+        for e in engines.values():
+            e.close()

@@ -23,6 +23,32 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(L, n), f"{n} declared in include/m0_engine.h but not exported"
 
 
+def test_engine_entry_points_refuse_a_null_handle():
+    """Every call that takes an engine handle, as include/m0_engine.h declares it, answers a null one as the header says:
+    M0_ERR_INVALID from the int-returning calls, 0 from the three counters / predicates, and m0_selfplay_destroy returns.  The null
+    test is the first thing the call guard does, so this needs no device; an entry point added without the guard fails here."""
+    import ctypes as C
+    hdr = open(os.path.join(ROOT, "include", "m0_engine.h")).read()
+    decls = re.findall(r"^(int|uint64_t|void)\s+(m0_(?:selfplay|arena_ext|search|analysis)_[a-z0-9_]+)\s*\(\s*m0_selfplay\s*\*([^;]*)\)\s*;",
+                       hdr, flags=re.M)
+    names = [n for _, n, _ in decls]
+    assert len(names) == len(set(names)) >= 25, names
+    for must in ("m0_selfplay_step", "m0_arena_ext_expand", "m0_search_result", "m0_analysis_pending", "m0_selfplay_tb_leaves",
+                 "m0_selfplay_set_search_tablebase", "m0_selfplay_destroy"):
+        assert must in names, must
+    _lib.lib()                                           # the loader's own order of libraries
+    L = C.CDLL(_lib.LIB_PATH)                            # function objects of its own: no argtypes, a null for every argument
+    zero = ("m0_selfplay_running", "m0_selfplay_tb_leaves", "m0_selfplay_tb_adjudications")
+    for ret, name, rest in decls:
+        fn = getattr(L, name)
+        fn.restype = {"int": C.c_int, "uint64_t": C.c_uint64, "void": None}[ret]
+        got = fn(None, *[None if "*" in a else 0 for a in rest.split(",")[1:]])
+        if ret == "void":
+            assert name == "m0_selfplay_destroy"
+        else:
+            assert got == (0 if name in zero else _lib.M0_ERR_INVALID), (name, got)
+
+
 def test_create_without_gpu_fails_loudly_or_works():
     """No CPU fallback: on a box without a HIP device creation must raise, never silently degrade."""
     import torch
