@@ -433,10 +433,9 @@ __device__ __forceinline__ void ab_second_output(const AbLane& L) {
         float s = 0.f, ss = 0.f;
         for (int ww = 0; ww < 4; ++ww)
             for (int q = 0; q < 4; ++q) { const float2 v = scr[((bd * 4 + ww) * 20 + j) * 4 + q]; s += v.x; ss += v.y; }
-        const float mu = s * (1.f / 1024.f);
-        float vr = ss * (1.f / 1024.f) - mu * mu;
-        vr = vr > 0.f ? vr : 0.f;
-        tot[tid] = make_float2(mu, rsqrtf(vr + 1e-5f));
+        float mu, rstd;
+        gn16_mean_rstd(s, ss, mu, rstd);
+        tot[tid] = make_float2(mu, rstd);
     }
     __syncthreads();
     // per (board, channel) scale and shift over the gamma / beta slots (the second GroupNorm's parameters are dead after this)

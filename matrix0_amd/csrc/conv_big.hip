@@ -1,14 +1,18 @@
-// conv_big_kernel: the 1x1 big-tile GEMM on MFMA with global_load_lds staging: the piece-square-table conv with the PRE
-// block tail (conv_tail.h), the split-K FCs and the unfused qkv / proj path.  See net_kernels.hip's header for the design.
+// conv_big_kernel: the 1x1 big-tile GEMM: the piece-square-table conv with the PRE block tail (conv_tail.h), the split-K FCs
+// and the unfused qkv / proj path, on v_mfma_f32_32x32x16_f16, fp32 accumulate (data layout: net_kernels.h).  WG = 8 waves,
+// tile = 256 rows (4 boards) x 320 output channels, K stepped in 64-channel chunks.  Both operands go global -> LDS by
+// global_load_lds (16 B/lane, no VGPR staging), double-buffered: the 64-channel slice of the 4 boards and one 320x64 weight
+// stage per chunk (pre-swizzled on the host).  128-byte LDS rows, 16-byte chunk index XOR (row>>1)&7 -> conflict-free
+// ds_read_b128.  Epilogue: bias/act/mul/scale + per-(board,channel) sums, staged or per element, or the PRE block tail.
+// (The 3x3 tower convs: conv_zs_kernel, conv_zs.hip.)
 #include "kernel_common.h"
 #include "conv_epilogue.h"
 #include "conv_tail.h"
 
-// EPI: 0 plain (bias/act/mul/scale + column sums), 2 the same per element (mul / f32 / activation), 5 the PRE block tail.
-// A template parameter so that each epilogue gets its own register allocation.
+// EPI (ConvEpi, net_kernels.h): EPI_PLAIN, EPI_ELEMENT (mul / f32 / activation) or EPI_TAIL_PRE with its activation ACT.
 // 8 waves (2 per SIMD), wave tile 64x160, <=256 VGPRs.  (A 4-wave form with a 64x320 wave tile was built and measured:
 // numerically identical, 2x slower with hipcc's schedule -- LDS latency exposed with one wave per SIMD, spills.)
-template <int EPI, int ACT = ACT_NONE>
+template <ConvEpi EPI, int ACT = ACT_NONE>
 __global__ __launch_bounds__(512) void conv_big_kernel(GemmArgs a) {
     // split K: workgroup row blockIdx.y takes 1/ksplit of the 64-channel chunks and writes an fp32 partial tile
     const int ksp = a.ksplit > 1 ? a.ksplit : 1;
@@ -179,12 +183,11 @@ __global__ __launch_bounds__(512) void conv_big_kernel(GemmArgs a) {
 
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();                      // the epilogue stages the output tile over the A/W buffers
-    // EPI 5: out = res + act(GroupNorm16(conv)) (+ the next GroupNorm's second output), conv_tail.h's PRE form
-    if constexpr (EPI == 5) conv_tail_epilogue<ACT>(acc, a, smem, m0, wm, wn, wave, lane);
+    if constexpr (EPI == EPI_TAIL_PRE) conv_tail_epilogue<ACT>(acc, a, smem, m0, wm, wn, wave, lane);
     else conv_tile_epilogue<EPI, ACT_NONE, NT>(acc, a, smem + wave * (NT * 64 * 64), m0, n0, wm, wn, lane);
 }
 
-template <int EPI, int ACT = ACT_NONE>
+template <ConvEpi EPI, int ACT = ACT_NONE>
 static hipError_t launch_conv_big_e(const GemmArgs& a, hipStream_t st) {
     const size_t lds = 160 * 1024;
     static DeviceOnce once;
@@ -206,8 +209,8 @@ hipError_t launch_conv_big(const GemmArgs& a, int taps, hipStream_t st) {
             a.out_stats != nullptr || a.mul != nullptr || a.out_f32 != 0 || a.ksplit > 1 || (a.y2 != nullptr && a.gn_gamma == nullptr))
             return hipErrorInvalidValue;
         if ((size_t)a.Mrows * a.ldo * 2 >= ((size_t)1 << 32)) return hipErrorInvalidValue;
-        if (a.epi_act == ACT_SILU) return launch_conv_big_e<5, ACT_SILU>(a, st);
-        if (a.epi_act == ACT_RELU) return launch_conv_big_e<5, ACT_RELU>(a, st);
+        if (a.epi_act == ACT_SILU) return launch_conv_big_e<EPI_TAIL_PRE, ACT_SILU>(a, st);
+        if (a.epi_act == ACT_RELU) return launch_conv_big_e<EPI_TAIL_PRE, ACT_RELU>(a, st);
         return hipErrorInvalidValue;
     }
     if (a.gn_gamma != nullptr) return hipErrorInvalidValue;
@@ -215,7 +218,7 @@ hipError_t launch_conv_big(const GemmArgs& a, int taps, hipStream_t st) {
         return hipErrorInvalidValue;
     if ((size_t)a.Mrows * a.ldo * 2 >= ((size_t)1 << 32)) return hipErrorInvalidValue;   // 32-bit store offsets
     const bool general = a.mul != nullptr || a.out_f32 != 0 || a.epi_act != ACT_NONE;   // per-element epilogue
-    return general ? launch_conv_big_e<2>(a, st) : launch_conv_big_e<0>(a, st);
+    return general ? launch_conv_big_e<EPI_ELEMENT>(a, st) : launch_conv_big_e<EPI_PLAIN>(a, st);
 }
 
 // Second pass of a split-K GEMM: fixed-order sum of the partial tiles, bias, activation, fp16.

@@ -1,4 +1,6 @@
-// Output epilogues of the 256x320 conv tile (conv_big_kernel; the 32x32x16 3x3 experiment tools/ubench/conv_pp.hip uses them too).
+// Output epilogues of the 32x32-accumulator conv tiles, 64 rows x 32 NT columns per wave: conv_big_kernel (NT = 5),
+// conv_gemm_kernel (NT = 1, 2, 5) and the 32x32x16 3x3 experiments tools/ubench/conv_pp.hip / conv_sw.hip.  Also the one
+// spelling of the GroupNorm16 arithmetic (gn16_*) that every normalising kernel uses.
 #pragma once
 #include "kernel_common.h"
 
@@ -64,36 +66,60 @@ __device__ __forceinline__ void conv_stage_flush(const GemmArgs& a, const char* 
     }
 }
 
-// acc[mi][ni]: 32x32 MFMA accumulators of the wave's 64 x (32*NT) tile (board wm of the 4-board tile, N part wn).
-// EPI 0: bias / activation ACT / scale, fp16 store, per-(board,channel) sum and sum of squares.
-// EPI 1: GroupNorm(16 channels x 64 squares) + activation ACT in registers -- the wave owns whole groups.
-// EPI 2: bias / runtime activation a.epi_act / gate multiply / scale, fp16 or f32 output stored per element
-//        (small head GEMMs only; ACT ignored).
-// EPI 0/1 finish each 32x32 tile's values, stage the tile in LDS at once (frees its accumulators), then flush.
-template <int EPI, int ACT, int NT>
+// GroupNorm over one group of 16 channels x 64 squares (resnet.py's GroupNorm(C / 16, C), eps 1e-5), from the group's sum and
+// sum of squares.  Every kernel that normalises goes through these two, so the arithmetic -- and where hipcc contracts it
+// into FMAs -- is the same everywhere; a site that serves several channels of one group takes (mean, rstd) once.
+__device__ __forceinline__ void gn16_mean_rstd(float s, float ss, float& mean, float& rstd) {
+    mean = s * (1.f / 1024.f);
+    float var = ss * (1.f / 1024.f) - mean * mean;
+    var = var > 0.f ? var : 0.f;
+    rstd = rsqrtf(var + 1e-5f);
+}
+// ... and one channel's affine form of it: GroupNorm(v) = v * scale + shift.  (gamma / beta by reference: a parameter that
+// is still in memory is fetched where it is used, beta after the scale.)
+__device__ __forceinline__ void gn16_affine(float mean, float rstd, const float& gamma, const float& beta, float& scale,
+                                            float& shift) {
+    scale = gamma * rstd;
+    shift = beta - mean * scale;
+}
+
+// GroupNorm16 of the conv output on the 32x32 accumulators: scale and shift of this lane's column `col` of tile column NI.
+// The wave holds all 64 squares of its board and whole groups: a group is 16 neighbouring lanes of both lane halves.
+template <int NI, int NT>
+__device__ __forceinline__ void conv_gn_column(const float16v (&acc)[2][NT], const float* gamma, const float* beta, int col,
+                                               float& scale, float& shift) {
+    float s = 0.f, ss = 0.f;
+    static_for<0, 2>([&](auto mi_) __attribute__((always_inline)) {
+        const float16v av = acc[decltype(mi_)::value][NI];
+        static_for<0, 16>([&](auto r_) __attribute__((always_inline)) { const float v = av[decltype(r_)::value]; s += v; ss += v * v; });
+    });
+#pragma unroll
+    for (int o = 1; o <= 8; o <<= 1) { s += __shfl_xor(s, o); ss += __shfl_xor(ss, o); }
+    s += __shfl_xor(s, 32); ss += __shfl_xor(ss, 32);
+    float mean, rstd;
+    gn16_mean_rstd(s, ss, mean, rstd);
+    gn16_affine(mean, rstd, gamma[col], beta[col], scale, shift);
+}
+
+// acc[mi][ni]: 32x32 MFMA accumulators of the wave's 64 x (32*NT) tile (board wm of the 4-board tile, N part wn); the
+// kinds are ConvEpi's (net_kernels.h).  EPI_ELEMENT ignores ACT and lds_wave.  EPI_GN adds a.posenc when it is not null: only
+// the stem sets it, every other caller leaves it null (GemmArgs a{} does).  EPI_GN stores column c at a.out + c - out_col0:
+// conv_gemm_kernel's second output starts at column a.nsplit of the tile; everyone else leaves out_col0 at 0.
+// EPI_PLAIN / EPI_GN finish each 32x32 tile's values, stage the tile in LDS at once (frees its accumulators), then flush.
+// (everything indexed with compile-time constants: a runtime-indexed accumulator goes to scratch)
+template <ConvEpi EPI, int ACT, int NT>
 __device__ __forceinline__ void conv_tile_epilogue(float16v (&acc)[2][NT], const GemmArgs& a, char* lds_wave, int m0,
-                                                   int n0, int wm, int wn, int lane) {
+                                                   int n0, int wm, int wn, int lane, int out_col0 = 0) {
     const int half = lane >> 5;
     const int r31 = lane & 31;
     const int colbase = n0 + wn * NT * 32 + r31;
     char* wbase = conv_stage_base<NT>(lds_wave, lane);
-    if constexpr (EPI == 1) {
+    if constexpr (EPI == EPI_GN) {
         static_for<0, NT>([&](auto ni_) __attribute__((always_inline)) {
             constexpr int ni = decltype(ni_)::value;
             const int col = colbase + ni * 32;
-            float s = 0.f, ss = 0.f;
-            static_for<0, 2>([&](auto mi_) __attribute__((always_inline)) {
-                const float16v av = acc[decltype(mi_)::value][ni];
-                static_for<0, 16>([&](auto r_) __attribute__((always_inline)) { const float v = av[decltype(r_)::value]; s += v; ss += v * v; });
-            });
-#pragma unroll
-            for (int o = 1; o <= 8; o <<= 1) { s += __shfl_xor(s, o); ss += __shfl_xor(ss, o); }
-            s += __shfl_xor(s, 32); ss += __shfl_xor(ss, 32);
-            const float mean = s * (1.f / 1024.f);
-            float var = ss * (1.f / 1024.f) - mean * mean;
-            var = var > 0.f ? var : 0.f;
-            const float g = rsqrtf(var + 1e-5f) * a.gn_gamma[col];
-            const float sh = a.gn_beta[col] - mean * g;
+            float g, sh;
+            conv_gn_column<ni>(acc, a.gn_gamma, a.gn_beta, col, g, sh);
             static_for<0, 2>([&](auto mi_) __attribute__((always_inline)) {
                 constexpr int mi = decltype(mi_)::value;
                 float v[16];
@@ -101,12 +127,19 @@ __device__ __forceinline__ void conv_tile_epilogue(float16v (&acc)[2][NT], const
                     constexpr int r = decltype(r_)::value;
                     v[r] = act_fast<ACT>(acc[mi][ni][r] * g + sh);
                 });
+                if (a.posenc != nullptr) {
+                    static_for<0, 16>([&](auto r_) __attribute__((always_inline)) {
+                        constexpr int r = decltype(r_)::value;
+                        const int sq = mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                        v[r] += a.posenc[(size_t)sq * a.N + col];
+                    });
+                }
                 conv_stage_tile<NT, mi, ni>(v, wbase, lane);
             });
         });
-        conv_stage_flush<NT>(a, lds_wave, m0, n0, wm, wn, lane);
+        conv_stage_flush<NT>(a, lds_wave, m0, n0 - out_col0, wm, wn, lane);
     }
-    if constexpr (EPI == 0) {
+    if constexpr (EPI == EPI_PLAIN) {
         const float oscale = a.out_scale;
         const bool want_stats = a.out_stats != nullptr;
         float* stats = a.out_stats + ((size_t)(m0 / 64 + wm) * a.N + colbase) * 2;
@@ -132,7 +165,7 @@ __device__ __forceinline__ void conv_tile_epilogue(float16v (&acc)[2][NT], const
         });
         conv_stage_flush<NT>(a, lds_wave, m0, n0, wm, wn, lane);
     }
-    if constexpr (EPI == 2) {
+    if constexpr (EPI == EPI_ELEMENT) {
         const int ldo = a.ldo;
         const int rowbase = m0 + wm * 64 + 4 * half;
         const int epi_act = a.epi_act;

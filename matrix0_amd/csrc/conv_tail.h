@@ -7,9 +7,9 @@
 //   y2     = act(GroupNorm16(y; next block's bn1))                    the next conv1's operand     -> a.y2 (optional)
 // i.e. what conv2's plain epilogue + se_gate_kernel + ew_board_kernel did with three launches and two more trips of
 // the tensor through HBM.  Everything a board needs is inside the workgroup, so the only new global traffic is the
-// read of x.  Each accumulator layout has its own tail: conv_tail_epilogue below (conv_big_kernel, PRE only) and
-// conv_zs_tail.h (conv_zs_kernel).  Each reads its accumulators (channel means, squeeze-excite gate, PRE statistics)
-// and stages gate * t as fp16 in the wave's private LDS image, 64 rows of 20
+// read of x.  Each accumulator layout has its own tail: conv_tail_epilogue below (conv_big_kernel, EPI_TAIL_PRE only)
+// and conv_zs_tail.h (conv_zs_kernel, EPI_TAIL and EPI_TAIL_PRE).  Each reads its accumulators (channel means,
+// squeeze-excite gate, PRE statistics) and stages gate * t as fp16 in the wave's private LDS image, 64 rows of 20
 // 16-byte chunks, issuing the loads of x between the tile columns.  The rest works on that image and is shared:
 //   tail_gn_params  the second GroupNorm's parameters of the lane's 8 channels (fetched first: a late load is an
 //                   exposed global-memory latency in a kernel with one workgroup per CU)
@@ -29,10 +29,8 @@ constexpr int TAIL_NCH = 20;         // 16-byte chunks per image row (160 channe
 constexpr int TAIL_NIT = 22;         // image rows per lane: ceil(64 / 3)
 
 __device__ __forceinline__ void tail_gn_params(const GemmArgs& a, int c0, float (&gg)[8], float (&bb)[8]) {
-    const float4 g0 = *reinterpret_cast<const float4*>(a.gn_gamma + c0), g1 = *reinterpret_cast<const float4*>(a.gn_gamma + c0 + 4);
-    const float4 b0 = *reinterpret_cast<const float4*>(a.gn_beta + c0), b1 = *reinterpret_cast<const float4*>(a.gn_beta + c0 + 4);
-    gg[0] = g0.x; gg[1] = g0.y; gg[2] = g0.z; gg[3] = g0.w; gg[4] = g1.x; gg[5] = g1.y; gg[6] = g1.z; gg[7] = g1.w;
-    bb[0] = b0.x; bb[1] = b0.y; bb[2] = b0.z; bb[3] = b0.w; bb[4] = b1.x; bb[5] = b1.y; bb[6] = b1.z; bb[7] = b1.w;
+    load8f(a.gn_gamma + c0, gg);
+    load8f(a.gn_beta + c0, bb);
 }
 
 // y = x + image; lane = (chunk = lane % 20, rsub = lane / 20), rows rsub, rsub+3, ...; lanes 60..63 idle.  Row `row` of
@@ -85,14 +83,12 @@ __device__ __forceinline__ void tail_y2(const char* img, uint32_t lane_loff, cha
                                         int rows_valid, float gs, float gss, const float (&gg)[8], const float (&bb)[8], int lane) {
     const int rsub = lane / TAIL_NCH;
     const bool lane_on = rsub < 3;
-    const float mean = gs * (1.f / 1024.f);
-    float var = gss * (1.f / 1024.f) - mean * mean;
-    var = var > 0.f ? var : 0.f;
-    const float rstd = rsqrtf(var + 1e-5f);
+    float mean, rstd;
+    gn16_mean_rstd(gs, gss, mean, rstd);
     float scl[8], shl[8];
     static_for<0, 8>([&](auto i_) __attribute__((always_inline)) {
         constexpr int i = decltype(i_)::value;
-        scl[i] = gg[i] * rstd; shl[i] = bb[i] - mean * scl[i];
+        gn16_affine(mean, rstd, gg[i], bb[i], scl[i], shl[i]);
     });
 #pragma unroll
     for (int it = 0; it < TAIL_NIT; ++it) {
@@ -120,24 +116,11 @@ __device__ __forceinline__ void conv_tail_epilogue(float16v (&acc)[2][5], const 
     const bool lane_on = rsub < 3;
     float gg[8], bb[8];
     if (a.y2 != nullptr) tail_gn_params(a, wn * 160 + chunk * 8, gg, bb);
-    // GroupNorm(16 channels x 64 squares) of t on the accumulators: the wave owns whole groups (as EPI 1)
-    float gv[NT], pv[NT];                                         // per-column scale and shift
+    // GroupNorm16 of t on the accumulators, as EPI_GN: per-column scale and shift
+    float gv[NT], pv[NT];
     static_for<0, NT>([&](auto ni_) __attribute__((always_inline)) {
         constexpr int ni = decltype(ni_)::value;
-        const int col = wn * 160 + ni * 32 + r31;
-        float s = 0.f, ss = 0.f;
-        static_for<0, 2>([&](auto mi_) __attribute__((always_inline)) {
-            const float16v av = acc[decltype(mi_)::value][ni];
-            static_for<0, 16>([&](auto r_) __attribute__((always_inline)) { const float v = av[decltype(r_)::value]; s += v; ss += v * v; });
-        });
-#pragma unroll
-        for (int o = 1; o <= 8; o <<= 1) { s += __shfl_xor(s, o); ss += __shfl_xor(ss, o); }
-        s += __shfl_xor(s, 32); ss += __shfl_xor(ss, 32);
-        const float mean = s * (1.f / 1024.f);
-        float var = ss * (1.f / 1024.f) - mean * mean;
-        var = var > 0.f ? var : 0.f;
-        gv[ni] = rsqrtf(var + 1e-5f) * a.pre_gamma[col];
-        pv[ni] = a.pre_beta[col] - mean * gv[ni];
+        conv_gn_column<ni>(acc, a.pre_gamma, a.pre_beta, wn * 160 + ni * 32 + r31, gv[ni], pv[ni]);
     });
 
     // act(t * scale + shift) -> the wave's fp16 image; the loads of x are issued between the tile columns, into the

@@ -60,7 +60,7 @@ constexpr int ZS_LDS_MAIN = ZS_OFF_D + 4096;          // 159,744 B
 __device__ unsigned long long* g_zs_stamp;      // [blocks][4]: s_memtime / s_memrealtime at main-loop start and end
 #endif
 
-template <int EPI, int ACT>
+template <ConvEpi EPI, int ACT>
 __global__ __launch_bounds__(512) void conv_zs_kernel(GemmArgs a) {
     constexpr int NG = 5, MT = 8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -228,7 +228,7 @@ __global__ __launch_bounds__(512) void conv_zs_kernel(GemmArgs a) {
                             constexpr int mi = decltype(mi_)::value;
                             // operand order = accumulator layout (conv_zs_epilogue.h): weights as A for the plain / GroupNorm epilogues
                             // (a lane gets 4 consecutive channels of a square), activations as A for the fused tail
-                            if constexpr (EPI == 3 || EPI == 5)
+                            if constexpr (EPI == EPI_TAIL || EPI == EPI_TAIL_PRE)
                                 acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[mi], fb[ni], acc[mi][ni], 0, 0, 0);
                             else
                                 acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb[ni], fa[mi], acc[mi][ni], 0, 0, 0);
@@ -256,8 +256,8 @@ __global__ __launch_bounds__(512) void conv_zs_kernel(GemmArgs a) {
     if (wp == 0) __builtin_amdgcn_s_barrier();          // matches group 1's extra barrier
     __builtin_amdgcn_s_barrier();                       // every wave's DMA has landed before anyone stages output (header)
 
-    if constexpr (EPI == 3) zs_tail_epilogue<ACT, false>(acc, a, smem, m0, wp, wn, wave, lane);
-    else if constexpr (EPI == 5) zs_tail_epilogue<ACT, true>(acc, a, smem, m0, wp, wn, wave, lane);
+    if constexpr (EPI == EPI_TAIL) zs_tail_epilogue<ACT, false>(acc, a, smem, m0, wp, wn, wave, lane);
+    else if constexpr (EPI == EPI_TAIL_PRE) zs_tail_epilogue<ACT, true>(acc, a, smem, m0, wp, wn, wave, lane);
     else zs_tile_epilogue<EPI, ACT>(acc, a, smem + wave * 20480, m0, n0, wp, wn, lane);
 #ifdef SW_STAMP     // timeline of the workgroup (10-ns ticks, wave 0) and where it ran: [blocks][4] behind the main-loop stamps
     if (tid == 0) {
@@ -269,7 +269,7 @@ __global__ __launch_bounds__(512) void conv_zs_kernel(GemmArgs a) {
 #endif
 }
 
-template <int EPI, int ACT>
+template <ConvEpi EPI, int ACT>
 static hipError_t launch_conv_zs_e(const GemmArgs& a, hipStream_t st) {
     const size_t lds = 160 * 1024;     // main loop 159,744 B; the epilogue stages the whole tile (8 x 20 KiB)
     static DeviceOnce once;             // the attribute is per device: a process may drive several GPUs (arena, tests)
@@ -294,18 +294,18 @@ hipError_t launch_conv_zs(const GemmArgs& a, hipStream_t st) {
         if (a.se_w1 != nullptr && (a.se_wf == nullptr || a.se_hidden < 1 || a.se_hidden > TAIL_SE_HMAX)) return hipErrorInvalidValue;
         if (a.pre_gamma != nullptr) {               // x += act(norm(conv(x))) (chess-feature conv) + next GroupNorm
             if (a.se_w1 != nullptr) return hipErrorInvalidValue;
-            if (a.epi_act == ACT_SILU) return launch_conv_zs_e<5, ACT_SILU>(a, st);
-            if (a.epi_act == ACT_RELU) return launch_conv_zs_e<5, ACT_RELU>(a, st);
+            if (a.epi_act == ACT_SILU) return launch_conv_zs_e<EPI_TAIL_PRE, ACT_SILU>(a, st);
+            if (a.epi_act == ACT_RELU) return launch_conv_zs_e<EPI_TAIL_PRE, ACT_RELU>(a, st);
             return hipErrorInvalidValue;
         }
-        if (a.epi_act == ACT_SILU) return launch_conv_zs_e<3, ACT_SILU>(a, st);
-        if (a.epi_act == ACT_RELU) return launch_conv_zs_e<3, ACT_RELU>(a, st);
+        if (a.epi_act == ACT_SILU) return launch_conv_zs_e<EPI_TAIL, ACT_SILU>(a, st);
+        if (a.epi_act == ACT_RELU) return launch_conv_zs_e<EPI_TAIL, ACT_RELU>(a, st);
         return hipErrorInvalidValue;
     }
     if (a.gn_gamma != nullptr) {                // conv1 of a block: GroupNorm + the network activation
-        if (a.epi_act == ACT_SILU) return launch_conv_zs_e<1, ACT_SILU>(a, st);
-        if (a.epi_act == ACT_RELU) return launch_conv_zs_e<1, ACT_RELU>(a, st);
+        if (a.epi_act == ACT_SILU) return launch_conv_zs_e<EPI_GN, ACT_SILU>(a, st);
+        if (a.epi_act == ACT_RELU) return launch_conv_zs_e<EPI_GN, ACT_RELU>(a, st);
         return hipErrorInvalidValue;
     }
-    return a.epi_act == ACT_NONE ? launch_conv_zs_e<0, ACT_NONE>(a, st) : hipErrorInvalidValue;
+    return a.epi_act == ACT_NONE ? launch_conv_zs_e<EPI_PLAIN, ACT_NONE>(a, st) : hipErrorInvalidValue;
 }

@@ -1,7 +1,7 @@
-// Output epilogues of conv_zs_kernel (conv_zs.hip): a wave holds TWO boards x 80 channels as 8 x 5 accumulator tiles of
-// v_mfma_f32_16x16x32_f16.  M-tile mi = board row y = mi of both boards (8 squares of board a, 8 of board b).  The MFMAs are
-// issued with the WEIGHT fragment as operand A and the activation fragment as operand B, so lane l = (c15 = l & 15, q = l >> 4)
-// holds, in register r of tile (mi, ni),
+// Output epilogues EPI_PLAIN and EPI_GN of conv_zs_kernel (conv_zs.hip; its tails: conv_zs_tail.h): a wave holds TWO boards x 80
+// channels as 8 x 5 accumulator tiles of v_mfma_f32_16x16x32_f16.  M-tile mi = board row y = mi of both boards (8 squares of
+// board a, 8 of board b).  The MFMAs are issued with the WEIGHT fragment as operand A and the activation fragment as operand
+// B, so lane l = (c15 = l & 15, q = l >> 4) holds, in register r of tile (mi, ni),
 //     board  c15 >> 3  (of the wave's pair),   square  8 mi + (c15 & 7),   channel  16 ni + 4 q + r  (of the wave's quarter):
 // four CONSECUTIVE channels of one square -- one 8-byte LDS write per tile and no cross-lane exchange (with the activations as
 // operand A a lane held four squares of one channel and neighbouring lanes had to swap values through DPP before every
@@ -90,10 +90,8 @@ __device__ __forceinline__ void zs_stage_flush(char* out, uint32_t ldo2, int row
     }
 }
 
-// EPI 0: bias / activation ACT / scale, fp16 store, per-(board, channel) sum and sum of squares.
-// EPI 1: GroupNorm(16 channels x 64 squares) + activation ACT in registers.
-// wp = board pair of the 4-board tile, wn = channel quarter.
-template <int EPI, int ACT>
+// EPI_PLAIN or EPI_GN (net_kernels.h; the tails are conv_zs_tail.h).  wp = board pair of the 4-board tile, wn = channel quarter.
+template <ConvEpi EPI, int ACT>
 __device__ __forceinline__ void zs_tile_epilogue(float4v (&acc)[8][5], const GemmArgs& a, char* img, int m0, int n0, int wp,
                                                  int wn, int lane) {
     const int c15 = lane & 15, q = lane >> 4;
@@ -101,7 +99,7 @@ __device__ __forceinline__ void zs_tile_epilogue(float4v (&acc)[8][5], const Gem
     char* wbase = zs_stage_base(img, lane);
     char* out = reinterpret_cast<char*>(a.out) + ((size_t)(m0 + wp * 128) * a.ldo + n0 + wn * 80) * 2;
     const int rows_valid = a.Mvalid - (m0 + wp * 128);
-    if constexpr (EPI == 1) {
+    if constexpr (EPI == EPI_GN) {
         // pass 1: statistics -> per-channel scale / shift.  Pass 2 goes board row by board row (M-tile mi = 8 squares of both
         // boards = 8 complete image rows): normalise + activate + stage the row's 5 tiles, then store that row -- the global
         // stores of row mi are in flight while the VALU works on row mi + 1.
@@ -114,15 +112,14 @@ __device__ __forceinline__ void zs_tile_epilogue(float4v (&acc)[8][5], const Gem
                 static_for<0, 4>([&](auto r_) __attribute__((always_inline)) { const float v = av[decltype(r_)::value]; s += v; ss += v * v; });
             });
             s = zs_sum_board(s); ss = zs_sum_board(ss);
-            const float mean = s * (1.f / 1024.f);
-            float var = ss * (1.f / 1024.f) - mean * mean;
-            var = var > 0.f ? var : 0.f;
-            const float rstd = rsqrtf(var + 1e-5f);
+            float mean, rstd;
+            gn16_mean_rstd(s, ss, mean, rstd);
             const float4 gm = *reinterpret_cast<const float4*>(a.gn_gamma + colbase + ni * 16);
             const float4 bt = *reinterpret_cast<const float4*>(a.gn_beta + colbase + ni * 16);
-            g[ni][0] = rstd * gm.x; g[ni][1] = rstd * gm.y; g[ni][2] = rstd * gm.z; g[ni][3] = rstd * gm.w;
-            sh[ni][0] = bt.x - mean * g[ni][0]; sh[ni][1] = bt.y - mean * g[ni][1];
-            sh[ni][2] = bt.z - mean * g[ni][2]; sh[ni][3] = bt.w - mean * g[ni][3];
+            gn16_affine(mean, rstd, gm.x, bt.x, g[ni][0], sh[ni][0]);
+            gn16_affine(mean, rstd, gm.y, bt.y, g[ni][1], sh[ni][1]);
+            gn16_affine(mean, rstd, gm.z, bt.z, g[ni][2], sh[ni][2]);
+            gn16_affine(mean, rstd, gm.w, bt.w, g[ni][3], sh[ni][3]);
         });
         const uint32_t ldo2 = (uint32_t)a.ldo * 2u;
         // row mi of the image = 8 squares x 20 chunks = 160 16-byte units: lanes 0..63 take units lane, 64 + lane and (lanes < 32)
@@ -153,7 +150,7 @@ __device__ __forceinline__ void zs_tile_epilogue(float4v (&acc)[8][5], const Gem
             }
         });
     }
-    if constexpr (EPI == 0) {
+    if constexpr (EPI == EPI_PLAIN) {
         const float oscale = a.out_scale;
         const bool want_stats = a.out_stats != nullptr;
         float* stats = a.out_stats + ((size_t)(m0 / 64 + 2 * wp + (c15 >> 3)) * a.N + colbase) * 2;

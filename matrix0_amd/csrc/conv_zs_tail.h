@@ -1,5 +1,5 @@
-// Residual-block tail fused into conv2's epilogue, for conv_zs_kernel's accumulator layout (conv_zs_epilogue.h; the
-// arithmetic is conv_tail.h's):
+// Residual-block tail fused into conv2's epilogue (EPI_TAIL; PRE = EPI_TAIL_PRE), for conv_zs_kernel's accumulator layout
+// (conv_zs_epilogue.h; the arithmetic is conv_tail.h's):
 //   t      = conv2 output (the workgroup holds 4 whole boards x all 320 channels in its accumulators)
 //   gate   = sigmoid(W2 act(W1 mean_squares(t) + b1) + b2)            squeeze-excite, resnet.py:59-68 (optional)
 //   y      = x + gate * t                                             the residual stream          -> a.out
@@ -155,11 +155,9 @@ __device__ __forceinline__ void zs_tail_epilogue(float4v (&acc)[8][5], const Gem
                 static_for<0, 4>([&](auto r_) __attribute__((always_inline)) { const float v = av[decltype(r_)::value]; s += v; ss += v * v; });
             });
             s = zsa_sum_board(s); ss = zsa_sum_board(ss);
-            const float mean = s * (1.f / 1024.f);
-            float var = ss * (1.f / 1024.f) - mean * mean;
-            var = var > 0.f ? var : 0.f;
-            gv[ni] = rsqrtf(var + 1e-5f) * a.pre_gamma[col];
-            pv[ni] = a.pre_beta[col] - mean * gv[ni];
+            float mean, rstd;
+            gn16_mean_rstd(s, ss, mean, rstd);
+            gn16_affine(mean, rstd, a.pre_gamma[col], a.pre_beta[col], gv[ni], pv[ni]);
         });
     }
 

@@ -50,6 +50,12 @@ __device__ __forceinline__ void static_for(F&& f) {
     }
 }
 
+// 8 consecutive floats (16-byte aligned) as two 16-byte loads
+__device__ __forceinline__ void load8f(const float* p, float (&v)[8]) {
+    const float4 lo = *reinterpret_cast<const float4*>(p), hi = *reinterpret_cast<const float4*>(p + 4);
+    v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
+}
+
 __device__ __forceinline__ float act_apply(float v, int act) {
     switch (act) {
         case ACT_RELU: return v > 0.f ? v : 0.f;

@@ -6,21 +6,25 @@
 // per-(board, channel) statistics, then ew_board_kernel.  Every "conv -> GroupNorm + act" step goes through conv_norm_act, which
 // picks the form; Plan (net.h) holds the choices that do not depend on the step.
 //
+// Kernels: conv_gemm_kernel<taps> (conv_gemm.hip, small tile), conv_big_kernel (conv_big.hip, 1x1, N % 320 == 0), conv_zs_kernel
+// (conv_zs.hip, 3x3, N % 320 == 0), attn_block_kernel / attn_core_kernel (attn_*.hip), the rest net_kernels.hip.  EPI_* is the
+// conv's epilogue kind (ConvEpi, net_kernels.h); "conv" alone is the raw conv with statistics (EPI_PLAIN, small tile EPI_ELEMENT).
+//
 //   step                                   fused                                            unfused
 //   input planes -> NHWC fp16              planes_to_nhwc (skipped when the engine encoded into X0_)
-//   stem + positional encoding             conv_gemm_kernel<9> GN epilogue (trunk % 64 == 0) conv_gemm_kernel<9> + ew_board
+//   stem + positional encoding             conv_gemm_kernel<9> EPI_GN (trunk % 64 == 0)     conv_gemm_kernel<9> + ew_board
 //   stem without chess features            --                                               conv_gemm_kernel<9> + ew_board (+ next bn1)
-//   piece-square-table 1x1 + residual      conv_big_kernel, pre_gamma tail                  conv + ew_board
-//   interaction 3x3 + residual + next bn1  conv_zs_kernel, pre_gamma tail                   conv + ew_board
-//   block conv1 + bn2                      conv_zs_kernel GN epilogue                       conv_gemm_kernel<9> + ew_board
-//   block conv2 + SE + residual + next bn1 conv_zs_kernel tail (conv_zs_tail.h)             conv + se_gate + ew_board
+//   piece-square-table 1x1 + residual      conv_big_kernel EPI_TAIL_PRE (conv_tail.h)       conv + ew_board
+//   interaction 3x3 + residual + next bn1  conv_zs_kernel EPI_TAIL_PRE (conv_zs_tail.h)     conv + ew_board
+//   block conv1 + bn2                      conv_zs_kernel EPI_GN                            conv_gemm_kernel<9> + ew_board
+//   block conv2 + SE + residual + next bn1 conv_zs_kernel EPI_TAIL (conv_zs_tail.h)         conv + se_gate + ew_board
 //   attention block                        attn_block_kernel                                qkv GEMM + attn_core + proj GEMM + ew_board
-//   policy_head.0 and value_head.0         one conv_gemm_kernel<1>, N = 64 + 128, two outputs  two convs, each + ew_board
-//   policy FCs                             conv_gemm_kernel<1> (bias, ReLU; f32 logits * logit scale)
-//   value_head.3                           conv_gemm_kernel<1> GN epilogue                  conv + ew_board
+//   policy_head.0 and value_head.0         one conv_gemm_kernel<1> EPI_GN, N = 64 + 128, two outputs  two convs, each + ew_board
+//   policy FCs                             conv_gemm_kernel<1> EPI_ELEMENT (bias, ReLU; f32 logits * logit scale)
+//   value_head.3                           conv_gemm_kernel<1> EPI_GN                       conv + ew_board
 //   value_fc1                              conv_big_kernel split-K + splitk_reduce (widths 160, 320), else conv_gemm_kernel<1>
-//   value_fc2, gate, fc3                   conv_gemm_kernel<1>
-//   SSL head: conv + GN, conv, transpose   conv_gemm_kernel<1> GN epilogue (N in 32/64/128/160), conv, nhwc_to_nchw_f32
+//   value_fc2, gate, fc3                   conv_gemm_kernel<1> EPI_ELEMENT
+//   SSL head: conv + GN, conv, transpose   conv_gemm_kernel<1> EPI_GN (N in 32/64/128/160), conv, nhwc_to_nchw_f32
 #include "net.h"
 #include "attn_math.h"
 #include <math.h>

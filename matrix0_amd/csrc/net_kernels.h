@@ -1,9 +1,24 @@
-// Launch interfaces of the network kernels (net_kernels.hip).
+// Launch interfaces of the network kernels (conv_gemm.hip, conv_big.hip, conv_zs.hip, attn_core.hip, attn_block.hip,
+// net_kernels.hip), which replace the reference's torch forward (azchess/model/resnet.py:656-760) on the self-play hot path.
+// Data layout in HBM: every activation is "NHWC" [board][64 squares][C] fp16, square n = row*8+col of the reference tensor
+// (row 0 = rank 8).  A board's 64 squares are the 64 rows of one wave's MFMA tile, so every per-board reduction (GroupNorm
+// statistics, SE pooling) is wave-local.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2, ACT_LEAKY = 3, ACT_SIGMOID = 4, ACT_TANH = 5 };
+
+// What a conv kernel does between its accumulators and HBM: the template parameter of conv_gemm_kernel, conv_big_kernel,
+// conv_zs_kernel and of their epilogues (conv_epilogue.h, conv_tail.h, conv_zs_epilogue.h, conv_zs_tail.h), so that each
+// kind gets its own register allocation.  A kernel instantiates the kinds its launcher names, not all of them.
+enum ConvEpi {
+    EPI_PLAIN,       // bias / activation ACT / scale, fp16 through the LDS staging image, per-(board, channel) sums
+    EPI_GN,          // act(GroupNorm16(conv)) [+ positional encoding] on the accumulators, fp16 through the staging image
+    EPI_ELEMENT,     // bias / runtime activation a.epi_act / gate multiply / scale, fp16 or f32 stored per element, sums
+    EPI_TAIL,        // residual-block tail: out = res + gate * conv (squeeze-excite), y2 = act(GroupNorm16(out))
+    EPI_TAIL_PRE,    // block tail in PRE form: out = res + act(GroupNorm16(conv)), y2 likewise (chess-feature convs)
+};
 
 // Most squeeze-excite hidden units the fused residual-block tail takes (conv_zs_tail.h; its LDS holds 60 + 60 weight
 // pieces).  A network with a wider squeeze-excite runs conv2, se_gate_kernel and ew_board_kernel instead (net.hip).
@@ -42,7 +57,7 @@ struct GemmArgs {
     const float* se_b2;
     int se_hidden;           // at most TAIL_SE_HMAX
     const void* se_wf;       // conv_zs_kernel's tail: W1 and W2 as fp16 MFMA B-fragment pieces of 1 KiB (conv_zs_tail.h; net.hip packs)
-    // small tile with gn_gamma != null (conv_gemm_kernel, EPI 1): out = epi_act(GroupNorm16(conv)) [+ posenc], fp16, through the
+    // small tile with gn_gamma != null (conv_gemm_kernel, EPI_GN): out = epi_act(GroupNorm16(conv)) [+ posenc], fp16, through the
     // LDS-staged 16-byte-store epilogue.  Two consumers of one input in ONE launch (policy-head and value-head 1x1 convs over the
     // trunk): columns >= nsplit go to out2 (row stride ldo2, column - nsplit); gn_gamma / gn_beta cover all N columns.
     const float* posenc;     // [64 squares][N] f32 added after the activation (stem), or null

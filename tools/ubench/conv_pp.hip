@@ -71,7 +71,7 @@ __device__ unsigned long long* g_pp_trace;
 __device__ unsigned long long* g_pp_stamp;      // [blocks][4]: s_memtime / s_memrealtime at main-loop start and end
 #endif
 
-template <int EPI, int ACT>
+template <ConvEpi EPI, int ACT>
 __global__ __launch_bounds__(512) void conv_pp_kernel(GemmArgs a) {
     constexpr int NT = 5;
     constexpr int A_BYTES = 256 * 128;    // 4 boards x 64 squares x 64 channels fp16, 128-byte rows
@@ -416,7 +416,7 @@ __global__ __launch_bounds__(512) void conv_pp_kernel(GemmArgs a) {
 #endif
 }
 
-template <int EPI, int ACT>
+template <ConvEpi EPI, int ACT>
 static hipError_t launch_conv_pp_e(const GemmArgs& a, hipStream_t st) {
     const size_t lds = 160 * 1024;     // main loop 151,680 B; the epilogue stages the whole 256 x 320 fp16 tile
     static bool attr_set = false;
@@ -439,9 +439,9 @@ hipError_t launch_conv_pp(const GemmArgs& a, hipStream_t st) {
     // the fused block tail of this layout went with conv_tail.h's squeeze-excite form: conv_zs has its own (conv_zs_tail.h)
     if (a.res != nullptr) return hipErrorInvalidValue;
     if (a.gn_gamma != nullptr) {                // conv1 of a block: GroupNorm + the network activation
-        if (a.epi_act == ACT_SILU) return launch_conv_pp_e<1, ACT_SILU>(a, st);
-        if (a.epi_act == ACT_RELU) return launch_conv_pp_e<1, ACT_RELU>(a, st);
+        if (a.epi_act == ACT_SILU) return launch_conv_pp_e<EPI_GN, ACT_SILU>(a, st);
+        if (a.epi_act == ACT_RELU) return launch_conv_pp_e<EPI_GN, ACT_RELU>(a, st);
         return hipErrorInvalidValue;
     }
-    return a.epi_act == ACT_NONE ? launch_conv_pp_e<0, ACT_NONE>(a, st) : hipErrorInvalidValue;
+    return a.epi_act == ACT_NONE ? launch_conv_pp_e<EPI_PLAIN, ACT_NONE>(a, st) : hipErrorInvalidValue;
 }

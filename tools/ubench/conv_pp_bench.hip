@@ -43,7 +43,7 @@ int main(int argc, char** argv) {
     GemmArgs a{};
     a.in = din; a.w = dw; a.out = dout; a.out_stats = dstats; a.Mrows = M; a.Mvalid = M; a.Cin = C; a.N = C; a.Npad = C;
     a.ldo = C; a.out_scale = 1.f; a.w_pp = 1;
-#if defined(BENCH_GN)   // conv1: GroupNorm + SiLU epilogue (EPI 1)
+#if defined(BENCH_GN)   // conv1: GroupNorm + SiLU epilogue (EPI_GN)
     {
         std::vector<float> gam(C, 1.f), bet(C, 0.f), tbl((size_t)boards * C * 2);
         for (size_t i = 0; i < tbl.size(); i += 2) { tbl[i] = 1.f + rnd() * 0.2f; tbl[i + 1] = rnd() * 0.2f; }
@@ -58,7 +58,7 @@ int main(int argc, char** argv) {
 #if defined(BENCH_TAIL) && !defined(BENCH_ZS)
 #error "BENCH_TAIL needs BENCH_ZS (conv_pp_kernel has no fused tail)"
 #endif
-#ifdef BENCH_TAIL   // conv2 with the residual-block tail fused (EPI 3): x, squeeze-excite weights, next GroupNorm, y2
+#ifdef BENCH_TAIL   // conv2 with the residual-block tail fused (EPI_TAIL): x, squeeze-excite weights, next GroupNorm, y2
     {
         const int Hd = 80;
         std::vector<float> w1((size_t)C * Hd), w2((size_t)Hd * C), b1(Hd, 0.01f), b2(C, 0.02f), gam(C, 1.f), bet(C, 0.f);

@@ -37,7 +37,7 @@ __device__ __forceinline__ void sw_mfma(float16v& c, const half8& x, const half8
 __device__ unsigned long long* g_sw_stamp;      // [blocks][4]: s_memtime / s_memrealtime at main-loop start and end
 #endif
 
-template <int EPI, int ACT>
+template <ConvEpi EPI, int ACT>
 __global__ __launch_bounds__(256) void conv_sw_kernel(GemmArgs a) {
     constexpr int NT = 5, MT = 4;
     constexpr int A_BYTES = 256 * 128;    // 4 boards x 64 squares x 64 channels fp16, 128-byte rows
@@ -258,7 +258,7 @@ __global__ __launch_bounds__(256) void conv_sw_kernel(GemmArgs a) {
 #endif
 }
 
-template <int EPI, int ACT>
+template <ConvEpi EPI, int ACT>
 static hipError_t launch_conv_sw_e(const GemmArgs& a, hipStream_t st) {
     static bool attr_set = false;
     if (!attr_set) {
@@ -276,9 +276,9 @@ hipError_t launch_conv_sw(const GemmArgs& a, hipStream_t st) {
     if (a.Cin % 64 != 0 || a.Npad % 320 != 0 || a.Mrows % 256 != 0 || a.Cin < 128) return hipErrorInvalidValue;
     if (a.res != nullptr || a.mul != nullptr || a.out_f32 != 0) return hipErrorInvalidValue;
     if (a.gn_gamma != nullptr) {
-        if (a.epi_act == ACT_SILU) return launch_conv_sw_e<1, ACT_SILU>(a, st);
-        if (a.epi_act == ACT_RELU) return launch_conv_sw_e<1, ACT_RELU>(a, st);
+        if (a.epi_act == ACT_SILU) return launch_conv_sw_e<EPI_GN, ACT_SILU>(a, st);
+        if (a.epi_act == ACT_RELU) return launch_conv_sw_e<EPI_GN, ACT_RELU>(a, st);
         return hipErrorInvalidValue;
     }
-    return a.epi_act == ACT_NONE ? launch_conv_sw_e<0, ACT_NONE>(a, st) : hipErrorInvalidValue;
+    return a.epi_act == ACT_NONE ? launch_conv_sw_e<EPI_PLAIN, ACT_NONE>(a, st) : hipErrorInvalidValue;
 }

@@ -37,7 +37,7 @@ __device__ unsigned long long* g_z2_stamp;
 #endif
 __device__ int g_z2_delay = 0;          // 10-ns ticks
 
-template <int EPI, int ACT>
+template <ConvEpi EPI, int ACT>
 __global__ __launch_bounds__(256, 2) void conv_z2_kernel(GemmArgs a) {
     constexpr int NG = 5, MT = 8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256, 2) void conv_z2_kernel(GemmArgs a) {
                         constexpr int ni = decltype(ni_)::value;
                         static_for<LO, HI>([&](auto mi_) __attribute__((always_inline)) {
                             constexpr int mi = decltype(mi_)::value;
-                            if constexpr (EPI == 3 || EPI == 5)
+                            if constexpr (EPI == EPI_TAIL || EPI == EPI_TAIL_PRE)
                                 acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[mi], fb[ni], acc[mi][ni], 0, 0, 0);
                             else
                                 acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb[ni], fa[mi], acc[mi][ni], 0, 0, 0);
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(256, 2) void conv_z2_kernel(GemmArgs a) {
 #endif
 }
 
-template <int EPI, int ACT>
+template <ConvEpi EPI, int ACT>
 static hipError_t launch_conv_z2_e(const GemmArgs& a, hipStream_t st) {
     static bool attr_set = false;
     if (!attr_set) {
@@ -228,8 +228,8 @@ hipError_t launch_conv_z2(const GemmArgs& a, hipStream_t st) {
     if (a.mul != nullptr || a.out_f32 != 0 || a.res != nullptr) return hipErrorInvalidValue;
     if ((size_t)a.Mrows * a.ldo * 2 >= ((size_t)1 << 32)) return hipErrorInvalidValue;
     if (a.gn_gamma != nullptr) {
-        if (a.epi_act == ACT_SILU) return launch_conv_z2_e<1, ACT_SILU>(a, st);
+        if (a.epi_act == ACT_SILU) return launch_conv_z2_e<EPI_GN, ACT_SILU>(a, st);
         return hipErrorInvalidValue;
     }
-    return a.epi_act == ACT_NONE ? launch_conv_z2_e<0, ACT_NONE>(a, st) : hipErrorInvalidValue;
+    return a.epi_act == ACT_NONE ? launch_conv_z2_e<EPI_PLAIN, ACT_NONE>(a, st) : hipErrorInvalidValue;
 }
