@@ -458,6 +458,44 @@ double m0_temperature_for(int fullmove_number, double t_start, double t_end, int
  * bit8 can_claim_threefold, bit9 fivefold, bit10 seventyfive ; result = game_result(board) */
 int m0_rules_probe(const m0_selfplay_cfg* cfg, const char* fen, const char* const* ucis, int n, int* flags, float* result);
 
+/* ---- reading games back in: written moves -> training positions (replaces the python-chess loop of the reference's
+ * azchess/tools/process_lichess.py:59-106, and also yields the legal masks its backfill_legal_masks.py adds afterwards) ----
+ * A written move becomes a 32-bit pattern without looking at a position (bit layout and matching rule: csrc/san_match.h); a
+ * game is an array of patterns, replayed on the device with the engine's own move generator, one wave per game. */
+/* One SAN token -> pattern, as python-chess's SAN reader takes it: trailing '!' / '?' and one '+' or '#' dropped; O-O / O-O-O
+ * (also written with zeros); [NBRQK]? [a-h]? [1-8]? [-x]? <square> (=?[NBRQ])?.  M0_ERR_INVALID (pattern 0, which matches no
+ * move) for anything else, the null moves "--" and "Z0" included.  Host only, no GPU. */
+int m0_san_pattern(const char* token, uint32_t* pattern);
+/* An exact move -> pattern.  The caller names what it passes ("b1c3" is also a well-formed SAN pawn token): kind M0_MOVE_UCI
+ * reads `uci` ("e2e4", "e7e8q"), kind M0_MOVE_RAW reads `raw` = from | to<<6 | promo<<12 (promo 0 none, 1 N, 2 B, 3 R, 4 Q: an
+ * engine record's `played`).  Host only. */
+#define M0_MOVE_UCI 0
+#define M0_MOVE_RAW 1
+int m0_move_pattern(int kind, const char* uci, uint32_t raw, uint32_t* pattern);
+/* per-game status */
+#define M0_REPLAY_OK 0         /* every token resolved to exactly one legal move */
+#define M0_REPLAY_ILLEGAL 1    /* the token at index plies[g] fits no legal move (or did not parse) */
+#define M0_REPLAY_AMBIGUOUS 2  /* it fits more than one */
+#define M0_REPLAY_TOO_LONG 3   /* the game has more than max_plies tokens; its first max_plies are resolved */
+/* per-game end flags: the position after the last resolved move */
+#define M0_REPLAY_END_CHECKMATE 1
+#define M0_REPLAY_END_STALEMATE 2
+#define M0_REPLAY_END_INSUFFICIENT 4
+#define M0_REPLAY_END_WHITE_TO_MOVE 8
+/* Replays n_games games.  Game g starts from start_fens[g] (start_fens or an entry NULL: the initial position) and owns rows
+ * offsets[g] .. offsets[g+1] of `patterns` and of every per-ply output (offsets[0] = 0).  It resolves its tokens in order and
+ * stops at the first that does not resolve to exactly one legal move, or after max_plies: plies[g] rows are written and the
+ * rest of its rows are zero.  Per ply k, for the position BEFORE the move: moves (as M0_MOVE_RAW), policy_idx (move_to_index),
+ * nlegal, turn (1 White), planes f32 [19][8][8], mask u8 [4672], ssl f32 [17][8][8] (piece 13, threat, pin, fork, control); each
+ * per-ply output may be NULL.  plies, status and end_flags are required.
+ * The work is issued in launches of whole games holding at most max_positions_per_launch rows (<= 0: one launch; a game longer
+ * than the limit goes alone), which bounds device and staging memory at about 9.5 KB per row for planes and mask; the results
+ * do not depend on that number or on the order of the games.  A bad start FEN is M0_ERR_INVALID for the whole call and the
+ * message names the game index.  M0_ERR_HIP without a HIP device: there is no CPU path. */
+int m0_replay_games(int hip_device, const char* const* start_fens, const uint32_t* patterns, const int32_t* offsets, int n_games,
+                    int max_plies, int max_positions_per_launch, int32_t* plies, int32_t* status, int32_t* end_flags,
+                    uint16_t* moves, int32_t* policy_idx, int32_t* nlegal, int8_t* turn, float* planes, uint8_t* mask, float* ssl);
+
 #ifdef __cplusplus
 }
 #endif

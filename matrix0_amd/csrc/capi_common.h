@@ -16,3 +16,15 @@ void m0_net_unlock(m0_net* n);
 // A non-blocking stream; when the environment variable env_name holds w0,w1,...,w7 (hex words, bit b = CU b in the driver's
 // numbering) the stream runs on those CUs only (hipExtStreamCreateWithCUMask).  Measurement switch; read at every call.
 hipError_t create_stream_cu_mask_env(const char* env_name, hipStream_t* stream);
+
+// device memory for the length of one call
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    DevBuf() {}
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    bool alloc(size_t count) { return hipMalloc((void**)&p, count * sizeof(T)) == hipSuccess; }
+    void download(T* host, size_t count) const { (void)hipMemcpy(host, p, count * sizeof(T), hipMemcpyDeviceToHost); }
+};

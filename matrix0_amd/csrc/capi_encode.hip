@@ -13,18 +13,6 @@ using namespace m0;
 
 namespace {
 
-// device memory for the length of one call
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    DevBuf() {}
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    bool alloc(size_t count) { return hipMalloc((void**)&p, count * sizeof(T)) == hipSuccess; }
-    void download(T* host, size_t count) const { (void)hipMemcpy(host, p, count * sizeof(T), hipMemcpyDeviceToHost); }
-};
-
 // selects the device, parses the n FENs and puts the positions on it
 int upload_fens(int hip_device, const char* const* fens, int n, DevBuf<Pos>& dp) {
     int ndev = 0;

@@ -201,3 +201,12 @@ hipError_t launch_policy_lines(const float* logits_dev, const float* values_dev,
 
 // SSL training targets for recorded positions: out f32 [n][17][64] (piece 13, threat, pin, fork, control)
 hipError_t launch_ssl_targets(const m0::Pos* pos_dev, int n, float* out_dev, hipStream_t st);
+
+// Replay of written games (replay_kernels.hip, patterns: san_match.h), one wave per game.  Game g owns rows offsets[g] ..
+// offsets[g+1] of patterns and of the per-ply outputs and writes the first plies[g] of them: the position before each resolved
+// move (input of launch_encode_positions / launch_ssl_targets), the move, its policy index, the legal-move count and the side
+// to move.  status: REPLAY_*; end_flags: REPLAY_END_* of the position after the last resolved move.
+hipError_t launch_replay_games(const m0::Pos* start_dev, const uint32_t* patterns_dev, const int32_t* offsets_dev /*[n_games+1]*/,
+                               int n_games, int max_plies, m0::Pos* pos_dev, uint16_t* moves_dev, int32_t* policy_idx_dev,
+                               int32_t* nlegal_dev, int8_t* turn_dev, int32_t* plies_dev, int32_t* status_dev,
+                               int32_t* end_flags_dev, hipStream_t st);
