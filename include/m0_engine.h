@@ -385,6 +385,48 @@ int m0_analysis_poll(m0_selfplay* sp, m0_analysis_result* out);   /* 1 written, 
 int m0_analysis_pending(m0_selfplay* sp);                         /* queued + in flight (answered ones not counted) */
 size_t m0_analysis_result_size(void);                             /* sizeof(m0_analysis_result), for foreign mirrors */
 
+/* ---- stored training rows back to positions (the inverse of encode_board; csrc/planes_decode.h says what the planes hold) ----
+ * Per row a status: 0 or the FIRST of these reasons, in this order. */
+#define M0_DECODE_OK 0
+#define M0_DECODE_PIECE_VALUE 1         /* a piece-plane value that is not exactly 0.0f or 1.0f (NaN included) */
+#define M0_DECODE_SQUARE_CLASH 2        /* two men on one square */
+#define M0_DECODE_KINGS 3               /* a side without exactly one king */
+#define M0_DECODE_PAWN_RANK 4           /* a pawn on rank 1 or 8 */
+#define M0_DECODE_NOT_UNIFORM 5         /* one of the seven constant planes varies over the board */
+#define M0_DECODE_FLAG_VALUE 6          /* the turn plane or a castling plane is neither 0 nor 1 */
+#define M0_DECODE_CASTLING 7            /* a castling plane set without king and rook on their original squares */
+#define M0_DECODE_COUNTER 8             /* a counter plane that is no float32(k / 99.0) resp. float32(k / 199.0) */
+#define M0_DECODE_OPPONENT_IN_CHECK 9   /* the side NOT to move is in check */
+#define M0_DECODE_TOO_MANY_MOVES 10     /* more pseudo-legal moves than a move list holds (256): no reachable position */
+#define M0_DECODE_MASK_MISMATCH 11      /* with a mask: it differs from the legal moves of the decoded position (the audit of
+                                           the reference's audit_legal_masks.py); the position and nlegal are still written */
+/* per row flags: information, not errors */
+#define M0_DECODE_HALFMOVE_SATURATED 1  /* half-move plane exactly 1.0: the clock was 99 OR MORE, the position carries 99 */
+#define M0_DECODE_FULLMOVE_SATURATED 2  /* full-move plane exactly 1.0: 199 or more */
+#define M0_DECODE_EP_FROM_MASK 4        /* the en-passant square was recovered from the mask */
+#define M0_DECODE_NO_MASK 8             /* no mask given: en passant is unknown and set to none */
+/* planes f32 [n,19,8,8]; mask u8 [n,4672] or NULL; outputs nullable: status / flags / nlegal i32 [n]; fens n strings of
+ * fen_stride bytes each (>= 96), Board.fen() of the decoded position as m0_fen_after writes it, empty for a row whose status
+ * leaves no position (every status but OK and MASK_MISMATCH).  One wave per row on the device; M0_ERR_HIP without one. */
+int m0_decode_planes(int hip_device, const float* planes, const uint8_t* mask, int n, int32_t* status, int32_t* flags,
+                     int32_t* nlegal, char* fens, int fen_stride);
+/* The same rows into an analysis engine: decoded on the engine's device and stream, and every row of status 0 queued as
+ * m0_analysis_submit queues its FEN (ids[i], or i when ids is NULL; sims = 0: policy mode), with an empty repetition window
+ * and without a FEN round trip: the result is bit for bit that of m0_analysis_submit(fen of the row, no moves, sims, id).
+ * Rows of another status are reported in status[] (required) and not queued: nothing is answered for them.  Roots without
+ * legal moves and, with tables attached, roots inside them are answered at once, as m0_analysis_submit does.  flags nullable. */
+int m0_analysis_submit_planes(m0_selfplay* sp, const float* planes, const uint8_t* mask, int n, int sims, const int64_t* ids,
+                              int32_t* status, int32_t* flags);
+/* Policy targets need every root child, not the 8 best: with keeping on, each harvest also gathers (policy index, visits)
+ * of every root child of the finished searches, in move-generation order, and m0_analysis_poll_visits hands them out with the
+ * result.  Off (the default) nothing extra is launched or copied and nchild is 0. */
+int m0_analysis_keep_visits(m0_selfplay* sp, int on);
+/* m0_analysis_poll plus the root's children: nchild, policy_idx[nchild], visits[nchild].  cap = entries of the two arrays,
+ * at least 256 (M0_ERR_INVALID otherwise).  nchild = 0 for results answered on the host (mate, stalemate, tablebases), for
+ * policy-mode results and for searches harvested while keeping was off. */
+int m0_analysis_poll_visits(m0_selfplay* sp, m0_analysis_result* out, int32_t* nchild, int32_t* policy_idx, int32_t* visits,
+                            int cap);
+
 /* ---- generated 3- and 4-man endgame tablebases (the reference's tablebases.enabled: selfplay/internal.py:250-260, 559-581) ----
  * The reference ends a self-play game as soon as the position after a move is found in a Syzygy table and takes the sign of
  * its WDL as the result.  Here the tables are computed instead of read: distance-to-mate tables by retrograde analysis on the

@@ -1,6 +1,7 @@
 // Result kernels of the analysis engine (capi_analysis.hip), one wavefront each:
 //   analysis_lines_kernel  (finished slot, line l): the root child of rank l by visits and the principal variation behind it.
 //   policy_lines_kernel    (batch row): legal-softmax priors of a position that is not searched, the best of them by prior.
+//   root_children_kernel   (finished slot): every root child's policy index and visits, for policy targets (keep_visits).
 // A node's children are one contiguous block, child i = lane + 64 k (CPL per lane): ranks are counted per lane from values
 // passed round the wave, the arg-max of a level is a wave reduction.  No atomics, no LDS.
 #include "tree_device.h"
@@ -88,6 +89,28 @@ hipError_t launch_analysis_lines(const TreeDev& d, const int* slots_dev, int cou
                                  m0_analysis_line* lines_dev, int* nlines_dev, hipStream_t st) {
     if (count <= 0) return hipSuccess;
     hipLaunchKernelGGL(analysis_lines_kernel, dim3(count, multipv), dim3(64), 0, st, d, slots_dev, multipv, pv_len, lines_dev, nlines_dev);
+    return hipGetLastError();
+}
+
+// A finished search already holds its root children on the device in the slot's RootResult (expand_kernel writes it with
+// the `finished` flag): the two columns a policy target needs, compact, one entry per finished slot.
+__global__ __launch_bounds__(64) void root_children_kernel(TreeDev d, const int* slots, int32_t* policy_idx, int32_t* visits,
+                                                           int32_t* nchild) {
+    const int j = blockIdx.x, lane = threadIdx.x;
+    const RootResult* R = d.results + slots[j];
+    int k = R->nchild;
+    k = k < 0 ? 0 : (k > M0_MAX_CHILDREN ? M0_MAX_CHILDREN : k);
+    for (int i = lane; i < M0_MAX_CHILDREN; i += 64) {
+        policy_idx[(size_t)j * M0_MAX_CHILDREN + i] = i < k ? (int32_t)R->child_idx[i] : 0;
+        visits[(size_t)j * M0_MAX_CHILDREN + i] = i < k ? R->child_n[i] : 0;
+    }
+    if (lane == 0) nchild[j] = k;
+}
+
+hipError_t launch_root_children(const TreeDev& d, const int* slots_dev, int count, int32_t* policy_idx_dev, int32_t* visits_dev,
+                                int32_t* nchild_dev, hipStream_t st) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(root_children_kernel, dim3(count), dim3(64), 0, st, d, slots_dev, policy_idx_dev, visits_dev, nchild_dev);
     return hipGetLastError();
 }
 

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <memory>
 #include "selfplay_engine.h"
+#include "planes_decode.h"
 #include "tb.h"
 
 using namespace m0;
@@ -25,6 +26,31 @@ static m0_analysis_result blank_result(const AnalysisJob& job) {
     memset(&r, 0, sizeof(r));
     r.id = job.id; r.nlegal = job.nlegal; r.sims = job.sims;
     return r;
+}
+
+// A result joins the answered ones with its root children ((policy index, visits) pairs, empty unless a harvest kept them).
+static void answer(Analysis& a, const m0_analysis_result& r, std::vector<int32_t>&& children = std::vector<int32_t>()) {
+    a.done.push_back(r);
+    a.done_children.push_back(std::move(children));
+}
+
+// What m0_analysis_submit does with a position once it stands in job.line and job.nlegal is known: roots without legal moves
+// and roots inside the attached tables are answered here, on the host; every other one waits for a slot (or a policy pass).
+static void queue_job(m0_selfplay* sp, AnalysisJob&& job) {
+    if (job.nlegal == 0) {                 // no search, no evaluation, no slot
+        m0_analysis_result r = blank_result(job);
+        r.status = in_check(job.line.pos) ? 1 : 2;
+        answer(*sp->an, r);
+        return;
+    }
+    if (sp->tb) {                          // a root inside the attached tables: answered from them, as the two cases above
+        m0_analysis_result r = blank_result(job);
+        if (tb_root_lines(sp->tb, sp->tb_max_pieces, job.line.pos, sp->an->opts.multipv, sp->an->opts.pv_len, &r)) {
+            answer(*sp->an, r);
+            return;
+        }
+    }
+    (job.sims == 0 ? sp->an->policy_queue : sp->an->queue).push_back(std::move(job));
 }
 
 // entry j of what a result kernel wrote (hlines / hnlines) -> the lines of r
@@ -61,6 +87,11 @@ int analysis_harvest(m0_selfplay* sp) {
         launch_analysis_lines(sp->d, sp->ids_dev, nf, a.opts.multipv, a.opts.pv_len, a.lines_dev, a.nlines_dev, sp->stream) != hipSuccess ||
         hipMemcpyAsync(a.hlines.data(), a.lines_dev, sizeof(m0_analysis_line) * M0_AN_MAX_LINES * nf, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
         hipMemcpyAsync(a.hnlines.data(), a.nlines_dev, (size_t)nf * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
+        (a.keep_visits &&          // the root children of the same searches, in the same trip
+         (launch_root_children(sp->d, sp->ids_dev, nf, a.child_idx_dev, a.child_n_dev, a.nchild_dev, sp->stream) != hipSuccess ||
+          hipMemcpyAsync(a.hchild_idx.data(), a.child_idx_dev, (size_t)nf * M0_MAX_CHILDREN * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
+          hipMemcpyAsync(a.hchild_n.data(), a.child_n_dev, (size_t)nf * M0_MAX_CHILDREN * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
+          hipMemcpyAsync(a.hnchild.data(), a.nchild_dev, (size_t)nf * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess)) ||
         hipStreamSynchronize(sp->stream) != hipSuccess) {
         m0_set_error(std::string("analysis harvest failed: ") + hipGetErrorString(hipGetLastError()));
         return M0_ERR_HIP;
@@ -74,7 +105,15 @@ int analysis_harvest(m0_selfplay* sp) {
         r.root_q = g.root_n > 0 ? g.root_q : g.root_v;
         copy_lines(a, j, r);
         if (g.overflow) sp->stats.arena_overflows++;
-        a.done.push_back(r);
+        std::vector<int32_t> children;
+        if (a.keep_visits) {               // [policy index x k | visits x k]
+            const int k = a.hnchild[j] < 0 ? 0 : (a.hnchild[j] > M0_MAX_CHILDREN ? M0_MAX_CHILDREN : a.hnchild[j]);
+            const int32_t* ci = a.hchild_idx.data() + (size_t)j * M0_MAX_CHILDREN;
+            const int32_t* cn = a.hchild_n.data() + (size_t)j * M0_MAX_CHILDREN;
+            children.assign(ci, ci + k);
+            children.insert(children.end(), cn, cn + k);
+        }
+        answer(a, r, std::move(children));
         g.active = 0; g.finished = 0;
         sp->games[s].in_use = false;
     }
@@ -115,7 +154,7 @@ static int policy_pass(m0_selfplay* sp) {
         r.value = a.hvalues[i];
         r.root_q = (double)r.value;
         copy_lines(a, i, r);
-        a.done.push_back(r);
+        answer(a, r);
         a.policy_queue.pop_front();
     }
     sp->stats.evals += (uint64_t)n;
@@ -194,20 +233,59 @@ int m0_analysis_submit(m0_selfplay* sp, const char* fen, const char* const* ucis
         }
     }
     job.nlegal = gen_legal(job.line.pos, legal);
-    if (job.nlegal == 0) {                 // no search, no evaluation, no slot
-        m0_analysis_result r = blank_result(job);
-        r.status = in_check(job.line.pos) ? 1 : 2;
-        sp->an->done.push_back(r);
-        return M0_OK;
+    queue_job(sp, std::move(job));
+    return M0_OK;
+}
+
+int m0_analysis_submit_planes(m0_selfplay* sp, const float* planes, const uint8_t* mask, int n, int sims, const int64_t* ids,
+                              int32_t* status, int32_t* flags) {
+    M0_ENGINE_CALL(sp, "m0_analysis_submit_planes", KIND_ANALYSIS, true);
+    if (!planes || !status || n <= 0 || sims < 0) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
+    if (sims == 0 && !sp->net) { m0_set_error("policy mode (sims = 0) needs an engine with a network"); return M0_ERR_UNSUPPORTED; }
+    // decoded on the engine's device and stream; the buffers live for this call
+    const size_t N = (size_t)n;
+    DevBuf<float> dpl; DevBuf<uint8_t> dm; DevBuf<Pos> dp; DevBuf<int32_t> dst, dfl, dnl;
+    if (!dpl.alloc(N * M0_PLANES * 64) || (mask && !dm.alloc(N * M0_POLICY_SIZE)) || !dp.alloc(N) || !dst.alloc(N) || !dfl.alloc(N) ||
+        !dnl.alloc(N)) { m0_set_error("hipMalloc failed"); return M0_ERR_HIP; }
+    std::vector<Pos> hp(N);
+    std::vector<int32_t> hfl(N), hnl(N);
+    if (hipMemcpyAsync(dpl.p, planes, N * M0_PLANES * 64 * sizeof(float), hipMemcpyHostToDevice, sp->stream) != hipSuccess ||
+        (mask && hipMemcpyAsync(dm.p, mask, N * M0_POLICY_SIZE, hipMemcpyHostToDevice, sp->stream) != hipSuccess) ||
+        launch_decode_planes(dpl.p, dm.p, n, dp.p, dst.p, dfl.p, dnl.p, sp->stream) != hipSuccess ||
+        hipMemcpyAsync(hp.data(), dp.p, N * sizeof(Pos), hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
+        hipMemcpyAsync(status, dst.p, N * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
+        hipMemcpyAsync(hfl.data(), dfl.p, N * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
+        hipMemcpyAsync(hnl.data(), dnl.p, N * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
+        hipStreamSynchronize(sp->stream) != hipSuccess) {
+        m0_set_error(std::string("decoding the planes failed: ") + hipGetErrorString(hipGetLastError()));
+        return M0_ERR_HIP;
     }
-    if (sp->tb) {                          // a root inside the attached tables: answered from them, as the two cases above
-        m0_analysis_result r = blank_result(job);
-        if (tb_root_lines(sp->tb, sp->tb_max_pieces, job.line.pos, sp->an->opts.multipv, sp->an->opts.pv_len, &r)) {
-            sp->an->done.push_back(r);
-            return M0_OK;
-        }
+    if (flags) memcpy(flags, hfl.data(), N * 4);
+    for (int i = 0; i < n; ++i) {
+        if (status[i] != M0_DECODE_OK) continue;             // reported, not queued
+        AnalysisJob job;
+        job.sims = sims; job.id = ids ? ids[i] : (int64_t)i;
+        job.line.pos = hp[i];                                // an empty repetition window: the planes hold no history
+        job.nlegal = hnl[i];
+        queue_job(sp, std::move(job));
     }
-    (sims == 0 ? sp->an->policy_queue : sp->an->queue).push_back(std::move(job));
+    return M0_OK;
+}
+
+int m0_analysis_keep_visits(m0_selfplay* sp, int on) {
+    M0_ENGINE_CALL(sp, "m0_analysis_keep_visits", KIND_ANALYSIS, true);
+    Analysis& a = *sp->an;
+    if (on && !a.child_idx_dev) {          // the first time: one entry per slot, as the lines of a harvest
+        const size_t G = (size_t)sp->G;
+        a.child_idx_dev = dalloc<int32_t>(sp, G * M0_MAX_CHILDREN);
+        a.child_n_dev = dalloc<int32_t>(sp, G * M0_MAX_CHILDREN);
+        a.nchild_dev = dalloc<int32_t>(sp, G);
+        if (sp->alloc_failed) { a.child_idx_dev = nullptr; m0_set_error("hipMalloc failed for the root-children buffers"); return M0_ERR_HIP; }
+        a.hchild_idx.resize(G * M0_MAX_CHILDREN);
+        a.hchild_n.resize(G * M0_MAX_CHILDREN);
+        a.hnchild.resize(G);
+    }
+    a.keep_visits = on != 0;
     return M0_OK;
 }
 
@@ -241,6 +319,23 @@ int m0_analysis_poll(m0_selfplay* sp, m0_analysis_result* out) {
     if (sp->an->done.empty()) return 0;
     *out = sp->an->done.front();
     sp->an->done.pop_front();
+    sp->an->done_children.pop_front();
+    return 1;
+}
+
+int m0_analysis_poll_visits(m0_selfplay* sp, m0_analysis_result* out, int32_t* nchild, int32_t* policy_idx, int32_t* visits,
+                            int cap) {
+    M0_ENGINE_CALL(sp, "m0_analysis_poll_visits", KIND_ANALYSIS, true);
+    if (!out || !nchild || !policy_idx || !visits) { m0_set_error("null argument"); return M0_ERR_INVALID; }
+    if (cap < M0_MAX_CHILDREN) { m0_set_error("cap must be at least 256 (M0_MAX_CHILDREN)"); return M0_ERR_INVALID; }
+    if (sp->an->done.empty()) return 0;
+    *out = sp->an->done.front();
+    const std::vector<int32_t>& ch = sp->an->done_children.front();
+    const int k = (int)(ch.size() / 2);
+    *nchild = k;
+    if (k > 0) { memcpy(policy_idx, ch.data(), (size_t)k * 4); memcpy(visits, ch.data() + k, (size_t)k * 4); }
+    sp->an->done.pop_front();
+    sp->an->done_children.pop_front();
     return 1;
 }
 

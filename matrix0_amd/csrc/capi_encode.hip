@@ -1,5 +1,5 @@
 // extern "C" device hooks that take FEN strings and need no engine (include/m0_engine.h): encoding.py on the device and the
-// SSL target maps.
+// SSL target maps; and the way back, stored planes to positions.
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <string>
@@ -7,6 +7,7 @@
 #include "../../include/m0_engine.h"
 #include "capi_common.h"
 #include "chess_core.h"
+#include "fen_text.h"
 #include "tree.h"
 
 using namespace m0;
@@ -74,6 +75,40 @@ int m0_ssl_targets_fens(int hip_device, const char* const* fens, int n, float* o
     if (!dout.alloc((size_t)n * 17 * 64)) { m0_set_error("hipMalloc failed"); return M0_ERR_HIP; }
     if (launch_ssl_targets(dp.p, n, dout.p, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { m0_set_error("ssl kernel failed"); return M0_ERR_HIP; }
     dout.download(out, (size_t)n * 17 * 64);
+    return M0_OK;
+}
+
+int m0_decode_planes(int hip_device, const float* planes, const uint8_t* mask, int n, int32_t* status, int32_t* flags,
+                     int32_t* nlegal, char* fens, int fen_stride) {
+    if (!planes || n <= 0 || (fens && fen_stride < 96)) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { m0_set_error("no HIP device available (no CPU fallback)"); return M0_ERR_HIP; }
+    if (hipSetDevice(hip_device) != hipSuccess) { m0_set_error("hipSetDevice failed"); return M0_ERR_HIP; }
+    const size_t N = (size_t)n;
+    DevBuf<float> dpl; DevBuf<uint8_t> dm; DevBuf<Pos> dp; DevBuf<int32_t> dst, dfl, dnl;
+    if (!dpl.alloc(N * M0_PLANES * 64) || (mask && !dm.alloc(N * M0_POLICY_SIZE)) || !dp.alloc(N) || !dst.alloc(N) || !dfl.alloc(N) ||
+        !dnl.alloc(N)) { m0_set_error("hipMalloc failed"); return M0_ERR_HIP; }
+    (void)hipMemcpy(dpl.p, planes, N * M0_PLANES * 64 * sizeof(float), hipMemcpyHostToDevice);
+    if (mask) (void)hipMemcpy(dm.p, mask, N * M0_POLICY_SIZE, hipMemcpyHostToDevice);
+    if (launch_decode_planes(dpl.p, dm.p, n, dp.p, dst.p, dfl.p, dnl.p, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        m0_set_error("decode kernel failed");
+        return M0_ERR_HIP;
+    }
+    std::vector<int32_t> hst(N);
+    dst.download(hst.data(), N);
+    if (status) memcpy(status, hst.data(), N * sizeof(int32_t));
+    if (flags) dfl.download(flags, N);
+    if (nlegal) dnl.download(nlegal, N);
+    if (fens) {
+        std::vector<Pos> hp(N);
+        dp.download(hp.data(), N);
+        memset(fens, 0, N * (size_t)fen_stride);
+        for (size_t i = 0; i < N; ++i) {
+            if (hst[i] != M0_DECODE_OK && hst[i] != M0_DECODE_MASK_MISMATCH) continue;
+            const std::string f = fen_of(hp[i]);
+            memcpy(fens + i * (size_t)fen_stride, f.c_str(), f.size() < (size_t)fen_stride ? f.size() : (size_t)fen_stride - 1);
+        }
+    }
     return M0_OK;
 }
 

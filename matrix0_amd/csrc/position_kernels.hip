@@ -2,9 +2,11 @@
 //   encode_positions_kernel  encoding.py on device (planes, NHWC input, legal moves, policy indices, mask): parity tests and
 //                            boundary helpers; shares the move generator and the encoder with select_kernel.
 //   ssl_targets_kernel       self-supervised training targets of recorded positions.
+//   decode_planes_kernel     the way back: stored planes (and legal mask) -> position, checked (planes_decode.h).
 #include <hip/hip_runtime.h>
 #include "tree.h"
 #include "movegen_wave.h"
+#include "planes_decode.h"
 
 using namespace m0;
 
@@ -114,5 +116,73 @@ __global__ __launch_bounds__(64) void ssl_targets_kernel(const Pos* pos, int n, 
 hipError_t launch_ssl_targets(const Pos* pos_dev, int n, float* out_dev, hipStream_t st) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(ssl_targets_kernel, dim3(n), dim3(64), 0, st, pos_dev, n, out_dev);
+    return hipGetLastError();
+}
+
+// ---- stored planes -> position (planes_decode.h), one wave per row, lane = tensor square.  A ballot per piece plane is that
+// plane's bitboard in tensor order (rank 8 first); a byte swap turns it into Pos order (a1 = bit 0).  The seven constant planes
+// must be uniform over the lanes: one ballot each.  The decoded position's legal moves come from the search's generator
+// (the two LDS lists of encode_positions_kernel); with a mask they must set exactly its bits.  Nothing is shared between
+// waves, no atomics.  Every read stays inside the row: planes and mask are indexed by lane / a strided loop only, except
+// ep_from_mask and the legal moves' indices, both bounded to [0, M0_POLICY_SIZE) before use.
+__global__ __launch_bounds__(64) void decode_planes_kernel(const float* planes, const uint8_t* mask, int n, Pos* pos,
+                                                           int32_t* status, int32_t* flags, int32_t* nlegal) {
+    __shared__ Move smoves[M0_MAX_MOVES];
+    __shared__ Move spseudo[M0_MAX_MOVES];
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    const float* row = planes + (size_t)i * M0_PLANES * 64;
+    const uint8_t* mrow = mask ? mask + (size_t)i * M0_POLICY_SIZE : nullptr;
+    PlaneBits b;
+    bool bad = false;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        const uint32_t u = f32_bits(row[k * 64 + lane]);
+        b.pc[k] = __builtin_bswap64(__ballot(u == 0x3f800000u));
+        bad = bad || (u != 0u && u != 0x3f800000u);
+    }
+    b.bad_piece_value = __any(bad);
+    b.not_uniform = false;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+        const float v = row[(12 + k) * 64 + lane];
+        b.c7[k] = __shfl(v, 0);
+        b.not_uniform = b.not_uniform || __ballot(f32_bits(v) != f32_bits(b.c7[k])) != 0ull;
+    }
+    Pos p;
+    int fl = mrow ? 0 : M0_DECODE_NO_MASK;
+    int st = pos_from_plane_bits(b, p, fl);                            // uniform: every lane holds the same planes
+    int k = 0;
+    if (st == M0_DECODE_OK) {                                          // (uniform branch: the generator synchronises)
+        if (mrow) {
+            const int ep = ep_from_mask(p, mrow);
+            if (ep >= 0) { p.ep = (int8_t)ep; fl |= M0_DECODE_EP_FROM_MASK; }
+        }
+        k = gen_legal_wave(p, smoves, spseudo, lane);
+        if (mrow) {
+            // the legal moves' indices are distinct: equal masks = every one of them set and as many bytes set as moves
+            int set = 0;
+            for (int j = lane; j < M0_POLICY_SIZE; j += 64) set += mrow[j] ? 1 : 0;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) set += __shfl_xor(set, off);
+            bool miss = false;
+            for (int j = lane; j < k; j += 64) {
+                const int idx = move_to_index(p, smoves[j]);
+                miss = miss || idx < 0 || idx >= M0_POLICY_SIZE || !mrow[idx];
+            }
+            if (__any(miss) || set != k) st = M0_DECODE_MASK_MISMATCH;
+        }
+    } else {
+        for (int t = 0; t < 6; ++t) p.bb[t] = 0;
+        p.occ[0] = p.occ[1] = 0;
+        p.turn = 0; p.cr = 0; p.ep = 0; p.pad = 0; p.halfmove = 0; p.fullmove = 0;
+    }
+    if (lane == 0) { pos[i] = p; status[i] = st; flags[i] = fl; nlegal[i] = k; }
+}
+
+hipError_t launch_decode_planes(const float* planes_dev, const uint8_t* mask_dev, int n, Pos* pos_dev, int32_t* status_dev,
+                                int32_t* flags_dev, int32_t* nlegal_dev, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(decode_planes_kernel, dim3(n), dim3(64), 0, st, planes_dev, mask_dev, n, pos_dev, status_dev, flags_dev, nlegal_dev);
     return hipGetLastError();
 }

@@ -74,6 +74,7 @@ struct Analysis {
     std::deque<AnalysisJob> queue;         // submitted searches that wait for a slot
     std::deque<AnalysisJob> policy_queue;  // submitted policy-mode positions (sims = 0)
     std::deque<m0_analysis_result> done;   // answered, not yet polled
+    std::deque<std::vector<int32_t>> done_children;   // beside `done`: the root children of each (answer(), capi_analysis.hip)
     std::vector<AnalysisJob> slot_job;     // per slot: what it searches (the Line lives in games[slot])
     std::vector<int> finished;             // scratch: slots harvested by this step
     std::vector<m0_analysis_line> hlines;  // host copies of the result kernels' output
@@ -87,6 +88,11 @@ struct Analysis {
     int32_t* nlegal_dev = nullptr;
     uint16_t* moves_dev = nullptr;
     int32_t* idx_dev = nullptr;
+    bool keep_visits = false;              // m0_analysis_keep_visits: a harvest also fetches every root child's policy index and visits
+    int32_t* child_idx_dev = nullptr;      // [G][M0_MAX_CHILDREN] each, allocated when keeping is first turned on
+    int32_t* child_n_dev = nullptr;
+    int32_t* nchild_dev = nullptr;         // [G]
+    std::vector<int32_t> hchild_idx, hchild_n, hnchild;
 };
 
 }  // namespace m0

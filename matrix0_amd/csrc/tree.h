@@ -188,11 +188,20 @@ hipError_t launch_encode_positions(const m0::Pos* pos_dev, int n, float* planes_
                                    int32_t* nlegal_dev, uint16_t* moves_dev /*[n][256]*/, int32_t* idx_dev /*[n][256]*/,
                                    hipStream_t st);
 
+// The way back (planes_decode.h): rows of planes f32 [n][M0_PLANES][64] and, nullable, masks u8 [n][M0_POLICY_SIZE] -> per row
+// the position (zeroed unless the status is M0_DECODE_OK or M0_DECODE_MASK_MISMATCH), M0_DECODE_* status and flags, legal moves.
+hipError_t launch_decode_planes(const float* planes_dev, const uint8_t* mask_dev, int n, m0::Pos* pos_dev, int32_t* status_dev,
+                                int32_t* flags_dev, int32_t* nlegal_dev, hipStream_t st);
+
 // Results of the analysis engine (analysis_kernels.hip).  lines: M0_AN_MAX_LINES per entry, nlines: lines written per entry.
 // launch_analysis_lines: entry j = the finished search of slot slots_dev[j]: its root children by visits (ties by move order)
 // with the most-visited line behind each, at most pv_len moves.
 hipError_t launch_analysis_lines(const TreeDev& d, const int* slots_dev, int count, int multipv, int pv_len,
                                  m0_analysis_line* lines_dev, int* nlines_dev, hipStream_t st);
+// launch_root_children: entry j = the finished search of slot slots_dev[j]: (policy index, visits) of every root child in
+// move-generation order from the slot's RootResult, zero-padded to M0_MAX_CHILDREN, and their number.
+hipError_t launch_root_children(const TreeDev& d, const int* slots_dev, int count, int32_t* policy_idx_dev, int32_t* visits_dev,
+                                int32_t* nchild_dev, hipStream_t st);
 // launch_policy_lines: entry r = batch row r of a forward over positions that launch_encode_positions prepared (nlegal, moves,
 // idx): the legal moves by legal-softmax prior (ties by move order) and the row's value.
 hipError_t launch_policy_lines(const float* logits_dev, const float* values_dev, const int32_t* nlegal_dev, const uint16_t* moves_dev,

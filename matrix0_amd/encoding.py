@@ -37,6 +37,41 @@ def encode_fens(fens: Sequence[str], device_index: int = 0, want_moves: bool = T
     return planes, mask.astype(bool), moves
 
 
+DECODE_STATUS = {0: "ok", 1: "piece_value", 2: "square_clash", 3: "kings", 4: "pawn_rank", 5: "not_uniform", 6: "flag_value",
+                 7: "castling", 8: "counter", 9: "opponent_in_check", 10: "too_many_moves", 11: "mask_mismatch"}
+DECODE_OK, DECODE_MASK_MISMATCH = 0, 11
+# flag bits of a decoded row (include/m0_engine.h M0_DECODE_*): information, not errors
+HALFMOVE_SATURATED, FULLMOVE_SATURATED, EP_FROM_MASK, NO_MASK = 1, 2, 4, 8
+
+
+def decode_planes(planes, mask=None, device_index: int = 0) -> dict:
+    """The way back from stored rows: planes f32 [n,19,8,8] (a shard's `s`) and, optionally, their `legal_mask` [n,4672] ->
+    {"status": i32 [n] (0 or a DECODE_STATUS reason), "flags": i32 [n], "nlegal": i32 [n], "fens": [str] * n}.  The mask
+    supplies the en-passant square (the planes have none) and is audited against the decoded position's legal moves
+    (status "mask_mismatch"); without one en passant is unknown and set to none.  A FEN is empty where the status leaves no
+    position.  One wave per row on the device (m0_decode_planes)."""
+    L = _bind()
+    pl = np.ascontiguousarray(planes, dtype=np.float32)
+    if pl.ndim != 4 or pl.shape[1:] != (19, 8, 8):
+        raise ValueError("planes must be [n,19,8,8]")
+    n = int(pl.shape[0])
+    mk = None
+    if mask is not None:
+        mk = np.ascontiguousarray(np.asarray(mask).reshape(n, -1), dtype=np.uint8)
+        if mk.shape != (n, 4672):
+            raise ValueError("mask must be [n,4672]")
+    status, flags, nlegal = (np.zeros((n,), np.int32) for _ in range(3))
+    stride = 96
+    fens = C.create_string_buffer(max(1, n) * stride)
+    if n:
+        _lib.check(L.m0_decode_planes(int(device_index), pl.ctypes.data_as(C.c_void_p), mk.ctypes.data_as(C.c_void_p) if mk is not None else None,
+                                      n, status.ctypes.data_as(C.c_void_p), flags.ctypes.data_as(C.c_void_p),
+                                      nlegal.ctypes.data_as(C.c_void_p), fens, stride), "m0_decode_planes")
+    raw = fens.raw
+    return {"status": status, "flags": flags, "nlegal": nlegal,
+            "fens": [raw[i * stride: (i + 1) * stride].split(b"\0", 1)[0].decode() for i in range(n)]}
+
+
 def encode_board(fen: str) -> np.ndarray:
     """encode_board, encoding.py:11-46 -> float32 [19,8,8]."""
     return encode_fens([fen], want_moves=False)[0][0]

@@ -130,6 +130,10 @@ def _bind():
     L.m0_analysis_ext_expand.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, c_int]
     L.m0_analysis_poll.argtypes = [C.c_void_p, C.POINTER(AnalysisResult)]
     L.m0_analysis_pending.argtypes = [C.c_void_p]
+    L.m0_decode_planes.argtypes = [c_int, C.c_void_p, C.c_void_p, c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, c_int]
+    L.m0_analysis_submit_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, c_int, c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.m0_analysis_keep_visits.argtypes = [C.c_void_p, c_int]
+    L.m0_analysis_poll_visits.argtypes = [C.c_void_p, C.POINTER(AnalysisResult), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, c_int]
     L.m0_selfplay_set_tablebase.argtypes = [C.c_void_p, C.c_void_p, c_int]
     L.m0_selfplay_tb_adjudications.restype = c_u64
     L.m0_selfplay_tb_adjudications.argtypes = [C.c_void_p]
@@ -637,12 +641,57 @@ class AnalysisEngine(SelfplayEngine):
             _lib.check(n, "m0_analysis_pending")
         return n
 
-    def poll(self) -> Optional[dict]:
+    def submit_planes(self, planes, mask=None, sims: int = 0, ids=None):
+        """Stored rows straight into the queue: planes f32 [n,19,8,8] and, optionally, their legal masks [n,4672] are decoded on
+        the engine's device (encoding.decode_planes says what is recovered) and every row of status 0 is queued under ids[i]
+        (default i) as `submit(fen of the row)` would queue it -- same result, bit for bit; the planes hold no history.  Rows of
+        another status are not queued and nothing is answered for them.  Returns (status i32 [n], flags i32 [n])."""
+        pl = np.ascontiguousarray(planes, dtype=np.float32)
+        if pl.ndim != 4 or pl.shape[1:] != (19, 8, 8):
+            raise ValueError("planes must be [n,19,8,8]")
+        n = int(pl.shape[0])
+        mk = None
+        if mask is not None:
+            mk = np.ascontiguousarray(np.asarray(mask).reshape(n, -1), dtype=np.uint8)
+            if mk.shape != (n, 4672):
+                raise ValueError("mask must be [n,4672]")
+        idv = None
+        if ids is not None:
+            idv = np.ascontiguousarray(ids, dtype=np.int64)
+            if idv.shape != (n,):
+                raise ValueError("one id per row")
+        status, flags = np.zeros((n,), np.int32), np.zeros((n,), np.int32)
+        if n:
+            _lib.check(self._L.m0_analysis_submit_planes(self._h, _ptr(pl), _ptr(mk) if mk is not None else None, n, int(sims),
+                                                         _ptr(idv) if idv is not None else None, _ptr(status), _ptr(flags)),
+                       "m0_analysis_submit_planes")
+        return status, flags
+
+    def keep_visits(self, on: bool = True) -> None:
+        """With keeping on, every harvested search also brings every root child's (policy index, visits) to the host, for
+        `poll(visits=True)`: what a policy target needs.  Off (the default) nothing extra is launched or copied."""
+        _lib.check(self._L.m0_analysis_keep_visits(self._h, int(bool(on))), "m0_analysis_keep_visits")
+
+    def poll(self, visits: bool = False) -> Optional[dict]:
+        """One answered position, or None.  visits=True adds `policy_idx` and `visits` (i32 arrays, the root's children in
+        move-generation order; empty for results answered on the host, policy-mode results and searches harvested while
+        `keep_visits` was off)."""
         r = AnalysisResult()
-        rc = self._L.m0_analysis_poll(self._h, C.byref(r))
+        if not visits:
+            rc = self._L.m0_analysis_poll(self._h, C.byref(r))
+            if rc < 0:
+                _lib.check(rc, "m0_analysis_poll")
+            return analysis_result_to_dict(r) if rc == 1 else None
+        k = C.c_int32(0)
+        idx, cn = np.zeros(256, np.int32), np.zeros(256, np.int32)
+        rc = self._L.m0_analysis_poll_visits(self._h, C.byref(r), C.byref(k), _ptr(idx), _ptr(cn), 256)
         if rc < 0:
-            _lib.check(rc, "m0_analysis_poll")
-        return analysis_result_to_dict(r) if rc == 1 else None
+            _lib.check(rc, "m0_analysis_poll_visits")
+        if rc != 1:
+            return None
+        out = analysis_result_to_dict(r)
+        out["policy_idx"], out["visits"] = idx[: k.value].copy(), cn[: k.value].copy()
+        return out
 
 
 class AnalysisExtEngine(AnalysisEngine):
