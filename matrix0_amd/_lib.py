@@ -8,33 +8,13 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+from ._abi import (ACT, M0_ERR_HIP, M0_ERR_INVALID, M0_ERR_NONFINITE, M0_ERR_STATE,  # noqa: F401
+                   M0_ERR_UNSUPPORTED, M0_OK, POLICY_SIZE, SSL_BITS, AnalysisResult, NetCfg, bind)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "_build", "libm0engine.so")
-
-M0_OK = 0
-M0_ERR_INVALID = -1
-M0_ERR_UNSUPPORTED = -2
-M0_ERR_HIP = -3
-M0_ERR_STATE = -4
-M0_ERR_NONFINITE = -5
-POLICY_SIZE = 4672
-
-ACT = {"relu": 1, "silu": 2, "leaky_relu": 3}
-SSL_BITS = {"piece": 1, "threat": 2, "pin": 4, "fork": 8, "control": 16}
-SSL_CH = {"piece": 13, "threat": 1, "pin": 1, "fork": 1, "control": 3}
-SSL_ORDER = ["piece", "threat", "pin", "fork", "control"]
-
-
-class NetCfg(C.Structure):
-    _fields_ = [
-        ("planes", C.c_int), ("channels", C.c_int), ("blocks", C.c_int), ("attention", C.c_int),
-        ("attention_heads", C.c_int), ("attention_every_k", C.c_int), ("attention_relbias", C.c_int),
-        ("attention_unmasked_mix", C.c_float), ("se", C.c_int), ("se_ratio", C.c_float),
-        ("chess_features", C.c_int), ("piece_square_tables", C.c_int), ("policy_factor_rank", C.c_int),
-        ("norm_group", C.c_int), ("activation", C.c_int), ("value_activation", C.c_int), ("preact", C.c_int),
-        ("self_supervised", C.c_int), ("ssl_tasks", C.c_int), ("infer_attention_stride", C.c_int),
-    ]
-
+SSL_ORDER = list(SSL_BITS)                         # task order of the SSL outputs and of a record's target maps
+SSL_CH = {"piece": 13, "threat": 1, "pin": 1, "fork": 1, "control": 3}      # channels per task of the network's SSL heads
 
 _lib = None
 
@@ -61,24 +41,12 @@ def lib():
     except Exception:
         pass
     L = C.CDLL(LIB_PATH)
-    L.m0_last_error.restype = C.c_char_p
-    L.m0_version.restype = C.c_char_p
-    L.m0_net_create.restype = C.c_void_p
-    L.m0_net_create.argtypes = [C.POINTER(NetCfg), C.c_int]
-    L.m0_net_destroy.argtypes = [C.c_void_p]
-    L.m0_net_destroy.restype = None
-    L.m0_net_load_weight.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int]
-    L.m0_net_finalize.argtypes = [C.c_void_p]
-    L.m0_net_infer.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.m0_net_ssl_channels.argtypes = [C.c_void_p]
-    L.m0_net_param_count.argtypes = [C.c_void_p]
-    L.m0_net_param_count.restype = C.c_int64
-    L.m0_net_flops_per_position.argtypes = [C.c_void_p, C.c_int]
-    L.m0_net_flops_per_position.restype = C.c_double
-    L.m0_net_bench_forward.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
-    L.m0_net_profile_enable.argtypes = [C.c_void_p, C.c_int]
-    L.m0_net_profile_get.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
-    L.m0_net_profile_get_tail.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    missing = bind(L)
+    if missing:
+        raise EngineLibraryMissing(f"{LIB_PATH} lacks {', '.join(missing)}: it was built from an older tree; rebuild it with "
+                                   "`python -c 'import __graft_entry__ as g; g.build()'`")
+    # the mirror against the library's own struct
+    assert C.sizeof(AnalysisResult) == L.m0_analysis_result_size(), (C.sizeof(AnalysisResult), L.m0_analysis_result_size())
     _lib = L
     return L
 
@@ -102,6 +70,30 @@ def check(rc: int, what: str = "m0 call"):
     if rc == M0_ERR_INVALID:
         raise ValueError(msg)
     raise RuntimeError(msg)
+
+
+def ptr(a):
+    """A numpy array (or None) as the void pointer the library takes."""
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def cstrings(seq):
+    """Strings as a `const char* const*` argument (never of length 0); a None entry stays a null pointer."""
+    seq = list(seq)
+    return (C.c_char_p * max(1, len(seq)))(*[s.encode() if s is not None else None for s in seq])
+
+
+def count(rc: int, what: str) -> int:
+    """The return of a call that answers a count, or a negative error code."""
+    if rc < 0:
+        check(rc, what)
+    return rc
+
+
+def split_ssl(a):
+    """SSL target maps [n,17,8,8] as the NPZ fields of selfplay/internal.py:475-482: piece [n,13,8,8], the others [n,8,8]."""
+    n = SSL_CH["piece"]
+    return {"piece": a[:, :n], **{t: a[:, n + k] for k, t in enumerate(SSL_ORDER[1:])}}
 
 
 def net_cfg_from_dict(d: dict) -> NetCfg:

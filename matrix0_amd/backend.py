@@ -44,7 +44,7 @@ class M0Backend:
                 v = v.detach().cpu().float().numpy()
             a = np.ascontiguousarray(np.asarray(v), dtype=np.float32)
             shape = (C.c_int64 * max(1, a.ndim))(*a.shape)
-            _lib.check(self._L.m0_net_load_weight(self._h, k.encode(), a.ctypes.data_as(C.c_void_p), 0, shape, a.ndim),
+            _lib.check(self._L.m0_net_load_weight(self._h, k.encode(), _lib.ptr(a), 0, shape, a.ndim),
                        f"m0_net_load_weight({k})")
         _lib.check(self._L.m0_net_finalize(self._h), "m0_net_finalize")
         self._finalized = True
@@ -92,10 +92,7 @@ class M0Backend:
         val = np.empty((B,), dtype=np.float32)
         sslc = self._L.m0_net_ssl_channels(self._h)
         ssl = np.empty((B, sslc, 8, 8), dtype=np.float32) if (want_ssl and sslc > 0) else None
-        rc = self._L.m0_net_infer(self._h, a.ctypes.data_as(C.c_void_p), B, pol.ctypes.data_as(C.c_void_p),
-                                  val.ctypes.data_as(C.c_void_p),
-                                  ssl.ctypes.data_as(C.c_void_p) if ssl is not None else None)
-        _lib.check(rc, "m0_net_infer")
+        _lib.check(self._L.m0_net_infer(self._h, _lib.ptr(a), B, _lib.ptr(pol), _lib.ptr(val), _lib.ptr(ssl)), "m0_net_infer")
         out = None
         if ssl is not None:
             out, off = {}, 0

@@ -76,13 +76,8 @@ class CAbiDist:
     ranks by any out-of-band means -- a file on a shared path in `CAbiDist.from_file`."""
 
     def __init__(self, rank: int, world: int, id128: bytes, device_index: int = 0):
-        import ctypes as C
         from . import _lib
         L = _lib.lib()
-        L.m0_dist_create.restype = C.c_void_p
-        L.m0_dist_create.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_int]
-        L.m0_dist_destroy.argtypes = [C.c_void_p]
-        L.m0_net_broadcast_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         if len(id128) != 128:
             raise ValueError("id128 must be the 128 bytes of m0_dist_unique_id")
         self._L = L

@@ -11,7 +11,10 @@ from typing import List, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .engine import _bind, move_to_uci
+from ._abi import (DECODE_MASK_MISMATCH, DECODE_OK, DECODE_STATUS, EP_FROM_MASK, FULLMOVE_SATURATED,  # noqa: F401
+                   HALFMOVE_SATURATED, NO_MASK)
+from ._lib import ptr
+from .engine import move_to_uci
 
 POLICY_SHAPE = (8, 8, 73)
 LEGACY_POLICY_SIZE = 4672
@@ -20,28 +23,18 @@ LEGACY_POLICY_SIZE = 4672
 def encode_fens(fens: Sequence[str], device_index: int = 0, want_moves: bool = True):
     """Batched: planes f32 [n,19,8,8], mask bool [n,4672], per-position (ucis, indices) in
     legal_moves order."""
-    L = _bind()
     n = len(fens)
-    arr = (C.c_char_p * n)(*[f.encode() for f in fens])
     planes = np.empty((n, 19, 8, 8), np.float32)
     mask = np.empty((n, 4672), np.uint8)
     nl = np.empty((n,), np.int32)
     mv = np.empty((n, 256), np.uint16)
     idx = np.empty((n, 256), np.int32)
-    _lib.check(L.m0_encode_fens(int(device_index), arr, n, planes.ctypes.data_as(C.c_void_p), mask.ctypes.data_as(C.c_void_p),
-                                nl.ctypes.data_as(C.c_void_p), mv.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p)),
-               "m0_encode_fens")
+    _lib.check(_lib.lib().m0_encode_fens(int(device_index), _lib.cstrings(fens), n, ptr(planes), ptr(mask), ptr(nl), ptr(mv),
+                                         ptr(idx)), "m0_encode_fens")
     moves = None
     if want_moves:
         moves = [([move_to_uci(int(m)) for m in mv[i, : nl[i]]], idx[i, : nl[i]].tolist()) for i in range(n)]
     return planes, mask.astype(bool), moves
-
-
-DECODE_STATUS = {0: "ok", 1: "piece_value", 2: "square_clash", 3: "kings", 4: "pawn_rank", 5: "not_uniform", 6: "flag_value",
-                 7: "castling", 8: "counter", 9: "opponent_in_check", 10: "too_many_moves", 11: "mask_mismatch"}
-DECODE_OK, DECODE_MASK_MISMATCH = 0, 11
-# flag bits of a decoded row (include/m0_engine.h M0_DECODE_*): information, not errors
-HALFMOVE_SATURATED, FULLMOVE_SATURATED, EP_FROM_MASK, NO_MASK = 1, 2, 4, 8
 
 
 def decode_planes(planes, mask=None, device_index: int = 0) -> dict:
@@ -50,7 +43,6 @@ def decode_planes(planes, mask=None, device_index: int = 0) -> dict:
     supplies the en-passant square (the planes have none) and is audited against the decoded position's legal moves
     (status "mask_mismatch"); without one en passant is unknown and set to none.  A FEN is empty where the status leaves no
     position.  One wave per row on the device (m0_decode_planes)."""
-    L = _bind()
     pl = np.ascontiguousarray(planes, dtype=np.float32)
     if pl.ndim != 4 or pl.shape[1:] != (19, 8, 8):
         raise ValueError("planes must be [n,19,8,8]")
@@ -64,9 +56,8 @@ def decode_planes(planes, mask=None, device_index: int = 0) -> dict:
     stride = 96
     fens = C.create_string_buffer(max(1, n) * stride)
     if n:
-        _lib.check(L.m0_decode_planes(int(device_index), pl.ctypes.data_as(C.c_void_p), mk.ctypes.data_as(C.c_void_p) if mk is not None else None,
-                                      n, status.ctypes.data_as(C.c_void_p), flags.ctypes.data_as(C.c_void_p),
-                                      nlegal.ctypes.data_as(C.c_void_p), fens, stride), "m0_decode_planes")
+        _lib.check(_lib.lib().m0_decode_planes(int(device_index), ptr(pl), ptr(mk), n, ptr(status), ptr(flags), ptr(nlegal), fens,
+                                               stride), "m0_decode_planes")
     raw = fens.raw
     return {"status": status, "flags": flags, "nlegal": nlegal,
             "fens": [raw[i * stride: (i + 1) * stride].split(b"\0", 1)[0].decode() for i in range(n)]}
@@ -80,7 +71,7 @@ def encode_board(fen: str) -> np.ndarray:
 def move_to_index(fen: str, uci: str) -> int:
     """move_to_index, encoding.py:114-150; ValueError for an illegal move (:120-121)."""
     out = C.c_int32(0)
-    _lib.check(_bind().m0_move_to_index_fen(0, fen.encode(), uci.encode(), C.byref(out)), "move_to_index")
+    _lib.check(_lib.lib().m0_move_to_index_fen(0, fen.encode(), uci.encode(), C.byref(out)), "move_to_index")
     return int(out.value)
 
 
@@ -95,7 +86,7 @@ class MoveEncoder:
         if not (0 <= int(action_idx) < 4672):
             raise ValueError("action_idx out of range")
         buf = C.create_string_buffer(8)
-        _lib.check(_bind().m0_decode_move_fen(0, fen.encode(), int(action_idx), buf), "decode_move")
+        _lib.check(_lib.lib().m0_decode_move_fen(0, fen.encode(), int(action_idx), buf), "decode_move")
         return buf.value.decode()
 
     def get_legal_actions(self, fen: str) -> np.ndarray:

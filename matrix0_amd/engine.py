@@ -8,145 +8,11 @@ import numpy as np
 
 from . import _lib
 
-c_double, c_int, c_u64 = C.c_double, C.c_int, C.c_uint64
+from ._abi import (AN_MAX_LINES, AN_MAX_PV, AnalysisLine, AnalysisOpts, AnalysisResult, GameRecord,  # noqa: F401
+                   SelfplayCfg, SelfplayStats)
+from ._lib import ptr
 
-
-class SelfplayCfg(C.Structure):
-    _fields_ = [
-        ("num_simulations", c_int), ("cpuct", c_double), ("cpuct_start", c_double), ("cpuct_end", c_double),
-        ("cpuct_plies", c_int), ("use_c_base", c_int), ("cpuct_c_base", c_double), ("cpuct_c_init", c_double),
-        ("dirichlet_alpha", c_double), ("dirichlet_frac", c_double), ("dirichlet_plies", c_int),
-        ("selection_jitter", c_double), ("fpu_reduction", c_double), ("draw_penalty", c_double), ("virtual_loss", c_double),
-        ("legal_softmax", c_int), ("enable_entropy_noise", c_int), ("no_instant_backtrack", c_int), ("value_from_white", c_int),
-        ("inference_batch_size", c_int), ("playout_random_frac", c_double),
-        ("max_game_len", c_int), ("min_resign_plies", c_int), ("opening_random_plies", c_int),
-        ("resign_threshold", c_double), ("resign_window", c_int), ("resign_consecutive_bad", c_int),
-        ("resign_min_entropy", c_double), ("resign_value_margin", c_double),
-        ("temperature_start", c_double), ("temperature_end", c_double), ("temperature_moves", c_int),
-        ("low_visit_threshold", c_int),
-        ("draw_enabled", c_int), ("draw_min_plies", c_int), ("draw_window", c_int), ("draw_min_unique", c_int),
-        ("draw_halfmove_cap", c_int), ("draw_material_threshold", c_int), ("draw_stalemate", c_int),
-        ("concurrent_games", c_int), ("total_games", c_int), ("first_game_index", c_int), ("arena_nodes", c_int),
-        ("seed", c_u64), ("virtual_loss_active", c_int), ("ssl_in_forward", c_int), ("ssl_targets", c_int), ("record_games", c_int),
-        ("arena_mode", c_int), ("arena_temp", c_double), ("arena_temp_plies", c_int),
-        ("fresh_tree_per_move", c_int), ("tt_merge", c_int), ("raw_legal_priors", c_int), ("max_children", c_int),
-        ("min_child_prior", c_double), ("root_reinfer", c_int), ("eval_cache", c_int), ("eval_cache_entries", c_int),
-        ("tail_split", c_int), ("arena_eval_cache", c_int), ("arena_paired_openings", c_int),
-    ]
-
-
-class SelfplayStats(C.Structure):
-    _fields_ = [("steps", c_u64), ("evals", c_u64), ("sims", c_u64), ("plies", c_u64), ("games_finished", c_u64),
-                ("games_started", c_u64), ("ms_total", c_double), ("ms_net", c_double), ("ms_tree", c_double),
-                ("ms_host", c_double), ("arena_overflows", c_u64), ("ssl_dropped", c_u64), ("evals_cached", c_u64), ("active_games", c_int),
-                ("rows_tail", c_u64)]
-
-
-class GameRecord(C.Structure):
-    _fields_ = [("game_index", c_int), ("moves", c_int), ("resigned", c_int), ("resigner", c_int), ("draw", c_int),
-                ("total_plies", c_int), ("result", C.c_float), ("avg_policy_entropy", C.c_float), ("avg_sims", C.c_float),
-                ("secs", c_double), ("s", C.POINTER(C.c_float)), ("pi", C.POINTER(C.c_float)), ("z", C.POINTER(C.c_float)),
-                ("legal_mask", C.POINTER(C.c_uint8)), ("search_values", C.POINTER(C.c_float)),
-                ("played", C.POINTER(C.c_uint16)), ("ssl", C.POINTER(C.c_float)), ("owner", C.c_void_p),
-                ("start_fen", C.c_char_p)]
-
-
-AN_MAX_LINES, AN_MAX_PV = 8, 16
-
-
-class AnalysisOpts(C.Structure):
-    _fields_ = [("multipv", c_int), ("pv_len", c_int), ("dirichlet", c_int)]
-
-
-class AnalysisLine(C.Structure):
-    _fields_ = [("move", C.c_uint16), ("policy_index", C.c_int32), ("visits", C.c_int32), ("prior", C.c_float),
-                ("q", c_double), ("pv_len", C.c_int32), ("pv", C.c_uint16 * AN_MAX_PV)]
-
-
-class AnalysisResult(C.Structure):
-    _fields_ = [("id", C.c_int64), ("status", C.c_int32), ("nlegal", C.c_int32), ("overflow", C.c_int32),
-                ("sims", C.c_int32), ("root_n", C.c_int32), ("evals", c_u64), ("value", C.c_float), ("root_q", c_double),
-                ("nlines", C.c_int32), ("lines", AnalysisLine * AN_MAX_LINES),
-                ("tb_dtm", C.c_int32), ("line_dtm", C.c_int32 * AN_MAX_LINES)]
-
-
-_bound = False
-
-
-def _bind():
-    global _bound
-    L = _lib.lib()
-    if _bound:
-        return L
-    L.m0_selfplay_create.restype = C.c_void_p
-    L.m0_selfplay_create.argtypes = [C.c_void_p, C.POINTER(SelfplayCfg)]
-    L.m0_arena_create.restype = C.c_void_p
-    L.m0_arena_create.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(SelfplayCfg)]
-    L.m0_arena_create_ext.restype = C.c_void_p
-    L.m0_arena_create_ext.argtypes = [C.POINTER(SelfplayCfg)]
-    L.m0_arena_ext_select.argtypes = [C.c_void_p, C.POINTER(c_int), C.POINTER(c_int), C.c_void_p, C.c_void_p, c_int]
-    L.m0_arena_ext_expand.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, c_int, C.c_void_p, C.c_void_p, c_int]
-    L.m0_san_legal_fen.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.POINTER(c_int)]
-    L.m0_san_game.argtypes = [C.c_void_p, c_int, C.c_char_p, c_int]
-    L.m0_san_game_fen.argtypes = [C.c_char_p, C.c_void_p, c_int, C.c_char_p, c_int]
-    L.m0_fen_after.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), c_int, C.c_char_p, c_int]
-    L.m0_selfplay_destroy.argtypes = [C.c_void_p]
-    L.m0_selfplay_destroy.restype = None
-    L.m0_selfplay_step.argtypes = [C.c_void_p, c_int]
-    L.m0_selfplay_stats_get.argtypes = [C.c_void_p, C.POINTER(SelfplayStats)]
-    L.m0_selfplay_poll.argtypes = [C.c_void_p, C.POINTER(GameRecord)]
-    L.m0_game_record_free.argtypes = [C.POINTER(GameRecord)]
-    L.m0_game_record_free.restype = None
-    L.m0_selfplay_running.argtypes = [C.c_void_p]
-    L.m0_selfplay_set_openings.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), c_int]
-    L.m0_selfplay_ext_select.argtypes = [C.c_void_p, C.POINTER(c_int), C.c_void_p, c_int]
-    L.m0_selfplay_ext_expand.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, c_int]
-    L.m0_selfplay_last_batch_nhwc.argtypes = [C.c_void_p, C.c_void_p, c_int, C.POINTER(c_int)]
-    L.m0_encode_fens_nhwc.argtypes = [c_int, C.POINTER(C.c_char_p), c_int, C.c_void_p]
-    L.m0_search_begin.argtypes = [C.c_void_p, c_int, C.c_char_p, c_int, c_int, c_int]
-    L.m0_search_select.argtypes = [C.c_void_p, C.POINTER(c_int), C.c_void_p, c_int]
-    L.m0_search_expand.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, c_int]
-    L.m0_search_result.argtypes = [C.c_void_p, c_int, C.POINTER(c_int)] + [C.c_void_p] * 5 + \
-        [C.POINTER(c_double), C.POINTER(c_int), C.POINTER(c_int)]
-    L.m0_search_advance.argtypes = [C.c_void_p, c_int, c_int, c_int, c_int]
-    L.m0_encode_fens.argtypes = [c_int, C.POINTER(C.c_char_p), c_int] + [C.c_void_p] * 5
-    L.m0_move_to_index_fen.argtypes = [c_int, C.c_char_p, C.c_char_p, C.POINTER(C.c_int32)]
-    L.m0_decode_move_fen.argtypes = [c_int, C.c_char_p, c_int, C.c_char_p]
-    L.m0_ssl_targets_fens.argtypes = [c_int, C.POINTER(C.c_char_p), c_int, C.c_void_p]
-    L.m0_sample_move_index.argtypes = [C.c_void_p, c_int, c_double, c_double]
-    L.m0_playout_cap.argtypes = [c_int, c_double, c_double]
-    L.m0_temperature_for.argtypes = [c_int, c_double, c_double, c_int]
-    L.m0_temperature_for.restype = c_double
-    L.m0_rules_probe.argtypes = [C.POINTER(SelfplayCfg), C.c_char_p, C.POINTER(C.c_char_p), c_int, C.POINTER(c_int),
-                                 C.POINTER(C.c_float)]
-    L.m0_arena_choose_move.argtypes = [C.c_void_p, c_int, c_double, c_int, c_int, c_double]
-    L.m0_analysis_create.restype = C.c_void_p
-    L.m0_analysis_create.argtypes = [C.c_void_p, C.POINTER(SelfplayCfg), C.POINTER(AnalysisOpts)]
-    L.m0_analysis_create_ext.restype = C.c_void_p
-    L.m0_analysis_create_ext.argtypes = [C.POINTER(SelfplayCfg), C.POINTER(AnalysisOpts)]
-    L.m0_analysis_submit.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_char_p), c_int, c_int, C.c_int64]
-    L.m0_analysis_step.argtypes = [C.c_void_p, c_int]
-    L.m0_analysis_ext_select.argtypes = [C.c_void_p, C.POINTER(c_int), C.c_void_p, c_int]
-    L.m0_analysis_ext_expand.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, c_int]
-    L.m0_analysis_poll.argtypes = [C.c_void_p, C.POINTER(AnalysisResult)]
-    L.m0_analysis_pending.argtypes = [C.c_void_p]
-    L.m0_decode_planes.argtypes = [c_int, C.c_void_p, C.c_void_p, c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, c_int]
-    L.m0_analysis_submit_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, c_int, c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.m0_analysis_keep_visits.argtypes = [C.c_void_p, c_int]
-    L.m0_analysis_poll_visits.argtypes = [C.c_void_p, C.POINTER(AnalysisResult), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, c_int]
-    L.m0_selfplay_set_tablebase.argtypes = [C.c_void_p, C.c_void_p, c_int]
-    L.m0_selfplay_tb_adjudications.restype = c_u64
-    L.m0_selfplay_tb_adjudications.argtypes = [C.c_void_p]
-    L.m0_selfplay_set_search_tablebase.argtypes = [C.c_void_p, C.c_void_p, c_int]
-    L.m0_selfplay_tb_leaves.restype = c_u64
-    L.m0_selfplay_tb_leaves.argtypes = [C.c_void_p]
-    L.m0_analysis_result_size.restype = C.c_size_t
-    L.m0_analysis_result_size.argtypes = []
-    # the mirror above against the library's own struct
-    assert C.sizeof(AnalysisResult) == L.m0_analysis_result_size(), \
-        (C.sizeof(AnalysisResult), L.m0_analysis_result_size())
-    _bound = True
-    return L
+c_double, c_int = C.c_double, C.c_int
 
 
 def selfplay_cfg_from_dict(cfg: dict, *, concurrent_games: int, total_games: int = 0, first_game_index: int = 0,
@@ -244,10 +110,6 @@ def selfplay_cfg_from_dict(cfg: dict, *, concurrent_games: int, total_games: int
     return c
 
 
-def _ptr(a: np.ndarray):
-    return a.ctypes.data_as(C.c_void_p)
-
-
 def move_to_uci(m: int) -> str:
     f, t, p = m & 63, (m >> 6) & 63, (m >> 12) & 7
     s = "abcdefgh"[f & 7] + str((f >> 3) + 1) + "abcdefgh"[t & 7] + str((t >> 3) + 1)
@@ -263,7 +125,7 @@ class SelfplayEngine:
 
     def _open(self, backend, cfg: SelfplayCfg, create: str, *args) -> None:
         """What every engine class constructs: the handle from its own create call."""
-        self._L = _bind()
+        self._L = _lib.lib()
         self.backend = backend
         self.cfg = cfg
         self._h = getattr(self._L, create)(*args)
@@ -276,7 +138,7 @@ class SelfplayEngine:
         cap = self.cfg.concurrent_games * (self.cfg.inference_batch_size + 1)
         rows = [c_int(0) for _ in range(regions)]
         planes = [np.zeros((cap, 19, 8, 8), dtype=np.float32) for _ in range(regions)]
-        _lib.check(fn(self._h, *[C.byref(r) for r in rows], *[_ptr(p) for p in planes], cap), what)
+        _lib.check(fn(self._h, *[C.byref(r) for r in rows], *[ptr(p) for p in planes], cap), what)
         return [p[: r.value] for p, r in zip(planes, rows)]
 
     def _expand(self, fn, what: str, *answers) -> None:
@@ -286,7 +148,7 @@ class SelfplayEngine:
         for logits, values in answers:
             lg = np.ascontiguousarray(logits, dtype=np.float32)
             vv = np.ascontiguousarray(values, dtype=np.float32)
-            args += [_ptr(lg), _ptr(vv), int(lg.shape[0])]         # the pointers keep their arrays alive
+            args += [ptr(lg), ptr(vv), int(lg.shape[0])]         # the pointers keep their arrays alive
         _lib.check(fn(self._h, *args), what)
 
     def step(self, steps: int = 1) -> None:
@@ -303,10 +165,7 @@ class SelfplayEngine:
     def poll(self) -> Optional[dict]:
         """One finished game as the reference's NPZ dict (selfplay/internal.py:628-646) + queue metadata."""
         r = GameRecord()
-        rc = self._L.m0_selfplay_poll(self._h, C.byref(r))
-        if rc < 0:
-            _lib.check(rc, "m0_selfplay_poll")
-        if rc == 0:
+        if _lib.count(self._L.m0_selfplay_poll(self._h, C.byref(r)), "m0_selfplay_poll") == 0:
             return None
         try:
             T = r.moves
@@ -329,18 +188,14 @@ class SelfplayEngine:
                 out["z"] = np.ctypeslib.as_array(r.z, shape=(T,)).copy()
                 out["search_values"] = np.ctypeslib.as_array(r.search_values, shape=(T,)).copy()
             if r.ssl:
-                ssl = np.ctypeslib.as_array(r.ssl, shape=(T, 17, 8, 8)).copy()
-                # NPZ field shapes of selfplay/internal.py:475-482: piece [T,13,8,8], the others [T,8,8]
-                out["ssl"] = {"piece": ssl[:, :13], "threat": ssl[:, 13], "pin": ssl[:, 14], "fork": ssl[:, 15],
-                              "control": ssl[:, 16]}
+                out["ssl"] = _lib.split_ssl(np.ctypeslib.as_array(r.ssl, shape=(T, 17, 8, 8)).copy())
         finally:
             self._L.m0_game_record_free(C.byref(r))
         return out
 
     def set_openings(self, fens: List[str]) -> None:
         """Opening book positions (selfplay/internal.py:34-69); call before the first step."""
-        arr = (C.c_char_p * max(1, len(fens)))(*[f.encode() for f in fens])
-        _lib.check(self._L.m0_selfplay_set_openings(self._h, arr, len(fens)), "m0_selfplay_set_openings")
+        _lib.check(self._L.m0_selfplay_set_openings(self._h, _lib.cstrings(fens), len(fens)), "m0_selfplay_set_openings")
 
     def set_tablebase(self, tb, max_pieces: int = 4) -> None:
         """Attach a matrix0_amd.tablebase.Tablebase (None detaches); call before the first step.  After every played move a
@@ -381,7 +236,7 @@ class SelfplayEngine:
         cap = self.cfg.concurrent_games * (self.cfg.inference_batch_size + 1) + 4
         out = np.zeros((cap, 64, 32), dtype=np.float16)
         rows = c_int(0)
-        _lib.check(self._L.m0_selfplay_last_batch_nhwc(self._h, _ptr(out), cap, C.byref(rows)),
+        _lib.check(self._L.m0_selfplay_last_batch_nhwc(self._h, ptr(out), cap, C.byref(rows)),
                    "m0_selfplay_last_batch_nhwc")
         return out[: rows.value]
 
@@ -399,9 +254,8 @@ class SelfplayEngine:
         n = c_int(0); rn = c_int(0); fin = c_int(0); rq = c_double(0)
         cn = np.zeros(256, np.int32); mv = np.zeros(256, np.uint16); idx = np.zeros(256, np.int32)
         pr = np.zeros(256, np.float64); q = np.zeros(256, np.float64)
-        _lib.check(self._L.m0_search_result(self._h, g, C.byref(n), _ptr(cn), _ptr(mv),
-                                            _ptr(idx), _ptr(pr),
-                                            _ptr(q), C.byref(rq), C.byref(rn), C.byref(fin)),
+        _lib.check(self._L.m0_search_result(self._h, g, C.byref(n), ptr(cn), ptr(mv), ptr(idx), ptr(pr), ptr(q),
+                                            C.byref(rq), C.byref(rn), C.byref(fin)),
                    "m0_search_result")
         k = n.value
         return {"finished": bool(fin.value), "n": cn[:k].copy(), "moves": [move_to_uci(int(x)) for x in mv[:k]],
@@ -511,17 +365,17 @@ class SelfplayPool:
 
 # ---- host decision functions (no GPU needed) ----
 def sample_move_index(visits, temperature: float, u: float) -> int:
-    L = _bind()
+    L = _lib.lib()
     v = np.ascontiguousarray(visits, dtype=np.int32)
-    return int(L.m0_sample_move_index(_ptr(v), int(v.shape[0]), float(temperature), float(u)))
+    return int(L.m0_sample_move_index(ptr(v), int(v.shape[0]), float(temperature), float(u)))
 
 
 def playout_cap(sims: int, frac: float, u: float) -> int:
-    return int(_bind().m0_playout_cap(int(sims), float(frac), float(u)))
+    return int(_lib.lib().m0_playout_cap(int(sims), float(frac), float(u)))
 
 
 def temperature_for(fullmove: int, t_start: float, t_end: float, t_moves: int) -> float:
-    return float(_bind().m0_temperature_for(int(fullmove), float(t_start), float(t_end), int(t_moves)))
+    return float(_lib.lib().m0_temperature_for(int(fullmove), float(t_start), float(t_end), int(t_moves)))
 
 
 RULE_FLAGS = ["game_over", "game_over_claim", "adjudicate_draw", "checkmate", "stalemate", "insufficient",
@@ -529,10 +383,10 @@ RULE_FLAGS = ["game_over", "game_over_claim", "adjudicate_draw", "checkmate", "s
 
 
 def rules_probe(cfg: SelfplayCfg, fen: str, ucis: List[str]) -> dict:
-    L = _bind()
-    arr = (C.c_char_p * max(1, len(ucis)))(*[u.encode() for u in ucis])
+    L = _lib.lib()
     flags = c_int(0); res = C.c_float(0)
-    _lib.check(L.m0_rules_probe(C.byref(cfg), fen.encode(), arr, len(ucis), C.byref(flags), C.byref(res)), "m0_rules_probe")
+    _lib.check(L.m0_rules_probe(C.byref(cfg), fen.encode(), _lib.cstrings(ucis), len(ucis), C.byref(flags), C.byref(res)),
+               "m0_rules_probe")
     out = {name: bool(flags.value >> i & 1) for i, name in enumerate(RULE_FLAGS)}
     out["result"] = float(res.value)
     return out
@@ -540,11 +394,10 @@ def rules_probe(cfg: SelfplayCfg, fen: str, ucis: List[str]) -> dict:
 
 def encode_fens_nhwc(fens, device_index: int = 0) -> np.ndarray:
     """encode_board (encoding.py:11-46) as the search's select kernel writes it for the network: f16 [n,64,32]."""
-    L = _bind()
+    L = _lib.lib()
     n = len(fens)
-    arr = (C.c_char_p * n)(*[f.encode() for f in fens])
     out = np.empty((n, 64, 32), np.float16)
-    _lib.check(L.m0_encode_fens_nhwc(int(device_index), arr, n, _ptr(out)), "m0_encode_fens_nhwc")
+    _lib.check(L.m0_encode_fens_nhwc(int(device_index), _lib.cstrings(fens), n, ptr(out)), "m0_encode_fens_nhwc")
     return out
 
 
@@ -558,12 +411,11 @@ def planes_to_nhwc(planes: np.ndarray) -> np.ndarray:
 
 def ssl_targets_fens(fens, device_index: int = 0) -> dict:
     """create_enhanced_ssl_targets (ssl_algorithms.py:519-543) on the device for a list of FENs."""
-    L = _bind()
+    L = _lib.lib()
     n = len(fens)
-    arr = (C.c_char_p * n)(*[f.encode() for f in fens])
     out = np.empty((n, 17, 8, 8), np.float32)
-    _lib.check(L.m0_ssl_targets_fens(int(device_index), arr, n, _ptr(out)), "m0_ssl_targets_fens")
-    return {"piece": out[:, :13], "threat": out[:, 13], "pin": out[:, 14], "fork": out[:, 15], "control": out[:, 16]}
+    _lib.check(L.m0_ssl_targets_fens(int(device_index), _lib.cstrings(fens), n, ptr(out)), "m0_ssl_targets_fens")
+    return _lib.split_ssl(out)
 
 
 class ArenaEngine(SelfplayEngine):
@@ -629,17 +481,14 @@ class AnalysisEngine(SelfplayEngine):
 
     def submit(self, fen: str, ucis=(), sims: int = 0, id: int = 0) -> None:
         ucis = list(ucis)
-        arr = (C.c_char_p * max(1, len(ucis)))(*[u.encode() for u in ucis])
-        _lib.check(self._L.m0_analysis_submit(self._h, fen.encode(), arr, len(ucis), int(sims), int(id)), "m0_analysis_submit")
+        _lib.check(self._L.m0_analysis_submit(self._h, fen.encode(), _lib.cstrings(ucis), len(ucis), int(sims), int(id)),
+                   "m0_analysis_submit")
 
     def step(self, steps: int = 1) -> None:
         _lib.check(self._L.m0_analysis_step(self._h, int(steps)), "m0_analysis_step")
 
     def pending(self) -> int:
-        n = int(self._L.m0_analysis_pending(self._h))
-        if n < 0:
-            _lib.check(n, "m0_analysis_pending")
-        return n
+        return _lib.count(self._L.m0_analysis_pending(self._h), "m0_analysis_pending")
 
     def submit_planes(self, planes, mask=None, sims: int = 0, ids=None):
         """Stored rows straight into the queue: planes f32 [n,19,8,8] and, optionally, their legal masks [n,4672] are decoded on
@@ -662,8 +511,8 @@ class AnalysisEngine(SelfplayEngine):
                 raise ValueError("one id per row")
         status, flags = np.zeros((n,), np.int32), np.zeros((n,), np.int32)
         if n:
-            _lib.check(self._L.m0_analysis_submit_planes(self._h, _ptr(pl), _ptr(mk) if mk is not None else None, n, int(sims),
-                                                         _ptr(idv) if idv is not None else None, _ptr(status), _ptr(flags)),
+            _lib.check(self._L.m0_analysis_submit_planes(self._h, ptr(pl), ptr(mk), n, int(sims), ptr(idv), ptr(status),
+                                                         ptr(flags)),
                        "m0_analysis_submit_planes")
         return status, flags
 
@@ -678,16 +527,12 @@ class AnalysisEngine(SelfplayEngine):
         `keep_visits` was off)."""
         r = AnalysisResult()
         if not visits:
-            rc = self._L.m0_analysis_poll(self._h, C.byref(r))
-            if rc < 0:
-                _lib.check(rc, "m0_analysis_poll")
+            rc = _lib.count(self._L.m0_analysis_poll(self._h, C.byref(r)), "m0_analysis_poll")
             return analysis_result_to_dict(r) if rc == 1 else None
         k = C.c_int32(0)
         idx, cn = np.zeros(256, np.int32), np.zeros(256, np.int32)
-        rc = self._L.m0_analysis_poll_visits(self._h, C.byref(r), C.byref(k), _ptr(idx), _ptr(cn), 256)
-        if rc < 0:
-            _lib.check(rc, "m0_analysis_poll_visits")
-        if rc != 1:
+        rc = self._L.m0_analysis_poll_visits(self._h, C.byref(r), C.byref(k), ptr(idx), ptr(cn), 256)
+        if _lib.count(rc, "m0_analysis_poll_visits") != 1:
             return None
         out = analysis_result_to_dict(r)
         out["policy_idx"], out["visits"] = idx[: k.value].copy(), cn[: k.value].copy()
@@ -712,29 +557,28 @@ class AnalysisExtEngine(AnalysisEngine):
 
 def arena_choose_move(visits, temp: float, ply: int, temp_plies: int, u: float) -> int:
     """arena.py:73-106 (host_rules.h::arena_choose_move)."""
-    L = _bind()
+    L = _lib.lib()
     v = np.ascontiguousarray(visits, dtype=np.int32)
-    return int(L.m0_arena_choose_move(_ptr(v), int(len(v)), float(temp), int(ply), int(temp_plies), float(u)))
+    return int(L.m0_arena_choose_move(ptr(v), int(len(v)), float(temp), int(ply), int(temp_plies), float(u)))
 
 
 def san_legal(fen: str):
     """[(uci, san)] of the legal moves of `fen` in legal_moves order (python-chess Board.san semantics)."""
-    L = _bind()
+    L = _lib.lib()
     mv = np.zeros(256, np.uint16)
     san = C.create_string_buffer(256 * 8)
     n = c_int(0)
-    _lib.check(L.m0_san_legal_fen(fen.encode(), _ptr(mv), san, C.byref(n)), "m0_san_legal_fen")
+    _lib.check(L.m0_san_legal_fen(fen.encode(), ptr(mv), san, C.byref(n)), "m0_san_legal_fen")
     raw = san.raw
     return [(move_to_uci(int(mv[i])), raw[8 * i: 8 * i + 8].split(b"\0", 1)[0].decode()) for i in range(n.value)]
 
 
 def fen_after(fen: str, ucis) -> str:
     """Board.fen() after pushing the legal moves `ucis` on `fen` (python-chess semantics); ValueError for an illegal move."""
-    L = _bind()
+    L = _lib.lib()
     ucis = list(ucis)
-    arr = (C.c_char_p * max(1, len(ucis)))(*[u.encode() for u in ucis])
     buf = C.create_string_buffer(128)
-    rc = L.m0_fen_after(fen.encode(), arr, len(ucis), buf, len(buf))
+    rc = L.m0_fen_after(fen.encode(), _lib.cstrings(ucis), len(ucis), buf, len(buf))
     if rc == -1:
         raise ValueError(_lib.last_error())
     _lib.check(rc, "m0_fen_after")
@@ -744,13 +588,12 @@ def fen_after(fen: str, ucis) -> str:
 def san_game(moves_raw, fen: Optional[str] = None) -> str:
     """Movetext '1. e4 e5 2. Nf3 ...' of a game (moves as in a record's `played_raw`) from the start position or from `fen`
     (a record's `start_fen`); the move numbers follow the FEN, '12... Nf6 13. e4' when Black moves first."""
-    L = _bind()
+    L = _lib.lib()
     mv = np.ascontiguousarray(moves_raw, dtype=np.uint16)
     buf = C.create_string_buffer(16 * (len(mv) + 4))
     if fen is None:
-        rc = L.m0_san_game(_ptr(mv), int(len(mv)), buf, len(buf))
+        rc = L.m0_san_game(ptr(mv), int(len(mv)), buf, len(buf))
     else:
-        rc = L.m0_san_game_fen(fen.encode(), _ptr(mv), int(len(mv)), buf, len(buf))
-    if rc < 0:
-        _lib.check(rc, "m0_san_game")
+        rc = L.m0_san_game_fen(fen.encode(), ptr(mv), int(len(mv)), buf, len(buf))
+    _lib.count(rc, "m0_san_game")
     return buf.value.decode().strip()

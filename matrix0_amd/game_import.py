@@ -27,29 +27,13 @@ from typing import Dict, Iterator, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from ._abi import MOVE_RAW, MOVE_UCI, REPLAY_END_BITS as END_BITS, REPLAY_STATUS as STATUS
+from ._lib import ptr
 from .pgn_book import RESULTS, _TOKEN, _games
 
-STATUS = {0: "ok", 1: "illegal", 2: "ambiguous", 3: "too_long"}
-END_BITS = {"checkmate": 1, "stalemate": 2, "insufficient": 4, "white_to_move": 8}
-SSL_KEYS = ["piece", "threat", "pin", "fork", "control"]
-MOVE_UCI, MOVE_RAW = 0, 1
+SSL_KEYS = _lib.SSL_ORDER
 _RESULT_Z = {"1-0": 1.0, "0-1": -1.0, "1/2-1/2": 0.0}
 _MOVE_NUMBER = re.compile(r"^\d+\.(?:\.\.)?")
-
-_bound = False
-
-
-def _bind():
-    global _bound
-    L = _lib.lib()
-    if not _bound:
-        L.m0_san_pattern.argtypes = [C.c_char_p, C.POINTER(C.c_uint32)]
-        L.m0_move_pattern.argtypes = [C.c_int, C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32)]
-        L.m0_replay_games.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + \
-            [C.c_void_p] * 10
-        _bound = True
-    return L
-
 
 _pattern_cache: Dict[Tuple[str, object], int] = {}
 
@@ -63,7 +47,7 @@ def move_pattern(token, notation: str = "san") -> int:
     hit = _pattern_cache.get(key)
     if hit is not None:
         return hit
-    L = _bind()
+    L = _lib.lib()
     out = C.c_uint32(0)
     if raw:
         v = int(token)
@@ -78,10 +62,6 @@ def move_pattern(token, notation: str = "san") -> int:
     if len(_pattern_cache) < 1 << 20:
         _pattern_cache[key] = pat
     return pat
-
-
-def _ptr(a: Optional[np.ndarray]):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
 def end_flags_to_dict(flags: int) -> dict:
@@ -100,7 +80,7 @@ def replay_games(games: Sequence[Tuple[Optional[str], Sequence]], *, notation: s
     `ssl` f32 [.,17,8,8] (piece 13, threat, pin, fork, control) when asked for.  `status` is "ok", "illegal", "ambiguous" or
     "too_long"; `end` holds checkmate / stalemate / insufficient / white_to_move of the position after the last resolved move.
     ValueError for a bad start FEN (the message names the game); RuntimeError without a HIP device."""
-    L = _bind()
+    L = _lib.lib()
     n = len(games)
     if n == 0:
         return []
@@ -109,7 +89,7 @@ def replay_games(games: Sequence[Tuple[Optional[str], Sequence]], *, notation: s
     np.cumsum(counts, out=offsets[1:])
     total = int(offsets[n])
     pats = np.fromiter((move_pattern(t, notation) for _, toks in games for t in toks), np.uint32, total)
-    fens = (C.c_char_p * n)(*[f.encode() if f else None for f, _ in games])
+    fens = _lib.cstrings(f or None for f, _ in games)
     rows = max(total, 1)
     out = {
         "plies": np.zeros(n, np.int32), "status": np.zeros(n, np.int32), "end": np.zeros(n, np.int32),
@@ -119,7 +99,6 @@ def replay_games(games: Sequence[Tuple[Optional[str], Sequence]], *, notation: s
         "mask": np.zeros((rows, 4672), np.uint8) if mask else None,
         "ssl": np.zeros((rows, 17, 8, 8), np.float32) if ssl else None,
     }
-    ptr = _ptr
     _lib.check(L.m0_replay_games(int(device_index), fens, ptr(pats if total else np.zeros(1, np.uint32)), ptr(offsets), n,
                                  int(max_plies), int(max_positions_per_launch or 0), ptr(out["plies"]), ptr(out["status"]),
                                  ptr(out["end"]), ptr(out["moves"]), ptr(out["policy_idx"]), ptr(out["nlegal"]),
@@ -319,9 +298,9 @@ def import_pgn(path, out_dir: str, *, min_elo: int = 0, require_normal_terminati
                     "z": (np.float32(_RESULT_Z[result]) * (2.0 * turn - 1.0)).astype(np.float32)}
             if legal_mask:
                 part["legal_mask"] = r["mask"][:n]
-            for t in ssl_tasks:
-                ch = {"piece": slice(0, 13), "threat": 13, "pin": 14, "fork": 15, "control": 16}[t]
-                part[f"ssl_{t}"] = r["ssl"][:n, ch]
+            if ssl_tasks:
+                maps = _lib.split_ssl(r["ssl"][:n])
+                part.update({f"ssl_{t}": maps[t] for t in ssl_tasks})
             summary["games_kept"] += 1
             summary["samples"] += n
             writer.add(part)

@@ -22,32 +22,8 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-
-_bound = False
-
-
-def _bind():
-    global _bound
-    L = _lib.lib()
-    if _bound:
-        return L
-    L.m0_tb_build.restype = C.c_void_p
-    L.m0_tb_build.argtypes = [C.c_int, C.c_int]
-    L.m0_tb_build_signatures.restype = C.c_void_p
-    L.m0_tb_build_signatures.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_int]
-    L.m0_tb_load.restype = C.c_void_p
-    L.m0_tb_load.argtypes = [C.c_char_p]
-    L.m0_tb_save.argtypes = [C.c_void_p, C.c_char_p]
-    L.m0_tb_destroy.restype = None
-    L.m0_tb_destroy.argtypes = [C.c_void_p]
-    L.m0_tb_max_men.argtypes = [C.c_void_p]
-    L.m0_tb_table.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
-    L.m0_tb_table_info.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)]
-    L.m0_tb_probe_fens.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.m0_tb_root_lines.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p]
-    _bound = True
-    return L
-
+from ._abi import AnalysisResult
+from .engine import analysis_result_to_dict
 
 def tablebase_cfg(cfg_dict: dict) -> Optional[dict]:
     """`engine.tablebase` of config.yaml -> {"max_pieces": 3 | 4, "cache": path or None}; None when the key is absent.
@@ -94,27 +70,23 @@ class Tablebase:
     def __init__(self, handle):
         if not handle:
             raise RuntimeError(f"tablebase: {_lib.last_error()}")
-        self._L = _bind()
+        self._L = _lib.lib()
         self.handle = handle
 
     @classmethod
     def build(cls, max_men: int = 4, device: int = 0) -> "Tablebase":
         """Every signature in scope with at most `max_men` (3 or 4) men, built on GPU `device`."""
-        L = _bind()
-        return cls(L.m0_tb_build(int(device), int(max_men)))
+        return cls(_lib.lib().m0_tb_build(int(device), int(max_men)))
 
     @classmethod
     def build_signatures(cls, sigs: Sequence[str], device: int = 0) -> "Tablebase":
         """The given signatures ("KQKR", ...) and every table their captures and promotions lead into."""
-        L = _bind()
-        arr = (C.c_char_p * max(1, len(sigs)))(*[s.encode() for s in sigs])
-        return cls(L.m0_tb_build_signatures(int(device), arr, len(sigs)))
+        return cls(_lib.lib().m0_tb_build_signatures(int(device), _lib.cstrings(sigs), len(sigs)))
 
     @classmethod
     def load(cls, path: str) -> "Tablebase":
         """A cache file written by `save`; needs no GPU.  RuntimeError for a file that is damaged or of another format."""
-        L = _bind()
-        return cls(L.m0_tb_load(os.fspath(path).encode()))
+        return cls(_lib.lib().m0_tb_load(os.fspath(path).encode()))
 
     @classmethod
     def cached(cls, path: Optional[str], max_men: int = 4, device: int = 0) -> "Tablebase":
@@ -162,10 +134,9 @@ class Tablebase:
     def probe(self, fens: Sequence[str]):
         """(hit bool[n], wdl int8[n] for the side to move, dtm int16[n] in plies)."""
         n = len(fens)
-        arr = (C.c_char_p * max(1, n))(*[f.encode() for f in fens])
         hit = np.zeros(n, np.uint8); wdl = np.zeros(n, np.int8); dtm = np.zeros(n, np.int16)
-        _lib.check(self._L.m0_tb_probe_fens(self.handle, arr, n, hit.ctypes.data_as(C.c_void_p), wdl.ctypes.data_as(C.c_void_p),
-                                            dtm.ctypes.data_as(C.c_void_p)), "m0_tb_probe_fens")
+        _lib.check(self._L.m0_tb_probe_fens(self.handle, _lib.cstrings(fens), n, _lib.ptr(hit), _lib.ptr(wdl), _lib.ptr(dtm)),
+                   "m0_tb_probe_fens")
         return hit.astype(bool), wdl, dtm
 
     def root_lines(self, fen: str, multipv: int = 1, pv_len: int = 8) -> Optional[dict]:
@@ -173,13 +144,9 @@ class Tablebase:
         root_q the wdl for the side to move, `dtm`, evals 0; lines best first -- shortest win, draws, longest loss -- each
         with q, `dtm` of the position after the move and the principal variation under the same rule).  None when `fen` is
         no hit."""
-        from . import engine as eng
-        eng._bind()
-        r = eng.AnalysisResult()
+        r = AnalysisResult()
         rc = self._L.m0_tb_root_lines(self.handle, fen.encode(), int(multipv), int(pv_len), C.byref(r))
-        if rc < 0:
-            _lib.check(rc, "m0_tb_root_lines")
-        return eng.analysis_result_to_dict(r) if rc == 1 else None
+        return analysis_result_to_dict(r) if _lib.count(rc, "m0_tb_root_lines") == 1 else None
 
     def close(self) -> None:
         if getattr(self, "handle", None):

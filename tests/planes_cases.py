@@ -1,15 +1,11 @@
 """Shared by tests/test_planes_decode.py (CPU) and tests/test_reanalyse_gpu.py: the host build of the planes decode
-(tests/planes_shim), the hand-written en-passant positions and one malformed row per decode status."""
+(tests/host_shim/planes_shim.cpp), the hand-written en-passant positions and one malformed row per decode status."""
 import ctypes as C
-import functools
-import os
-import subprocess
 
 import numpy as np
 
 from oracle import chess_py as ch
-
-HERE = os.path.dirname(os.path.abspath(__file__))
+from tests import host_shim
 
 # status codes and flags of include/m0_engine.h
 (OK, PIECE_VALUE, SQUARE_CLASH, KINGS, PAWN_RANK, NOT_UNIFORM, FLAG_VALUE, CASTLING, COUNTER, OPPONENT_IN_CHECK, TOO_MANY_MOVES,
@@ -34,12 +30,6 @@ EP_FENS = [
 ]
 
 
-@functools.lru_cache(maxsize=None)
-def shim():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "planes_shim")])
-    return C.CDLL(os.path.join(HERE, "_build", "libplanes_shim.so"))
-
-
 def host_decode(planes, mask=None):
     """decode_planes_host (csrc/planes_decode.h) over rows: status, flags, nlegal, fens and, for the rows that left a position,
     its legal moves (raw u16) with their policy indices in generation order and its planes encoded again."""
@@ -52,8 +42,8 @@ def host_decode(planes, mask=None):
     moves, idx = np.zeros((n, 256), np.uint16), np.full((n, 256), -1, np.int32)
     again = np.zeros((n, 19, 8, 8), np.float32)
     ptr = lambda a: a.ctypes.data_as(C.c_void_p)
-    rc = shim().pd_decode(ptr(pl), ptr(mk) if mk is not None else None, n, ptr(status), ptr(flags), ptr(nlegal), fens, stride,
-                          ptr(moves), ptr(idx), ptr(again))
+    rc = host_shim.load("planes").pd_decode(ptr(pl), ptr(mk) if mk is not None else None, n, ptr(status), ptr(flags),
+                                            ptr(nlegal), fens, stride, ptr(moves), ptr(idx), ptr(again))
     assert rc == 0
     raw = fens.raw
     return {"status": status, "flags": flags, "nlegal": nlegal, "moves": moves, "idx": idx, "planes": again,

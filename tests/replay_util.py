@@ -1,14 +1,15 @@
-"""Shared by tests/test_game_import.py and tests/test_game_import_gpu.py: the host shim of the replay (tests/replay_shim: san_match.h
-and a scalar replay over gen_legal, compiled by g++), wrapped to answer like matrix0_amd.game_import.replay_games, the fixture
-games, and the hand-made cases with their expected outcome."""
+"""Shared by tests/test_game_import.py and tests/test_game_import_gpu.py: the host shim of the replay
+(tests/host_shim/replay_shim.cpp: san_match.h and a scalar replay over gen_legal, compiled by g++), wrapped to answer like
+matrix0_amd.game_import.replay_games, the fixture games, and the hand-made cases with their expected outcome."""
 import ctypes as C
 import functools
 import gzip
 import json
 import os
-import subprocess
 
 import numpy as np
+
+from tests import host_shim
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = os.path.join(HERE, "golden", "eval_games_san.json.gz")
@@ -18,17 +19,8 @@ KIND_SAN, KIND_SHORT, KIND_LONG, KIND_EXACT = 0, 1, 2, 3
 PAWN, KNIGHT, BISHOP, ROOK, QUEEN, KING = range(6)
 
 
-@functools.lru_cache(maxsize=None)
 def shim():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "replay_shim")])
-    l = C.CDLL(os.path.join(HERE, "_build", "libreplay_shim.so"))
-    l.rs_san_pattern.argtypes = [C.c_char_p, C.POINTER(C.c_uint32)]
-    l.rs_uci_pattern.argtypes = [C.c_char_p, C.POINTER(C.c_uint32)]
-    l.rs_raw_pattern.argtypes = [C.c_uint32, C.POINTER(C.c_uint32)]
-    l.rs_pattern_fields.argtypes = [C.c_uint32, C.c_void_p]
-    l.rs_pattern_fields.restype = None
-    l.rs_replay.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.POINTER(C.c_int32)] * 3
-    return l
+    return host_shim.load("replay")
 
 
 @functools.lru_cache(maxsize=None)

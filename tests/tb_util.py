@@ -1,11 +1,14 @@
-"""Shared helpers of the tablebase tests: the independent generator (tests/tb_ref), the host shim (tests/tb_shim), a third,
-Python statement of the index contract (index -> FEN), the colour flip of a FEN, and a writer of the cache-file format."""
+"""Shared helpers of the tablebase tests: the independent generator (tests/tb_ref), the host shim
+(tests/host_shim/tb_shim.cpp), a third, Python statement of the index contract (index -> FEN), the colour flip of a FEN, and
+a writer of the cache-file format."""
 import ctypes as C
 import os
 import struct
 import subprocess
 
 import numpy as np
+
+from tests import host_shim
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 BUILD = os.path.join(HERE, "_build")
@@ -51,21 +54,7 @@ def certificate(tables: dict, sig: str, seed: int, samples: int, workdir: str):
 
 
 def shim():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "tb_shim")])
-    l = C.CDLL(os.path.join(BUILD, "libtb_shim.so"))
-    l.tbs_new.restype = C.c_void_p
-    l.tbs_free.argtypes = [C.c_void_p]
-    l.tbs_free.restype = None
-    l.tbs_generate.argtypes = [C.c_void_p, C.c_char_p]
-    l.tbs_table.restype = C.POINTER(C.c_uint8)
-    l.tbs_table.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    l.tbs_roundtrip.restype = C.c_int64
-    l.tbs_roundtrip.argtypes = [C.c_char_p]
-    l.tbs_locate.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]
-    l.tbs_sig_code.argtypes = [C.c_char_p]
-    l.tbs_order.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
-    l.tbs_all_signatures.argtypes = [C.c_int, C.c_char_p, C.c_int]
-    return l
+    return host_shim.load("tb")
 
 
 def shim_table(l, h, sig):

@@ -268,7 +268,7 @@ def test_mode_errors_leave_the_engine_usable():
     import ctypes as C
     from matrix0_amd import _lib, analysis
     from matrix0_amd import engine as eng
-    L = eng._bind()
+    L = _lib.lib()
     an = _ext(2)
     h = an.engine._h
     rec, res, rows = eng.GameRecord(), eng.AnalysisResult(), C.c_int(0)
@@ -312,7 +312,7 @@ def test_every_entry_point_refuses_the_wrong_kind_of_engine():
     import ctypes as C
     from matrix0_amd import _lib
     from matrix0_amd import engine as eng
-    L = eng._bind()
+    L = _lib.lib()
 
     def cfg():
         return eng.selfplay_cfg_from_dict(_cfg(sims=4, leaves=2), concurrent_games=1)

@@ -5,23 +5,19 @@ import ctypes as C
 import gzip
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import chess_py as ch
+from tests import host_shim
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 @pytest.fixture(scope="module")
 def shim():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "host_shim")])
-    l = C.CDLL(os.path.join(HERE, "_build", "libchess_shim.so"))
-    l.hc_perft.restype = C.c_uint64
-    l.hc_perft.argtypes = [C.c_char_p, C.c_int]
-    return l
+    return host_shim.load("chess")
 
 
 def _legal(shim, fen):

@@ -1,5 +1,5 @@
 """Reading games back in, the parts that need no GPU: the token parser and the matching rule of csrc/san_match.h (compiled for the
-host by tests/replay_shim, with a scalar replay over gen_legal) against engine.san_legal and the oracle on the reference's own 125
+host by tests/host_shim/replay_shim.cpp, with a scalar replay over gen_legal) against engine.san_legal and the oracle on the reference's own 125
 evaluation games and on hand-made positions; the PGN reader; and import_pgn's filters, result handling and shard layout over a
 fake replay_games that returns the shim's answers."""
 import bz2

@@ -1,6 +1,6 @@
 """Reading games back in, on the device: m0_replay_games (one wave per game, csrc/replay_kernels.hip) through
 game_import.replay_games and import_pgn.  Every comparison is bit-exact: against the host shim of the same rule
-(tests/replay_shim), against encoding.encode_fens / engine.ssl_targets_fens on engine.fen_after positions, against the oracle, and
+(tests/host_shim/replay_shim.cpp), against encoding.encode_fens / engine.ssl_targets_fens on engine.fen_after positions, against the oracle, and
 against the engine's own self-play records."""
 import os
 

@@ -3,16 +3,13 @@ tools/gen_golden_mcts.py: encode_board / move_to_index / MoveEncoder.get_legal_a
 its own 10 000 tactical FENs + edge cases).  CPU: the oracle and the host build of the product's bitboard core; GPU: the
 device kernels through the C-ABI, compared with the golden file directly.  Bit-exact."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import chess_py as ch
+from tests import host_shim
 from tests.golden_ref import load_npz, planes_from_bits, uci
-
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 @pytest.fixture(scope="module")
@@ -42,8 +39,7 @@ def test_oracle_encoding_matches_reference_outputs(gold):
 
 def test_product_bitboard_core_matches_reference_outputs(gold):
     """csrc/chess_core.h compiled for the host (tests/host_shim): the code the device kernels are built from."""
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "host_shim")])
-    shim = C.CDLL(os.path.join(HERE, "_build", "libchess_shim.so"))
+    shim = host_shim.load("chess")
     mv = (C.c_int32 * 256)()
     idx = (C.c_int32 * 256)()
     buf = np.zeros((19, 8, 8), np.float32)

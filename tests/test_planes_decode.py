@@ -1,4 +1,4 @@
-"""Planes -> position on the CPU: csrc/planes_decode.h built for the host (tests/planes_shim), the function that
+"""Planes -> position on the CPU: csrc/planes_decode.h built for the host (tests/host_shim/planes_shim.cpp), the function that
 decode_planes_kernel runs one wave per row.  All 10 016 rows of tests/golden/ref_encoding.npz (outputs of the reference's own
 encode_board / move_to_index) decode to positions with the golden legal moves, indices, planes and FEN fields; hand-written
 en-passant positions with and without their mask; one malformed row per status; and the same code under
@@ -134,7 +134,7 @@ def test_saturated_counters_decode_with_their_flag():
 def test_sanitizer_build_over_malformed_rows():
     """The decode as a stand-alone host program (its own main, never loaded into Python) under AddressSanitizer and
     UndefinedBehaviorSanitizer over 20 000 malformed and well-formed rows with exactly-sized buffers."""
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "planes_shim"), "../_build/planes_fuzz_san"])
+    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "host_shim"), "../_build/planes_fuzz_san"])
     out = subprocess.run([os.path.join(HERE, "_build", "planes_fuzz_san")], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
     hist = dict(line.replace("status ", "").split(": ") for line in out.stdout.strip().split("\n"))

@@ -1,6 +1,6 @@
 """Host side of reanalyse (no GPU): the target rule, every reason a row keeps its targets, ids over shard boundaries and the
 shard tool, against a stand-in engine behind the real Analyzer (in the manner of tests/test_analysis.py).  The stand-in
-decodes with the host build of the planes decode (tests/planes_shim) and answers each row with visit counts drawn from its
+decodes with the host build of the planes decode (tests/host_shim/planes_shim.cpp) and answers each row with visit counts drawn from its
 id alone, so that a result can only depend on what the real engine's may depend on."""
 import json
 

@@ -1,4 +1,4 @@
-"""Reanalyse on the GPU: decode_planes_kernel against the host build of the same decode (tests/planes_shim), the round trip
+"""Reanalyse on the GPU: decode_planes_kernel against the host build of the same decode (tests/host_shim/planes_shim.cpp), the round trip
 planes -> position -> planes on replayed games, every root child's visits against the oracle tree of
 tests/test_analysis_gpu.py, m0_analysis_submit_planes against m0_analysis_submit bit for bit, and the tool end to end on rows
 of a short self-play run."""

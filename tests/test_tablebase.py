@@ -1,5 +1,5 @@
 """Endgame tablebases without a GPU: the core the build kernels are made of (matrix0_amd/csrc/tb_core.h, compiled for the host
-by tests/tb_shim, init pass and sweeps in a plain loop) against the independent generator (tests/tb_ref: the oracle's mailbox
+by tests/host_shim/tb_shim.cpp, init pass and sweeps in a plain loop) against the independent generator (tests/tb_ref: the oracle's mailbox
 rules, another loop), the cache file through the library's host-only loader and prober, and the worker's configuration."""
 import ctypes as C
 import os

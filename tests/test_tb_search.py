@@ -1,6 +1,6 @@
 """The tablebases inside the search, the part that needs no GPU: m0_tb_root_lines (the analysis of a root inside the tables)
-against a Python walk over the independent generator's tables with the oracle's rules (tests/tb_search_util.py), the
-configuration key, and the ctypes mirror of the grown result struct."""
+against a Python walk over the independent generator's tables with the oracle's rules (tests/tb_search_util.py), and the
+configuration key."""
 import ctypes as C
 
 import numpy as np
@@ -97,7 +97,6 @@ def test_root_lines_of_sampled_entries_and_their_colour_flips(tb, sig):
 
 
 def test_no_hit_leaves_the_result_untouched(tb):
-    eng._bind()
     r = eng.AnalysisResult()
     for fen in ("4k3/8/8/8/8/8/8/R3K3 w Q - 0 1",          # a castling right left
                 "4k3/4p3/8/8/8/8/4P3/4K3 w - - 0 1",        # KPKP: not in scope
@@ -127,12 +126,3 @@ def test_in_search_configuration_key():
             tbm.tablebase_cfg({"engine": {"tablebase": {"max_pieces": 3, "in_search": bad}}})
     with pytest.raises(ValueError, match="unknown"):
         tbm.tablebase_cfg({"engine": {"tablebase": {"max_pieces": 3, "in_search": True, "on_gpu": True}}})
-
-
-def test_analysis_result_mirror_has_the_library_size_and_the_new_fields_at_the_end():
-    L = eng._bind()
-    assert C.sizeof(eng.AnalysisResult) == L.m0_analysis_result_size()
-    names = [f[0] for f in eng.AnalysisResult._fields_]
-    assert names[-2:] == ["tb_dtm", "line_dtm"] and names.index("lines") == len(names) - 3
-    assert eng.AnalysisResult.tb_dtm.offset == eng.AnalysisResult.lines.offset + C.sizeof(eng.AnalysisLine) * eng.AN_MAX_LINES
-    assert eng.ANALYSIS_STATUS[3] == "tablebase"
