@@ -23,6 +23,10 @@
 // bookkeeping is identical); one barrier per piece.  The proj pieces of a group are consumed together with the qkv pieces
 // of the next one as one software-pipelined sequence: the fragments of the next half-piece are read from LDS (untracked
 // inline-asm reads, counted lgkmcnt waits) while the MFMAs of the current one issue.
+// A workgroup walks the board pairs b, b + grid, b + 2 grid, ... (grid = the CU count unless the caller caps it: LDS holds one
+// workgroup per CU).  Only the first pair's rows arrive by LDS-DMA with nothing to overlap them; every later pair's rows are
+// requested into registers as soon as the accumulators are dead (after the LayerNorm), travel under the rest of the epilogue
+// and are written to the X image at the top of the next pass.
 #include "attn_math.h"
 #include "conv_epilogue.h"
 
@@ -47,7 +51,6 @@ struct AbLane {
     int tid, lane, w;                      // w = wave, wave-uniform
     int l15, lq, r31, half;                // lane & 15, lane >> 4, lane & 31, lane >> 5
     int wm, wn;                            // GEMM role: token rows 32 wm .. 32 wm + 31, column half wn
-    size_t b0;                             // first board of the pair
     uint32_t xa[2];                        // X rows 32 wm + l15 (and + 16 * 640: 32 wm + 16 + l15), k-step 0 / 1
     int wq0, wq1, wpo;                     // this lane's offset in a qkv piece (k-step 0 / 1) and in a proj piece
     uint32_t ring_a, of_a;                 // the ring; this wave's O rows (proj operand)
@@ -67,6 +70,12 @@ struct AbRegs {
                                            // kt*32 + 8(r>>2) + 4 half + (r&3)  (fp16 pairs: 16 registers; the products take them
                                            // as the fp16 operand of a mixed-precision FMA)
 };
+// The next pair on its way through registers: this lane's ten 16-byte chunks of the X image and (threads 0-319) its four
+// values of the parameter table.  Alive from the LayerNorm of one pair to the top of the next, while AbRegs is dead.
+struct AbNext {
+    half8 x[10];
+    float par[4];
+};
 }
 
 // 64 bytes per lane from global memory that the compiler does not track (the caller waits: vmcnt)
@@ -74,6 +83,23 @@ __device__ __forceinline__ void ab_load64(half8& b0, half8& b1, half8& b2, half8
     asm volatile("global_load_dwordx4 %0, %4, off\n\tglobal_load_dwordx4 %1, %4, off offset:16\n\t"
                  "global_load_dwordx4 %2, %4, off offset:32\n\tglobal_load_dwordx4 %3, %4, off offset:48"
                  : "=&v"(b0), "=&v"(b1), "=&v"(b2), "=&v"(b3) : "v"(p) : "memory");
+}
+// 16 / 4 bytes per lane from `base` (wave-uniform) + `off`, untracked as well
+__device__ __forceinline__ void ab_gload16(half8& d, int off, const void* base) {
+    asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(d) : "v"(off), "s"(base) : "memory");
+}
+__device__ __forceinline__ void ab_gload4(float& d, int off, const void* base) {
+    asm volatile("global_load_dword %0, %1, %2" : "+v"(d) : "v"(off), "s"(base) : "memory");
+}
+// LDS stores the compiler does not track (before an ordinary one hipcc drains every LDS-DMA in flight and reorders freely
+// around s_barrier)
+template <int OFF>
+__device__ __forceinline__ void ab_lds_store16(uint32_t addr, const half8& v) {
+    asm volatile("ds_write_b128 %0, %1 offset:%2" :: "v"(addr), "v"(v), "n"(OFF) : "memory");
+}
+template <int OFF>
+__device__ __forceinline__ void ab_lds_store4(uint32_t addr, float v) {
+    asm volatile("ds_write_b32 %0, %1 offset:%2" :: "v"(addr), "v"(v), "n"(OFF) : "memory");
 }
 // one 16-byte LDS read the compiler does not track (the caller waits: lgkmcnt)
 template <int OFF>
@@ -121,7 +147,6 @@ __device__ __forceinline__ AbLane ab_lane(const AttnBlockArgs& a) {
     L.w = __builtin_amdgcn_readfirstlane(L.tid >> 6);
     L.l15 = L.lane & 15; L.lq = L.lane >> 4; L.r31 = L.lane & 31; L.half = L.lane >> 5;
     L.wm = L.w >> 1; L.wn = L.w & 1;
-    L.b0 = (size_t)blockIdx.x * 2;
     const int l15 = L.l15, lq = L.lq, w = L.w;
     const int xrow0 = 32 * L.wm + l15;
     const int xsw = (xrow0 >> 1) & 7;
@@ -143,29 +168,49 @@ __device__ __forceinline__ AbLane ab_lane(const AttnBlockArgs& a) {
     return L;
 }
 
+// L is built once, but what the phases derive from it must not outlive a pass: with the pair loop around them hipcc forms every
+// pair-independent per-lane value (the 64-bit source address of each weight piece with a constant index, the staging and
+// attention addresses, the epilogue's) in front of the loop and holds it across all phases; there are no registers for that
+// (seen: 31 to 161 spilled, the next pair's rows among them).  No instruction: the fields stay where they are, the optimizer
+// just cannot see through them.
+__device__ __forceinline__ void ab_per_pass(AbLane& L) {
+    asm volatile("" : "+v"(L.lane), "+v"(L.l15), "+v"(L.lq), "+v"(L.r31), "+v"(L.half), "+v"(L.aq), "+v"(L.xa[0]), "+v"(L.xa[1]),
+                      "+v"(L.wq0), "+v"(L.wq1), "+v"(L.wpo), "+v"(L.of_a), "+v"(L.wsrc));
+}
 // DMA weight piece t into its ring slot.
 // A piece is 12 x 1 KB: every wave issues one full 16-byte DMA and one with its upper 32 lanes masked off (1.5 KB per
 // wave), so the count of outstanding vector-memory operations is the same in all 8 waves.  (global_load_lds_dwordx3
 // would give 16 x 768 B, but on gfx950 it places lane i's 12 bytes at base + 16 i.  Twelve full instructions -- waves 0-3
 // two, waves 4-7 one, with per-wave wait counts -- measured the same or slower.)
+// The lane test is opaque and each call has its own: given one condition under several calls in a row, hipcc joins their
+// branches and moves the full DMAs between them into the two arms (seen at the top of the pair loop) -- lanes of one
+// instruction then carry different pieces, while the LDS destination (M0) is one per wave, taken from the first lane.
 __device__ __forceinline__ void ab_issue(const AbLane& L, int t) {
     const char* s = L.wsrc + (size_t)t * AB_PIECE;
     char* d = L.ring_w + (t & 3) * AB_PIECE;
     glds16(s, d);
-    if (L.lane < 32) glds16(s + 1024, d + 1024);
+    int lane = L.lane;
+    asm volatile("" : "+v"(lane));
+    if (lane < 32) glds16(s + 1024, d + 1024);
 }
 
-// the two boards' rows, the first three weight pieces and the parameter table
-__device__ __forceinline__ void ab_prologue(const AttnBlockArgs& a, const AbLane& L) {
-    const char* xg = reinterpret_cast<const char*>(a.x) + L.b0 * 64 * 640;
+// The X image is filled in 16-byte chunks: lane l of wave w, piece n owns chunk q = (10 w + n) 64 + l at AB_X + 16 q.
+// Byte offset in the pair's rows of the chunk that belongs there (the image's swizzle applied on the way in).
+__device__ __forceinline__ int ab_x_source(const AbLane& L, int n) {
+    const int q = (L.w * 10 + n) * 64 + L.lane;
+    const int row = q / 40, pos = q - row * 40;
+    const int src = (pos & ~7) | ((pos ^ (row >> 1)) & 7);
+    return row * 640 + src * 16;
+}
+__device__ __forceinline__ const char* ab_pair_rows(const AttnBlockArgs& a, int pair) {
+    return reinterpret_cast<const char*>(a.x) + (size_t)pair * (128 * 640);
+}
+
+// the first pair's rows, the first three weight pieces and the parameter table
+__device__ __forceinline__ void ab_prologue(const AttnBlockArgs& a, const AbLane& L, int pair) {
+    const char* xg = ab_pair_rows(a, pair);
 #pragma unroll
-    for (int n = 0; n < 10; ++n) {
-        const int idx = L.w * 10 + n;
-        const int q = idx * 64 + L.lane;
-        const int row = q / 40, pos = q - row * 40;
-        const int src = (pos & ~7) | ((pos ^ (row >> 1)) & 7);
-        glds16(xg + row * 640 + src * 16, ab_smem() + AB_X + idx * 1024);
-    }
+    for (int n = 0; n < 10; ++n) glds16(xg + ab_x_source(L, n), ab_smem() + AB_X + (L.w * 10 + n) * 1024);
     ab_issue(L, 0); ab_issue(L, 1); ab_issue(L, 2);
     const int tid = L.tid;
     if (tid < 320) {
@@ -173,6 +218,54 @@ __device__ __forceinline__ void ab_prologue(const AttnBlockArgs& a, const AbLane
         par[tid] = a.ln_g[tid]; par[320 + tid] = a.ln_b[tid];
         par[640 + tid] = a.y2 ? a.gn2_gamma[tid] : 0.f; par[960 + tid] = a.y2 ? a.gn2_beta[tid] : 0.f;
     }
+}
+
+// N's registers are given a definition on every path of a pass (no instruction): defined only where a next pair exists, they
+// reach the loop's head as "maybe defined" and hipcc keeps all 44 alive around the whole loop (seen: every one spilled).
+__device__ __forceinline__ void ab_define_next(AbNext& N) {
+    asm volatile("" : "=v"(N.x[0]), "=v"(N.x[1]), "=v"(N.x[2]), "=v"(N.x[3]), "=v"(N.x[4]), "=v"(N.x[5]), "=v"(N.x[6]), "=v"(N.x[7]),
+                      "=v"(N.x[8]), "=v"(N.x[9]), "=v"(N.par[0]), "=v"(N.par[1]), "=v"(N.par[2]), "=v"(N.par[3]));
+}
+// Request the next pair: ten 16-byte loads per lane and, where ab_second_output overwrites the parameter table (y2), the
+// lane's four parameters.  Inline asm the compiler does not track: an ordinary load would be drained (vmcnt(0)) at whatever
+// point hipcc places its first use.  Issued after the AB_WAIT(0) that ends a pair's sequences, retired by ab_next_arrived
+// before the next pair's first DMA: no counted wait ever sees them (see AB_WAIT).
+__device__ __forceinline__ void ab_request_next(const AttnBlockArgs& a, const AbLane& L, int pair, AbNext& N) {
+    const char* xg = ab_pair_rows(a, pair);
+    static_for<0, 10>([&](auto n_) __attribute__((always_inline)) {
+        constexpr int n = decltype(n_)::value;
+        ab_gload16(N.x[n], ab_x_source(L, n), xg);
+    });
+    if (a.y2 != nullptr && L.w < 5) {
+        const int po = L.tid * 4;
+        ab_gload4(N.par[0], po, a.ln_g); ab_gload4(N.par[1], po, a.ln_b);
+        ab_gload4(N.par[2], po, a.gn2_gamma); ab_gload4(N.par[3], po, a.gn2_beta);
+    }
+}
+// Top of every pass but the first.  All waves have left the X image, the parameter table and the GroupNorm scratch in the
+// ring (barrier); the requested rows and this wave's flush stores have retired (vmcnt(0); the operands tie the registers
+// to this point); the rows and parameters go to LDS; the first three weight pieces start.  ab_sequence's opening
+// lgkmcnt(0) + barrier makes the image visible to all waves.
+__device__ __forceinline__ void ab_next_arrived(const AttnBlockArgs& a, const AbLane& L, AbNext& N) {
+    AB_LGKM0();
+    __builtin_amdgcn_s_barrier();
+    asm volatile("s_waitcnt vmcnt(0)"
+                 : "+v"(N.x[0]), "+v"(N.x[1]), "+v"(N.x[2]), "+v"(N.x[3]), "+v"(N.x[4]), "+v"(N.x[5]), "+v"(N.x[6]), "+v"(N.x[7]),
+                   "+v"(N.x[8]), "+v"(N.x[9]), "+v"(N.par[0]), "+v"(N.par[1]), "+v"(N.par[2]), "+v"(N.par[3]) :: "memory");
+    const uint32_t lds0 = (uint32_t)(uintptr_t)ab_smem();
+    const uint32_t xd = lds0 + AB_X + L.w * 10240 + L.lane * 16;
+    static_for<0, 10>([&](auto n_) __attribute__((always_inline)) {
+        constexpr int n = decltype(n_)::value;
+        ab_lds_store16<n * 1024>(xd, N.x[n]);
+    });
+    if (a.y2 != nullptr && L.w < 5) {
+        const uint32_t pd = lds0 + AB_PAR + L.tid * 4;
+        static_for<0, 4>([&](auto i_) __attribute__((always_inline)) {
+            constexpr int i = decltype(i_)::value;
+            ab_lds_store4<i * 1280>(pd, N.par[i]);
+        });
+    }
+    ab_issue(L, 0); ab_issue(L, 1); ab_issue(L, 2);
 }
 
 __device__ __forceinline__ void ab_visibility(const AttnBlockArgs& a, const AbLane& L, half2v (&visp)[16]) {
@@ -407,8 +500,8 @@ __device__ __forceinline__ void ab_residual_layernorm(const AttnBlockArgs& a, co
 }
 
 // the wave's 16 rows are contiguous in the output: linear 16-byte reads of the LDS image, swizzle undone on the way
-__device__ __forceinline__ void ab_flush(const AbLane& L, _Float16* outp) {
-    char* og = reinterpret_cast<char*>(outp) + (L.b0 * 64 + 16 * L.w) * 640;
+__device__ __forceinline__ void ab_flush(const AbLane& L, _Float16* outp, int pair) {
+    char* og = reinterpret_cast<char*>(outp) + ((size_t)pair * 128 + 16 * L.w) * 640;
 #pragma unroll
     for (int n = 0; n < 10; ++n) {
         const int q = n * 64 + L.lane;
@@ -470,8 +563,10 @@ __device__ __forceinline__ void ab_second_output(const AbLane& L) {
 
 template <int ACT>
 __global__ __launch_bounds__(512) void attn_block_kernel(AttnBlockArgs a) {
-    const AbLane L = ab_lane(a);
-    ab_prologue(a, L);
+    AbLane L = ab_lane(a);
+    const int pairs = a.B >> 1, stride = (int)gridDim.x;
+    int pair = (int)blockIdx.x;
+    ab_prologue(a, L, pair);
     AbRegs R;
     ab_visibility(a, L, R.visp);
     float wm, wu;
@@ -479,45 +574,76 @@ __global__ __launch_bounds__(512) void attn_block_kernel(AttnBlockArgs a) {
     const float isd = a.inv_sqrt_d * kLog2e;
     const float clampv = 50.f * kLog2e;
     const float4v zero4 = {0.f, 0.f, 0.f, 0.f};
-    static_for<0, 20>([&](auto j_) __attribute__((always_inline)) { R.oc[decltype(j_)::value] = zero4; });
 
-    // qkv of group 0 | 9 x (attention of group g, then proj of g and qkv of g + 1 as one sequence) | attention and proj of group 9
-    ab_zero_qa(R.qa);
-    ab_sequence<false, true>(a, L, R, 0, 0);
 #pragma unroll 1
-    for (int g = 0; g < AB_GROUPS - 1; ++g) {
+    for (;;) {
+        ab_per_pass(L);
+        static_for<0, 20>([&](auto j_) __attribute__((always_inline)) { R.oc[decltype(j_)::value] = zero4; });
+        // qkv of group 0 | 9 x (attention of group g, then proj of g and qkv of g + 1 as one sequence) | attention and proj of group 9
+        ab_zero_qa(R.qa);
+        ab_sequence<false, true>(a, L, R, 0, 0);
+#pragma unroll 1
+        for (int g = 0; g < AB_GROUPS - 1; ++g) {
+            ab_stage_qkv(L, R.qa);
+            ab_attend(L, R, isd, clampv, wm, wu);
+            ab_zero_qa(R.qa);
+            ab_sequence<true, true>(a, L, R, 7 * g + 5, g + 1);
+        }
         ab_stage_qkv(L, R.qa);
         ab_attend(L, R, isd, clampv, wm, wu);
-        ab_zero_qa(R.qa);
-        ab_sequence<true, true>(a, L, R, 7 * g + 5, g + 1);
-    }
-    ab_stage_qkv(L, R.qa);
-    ab_attend(L, R, isd, clampv, wm, wu);
-    ab_sequence<true, false>(a, L, R, 7 * AB_GROUPS - 2, AB_GROUPS);
-    // every wave's DMA (the three pad pieces included) has landed and every wave has left the ring before it is reused
-    AB_WAIT(0);
-    __syncthreads();
+        ab_sequence<true, false>(a, L, R, 7 * AB_GROUPS - 2, AB_GROUPS);
+        // every wave's DMA (the three pad pieces included) has landed and every wave has left the ring before it is reused
+        AB_WAIT(0);
+        __syncthreads();
 
-    ab_residual_layernorm(a, L, R.oc);
-    ab_flush(L, a.y);
-    if (a.y2 == nullptr) return;
-    ab_second_output<ACT>(L);
-    ab_flush(L, a.y2);
+        ab_residual_layernorm(a, L, R.oc);
+        // R is dead from here to the top of the next pass: that is where the next pair's rows travel
+        const int next = pair + stride;
+        const bool more = next < pairs;                   // workgroup-uniform: every wave runs the same barriers
+        AbNext N;
+        ab_define_next(N);
+        if (more) ab_request_next(a, L, next, N);
+        ab_flush(L, a.y, pair);
+        if (a.y2 != nullptr) {
+            ab_second_output<ACT>(L);
+            ab_flush(L, a.y2, pair);
+        }
+        if (!more) break;
+        ab_next_arrived(a, L, N);
+        pair = next;
+    }
 }
 
+// Workgroups of a launch: one per board pair up to the cap (0 = the device's CU count; LDS holds one workgroup per CU, so a
+// larger grid only queues), each walking pairs b, b + grid, ...
 hipError_t launch_attn_block(const AttnBlockArgs& a, hipStream_t st) {
-    if (a.B <= 0 || a.B % 2 != 0 || a.ln_count <= 0 || a.ln_count > 320) return hipErrorInvalidValue;
+    if (a.B <= 0 || a.B % 2 != 0 || a.ln_count <= 0 || a.ln_count > 320 || a.grid_cap < 0) return hipErrorInvalidValue;
     if (a.y2 != nullptr && a.act != ACT_SILU && a.act != ACT_RELU) return hipErrorInvalidValue;
     static DeviceOnce once;
-    hipError_t e = once.run([] {
+    static std::atomic<int> cu_count[32];                 // per device, written before DeviceOnce publishes the device
+    int cus = 0;
+    hipError_t e = once.run([&cus] {
         hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_block_kernel<ACT_SILU>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, AB_LDS);
         if (r != hipSuccess) return r;
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_block_kernel<ACT_RELU>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, AB_LDS);
+        r = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_block_kernel<ACT_RELU>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, AB_LDS);
+        if (r != hipSuccess) return r;
+        int d = 0;
+        if ((r = hipGetDevice(&d)) != hipSuccess) return r;
+        if ((r = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d)) != hipSuccess) return r;
+        if (cus <= 0) return hipErrorInvalidDevice;
+        if ((unsigned)d < 32u) cu_count[d].store(cus, std::memory_order_relaxed);
+        return hipSuccess;
     });
     if (e != hipSuccess) return e;
-    const dim3 grid((unsigned)(a.B / 2));
+    if (cus == 0) {                                       // configured earlier
+        int d = 0;
+        if ((e = hipGetDevice(&d)) != hipSuccess) return e;
+        cus = cu_count[d].load(std::memory_order_relaxed);
+    }
+    const int pairs = a.B / 2, cap = a.grid_cap > 0 ? a.grid_cap : cus;
+    const dim3 grid((unsigned)(pairs < cap ? pairs : cap));
     if (a.act == ACT_RELU) hipLaunchKernelGGL(attn_block_kernel<ACT_RELU>, grid, dim3(512), AB_LDS, st, a);
     else hipLaunchKernelGGL(attn_block_kernel<ACT_SILU>, grid, dim3(512), AB_LDS, st, a);
     return hipGetLastError();

@@ -109,7 +109,7 @@ private:
     m0_net_cfg cfg_;
     int device_;
     hipStream_t stream_ = nullptr;
-    struct Switches { bool fuse_tail = true, fuse_attn = true; } sw_;   // read once (constructor)
+    struct Switches { bool fuse_tail = true, fuse_attn = true; int attn_grid = 0; } sw_;   // read once (constructor)
     // What forward() would otherwise derive again on every call: fixed by the configuration, the switches and the squeeze-excite
     // width, filled in at the end of finalize().  Layers are named by index into res_ (TowerLayer::next_bn1, first_bn1), not by
     // pointer: shared_view() copies the vectors, and an index stays valid in the copy.

@@ -58,6 +58,7 @@ Net::Net(const m0_net_cfg& cfg, int device, hipStream_t stream) : cfg_(cfg), dev
     auto off = [](const char* name) { const char* e = getenv(name); return e && e[0] == '0'; };
     sw_.fuse_tail = !off("M0_FUSE_TAIL");     // =0: conv2 + se_gate + ew_board as separate kernels
     sw_.fuse_attn = !off("M0_FUSE_ATTN");     // =0: qkv GEMM + attn_core + proj GEMM + ew_board as separate kernels
+    if (const char* e = getenv("M0_ATTN_GRID")) sw_.attn_grid = std::max(0, atoi(e));   // most attn_block workgroups; 0 = CU count
     C_ = cfg.channels;
     Cp_ = (C_ > 256 && C_ < 320) ? 320 : C_;
     Cs_ = ceil_to(std::max(16, C_ / 2), 32);
@@ -763,7 +764,7 @@ int Net::forward(const float* planes_dev, const _Float16* nhwc_dev, int B, float
                 ab.x = xa; ab.wpack = w.blk_w; ab.bias = w.blk_bias; ab.mask = mask_dev_;
                 ab.ln_g = w.ln.gamma; ab.ln_b = w.ln.beta; ab.y = xb;
                 if (next_bn1) { ab.y2 = AA_; ab.gn2_gamma = next_bn1->gamma; ab.gn2_beta = next_bn1->beta; }
-                ab.B = Bp; ab.ln_count = C_; ab.act = act; ab.mix = cfg_.attention_unmasked_mix; ab.inv_sqrt_d = inv_sqrt_d;
+                ab.B = Bp; ab.ln_count = C_; ab.act = act; ab.grid_cap = sw_.attn_grid; ab.mix = cfg_.attention_unmasked_mix; ab.inv_sqrt_d = inv_sqrt_d;
                 KCHK(launch_attn_block(ab, st));
             } else {
                 KCHK(run_gemm(w.qkv, gemm_args(w.qkv, xa, QKV_, Mc), st));

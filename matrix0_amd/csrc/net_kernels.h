@@ -121,6 +121,7 @@ struct AttnBlockArgs {
     int B;                   // boards, even
     int ln_count;            // real channel count of the LayerNorm
     int act;                 // ACT_SILU / ACT_RELU (y2)
+    int grid_cap;            // most workgroups of the launch (each walks several board pairs); 0 = the device's CU count
     float mix;
     float inv_sqrt_d;
 };

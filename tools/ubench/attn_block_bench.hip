@@ -1,6 +1,6 @@
 // Stand-alone check + timing of attn_block_kernel (a whole attention block of the 320-channel trunk) on synthetic data.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 tools/ubench/attn_block_bench.hip -o attn_block_bench
-//   ./attn_block_bench [boards] [iters]
+//   ./attn_block_bench [boards] [iters] [grid]        grid = most workgroups of a launch (0: the device's CU count)
 // The first 4 boards are compared with a plain fp32 CPU computation of the block (qkv and O rounded to fp16 where the
 // kernel rounds them); then the launch is timed.
 #include "../../matrix0_amd/csrc/attn_block.hip"
@@ -53,6 +53,7 @@ static void pack(const std::vector<float>& wq, const std::vector<float>& wp, con
 int main(int argc, char** argv) {
     const int boards = argc > 1 ? atoi(argv[1]) : 4096;
     const int iters = argc > 2 ? atoi(argv[2]) : 20;
+    const int grid_cap = argc > 3 ? atoi(argv[3]) : 0;
     const int C = 320, H = 20;
     const size_t M = (size_t)boards * 64;
     uint64_t s = 88172645463325252ull;
@@ -64,8 +65,8 @@ int main(int argc, char** argv) {
     for (auto& v : wp) v = (float)(_Float16)(rnd() * 0.15f);
     for (auto& v : rb) v = rnd();
     for (int c = 0; c < C; ++c) { lg[c] = 1.f + 0.2f * rnd(); lb[c] = 0.2f * rnd(); g2[c] = 1.f + 0.2f * rnd(); b2[c] = 0.2f * rnd(); }
-    // the last 4 boards repeat the first 4: they are handled in a workgroup's LAST pass over its board pairs (the kernel is
-    // persistent), so their outputs must equal the first 4 boards' bit for bit
+    // the last 4 boards repeat the first 4: a workgroup walks several board pairs, these are handled in a LAST pass (rows
+    // that travelled through registers), so their outputs must equal the first 4 boards' bit for bit
     if (boards >= 8) memcpy(&hx[(size_t)(boards - 4) * 64 * C], &hx[0], (size_t)4 * 64 * C * 2);
     std::vector<uint64_t> mask(64, 0);
     for (int i = 0; i < 64; ++i)
@@ -87,7 +88,7 @@ int main(int argc, char** argv) {
     hipMemset(dy, 0, M * C * 2); hipMemset(dy2, 0, M * C * 2);
     AttnBlockArgs a{};
     a.x = dx; a.wpack = dw; a.bias = dbb; a.mask = dm; a.ln_g = dlg; a.ln_b = dlb; a.gn2_gamma = dg2; a.gn2_beta = db2;
-    a.y = dy; a.y2 = dy2; a.B = boards; a.ln_count = C; a.act = ACT_SILU; a.mix = 0.3f; a.inv_sqrt_d = 0.25f;
+    a.y = dy; a.y2 = dy2; a.B = boards; a.ln_count = C; a.act = ACT_SILU; a.grid_cap = grid_cap; a.mix = 0.3f; a.inv_sqrt_d = 0.25f;
     hipStream_t st; hipStreamCreate(&st);
     hipError_t e = launch_attn_block(a, st);
     hipError_t e2 = hipStreamSynchronize(st);
