@@ -29,7 +29,7 @@
 
 constexpr int ZS_SE_WOFF = 8192;          // LDS offset of the weight pieces during the squeeze-excite phase
 
-// number of 1-KiB pieces of GemmArgs::se_wf for Hd hidden units (net.hip packs them, pack_se_fragments)
+// number of 1-KiB pieces of GemmArgs::se_wf for Hd hidden units (net_pack.h lays them out, se_fragments)
 __host__ __device__ inline int zs_se_pieces_w1(int Hd) { return 10 * ((Hd + 15) >> 4); }
 __host__ __device__ inline int zs_se_pieces_w2(int Hd) { return 20 * ((Hd + 31) >> 5); }
 

@@ -1,5 +1,5 @@
-// Host side of the network: state-dict intake, repacking into kernel layouts,
-// workspace management and the forward schedule.
+// Host side of the network: state-dict intake and repacking into kernel layouts (net_pack.hip, over the host-only layout
+// functions of net_pack.h), workspace management and the forward schedule (net.hip).
 // Mirrors PolicyValueNet (azchess/model/resnet.py:285-582 ctor, 656-760 forward)
 // for the inference configuration the self-play path uses.
 #pragma once
@@ -10,6 +10,10 @@
 #include <vector>
 #include "../../include/m0_engine.h"
 #include "net_kernels.h"
+
+namespace net_pack { struct GemmShape; }
+
+inline int ceil_to(int v, int m) { return (v + m - 1) / m * m; }
 
 struct HostTensor {
     std::vector<float> data;
@@ -27,6 +31,8 @@ struct NormParams {
     float* gamma = nullptr;
     float* beta = nullptr;
 };
+
+struct HostNorm { std::vector<float> gamma, beta; };   // a norm's padded parameters as they were uploaded
 
 struct ResBlockW {
     PackedGemm conv1, conv2;
@@ -165,20 +171,24 @@ private:
     float* VAL_ = nullptr;
     float* SPK_ = nullptr;      // split-K partial tiles [8][Mfc][2C] f32 (value_fc1)
 
+    // weight intake (net_pack.hip)
     const HostTensor* get(const std::string& k, std::string& err);
-    int pack_gemm(PackedGemm& g, const std::string& wkey, const std::string& bkey, int taps, int Cin_real,
-                  int Cin_pad, int N_real, int N_pad, int k_perm_ch, std::string& err, int qkv_heads = 0,
-                  int qkv_heads_pad = 0);
-    int pack_attn_block(AttnW& a, const std::string& prefix, std::string& err);
+    const HostTensor* get(const std::string& k, size_t count, std::string& err);
+    // the one place that allocates and fills a weight buffer: M0_ERR_HIP with `err` set when either fails, `dst` set otherwise
+    int upload_bytes(void*& dst, const void* src, size_t bytes, std::string& err);
+    template <class P, class T>
+    int upload(P*& dst, const std::vector<T>& v, std::string& err);
+    // `keep`: also hand back the packed host copy (the joint head is built from two of them)
+    int pack_gemm(PackedGemm& g, const std::string& wkey, const std::string& bkey, const net_pack::GemmShape& s, std::string& err,
+                  std::vector<_Float16>* keep = nullptr);
+    int upload_norm(NormParams& n, const std::string& prefix, int C_real, int C_pad, std::string& err, HostNorm* keep = nullptr);
     int pack_chess_features(std::string& err);
     int pack_se(ResBlockW& r, const std::string& prefix, std::string& err);
     int pack_attn(AttnW& a, bool skip, const std::string& prefix, std::string& err);
-    void upload_attn_mask();
-    int pack_joint_head(std::string& err);
+    int pack_joint_head(const std::vector<_Float16>& ph_w, const std::vector<_Float16>& vh_w, const HostNorm& ph_n,
+                        const HostNorm& vh_n, std::string& err);
     int pack_ssl_heads(std::string& err);
     void make_plan();
-    int upload_norm(NormParams& n, const std::string& prefix, int C_real, int C_pad, std::string& err);
-    float* upload_f32(const std::vector<float>& v);
     void* dalloc(size_t bytes, bool ws);
     const NormParams* bn1(int res_index) const { return res_index < 0 ? nullptr : &res_[res_index].bn1; }
     // roofline bracket: `launch()` between two events on `st` when `on`, with its FLOP count and whether it carries a fused tail

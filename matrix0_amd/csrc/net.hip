@@ -1,5 +1,4 @@
-// Host side of the network forward (see net.h): state-dict intake and repacking (finalize and its pack_* / upload_* helpers),
-// the workspace, and the schedule of one forward.
+// Host side of the network forward (see net.h): the workspace and the schedule of one forward.  Weight intake is net_pack.hip.
 //
 // The forward, step by step, with the kernel each step launches.  "fused" is what a 320-wide trunk runs by default; "unfused" is
 // what a kernel-less width, M0_FUSE_TAIL=0 / M0_FUSE_ATTN=0 or a wide squeeze-excite falls back to: the raw conv with
@@ -26,16 +25,10 @@
 //   value_fc2, gate, fc3                   conv_gemm_kernel<1> EPI_ELEMENT
 //   SSL head: conv + GN, conv, transpose   conv_gemm_kernel<1> EPI_GN (N in 32/64/128/160), conv, nhwc_to_nchw_f32
 #include "net.h"
-#include "attn_math.h"
 #include <math.h>
 #include <string.h>
 #include <algorithm>
 #include <stdlib.h>
-
-static inline int ceil_to(int v, int m) { return (v + m - 1) / m * m; }
-
-static const char* kSslNames[5] = {"piece", "threat", "pin", "fork", "control"};
-static const int kSslOut[5] = {13, 1, 1, 1, 3};
 
 const char* Net::check_supported(const m0_net_cfg& c) {
     if (!c.norm_group) return "HIP path supports norm='group' only (BatchNorm configs are not built)";
@@ -105,400 +98,6 @@ void* Net::dalloc(size_t bytes, bool ws) {
     (ws ? ws_allocs_ : dev_allocs_).push_back(p);
     if (!ws) dev_sizes_.push_back(bytes);
     return p;
-}
-
-float* Net::upload_f32(const std::vector<float>& v) {
-    float* d = (float*)dalloc(v.size() * 4, false);
-    if (d && !v.empty()) (void)hipMemcpy(d, v.data(), v.size() * 4, hipMemcpyHostToDevice);
-    return d;
-}
-
-int Net::load(const char* name, const void* data, int dtype, const int64_t* shape, int ndim, std::string& err) {
-    if (finalized_) { err = "weights already finalized"; return M0_ERR_STATE; }
-    if (!name || (!data && ndim >= 0)) { err = "null argument"; return M0_ERR_INVALID; }
-    HostTensor t;
-    size_t n = 1;
-    for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= (size_t)shape[i]; }
-    t.data.resize(n);
-    if (dtype == 0) memcpy(t.data.data(), data, n * 4);
-    else if (dtype == 1) {
-        const _Float16* h = (const _Float16*)data;
-        for (size_t i = 0; i < n; ++i) t.data[i] = (float)h[i];
-    } else { err = "dtype must be 0 (f32) or 1 (f16)"; return M0_ERR_INVALID; }
-    std::string key(name);
-    // resnet.py:1405-1416: legacy rename policy_fc.* -> policy_fc1.* only matters for factorised heads
-    if (cfg_.policy_factor_rank > 0 && key.rfind("policy_fc.", 0) == 0) key = "policy_fc1." + key.substr(10);
-    sd_[key] = std::move(t);
-    return M0_OK;
-}
-
-const HostTensor* Net::get(const std::string& k, std::string& err) {
-    auto it = sd_.find(k);
-    if (it == sd_.end()) { err = "missing state-dict key: " + k; return nullptr; }
-    return &it->second;
-}
-
-int Net::pack_gemm(PackedGemm& g, const std::string& wkey, const std::string& bkey, int taps, int Cin_real,
-                   int Cin_pad, int N_real, int N_pad, int k_perm_ch, std::string& err, int qkv_heads, int qkv_heads_pad) {
-    const HostTensor* w = get(wkey, err);
-    if (!w) return M0_ERR_INVALID;
-    size_t expect = (size_t)N_real * Cin_real * taps;
-    if (w->data.size() != expect) { err = "shape mismatch for " + wkey; return M0_ERR_INVALID; }
-    nparams_ += expect;
-    const int KC = conv_gemm_kc(Cin_pad, N_pad);
-    const int nchunk = Cin_pad / KC;
-    const bool pp = KC == 64 && taps == 9;       // 3x3 big tile: the half-tile layout of conv_zs_kernel
-    const int nblk = N_pad / 320;
-    std::vector<_Float16> p((size_t)taps * Cin_pad * N_pad, (_Float16)0.f);
-    for (int nr = 0; nr < N_real; ++nr)
-        for (int k = 0; k < Cin_real; ++k)
-            for (int t = 0; t < taps; ++t) {
-                float v = w->data[((size_t)nr * Cin_real + k) * taps + t];
-                int n = nr;
-                if (qkv_heads > 0) {           // qkv rows (t, head, dim) -> the same with the padded head count
-                    const int d = nr % 16, th = nr / 16, hh = th % qkv_heads, tt = th / qkv_heads;
-                    n = (tt * qkv_heads_pad + hh) * 16 + d;
-                }
-                int kk = k;
-                if (k_perm_ch > 0) {           // reference flatten index c*64+sq -> ours sq*Cp+c
-                    int c = k / 64, sq = k % 64;
-                    kk = sq * k_perm_ch + c;
-                }
-                int chunk = kk / KC, kc = kk % KC;
-                if (pp) {       // conv_zs_kernel: half-K-tiles of 320 x 32 k, 64-byte rows, 16-byte chunk index
-                                // ^ ((4 - (row >> 2)) & 3): conflict-free for its 16x16x32 fragment reads
-                    const int kt = chunk * 9 + t, by = n / 320, nl = n % 320, h = kc >> 5, k32 = kc & 31;
-                    const int kx = (((k32 >> 3) ^ ((4 - ((nl >> 2) & 3)) & 3)) << 3) | (k32 & 7);
-                    p[((((size_t)kt * nblk + by) * 2 + h) * 320 + nl) * 32 + kx] = (_Float16)v;
-                    continue;
-                }
-                if (KC == 64)   // big tile: LDS image order, 16-byte chunk index XOR (row>>1)&7 (conv_big_kernel)
-                    kc = (((kc >> 3) ^ ((n >> 1) & 7)) << 3) | (kc & 7);
-                p[(((size_t)t * nchunk + chunk) * N_pad + n) * KC + kc] = (_Float16)v;
-            }
-    g.w = (_Float16*)dalloc(p.size() * 2, false);
-    if (!g.w) { err = "hipMalloc failed"; return M0_ERR_HIP; }
-    (void)hipMemcpy(g.w, p.data(), p.size() * 2, hipMemcpyHostToDevice);
-    g.taps = taps; g.Cin = Cin_pad; g.N = N_pad; g.pp = pp;
-    g.bias = nullptr;
-    if (!bkey.empty()) {
-        const HostTensor* b = get(bkey, err);
-        if (!b) return M0_ERR_INVALID;
-        if ((int)b->data.size() != N_real) { err = "shape mismatch for " + bkey; return M0_ERR_INVALID; }
-        nparams_ += N_real;
-        std::vector<float> bp(N_pad, 0.f);
-        std::copy(b->data.begin(), b->data.end(), bp.begin());
-        g.bias = upload_f32(bp);
-    }
-    return M0_OK;
-}
-
-// attn_block_kernel operands (attn_block.hip): the block's qkv and proj weights as one stream of 12 KB pieces in LDS
-// image order -- per group g of two heads: five pieces [96 cols = q,k,v x 2 heads x 16][64 k] (128-byte rows, 16-byte
-// chunk ^ (col>>1)&7) and two pieces [160 output channels][32 k = 2 heads x 16] (64-byte rows, chunk ^ (ch>>2)&3, padded
-// to 12 KB) -- and the relative-position bias per (head, query half, lane) in MFMA accumulator order.
-int Net::pack_attn_block(AttnW& a, const std::string& prefix, std::string& err) {
-    const HostTensor* wq = get(prefix + ".qkv.weight", err); if (!wq) return M0_ERR_INVALID;
-    const HostTensor* wp = get(prefix + ".proj.weight", err); if (!wp) return M0_ERR_INVALID;
-    const int Cr = C_, Hr = cfg_.attention_heads;
-    if (Cp_ != 320 || Cr != Hr * 16 || wq->data.size() != (size_t)3 * Cr * Cr || wp->data.size() != (size_t)Cr * Cr) {
-        err = "shape mismatch for " + prefix; return M0_ERR_INVALID;
-    }
-    std::vector<_Float16> buf(attn_block_pack_bytes() / 2, (_Float16)0.f);
-    auto qkv_w = [&](int type, int h, int d, int k) -> float {
-        return (h < Hr && k < Cr) ? wq->data[(size_t)((type * Hr + h) * 16 + d) * Cr + k] : 0.f;
-    };
-    auto proj_w = [&](int oc, int h, int d) -> float {
-        return (oc < Cr && h < Hr) ? wp->data[(size_t)oc * Cr + h * 16 + d] : 0.f;
-    };
-    for (int g = 0; g < 10; ++g) {
-        for (int pc = 0; pc < 5; ++pc) {
-            const size_t base = (size_t)(g * 7 + pc) * 6144;
-            for (int col = 0; col < 96; ++col) {
-                const int J = col >> 4, type = J >> 1, hl = J & 1, d = col & 15;
-                for (int k = 0; k < 64; ++k) {
-                    const int pos = (k >> 3) ^ ((col >> 1) & 7);
-                    buf[base + (size_t)col * 64 + pos * 8 + (k & 7)] = (_Float16)qkv_w(type, 2 * g + hl, d, 64 * pc + k);
-                }
-            }
-        }
-        for (int hh = 0; hh < 2; ++hh) {
-            const size_t base = (size_t)(g * 7 + 5 + hh) * 6144;
-            for (int cl = 0; cl < 160; ++cl)
-                for (int k = 0; k < 32; ++k) {
-                    const int pos = (k >> 3) ^ ((4 - ((cl >> 2) & 3)) & 3);
-                    buf[base + (size_t)cl * 32 + pos * 8 + (k & 7)] = (_Float16)proj_w(160 * hh + cl, 2 * g + (k >> 4), k & 15);
-                }
-        }
-    }
-    a.blk_w = dalloc(buf.size() * 2, false);
-    if (!a.blk_w) { err = "hipMalloc failed"; return M0_ERR_HIP; }
-    (void)hipMemcpy(a.blk_w, buf.data(), buf.size() * 2, hipMemcpyHostToDevice);
-    std::vector<_Float16> bb((size_t)20 * 2 * 64 * 32, (_Float16)0.f);
-    if (cfg_.attention_relbias) {
-        const HostTensor* rb = get(prefix + ".rel_bias", err); if (!rb) return M0_ERR_INVALID;
-        for (int h = 0; h < Hr; ++h)
-            for (int qt = 0; qt < 2; ++qt)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int e = 0; e < 32; ++e) {
-                        const int kt = e >> 4, r = e & 15;
-                        const int q = qt * 32 + (lane & 31), key = kt * 32 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
-                        bb[(((size_t)h * 2 + qt) * 64 + lane) * 32 + e] =
-                            (_Float16)(rb->data[((size_t)h * 64 + q) * 64 + key] * kLog2e);
-                    }
-    }
-    a.blk_bias = (_Float16*)dalloc(bb.size() * 2, false);
-    if (!a.blk_bias) { err = "hipMalloc failed"; return M0_ERR_HIP; }
-    (void)hipMemcpy(a.blk_bias, bb.data(), bb.size() * 2, hipMemcpyHostToDevice);
-    return M0_OK;
-}
-
-int Net::upload_norm(NormParams& n, const std::string& prefix, int C_real, int C_pad, std::string& err) {
-    const HostTensor* g = get(prefix + ".weight", err);
-    if (!g) return M0_ERR_INVALID;
-    const HostTensor* b = get(prefix + ".bias", err);
-    if (!b) return M0_ERR_INVALID;
-    if ((int)g->data.size() != C_real || (int)b->data.size() != C_real) { err = "shape mismatch for " + prefix; return M0_ERR_INVALID; }
-    nparams_ += 2 * (size_t)C_real;
-    std::vector<float> gp(C_pad, 0.f), bp(C_pad, 0.f);
-    std::copy(g->data.begin(), g->data.end(), gp.begin());
-    std::copy(b->data.begin(), b->data.end(), bp.begin());
-    n.gamma = upload_f32(gp);
-    n.beta = upload_f32(bp);
-    return M0_OK;
-}
-
-#define TRY(x) do { int rc_ = (x); if (rc_ != M0_OK) return rc_; } while (0)
-
-// positional encoding [64][P] and the two feature convs (resnet.py:229-244)
-int Net::pack_chess_features(std::string& err) {
-    const int C = C_, P = Cp_;
-    const HostTensor* pe = get("chess_features.position_encoding", err);
-    if (!pe) return M0_ERR_INVALID;
-    if ((int)pe->data.size() != C * 64) { err = "shape mismatch for position_encoding"; return M0_ERR_INVALID; }
-    nparams_ += pe->data.size();
-    std::vector<float> t((size_t)64 * P, 0.f);
-    for (int c = 0; c < C; ++c)
-        for (int n = 0; n < 64; ++n) t[(size_t)n * P + c] = pe->data[(size_t)c * 64 + n];
-    posenc_ = upload_f32(t);
-    if (cfg_.piece_square_tables) {
-        TRY(pack_gemm(pst_, "chess_features.pst_conv.weight", "", 1, C, P, C, P, 0, err));
-        TRY(upload_norm(pst_n_, "chess_features.pst_norm", C, P, err));
-    }
-    TRY(pack_gemm(inter_, "chess_features.interaction_conv.weight", "", 9, C, P, C, P, 0, err));
-    return upload_norm(inter_n_, "chess_features.interaction_norm", C, P, err);
-}
-
-// squeeze-excite of one block: both FCs transposed for se_gate_kernel and, where the fused tail can take them, as fp16 MFMA
-// fragment pieces for conv_zs_kernel
-int Net::pack_se(ResBlockW& r, const std::string& p, std::string& err) {
-    const int C = C_, P = Cp_;
-    const int hd = std::max(8, (int)(C * cfg_.se_ratio));
-    r.se_hidden = hd;
-    const HostTensor* w1 = get(p + ".se_fc1.weight", err); if (!w1) return M0_ERR_INVALID;
-    const HostTensor* b1 = get(p + ".se_fc1.bias", err); if (!b1) return M0_ERR_INVALID;
-    const HostTensor* w2 = get(p + ".se_fc2.weight", err); if (!w2) return M0_ERR_INVALID;
-    const HostTensor* b2 = get(p + ".se_fc2.bias", err); if (!b2) return M0_ERR_INVALID;
-    if ((int)w1->data.size() != hd * C || (int)w2->data.size() != hd * C || (int)b1->data.size() != hd ||
-        (int)b2->data.size() != C) { err = "shape mismatch for " + p + ".se_*"; return M0_ERR_INVALID; }
-    nparams_ += (size_t)2 * hd * C + hd + C;
-    std::vector<float> w1t((size_t)P * hd, 0.f);  // [P][hd] from [hd][C]
-    for (int j = 0; j < hd; ++j)
-        for (int c = 0; c < C; ++c) w1t[(size_t)c * hd + j] = w1->data[(size_t)j * C + c];
-    r.se_w1 = upload_f32(w1t);
-    r.se_b1 = upload_f32(b1->data);
-    std::vector<float> w2t((size_t)hd * P, 0.f);  // [hd][P] from [C][hd]: coalesced across channels
-    for (int c = 0; c < C; ++c)
-        for (int j = 0; j < hd; ++j) w2t[(size_t)j * P + c] = w2->data[(size_t)c * hd + j];
-    r.se_w2 = upload_f32(w2t);
-    if (P == 320 && hd <= TAIL_SE_HMAX) {
-        // conv_zs_kernel's tail runs the two FCs on the matrix cores: B-fragment pieces of v_mfma_f32_16x16x32_f16,
-        // lane (c15 = lane & 15, q = lane >> 4) holds column c15, k = 8q..8q+7 of its tile (conv_zs_tail.h):
-        //   W1 piece (nt, ks):   W1[channel 32 ks + 8 q + e][hidden 16 nt + c15]     nt < ceil(hd/16), ks < 10
-        //   W2 piece (nt, ks):   W2[hidden 32 ks + 8 q + e][channel 16 nt + c15]     nt < 20, ks < ceil(hd/32)
-        const int NT1 = (hd + 15) / 16, KS2 = (hd + 31) / 32;
-        std::vector<_Float16> wf((size_t)(10 * NT1 + 20 * KS2) * 512, (_Float16)0.f);
-        for (int nt = 0; nt < NT1; ++nt)
-            for (int ks = 0; ks < 10; ++ks)
-                for (int l = 0; l < 64; ++l)
-                    for (int e = 0; e < 8; ++e) {
-                        const int c = 32 * ks + 8 * (l >> 4) + e, j = 16 * nt + (l & 15);
-                        if (j < hd) wf[((size_t)(nt * 10 + ks) * 64 + l) * 8 + e] = (_Float16)w1t[(size_t)c * hd + j];
-                    }
-        for (int nt = 0; nt < 20; ++nt)
-            for (int ks = 0; ks < KS2; ++ks)
-                for (int l = 0; l < 64; ++l)
-                    for (int e = 0; e < 8; ++e) {
-                        const int j = 32 * ks + 8 * (l >> 4) + e, c = 16 * nt + (l & 15);
-                        if (j < hd) wf[((size_t)(10 * NT1 + nt * KS2 + ks) * 64 + l) * 8 + e] = (_Float16)w2t[(size_t)j * P + c];
-                    }
-        r.se_wf = dalloc(wf.size() * 2, false);
-        if (!r.se_wf) { err = "hipMalloc failed"; return M0_ERR_HIP; }
-        (void)hipMemcpy(r.se_wf, wf.data(), wf.size() * 2, hipMemcpyHostToDevice);
-    }
-    std::vector<float> b2p(P, 0.f);
-    std::copy(b2->data.begin(), b2->data.end(), b2p.begin());
-    r.se_b2 = upload_f32(b2p);
-    return M0_OK;
-}
-
-int Net::pack_attn(AttnW& a, bool skip, const std::string& p, std::string& err) {
-    const int C = C_, P = Cp_;
-    if (skip) {   // never executed at inference; count parameters, keep nothing resident
-        for (const char* k : {".qkv.weight", ".proj.weight", ".norm.weight", ".norm.bias", ".rel_bias"}) {
-            auto it = sd_.find(p + k);
-            if (it != sd_.end()) nparams_ += it->second.data.size();
-        }
-        return M0_OK;
-    }
-    TRY(pack_gemm(a.qkv, p + ".qkv.weight", "", 1, C, P, 3 * C, 3 * P, 0, err, P != C ? cfg_.attention_heads : 0, P / 16));
-    TRY(pack_gemm(a.proj, p + ".proj.weight", "", 1, C, P, C, P, 0, err));
-    TRY(upload_norm(a.ln, p + ".norm", C, P, err));
-    if (P == 320) TRY(pack_attn_block(a, p, err));
-    if (cfg_.attention_relbias) {
-        const HostTensor* rb = get(p + ".rel_bias", err); if (!rb) return M0_ERR_INVALID;
-        if ((int)rb->data.size() != cfg_.attention_heads * 4096) { err = "shape mismatch for rel_bias"; return M0_ERR_INVALID; }
-        nparams_ += rb->data.size();
-        // stored pre-multiplied by log2(e): the attention kernel exponentiates with exp2
-        std::vector<float> rbs((size_t)(P / 16) * 4096, 0.f);      // padded heads: zero bias
-        for (size_t i = 0; i < rb->data.size(); ++i) rbs[i] = rb->data[i] * kLog2e;
-        a.rel_bias = upload_f32(rbs);
-    }
-    return M0_OK;
-}
-
-// attention visibility mask, resnet.py:104-130
-void Net::upload_attn_mask() {
-    std::vector<uint64_t> m(64, 0);
-    for (int i = 0; i < 64; ++i)
-        for (int j = 0; j < 64; ++j) {
-            int dr = i / 8 - j / 8, dc = i % 8 - j % 8;
-            int adr = abs(dr), adc = abs(dc);
-            bool vis = dr == 0 || dc == 0 || adr == adc || (adr == 2 && adc == 1) || (adr == 1 && adc == 2) ||
-                       (adr <= 1 && adc <= 1);
-            if (vis) m[i] |= (1ull << j);
-        }
-    mask_dev_ = (uint64_t*)dalloc(64 * 8, false);
-    (void)hipMemcpy(mask_dev_, m.data(), 64 * 8, hipMemcpyHostToDevice);
-}
-
-// policy_head.0 (64 channels) and value_head.0 (128) read the same trunk: one GEMM with N = 192, columns [policy | value], both
-// in the small-tile layout [Cin / 32][N][32]; GroupNorm parameters concatenated the same way.  Built from the two packed
-// convs and their norms as they were uploaded.
-int Net::pack_joint_head(std::string& err) {
-    const int nch = Cp_ / 32;
-    std::vector<_Float16> a((size_t)nch * 64 * 32), b((size_t)nch * 128 * 32), c((size_t)nch * 192 * 32);
-    (void)hipMemcpy(a.data(), ph_conv_.w, a.size() * 2, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(b.data(), vh0_.w, b.size() * 2, hipMemcpyDeviceToHost);
-    for (int ch = 0; ch < nch; ++ch) {
-        std::copy(a.begin() + (size_t)ch * 64 * 32, a.begin() + (size_t)(ch + 1) * 64 * 32, c.begin() + (size_t)ch * 192 * 32);
-        std::copy(b.begin() + (size_t)ch * 128 * 32, b.begin() + (size_t)(ch + 1) * 128 * 32, c.begin() + ((size_t)ch * 192 + 64) * 32);
-    }
-    hv_.w = (_Float16*)dalloc(c.size() * 2, false);
-    if (!hv_.w) { err = "hipMalloc failed"; return M0_ERR_HIP; }
-    (void)hipMemcpy(hv_.w, c.data(), c.size() * 2, hipMemcpyHostToDevice);
-    hv_.taps = 1; hv_.Cin = Cp_; hv_.N = 192; hv_.pp = false; hv_.bias = nullptr;
-    std::vector<float> g(192), be(192);
-    (void)hipMemcpy(g.data(), ph_n_.gamma, 64 * 4, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(g.data() + 64, vh1_n_.gamma, 128 * 4, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(be.data(), ph_n_.beta, 64 * 4, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(be.data() + 64, vh1_n_.beta, 128 * 4, hipMemcpyDeviceToHost);
-    hv_n_.gamma = upload_f32(g); hv_n_.beta = upload_f32(be);
-    if (!hv_n_.gamma || !hv_n_.beta) { err = "hipMalloc failed"; return M0_ERR_HIP; }
-    return M0_OK;
-}
-
-int Net::pack_ssl_heads(std::string& err) {
-    for (int t = 0; t < 5; ++t) {
-        if (!(cfg_.ssl_tasks & (1 << t))) continue;
-        SslHeadW h;
-        h.out_ch = kSslOut[t];
-        std::string p = std::string("ssl_heads.") + kSslNames[t];
-        TRY(pack_gemm(h.c0, p + ".0.weight", "", 1, C_, Cp_, C_ / 2, Cs_, 0, err));
-        TRY(upload_norm(h.n, p + ".1", C_ / 2, Cs_, err));
-        TRY(pack_gemm(h.c1, p + ".3.weight", "", 1, C_ / 2, Cs_, h.out_ch, 32, 0, err));
-        ssl_.push_back(h);
-    }
-    return M0_OK;
-}
-
-// The schedule choices that do not depend on the batch (Plan, TowerLayer::next_bn1): see net.h.
-void Net::make_plan() {
-    const bool big = conv_gemm_tile_n(Cp_, Cp_) == 320;     // 320-wide trunk: conv_zs_kernel / conv_big_kernel with their epilogues
-    // a squeeze-excite wider than the fused tail takes runs conv2 + se_gate + ew_board instead, as M0_FUSE_TAIL=0 does
-    plan_.fuse_tail = big && sw_.fuse_tail &&
-                      (!cfg_.se || (res_[0].se_hidden <= TAIL_SE_HMAX && res_[0].se_hidden % 4 == 0));
-    plan_.fuse_attn = big && sw_.fuse_attn;
-    plan_.gn_small = Cp_ % 64 == 0;
-    plan_.act = cfg_.activation == M0_ACT_SILU ? ACT_SILU : ACT_RELU;
-    plan_.vact = cfg_.value_activation == M0_ACT_SILU ? ACT_SILU : (cfg_.value_activation == M0_ACT_LEAKY ? ACT_LEAKY : ACT_RELU);
-    int next = -1;                      // walking up from the end: the residual block that follows position i
-    for (size_t i = tower_.size(); i-- > 0;) {
-        TowerLayer& L = tower_[i];
-        if (L.kind == 1 && L.skip) continue;
-        L.next_bn1 = next;
-        next = L.kind == 0 ? L.index : -1;
-    }
-    plan_.first_bn1 = next;
-}
-
-int Net::finalize(std::string& err) {
-    if (finalized_) return M0_OK;
-    if (hipSetDevice(device_) != hipSuccess) { err = "hipSetDevice failed"; return M0_ERR_HIP; }
-    const int C = C_, P = Cp_;          // real / in-memory trunk width (padded channels carry zeros everywhere)
-    nparams_ = 0;
-    TRY(pack_gemm(stem_, "stem.0.weight", "", 9, cfg_.planes, 32, C, P, 0, err));
-    TRY(upload_norm(stem_n_, "stem.1", C, P, err));
-    if (cfg_.chess_features) TRY(pack_chess_features(err));
-    int ti = 0;
-    for (auto& L : tower_) {
-        std::string p = "tower." + std::to_string(ti++);
-        if (L.kind == 0) {
-            ResBlockW& r = res_[L.index];
-            TRY(pack_gemm(r.conv1, p + ".conv1.weight", "", 9, C, P, C, P, 0, err));
-            TRY(pack_gemm(r.conv2, p + ".conv2.weight", "", 9, C, P, C, P, 0, err));
-            TRY(upload_norm(r.bn1, p + ".bn1", C, P, err));
-            TRY(upload_norm(r.bn2, p + ".bn2", C, P, err));
-            if (cfg_.se) TRY(pack_se(r, p, err));
-        } else {
-            TRY(pack_attn(att_[L.index], L.skip, p, err));
-        }
-    }
-    upload_attn_mask();
-    // policy head
-    TRY(pack_gemm(ph_conv_, "policy_head.0.weight", "", 1, C, P, 64, 64, 0, err));
-    TRY(upload_norm(ph_n_, "policy_head.1", 64, 64, err));
-    if (cfg_.policy_factor_rank > 0) {
-        int r = cfg_.policy_factor_rank, rp = ceil_to(r, 32);
-        TRY(pack_gemm(pfc1_, "policy_fc1.weight", "policy_fc1.bias", 1, 4096, 4096, r, rp, 64, err));
-        TRY(pack_gemm(pfc2_, "policy_fc2.weight", "policy_fc2.bias", 1, r, rp, M0_POLICY_SIZE, M0_POLICY_SIZE, 0, err));
-    } else {
-        TRY(pack_gemm(pfc1_, "policy_fc.weight", "policy_fc.bias", 1, 4096, 4096, M0_POLICY_SIZE, M0_POLICY_SIZE, 64, err));
-    }
-    {
-        const HostTensor* ls = get("_policy_logit_scale_raw", err); if (!ls) return M0_ERR_INVALID;
-        nparams_ += 1;
-        double raw = ls->data.empty() ? 0.0 : ls->data[0];
-        double sp = raw > 20.0 ? raw : log1p(exp(raw));
-        logit_scale_ = (float)std::min(5.0, sp + 1e-3);
-    }
-    // value head
-    TRY(pack_gemm(vh0_, "value_head.0.weight", "", 1, C, P, 128, 128, 0, err));
-    TRY(upload_norm(vh1_n_, "value_head.1", 128, 128, err));
-    TRY(pack_gemm(vh3_, "value_head.3.weight", "", 1, 128, 128, 128, 128, 0, err));
-    TRY(upload_norm(vh4_n_, "value_head.4", 128, 128, err));
-    TRY(pack_joint_head(err));
-    const int h1 = 2 * C, h1p = ceil_to(h1, 32), h2 = C, h2p = ceil_to(C, 32);
-    TRY(pack_gemm(vfc1_, "value_fc1.weight", "value_fc1.bias", 1, 8192, 8192, h1, h1p, 128, err));
-    TRY(pack_gemm(vfc2_, "value_fc2.weight", "value_fc2.bias", 1, h1, h1p, h2, h2p, 0, err));
-    TRY(pack_gemm(vgate_, "value_gate.0.weight", "value_gate.0.bias", 1, h2, h2p, h2, h2p, 0, err));
-    TRY(pack_gemm(vfc3_, "value_fc3.weight", "value_fc3.bias", 1, h2, h2p, 1, 32, 0, err));
-    if (cfg_.self_supervised) TRY(pack_ssl_heads(err));
-    sd_.clear();
-    (void)hipDeviceSynchronize();       // uploads (blocking NULL-stream copies) have landed before any non-blocking stream reads them
-    make_plan();
-    finalized_ = true;
-    return M0_OK;
 }
 
 int Net::ssl_channels_total() const {
@@ -693,7 +292,7 @@ int Net::forward(const float* planes_dev, const _Float16* nhwc_dev, int B, float
                  float* ssl_dev, hipStream_t st, std::string& err) {
     if (!finalized_) { err = "weights not finalized"; return M0_ERR_STATE; }
     if (B <= 0) { err = "batch must be positive"; return M0_ERR_INVALID; }
-    TRY(ensure_workspace(B, err));
+    if (int rc = ensure_workspace(B, err)) return rc;
     const int Bp = ceil_to(B, 4);
     const int Mc = Bp * 64;
     const int Mfc = ceil_to(B, 256);

@@ -22,7 +22,7 @@ def shard_games(total_games: int, rank: int, world: int) -> Tuple[int, int]:
 
 
 def is_gemm_weight(name: str, shape) -> bool:
-    """Tensors the engine packs as fp16 MFMA operands (csrc/net.hip pack_gemm / pack_attn_block): conv and fully
+    """Tensors the engine packs as fp16 MFMA operands (csrc/net_pack.hip pack_gemm / pack_attn): conv and fully
     connected weight matrices.  Everything else (norm gains and biases, squeeze-excite, positional encoding, relative
     position bias, the logit scale) is consumed in fp32."""
     return name.endswith(".weight") and len(shape) >= 2 and ".se_fc" not in name

@@ -39,6 +39,16 @@ SHIMS = {
         "tbs_order": (i32, [cstr, cstr, i32]),
         "tbs_all_signatures": (i32, [i32, cstr, i32]),
     },
+    "pack": {                                           # csrc/net_pack.h, int32 -> int32; (..., out, capacity) -> length
+        "pk_gemm": (i64, [vp] + [i32] * 9 + [vp, i64]),
+        "pk_attn_weights": (i64, [vp, vp, i32, vp, i64]),
+        "pk_attn_bias": (i64, [vp, i32, vp, i64]),
+        "pk_zero_padded": (i64, [vp, i64, i64, vp, i64]),
+        "pk_transposed": (i64, [vp, i32, i32, i32, i32, vp, i64]),
+        "pk_se_fragments": (i64, [vp, vp, i32, i32, vp, i64]),
+        "pk_attn_mask": (None, [vp]),
+        "pk_joint_columns": (i64, [vp, i32, vp, i32, i32, vp, i64]),
+    },
 }
 
 

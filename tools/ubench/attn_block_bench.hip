@@ -4,6 +4,7 @@
 // The first 4 boards are compared with a plain fp32 CPU computation of the block (qkv and O rounded to fp16 where the
 // kernel rounds them); then the launch is timed.
 #include "../../matrix0_amd/csrc/attn_block.hip"
+#include "../../matrix0_amd/csrc/net_pack.h"
 #ifdef AB_AFTER_CONV   // every attention launch behind six conv_zs launches, as in the tower (is its in-network time the convs' clock?)
 #include "../../matrix0_amd/csrc/conv_zs.hip"
 #endif
@@ -12,43 +13,6 @@
 #include <string.h>
 #include <vector>
 #include <algorithm>
-
-static void pack(const std::vector<float>& wq, const std::vector<float>& wp, const std::vector<float>& rb,
-                 std::vector<_Float16>& buf, std::vector<_Float16>& bb) {
-    const int Cr = 320;
-    buf.assign(attn_block_pack_bytes() / 2, (_Float16)0.f);
-    for (int g = 0; g < 10; ++g) {
-        for (int pc = 0; pc < 5; ++pc) {
-            const size_t base = (size_t)(g * 7 + pc) * 6144;
-            for (int col = 0; col < 96; ++col) {
-                const int J = col >> 4, type = J >> 1, hl = J & 1, d = col & 15;
-                for (int k = 0; k < 64; ++k) {
-                    const int pos = (k >> 3) ^ ((col >> 1) & 7);
-                    buf[base + (size_t)col * 64 + pos * 8 + (k & 7)] =
-                        (_Float16)wq[(size_t)((type * 20 + 2 * g + hl) * 16 + d) * Cr + 64 * pc + k];
-                }
-            }
-        }
-        for (int hh = 0; hh < 2; ++hh) {
-            const size_t base = (size_t)(g * 7 + 5 + hh) * 6144;
-            for (int cl = 0; cl < 160; ++cl)
-                for (int k = 0; k < 32; ++k) {
-                    const int pos = (k >> 3) ^ ((4 - ((cl >> 2) & 3)) & 3);
-                    buf[base + (size_t)cl * 32 + pos * 8 + (k & 7)] =
-                        (_Float16)wp[(size_t)(160 * hh + cl) * Cr + (2 * g + (k >> 4)) * 16 + (k & 15)];
-                }
-        }
-    }
-    bb.assign((size_t)20 * 2 * 64 * 32, (_Float16)0.f);
-    for (int h = 0; h < 20; ++h)
-        for (int qt = 0; qt < 2; ++qt)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 32; ++e) {
-                    const int kt = e >> 4, r = e & 15;
-                    const int q = qt * 32 + (lane & 31), key = kt * 32 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
-                    bb[(((size_t)h * 2 + qt) * 64 + lane) * 32 + e] = (_Float16)(rb[((size_t)h * 64 + q) * 64 + key] * kLog2e);
-                }
-}
 
 int main(int argc, char** argv) {
     const int boards = argc > 1 ? atoi(argv[1]) : 4096;
@@ -68,15 +32,11 @@ int main(int argc, char** argv) {
     // the last 4 boards repeat the first 4: a workgroup walks several board pairs, these are handled in a LAST pass (rows
     // that travelled through registers), so their outputs must equal the first 4 boards' bit for bit
     if (boards >= 8) memcpy(&hx[(size_t)(boards - 4) * 64 * C], &hx[0], (size_t)4 * 64 * C * 2);
-    std::vector<uint64_t> mask(64, 0);
-    for (int i = 0; i < 64; ++i)
-        for (int j = 0; j < 64; ++j) {
-            int dr = i / 8 - j / 8, dc = i % 8 - j % 8, adr = abs(dr), adc = abs(dc);
-            bool vis = dr == 0 || dc == 0 || adr == adc || (adr == 2 && adc == 1) || (adr == 1 && adc == 2);
-            if (vis) mask[i] |= 1ull << j;
-        }
-    std::vector<_Float16> buf, bb;
-    pack(wq, wp, rb, buf, bb);
+    const std::vector<uint64_t> mask = net_pack::attn_mask();
+    std::vector<float> rbs(rb.size());
+    for (size_t i = 0; i < rb.size(); ++i) rbs[i] = rb[i] * kLog2e;
+    const std::vector<_Float16> buf = net_pack::attn_block_weights<_Float16>(wq.data(), wp.data(), H);
+    const std::vector<_Float16> bb = net_pack::attn_block_bias<_Float16>(rbs.data(), H);
     _Float16 *dx, *dy, *dy2, *dbb; void* dw; uint64_t* dm; float *dlg, *dlb, *dg2, *db2;
     hipMalloc(&dx, M * C * 2); hipMalloc(&dy, M * C * 2); hipMalloc(&dy2, M * C * 2); hipMalloc(&dw, buf.size() * 2);
     hipMalloc(&dbb, bb.size() * 2); hipMalloc(&dm, 512); hipMalloc(&dlg, C * 4); hipMalloc(&dlb, C * 4);
