@@ -13,7 +13,10 @@
  *   for callers that keep python-chess:  m0_encode_fens, m0_move_to_index_fen.
  *
  * Conventions: every function returns 0 on success or a negative code; the message is
- * available from m0_last_error() (thread-local).  No exception crosses the ABI.  All buffers
+ * available from m0_last_error() (thread-local).  After M0_ERR_HIP from a call on a network or
+ * engine handle every later device call on that handle returns M0_ERR_HIP with the first
+ * failure's message and starts nothing on the GPU: destroy the handle.  (Calls that only read
+ * host state -- m0_selfplay_stats_get, _poll, _running -- still answer.)  No exception crosses the ABI.  All buffers
  * are caller-allocated host memory unless a parameter says "_dev".  Handles are opaque.
  * The library never falls back to a CPU path: without a HIP device m0_net_create fails.
  */

@@ -83,19 +83,18 @@ int analysis_harvest(m0_selfplay* sp) {
         if (sp->hg[s].active && sp->hg[s].finished) a.finished.push_back(s);
     const int nf = (int)a.finished.size();
     if (nf == 0) return M0_OK;
-    if (hipMemcpyAsync(sp->ids_dev, a.finished.data(), (size_t)nf * 4, hipMemcpyHostToDevice, sp->stream) != hipSuccess ||
-        launch_analysis_lines(sp->d, sp->ids_dev, nf, a.opts.multipv, a.opts.pv_len, a.lines_dev, a.nlines_dev, sp->stream) != hipSuccess ||
-        hipMemcpyAsync(a.hlines.data(), a.lines_dev, sizeof(m0_analysis_line) * M0_AN_MAX_LINES * nf, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
-        hipMemcpyAsync(a.hnlines.data(), a.nlines_dev, (size_t)nf * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
-        (a.keep_visits &&          // the root children of the same searches, in the same trip
-         (launch_root_children(sp->d, sp->ids_dev, nf, a.child_idx_dev, a.child_n_dev, a.nchild_dev, sp->stream) != hipSuccess ||
-          hipMemcpyAsync(a.hchild_idx.data(), a.child_idx_dev, (size_t)nf * M0_MAX_CHILDREN * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
-          hipMemcpyAsync(a.hchild_n.data(), a.child_n_dev, (size_t)nf * M0_MAX_CHILDREN * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
-          hipMemcpyAsync(a.hnchild.data(), a.nchild_dev, (size_t)nf * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess)) ||
-        hipStreamSynchronize(sp->stream) != hipSuccess) {
-        m0_set_error(std::string("analysis harvest failed: ") + hipGetErrorString(hipGetLastError()));
-        return M0_ERR_HIP;
+    HipStatus& hs = sp->hip;
+    M0_HIP(hs, hipMemcpyAsync(sp->ids_dev, a.finished.data(), (size_t)nf * 4, hipMemcpyHostToDevice, sp->stream));
+    M0_HIP(hs, launch_analysis_lines(sp->d, sp->ids_dev, nf, a.opts.multipv, a.opts.pv_len, a.lines_dev, a.nlines_dev, sp->stream));
+    M0_HIP(hs, hipMemcpyAsync(a.hlines.data(), a.lines_dev, sizeof(m0_analysis_line) * M0_AN_MAX_LINES * nf, hipMemcpyDeviceToHost, sp->stream));
+    M0_HIP(hs, hipMemcpyAsync(a.hnlines.data(), a.nlines_dev, (size_t)nf * 4, hipMemcpyDeviceToHost, sp->stream));
+    if (a.keep_visits) {           // the root children of the same searches, in the same trip
+        M0_HIP(hs, launch_root_children(sp->d, sp->ids_dev, nf, a.child_idx_dev, a.child_n_dev, a.nchild_dev, sp->stream));
+        M0_HIP(hs, hipMemcpyAsync(a.hchild_idx.data(), a.child_idx_dev, (size_t)nf * M0_MAX_CHILDREN * 4, hipMemcpyDeviceToHost, sp->stream));
+        M0_HIP(hs, hipMemcpyAsync(a.hchild_n.data(), a.child_n_dev, (size_t)nf * M0_MAX_CHILDREN * 4, hipMemcpyDeviceToHost, sp->stream));
+        M0_HIP(hs, hipMemcpyAsync(a.hnchild.data(), a.nchild_dev, (size_t)nf * 4, hipMemcpyDeviceToHost, sp->stream));
     }
+    if (!M0_HIP(hs, hipStreamSynchronize(sp->stream))) return m0_hip_error(hs, "analysis harvest failed");
     for (int j = 0; j < nf; ++j) {
         const int s = a.finished[j];
         GameDev& g = sp->hg[s];
@@ -117,8 +116,7 @@ int analysis_harvest(m0_selfplay* sp) {
         g.active = 0; g.finished = 0;
         sp->games[s].in_use = false;
     }
-    if (sync_games_h2d(sp) != 0) { m0_set_error("releasing the slots failed"); return M0_ERR_HIP; }
-    return M0_OK;
+    return sync_games_h2d(sp) ? M0_OK : m0_hip_error(hs, "releasing the slots failed");
 }
 
 // Policy mode: up to rows_max queued positions -> network input, legal moves and policy indices (the position encoder), one
@@ -129,25 +127,21 @@ static int policy_pass(m0_selfplay* sp) {
     if (n <= 0) return M0_OK;
     const double t0 = now_ms();
     for (int i = 0; i < n; ++i) a.hpos[i] = a.policy_queue[i].line.pos;
-    if (hipMemcpyAsync(a.pos_dev, a.hpos.data(), sizeof(Pos) * n, hipMemcpyHostToDevice, sp->stream) != hipSuccess ||
-        launch_encode_positions(a.pos_dev, n, nullptr, sp->d.x0, nullptr, a.nlegal_dev, a.moves_dev, a.idx_dev, sp->stream) != hipSuccess) {
-        m0_set_error("position encode failed");
-        return M0_ERR_HIP;
-    }
+    HipStatus& hs = sp->hip;
+    M0_HIP(hs, hipMemcpyAsync(a.pos_dev, a.hpos.data(), sizeof(Pos) * n, hipMemcpyHostToDevice, sp->stream));
+    if (!M0_HIP(hs, launch_encode_positions(a.pos_dev, n, nullptr, sp->d.x0, nullptr, a.nlegal_dev, a.moves_dev, a.idx_dev, sp->stream)))
+        return m0_hip_error(hs, "position encode failed");
     std::string err;
     m0_net_lock(sp->nethandle);
     const int rc = sp->net->forward(nullptr, sp->d.x0, n, sp->logits_dev, sp->values_dev, nullptr, sp->stream, err);
     m0_net_unlock(sp->nethandle);
-    if (rc != M0_OK) { m0_set_error(err); return rc; }
-    if (launch_policy_lines(sp->logits_dev, sp->values_dev, a.nlegal_dev, a.moves_dev, a.idx_dev, n, a.opts.multipv, a.lines_dev,
-                            a.nlines_dev, a.value_out_dev, sp->stream) != hipSuccess ||
-        hipMemcpyAsync(a.hlines.data(), a.lines_dev, sizeof(m0_analysis_line) * M0_AN_MAX_LINES * n, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
-        hipMemcpyAsync(a.hnlines.data(), a.nlines_dev, (size_t)n * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
-        hipMemcpyAsync(a.hvalues.data(), a.value_out_dev, (size_t)n * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
-        hipStreamSynchronize(sp->stream) != hipSuccess) {
-        m0_set_error(std::string("policy pass failed: ") + hipGetErrorString(hipGetLastError()));
-        return M0_ERR_HIP;
-    }
+    if (rc != M0_OK) { hs.check(sp->net->hip()); m0_set_error(err); return rc; }
+    M0_HIP(hs, launch_policy_lines(sp->logits_dev, sp->values_dev, a.nlegal_dev, a.moves_dev, a.idx_dev, n, a.opts.multipv, a.lines_dev,
+                                   a.nlines_dev, a.value_out_dev, sp->stream));
+    M0_HIP(hs, hipMemcpyAsync(a.hlines.data(), a.lines_dev, sizeof(m0_analysis_line) * M0_AN_MAX_LINES * n, hipMemcpyDeviceToHost, sp->stream));
+    M0_HIP(hs, hipMemcpyAsync(a.hnlines.data(), a.nlines_dev, (size_t)n * 4, hipMemcpyDeviceToHost, sp->stream));
+    M0_HIP(hs, hipMemcpyAsync(a.hvalues.data(), a.value_out_dev, (size_t)n * 4, hipMemcpyDeviceToHost, sp->stream));
+    if (!M0_HIP(hs, hipStreamSynchronize(sp->stream))) return m0_hip_error(hs, "policy pass failed");
     for (int i = 0; i < n; ++i) {
         m0_analysis_result r = blank_result(a.policy_queue.front());
         r.evals = 1;
@@ -197,11 +191,8 @@ static m0_selfplay* analysis_create_impl(m0_net* nh, const m0_selfplay_cfg* cfg,
         a->moves_dev = dalloc<uint16_t>(sp, R * M0_MAX_MOVES);
         a->idx_dev = dalloc<int32_t>(sp, R * M0_MAX_MOVES);
     }
-    if (sp->alloc_failed || hipStreamSynchronize(sp->stream) != hipSuccess) {
-        m0_set_error("hipMalloc failed for the analysis result buffers");
-        return nullptr;
-    }
-    return owner.release();
+    M0_HIP(sp->hip, hipStreamSynchronize(sp->stream));
+    return hip_ok(sp, "hipMalloc failed for the analysis result buffers") ? owner.release() : nullptr;
 }
 
 }  // namespace m0
@@ -245,21 +236,19 @@ int m0_analysis_submit_planes(m0_selfplay* sp, const float* planes, const uint8_
     // decoded on the engine's device and stream; the buffers live for this call
     const size_t N = (size_t)n;
     DevBuf<float> dpl; DevBuf<uint8_t> dm; DevBuf<Pos> dp; DevBuf<int32_t> dst, dfl, dnl;
-    if (!dpl.alloc(N * M0_PLANES * 64) || (mask && !dm.alloc(N * M0_POLICY_SIZE)) || !dp.alloc(N) || !dst.alloc(N) || !dfl.alloc(N) ||
-        !dnl.alloc(N)) { m0_set_error("hipMalloc failed"); return M0_ERR_HIP; }
+    HipStatus& hs = sp->hip; HipStatus as;   // `as`: a batch too large for the call's own buffers is refused, the engine lives on
+    if (!dpl.alloc(as, N * M0_PLANES * 64) || (mask && !dm.alloc(as, N * M0_POLICY_SIZE)) || !dp.alloc(as, N) || !dst.alloc(as, N) ||
+        !dfl.alloc(as, N) || !dnl.alloc(as, N)) return m0_hip_error(as, "hipMalloc failed");
     std::vector<Pos> hp(N);
     std::vector<int32_t> hfl(N), hnl(N);
-    if (hipMemcpyAsync(dpl.p, planes, N * M0_PLANES * 64 * sizeof(float), hipMemcpyHostToDevice, sp->stream) != hipSuccess ||
-        (mask && hipMemcpyAsync(dm.p, mask, N * M0_POLICY_SIZE, hipMemcpyHostToDevice, sp->stream) != hipSuccess) ||
-        launch_decode_planes(dpl.p, dm.p, n, dp.p, dst.p, dfl.p, dnl.p, sp->stream) != hipSuccess ||
-        hipMemcpyAsync(hp.data(), dp.p, N * sizeof(Pos), hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
-        hipMemcpyAsync(status, dst.p, N * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
-        hipMemcpyAsync(hfl.data(), dfl.p, N * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
-        hipMemcpyAsync(hnl.data(), dnl.p, N * 4, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
-        hipStreamSynchronize(sp->stream) != hipSuccess) {
-        m0_set_error(std::string("decoding the planes failed: ") + hipGetErrorString(hipGetLastError()));
-        return M0_ERR_HIP;
-    }
+    M0_HIP(hs, hipMemcpyAsync(dpl.p, planes, N * M0_PLANES * 64 * sizeof(float), hipMemcpyHostToDevice, sp->stream));
+    if (mask) M0_HIP(hs, hipMemcpyAsync(dm.p, mask, N * M0_POLICY_SIZE, hipMemcpyHostToDevice, sp->stream));
+    M0_HIP(hs, launch_decode_planes(dpl.p, dm.p, n, dp.p, dst.p, dfl.p, dnl.p, sp->stream));
+    M0_HIP(hs, hipMemcpyAsync(hp.data(), dp.p, N * sizeof(Pos), hipMemcpyDeviceToHost, sp->stream));
+    M0_HIP(hs, hipMemcpyAsync(status, dst.p, N * 4, hipMemcpyDeviceToHost, sp->stream));
+    M0_HIP(hs, hipMemcpyAsync(hfl.data(), dfl.p, N * 4, hipMemcpyDeviceToHost, sp->stream));
+    M0_HIP(hs, hipMemcpyAsync(hnl.data(), dnl.p, N * 4, hipMemcpyDeviceToHost, sp->stream));
+    if (!M0_HIP(hs, hipStreamSynchronize(sp->stream))) return m0_hip_error(hs, "decoding the planes failed");
     if (flags) memcpy(flags, hfl.data(), N * 4);
     for (int i = 0; i < n; ++i) {
         if (status[i] != M0_DECODE_OK) continue;             // reported, not queued
@@ -280,7 +269,7 @@ int m0_analysis_keep_visits(m0_selfplay* sp, int on) {
         a.child_idx_dev = dalloc<int32_t>(sp, G * M0_MAX_CHILDREN);
         a.child_n_dev = dalloc<int32_t>(sp, G * M0_MAX_CHILDREN);
         a.nchild_dev = dalloc<int32_t>(sp, G);
-        if (sp->alloc_failed) { a.child_idx_dev = nullptr; m0_set_error("hipMalloc failed for the root-children buffers"); return M0_ERR_HIP; }
+        if (!sp->hip.ok()) { a.child_idx_dev = nullptr; return m0_hip_error(sp->hip, "hipMalloc failed for the root-children buffers"); }
         a.hchild_idx.resize(G * M0_MAX_CHILDREN);
         a.hchild_n.resize(G * M0_MAX_CHILDREN);
         a.hnchild.resize(G);

@@ -3,9 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <string>
 #include "../../include/m0_engine.h"
+#include "hip_check.h"
 
 class Net;
-void m0_set_error(const std::string& s);
 Net* m0_net_impl(m0_net* n);
 hipStream_t m0_net_stream(m0_net* n);
 int m0_net_device(m0_net* n);
@@ -25,6 +25,6 @@ struct DevBuf {
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
     ~DevBuf() { if (p) (void)hipFree(p); }
-    bool alloc(size_t count) { return hipMalloc((void**)&p, count * sizeof(T)) == hipSuccess; }
-    void download(T* host, size_t count) const { (void)hipMemcpy(host, p, count * sizeof(T), hipMemcpyDeviceToHost); }
+    bool alloc(HipStatus& st, size_t count) { return M0_HIP(st, hipMalloc((void**)&p, count * sizeof(T))); }
+    bool download(HipStatus& st, T* host, size_t count) const { return M0_HIP(st, hipMemcpy(host, p, count * sizeof(T), hipMemcpyDeviceToHost)); }
 };

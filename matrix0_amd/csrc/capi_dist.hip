@@ -120,9 +120,10 @@ int m0_net_broadcast_weights(m0_net* n, m0_dist* d, int root) {
     if (m0_net_device(n) != d->device) { m0_set_error("network and communicator are on different devices"); return M0_ERR_INVALID; }
     Rccl* r = rccl();
     if (!r) { m0_set_error("RCCL unavailable"); return M0_ERR_UNSUPPORTED; }
-    if (hipSetDevice(d->device) != hipSuccess) { m0_set_error("hipSetDevice failed"); return M0_ERR_HIP; }
+    HipStatus hs;                                       // the HIP calls around the collectives; a collective is issued only while it is good
+    if (!M0_HIP(hs, hipSetDevice(d->device))) return m0_hip_error(hs);
     m0_net_lock(n);                                     // no forward of this network while its weights change
-    (void)hipStreamSynchronize(m0_net_stream(n));
+    M0_HIP(hs, hipStreamSynchronize(m0_net_stream(n)));
     const std::vector<void*>& bufs = net->device_buffers();
     const std::vector<size_t>& bytes = net->device_buffer_bytes();
     int rc = M0_OK;
@@ -132,14 +133,14 @@ int m0_net_broadcast_weights(m0_net* n, m0_dist* d, int root) {
         uint64_t sig[4] = {bufs.size(), 0, 0x9E3779B97F4A7C15ull, 0};
         for (size_t i = 0; i < bytes.size(); ++i) { sig[1] += bytes[i]; sig[2] = (sig[2] ^ bytes[i]) * 0x100000001B3ull + i; }
         uint64_t mx[4], mn[4];
-        (void)hipMemcpyAsync(d->scratch, sig, sizeof(sig), hipMemcpyHostToDevice, d->stream);
-        int e = r->AllReduce(d->scratch, d->scratch, 4, ncclUint64, ncclMax, d->comm, d->stream);
-        if (e == ncclSuccess) (void)hipMemcpyAsync(mx, d->scratch, sizeof(mx), hipMemcpyDeviceToHost, d->stream);
-        if (e == ncclSuccess) (void)hipMemcpyAsync(d->scratch, sig, sizeof(sig), hipMemcpyHostToDevice, d->stream);
-        if (e == ncclSuccess) e = r->AllReduce(d->scratch, d->scratch, 4, ncclUint64, ncclMin, d->comm, d->stream);
-        if (e == ncclSuccess) (void)hipMemcpyAsync(mn, d->scratch, sizeof(mn), hipMemcpyDeviceToHost, d->stream);
+        M0_HIP(hs, hipMemcpyAsync(d->scratch, sig, sizeof(sig), hipMemcpyHostToDevice, d->stream));
+        int e = hs.ok() ? r->AllReduce(d->scratch, d->scratch, 4, ncclUint64, ncclMax, d->comm, d->stream) : ncclSuccess;
+        if (e == ncclSuccess) M0_HIP(hs, hipMemcpyAsync(mx, d->scratch, sizeof(mx), hipMemcpyDeviceToHost, d->stream));
+        if (e == ncclSuccess) M0_HIP(hs, hipMemcpyAsync(d->scratch, sig, sizeof(sig), hipMemcpyHostToDevice, d->stream));
+        if (e == ncclSuccess && hs.ok()) e = r->AllReduce(d->scratch, d->scratch, 4, ncclUint64, ncclMin, d->comm, d->stream);
+        if (e == ncclSuccess) M0_HIP(hs, hipMemcpyAsync(mn, d->scratch, sizeof(mn), hipMemcpyDeviceToHost, d->stream));
         if (e != ncclSuccess) { m0_set_error(rccl_err("ncclAllReduce", e)); rc = M0_ERR_HIP; break; }
-        if (hipStreamSynchronize(d->stream) != hipSuccess) { m0_set_error("broadcast: stream failed"); rc = M0_ERR_HIP; break; }
+        if (!M0_HIP(hs, hipStreamSynchronize(d->stream))) { rc = m0_hip_error(hs, "broadcast: stream failed"); break; }
         if (memcmp(mx, mn, sizeof(mx)) != 0) {
             m0_set_error("broadcast: the ranks hold networks of different configurations (buffer lists differ)");
             rc = M0_ERR_INVALID;
@@ -149,7 +150,7 @@ int m0_net_broadcast_weights(m0_net* n, m0_dist* d, int root) {
             e = r->Broadcast(bufs[i], bufs[i], bytes[i], ncclInt8, root, d->comm, d->stream);
             if (e != ncclSuccess) { m0_set_error(rccl_err("ncclBroadcast", e)); rc = M0_ERR_HIP; }
         }
-        if (rc == M0_OK && hipStreamSynchronize(d->stream) != hipSuccess) { m0_set_error("broadcast: stream failed"); rc = M0_ERR_HIP; }
+        if (rc == M0_OK && !M0_HIP(hs, hipStreamSynchronize(d->stream))) rc = m0_hip_error(hs, "broadcast: stream failed");
     } while (0);
     m0_net_unlock(n);
     return rc;

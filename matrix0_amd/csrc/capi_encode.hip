@@ -15,16 +15,15 @@ using namespace m0;
 namespace {
 
 // selects the device, parses the n FENs and puts the positions on it
-int upload_fens(int hip_device, const char* const* fens, int n, DevBuf<Pos>& dp) {
+int upload_fens(HipStatus& hs, int hip_device, const char* const* fens, int n, DevBuf<Pos>& dp) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { m0_set_error("no HIP device available (no CPU fallback)"); return M0_ERR_HIP; }
-    if (hipSetDevice(hip_device) != hipSuccess) { m0_set_error("hipSetDevice failed"); return M0_ERR_HIP; }
+    if (!M0_HIP(hs, hipSetDevice(hip_device))) return m0_hip_error(hs);
     std::vector<Pos> hp(n);
     for (int i = 0; i < n; ++i)
         if (!fens[i] || parse_fen(fens[i], hp[i]) != 0) { m0_set_error(std::string("bad FEN at index ") + std::to_string(i)); return M0_ERR_INVALID; }
-    if (!dp.alloc(n)) { m0_set_error("hipMalloc failed"); return M0_ERR_HIP; }
-    (void)hipMemcpy(dp.p, hp.data(), sizeof(Pos) * n, hipMemcpyHostToDevice);
-    return M0_OK;
+    dp.alloc(hs, n);
+    return M0_HIP(hs, hipMemcpy(dp.p, hp.data(), sizeof(Pos) * n, hipMemcpyHostToDevice)) ? M0_OK : m0_hip_error(hs, "position upload failed");
 }
 
 }  // namespace
@@ -35,47 +34,47 @@ int m0_encode_fens(int hip_device, const char* const* fens, int n, float* planes
                    uint16_t* moves, int32_t* idx) {
     if (!fens || n <= 0) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
     DevBuf<Pos> dp;
-    const int rc = upload_fens(hip_device, fens, n, dp);
+    HipStatus hs;
+    const int rc = upload_fens(hs, hip_device, fens, n, dp);
     if (rc != M0_OK) return rc;
     const size_t N = (size_t)n;
     DevBuf<float> dpl; DevBuf<uint8_t> dm; DevBuf<int32_t> dn; DevBuf<uint16_t> dmv; DevBuf<int32_t> di;
-    if ((planes && !dpl.alloc(N * 19 * 64)) || (mask && !dm.alloc(N * 4672)) || (nlegal && !dn.alloc(N)) ||
-        (moves && !dmv.alloc(N * M0_MAX_MOVES)) || (idx && !di.alloc(N * M0_MAX_MOVES))) { m0_set_error("hipMalloc failed"); return M0_ERR_HIP; }
-    if (launch_encode_positions(dp.p, n, dpl.p, nullptr, dm.p, dn.p, dmv.p, di.p, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-        m0_set_error("encode kernel failed");
-        return M0_ERR_HIP;
-    }
-    if (planes) dpl.download(planes, N * 19 * 64);
-    if (mask) dm.download(mask, N * 4672);
-    if (nlegal) dn.download(nlegal, N);
-    if (moves) dmv.download(moves, N * M0_MAX_MOVES);
-    if (idx) di.download(idx, N * M0_MAX_MOVES);
-    return M0_OK;
+    if ((planes && !dpl.alloc(hs, N * 19 * 64)) || (mask && !dm.alloc(hs, N * 4672)) || (nlegal && !dn.alloc(hs, N)) ||
+        (moves && !dmv.alloc(hs, N * M0_MAX_MOVES)) || (idx && !di.alloc(hs, N * M0_MAX_MOVES))) return m0_hip_error(hs, "hipMalloc failed");
+    M0_HIP(hs, launch_encode_positions(dp.p, n, dpl.p, nullptr, dm.p, dn.p, dmv.p, di.p, nullptr));
+    if (!M0_HIP(hs, hipDeviceSynchronize())) return m0_hip_error(hs, "encode kernel failed");
+    if (planes) dpl.download(hs, planes, N * 19 * 64);
+    if (mask) dm.download(hs, mask, N * 4672);
+    if (nlegal) dn.download(hs, nlegal, N);
+    if (moves) dmv.download(hs, moves, N * M0_MAX_MOVES);
+    if (idx) di.download(hs, idx, N * M0_MAX_MOVES);
+    return hs.ok() ? M0_OK : m0_hip_error(hs, "download failed");
 }
 
 int m0_encode_fens_nhwc(int hip_device, const char* const* fens, int n, uint16_t* out) {
     if (!fens || n <= 0 || !out) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
     DevBuf<Pos> dp;
-    const int rc = upload_fens(hip_device, fens, n, dp);
+    HipStatus hs;
+    const int rc = upload_fens(hs, hip_device, fens, n, dp);
     if (rc != M0_OK) return rc;
     DevBuf<_Float16> dx;
-    if (!dx.alloc((size_t)n * 64 * 32)) { m0_set_error("hipMalloc failed"); return M0_ERR_HIP; }
-    if (launch_encode_positions(dp.p, n, nullptr, dx.p, nullptr, nullptr, nullptr, nullptr, nullptr) != hipSuccess ||
-        hipDeviceSynchronize() != hipSuccess) { m0_set_error("encode kernel failed"); return M0_ERR_HIP; }
-    dx.download((_Float16*)out, (size_t)n * 64 * 32);
-    return M0_OK;
+    if (!dx.alloc(hs, (size_t)n * 64 * 32)) return m0_hip_error(hs, "hipMalloc failed");
+    M0_HIP(hs, launch_encode_positions(dp.p, n, nullptr, dx.p, nullptr, nullptr, nullptr, nullptr, nullptr));
+    if (!M0_HIP(hs, hipDeviceSynchronize())) return m0_hip_error(hs, "encode kernel failed");
+    return dx.download(hs, (_Float16*)out, (size_t)n * 64 * 32) ? M0_OK : m0_hip_error(hs, "download failed");
 }
 
 int m0_ssl_targets_fens(int hip_device, const char* const* fens, int n, float* out) {
     if (!fens || n <= 0 || !out) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
     DevBuf<Pos> dp;
-    const int rc = upload_fens(hip_device, fens, n, dp);
+    HipStatus hs;
+    const int rc = upload_fens(hs, hip_device, fens, n, dp);
     if (rc != M0_OK) return rc;
     DevBuf<float> dout;
-    if (!dout.alloc((size_t)n * 17 * 64)) { m0_set_error("hipMalloc failed"); return M0_ERR_HIP; }
-    if (launch_ssl_targets(dp.p, n, dout.p, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { m0_set_error("ssl kernel failed"); return M0_ERR_HIP; }
-    dout.download(out, (size_t)n * 17 * 64);
-    return M0_OK;
+    if (!dout.alloc(hs, (size_t)n * 17 * 64)) return m0_hip_error(hs, "hipMalloc failed");
+    M0_HIP(hs, launch_ssl_targets(dp.p, n, dout.p, nullptr));
+    if (!M0_HIP(hs, hipDeviceSynchronize())) return m0_hip_error(hs, "ssl kernel failed");
+    return dout.download(hs, out, (size_t)n * 17 * 64) ? M0_OK : m0_hip_error(hs, "download failed");
 }
 
 int m0_decode_planes(int hip_device, const float* planes, const uint8_t* mask, int n, int32_t* status, int32_t* flags,
@@ -83,25 +82,25 @@ int m0_decode_planes(int hip_device, const float* planes, const uint8_t* mask, i
     if (!planes || n <= 0 || (fens && fen_stride < 96)) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { m0_set_error("no HIP device available (no CPU fallback)"); return M0_ERR_HIP; }
-    if (hipSetDevice(hip_device) != hipSuccess) { m0_set_error("hipSetDevice failed"); return M0_ERR_HIP; }
+    HipStatus hs;
+    if (!M0_HIP(hs, hipSetDevice(hip_device))) return m0_hip_error(hs);
     const size_t N = (size_t)n;
     DevBuf<float> dpl; DevBuf<uint8_t> dm; DevBuf<Pos> dp; DevBuf<int32_t> dst, dfl, dnl;
-    if (!dpl.alloc(N * M0_PLANES * 64) || (mask && !dm.alloc(N * M0_POLICY_SIZE)) || !dp.alloc(N) || !dst.alloc(N) || !dfl.alloc(N) ||
-        !dnl.alloc(N)) { m0_set_error("hipMalloc failed"); return M0_ERR_HIP; }
-    (void)hipMemcpy(dpl.p, planes, N * M0_PLANES * 64 * sizeof(float), hipMemcpyHostToDevice);
-    if (mask) (void)hipMemcpy(dm.p, mask, N * M0_POLICY_SIZE, hipMemcpyHostToDevice);
-    if (launch_decode_planes(dpl.p, dm.p, n, dp.p, dst.p, dfl.p, dnl.p, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-        m0_set_error("decode kernel failed");
-        return M0_ERR_HIP;
-    }
+    if (!dpl.alloc(hs, N * M0_PLANES * 64) || (mask && !dm.alloc(hs, N * M0_POLICY_SIZE)) || !dp.alloc(hs, N) || !dst.alloc(hs, N) ||
+        !dfl.alloc(hs, N) || !dnl.alloc(hs, N)) return m0_hip_error(hs, "hipMalloc failed");
+    M0_HIP(hs, hipMemcpy(dpl.p, planes, N * M0_PLANES * 64 * sizeof(float), hipMemcpyHostToDevice));
+    if (mask) M0_HIP(hs, hipMemcpy(dm.p, mask, N * M0_POLICY_SIZE, hipMemcpyHostToDevice));
+    M0_HIP(hs, launch_decode_planes(dpl.p, dm.p, n, dp.p, dst.p, dfl.p, dnl.p, nullptr));
+    if (!M0_HIP(hs, hipDeviceSynchronize())) return m0_hip_error(hs, "decode kernel failed");
     std::vector<int32_t> hst(N);
-    dst.download(hst.data(), N);
+    std::vector<Pos> hp(fens ? N : 0);
+    dst.download(hs, hst.data(), N);
+    if (flags) dfl.download(hs, flags, N);
+    if (nlegal) dnl.download(hs, nlegal, N);
+    if (fens) dp.download(hs, hp.data(), N);
+    if (!hs.ok()) return m0_hip_error(hs, "download failed");
     if (status) memcpy(status, hst.data(), N * sizeof(int32_t));
-    if (flags) dfl.download(flags, N);
-    if (nlegal) dnl.download(nlegal, N);
     if (fens) {
-        std::vector<Pos> hp(N);
-        dp.download(hp.data(), N);
         memset(fens, 0, N * (size_t)fen_stride);
         for (size_t i = 0; i < N; ++i) {
             if (hst[i] != M0_DECODE_OK && hst[i] != M0_DECODE_MASK_MISMATCH) continue;

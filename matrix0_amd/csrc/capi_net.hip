@@ -106,6 +106,7 @@ int m0_net_load_weight(m0_net* n, const char* name, const void* data, int dtype,
 int m0_net_finalize(m0_net* n) {
     if (!n) { m0_set_error("net is null"); return M0_ERR_INVALID; }
     std::lock_guard<std::mutex> lk(n->mu);
+    if (!n->net->hip().ok()) return m0_hip_error(n->net->hip());
     std::string err;
     int rc = n->net->finalize(err);
     if (rc != M0_OK) m0_set_error(err);
@@ -114,22 +115,20 @@ int m0_net_finalize(m0_net* n) {
 
 static int ensure_io(m0_net* n, int B) {
     if (B <= n->cap) return M0_OK;
-    if (n->planes_dev) (void)hipFree(n->planes_dev);
-    if (n->logits_dev) (void)hipFree(n->logits_dev);
-    if (n->value_dev) (void)hipFree(n->value_dev);
-    if (n->ssl_dev) (void)hipFree(n->ssl_dev);
-    n->planes_dev = n->logits_dev = n->value_dev = n->ssl_dev = nullptr;
+    HipStatus& hs = n->net->hip();
+    for (float** p : {&n->planes_dev, &n->logits_dev, &n->value_dev, &n->ssl_dev}) {
+        if (*p) M0_HIP(hs, hipFree(*p));
+        *p = nullptr;
+    }
     n->cap = 0;
     int cap = B < 64 ? 64 : B;
     const int P = n->net->cfg().planes;
     int sslc = n->net->ssl_channels_total();
-    if (hipMalloc((void**)&n->planes_dev, (size_t)cap * P * 64 * 4) != hipSuccess ||
-        hipMalloc((void**)&n->logits_dev, (size_t)cap * M0_POLICY_SIZE * 4) != hipSuccess ||
-        hipMalloc((void**)&n->value_dev, (size_t)cap * 4) != hipSuccess ||
-        hipMalloc((void**)&n->ssl_dev, (size_t)cap * (sslc > 0 ? sslc : 1) * 64 * 4) != hipSuccess) {
-        m0_set_error("hipMalloc failed for I/O staging");
-        return M0_ERR_HIP;
-    }
+    M0_HIP(hs, hipMalloc((void**)&n->planes_dev, (size_t)cap * P * 64 * 4));
+    M0_HIP(hs, hipMalloc((void**)&n->logits_dev, (size_t)cap * M0_POLICY_SIZE * 4));
+    M0_HIP(hs, hipMalloc((void**)&n->value_dev, (size_t)cap * 4));
+    M0_HIP(hs, hipMalloc((void**)&n->ssl_dev, (size_t)cap * (sslc > 0 ? sslc : 1) * 64 * 4));
+    if (!hs.ok()) return m0_hip_error(hs, "hipMalloc failed for I/O staging");
     n->cap = cap;
     return M0_OK;
 }
@@ -138,22 +137,22 @@ int m0_net_infer(m0_net* n, const float* planes, int B, float* policy, float* va
     if (!n || !planes || !policy || !value) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     if (B <= 0) { m0_set_error("batch must be positive"); return M0_ERR_INVALID; }
     std::lock_guard<std::mutex> lk(n->mu);
-    if (hipSetDevice(n->device) != hipSuccess) { m0_set_error("hipSetDevice failed"); return M0_ERR_HIP; }
+    HipStatus& hs = n->net->hip();
+    if (!M0_HIP(hs, hipSetDevice(n->device))) return m0_hip_error(hs);       // also a network that has failed before
     int rc = ensure_io(n, B);
     if (rc != M0_OK) return rc;
     const int P = n->net->cfg().planes;
     const int sslc = n->net->ssl_channels_total();
     if (ssl && sslc == 0) { m0_set_error("ssl output requested but the net has no SSL heads"); return M0_ERR_INVALID; }
     std::string err;
-    hipError_t e = hipMemcpyAsync(n->planes_dev, planes, (size_t)B * P * 64 * 4, hipMemcpyHostToDevice, n->stream);
-    if (e != hipSuccess) { m0_set_error(std::string("H2D copy: ") + hipGetErrorString(e)); return M0_ERR_HIP; }
+    if (!M0_HIP(hs, hipMemcpyAsync(n->planes_dev, planes, (size_t)B * P * 64 * 4, hipMemcpyHostToDevice, n->stream)))
+        return m0_hip_error(hs, "H2D copy");
     rc = n->net->forward(n->planes_dev, nullptr, B, n->logits_dev, n->value_dev, ssl ? n->ssl_dev : nullptr, n->stream, err);
     if (rc != M0_OK) { m0_set_error(err); return rc; }
-    (void)hipMemcpyAsync(policy, n->logits_dev, (size_t)B * M0_POLICY_SIZE * 4, hipMemcpyDeviceToHost, n->stream);
-    (void)hipMemcpyAsync(value, n->value_dev, (size_t)B * 4, hipMemcpyDeviceToHost, n->stream);
-    if (ssl) (void)hipMemcpyAsync(ssl, n->ssl_dev, (size_t)B * sslc * 64 * 4, hipMemcpyDeviceToHost, n->stream);
-    e = hipStreamSynchronize(n->stream);
-    if (e != hipSuccess) { m0_set_error(std::string("forward failed: ") + hipGetErrorString(e)); return M0_ERR_HIP; }
+    M0_HIP(hs, hipMemcpyAsync(policy, n->logits_dev, (size_t)B * M0_POLICY_SIZE * 4, hipMemcpyDeviceToHost, n->stream));
+    M0_HIP(hs, hipMemcpyAsync(value, n->value_dev, (size_t)B * 4, hipMemcpyDeviceToHost, n->stream));
+    if (ssl) M0_HIP(hs, hipMemcpyAsync(ssl, n->ssl_dev, (size_t)B * sslc * 64 * 4, hipMemcpyDeviceToHost, n->stream));
+    if (!M0_HIP(hs, hipStreamSynchronize(n->stream))) return m0_hip_error(hs, "forward failed");
     // NaN/Inf must surface as errors (mcts.py:1165-1177, tests/test_error_handling.py:23-53)
     for (size_t i = 0, nn = (size_t)B * M0_POLICY_SIZE; i < nn; ++i)
         if (!isfinite(policy[i])) { m0_set_error("network produced non-finite policy logits"); return M0_ERR_NONFINITE; }
@@ -194,7 +193,8 @@ int m0_net_profile_get_tail(m0_net* n, double* tail_ms, int64_t* tail_launches) 
 int m0_net_bench_forward(m0_net* n, int B, int iters, int with_ssl, float* ms_per_forward) {
     if (!n || !ms_per_forward || B <= 0 || iters <= 0) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
     std::lock_guard<std::mutex> lk(n->mu);
-    if (hipSetDevice(n->device) != hipSuccess) { m0_set_error("hipSetDevice failed"); return M0_ERR_HIP; }
+    HipStatus& hs = n->net->hip();
+    if (!M0_HIP(hs, hipSetDevice(n->device))) return m0_hip_error(hs);
     int rc = ensure_io(n, B);
     if (rc != M0_OK) return rc;
     std::string err;
@@ -210,24 +210,25 @@ int m0_net_bench_forward(m0_net* n, int B, int iters, int with_ssl, float* ms_pe
             if (p < 12) h[i] = ((s >> 20) % 100) < 8 ? 1.f : 0.f;
             else h[i] = (float)((((i / 64 / P) * 7 + p) % 10) / 10.0);
         }
-        (void)hipMemcpy(n->planes_dev, h.data(), h.size() * 4, hipMemcpyHostToDevice);
+        if (!M0_HIP(hs, hipMemcpy(n->planes_dev, h.data(), h.size() * 4, hipMemcpyHostToDevice))) return m0_hip_error(hs, "H2D copy");
     }
     float* ssl = ((with_ssl & 1) && n->net->ssl_channels_total() > 0) ? n->ssl_dev : nullptr;
     rc = n->net->forward(n->planes_dev, nullptr, B, n->logits_dev, n->value_dev, ssl, n->stream, err);   // warm-up
     if (rc != M0_OK) { m0_set_error(err); return rc; }
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    (void)hipEventRecord(e0, n->stream);
-    for (int i = 0; i < iters; ++i) {
+    struct Events {                          // destroyed on every way out
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    } ev;
+    M0_HIP(hs, hipEventCreate(&ev.e0)); M0_HIP(hs, hipEventCreate(&ev.e1));
+    M0_HIP(hs, hipEventRecord(ev.e0, n->stream));
+    for (int i = 0; i < iters && hs.ok(); ++i) {
         rc = n->net->forward(n->planes_dev, nullptr, B, n->logits_dev, n->value_dev, ssl, n->stream, err);
         if (rc != M0_OK) { m0_set_error(err); return rc; }
     }
-    (void)hipEventRecord(e1, n->stream);
-    hipError_t e = hipEventSynchronize(e1);
-    if (e != hipSuccess) { m0_set_error(std::string("bench forward failed: ") + hipGetErrorString(e)); return M0_ERR_HIP; }
+    M0_HIP(hs, hipEventRecord(ev.e1, n->stream));
+    M0_HIP(hs, hipEventSynchronize(ev.e1));
     float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    if (!M0_HIP(hs, hipEventElapsedTime(&ms, ev.e0, ev.e1))) return m0_hip_error(hs, "bench forward failed");
     *ms_per_forward = ms / iters;
     n->net->harvest_profile();
     return M0_OK;

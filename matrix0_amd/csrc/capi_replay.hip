@@ -31,11 +31,11 @@ struct ReplayLaunch {
 
 // copies the first plies[g] rows of every game of a launch from the staging buffer to the caller's flat array
 template <typename T>
-void scatter_rows(const DevBuf<T>& dev, std::vector<T>& staging, const ReplayLaunch& L, const std::vector<int32_t>& local_off,
+void scatter_rows(HipStatus& hs, const DevBuf<T>& dev, std::vector<T>& staging, const ReplayLaunch& L, const std::vector<int32_t>& local_off,
                   const int32_t* offsets, const int32_t* plies, size_t width, T* out) {
     if (!out) return;
     staging.resize(L.rows * width);
-    dev.download(staging.data(), L.rows * width);
+    if (!dev.download(hs, staging.data(), L.rows * width)) return;
     for (int g = L.g0; g < L.g1; ++g)
         memcpy(out + (size_t)offsets[g] * width, staging.data() + (size_t)local_off[g - L.g0] * width,
                (size_t)plies[g] * width * sizeof(T));
@@ -74,7 +74,8 @@ int m0_replay_games(int hip_device, const char* const* start_fens, const uint32_
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { m0_set_error("no HIP device available (no CPU fallback)"); return M0_ERR_HIP; }
-    if (hipSetDevice(hip_device) != hipSuccess) { m0_set_error("hipSetDevice failed"); return M0_ERR_HIP; }
+    HipStatus hs;
+    if (!M0_HIP(hs, hipSetDevice(hip_device))) return m0_hip_error(hs);
 
     // A game puts min(tokens, max_plies + 1) rows on the device: the tokens it may resolve, and one more for a game past the
     // cap so that the kernel sees it is longer.  A launch takes whole games while they fit; a game larger than the limit goes alone.
@@ -106,11 +107,11 @@ int m0_replay_games(int hip_device, const char* const* start_fens, const uint32_
     DevBuf<int8_t> dturn;
     DevBuf<float> dplanes, dssl;
     DevBuf<uint8_t> dmask;
-    if (!dstart.alloc(max_games) || !dpos.alloc(max_rows) || !dpat.alloc(max_rows) || !doff.alloc(max_games + 1) ||
-        !dplies.alloc(max_games) || !dstatus.alloc(max_games) || !dend.alloc(max_games) || !didx.alloc(max_rows) ||
-        !dnl.alloc(max_rows) || !dmv.alloc(max_rows) || !dturn.alloc(max_rows) ||
-        (planes && !dplanes.alloc(max_rows * M0_PLANES * 64)) || (mask && !dmask.alloc(max_rows * M0_POLICY_SIZE)) ||
-        (ssl && !dssl.alloc(max_rows * 17 * 64))) { m0_set_error("hipMalloc failed"); return M0_ERR_HIP; }
+    if (!dstart.alloc(hs, max_games) || !dpos.alloc(hs, max_rows) || !dpat.alloc(hs, max_rows) || !doff.alloc(hs, max_games + 1) ||
+        !dplies.alloc(hs, max_games) || !dstatus.alloc(hs, max_games) || !dend.alloc(hs, max_games) || !didx.alloc(hs, max_rows) ||
+        !dnl.alloc(hs, max_rows) || !dmv.alloc(hs, max_rows) || !dturn.alloc(hs, max_rows) ||
+        (planes && !dplanes.alloc(hs, max_rows * M0_PLANES * 64)) || (mask && !dmask.alloc(hs, max_rows * M0_POLICY_SIZE)) ||
+        (ssl && !dssl.alloc(hs, max_rows * 17 * 64))) return m0_hip_error(hs, "hipMalloc failed");
 
     std::vector<uint32_t> hpat;
     std::vector<int32_t> local_off, s_i32;
@@ -126,27 +127,29 @@ int m0_replay_games(int hip_device, const char* const* start_fens, const uint32_
             hpat.insert(hpat.end(), patterns + offsets[g], patterns + offsets[g] + rows_of(g));
             local_off.push_back((int32_t)hpat.size());
         }
-        bool ok = hipMemcpy(dstart.p, hstart.data() + L.g0, sizeof(Pos) * ng, hipMemcpyHostToDevice) == hipSuccess &&
-                  hipMemcpy(doff.p, local_off.data(), sizeof(int32_t) * (ng + 1), hipMemcpyHostToDevice) == hipSuccess &&
-                  (L.rows == 0 || hipMemcpy(dpat.p, hpat.data(), sizeof(uint32_t) * L.rows, hipMemcpyHostToDevice) == hipSuccess) &&
-                  // rows a game does not resolve are encoded too (and not copied back): they must hold a defined position
-                  (L.rows == 0 || hipMemset(dpos.p, 0, sizeof(Pos) * L.rows) == hipSuccess);
-        ok = ok && launch_replay_games(dstart.p, dpat.p, doff.p, ng, max_plies, dpos.p, dmv.p, didx.p, dnl.p, dturn.p, dplies.p,
-                                       dstatus.p, dend.p, nullptr) == hipSuccess;
-        if (ok && (planes || mask))
-            ok = launch_encode_positions(dpos.p, (int)L.rows, dplanes.p, nullptr, dmask.p, nullptr, nullptr, nullptr, nullptr) == hipSuccess;
-        if (ok && ssl) ok = launch_ssl_targets(dpos.p, (int)L.rows, dssl.p, nullptr) == hipSuccess;
-        if (!ok || hipDeviceSynchronize() != hipSuccess) { m0_set_error("replay kernels failed"); return M0_ERR_HIP; }
-        dplies.download(plies + L.g0, ng);
-        dstatus.download(status + L.g0, ng);
-        dend.download(end_flags + L.g0, ng);
-        scatter_rows(dmv, s_u16, L, local_off, offsets, plies, 1, moves);
-        scatter_rows(didx, s_i32, L, local_off, offsets, plies, 1, policy_idx);
-        scatter_rows(dnl, s_i32, L, local_off, offsets, plies, 1, nlegal);
-        scatter_rows(dturn, s_i8, L, local_off, offsets, plies, 1, turn);
-        scatter_rows(dplanes, s_f32, L, local_off, offsets, plies, (size_t)M0_PLANES * 64, planes);
-        scatter_rows(dmask, s_u8, L, local_off, offsets, plies, (size_t)M0_POLICY_SIZE, mask);
-        scatter_rows(dssl, s_f32, L, local_off, offsets, plies, (size_t)17 * 64, ssl);
+        M0_HIP(hs, hipMemcpy(dstart.p, hstart.data() + L.g0, sizeof(Pos) * ng, hipMemcpyHostToDevice));
+        M0_HIP(hs, hipMemcpy(doff.p, local_off.data(), sizeof(int32_t) * (ng + 1), hipMemcpyHostToDevice));
+        if (L.rows) M0_HIP(hs, hipMemcpy(dpat.p, hpat.data(), sizeof(uint32_t) * L.rows, hipMemcpyHostToDevice));
+        // rows a game does not resolve are encoded too (and not copied back): they must hold a defined position
+        if (L.rows) M0_HIP(hs, hipMemset(dpos.p, 0, sizeof(Pos) * L.rows));
+        M0_HIP(hs, launch_replay_games(dstart.p, dpat.p, doff.p, ng, max_plies, dpos.p, dmv.p, didx.p, dnl.p, dturn.p, dplies.p,
+                                       dstatus.p, dend.p, nullptr));
+        if (planes || mask)
+            M0_HIP(hs, launch_encode_positions(dpos.p, (int)L.rows, dplanes.p, nullptr, dmask.p, nullptr, nullptr, nullptr, nullptr));
+        if (ssl) M0_HIP(hs, launch_ssl_targets(dpos.p, (int)L.rows, dssl.p, nullptr));
+        if (!M0_HIP(hs, hipDeviceSynchronize())) return m0_hip_error(hs, "replay kernels failed");
+        dplies.download(hs, plies + L.g0, ng);
+        dstatus.download(hs, status + L.g0, ng);
+        dend.download(hs, end_flags + L.g0, ng);
+        if (!hs.ok()) return m0_hip_error(hs, "replay download failed");      // scatter_rows reads plies
+        scatter_rows(hs, dmv, s_u16, L, local_off, offsets, plies, 1, moves);
+        scatter_rows(hs, didx, s_i32, L, local_off, offsets, plies, 1, policy_idx);
+        scatter_rows(hs, dnl, s_i32, L, local_off, offsets, plies, 1, nlegal);
+        scatter_rows(hs, dturn, s_i8, L, local_off, offsets, plies, 1, turn);
+        scatter_rows(hs, dplanes, s_f32, L, local_off, offsets, plies, (size_t)M0_PLANES * 64, planes);
+        scatter_rows(hs, dmask, s_u8, L, local_off, offsets, plies, (size_t)M0_POLICY_SIZE, mask);
+        scatter_rows(hs, dssl, s_f32, L, local_off, offsets, plies, (size_t)17 * 64, ssl);
+        if (!hs.ok()) return m0_hip_error(hs, "replay download failed");
     }
     return M0_OK;
 }

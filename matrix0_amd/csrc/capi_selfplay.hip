@@ -21,7 +21,7 @@ static void fill_tree_cfg(const m0_selfplay_cfg& c, bool match, TreeCfg& t) {
     t.eval_cache = ((match ? c.arena_eval_cache : c.eval_cache) && c.legal_softmax && !c.raw_legal_priors && !c.tt_merge) ? 1 : 0;
 }
 
-static void alloc_tree_arenas(m0_selfplay* sp) {
+static bool alloc_tree_arenas(m0_selfplay* sp) {
     // arena: reused subtree + one search of new children (218 max per expansion is far above the ~35 mean)
     const m0_selfplay_cfg& c = sp->cfg;
     long want = c.arena_nodes > 0 ? c.arena_nodes : (long)(c.num_simulations * 1.3 + 64) * 96;
@@ -38,6 +38,7 @@ static void alloc_tree_arenas(m0_selfplay* sp) {
     sp->d.samples = dalloc<Sample>(sp, (size_t)sp->G * LS);
     sp->d.paths = dalloc<int>(sp, (size_t)sp->G * LS * M0_MAX_DEPTH);
     sp->d.leaf_moves = dalloc<uint16_t>(sp, (size_t)sp->G * LS * M0_MAX_CHILDREN);
+    return hip_ok(sp, "hipMalloc failed for the search arenas (lower concurrent_games or arena_nodes)");
 }
 
 // cfg.tt_merge: the transposition tables
@@ -56,9 +57,7 @@ static bool alloc_position_tables(m0_selfplay* sp) {
     sp->d.epaths = dalloc<int>(sp, (size_t)sp->G * LS * M0_MAX_DEPTH);
     sp->d.tt_keys = dalloc<uint64_t>(sp, (size_t)sp->G * sp->d.tt_sides * tc);
     sp->d.tt_nodes = dalloc<int>(sp, (size_t)sp->G * sp->d.tt_sides * tc);
-    if (sp->d.epaths && sp->d.tt_keys && sp->d.tt_nodes) return true;
-    m0_set_error("hipMalloc failed for the position tables (tt_merge): lower concurrent_games or arena_nodes");
-    return false;
+    return hip_ok(sp, "hipMalloc failed for the position tables (tt_merge): lower concurrent_games or arena_nodes");
 }
 
 static bool alloc_eval_cache(m0_selfplay* sp) {
@@ -75,9 +74,7 @@ static bool alloc_eval_cache(m0_selfplay* sp) {
     ec.stamps = dalloc<uint32_t>(sp, entries_all);
     ec.payload = dalloc<float>(sp, entries_all * M0_EC_WORDS);
     ec.hit_stage = dalloc<float>(sp, (size_t)sp->G * LS * M0_EC_WORDS);
-    if (ec.keys && ec.stamps && ec.payload && ec.hit_stage) return true;
-    m0_set_error("hipMalloc failed for the evaluation cache: lower eval_cache_entries or concurrent_games");
-    return false;
+    return hip_ok(sp, "hipMalloc failed for the evaluation cache: lower eval_cache_entries or concurrent_games");
 }
 
 // the batch (one region per network), the evaluator's outputs and the small staging buffers
@@ -96,16 +93,13 @@ static bool alloc_batch_buffers(m0_selfplay* sp) {
         sp->ssl_cap = sp->cfg.max_game_len > 0 ? sp->cfg.max_game_len + 1 : 513;
         sp->ssl_pos_dev = dalloc<Pos>(sp, sp->ssl_cap);
         sp->ssl_out_dev = dalloc<float>(sp, (size_t)sp->ssl_cap * 17 * 64);
-        if (!sp->ssl_pos_dev || !sp->ssl_out_dev) {
-            m0_set_error("hipMalloc failed for the SSL target staging buffers");
-            return false;
-        }
+        if (!hip_ok(sp, "hipMalloc failed for the SSL target staging buffers")) return false;
     }
     sp->ids_dev = dalloc<int>(sp, sp->G);
     sp->roots_dev = dalloc<int>(sp, sp->G);
     sp->d.logits = sp->logits_dev; sp->d.values = sp->values_dev;
     sp->d.G = sp->G; sp->d.L = sp->L;
-    return true;
+    return hip_ok(sp, "hipMalloc failed for the batch buffers (lower concurrent_games or inference_batch_size)");
 }
 
 // cfg.tail_split: the second instance of the network on a stream of its own (one_step, split_rows)
@@ -114,12 +108,10 @@ static bool make_tail_view(m0_selfplay* sp) {
           sp->rows_max >= 2048)) return true;
     // M0_TAIL_CU_MASK=w0,...,w7 (measurement switch, like M0_NET_CU_MASK for the network's own stream): the second instance's
     // stream runs on those CUs only -- with complementary masks every launch of the two halves has a known share of the chip
-    if (create_stream_cu_mask_env("M0_TAIL_CU_MASK", &sp->stream_tail) != hipSuccess ||
-        hipEventCreateWithFlags(&sp->ev_sel, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&sp->ev_tail, hipEventDisableTiming) != hipSuccess) {
-        m0_set_error("hipStreamCreate / hipEventCreate failed (tail split)");
-        return false;
-    }
+    M0_HIP(sp->hip, create_stream_cu_mask_env("M0_TAIL_CU_MASK", &sp->stream_tail));
+    M0_HIP(sp->hip, hipEventCreateWithFlags(&sp->ev_sel, hipEventDisableTiming));
+    M0_HIP(sp->hip, hipEventCreateWithFlags(&sp->ev_tail, hipEventDisableTiming));
+    if (!hip_ok(sp, "hipStreamCreate / hipEventCreate failed (tail split)")) return false;
     sp->net_tail = sp->net->shared_view(sp->stream_tail);
     std::string werr;                   // its workspace now, at its largest (a regrowth synchronises the device)
     sp->half_split = sp->cfg.tail_split == 2;
@@ -132,29 +124,21 @@ static bool make_tail_view(m0_selfplay* sp) {
 
 // the device side of a new engine; false with the error string set
 static bool build_engine(m0_selfplay* sp) {
-    alloc_tree_arenas(sp);
-    if (!alloc_position_tables(sp) || !alloc_eval_cache(sp) || !alloc_batch_buffers(sp)) return false;
-    if (sp->alloc_failed) {
-        m0_set_error("hipMalloc failed for the search arenas (lower concurrent_games or arena_nodes)");
-        return false;
-    }
+    if (!alloc_tree_arenas(sp) || !alloc_position_tables(sp) || !alloc_eval_cache(sp) || !alloc_batch_buffers(sp)) return false;
     sp->hg.assign(sp->G, GameDev());
     for (auto& g : sp->hg) memset(&g, 0, sizeof(GameDev));
     sp->games.assign(sp->G, HostGame());
     sp->hres.resize(sp->G);
     sp->hsamples.resize((size_t)sp->G * (sp->L + 1));
     sp->prev_done.assign(sp->G, 0);
-    (void)hipEventCreate(&sp->ev0); (void)hipEventCreate(&sp->ev1); (void)hipEventCreate(&sp->ev2); (void)hipEventCreate(&sp->ev3);
-    if (!make_tail_view(sp)) return false;
+    for (hipEvent_t* e : {&sp->ev0, &sp->ev1, &sp->ev2, &sp->ev3}) M0_HIP(sp->hip, hipEventCreate(e));
+    if (!hip_ok(sp, "hipEventCreate failed") || !make_tail_view(sp)) return false;
     std::string err;
     if (sp->net && sp->net->ensure_workspace(sp->rows_max, err) != M0_OK) { m0_set_error(err); return false; }
     if (sp->net && sp->net_b && sp->net_b->ensure_workspace(sp->rows_max, err) != M0_OK) { m0_set_error(err); return false; }
     // the clears ride the engine's stream; wait once so that an allocation / clear failure surfaces here, not in the first step
-    if (hipStreamSynchronize(sp->stream) != hipSuccess) {
-        m0_set_error(std::string("clearing the search arenas failed: ") + hipGetErrorString(hipGetLastError()));
-        return false;
-    }
-    return true;
+    M0_HIP(sp->hip, hipStreamSynchronize(sp->stream));
+    return hip_ok(sp, "clearing the search arenas failed");
 }
 
 m0_selfplay* m0::engine_create(m0_net* nh, m0_net* nh_b, const m0_selfplay_cfg* cfg, EngineKind kind) {
@@ -184,22 +168,23 @@ m0_selfplay* m0::engine_create(m0_net* nh, m0_net* nh_b, const m0_selfplay_cfg* 
     fill_tree_cfg(sp->cfg, match, sp->tc);
     sp->device = nh ? m0_net_device(nh) : 0;
     if (nh) forward_gate_join(sp);
-    (void)hipSetDevice(sp->device);
+    M0_HIP(sp->hip, hipSetDevice(sp->device));
     if (nh) sp->stream = m0_net_stream(nh);
-    else { (void)hipStreamCreateWithFlags(&sp->stream, hipStreamNonBlocking); sp->own_stream = true; }
+    else { M0_HIP(sp->hip, hipStreamCreateWithFlags(&sp->stream, hipStreamNonBlocking)); sp->own_stream = true; }
     sp->G = cfg->concurrent_games;
     sp->L = cfg->inference_batch_size;
     sp->rows_max = (sp->G * (sp->L + 1) + 3) & ~3;      // L leaves + the re-evaluation of a reused root, per game
     memset(&sp->stats, 0, sizeof(sp->stats));
     memset(&sp->d, 0, sizeof(sp->d));
-    return build_engine(sp) ? owner.release() : nullptr;
+    return hip_ok(sp, "engine stream") && build_engine(sp) ? owner.release() : nullptr;
 }
 
 // The leaves of the last select as f32 planes for an external evaluator: rows [0, rows_a) into planes_a and, for a match
 // engine, rows [net_row_base, net_row_base + rows_b) into planes_b (rows_b = 0 with one network).
 static int leaf_planes(m0_selfplay* sp, int rows_a, float* planes_a, int rows_b, float* planes_b) {
-    if (sync_games_d2h(sp) != 0) { m0_set_error("device sync failed"); return M0_ERR_HIP; }
-    (void)hipMemcpy(sp->hsamples.data(), sp->d.samples, sizeof(Sample) * (size_t)sp->G * (sp->L + 1), hipMemcpyDeviceToHost);
+    sync_games_d2h(sp);
+    if (!M0_HIP(sp->hip, hipMemcpy(sp->hsamples.data(), sp->d.samples, sizeof(Sample) * (size_t)sp->G * (sp->L + 1), hipMemcpyDeviceToHost)))
+        return m0_hip_error(sp->hip, "device sync failed");
     const int base = sp->d.net_row_base;
     for (int g = 0; g < sp->G; ++g) {
         if (!sp->hg[g].active) continue;
@@ -213,11 +198,12 @@ static int leaf_planes(m0_selfplay* sp, int rows_a, float* planes_a, int rows_b,
     return M0_OK;
 }
 
-// An external evaluator's results for `rows` rows of the batch, starting at row_base, onto the engine's stream.
+// An external evaluator's results for `rows` rows of the batch, starting at row_base, onto the engine's stream (a failure stays
+// in sp->hip: the expand that follows is not launched and reports it).
 static void upload_eval(m0_selfplay* sp, size_t row_base, const float* logits, const float* values, int rows) {
     if (rows <= 0) return;
-    (void)hipMemcpyAsync(sp->logits_dev + row_base * 4672, logits, (size_t)rows * 4672 * 4, hipMemcpyHostToDevice, sp->stream);
-    (void)hipMemcpyAsync(sp->values_dev + row_base, values, (size_t)rows * 4, hipMemcpyHostToDevice, sp->stream);
+    M0_HIP(sp->hip, hipMemcpyAsync(sp->logits_dev + row_base * 4672, logits, (size_t)rows * 4672 * 4, hipMemcpyHostToDevice, sp->stream));
+    M0_HIP(sp->hip, hipMemcpyAsync(sp->values_dev + row_base, values, (size_t)rows * 4, hipMemcpyHostToDevice, sp->stream));
 }
 
 // first half of a step for an external evaluator: select, then the leaves' planes on the host (region 0 = network A / the only
@@ -253,7 +239,7 @@ int m0::ext_expand_impl(m0_selfplay* sp, const float* logits_a, const float* val
     upload_eval(sp, 0, logits_a, values_a, rows_a);
     upload_eval(sp, (size_t)sp->d.net_row_base, logits_b, values_b, rows_b);
     sp->ext_pending = false;
-    (void)hipEventRecord(sp->ev0, sp->stream); (void)hipEventRecord(sp->ev1, sp->stream);
+    M0_HIP(sp->hip, hipEventRecord(sp->ev0, sp->stream)); M0_HIP(sp->hip, hipEventRecord(sp->ev1, sp->stream));
     return finish_step(sp, rows_a + rows_b, now_ms());
 }
 
@@ -379,7 +365,7 @@ int m0_search_begin(m0_selfplay* sp, int g, const char* fen, int sims, int diric
     M0_ENGINE_CALL(sp, "m0_search_begin", KIND_GAMES, true);
     Line line;                             // history-less
     if (parse_fen(fen, line.pos) != 0) { m0_set_error("bad FEN"); return M0_ERR_INVALID; }
-    if (sync_games_d2h(sp) != 0) { m0_set_error("device sync failed"); return M0_ERR_HIP; }
+    if (!sync_games_d2h(sp)) return m0_hip_error(sp->hip, "device sync failed");
     occupy_slot(sp, g, std::move(line), game_uid);
     begin_search(sp, g, sims, dirichlet != 0, ROOT_FRESH);
     return apply_advances(sp);
@@ -405,8 +391,8 @@ int m0_search_expand(m0_selfplay* sp, const float* logits, const float* values, 
     if (rows != sp->last_rows || rows > sp->rows_max) { m0_set_error("rows does not match the last select"); return M0_ERR_INVALID; }
     if (rows > 0 && (!logits || !values)) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     upload_eval(sp, 0, logits, values, rows);
-    if (launch_expand(sp->d, sp->tc, sp->stream) != hipSuccess) { m0_set_error("expand launch failed"); return M0_ERR_HIP; }
-    if (sync_games_d2h(sp) != 0) { m0_set_error(std::string("expand failed: ") + hipGetErrorString(hipGetLastError())); return M0_ERR_HIP; }
+    M0_HIP(sp->hip, launch_expand(sp->d, sp->tc, sp->stream));
+    if (!sync_games_d2h(sp)) return m0_hip_error(sp->hip, "expand failed");
     sp->stats.evals += (uint64_t)rows;
     return M0_OK;
 }
@@ -417,7 +403,8 @@ int m0_search_result(m0_selfplay* sp, int g, int* nchild, int32_t* child_n, uint
     M0_ENGINE_CALL(sp, "m0_search_result", KIND_GAMES, true);
     if (finished) *finished = sp->hg[g].finished;
     if (!sp->hg[g].finished) { if (nchild) *nchild = 0; return M0_OK; }
-    (void)hipMemcpy(&sp->hres[g], sp->d.results + g, sizeof(RootResult), hipMemcpyDeviceToHost);
+    if (!M0_HIP(sp->hip, hipMemcpy(&sp->hres[g], sp->d.results + g, sizeof(RootResult), hipMemcpyDeviceToHost)))
+        return m0_hip_error(sp->hip, "result copy failed");
     const RootResult& R = sp->hres[g];
     if (nchild) *nchild = R.nchild;
     for (int i = 0; i < R.nchild; ++i) {
@@ -436,9 +423,10 @@ int m0_search_advance(m0_selfplay* sp, int g, int slot, int sims, int dirichlet)
     if (!sp || g < 0 || g >= sp->G || sims <= 0) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
     M0_ENGINE_CALL(sp, "m0_search_advance", KIND_GAMES, true);
     // refresh the mirror first: an earlier advance changed root/next/arena on the device only
-    if (sync_games_d2h(sp) != 0) { m0_set_error("device sync failed"); return M0_ERR_HIP; }
+    if (!sync_games_d2h(sp)) return m0_hip_error(sp->hip, "device sync failed");
     if (!sp->hg[g].finished) { m0_set_error("search not finished"); return M0_ERR_STATE; }
-    (void)hipMemcpy(&sp->hres[g], sp->d.results + g, sizeof(RootResult), hipMemcpyDeviceToHost);
+    if (!M0_HIP(sp->hip, hipMemcpy(&sp->hres[g], sp->d.results + g, sizeof(RootResult), hipMemcpyDeviceToHost)))
+        return m0_hip_error(sp->hip, "result copy failed");
     const RootResult& R = sp->hres[g];
     if (slot < 0 || slot >= R.nchild) { m0_set_error("child slot out of range"); return M0_ERR_INVALID; }
     sp->games[g].play(R.child_mv[slot]);
@@ -454,8 +442,8 @@ int m0_selfplay_last_batch_nhwc(m0_selfplay* sp, uint16_t* out, int max_rows, in
     if (r > max_rows) { m0_set_error("output buffer too small"); return M0_ERR_INVALID; }
     *rows = r;
     if (r > 0) {
-        if (hipMemcpyAsync(out, sp->d.x0, (size_t)r * 64 * 32 * 2, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
-            hipStreamSynchronize(sp->stream) != hipSuccess) { m0_set_error("copy failed"); return M0_ERR_HIP; }
+        M0_HIP(sp->hip, hipMemcpyAsync(out, sp->d.x0, (size_t)r * 64 * 32 * 2, hipMemcpyDeviceToHost, sp->stream));
+        if (!M0_HIP(sp->hip, hipStreamSynchronize(sp->stream))) return m0_hip_error(sp->hip, "copy failed");
     }
     return M0_OK;
 }

@@ -107,22 +107,20 @@ int m0::tb_device_set(const m0_tb* tb, int hip_device, const TbSet** set_dev, st
     c.device = hip_device;
     TbSet host;
     for (auto& t : host.tab) t = nullptr;
-    hipError_t e = hipSetDevice(hip_device);
-    for (size_t i = 0; e == hipSuccess && i < tb->tables.size(); ++i) {
-        const TbTable& t = tb->tables[i];
+    HipStatus hs;
+    M0_HIP(hs, hipSetDevice(hip_device));
+    for (const TbTable& t : tb->tables) {
         void* p = nullptr;
-        e = hipMalloc(&p, t.bytes.size());
-        if (e != hipSuccess) break;
+        if (!M0_HIP(hs, hipMalloc(&p, t.bytes.size()))) break;
         c.allocs.push_back(p);
         host.tab[tb_material_code(t.sig)] = (const uint8_t*)p;
-        e = hipMemcpy(p, t.bytes.data(), t.bytes.size(), hipMemcpyHostToDevice);
+        M0_HIP(hs, hipMemcpy(p, t.bytes.data(), t.bytes.size(), hipMemcpyHostToDevice));
     }
     void* sd = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&sd, sizeof(TbSet));
-    if (e == hipSuccess) { c.allocs.push_back(sd); e = hipMemcpy(sd, &host, sizeof(TbSet), hipMemcpyHostToDevice); }
-    if (e == hipSuccess) e = hipDeviceSynchronize();          // nothing of the upload is left in flight when the caller goes on
-    if (e != hipSuccess) {
-        err = std::string("copying the tables to the device failed: ") + hipGetErrorString(e);
+    if (M0_HIP(hs, hipMalloc(&sd, sizeof(TbSet)))) c.allocs.push_back(sd);
+    M0_HIP(hs, hipMemcpy(sd, &host, sizeof(TbSet), hipMemcpyHostToDevice));
+    if (!M0_HIP(hs, hipDeviceSynchronize())) {                // nothing of the upload is left in flight when the caller goes on
+        err = "copying the tables to the device failed: " + hs.message();
         for (void* p : c.allocs) (void)hipFree(p);            // no kernel has seen them
         return M0_ERR_HIP;
     }
@@ -284,7 +282,7 @@ static int attach_tablebase(m0_selfplay* sp, const m0_tb* tb, int max_pieces, bo
         std::string err;
         const int rc = tb_device_set(tb, sp->device, &set_dev, err);
         if (rc != M0_OK) { m0_set_error("m0_selfplay_set_search_tablebase: " + err); return rc; }
-        (void)hipSetDevice(sp->device);
+        if (!M0_HIP(sp->hip, hipSetDevice(sp->device))) return m0_hip_error(sp->hip, "m0_selfplay_set_search_tablebase");
     }
     // the host probe of a root (after a played move; of a submission) and the leaf probe of select_kernel read the same limit
     sp->tb = tb;

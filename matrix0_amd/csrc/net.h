@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 #include "../../include/m0_engine.h"
+#include "hip_check.h"
 #include "net_kernels.h"
 
 namespace net_pack { struct GemmShape; }
@@ -85,6 +86,9 @@ public:
     int load(const char* name, const void* data, int dtype, const int64_t* shape, int ndim, std::string& err);
     int finalize(std::string& err);
     bool ready() const { return finalized_; }
+    // The first failed HIP call made for this network (hip_check.h); intake, workspace and forward issue nothing after it.  A
+    // shared_view copies the pointer, not the status: it records into the network it was made from.
+    HipStatus& hip() { return *hip_; }
     // every device buffer finalize() made (packed GEMM weights, norm parameters, bias / mask tables), in creation order: the same
     // list with the same sizes on every process that finalized a network of the same configuration
     const std::vector<void*>& device_buffers() const { return dev_allocs_; }
@@ -115,6 +119,7 @@ private:
     m0_net_cfg cfg_;
     int device_;
     hipStream_t stream_ = nullptr;
+    HipStatus own_hip_, *hip_ = &own_hip_;
     struct Switches { bool fuse_tail = true, fuse_attn = true; int attn_grid = 0; } sw_;   // read once (constructor)
     // What forward() would otherwise derive again on every call: fixed by the configuration, the switches and the squeeze-excite
     // width, filled in at the end of finalize().  Layers are named by index into res_ (TowerLayer::next_bn1, first_bn1), not by

@@ -90,14 +90,14 @@ Net::~Net() {
 void* Net::dalloc(size_t bytes, bool ws) {
     void* p = nullptr;
     if (bytes == 0) bytes = 16;
-    if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-    // cleared ON THE STREAM THAT WILL USE IT (a NULL-stream hipMemset is not ordered with the non-blocking streams: round 2's
-    // regrowth race).  Weight buffers are filled next by blocking NULL-stream copies, so their clear is waited for here.
-    (void)hipMemsetAsync(p, 0, bytes, stream_);
-    if (!ws) (void)hipStreamSynchronize(stream_);
+    if (!M0_HIP(*hip_, hipMalloc(&p, bytes))) return nullptr;
     (ws ? ws_allocs_ : dev_allocs_).push_back(p);
     if (!ws) dev_sizes_.push_back(bytes);
-    return p;
+    // cleared ON THE STREAM THAT WILL USE IT (a NULL-stream hipMemset is not ordered with the non-blocking streams: round 2's
+    // regrowth race).  Weight buffers are filled next by blocking NULL-stream copies, so their clear is waited for here.
+    M0_HIP(*hip_, hipMemsetAsync(p, 0, bytes, stream_));
+    if (!ws) M0_HIP(*hip_, hipStreamSynchronize(stream_));
+    return hip_->ok() ? p : nullptr;
 }
 
 int Net::ssl_channels_total() const {
@@ -133,9 +133,10 @@ int Net::ensure_workspace(int B, std::string& err) {
     const int Bp = ceil_to(B, 4);
     const int Mfc = ceil_to(B, 256);
     if (Bp <= wsB_ && Mfc <= wsM_) return M0_OK;
-    if (hipSetDevice(device_) != hipSuccess) { err = "hipSetDevice failed"; return M0_ERR_HIP; }
-    (void)hipDeviceSynchronize();
-    for (void* p : ws_allocs_) (void)hipFree(p);
+    M0_HIP(*hip_, hipSetDevice(device_));
+    M0_HIP(*hip_, hipDeviceSynchronize());
+    for (void* p : ws_allocs_) M0_HIP(*hip_, hipFree(p));
+    if (!hip_->ok()) { err = "workspace: " + hip_->message(); return M0_ERR_HIP; }     // the list stays for the destructor
     ws_allocs_.clear();
     const size_t C = Cp_;
     const size_t nb = Bp, nh = std::max(Bp, Mfc);
@@ -154,18 +155,13 @@ int Net::ensure_workspace(int B, std::string& err) {
     SH_ = H(nb * 64 * Cs_); SH2_ = H(nb * 64 * Cs_); SO_ = H(nb * 64 * 32);
     VAL_ = F((size_t)Mfc * 32);
     SPK_ = F((size_t)8 * Mfc * ceil_to(2 * C_, 32));
-    if (!X0_ || !XA_ || !XB_ || !AA_ || !T1_ || !T2_ || !QKV_ || !O_ || !S1_ || !S2_ || !PH_ || !PH2_ || !VH_ ||
-        !VH2_ || !F1_ || !F2_ || !F3_ || !F4_ || !SH_ || !SH2_ || !SO_ || !VAL_ || !SPK_) {
-        err = "workspace hipMalloc failed";
-        wsB_ = wsM_ = 0;
-        return M0_ERR_HIP;
-    }
     // The clears were enqueued on stream_.  A forward may run on ANOTHER stream (the match engine runs network B on network
     // A's stream, selfplay.hip::one_step), so the (rare) regrowth ends by waiting for them: a late clear would zero
     // activations a kernel already wrote.  The wait also surfaces an asynchronous memset failure.
     // (tests/test_net_gpu.py::test_workspace_regrowth_keeps_results, tests/test_arena_gpu.py::test_step_right_after_create)
-    if (hipStreamSynchronize(stream_) != hipSuccess || hipGetLastError() != hipSuccess) {
-        err = "workspace clear failed"; wsB_ = wsM_ = 0; return M0_ERR_HIP;
+    M0_HIP(*hip_, hipStreamSynchronize(stream_));
+    if (!M0_HIP(*hip_, hipGetLastError())) {     // an allocation (dalloc returned null), a clear or the wait has failed
+        err = "workspace hipMalloc / clear failed: " + hip_->message(); wsB_ = wsM_ = 0; return M0_ERR_HIP;
     }
     wsB_ = Bp; wsM_ = Mfc;
     return M0_OK;
@@ -198,11 +194,11 @@ template <class Launch>
 hipError_t Net::profiled(bool on, hipStream_t st, double flop, bool tail, Launch&& launch) {
     if (!on) return launch();
     if (pev_used_ + 2 > pev_.size()) {
-        for (int i = 0; i < 2; ++i) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return hipErrorOutOfMemory; pev_.push_back(e); }
+        for (int i = 0; i < 2; ++i) { hipEvent_t e; if (!M0_HIP(*hip_, hipEventCreate(&e))) return hip_->code(); pev_.push_back(e); }
     }
-    (void)hipEventRecord(pev_[pev_used_], st);
-    hipError_t rc = launch();
-    (void)hipEventRecord(pev_[pev_used_ + 1], st);
+    M0_HIP(*hip_, hipEventRecord(pev_[pev_used_], st));
+    hipError_t rc = hip_->ok() ? launch() : hip_->code();        // the caller records a failed launch under its own name
+    if (rc == hipSuccess && !M0_HIP(*hip_, hipEventRecord(pev_[pev_used_ + 1], st))) rc = hip_->code();
     pev_used_ += 2;
     pflop_.push_back(flop);
     ptail_.push_back(tail ? 1 : 0);
@@ -279,20 +275,14 @@ void Net::harvest_profile() {
     ptail_.clear();
 }
 
-#define KCHK(x)                                                                           \
-    do {                                                                                  \
-        hipError_t e_ = (x);                                                              \
-        if (e_ != hipSuccess) {                                                           \
-            err = std::string("kernel launch failed: ") + #x + ": " + hipGetErrorString(e_); \
-            return M0_ERR_HIP;                                                            \
-        }                                                                                 \
-    } while (0)
-
+// Every launch goes through M0_HIP on the network's status: after the first failure the rest of the schedule is skipped (the
+// host arithmetic between the launches still runs) and the one test at the end reports it.
 int Net::forward(const float* planes_dev, const _Float16* nhwc_dev, int B, float* logits_dev, float* value_dev,
                  float* ssl_dev, hipStream_t st, std::string& err) {
     if (!finalized_) { err = "weights not finalized"; return M0_ERR_STATE; }
     if (B <= 0) { err = "batch must be positive"; return M0_ERR_INVALID; }
     if (int rc = ensure_workspace(B, err)) return rc;
+    HipStatus& hs = *hip_;
     const int Bp = ceil_to(B, 4);
     const int Mc = Bp * 64;
     const int Mfc = ceil_to(B, 256);
@@ -302,7 +292,7 @@ int Net::forward(const float* planes_dev, const _Float16* nhwc_dev, int B, float
     const _Float16* x0 = nhwc_dev;
     if (!x0) {
         if (!planes_dev) { err = "no input"; return M0_ERR_INVALID; }
-        KCHK(launch_planes_to_nhwc(planes_dev, X0_, B, cfg_.planes, st));
+        M0_HIP(hs, launch_planes_to_nhwc(planes_dev, X0_, B, cfg_.planes, st));
         x0 = X0_;
     }
     // The residual stream alternates between xa (current) and xb; AA_ holds act(bn1(stream)) for the next residual block's
@@ -313,17 +303,17 @@ int Net::forward(const float* planes_dev, const _Float16* nhwc_dev, int B, float
     // stem (resnet.py:314-318) + chess features (229-244)
     ConvNormOpts so;
     if (cfg_.chess_features) so.posenc = posenc_; else so.next_bn1 = first_bn1;
-    KCHK(conv_norm_act(stem_, stem_n_, x0, xa, T1_, Mc, st, so));
+    M0_HIP(hs, conv_norm_act(stem_, stem_n_, x0, xa, T1_, Mc, st, so));
     if (cfg_.chess_features) {
         if (cfg_.piece_square_tables) {
             ConvNormOpts po;
             po.res = xa;
-            KCHK(conv_norm_act(pst_, pst_n_, xa, xb, T1_, Mc, st, po));
+            M0_HIP(hs, conv_norm_act(pst_, pst_n_, xa, xb, T1_, Mc, st, po));
             std::swap(xa, xb);
         }
         ConvNormOpts io;
         io.res = xa; io.next_bn1 = first_bn1;
-        KCHK(conv_norm_act(inter_, inter_n_, xa, xb, T1_, Mc, st, io));
+        M0_HIP(hs, conv_norm_act(inter_, inter_n_, xa, xb, T1_, Mc, st, io));
         std::swap(xa, xb);
     }
     // tower
@@ -333,7 +323,7 @@ int Net::forward(const float* planes_dev, const _Float16* nhwc_dev, int B, float
             const ResBlockW& r = res_[L.index];
             // pre-activation block (resnet.py:45-51): conv1 reads AA_ = act(bn1(x)) and leaves T1_ = act(bn2(conv1)), so conv2
             // also reads a ready operand
-            KCHK(conv_norm_act(r.conv1, r.bn2, AA_, T1_, T2_, Mc, st));
+            M0_HIP(hs, conv_norm_act(r.conv1, r.bn2, AA_, T1_, T2_, Mc, st));
             if (plan_.fuse_tail) {
                 // conv2 + squeeze-excite + residual add + the next block's GroupNorm/activation in one kernel
                 GemmArgs a = gemm_args(r.conv2, T1_, xb, Mc, act);
@@ -341,16 +331,16 @@ int Net::forward(const float* planes_dev, const _Float16* nhwc_dev, int B, float
                 if (next_bn1) { a.y2 = AA_; a.gn_gamma = next_bn1->gamma; a.gn_beta = next_bn1->beta; }
                 if (cfg_.se) { a.se_w1 = r.se_w1; a.se_b1 = r.se_b1; a.se_w2 = r.se_w2; a.se_b2 = r.se_b2; a.se_hidden = r.se_hidden;
                                a.se_wf = r.se_wf; }
-                KCHK(profiled(profile_, st, conv3x3_flop(r.conv2, Mc), true, [&] { return launch_conv_gemm(a, 9, st); }));
+                M0_HIP(hs, profiled(profile_, st, conv3x3_flop(r.conv2, Mc), true, [&] { return launch_conv_gemm(a, 9, st); }));
             } else {
                 GemmArgs a = gemm_args(r.conv2, T1_, T2_, Mc);
                 a.out_stats = S2_;
-                KCHK(run_gemm(r.conv2, a, st));
+                M0_HIP(hs, run_gemm(r.conv2, a, st));
                 EwArgs e = ew_args(T2_, xb, C, act);
                 e.t_stats = S2_; e.res = xa;
-                if (cfg_.se) { KCHK(se_gate(r, S2_, Bp, st)); e.gate = G_; }
+                if (cfg_.se) { M0_HIP(hs, se_gate(r, S2_, Bp, st)); e.gate = G_; }
                 ew_next_bn1(e, next_bn1, AA_);
-                KCHK(launch_ew_board(e, Bp, st));
+                M0_HIP(hs, launch_ew_board(e, Bp, st));
             }
         } else {
             if (L.skip) continue;
@@ -364,19 +354,19 @@ int Net::forward(const float* planes_dev, const _Float16* nhwc_dev, int B, float
                 ab.ln_g = w.ln.gamma; ab.ln_b = w.ln.beta; ab.y = xb;
                 if (next_bn1) { ab.y2 = AA_; ab.gn2_gamma = next_bn1->gamma; ab.gn2_beta = next_bn1->beta; }
                 ab.B = Bp; ab.ln_count = C_; ab.act = act; ab.grid_cap = sw_.attn_grid; ab.mix = cfg_.attention_unmasked_mix; ab.inv_sqrt_d = inv_sqrt_d;
-                KCHK(launch_attn_block(ab, st));
+                M0_HIP(hs, launch_attn_block(ab, st));
             } else {
-                KCHK(run_gemm(w.qkv, gemm_args(w.qkv, xa, QKV_, Mc), st));
+                M0_HIP(hs, run_gemm(w.qkv, gemm_args(w.qkv, xa, QKV_, Mc), st));
                 AttnArgs aa;
                 aa.qkv = QKV_; aa.rel_bias = w.rel_bias; aa.mask = mask_dev_; aa.o = O_;
                 aa.B = Bp; aa.H = C / 16; aa.C = C; aa.mix = cfg_.attention_unmasked_mix;      // head_dim 16; padded heads are all-zero
                 aa.inv_sqrt_d = inv_sqrt_d;
-                KCHK(launch_attn_core(aa, st));
-                KCHK(run_gemm(w.proj, gemm_args(w.proj, O_, T1_, Mc), st));
+                M0_HIP(hs, launch_attn_core(aa, st));
+                M0_HIP(hs, run_gemm(w.proj, gemm_args(w.proj, O_, T1_, Mc), st));
                 EwArgs e = ew_args(T1_, xb, C, act);
                 e.res = xa; e.ln_g = w.ln.gamma; e.ln_b = w.ln.beta; e.ln_count = C_;
                 ew_next_bn1(e, next_bn1, AA_);
-                KCHK(launch_ew_board(e, Bp, st));
+                M0_HIP(hs, launch_ew_board(e, Bp, st));
             }
         }
         std::swap(xa, xb);
@@ -389,40 +379,41 @@ int Net::forward(const float* planes_dev, const _Float16* nhwc_dev, int B, float
         GemmArgs a = gemm_args(hv_, xa, PH2_, Mc, act);
         a.gn_gamma = hv_n_.gamma; a.gn_beta = hv_n_.beta;
         a.ldo = 64; a.out2 = VH2_; a.ldo2 = 128; a.nsplit = 64;
-        KCHK(launch_conv_gemm(a, 1, st));
+        M0_HIP(hs, launch_conv_gemm(a, 1, st));
     } else {
-        KCHK(conv_norm_act(ph_conv_, ph_n_, xa, PH2_, PH_, Mc, st));
+        M0_HIP(hs, conv_norm_act(ph_conv_, ph_n_, xa, PH2_, PH_, Mc, st));
     }
     const bool factored = cfg_.policy_factor_rank > 0;
-    if (factored) KCHK(run_gemm(pfc1_, gemm_args(pfc1_, PH2_, F1_, Mfc, ACT_RELU), st));
+    if (factored) M0_HIP(hs, run_gemm(pfc1_, gemm_args(pfc1_, PH2_, F1_, Mfc, ACT_RELU), st));
     const PackedGemm& plast = factored ? pfc2_ : pfc1_;
     GemmArgs pl = gemm_args(plast, factored ? F1_ : PH2_, logits_dev, Mfc);
     pl.Mvalid = B; pl.out_f32 = 1; pl.out_scale = logit_scale_;
-    KCHK(run_gemm(plast, pl, st));
+    M0_HIP(hs, run_gemm(plast, pl, st));
     // value head (resnet.py:721-734)
-    if (!joint) KCHK(conv_norm_act(vh0_, vh1_n_, xa, VH2_, VH_, Mc, st));
+    if (!joint) M0_HIP(hs, conv_norm_act(vh0_, vh1_n_, xa, VH2_, VH_, Mc, st));
     // value_head.3 reads VH2_: its epilogue form writes VH_, the unfused form passes through VH_ and lands in VH2_ again
     _Float16* vflat = joint ? VH_ : VH2_;
-    KCHK(conv_norm_act(vh3_, vh4_n_, VH2_, vflat, VH_, Mc, st));
-    KCHK(run_gemm(vfc1_, gemm_args(vfc1_, vflat, F2_, Mfc, vact), st));
-    KCHK(run_gemm(vfc2_, gemm_args(vfc2_, F2_, F3_, Mfc, vact), st));
+    M0_HIP(hs, conv_norm_act(vh3_, vh4_n_, VH2_, vflat, VH_, Mc, st));
+    M0_HIP(hs, run_gemm(vfc1_, gemm_args(vfc1_, vflat, F2_, Mfc, vact), st));
+    M0_HIP(hs, run_gemm(vfc2_, gemm_args(vfc2_, F2_, F3_, Mfc, vact), st));
     GemmArgs vg = gemm_args(vgate_, F3_, F4_, Mfc, ACT_SIGMOID);
     vg.mul = F3_;
-    KCHK(run_gemm(vgate_, vg, st));
+    M0_HIP(hs, run_gemm(vgate_, vg, st));
     GemmArgs v3 = gemm_args(vfc3_, F4_, VAL_, Mfc, ACT_TANH);
     v3.out_f32 = 1;
-    KCHK(run_gemm(vfc3_, v3, st));
-    KCHK(hipMemcpy2DAsync(value_dev, 4, VAL_, 32 * 4, 4, B, hipMemcpyDeviceToDevice, st));
+    M0_HIP(hs, run_gemm(vfc3_, v3, st));
+    M0_HIP(hs, hipMemcpy2DAsync(value_dev, 4, VAL_, 32 * 4, 4, B, hipMemcpyDeviceToDevice, st));
     // ssl heads (resnet.py:738-745)
     if (ssl_dev && !ssl_.empty()) {
         const int ctot = ssl_channels_total();
         int coff = 0;
         for (auto& h : ssl_) {
-            KCHK(conv_norm_act(h.c0, h.n, xa, SH2_, SH_, Mc, st));
-            KCHK(run_gemm(h.c1, gemm_args(h.c1, SH2_, SO_, Mc), st));
-            KCHK(launch_nhwc_to_nchw_f32(SO_, ssl_dev, B, 32, h.out_ch, ctot, coff, st));
+            M0_HIP(hs, conv_norm_act(h.c0, h.n, xa, SH2_, SH_, Mc, st));
+            M0_HIP(hs, run_gemm(h.c1, gemm_args(h.c1, SH2_, SO_, Mc), st));
+            M0_HIP(hs, launch_nhwc_to_nchw_f32(SO_, ssl_dev, B, 32, h.out_ch, ctot, coff, st));
             coff += h.out_ch;
         }
     }
+    if (!hs.ok()) { err = "kernel launch failed: " + hs.message(); return M0_ERR_HIP; }
     return M0_OK;
 }

@@ -51,11 +51,8 @@ const HostTensor* Net::get(const std::string& k, size_t count, std::string& err)
 
 int Net::upload_bytes(void*& dst, const void* src, size_t bytes, std::string& err) {
     void* d = dalloc(bytes, false);
-    if (!d) { err = "hipMalloc failed"; return M0_ERR_HIP; }
-    if (bytes) {
-        hipError_t e = hipMemcpy(d, src, bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { err = std::string("weight upload failed: ") + hipGetErrorString(e); return M0_ERR_HIP; }
-    }
+    if (d && bytes) M0_HIP(*hip_, hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
+    if (!hip_->ok()) { err = "weight upload failed: " + hip_->message(); return M0_ERR_HIP; }
     dst = d;
     return M0_OK;
 }
@@ -229,7 +226,7 @@ void Net::make_plan() {
 
 int Net::finalize(std::string& err) {
     if (finalized_) return M0_OK;
-    if (hipSetDevice(device_) != hipSuccess) { err = "hipSetDevice failed"; return M0_ERR_HIP; }
+    if (!M0_HIP(*hip_, hipSetDevice(device_))) { err = hip_->message(); return M0_ERR_HIP; }
     const int C = C_, P = Cp_;          // real / in-memory trunk width (padded channels carry zeros everywhere)
     nparams_ = 0;
     TRY(pack_gemm(stem_, "stem.0.weight", "", conv3x3(cfg_.planes, 32, C, P), err));
@@ -283,7 +280,7 @@ int Net::finalize(std::string& err) {
     if (cfg_.self_supervised) TRY(pack_ssl_heads(err));
     sd_.clear();
     // uploads (blocking NULL-stream copies) have landed before any non-blocking stream reads them
-    if (hipDeviceSynchronize() != hipSuccess) { err = "weight upload failed: hipDeviceSynchronize"; return M0_ERR_HIP; }
+    if (!M0_HIP(*hip_, hipDeviceSynchronize())) { err = "weight upload failed: " + hip_->message(); return M0_ERR_HIP; }
     make_plan();
     finalized_ = true;
     return M0_OK;

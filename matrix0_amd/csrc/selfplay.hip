@@ -32,19 +32,19 @@ static void seed_game_dev(GameDev& g, uint64_t base, int uid) {
     g.ctr_jitter = g.ctr_noise = g.ctr_dir = 0;
 }
 
-int sync_games_d2h(m0_selfplay* sp) {
-    if (hipMemcpyAsync(sp->hg.data(), sp->d.games, sizeof(GameDev) * sp->G, hipMemcpyDeviceToHost, sp->stream) != hipSuccess) return -1;
-    return hipStreamSynchronize(sp->stream) == hipSuccess ? 0 : -1;
+bool sync_games_d2h(m0_selfplay* sp) {
+    M0_HIP(sp->hip, hipMemcpyAsync(sp->hg.data(), sp->d.games, sizeof(GameDev) * sp->G, hipMemcpyDeviceToHost, sp->stream));
+    return M0_HIP(sp->hip, hipStreamSynchronize(sp->stream));
 }
-int sync_games_h2d(m0_selfplay* sp) {
-    return hipMemcpyAsync(sp->d.games, sp->hg.data(), sizeof(GameDev) * sp->G, hipMemcpyHostToDevice, sp->stream) == hipSuccess ? 0 : -1;
+bool sync_games_h2d(m0_selfplay* sp) {
+    return M0_HIP(sp->hip, hipMemcpyAsync(sp->d.games, sp->hg.data(), sizeof(GameDev) * sp->G, hipMemcpyHostToDevice, sp->stream));
 }
 static void push_hist(m0_selfplay* sp, int slot, const RepWindow& w) {
     int n = (int)w.keys.size();
     const uint64_t* src = w.keys.data();
     if (n > M0_HIST_CAP) { src += n - M0_HIST_CAP; n = M0_HIST_CAP; }
     sp->hg[slot].hist_len = n;
-    if (n > 0) (void)hipMemcpyAsync(sp->d.hist + (size_t)slot * M0_HIST_CAP, src, (size_t)n * 8, hipMemcpyHostToDevice, sp->stream);
+    if (n > 0) M0_HIP(sp->hip, hipMemcpyAsync(sp->d.hist + (size_t)slot * M0_HIST_CAP, src, (size_t)n * 8, hipMemcpyHostToDevice, sp->stream));
 }
 
 // configure a search on slot for the host position (MCTS.run prologue, mcts.py:342-396)
@@ -110,10 +110,10 @@ static void finish_game(m0_selfplay* sp, int slot, bool resigned, int resigner, 
             }
             if (T <= sp->ssl_cap) {
                 o->ssl.resize((size_t)T * 17 * 64);
-                (void)hipMemcpyAsync(sp->ssl_pos_dev, hgm.rec_pos.data(), sizeof(Pos) * T, hipMemcpyHostToDevice, sp->stream);
-                (void)launch_ssl_targets(sp->ssl_pos_dev, T, sp->ssl_out_dev, sp->stream);
-                (void)hipMemcpyAsync(o->ssl.data(), sp->ssl_out_dev, (size_t)T * 17 * 64 * 4, hipMemcpyDeviceToHost, sp->stream);
-                (void)hipStreamSynchronize(sp->stream);
+                M0_HIP(sp->hip, hipMemcpyAsync(sp->ssl_pos_dev, hgm.rec_pos.data(), sizeof(Pos) * T, hipMemcpyHostToDevice, sp->stream));
+                M0_HIP(sp->hip, launch_ssl_targets(sp->ssl_pos_dev, T, sp->ssl_out_dev, sp->stream));
+                M0_HIP(sp->hip, hipMemcpyAsync(o->ssl.data(), sp->ssl_out_dev, (size_t)T * 17 * 64 * 4, hipMemcpyDeviceToHost, sp->stream));
+                if (!M0_HIP(sp->hip, hipStreamSynchronize(sp->stream))) o->ssl.clear();   // no targets in the record; the step fails
             }
         }
         m0_game_record r;
@@ -286,29 +286,27 @@ static void finish_search(m0_selfplay* sp, int slot) {
 }
 
 int run_select(m0_selfplay* sp, int* rows_out) {
-    if (hipMemsetAsync(sp->d.row_counter, 0, 8, sp->stream) != hipSuccess || launch_select(sp->d, sp->tc, sp->stream) != hipSuccess ||
-        hipMemcpyAsync(sp->rows2, sp->d.row_counter, 8, hipMemcpyDeviceToHost, sp->stream) != hipSuccess ||
-        hipStreamSynchronize(sp->stream) != hipSuccess) {
-        m0_set_error(std::string("select failed: ") + hipGetErrorString(hipGetLastError()));
-        return M0_ERR_HIP;
-    }
+    M0_HIP(sp->hip, hipMemsetAsync(sp->d.row_counter, 0, 8, sp->stream));
+    M0_HIP(sp->hip, launch_select(sp->d, sp->tc, sp->stream));
+    M0_HIP(sp->hip, hipMemcpyAsync(sp->rows2, sp->d.row_counter, 8, hipMemcpyDeviceToHost, sp->stream));
+    if (!M0_HIP(sp->hip, hipStreamSynchronize(sp->stream))) return m0_hip_error(sp->hip, "select failed");
     *rows_out = sp->rows2[0];              // network 0's rows; network 1's (arena) start at d.net_row_base
     return M0_OK;
 }
 
-static int launch_advances(m0_selfplay* sp) {
+static bool launch_advances(m0_selfplay* sp) {
     const std::vector<int>& ids = sp->adv.slots;
     const std::vector<int>& roots = sp->adv.roots;
-    if (sync_games_h2d(sp) != 0) return -1;
+    if (!sync_games_h2d(sp)) return false;
     if (!ids.empty()) {
-        (void)hipMemcpyAsync(sp->ids_dev, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, sp->stream);
-        (void)hipMemcpyAsync(sp->roots_dev, roots.data(), roots.size() * 4, hipMemcpyHostToDevice, sp->stream);
-        if (launch_advance(sp->d, sp->ids_dev, sp->roots_dev, (int)ids.size(), sp->stream) != hipSuccess) return -1;
-        if (hipStreamSynchronize(sp->stream) != hipSuccess) return -1;   // the list is reused by the next step
+        M0_HIP(sp->hip, hipMemcpyAsync(sp->ids_dev, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, sp->stream));
+        M0_HIP(sp->hip, hipMemcpyAsync(sp->roots_dev, roots.data(), roots.size() * 4, hipMemcpyHostToDevice, sp->stream));
+        M0_HIP(sp->hip, launch_advance(sp->d, sp->ids_dev, sp->roots_dev, (int)ids.size(), sp->stream));
+        if (!M0_HIP(sp->hip, hipStreamSynchronize(sp->stream))) return false;   // the list is reused by the next step
         if (sp->d.tt_sides == 2) {
             // per-side tables: only the device knows whether a root was found in its side's table.  A found root is evaluated
             // once more unless nn_cache holds the position (mcts.py:359-371; the cache belongs to the side's MCTS object).
-            if (sync_games_d2h(sp) != 0) return -1;
+            if (!sync_games_d2h(sp)) return false;
             bool any = false;
             for (size_t k = 0; k < ids.size(); ++k) {
                 if (roots[k] > ROOT_FROM_SIDE_TABLE) continue;
@@ -318,17 +316,16 @@ static int launch_advances(m0_selfplay* sp) {
                 g.reinfer = (g.root_found && nn_cache_miss(sp, tkey(g.root_pos) ^ salt ^ gsalt)) ? 1 : 0;
                 any = any || g.reinfer;
             }
-            if (any && sync_games_h2d(sp) != 0) return -1;
+            if (any && !sync_games_h2d(sp)) return false;
         }
     }
-    return 0;
+    return true;
 }
 
 int apply_advances(m0_selfplay* sp) {
-    const int rc = launch_advances(sp);
+    const bool ok = launch_advances(sp);
     sp->adv.clear();
-    if (rc != 0) { m0_set_error("advance failed"); return M0_ERR_HIP; }
-    return M0_OK;
+    return ok ? M0_OK : m0_hip_error(sp->hip, "advance failed");
 }
 
 static void count_active_games(m0_selfplay* sp) {
@@ -348,7 +345,7 @@ static void start_games(m0_selfplay* sp) {
 
 static int start_first_games(m0_selfplay* sp) {         // lazily, at the first step
     if (sp->stats.games_started != 0) return M0_OK;
-    if (sync_games_d2h(sp) != 0) { m0_set_error("device sync failed"); return M0_ERR_HIP; }
+    if (!sync_games_d2h(sp)) return m0_hip_error(sp->hip, "device sync failed");
     start_games(sp);
     const int rc = apply_advances(sp);
     if (rc != M0_OK) return rc;
@@ -365,7 +362,8 @@ int refill(m0_selfplay* sp) {
 
 // The searches that the last expand finished become moves; games end, free slots start the next ones.
 static int harvest_games(m0_selfplay* sp) {
-    (void)hipMemcpy(sp->hres.data(), sp->d.results, sizeof(RootResult) * sp->G, hipMemcpyDeviceToHost);
+    if (!M0_HIP(sp->hip, hipMemcpy(sp->hres.data(), sp->d.results, sizeof(RootResult) * sp->G, hipMemcpyDeviceToHost)))
+        return m0_hip_error(sp->hip, "harvest failed");
     for (int s = 0; s < sp->G; ++s) {
         if (!(sp->hg[s].active && sp->hg[s].finished)) continue;
         if (sp->hg[s].overflow) sp->stats.arena_overflows++;
@@ -422,16 +420,16 @@ void forward_gate_leave(m0_selfplay* sp) {
 
 // second half of a step: expand / backup on the device, then the host part (counters, the harvest of the finished searches)
 int finish_step(m0_selfplay* sp, int rows, double t0) {
-    (void)hipEventRecord(sp->ev2, sp->stream);
-    if (launch_expand(sp->d, sp->tc, sp->stream) != hipSuccess) { m0_set_error("expand launch failed"); return M0_ERR_HIP; }
-    (void)hipEventRecord(sp->ev3, sp->stream);
-    if (sync_games_d2h(sp) != 0) { m0_set_error(std::string("step failed: ") + hipGetErrorString(hipGetLastError())); return M0_ERR_HIP; }
+    M0_HIP(sp->hip, hipEventRecord(sp->ev2, sp->stream));
+    M0_HIP(sp->hip, launch_expand(sp->d, sp->tc, sp->stream));
+    M0_HIP(sp->hip, hipEventRecord(sp->ev3, sp->stream));
+    if (!sync_games_d2h(sp)) return m0_hip_error(sp->hip, "step failed");
     if (sp->net) sp->net->harvest_profile();
     if (sp->net_b) sp->net_b->harvest_profile();
     float ms_sel = 0, ms_net = 0, ms_exp = 0;
-    (void)hipEventElapsedTime(&ms_sel, sp->ev0, sp->ev1);
-    (void)hipEventElapsedTime(&ms_net, sp->ev1, sp->ev2);
-    (void)hipEventElapsedTime(&ms_exp, sp->ev2, sp->ev3);
+    M0_HIP(sp->hip, hipEventElapsedTime(&ms_sel, sp->ev0, sp->ev1));
+    M0_HIP(sp->hip, hipEventElapsedTime(&ms_net, sp->ev1, sp->ev2));
+    if (!M0_HIP(sp->hip, hipEventElapsedTime(&ms_exp, sp->ev2, sp->ev3))) return m0_hip_error(sp->hip, "step failed");
     sp->stats.ms_net += ms_net; sp->stats.ms_tree += ms_sel + ms_exp;
     sp->stats.steps++; sp->stats.evals += (uint64_t)rows;
     const double t1 = now_ms();
@@ -473,31 +471,31 @@ static RowSplit split_rows(int rows, bool have_tail, bool half_split) {
 int one_step(m0_selfplay* sp) {
     std::string err;                         // Net::forward's
     const double t0 = now_ms();
-    (void)hipEventRecord(sp->ev0, sp->stream);
+    M0_HIP(sp->hip, hipEventRecord(sp->ev0, sp->stream));
     int rows = 0;
     if (run_select(sp, &rows) != M0_OK) return M0_ERR_HIP;
-    (void)hipEventRecord(sp->ev1, sp->stream);
+    if (!M0_HIP(sp->hip, hipEventRecord(sp->ev1, sp->stream))) return m0_hip_error(sp->hip, "step failed");
     if (rows > sp->rows_max || sp->rows2[1] > sp->rows_max) { m0_set_error("row counter overflow"); return M0_ERR_STATE; }
     ForwardGate gate(sp->device, sp->stream, rows > 0 || sp->rows2[1] > 0);
     if (rows > 0) {
         if (!sp->net) { m0_set_error("m0_selfplay_step needs a network (use the split-step API without one)"); return M0_ERR_STATE; }
         const auto [main_rows, tail_rows] = split_rows(rows, sp->net_tail != nullptr, sp->half_split);
         float* ssl = sp->cfg.ssl_in_forward ? sp->ssl_dev : nullptr;
+        if (tail_rows > 0 && !M0_HIP(sp->hip, hipEventRecord(sp->ev_sel, sp->stream)))   // the select kernel has written the batch
+            return m0_hip_error(sp->hip, "step failed");
         m0_net_lock(sp->nethandle);          // an infer_np on the same backend from another thread waits here
-        int rc = M0_OK;
-        if (tail_rows > 0) (void)hipEventRecord(sp->ev_sel, sp->stream);          // the select kernel has written the batch
         // main part first: its launches start at once, the tail's are enqueued while they run
-        rc = sp->net->forward(nullptr, sp->d.x0, main_rows, sp->logits_dev, sp->values_dev, ssl, sp->stream, err);
-        if (rc == M0_OK && tail_rows > 0) {
-            (void)hipStreamWaitEvent(sp->stream_tail, sp->ev_sel, 0);
+        int rc = sp->net->forward(nullptr, sp->d.x0, main_rows, sp->logits_dev, sp->values_dev, ssl, sp->stream, err);
+        if (rc == M0_OK && tail_rows > 0 && M0_HIP(sp->hip, hipStreamWaitEvent(sp->stream_tail, sp->ev_sel, 0))) {
             const size_t sslw = ssl ? (size_t)sp->net->ssl_channels_total() * 64 : 0;
             rc = sp->net_tail->forward(nullptr, sp->d.x0 + (size_t)main_rows * 64 * 32, tail_rows, sp->logits_dev + (size_t)main_rows * 4672,
                                        sp->values_dev + main_rows, ssl ? ssl + (size_t)main_rows * sslw : nullptr, sp->stream_tail, err);
-            (void)hipEventRecord(sp->ev_tail, sp->stream_tail);
-            (void)hipStreamWaitEvent(sp->stream, sp->ev_tail, 0);
+            M0_HIP(sp->hip, hipEventRecord(sp->ev_tail, sp->stream_tail));
+            M0_HIP(sp->hip, hipStreamWaitEvent(sp->stream, sp->ev_tail, 0));
         }
         m0_net_unlock(sp->nethandle);
-        if (rc != M0_OK) { m0_set_error(err); return rc; }
+        if (rc != M0_OK) { sp->hip.check(sp->net->hip()); m0_set_error(err); return rc; }   // a network's HIP failure is the engine's too
+        if (!sp->hip.ok()) return m0_hip_error(sp->hip, "step failed");
         sp->stats.rows_tail += (uint64_t)tail_rows;
     }
     if (sp->rows2[1] > 0) {                 // arena: the other network's leaves, in their own region of the batch
@@ -507,7 +505,7 @@ int one_step(m0_selfplay* sp) {
         int rc = sp->net_b->forward(nullptr, sp->d.x0 + b * 64 * 32, sp->rows2[1], sp->logits_dev + b * 4672,
                                     sp->values_dev + b, nullptr, sp->stream, err);
         m0_net_unlock(sp->nethandle_b);
-        if (rc != M0_OK) { m0_set_error(err); return rc; }
+        if (rc != M0_OK) { sp->hip.check(sp->net_b->hip()); m0_set_error(err); return rc; }
         rows += sp->rows2[1];
     }
     gate.release();

@@ -115,7 +115,7 @@ struct m0_selfplay {
     int G = 0, L = 0, cap = 0, rows_max = 0;
     TreeDev d;
     std::vector<void*> allocs;
-    bool alloc_failed = false;            // a dalloc returned null (read by the creation path)
+    HipStatus hip;                        // every HIP call made for the engine goes through M0_HIP on it; the first failure stays
     std::vector<GameDev> hg;
     std::vector<m0::HostGame> games;
     std::vector<RootResult> hres;
@@ -153,21 +153,27 @@ struct m0_selfplay {
 
 namespace m0 {
 
-// Zeroed device memory that lives as long as the engine; null (and sp->alloc_failed) when hipMalloc fails.
+// Zeroed device memory that lives as long as the engine; null (and the failure in sp->hip) when hipMalloc fails.
 template <typename T>
 T* dalloc(m0_selfplay* sp, size_t count) {
     void* p = nullptr;
     size_t bytes = count * sizeof(T);
     if (bytes == 0) bytes = 16;
-    if (hipMalloc(&p, bytes) != hipSuccess) { sp->alloc_failed = true; return nullptr; }
-    (void)hipMemsetAsync(p, 0, bytes, sp->stream);          // on the engine's own stream: ordered before every kernel that uses it
+    if (!M0_HIP(sp->hip, hipMalloc(&p, bytes))) return nullptr;
     sp->allocs.push_back(p);
+    M0_HIP(sp->hip, hipMemsetAsync(p, 0, bytes, sp->stream));   // on the engine's own stream: ordered before every kernel that uses it
     return (T*)p;
+}
+// The creation paths' test after a group of allocations or creations: false, with the error string set, once sp->hip has failed.
+inline bool hip_ok(m0_selfplay* sp, const char* context) {
+    if (!sp->hip.ok()) m0_hip_error(sp->hip, context);
+    return sp->hip.ok();
 }
 
 // Head of every engine entry point, in this order: a null handle -> `null_result`; the engine's lock; an engine whose kind is
-// not in `kinds` -> M0_ERR_STATE with a message that names the call and the kind; the engine's device for the calls that touch
-// it (`on_device`; a host-only call must not move the calling thread's current device).
+// not in `kinds` -> M0_ERR_STATE with a message that names the call and the kind; for the calls that touch the device
+// (`on_device`; a host-only call must not move the calling thread's current device) an engine whose sp->hip has failed ->
+// M0_ERR_HIP with that first failure's message and no further HIP call, else the engine's device.
 //
 //   call                                                            accepted by
 //   m0_selfplay_step, _poll, _set_openings                          self-play, match
@@ -183,15 +189,15 @@ bool kind_accepted(const m0_selfplay* sp, const char* what, unsigned kinds);   /
     if (!(sp)) { m0_set_error(what ": sp is null"); return null_result; }             \
     std::lock_guard<std::mutex> lk((sp)->mu);                                         \
     if (!m0::kind_accepted(sp, what, kinds)) return M0_ERR_STATE;                     \
-    if (on_device) (void)hipSetDevice((sp)->device)
+    if ((on_device) && !M0_HIP((sp)->hip, hipSetDevice((sp)->device))) return m0_hip_error((sp)->hip)
 #define M0_ENGINE_CALL(sp, what, kinds, on_device) M0_ENGINE_CALL_OR(M0_ERR_INVALID, sp, what, kinds, on_device)
 
 // Internal functions set the error string (m0_set_error) where the error happens and return the M0_ERR_* code.
 // selfplay.hip
 void forward_gate_join(m0_selfplay* sp);        // an engine that owns a network takes part in M0_FORWARD_GATE
 void forward_gate_leave(m0_selfplay* sp);
-int sync_games_d2h(m0_selfplay* sp);            // the slots' control blocks: device -> sp->hg, waited for
-int sync_games_h2d(m0_selfplay* sp);            // ... sp->hg -> device, on the engine's stream
+bool sync_games_d2h(m0_selfplay* sp);           // the slots' control blocks: device -> sp->hg, waited for; false: sp->hip has failed
+bool sync_games_h2d(m0_selfplay* sp);           // ... sp->hg -> device, on the engine's stream
 // Take tree slot `slot` for `line`: a new HostGame, random streams keyed by `uid`, no evaluations counted yet.
 HostGame& occupy_slot(m0_selfplay* sp, int slot, Line&& line, int uid);
 // Arm a search of the slot's position (MCTS.run prologue) and queue its root (a child of the old root or a RootMode) in sp->adv.

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <map>
+#include "hip_check.h"
 #include "tb.h"
 
 namespace m0 {
@@ -45,21 +46,17 @@ struct DeviceBuild {
 
 }  // namespace
 
-#define TB_HIP(call)                                                                                         \
-    do {                                                                                                     \
-        const hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(e_); return M0_ERR_HIP; } \
-    } while (0)
-
 int tb_build_on_device(int hip_device, const std::vector<std::string>& order, m0_tb* tb, std::string& err) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { err = "no HIP device available (the tables are built on the GPU)"; return M0_ERR_HIP; }
     if (hip_device < 0 || hip_device >= ndev) { err = "hip_device out of range"; return M0_ERR_INVALID; }
-    TB_HIP(hipSetDevice(hip_device));
+    HipStatus hs;                                    // of this build: tested wherever the host waits for the stream
+    auto failed = [&] { err = hs.message(); return M0_ERR_HIP; };
+    M0_HIP(hs, hipSetDevice(hip_device));
     DeviceBuild B;
-    TB_HIP(hipStreamCreateWithFlags(&B.stream, hipStreamNonBlocking));
-    TB_HIP(hipMalloc((void**)&B.set_dev, sizeof(TbSet)));
-    TB_HIP(hipMalloc((void**)&B.counters_dev, 2 * sizeof(unsigned int)));
+    M0_HIP(hs, hipStreamCreateWithFlags(&B.stream, hipStreamNonBlocking));
+    M0_HIP(hs, hipMalloc((void**)&B.set_dev, sizeof(TbSet)));
+    if (!M0_HIP(hs, hipMalloc((void**)&B.counters_dev, 2 * sizeof(unsigned int)))) return failed();
     TbSet set_host;
     for (auto& t : set_host.tab) t = nullptr;
     tb->tables.clear();
@@ -76,14 +73,13 @@ int tb_build_on_device(int hip_device, const std::vector<std::string>& order, m0
         }
         const uint32_t total = tb_entries(T.sig.n);
         uint8_t* tab = nullptr;
-        TB_HIP(hipMalloc((void**)&tab, total));
+        if (!M0_HIP(hs, hipMalloc((void**)&tab, total))) return failed();
         B.resident[T.name] = tab;
         set_host.tab[tb_material_code(T.sig)] = tab;
-        TB_HIP(hipMemcpyAsync(B.set_dev, &set_host, sizeof(TbSet), hipMemcpyHostToDevice, B.stream));
-        TB_HIP(hipStreamSynchronize(B.stream));                 // set_host changes again below
+        M0_HIP(hs, hipMemcpyAsync(B.set_dev, &set_host, sizeof(TbSet), hipMemcpyHostToDevice, B.stream));
+        M0_HIP(hs, hipStreamSynchronize(B.stream));             // set_host changes again below
         const unsigned int blocks = (total + TB_BLOCK - 1) / TB_BLOCK;
-        hipLaunchKernelGGL(tb_init_kernel, dim3(blocks), dim3(TB_BLOCK), 0, B.stream, T.sig, tab, total);
-        TB_HIP(hipGetLastError());
+        M0_HIP(hs, (tb_init_kernel<<<blocks, TB_BLOCK, 0, B.stream>>>(T.sig, tab, total), hipGetLastError()));
         // sweep n decides the entries with d == n; stop after two sweeps in a row that change nothing, once n has passed
         // every d + 1 of the tables this one reads (a later d of theirs could still decide an entry here)
         int quiet = 0, n = 0;
@@ -91,12 +87,10 @@ int tb_build_on_device(int hip_device, const std::vector<std::string>& order, m0
             ++n;
             if (n + 1 >= TB_INVALID) { err = T.name + ": a distance to mate does not fit the entry byte"; return M0_ERR_STATE; }
             unsigned int counters[2] = {0, 0};
-            TB_HIP(hipMemsetAsync(B.counters_dev, 0, sizeof(counters), B.stream));
-            hipLaunchKernelGGL(tb_sweep_kernel, dim3(blocks), dim3(TB_BLOCK), 0, B.stream, T.sig, (const TbSet*)B.set_dev, tab,
-                               total, n, B.counters_dev);
-            TB_HIP(hipGetLastError());
-            TB_HIP(hipMemcpyAsync(counters, B.counters_dev, sizeof(counters), hipMemcpyDeviceToHost, B.stream));
-            TB_HIP(hipStreamSynchronize(B.stream));
+            M0_HIP(hs, hipMemsetAsync(B.counters_dev, 0, sizeof(counters), B.stream));
+            M0_HIP(hs, (tb_sweep_kernel<<<blocks, TB_BLOCK, 0, B.stream>>>(T.sig, B.set_dev, tab, total, n, B.counters_dev), hipGetLastError()));
+            M0_HIP(hs, hipMemcpyAsync(counters, B.counters_dev, sizeof(counters), hipMemcpyDeviceToHost, B.stream));
+            if (!M0_HIP(hs, hipStreamSynchronize(B.stream))) return failed();
             if (counters[1] & TB_WHY_NO_TABLE) { err = T.name + ": a move leads into a table that is not in the set"; return M0_ERR_STATE; }
             if (counters[1] & TB_WHY_BAD_ENTRY) { err = T.name + ": a legal move reaches an invalid entry (index or decode bug)"; return M0_ERR_STATE; }
             if (counters[0]) { quiet = 0; T.maxd = n; } else ++quiet;
@@ -104,8 +98,8 @@ int tb_build_on_device(int hip_device, const std::vector<std::string>& order, m0
         }
         T.sweeps = n;
         T.bytes.resize(total);
-        TB_HIP(hipMemcpyAsync(T.bytes.data(), tab, total, hipMemcpyDeviceToHost, B.stream));
-        TB_HIP(hipStreamSynchronize(B.stream));
+        M0_HIP(hs, hipMemcpyAsync(T.bytes.data(), tab, total, hipMemcpyDeviceToHost, B.stream));
+        if (!M0_HIP(hs, hipStreamSynchronize(B.stream))) return failed();
         if (T.maxd < 0)                                   // no sweep decided anything: d = 0 if there is a checkmate at all
             for (uint8_t v : T.bytes) if (v == 1) { T.maxd = 0; break; }
         T.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

@@ -49,6 +49,14 @@ SHIMS = {
         "pk_attn_mask": (None, [vp]),
         "pk_joint_columns": (i64, [vp, i32, vp, i32, i32, vp, i64]),
     },
+    "check": {                                          # csrc/hip_check.h with injected hipError_t values; (..., msg, capacity)
+        "hk_run": (i32, [vp, i32, vp, P(i32), vp, i32]),
+        "hk_fresh": (i32, []),
+        "hk_check_twice": (i32, [i32, i32, vp, i32]),
+        "hk_adopt": (i32, [i32, i32, vp, i32]),
+        "hk_convert": (i32, [i32, cstr, vp, i32]),
+        "hk_error_string": (None, [i32, vp, i32]),
+    },
 }
 
 
