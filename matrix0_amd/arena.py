@@ -37,6 +37,7 @@ from datetime import datetime
 from typing import Dict, List, Optional, Tuple
 
 from . import engine as eng
+from .pgn import save_pgn
 
 K_DEFAULT = 20.0
 
@@ -71,33 +72,6 @@ def game_score(result: str, a_is_white: bool) -> float:
     if result == "0-1":
         return 0.0 if a_is_white else 1.0
     return 0.5
-
-
-def save_pgn(moves_raw, result: str, headers: Dict[str, str], out_dir: str, idx: int, start_fen: Optional[str] = None) -> str:
-    """game_{idx:04d}.pgn with the seven-tag roster + caller headers and SAN movetext (lines wrapped at 80 columns).  A game
-    from an opening-book position (`start_fen`) also carries [SetUp "1"] and [FEN "..."], and its move numbers follow the FEN."""
-    os.makedirs(out_dir, exist_ok=True)
-    tags = {"Event": "?", "Site": "?", "Date": "????.??.??", "Round": "?", "White": "?", "Black": "?", "Result": result}
-    tags.update({k: str(v) for k, v in headers.items()})
-    tags["Result"] = result
-    if start_fen:
-        tags["SetUp"], tags["FEN"] = "1", start_fen
-    words = (eng.san_game(moves_raw, start_fen).split() if len(moves_raw) else []) + [result]
-    lines, cur = [], ""
-    for w in words:
-        if cur and len(cur) + 1 + len(w) > 80:
-            lines.append(cur)
-            cur = w
-        else:
-            cur = w if not cur else cur + " " + w
-    if cur:
-        lines.append(cur)
-    path = os.path.join(out_dir, f"game_{idx:04d}.pgn")
-    with open(path, "w") as f:
-        for k, v in tags.items():
-            f.write(f'[{k} "{v}"]\n')
-        f.write("\n" + "\n".join(lines) + "\n")
-    return path
 
 
 def arena_cfg_from_dict(cfg: dict, *, games: int, num_sims: int, max_moves: int, temp: float, temp_plies: int,

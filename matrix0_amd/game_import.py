@@ -8,32 +8,30 @@ wave per game, with the search's own move generator; planes, masks and SSL maps 
 and engine.ssl_targets_fens.  There is no CPU implementation.
 
     replay_games(games)       [(start_fen or None, tokens)] -> per-game arrays
-    read_pgn(path_or_text)    -> (headers, tokens) per game
+    read_pgn(path_or_text)    -> (headers, tokens) per game (pgn.py)
     import_pgn(path, out_dir) -> <prefix>_<index>.npz shards with s / pi / z (/ legal_mask / ssl_<task>) and a summary
     python -m matrix0_amd.game_import PGN OUT_DIR [--lichess ...]
 """
 from __future__ import annotations
 
 import argparse
-import bz2
 import ctypes as C
 import json
 import os
-import re
 import sys
 import time
-from typing import Dict, Iterator, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import _lib
 from ._abi import MOVE_RAW, MOVE_UCI, REPLAY_END_BITS as END_BITS, REPLAY_STATUS as STATUS
 from ._lib import ptr
-from .pgn_book import RESULTS, _TOKEN, _games
+from .data_writer import RowBuffer, write_npz
+from .pgn import mainline_tokens, read_pgn  # noqa: F401  (the readers live in pgn.py; callers know them under this module too)
 
 SSL_KEYS = _lib.SSL_ORDER
 _RESULT_Z = {"1-0": 1.0, "0-1": -1.0, "1/2-1/2": 0.0}
-_MOVE_NUMBER = re.compile(r"^\d+\.(?:\.\.)?")
 
 _pattern_cache: Dict[Tuple[str, object], int] = {}
 
@@ -114,51 +112,6 @@ def replay_games(games: Sequence[Tuple[Optional[str], Sequence]], *, notation: s
     return res
 
 
-# ---- PGN ----
-
-def _read_text(path_or_text) -> str:
-    """The text of a PGN file (.bz2 through the standard library), or the argument itself when it is PGN text."""
-    if isinstance(path_or_text, os.PathLike) or ("\n" not in path_or_text and os.path.exists(path_or_text)):
-        p = os.fspath(path_or_text)
-        opener = bz2.open if p.endswith(".bz2") else open
-        with opener(p, "rt", errors="replace") as f:
-            return f.read()
-    return path_or_text
-
-
-def mainline_tokens(movetext: str) -> List[str]:
-    """The mainline's move tokens: comments, NAGs, variations, move numbers (also glued: "1.e4", "12...Nf6") and the result token
-    removed.  Annotations and check marks stay on the tokens; the pattern parser drops them."""
-    out: List[str] = []
-    depth = 0
-    for tok in _TOKEN.findall(movetext):
-        if tok[0] in "{$":
-            continue
-        if tok == "(":
-            depth += 1
-            continue
-        if tok == ")":
-            depth = max(0, depth - 1)
-            continue
-        if depth > 0:
-            continue
-        if tok in RESULTS:
-            break
-        if tok == "..." or not tok.strip("!?"):                  # a stand-alone annotation is a NAG
-            continue
-        tok = _MOVE_NUMBER.sub("", tok)
-        if tok:
-            out.append(tok)
-    return out
-
-
-def read_pgn(path_or_text) -> Iterator[Tuple[dict, List[str]]]:
-    """(headers, tokens) per game of a PGN file or text.  The start position is headers["FEN"] when there is one, as
-    python-chess's Game.board() takes it."""
-    for headers, movetext in _games(_read_text(path_or_text)):
-        yield headers, mainline_tokens(movetext)
-
-
 # ---- PGN -> shards ----
 
 def _elo(headers: dict, key: str) -> Optional[int]:
@@ -183,52 +136,33 @@ def _passes(headers: dict, min_elo: int, require_normal_termination: bool, skip_
 
 
 class _ShardWriter:
-    """Collects sample arrays and writes <prefix>_<index:06d>.npz with exactly shard_size samples each (the tail is shorter)."""
+    """Collects sample arrays (data_writer.RowBuffer) and writes <prefix>_<index:06d>.npz with exactly shard_size samples each
+    (the tail is shorter) through data_writer.write_npz; no row in the shard index."""
 
     def __init__(self, out_dir: str, prefix: str, shard_size: int):
         self.out_dir, self.prefix, self.shard_size = out_dir, prefix, int(shard_size)
-        self.parts: List[Dict[str, np.ndarray]] = []
-        self.held = 0
+        self.buf = RowBuffer()
         self.shards = 0
         self.seconds = 0.0
         os.makedirs(out_dir, exist_ok=True)
 
     def add(self, part: Dict[str, np.ndarray]) -> None:
-        self.parts.append(part)
-        self.held += len(part["z"])
-        while self.held >= self.shard_size:
+        self.buf.add(part)
+        while self.buf.rows >= self.shard_size:
             self._write(self.shard_size)
 
     def finish(self) -> None:
-        if self.held:
-            self._write(self.held)
+        if self.buf.rows:
+            self._write(self.buf.rows)
 
     def _write(self, n: int) -> None:
         t0 = time.perf_counter()
-        take: List[Dict[str, np.ndarray]] = []
-        need = n
-        while need:
-            part = self.parts[0]
-            k = len(part["z"])
-            if k <= need:
-                take.append(self.parts.pop(0))
-                need -= k
-            else:
-                take.append({key: a[:need] for key, a in part.items()})
-                self.parts[0] = {key: a[need:] for key, a in part.items()}
-                need = 0
-        arrays = {key: np.concatenate([p[key] for p in take]) for key in take[0]}
-        idx = arrays.pop("_pi_idx")
+        arrays = self.buf.take(n)
         pi = np.zeros((n, 4672), np.float32)
-        pi[np.arange(n), idx] = 1.0
+        pi[np.arange(n), arrays.pop("_pi_idx")] = 1.0
         arrays["pi"] = pi
-        path = os.path.join(self.out_dir, f"{self.prefix}_{self.shards:06d}.npz")
-        tmp = f"{path}.{os.getpid()}.tmp"
-        with open(tmp, "wb") as f:                                     # a reader never sees a partial shard
-            np.savez_compressed(f, **arrays)
-        os.replace(tmp, path)
+        write_npz(os.path.join(self.out_dir, f"{self.prefix}_{self.shards:06d}.npz"), arrays)
         self.shards += 1
-        self.held -= n
         self.seconds += time.perf_counter() - t0
 
 

@@ -1,40 +1,34 @@
 """Training-side reader of the shards this package writes: the replay path of the reference's trainer input
 (azchess/training/npz_dataset.py:15-109 NPZBatchIterableDataset(mode="replay") over DataManager.get_training_batch /
 _iter_shard_samples, azchess/data_manager.py:264-470).  Same contract: shards come from the `shards` table of
-<base>/data_metadata.db (rows marked corrupted are skipped), a shard must hold `s` float32 (T,planes,8,8), `pi` float32
-(T,4672) and `z` float32 (T,) or (T,1) without NaN/Inf or it is MARKED corrupted and skipped (data_manager.py:411-424,
+<base>/data_metadata.db, read through data_writer.ShardIndex (rows marked corrupted are skipped), a shard must hold `s`
+float32 (T,planes,8,8), `pi` float32 (T,4672) and `z` float32 (T,) or (T,1) without NaN/Inf or it is MARKED corrupted and skipped (data_manager.py:411-424,
 1861-1946), `legal_mask` is reshaped to (T,4672) uint8, samples are shuffled within a shard and shards within an epoch, and
 only full batches are yielded, as tuples (s, pi, z, legal_mask) -- or (s, pi, z) when some row of the batch has no mask.
-Pure data plumbing (numpy + sqlite3): no GPU code here."""
+Pure data plumbing (numpy): no GPU code here."""
 from __future__ import annotations
 
-import sqlite3
 from pathlib import Path
 from typing import Iterator, List, Optional, Tuple
 
 import numpy as np
 
+from .data_writer import ShardIndex
+
 
 class ReplayReader:
     def __init__(self, base_dir: str = "data", expected_planes: int = 19, seed: Optional[int] = None):
         self.base_dir = Path(base_dir)
-        self.db_path = self.base_dir / "data_metadata.db"
+        self.index = ShardIndex(self.base_dir, create=False)      # a directory without a database has no shards, and gets none
         self.expected_planes = int(expected_planes)
         self.rng = np.random.default_rng(seed)
 
     # -- shard table ----------------------------------------------------------------------------------------------
     def valid_shards(self, sources: Tuple[str, ...] = ("selfplay", "")) -> List[str]:
-        if not self.db_path.exists():
-            return []
-        conn = sqlite3.connect(str(self.db_path), timeout=30)
-        rows = conn.execute("SELECT path, source FROM shards WHERE corrupted = 0 OR corrupted IS NULL").fetchall()
-        conn.close()
-        return [p for p, src in rows if (src or "") in sources and Path(p).exists()]
+        return [p for p, _, src, corrupted in self.index.rows() if not corrupted and (src or "") in sources and Path(p).exists()]
 
     def mark_corrupted(self, path: str) -> None:
-        conn = sqlite3.connect(str(self.db_path), timeout=30)
-        conn.execute("UPDATE shards SET corrupted = 1 WHERE path = ?", (path,))
-        conn.commit(); conn.close()
+        self.index.mark_corrupted(path)
 
     # -- validation (data_manager.py _validate_shapes / _validate_dtypes_and_ranges) ------------------------------------
     def _load(self, path: str):

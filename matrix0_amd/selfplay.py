@@ -37,16 +37,16 @@ from . import encoding
 from .backend import M0Backend
 from .data_writer import ReplayShardWriter, SelfplayShardWriter
 from .engine import SelfplayEngine, SelfplayPool, selfplay_cfg_from_dict
+from .pgn import START_FEN
 from .tablebase import Tablebase, probe_limit, tablebase_cfg
 from .weights import random_state_dict
 
-START_W = "rnbqkbnr/pppppppp/8/8/8/8/PPPPPPPP/RNBQKBNR w KQkq - 0 1"
-START_B = "rnbqkbnr/pppppppp/8/8/8/8/PPPPPPPP/RNBQKBNR b KQkq - 0 1"
+START_B = START_FEN.replace(" w ", " b ")                  # the same position with Black to move
 
 
 def detect_value_from_white(backend: M0Backend) -> bool:
     """selfplay/internal.py:203-238: same position with either side to move; side-to-move nets flip sign."""
-    planes, _, _ = encoding.encode_fens([START_W, START_B], want_moves=False)
+    planes, _, _ = encoding.encode_fens([START_FEN, START_B], want_moves=False)
     _, v = backend.infer_np(planes)
     v1, v2 = float(v[0]), float(v[1])
     return not (abs(v2 + v1) < abs(v2 - v1))

@@ -97,6 +97,8 @@ def test_setup_fen_header_and_bad_token():
     assert pgn_book.mainline_fens({"FEN": pfen}, "1. e8=N+ Kf8", 20) == _oracle_fens(["e7e8n", "g7f8"], start=pfen)
     assert pgn_book.mainline_fens({}, "1. e4 e5 2. Nf3 *  3. Nc3", 20) == _oracle_fens(["e2e4", "e7e5", "g1f3"])
     assert pgn_book.mainline_fens({}, "1. e4 e5 2. Nf3 Nc6", 3) == _oracle_fens(["e2e4", "e7e5", "g1f3"])
+    # a stand-alone annotation glyph is a NAG (python-chess reads it so): skipped, it does not end the line
+    assert pgn_book.mainline_fens({}, "1. e4 ! e5 ?! 2. Nf3", 20) == _oracle_fens(["e2e4", "e7e5", "g1f3"])
 
 
 def test_fen_after_matches_the_oracle_incl_en_passant_and_errors():

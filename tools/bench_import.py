@@ -7,8 +7,8 @@ the package had before it, over the same games of one PGN file and in one proces
 --repeat takes the file's games that many times over (a small file at a size worth timing); --runs repeats the two timed device
 calls and reports every run, so that the spread is on record.
 
-host path    what pgn_book.mainline_fens does per ply, without its 20-ply cap: the SAN list of the position (m0_san_legal_fen),
-             a string match, m0_fen_after; then one encoding.encode_fens call over all positions (planes and masks).
+host path    what pgn_book.mainline_fens does per ply, without its 20-ply cap: pgn_book.resolve_san (the SAN list of the position,
+             m0_san_legal_fen, and a string match), m0_fen_after; then one encoding.encode_fens call over all positions (planes and masks).
 device path  tokens -> patterns on the host, m0_replay_games (replay kernel, position encoder, copy back), then the shards.
 
 For the device path the wall time is split: parse (PGN text -> headers and tokens, inside import_pgn), patterns (tokens -> 32-bit patterns), replay (the call
@@ -31,14 +31,14 @@ def host_path(games, device):
     """[(headers, tokens)] -> positions resolved, seconds resolving, seconds encoding."""
     from matrix0_amd import encoding as enc
     from matrix0_amd import engine as eng
-    from matrix0_amd.pgn_book import START_FEN, _norm
+    from matrix0_amd.pgn import START_FEN
+    from matrix0_amd.pgn_book import resolve_san
     t0 = time.perf_counter()
     fens = []
     for headers, tokens in games:
         fen = headers.get("FEN") or START_FEN
         for tok in tokens:
-            want = _norm(tok)
-            hit = next((u for u, san in eng.san_legal(fen) if _norm(san) == want), None)
+            hit = resolve_san(fen, tok)
             if hit is None:
                 break
             fens.append(fen)
@@ -60,9 +60,10 @@ def main() -> int:
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "game_import.log"))
     a = ap.parse_args()
     from matrix0_amd import game_import as gi
+    from matrix0_amd import pgn
 
     games = []
-    for headers, tokens in gi.read_pgn(a.pgn):
+    for headers, tokens in pgn.read_pgn(a.pgn):
         if tokens:
             games.append((headers, tokens))
         if len(games) >= a.games:
