@@ -209,11 +209,23 @@ FUNCTIONS = {
     "m0_replay_games": (i32, [i32, cstrs, vp, vp, i32, i32, i32] + [vp] * 10),
 }
 
+# ---- include/m0_analysis_live.h (which m0_engine.h includes): live searches on an analysis engine, in that header's order;
+# tests/test_abi_live.py compares the two as tests/test_abi.py compares the table above with m0_engine.h ----
+LIVE_FUNCTIONS = {
+    "m0_analysis_submit_keep": (i32, [vp, cstr, cstrs, i32, i32, i64]),
+    "m0_analysis_peek": (i32, [vp, i64, _res]),
+    "m0_analysis_stop": (i32, [vp, i64]),
+    "m0_analysis_continue": (i32, [vp, i64, cstrs, i32, i32, i64, i32, _pi32]),
+    "m0_analysis_release": (i32, [vp, i64]),
+    "m0_analysis_held": (i32, [vp]),
+}
+
 
 def bind(L) -> list:
-    """Set restype and argtypes of every function of FUNCTIONS on the loaded library; the names it does not export."""
+    """Set restype and argtypes of every function of FUNCTIONS and LIVE_FUNCTIONS on the loaded library; the names it does not
+    export."""
     missing = []
-    for name, (restype, argtypes) in FUNCTIONS.items():
+    for name, (restype, argtypes) in list(FUNCTIONS.items()) + list(LIVE_FUNCTIONS.items()):
         fn = getattr(L, name, None)
         if fn is None:
             missing.append(name)

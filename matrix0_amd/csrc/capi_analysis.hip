@@ -3,8 +3,12 @@
 // filled from a host queue (analysis_refill, the engine's `refill`), searched by the pass of m0_selfplay_step (one_step / the
 // external-evaluator pair) and emptied by the result kernel (analysis_harvest, its `harvest`); positions that ask for no search go through the position
 // encoder, one forward and the policy kernel (policy_pass).
+// Live searches (include/m0_analysis_live.h): a running search is read with the result kernel on its one slot (live_result:
+// peek, and stop, which answers with that very readout), a search submitted with keep leaves its tree in its slot (held), and
+// m0_analysis_continue re-roots a held tree by moves on the device (tree_reroot.hip) and searches on in place.
 #include <string.h>
 #include <algorithm>
+#include <string>
 #include <memory>
 #include "selfplay_engine.h"
 #include "planes_decode.h"
@@ -14,9 +18,9 @@ using namespace m0;
 
 namespace m0 {
 
-static int searches_pending(const m0_selfplay* sp) {          // queued or in a slot
+static int searches_pending(const m0_selfplay* sp) {          // queued or searched in a slot (a held slot searches nothing)
     int n = (int)sp->an->queue.size();
-    for (const HostGame& hgm : sp->games) n += hgm.in_use ? 1 : 0;
+    for (int s = 0; s < sp->G; ++s) n += sp->games[s].in_use && !sp->an->held[s] ? 1 : 0;
     return n;
 }
 static int pending_count(const m0_selfplay* sp) { return searches_pending(sp) + (int)sp->an->policy_queue.size(); }
@@ -35,21 +39,26 @@ static void answer(Analysis& a, const m0_analysis_result& r, std::vector<int32_t
 }
 
 // What m0_analysis_submit does with a position once it stands in job.line and job.nlegal is known: roots without legal moves
-// and roots inside the attached tables are answered here, on the host; every other one waits for a slot (or a policy pass).
-static void queue_job(m0_selfplay* sp, AnalysisJob&& job) {
+// and roots inside the attached tables are answered here, on the host (answered_on_host); every other one waits for a slot (or
+// a policy pass).
+static bool answered_on_host(m0_selfplay* sp, const AnalysisJob& job) {
     if (job.nlegal == 0) {                 // no search, no evaluation, no slot
         m0_analysis_result r = blank_result(job);
         r.status = in_check(job.line.pos) ? 1 : 2;
         answer(*sp->an, r);
-        return;
+        return true;
     }
     if (sp->tb) {                          // a root inside the attached tables: answered from them, as the two cases above
         m0_analysis_result r = blank_result(job);
         if (tb_root_lines(sp->tb, sp->tb_max_pieces, job.line.pos, sp->an->opts.multipv, sp->an->opts.pv_len, &r)) {
             answer(*sp->an, r);
-            return;
+            return true;
         }
     }
+    return false;
+}
+static void queue_job(m0_selfplay* sp, AnalysisJob&& job) {
+    if (answered_on_host(sp, job)) return;
     (job.sims == 0 ? sp->an->policy_queue : sp->an->queue).push_back(std::move(job));
 }
 
@@ -59,6 +68,12 @@ static void copy_lines(const Analysis& a, int j, m0_analysis_result& r) {
     for (int l = 0; l < r.nlines; ++l) r.lines[l] = a.hlines[(size_t)j * M0_AN_MAX_LINES + l];
 }
 
+// An answered search leaves its slot: free for the next one, or held with its tree (submitted with keep).
+static void leave_slot(m0_selfplay* sp, int s) {
+    sp->an->held[s] = sp->an->slot_job[s].keep ? 1 : 0;
+    sp->games[s].in_use = sp->an->slot_job[s].keep;
+}
+
 // Free slots take the next queued searches: a fresh tree each, random streams keyed by the submission's id (not by the slot).
 int analysis_refill(m0_selfplay* sp) {
     Analysis& a = *sp->an;
@@ -66,16 +81,17 @@ int analysis_refill(m0_selfplay* sp) {
         if (sp->games[s].in_use) continue;
         AnalysisJob& job = a.queue.front();
         occupy_slot(sp, s, std::move(job.line), (int)job.id);
-        a.slot_job[s] = AnalysisJob{Line(), job.sims, job.nlegal, job.id};
+        a.slot_job[s] = AnalysisJob{Line(), job.sims, job.nlegal, job.id, job.keep};
         a.queue.pop_front();
         sp->hg[s].net_id = 0;
+        sp->hg[s].root_n = 0; sp->hg[s].root_q = 0.0; sp->hg[s].root_v = 0.0;   // what a peek before the first pass reports
         begin_search(sp, s, a.slot_job[s].sims, a.opts.dirichlet != 0, ROOT_FRESH);
     }
     return sp->adv.empty() ? M0_OK : apply_advances(sp);
 }
 
 // The searches that the last expand finished: their lines from the result kernel (the trees stay on the device), the rest
-// from the slots' control blocks, which the step has just mirrored.  The slots are free afterwards.
+// from the slots' control blocks, which the step has just mirrored.  The slots are free afterwards (or held: leave_slot).
 int analysis_harvest(m0_selfplay* sp) {
     Analysis& a = *sp->an;
     a.finished.clear();
@@ -114,7 +130,7 @@ int analysis_harvest(m0_selfplay* sp) {
         }
         answer(a, r, std::move(children));
         g.active = 0; g.finished = 0;
-        sp->games[s].in_use = false;
+        leave_slot(sp, s);
     }
     return sync_games_h2d(sp) ? M0_OK : m0_hip_error(hs, "releasing the slots failed");
 }
@@ -156,6 +172,49 @@ static int policy_pass(m0_selfplay* sp) {
     return M0_OK;
 }
 
+// Queued searches that can never start: none is in a slot and every slot is held.  Sets the error string.
+static bool blocked_by_held(const m0_selfplay* sp) {
+    if (sp->an->queue.empty()) return false;
+    for (int s = 0; s < sp->G; ++s) if (!sp->games[s].in_use || !sp->an->held[s]) return false;
+    m0_set_error("searches are queued but every slot is held: m0_analysis_release or m0_analysis_continue one");
+    return true;
+}
+
+// ---- live searches (include/m0_analysis_live.h)
+static bool live_call_ok(const m0_selfplay* sp, const char* what) {
+    if (!sp->ext_pending) return true;
+    m0_set_error(std::string(what) + ": m0_analysis_ext_expand outstanding");
+    return false;
+}
+static int slot_of(const m0_selfplay* sp, int64_t id, bool held) {      // the slot that searches / holds `id`, -1: none
+    for (int s = 0; s < sp->G; ++s)
+        if (sp->games[s].in_use && (sp->an->held[s] != 0) == held && sp->an->slot_job[s].id == id) return s;
+    return -1;
+}
+template <typename Q> static typename Q::iterator queued(Q& q, int64_t id) {
+    return std::find_if(q.begin(), q.end(), [id](const AnalysisJob& j) { return j.id == id; });
+}
+
+// The result of the search in slot s as it stands: the lines from the result kernel on that one slot (it reads the tree, not
+// the block a finished search writes), the rest from the slot's control block, read back first.
+static int live_result(m0_selfplay* sp, int s, m0_analysis_result& r) {
+    Analysis& a = *sp->an;
+    HipStatus& hs = sp->hip;
+    M0_HIP(hs, hipMemcpyAsync(sp->ids_dev, &s, 4, hipMemcpyHostToDevice, sp->stream));
+    M0_HIP(hs, launch_analysis_lines(sp->d, sp->ids_dev, 1, a.opts.multipv, a.opts.pv_len, a.lines_dev, a.nlines_dev, sp->stream));
+    M0_HIP(hs, hipMemcpyAsync(a.hlines.data(), a.lines_dev, sizeof(m0_analysis_line) * M0_AN_MAX_LINES, hipMemcpyDeviceToHost, sp->stream));
+    M0_HIP(hs, hipMemcpyAsync(a.hnlines.data(), a.nlines_dev, 4, hipMemcpyDeviceToHost, sp->stream));
+    if (!sync_games_d2h(sp)) return m0_hip_error(hs, "reading a running search failed");
+    const GameDev& g = sp->hg[s];
+    r = blank_result(a.slot_job[s]);
+    r.sims = g.sims_done;
+    r.overflow = g.overflow; r.root_n = g.root_n; r.evals = g.evals;
+    r.value = (float)g.root_v;
+    r.root_q = g.root_n > 0 ? g.root_q : g.root_v;
+    copy_lines(a, 0, r);
+    return M0_OK;
+}
+
 static m0_selfplay* analysis_create_impl(m0_net* nh, const m0_selfplay_cfg* cfg, const m0_analysis_opts* opts) {
     if (!cfg || !opts) { m0_set_error("cfg / opts is null"); return nullptr; }
     if (opts->multipv < 1 || opts->multipv > M0_AN_MAX_LINES || opts->pv_len < 1 || opts->pv_len > M0_AN_MAX_PV) {
@@ -178,6 +237,9 @@ static m0_selfplay* analysis_create_impl(m0_net* nh, const m0_selfplay_cfg* cfg,
     a->opts = *opts;
     const size_t R = (size_t)sp->rows_max;
     a->slot_job.resize(sp->G);
+    a->held.assign(sp->G, 0);
+    a->reroot_in_dev = dalloc<int>(sp, 2 + M0_REROOT_MAX_MOVES);
+    a->reroot_out_dev = dalloc<RerootOut>(sp, 1);
     a->hlines.resize(R * M0_AN_MAX_LINES);
     a->hnlines.resize(R);
     a->hvalues.resize(R);
@@ -208,12 +270,12 @@ m0_selfplay* m0_analysis_create_ext(const m0_selfplay_cfg* cfg, const m0_analysi
     return analysis_create_impl(nullptr, cfg, opts);
 }
 
-int m0_analysis_submit(m0_selfplay* sp, const char* fen, const char* const* ucis, int n_moves, int sims, int64_t id) {
-    M0_ENGINE_CALL(sp, "m0_analysis_submit", KIND_ANALYSIS, true);
-    if (!fen || sims < 0 || n_moves < 0 || (n_moves > 0 && !ucis)) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
+// m0_analysis_submit / _submit_keep behind the call guard
+static int submit_impl(m0_selfplay* sp, const char* fen, const char* const* ucis, int n_moves, int sims, int64_t id, bool keep) {
+    if (!fen || sims < (keep ? 1 : 0) || n_moves < 0 || (n_moves > 0 && !ucis)) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
     if (sims == 0 && !sp->net) { m0_set_error("policy mode (sims = 0) needs an engine with a network"); return M0_ERR_UNSUPPORTED; }
     AnalysisJob job;
-    job.sims = sims; job.id = id;
+    job.sims = sims; job.id = id; job.keep = keep;
     if (parse_fen(fen, job.line.pos) != 0) { m0_set_error("bad FEN"); return M0_ERR_INVALID; }
     Move legal[M0_MAX_MOVES];
     int n = 0;
@@ -226,6 +288,11 @@ int m0_analysis_submit(m0_selfplay* sp, const char* fen, const char* const* ucis
     job.nlegal = gen_legal(job.line.pos, legal);
     queue_job(sp, std::move(job));
     return M0_OK;
+}
+
+int m0_analysis_submit(m0_selfplay* sp, const char* fen, const char* const* ucis, int n_moves, int sims, int64_t id) {
+    M0_ENGINE_CALL(sp, "m0_analysis_submit", KIND_ANALYSIS, true);
+    return submit_impl(sp, fen, ucis, n_moves, sims, id, false);
 }
 
 int m0_analysis_submit_planes(m0_selfplay* sp, const float* planes, const uint8_t* mask, int n, int sims, const int64_t* ids,
@@ -284,6 +351,7 @@ int m0_analysis_step(m0_selfplay* sp, int steps) {
     if (sp->ext_pending) { m0_set_error("m0_analysis_ext_expand outstanding"); return M0_ERR_STATE; }
     for (int i = 0; i < steps && pending_count(sp) > 0; ++i) {
         int rc = policy_pass(sp);
+        if (rc == M0_OK && blocked_by_held(sp)) return M0_ERR_STATE;
         if (rc == M0_OK) rc = refill(sp);
         if (rc == M0_OK && searches_pending(sp) > 0) rc = one_step(sp);      // the pass and the harvest
         if (rc != M0_OK) return rc;
@@ -294,6 +362,7 @@ int m0_analysis_step(m0_selfplay* sp, int steps) {
 int m0_analysis_ext_select(m0_selfplay* sp, int* rows, float* planes, int max_rows) {
     M0_ENGINE_CALL(sp, "m0_analysis_ext_select", KIND_ANALYSIS, true);
     if (!rows) { m0_set_error("null argument"); return M0_ERR_INVALID; }
+    if (!sp->ext_pending && blocked_by_held(sp)) return M0_ERR_STATE;
     return ext_select_impl(sp, rows, nullptr, planes, nullptr, max_rows);
 }
 
@@ -334,5 +403,121 @@ int m0_analysis_pending(m0_selfplay* sp) {
 }
 
 size_t m0_analysis_result_size(void) { return sizeof(m0_analysis_result); }
+
+// ---- live searches (include/m0_analysis_live.h)
+int m0_analysis_submit_keep(m0_selfplay* sp, const char* fen, const char* const* ucis, int n_moves, int sims, int64_t id) {
+    M0_ENGINE_CALL(sp, "m0_analysis_submit_keep", KIND_ANALYSIS, true);
+    if (!live_call_ok(sp, "m0_analysis_submit_keep")) return M0_ERR_STATE;
+    return submit_impl(sp, fen, ucis, n_moves, sims, id, true);
+}
+
+int m0_analysis_peek(m0_selfplay* sp, int64_t id, m0_analysis_result* out) {
+    M0_ENGINE_CALL(sp, "m0_analysis_peek", KIND_ANALYSIS, true);
+    if (!live_call_ok(sp, "m0_analysis_peek")) return M0_ERR_STATE;
+    if (!out) { m0_set_error("null argument"); return M0_ERR_INVALID; }
+    Analysis& a = *sp->an;
+    const int s = slot_of(sp, id, false);
+    if (s < 0) {
+        if (queued(a.queue, id) != a.queue.end()) return 0;
+        m0_set_error("m0_analysis_peek: no search with this id is queued or running");
+        return M0_ERR_INVALID;
+    }
+    m0_analysis_result r;
+    const int rc = live_result(sp, s, r);
+    if (rc != M0_OK) return rc;
+    *out = r;
+    return 1;
+}
+
+int m0_analysis_stop(m0_selfplay* sp, int64_t id) {
+    M0_ENGINE_CALL(sp, "m0_analysis_stop", KIND_ANALYSIS, true);
+    if (!live_call_ok(sp, "m0_analysis_stop")) return M0_ERR_STATE;
+    Analysis& a = *sp->an;
+    const int s = slot_of(sp, id, false);
+    if (s < 0) {
+        auto it = queued(a.queue, id);
+        if (it == a.queue.end()) { m0_set_error("m0_analysis_stop: no search with this id is queued or running"); return M0_ERR_INVALID; }
+        m0_analysis_result r = blank_result(*it);      // never searched: no slot, nothing held
+        r.sims = 0;
+        a.queue.erase(it);
+        answer(a, r);
+        return M0_OK;
+    }
+    m0_analysis_result r;
+    const int rc = live_result(sp, s, r);
+    if (rc != M0_OK) return rc;
+    if (r.overflow) sp->stats.arena_overflows++;
+    answer(a, r);
+    sp->hg[s].active = 0; sp->hg[s].finished = 0;
+    leave_slot(sp, s);
+    sync_games_h2d(sp);
+    return M0_HIP(sp->hip, hipStreamSynchronize(sp->stream)) ? M0_OK : m0_hip_error(sp->hip, "stopping a search failed");
+}
+
+int m0_analysis_continue(m0_selfplay* sp, int64_t held_id, const char* const* ucis, int n_moves, int sims, int64_t id, int keep,
+                         int32_t* reused_n) {
+    M0_ENGINE_CALL(sp, "m0_analysis_continue", KIND_ANALYSIS, true);
+    if (!live_call_ok(sp, "m0_analysis_continue")) return M0_ERR_STATE;
+    if (sims < 1 || n_moves < 0 || n_moves > M0_REROOT_MAX_MOVES || (n_moves > 0 && !ucis)) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
+    Analysis& a = *sp->an;
+    const int s = slot_of(sp, held_id, true);
+    if (s < 0) { m0_set_error("m0_analysis_continue: this id is not held"); return M0_ERR_INVALID; }
+    AnalysisJob job;
+    job.line = static_cast<const Line&>(sp->games[s]);
+    job.sims = sims; job.id = id; job.keep = keep != 0;
+    int in[2 + M0_REROOT_MAX_MOVES] = {s, n_moves};
+    Move legal[M0_MAX_MOVES];
+    int n = 0;
+    for (int i = 0; i < n_moves; ++i) {
+        const Move m = ucis[i] ? parse_uci(ucis[i]) : (Move)0xFFFF;
+        if (!job.line.play_if_legal(m, legal, n)) {
+            m0_set_error(std::string("Illegal move: ") + (ucis[i] ? ucis[i] : "(null)"));
+            return M0_ERR_INVALID;
+        }
+        in[2 + i] = (int)m;
+    }
+    job.nlegal = gen_legal(job.line.pos, legal);
+    if (reused_n) *reused_n = 0;
+    a.held[s] = 0; sp->games[s].in_use = false;        // held_id is held no longer, whatever follows
+    // a final position that needs no search: answered as m0_analysis_submit answers it, the slot is free
+    if (answered_on_host(sp, job)) return M0_OK;
+    // the tree: follow the moves on the device and keep what is behind them
+    HipStatus& hs = sp->hip;
+    RerootOut out = {0, 0, 0.0};
+    M0_HIP(hs, hipMemcpyAsync(a.reroot_in_dev, in, sizeof(in), hipMemcpyHostToDevice, sp->stream));
+    M0_HIP(hs, launch_reroot_moves(sp->d, a.reroot_in_dev, a.reroot_in_dev + 1, a.reroot_in_dev + 2, 1, a.reroot_out_dev, sp->stream));
+    M0_HIP(hs, hipMemcpyAsync(&out, a.reroot_out_dev, sizeof(out), hipMemcpyDeviceToHost, sp->stream));
+    if (!sync_games_d2h(sp)) return m0_hip_error(hs, "re-rooting the held tree failed");    // root / arena / next as the kernel left them
+    const bool kept = out.kept != 0;
+    occupy_slot(sp, s, std::move(job.line), (int)id);
+    a.slot_job[s] = AnalysisJob{Line(), sims, job.nlegal, id, job.keep};
+    GameDev& g = sp->hg[s];
+    g.net_id = 0;
+    arm_slot_search(sp, s, sims, a.opts.dirichlet != 0, !kept);
+    g.reinfer = kept ? 1 : 0;                          // a kept root: its value once more, as MCTS.run on a root found again
+    g.root_n = kept ? out.n : 0; g.root_q = kept ? out.q : 0.0; g.root_v = 0.0;
+    sync_games_h2d(sp);
+    if (!M0_HIP(hs, hipStreamSynchronize(sp->stream))) return m0_hip_error(hs, "re-rooting the held tree failed");
+    if (reused_n) *reused_n = kept ? out.n : 0;
+    return M0_OK;
+}
+
+int m0_analysis_release(m0_selfplay* sp, int64_t held_id) {
+    M0_ENGINE_CALL(sp, "m0_analysis_release", KIND_ANALYSIS, true);
+    if (!live_call_ok(sp, "m0_analysis_release")) return M0_ERR_STATE;
+    const int s = slot_of(sp, held_id, true);
+    if (s < 0) { m0_set_error("m0_analysis_release: this id is not held"); return M0_ERR_INVALID; }
+    sp->an->held[s] = 0;
+    sp->games[s].in_use = false;
+    return M0_OK;
+}
+
+int m0_analysis_held(m0_selfplay* sp) {
+    M0_ENGINE_CALL(sp, "m0_analysis_held", KIND_ANALYSIS, true);
+    if (!live_call_ok(sp, "m0_analysis_held")) return M0_ERR_STATE;
+    int n = 0;
+    for (int s = 0; s < sp->G; ++s) n += sp->games[s].in_use && sp->an->held[s] ? 1 : 0;
+    return n;
+}
 
 }  // extern "C"

@@ -73,9 +73,13 @@ HostGame& occupy_slot(m0_selfplay* sp, int slot, Line&& line, int uid) {
     return hgm;
 }
 
-void begin_search(m0_selfplay* sp, int slot, int sims, bool dirichlet, int root) {
+void arm_slot_search(m0_selfplay* sp, int slot, int sims, bool dirichlet, bool fresh) {
     const HostGame& hgm = sp->games[slot];
-    arm_search(sp, slot, hgm.pos, hgm.win, sims, dirichlet, root < 0);
+    arm_search(sp, slot, hgm.pos, hgm.win, sims, dirichlet, fresh);
+}
+
+void begin_search(m0_selfplay* sp, int slot, int sims, bool dirichlet, int root) {
+    arm_slot_search(sp, slot, sims, dirichlet, root < 0);
     sp->adv.push(slot, root);
 }
 

@@ -68,7 +68,7 @@ struct AdvanceList {
 
 // What an analysis engine (capi_analysis.hip) keeps beside the tree slots.  A slot that searches holds its position and
 // repetition window in m0_selfplay::games[slot] (in_use) and its search in hg[slot], as a game does.
-struct AnalysisJob { Line line; int sims; int nlegal; int64_t id; };
+struct AnalysisJob { Line line; int sims; int nlegal; int64_t id; bool keep = false; };   // keep: m0_analysis_submit_keep / _continue
 struct Analysis {
     m0_analysis_opts opts;
     std::deque<AnalysisJob> queue;         // submitted searches that wait for a slot
@@ -76,6 +76,11 @@ struct Analysis {
     std::deque<m0_analysis_result> done;   // answered, not yet polled
     std::deque<std::vector<int32_t>> done_children;   // beside `done`: the root children of each (answer(), capi_analysis.hip)
     std::vector<AnalysisJob> slot_job;     // per slot: what it searches (the Line lives in games[slot])
+    // A HELD slot (include/m0_analysis_live.h): its search was answered (finished or stopped) and its tree stays for
+    // m0_analysis_continue: games[slot].in_use, hg[slot].active == 0, held[slot]; slot_job[slot].id is the held id.
+    std::vector<uint8_t> held;
+    int* reroot_in_dev = nullptr;          // m0_analysis_continue: [slot, n_moves, moves x M0_REROOT_MAX_MOVES]
+    RerootOut* reroot_out_dev = nullptr;
     std::vector<int> finished;             // scratch: slots harvested by this step
     std::vector<m0_analysis_line> hlines;  // host copies of the result kernels' output
     std::vector<int> hnlines;
@@ -202,6 +207,8 @@ bool sync_games_h2d(m0_selfplay* sp);           // ... sp->hg -> device, on the 
 HostGame& occupy_slot(m0_selfplay* sp, int slot, Line&& line, int uid);
 // Arm a search of the slot's position (MCTS.run prologue) and queue its root (a child of the old root or a RootMode) in sp->adv.
 void begin_search(m0_selfplay* sp, int slot, int sims, bool dirichlet, int root);
+// ... the arming alone, for a root that is already in place on the device (`fresh`: a brand-new node, not a reused one)
+void arm_slot_search(m0_selfplay* sp, int slot, int sims, bool dirichlet, bool fresh);
 int apply_advances(m0_selfplay* sp);            // control blocks -> device, advance_kernel over sp->adv, which is empty afterwards
 int run_select(m0_selfplay* sp, int* rows_out);
 int refill(m0_selfplay* sp);                    // before select: the first games (lazily, at the first step) / queued analyses

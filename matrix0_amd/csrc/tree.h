@@ -181,6 +181,14 @@ enum RootMode : int {
     ROOT_FIRST_OF_GAME = -3,    // the first search of a game: both tables are cleared first, then a new root
 };
 hipError_t launch_advance(const TreeDev& d, const int* game_ids_dev, const int* child_slots_dev, int count, hipStream_t st);
+// Re-root by moves (tree_reroot.hip).  Entry j: slot slots_dev[j] follows the nmoves_dev[j] <= M0_REROOT_MAX_MOVES moves
+// moves_dev[j][0..] (from | to<<6 | promo<<12, as a node's `mv`) from its root through expanded children and keeps the subtree
+// of the node it reaches, compacted into the other arena half; where the walk fails the slot gets a fresh root, as ROOT_FRESH.
+// out_dev[j]: kept 0/1 and, when kept, the visit count and q of the new root.  The slots must not be searching.
+#define M0_REROOT_MAX_MOVES 8
+struct RerootOut { int32_t kept, n; double q; };
+hipError_t launch_reroot_moves(const TreeDev& d, const int* slots_dev, const int* nmoves_dev, const int* moves_dev /*[count][8]*/,
+                               int count, RerootOut* out_dev, hipStream_t st);
 
 // test hooks: position-wise encode / legal move / index kernels (encoding.py on device)
 hipError_t launch_encode_positions(const m0::Pos* pos_dev, int n, float* planes_f32_dev /*[n][M0_PLANES][64]*/,

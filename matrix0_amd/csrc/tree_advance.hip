@@ -1,6 +1,6 @@
 // advance_kernel: re-root a game's tree on the played move, one wavefront per game.
-//   child_slot >= 0       keep that child's subtree, compacted breadth-first into the other arena half
-//   ROOT_FRESH            fresh tree (and an empty position table)
+//   child_slot >= 0       keep that child's subtree, compacted breadth-first into the other arena half (tree_device.h)
+//   ROOT_FRESH            fresh tree (and an empty position table; tree_device.h)
 //   ROOT_FROM_SIDE_TABLE  and below (RootMode, tree.h): match engine with per-side tables (tt_sides == 2), the root is looked
 //                         up in the side's table
 // and, before any of these, the slot's evaluation caches are emptied when the host flagged a new game (GameDev::ec_clear).
@@ -41,46 +41,6 @@ __device__ __forceinline__ void reroot_from_table(const TreeDev& d, GameDev* gd,
     }
 }
 
-__device__ __forceinline__ void reroot_fresh(const TreeDev& d, GameDev* gd, int g, int lane) {
-    const Arena D = arena_of(d.t, g, 0);
-    // a fresh root starts with an empty position table
-    if (d.tt_keys) tt_clear(d.tt_keys + (size_t)g * d.tt_sides * d.tt_cap, d.tt_sides * d.tt_cap, lane);
-    if (lane == 0) {
-        node_reset(D, 0, 0.0, 0, 0);
-        gd->arena = 0; gd->root = 0; gd->next = 1; gd->overflow = 0;
-    }
-}
-
-// The subtree of the root's child `slot` -> the other arena half, breadth-first: node 0 is the new root, then its children,
-// their children ... (select_kernel's LDS copy of the tree top relies on this order).
-__device__ __forceinline__ void reroot_keep_subtree(const TreeDev& d, GameDev* gd, int g, int slot, int lane) {
-    const int a = gd->arena;
-    const Arena Sx = arena_of(d.t, g, a), D = arena_of(d.t, g, a ^ 1);
-    const int r = Sx.cbase[gd->root] + slot;
-    if (lane == 0) node_copy(D, 0, Sx, r);
-    __syncthreads();
-    int head = 0, tail = 1;
-    while (head < tail) {
-        const int lim = tail < head + 64 ? tail : head + 64;
-        const int i = head + lane;
-        const int nc_i = i < lim ? (int)D.nch[i] : -1;
-        const int cb_i = i < lim ? D.cbase[i] : -1;     // still the OLD child base
-        unsigned long long mask = __ballot(nc_i > 0);
-        while (mask) {
-            const int b = __builtin_ctzll(mask);
-            mask &= mask - 1;
-            const int nc = __shfl(nc_i, b), ocb = __shfl(cb_i, b);
-            const int ncb = tail;
-            for (int k = lane; k < nc; k += 64) node_copy(D, ncb + k, Sx, ocb + k);
-            if (lane == 0) D.cbase[head + b] = ncb;
-            tail += nc;
-        }
-        __syncthreads();
-        head = lim;
-    }
-    if (lane == 0) { gd->arena = a ^ 1; gd->root = 0; gd->next = tail; gd->overflow = 0; }
-}
-
 __global__ __launch_bounds__(64) void advance_kernel(TreeDev d, const int* game_ids, const int* child_slots, int count) {
     const int j = blockIdx.x, lane = threadIdx.x;
     if (j >= count) return;
@@ -95,7 +55,7 @@ __global__ __launch_bounds__(64) void advance_kernel(TreeDev d, const int* game_
     }
     if (slot <= ROOT_FROM_SIDE_TABLE) reroot_from_table(d, gd, g, slot, lane);
     else if (slot < 0) reroot_fresh(d, gd, g, lane);
-    else reroot_keep_subtree(d, gd, g, slot, lane);
+    else reroot_keep_subtree(d, gd, g, arena_of(d.t, g, gd->arena).cbase[gd->root] + slot, lane);
 }
 
 hipError_t launch_advance(const TreeDev& d, const int* game_ids_dev, const int* child_slots_dev, int count, hipStream_t st) {

@@ -1,6 +1,6 @@
-// Device code shared by the tree kernels (tree_select.hip, tree_expand.hip, tree_advance.hip): the counter RNG, the arena
-// view of one game's node arrays, node reset / copy, wave reductions, the backup, the position table of the tt_merge mode,
-// batch-row reservation and the root value.  For the tree .hip units only (it opens namespace m0).  One wavefront per game
+// Device code shared by the tree kernels (tree_select.hip, tree_expand.hip, tree_advance.hip, tree_reroot.hip): the counter
+// RNG, the arena view of one game's node arrays, node reset / copy, wave reductions, the backup, the position table of the
+// tt_merge mode, batch-row reservation, the root value and the two ways a slot gets a new root (fresh, kept subtree).  For the tree .hip units only (it opens namespace m0).  One wavefront per game
 // tree: "whole-wave" functions are called by all 64 lanes.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -201,4 +201,44 @@ static __device__ void backprop(const Arena& A, const int* path, int depth, doub
         A.n[nd] = nn; A.w[nd] = ww; A.q[nd] = qq;
         mirror(nd, nn, qq);
     }
+}
+
+// ---- a new root for a slot (advance_kernel, reroot_moves_kernel); whole-wave, one wave per block
+__device__ __forceinline__ void reroot_fresh(const TreeDev& d, GameDev* gd, int g, int lane) {
+    const Arena D = arena_of(d.t, g, 0);
+    // a fresh root starts with an empty position table
+    if (d.tt_keys) tt_clear(d.tt_keys + (size_t)g * d.tt_sides * d.tt_cap, d.tt_sides * d.tt_cap, lane);
+    if (lane == 0) {
+        node_reset(D, 0, 0.0, 0, 0);
+        gd->arena = 0; gd->root = 0; gd->next = 1; gd->overflow = 0;
+    }
+}
+
+// The subtree of node `r` of the slot's current half -> the other arena half, breadth-first: node 0 is the new root, then its
+// children, their children ... (select_kernel's LDS copy of the tree top relies on this order).
+__device__ __forceinline__ void reroot_keep_subtree(const TreeDev& d, GameDev* gd, int g, int r, int lane) {
+    const int a = gd->arena;
+    const Arena Sx = arena_of(d.t, g, a), D = arena_of(d.t, g, a ^ 1);
+    if (lane == 0) node_copy(D, 0, Sx, r);
+    __syncthreads();
+    int head = 0, tail = 1;
+    while (head < tail) {
+        const int lim = tail < head + 64 ? tail : head + 64;
+        const int i = head + lane;
+        const int nc_i = i < lim ? (int)D.nch[i] : -1;
+        const int cb_i = i < lim ? D.cbase[i] : -1;     // still the OLD child base
+        unsigned long long mask = __ballot(nc_i > 0);
+        while (mask) {
+            const int b = __builtin_ctzll(mask);
+            mask &= mask - 1;
+            const int nc = __shfl(nc_i, b), ocb = __shfl(cb_i, b);
+            const int ncb = tail;
+            for (int k = lane; k < nc; k += 64) node_copy(D, ncb + k, Sx, ocb + k);
+            if (lane == 0) D.cbase[head + b] = ncb;
+            tail += nc;
+        }
+        __syncthreads();
+        head = lim;
+    }
+    if (lane == 0) { gd->arena = a ^ 1; gd->root = 0; gd->next = tail; gd->overflow = 0; }
 }

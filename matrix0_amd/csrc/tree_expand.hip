@@ -190,13 +190,15 @@ __device__ __forceinline__ int prune_children(const TreeCfg& c, const float (&pr
     return nkeep;
 }
 
-// The child block of `leaf`; false (and GameDev::overflow) if the arena half cannot take it.
+// The child block of `leaf`; false (and GameDev::overflow) if the arena half cannot take it.  q0: the q a new child starts
+// with (child_seed_q).
 // _register_children_in_tt (mcts.py:1330-1346): every child of an expanded NON-root node goes into the table
 // under the key of the position it leads to (run() registers only the fresh root itself, mcts.py:344-358)
 // A root that run() FOUND in the table and had to expand registers its children like any other node
 // (mcts.py:398-413): reg_children is false only for the brand-new root, which is registered itself instead.
 __device__ __forceinline__ bool write_children(const ExpandEnv& E, int leaf, const Pos& pos, const Move (&mvv)[CPL], const int (&idx)[CPL],
-                                               const float (&pr)[CPL], const int (&slot)[CPL], int n, int nkeep, bool reg_children) {
+                                               const float (&pr)[CPL], const int (&slot)[CPL], int n, int nkeep, bool reg_children,
+                                               double q0) {
     const Arena& A = E.A;
     GameDev* gd = E.gd;
     const int lane = E.lane;
@@ -208,6 +210,7 @@ __device__ __forceinline__ bool write_children(const ExpandEnv& E, int leaf, con
         if (i < n && slot[k] >= 0) {
             const int ci = cb + slot[k];
             node_reset(A, ci, (double)pr[k], mvv[k], (uint16_t)idx[k]);
+            if (q0 != 0.0) A.q[ci] = q0;
             if (E.TK && reg_children) {
                 Pos q = pos;
                 make_move(q, mvv[k]);
@@ -221,10 +224,21 @@ __device__ __forceinline__ bool write_children(const ExpandEnv& E, int leaf, con
     return true;
 }
 
+// Node._expand gives a new child q = -parent.q, the q of the PARENT OF THE EXPANDED NODE as it stands then, unless that is 0 or
+// the node has no parent (mcts.py:221-222).  No search reads it -- a child without visits is scored with the FPU value, the first
+// backup overwrites it -- but it is the q such a child reports (a line without visits, a root child of a kept subtree).  The
+// parent is the node before the leaf on the sample's path; the root has none.  The table modes keep 0: there the node's
+// creation parent need not be on the path.
+__device__ __forceinline__ double child_seed_q(const TreeCfg& c, const Arena& A, const int* path, int depth) {
+    if (c.tt_merge || depth < 1) return 0.0;
+    const double pq = A.q[path[depth - 1]];
+    return pq != 0.0 ? -pq : 0.0;
+}
+
 // Node._expand (mcts.py:135-225) for one leaf: priors -> prune -> child block; returns false if the arena is exhausted.
 // The legal moves of the leaf come from select (same position, same order): no second move generation.
 __device__ __forceinline__ bool expand_node(const ExpandEnv& E, const TreeCfg& c, int leaf, const Pos& pos, const uint16_t* smoves, int n,
-                                   const LeafLogits& src, bool is_root, bool reg_children) {
+                                   const LeafLogits& src, bool is_root, bool reg_children, double q0) {
     const int lane = E.lane;
     if (n <= 0) return true;
     // non-finite logits anywhere -> uniform priors (mcts.py:147-149)
@@ -250,13 +264,13 @@ __device__ __forceinline__ bool expand_node(const ExpandEnv& E, const TreeCfg& c
     }
     int slot[CPL];
     const int nkeep = prune_children(c, pr, n, lane, E.X, slot);
-    return write_children(E, leaf, pos, mvv, idx, pr, slot, n, nkeep, reg_children);
+    return write_children(E, leaf, pos, mvv, idx, pr, slot, n, nkeep, reg_children, q0);
 }
 
 // A leaf with a batch row of its own (SK_EVAL, or the unexpanded root SK_ROOT_INIT): expand it from the row's logits; a cacheable
 // leaf (SK_EVAL with a key set by select) also puts its evaluation into the cache.
 __device__ __forceinline__ void expand_evaluated(const TreeDev& d, const TreeCfg& c, const ExpandEnv& E, int g, const Sample& smp,
-                                                 const uint16_t* moves, const float* lg, float v) {
+                                                 const uint16_t* moves, const float* lg, float v, double q0) {
     const Arena& A = E.A;
     GameDev* gd = E.gd;
     const int lane = E.lane, kind = smp.kind, leaf = smp.leaf;
@@ -270,7 +284,7 @@ __device__ __forceinline__ void expand_evaluated(const TreeDev& d, const TreeCfg
         ec_invalidate(d.ec, ce, lane);                  // invalid while it is being rewritten
     }
     const bool ok = expand_node(E, c, leaf, pos, moves, smp.nlegal, logits_of_row(lg, cw), kind == SK_ROOT_INIT,
-                                !(kind == SK_ROOT_INIT && gd->root_fresh));
+                                !(kind == SK_ROOT_INIT && gd->root_fresh), q0);
     // an expansion that did not happen (node arena exhausted) must not leave the pending-row mark behind
     if (c.eval_cache && kind == SK_EVAL && lane == 0 && A.nch[leaf] < 0) A.cbase[leaf] = -1;
     const int sig = cw ? legal_sig(moves, smp.nlegal, lane) : 0;
@@ -335,7 +349,7 @@ __global__ __launch_bounds__(64) void expand_kernel(TreeDev d, TreeCfg c) {
             const float v = pay[EC_VALUE];
             if (A.nch[leaf] < 0) {
                 const Pos pos = S[s].pos;
-                expand_node(E, c, leaf, pos, moves, S[s].nlegal, logits_of_cache(pay), false, true);
+                expand_node(E, c, leaf, pos, moves, S[s].nlegal, logits_of_cache(pay), false, true, child_seed_q(c, A, path, depth));
             }
             backprop(A, path, depth, (double)v, lane, may_repeat, NoMirror{});
             ++sims; ++hits;
@@ -344,7 +358,7 @@ __global__ __launch_bounds__(64) void expand_kernel(TreeDev d, TreeCfg c) {
             const int leaf = S[s].leaf, depth = S[s].depth, row = S[s].row;
             const float* lg = d.logits + (size_t)row * M0_POLICY_SIZE;
             const float v = d.values[row];
-            if (A.nch[leaf] < 0) expand_evaluated(d, c, E, g, S[s], moves, lg, v);
+            if (A.nch[leaf] < 0) expand_evaluated(d, c, E, g, S[s], moves, lg, v, child_seed_q(c, A, path, depth));
             ++evals;
             if (kind == SK_EVAL) {
                 backprop(A, path, depth, (double)v, lane, may_repeat, NoMirror{});

@@ -479,10 +479,48 @@ class AnalysisEngine(SelfplayEngine):
         else:                                                  # AnalysisExtEngine
             self._open(None, cfg, "m0_analysis_create_ext", C.byref(cfg), C.byref(self.opts))
 
-    def submit(self, fen: str, ucis=(), sims: int = 0, id: int = 0) -> None:
+    def submit(self, fen: str, ucis=(), sims: int = 0, id: int = 0, keep: bool = False) -> None:
+        """keep=True (sims > 0): the search's tree stays in its slot when it is answered, held under `id`, for
+        `continue_search` / `release`."""
         ucis = list(ucis)
+        if keep:
+            _lib.check(self._L.m0_analysis_submit_keep(self._h, fen.encode(), _lib.cstrings(ucis), len(ucis), int(sims), int(id)),
+                       "m0_analysis_submit_keep")
+            return
         _lib.check(self._L.m0_analysis_submit(self._h, fen.encode(), _lib.cstrings(ucis), len(ucis), int(sims), int(id)),
                    "m0_analysis_submit")
+
+    # ---- live searches (include/m0_analysis_live.h)
+    def peek_raw(self, id: int) -> Optional[AnalysisResult]:
+        r = AnalysisResult()
+        rc = _lib.count(self._L.m0_analysis_peek(self._h, int(id), C.byref(r)), "m0_analysis_peek")
+        return r if rc == 1 else None
+
+    def peek(self, id: int) -> Optional[dict]:
+        """The result of the running search `id` as it stands (`sims`: simulations done so far), None while it is queued.
+        Reads only."""
+        r = self.peek_raw(id)
+        return None if r is None else analysis_result_to_dict(r)
+
+    def stop(self, id: int) -> None:
+        """Answer the search `id` now (its result, equal to a peek, comes through `poll`); a queued one is answered with zeros."""
+        _lib.check(self._L.m0_analysis_stop(self._h, int(id)), "m0_analysis_stop")
+
+    def continue_search(self, held_id: int, ucis=(), sims: int = 1, id: int = 0, keep: bool = False) -> int:
+        """Search the position of the held search `held_id` plus the moves `ucis` (at most 8) in its slot, under `id`: the
+        subtree behind the moves is kept.  Returns the visits the kept root carries, 0 when a fresh tree had to be started
+        (or the position was answered without a search)."""
+        ucis = list(ucis)
+        reused = C.c_int32(0)
+        _lib.check(self._L.m0_analysis_continue(self._h, int(held_id), _lib.cstrings(ucis), len(ucis), int(sims), int(id),
+                                                int(bool(keep)), C.byref(reused)), "m0_analysis_continue")
+        return int(reused.value)
+
+    def release(self, id: int) -> None:
+        _lib.check(self._L.m0_analysis_release(self._h, int(id)), "m0_analysis_release")
+
+    def held(self) -> int:
+        return _lib.count(self._L.m0_analysis_held(self._h), "m0_analysis_held")
 
     def step(self, steps: int = 1) -> None:
         _lib.check(self._L.m0_analysis_step(self._h, int(steps)), "m0_analysis_step")
