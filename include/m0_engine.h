@@ -96,6 +96,17 @@ int m0_net_finalize(m0_net* net);
  * Re-entrant: calls on one net are serialised internally (several MCTS objects may share a backend,
  * tests/test_stress.py:221-266).  NaN/Inf in the outputs -> M0_ERR_NONFINITE. */
 int m0_net_infer(m0_net* net, const float* planes, int B, float* policy, float* value, float* ssl);
+/* Trunk tap (per-layer parity tests; not used by the engines).  Steps of a forward in execution order: 0 = stem (+ positional
+ * encoding), 1 = piece-square conv, 2 = interaction conv, 3 + i = tower layer i (residual and attention blocks as the tower
+ * lists them).  *steps = their number, *width = the trunk's width in memory (320 for a 288-channel network). */
+int m0_net_tap_info(const m0_net* net, int* steps, int* width);
+/* m0_net_infer with the tap armed at `step`: besides policy, value and ssl (nullable), `stream` receives the residual stream
+ * right after that step and `second` the pre-activated input of the next residual block, act(GroupNorm(stream; its bn1)), when
+ * the step wrote one (*has_second = 1; else 0 and `second` is zeroed): both f32 [B][64][width], the kernels' fp16 values
+ * widened exactly.  A step the configuration does not have, or an attention layer the inference stride skips, returns the
+ * stream of the step before it and no second output.  The tap is off again when the call returns. */
+int m0_net_infer_tap(m0_net* net, const float* planes, int B, int step, float* policy, float* value, float* ssl,
+                     float* stream, float* second, int* has_second);
 int m0_net_ssl_channels(const m0_net* net);
 int64_t m0_net_param_count(const m0_net* net);
 double m0_net_flops_per_position(const m0_net* net, int with_ssl);

@@ -121,6 +121,8 @@ FUNCTIONS = {
     "m0_net_load_weight": (i32, [vp, cstr, vp, i32, P(i64), i32]),
     "m0_net_finalize": (i32, [vp]),
     "m0_net_infer": (i32, [vp, vp, i32, vp, vp, vp]),
+    "m0_net_tap_info": (i32, [vp, _pi32, _pi32]),
+    "m0_net_infer_tap": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, _pi32]),
     "m0_net_ssl_channels": (i32, [vp]),
     "m0_net_param_count": (i64, [vp]),
     "m0_net_flops_per_position": (f64, [vp, i32]),

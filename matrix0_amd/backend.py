@@ -78,7 +78,19 @@ class M0Backend:
         """(policy, value, {task: f32 [B,ch,8,8]}) -- forward(return_ssl=True), resnet.py:738-745."""
         return self._infer(arr, True)
 
-    def _infer(self, arr: np.ndarray, want_ssl: bool):
+    def tap_info(self) -> Tuple[int, int]:
+        """(steps of a forward the trunk tap can be armed at, trunk width in memory) -- m0_net_tap_info."""
+        steps, width = C.c_int(0), C.c_int(0)
+        _lib.check(self._L.m0_net_tap_info(self._h, C.byref(steps), C.byref(width)), "m0_net_tap_info")
+        return steps.value, width.value
+
+    def infer_tap(self, arr: np.ndarray, step: int):
+        """infer_np_ssl with the trunk tap armed at `step` (m0_net_infer_tap): (policy, value, ssl, stream, second), the last
+        two f32 [B,64,width]: the residual stream after that step and the next residual block's pre-activated input, or None
+        where the step wrote none."""
+        return self._infer(arr, True, int(step))
+
+    def _infer(self, arr: np.ndarray, want_ssl: bool, tap_step: Optional[int] = None):
         if not self._finalized:
             raise RuntimeError("weights not loaded")
         a = np.asarray(arr)
@@ -92,7 +104,15 @@ class M0Backend:
         val = np.empty((B,), dtype=np.float32)
         sslc = self._L.m0_net_ssl_channels(self._h)
         ssl = np.empty((B, sslc, 8, 8), dtype=np.float32) if (want_ssl and sslc > 0) else None
-        _lib.check(self._L.m0_net_infer(self._h, _lib.ptr(a), B, _lib.ptr(pol), _lib.ptr(val), _lib.ptr(ssl)), "m0_net_infer")
+        if tap_step is None:
+            _lib.check(self._L.m0_net_infer(self._h, _lib.ptr(a), B, _lib.ptr(pol), _lib.ptr(val), _lib.ptr(ssl)), "m0_net_infer")
+        else:
+            width = self.tap_info()[1]
+            stream = np.empty((B, 64, width), dtype=np.float32)
+            second = np.empty((B, 64, width), dtype=np.float32)
+            has_second = C.c_int(0)
+            _lib.check(self._L.m0_net_infer_tap(self._h, _lib.ptr(a), B, tap_step, _lib.ptr(pol), _lib.ptr(val), _lib.ptr(ssl),
+                                                _lib.ptr(stream), _lib.ptr(second), C.byref(has_second)), "m0_net_infer_tap")
         out = None
         if ssl is not None:
             out, off = {}, 0
@@ -100,6 +120,8 @@ class M0Backend:
                 n = _lib.SSL_CH[t]
                 out[t] = ssl[:, off:off + n]
                 off += n
+        if tap_step is not None:
+            return pol, val, out, stream, (second if has_second.value else None)
         return pol, val, out
 
     # ---- measurement helpers ----------------------------------------------------------------

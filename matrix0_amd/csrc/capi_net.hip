@@ -133,10 +133,10 @@ static int ensure_io(m0_net* n, int B) {
     return M0_OK;
 }
 
-int m0_net_infer(m0_net* n, const float* planes, int B, float* policy, float* value, float* ssl) {
-    if (!n || !planes || !policy || !value) { m0_set_error("null argument"); return M0_ERR_INVALID; }
-    if (B <= 0) { m0_set_error("batch must be positive"); return M0_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(n->mu);
+// The host-facing forward, under the network's lock.  tap_stream / tap_second (both or neither): the trunk tap's two buffers
+// after the forward, fp16 [B][64][width] widened to f32; the caller has armed the tap.
+static int infer_locked(m0_net* n, const float* planes, int B, float* policy, float* value, float* ssl,
+                        float* tap_stream = nullptr, float* tap_second = nullptr, int* has_second = nullptr) {
     HipStatus& hs = n->net->hip();
     if (!M0_HIP(hs, hipSetDevice(n->device))) return m0_hip_error(hs);       // also a network that has failed before
     int rc = ensure_io(n, B);
@@ -152,13 +152,57 @@ int m0_net_infer(m0_net* n, const float* planes, int B, float* policy, float* va
     M0_HIP(hs, hipMemcpyAsync(policy, n->logits_dev, (size_t)B * M0_POLICY_SIZE * 4, hipMemcpyDeviceToHost, n->stream));
     M0_HIP(hs, hipMemcpyAsync(value, n->value_dev, (size_t)B * 4, hipMemcpyDeviceToHost, n->stream));
     if (ssl) M0_HIP(hs, hipMemcpyAsync(ssl, n->ssl_dev, (size_t)B * sslc * 64 * 4, hipMemcpyDeviceToHost, n->stream));
+    std::vector<_Float16> th, ta;
+    const size_t tn = tap_stream ? (size_t)B * 64 * n->net->trunk_width() : 0;
+    if (tap_stream) {
+        th.resize(tn);
+        M0_HIP(hs, hipMemcpyAsync(th.data(), n->net->tap_stream(), tn * 2, hipMemcpyDeviceToHost, n->stream));
+        if (n->net->tap_has_second()) {
+            ta.resize(tn);
+            M0_HIP(hs, hipMemcpyAsync(ta.data(), n->net->tap_second(), tn * 2, hipMemcpyDeviceToHost, n->stream));
+        }
+    }
     if (!M0_HIP(hs, hipStreamSynchronize(n->stream))) return m0_hip_error(hs, "forward failed");
+    if (tap_stream) {
+        for (size_t i = 0; i < tn; ++i) tap_stream[i] = (float)th[i];
+        for (size_t i = 0; i < tn; ++i) tap_second[i] = ta.empty() ? 0.f : (float)ta[i];
+        *has_second = ta.empty() ? 0 : 1;
+    }
     // NaN/Inf must surface as errors (mcts.py:1165-1177, tests/test_error_handling.py:23-53)
     for (size_t i = 0, nn = (size_t)B * M0_POLICY_SIZE; i < nn; ++i)
         if (!isfinite(policy[i])) { m0_set_error("network produced non-finite policy logits"); return M0_ERR_NONFINITE; }
     for (int i = 0; i < B; ++i)
         if (!isfinite(value[i])) { m0_set_error("network produced non-finite value"); return M0_ERR_NONFINITE; }
     return M0_OK;
+}
+
+int m0_net_infer(m0_net* n, const float* planes, int B, float* policy, float* value, float* ssl) {
+    if (!n || !planes || !policy || !value) { m0_set_error("null argument"); return M0_ERR_INVALID; }
+    if (B <= 0) { m0_set_error("batch must be positive"); return M0_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(n->mu);
+    return infer_locked(n, planes, B, policy, value, ssl);
+}
+
+int m0_net_tap_info(const m0_net* n, int* steps, int* width) {
+    if (!n || !steps || !width) { m0_set_error("null argument"); return M0_ERR_INVALID; }
+    *steps = n->net->tap_steps();
+    *width = n->net->trunk_width();
+    return M0_OK;
+}
+
+int m0_net_infer_tap(m0_net* n, const float* planes, int B, int step, float* policy, float* value, float* ssl, float* stream,
+                     float* second, int* has_second) {
+    if (!n || !planes || !policy || !value || !stream || !second || !has_second) {
+        m0_set_error("null argument");
+        return M0_ERR_INVALID;
+    }
+    if (B <= 0) { m0_set_error("batch must be positive"); return M0_ERR_INVALID; }
+    if (step < 0 || step >= n->net->tap_steps()) { m0_set_error("tap step out of range"); return M0_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(n->mu);
+    n->net->set_tap(step);
+    const int rc = infer_locked(n, planes, B, policy, value, ssl, stream, second, has_second);
+    n->net->set_tap(-1);
+    return rc;
 }
 
 int m0_net_ssl_channels(const m0_net* n) { return n ? n->net->ssl_channels_total() : 0; }

@@ -104,6 +104,17 @@ public:
     size_t param_count() const { return nparams_; }
     double flops_per_position(bool with_ssl) const;
     _Float16* input_nhwc() { return X0_; }   // engine-side encoders write here directly
+    // Trunk tap (the per-layer parity tests): after step `step` of the next forwards the residual stream that step wrote, and AA_
+    // when the step wrote it, are copied into buffers of this network, on the forward's stream.  Steps in execution order:
+    // 0 = stem (+ positional encoding), 1 = piece-square conv, 2 = interaction conv, 3 + i = tower layer i.  A step the
+    // configuration lacks, or a skipped attention layer, hands back the stream as the step before left it, without a second output.
+    // -1 (the default) = off: the forward issues nothing for it.
+    int tap_steps() const { return 3 + (int)tower_.size(); }
+    int trunk_width() const { return Cp_; }
+    void set_tap(int step) { tap_step_ = step; }
+    const _Float16* tap_stream() const { return TAPX_; }      // [B][64][trunk_width()], valid after a tapped forward
+    const _Float16* tap_second() const { return TAPA_; }
+    bool tap_has_second() const { return tap_second_; }
     // Dominant-kernel timing (roofline): when enabled every 3x3 C->C conv launch is bracketed by HIP events on
     // the launch stream; harvest after the stream has been synchronised.
     void set_profile(bool on) { profile_ = on; }
@@ -175,6 +186,10 @@ private:
              *F3_ = nullptr, *F4_ = nullptr, *SH_ = nullptr, *SH2_ = nullptr, *SO_ = nullptr;
     float* VAL_ = nullptr;
     float* SPK_ = nullptr;      // split-K partial tiles [8][Mfc][2C] f32 (value_fc1)
+    // trunk tap: sized like XA_, part of the workspace once a tap has been asked for (a shared_view starts without them)
+    int tap_step_ = -1;
+    bool tap_second_ = false;
+    _Float16 *TAPX_ = nullptr, *TAPA_ = nullptr;
 
     // weight intake (net_pack.hip)
     const HostTensor* get(const std::string& k, std::string& err);

@@ -75,6 +75,7 @@ Net* Net::shared_view(hipStream_t stream) const {
     v->stream_ = stream;
     v->dev_allocs_.clear(); v->dev_sizes_.clear();          // not owned
     v->ws_allocs_.clear(); v->wsB_ = 0; v->wsM_ = 0;         // own workspace, allocated at its first forward
+    v->tap_step_ = -1; v->TAPX_ = v->TAPA_ = nullptr;        // the tap buffers are not shared either
     v->sd_.clear();
     v->pev_.clear(); v->pflop_.clear(); v->ptail_.clear(); v->pev_used_ = 0; v->profile_ = false;
     v->prof_ms_ = v->prof_flop_ = v->prof_tail_ms_ = 0; v->prof_launches_ = v->prof_tail_launches_ = 0;
@@ -130,9 +131,10 @@ double Net::flops_per_position(bool with_ssl) const {
 }
 
 int Net::ensure_workspace(int B, std::string& err) {
-    const int Bp = ceil_to(B, 4);
-    const int Mfc = ceil_to(B, 256);
-    if (Bp <= wsB_ && Mfc <= wsM_) return M0_OK;
+    const int Bp = std::max(ceil_to(B, 4), wsB_);             // a regrowth for the tap alone keeps the size
+    const int Mfc = std::max(ceil_to(B, 256), wsM_);
+    const bool want_tap = tap_step_ >= 0;
+    if (Bp <= wsB_ && Mfc <= wsM_ && (!want_tap || TAPX_)) return M0_OK;
     M0_HIP(*hip_, hipSetDevice(device_));
     M0_HIP(*hip_, hipDeviceSynchronize());
     for (void* p : ws_allocs_) M0_HIP(*hip_, hipFree(p));
@@ -155,6 +157,8 @@ int Net::ensure_workspace(int B, std::string& err) {
     SH_ = H(nb * 64 * Cs_); SH2_ = H(nb * 64 * Cs_); SO_ = H(nb * 64 * 32);
     VAL_ = F((size_t)Mfc * 32);
     SPK_ = F((size_t)8 * Mfc * ceil_to(2 * C_, 32));
+    TAPX_ = TAPA_ = nullptr;
+    if (want_tap) { TAPX_ = H(nb * 64 * C); TAPA_ = H(nb * 64 * C); }
     // The clears were enqueued on stream_.  A forward may run on ANOTHER stream (the match engine runs network B on network
     // A's stream, selfplay.hip::one_step), so the (rare) regrowth ends by waiting for them: a late clear would zero
     // activations a kernel already wrote.  The wait also surfaces an asynchronous memset failure.
@@ -300,10 +304,19 @@ int Net::forward(const float* planes_dev, const _Float16* nhwc_dev, int B, float
     _Float16* xa = XA_;
     _Float16* xb = XB_;
     const NormParams* first_bn1 = bn1(plan_.first_bn1);
+    // trunk tap (net.h): after step `step`, whose stream is `stream` and which wrote AA_ when `second`
+    auto tap = [&](int step, const _Float16* stream, bool second) {
+        if (step != tap_step_) return;
+        const size_t bytes = (size_t)Mc * C * sizeof(_Float16);
+        M0_HIP(hs, hipMemcpyAsync(TAPX_, stream, bytes, hipMemcpyDeviceToDevice, st));
+        if (second) M0_HIP(hs, hipMemcpyAsync(TAPA_, AA_, bytes, hipMemcpyDeviceToDevice, st));
+        tap_second_ = second;
+    };
     // stem (resnet.py:314-318) + chess features (229-244)
     ConvNormOpts so;
     if (cfg_.chess_features) so.posenc = posenc_; else so.next_bn1 = first_bn1;
     M0_HIP(hs, conv_norm_act(stem_, stem_n_, x0, xa, T1_, Mc, st, so));
+    tap(0, xa, so.next_bn1 != nullptr);
     if (cfg_.chess_features) {
         if (cfg_.piece_square_tables) {
             ConvNormOpts po;
@@ -311,13 +324,19 @@ int Net::forward(const float* planes_dev, const _Float16* nhwc_dev, int B, float
             M0_HIP(hs, conv_norm_act(pst_, pst_n_, xa, xb, T1_, Mc, st, po));
             std::swap(xa, xb);
         }
+        tap(1, xa, false);
         ConvNormOpts io;
         io.res = xa; io.next_bn1 = first_bn1;
         M0_HIP(hs, conv_norm_act(inter_, inter_n_, xa, xb, T1_, Mc, st, io));
         std::swap(xa, xb);
+        tap(2, xa, first_bn1 != nullptr);
+    } else {
+        tap(1, xa, false);
+        tap(2, xa, false);
     }
     // tower
-    for (const TowerLayer& L : tower_) {
+    for (size_t li = 0; li < tower_.size(); ++li) {
+        const TowerLayer& L = tower_[li];
         const NormParams* next_bn1 = bn1(L.next_bn1);
         if (L.kind == 0) {
             const ResBlockW& r = res_[L.index];
@@ -343,7 +362,7 @@ int Net::forward(const float* planes_dev, const _Float16* nhwc_dev, int B, float
                 M0_HIP(hs, launch_ew_board(e, Bp, st));
             }
         } else {
-            if (L.skip) continue;
+            if (L.skip) { tap(3 + (int)li, xa, false); continue; }
             const AttnW& w = att_[L.index];
             const float inv_sqrt_d = 1.f / sqrtf((float)(C_ / cfg_.attention_heads));
             if (plan_.fuse_attn && w.blk_w != nullptr) {
@@ -370,6 +389,7 @@ int Net::forward(const float* planes_dev, const _Float16* nhwc_dev, int B, float
             }
         }
         std::swap(xa, xb);
+        tap(3 + (int)li, xa, next_bn1 != nullptr);
     }
     // policy head (resnet.py:699-711).  Its first conv and the value head's read the same trunk: where the small-tile GroupNorm
     // epilogue is in use they are ONE launch over the joint weights hv_ (PH2_ <- policy columns, VH2_ <- value columns), the

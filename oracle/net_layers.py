@@ -1,0 +1,363 @@
+"""ORACLE (test infrastructure, not product): the network forward one step at a time, in float64, and a model of where the HIP
+kernels round to fp16.
+
+A "step" is what Net::forward (matrix0_amd/csrc/net.hip) runs between two states of the residual stream, in execution order:
+0 = stem (+ positional encoding), 1 = piece-square conv, 2 = interaction conv, 3 + i = tower layer i (net_ref.tower_layout).
+Every step maps the stream [B,C,8,8] (step 0: the input planes) to the next stream and, where a residual block consumes that
+stream next, to the block's pre-activated input act(GroupNorm(stream; bn1)) -- the kernels' second output, AA_.
+
+  step64 / heads64          the arithmetic of oracle/net_ref.py (its own functions, given float64 tensors)
+  step_model / heads_model  the same arithmetic in float64 with a round-to-nearest fp16 wherever a kernel stores a tensor as
+                            fp16 or multiplies fp16 operands; every such point cites the kernel code it was read off
+  compare                   the per-tensor metric and the bound MARGIN x (model error) that tests/test_net_layers_gpu.py applies
+                            to the GPU's steps, and tests/test_net_layers.py to mutated float64 steps (a test of the test)
+
+Which kernel form a step takes (fused epilogue or conv + ew_board) decides where it rounds: kernel_plan restates the choices of
+Net::make_plan (net_pack.hip) and Net::conv_norm_act (net.hip)."""
+from __future__ import annotations
+
+import math
+from typing import Dict, List, Optional
+
+import torch
+import torch.nn.functional as F
+
+from . import net_ref
+
+MARGIN = 3.0          # GPU error <= MARGIN x model error; tests/test_net_layers.py holds it below the weakest mutation
+LOG2E = 1.44269504088896          # attn_math.h: kLog2e
+
+
+def sd64(sd) -> Dict[str, torch.Tensor]:
+    return {k: torch.as_tensor(v).double() for k, v in sd.items()}
+
+
+def _h(t: torch.Tensor) -> torch.Tensor:
+    """Round to nearest fp16 (a kernel's fp16 store or MFMA operand)."""
+    return t.to(torch.float16).to(torch.float64)
+
+
+# ---- the schedule ---------------------------------------------------------------------------------------------------------
+def schedule(cfg: dict) -> List[dict]:
+    """One entry per step: kind ('stem' | 'pst' | 'inter' | 'res' | 'att'), prefix (state-dict prefix), run (False: the
+    configuration lacks the step, or the inference stride skips the attention layer) and next_bn1 (prefix of the residual block
+    whose bn1 + activation the step also applies, or None) -- TowerLayer::next_bn1 and Plan::first_bn1 of Net::make_plan."""
+    cfg = net_ref.full_cfg(cfg)
+    stride = max(1, int(cfg["infer_attention_stride"]))
+    tower, att_seen = [], 0
+    for kind, idx in net_ref.tower_layout(cfg):
+        run = True
+        if kind == "att":
+            att_seen += 1
+            run = not (stride > 1 and att_seen % stride != 0)
+        tower.append(dict(kind=kind, prefix=f"tower.{idx}", run=run, next_bn1=None))
+    nxt = None
+    for st in reversed(tower):
+        if not st["run"]:
+            continue
+        st["next_bn1"] = nxt
+        nxt = st["prefix"] if st["kind"] == "res" else None
+    cf = bool(cfg["chess_features"])
+    return [dict(kind="stem", prefix="stem", run=True, next_bn1=None if cf else nxt),
+            dict(kind="pst", prefix="chess_features.pst", run=cf and bool(cfg["piece_square_tables"]), next_bn1=None),
+            dict(kind="inter", prefix="chess_features.interaction", run=cf, next_bn1=nxt if cf else None)] + tower
+
+
+def kernel_plan(cfg: dict, fuse_tail: bool = True, fuse_attn: bool = True) -> dict:
+    """The kernel forms Net::make_plan picks (net_pack.hip:208-216); fuse_tail / fuse_attn False = M0_FUSE_TAIL=0 / M0_FUSE_ATTN=0."""
+    cfg = net_ref.full_cfg(cfg)
+    C = int(cfg["channels"])
+    Cp = 320 if 256 < C < 320 else C                           # net.hip: Cp_
+    big = Cp % 320 == 0                                        # conv_gemm.hip: conv_gemm_tile_n(Cp, Cp) == 320
+    hidden = max(8, int(C * float(cfg["se_ratio"])))
+    return dict(big=big, gn_small=Cp % 64 == 0, fuse_attn=big and fuse_attn,
+                fuse_tail=big and fuse_tail and (not cfg["se"] or (hidden <= 96 and hidden % 4 == 0)))
+
+
+# ---- float64 --------------------------------------------------------------------------------------------------------------
+def _second(out, sd, cfg, st):
+    return None if st["next_bn1"] is None else net_ref._act(net_ref._norm(out, sd, st["next_bn1"] + ".bn1", cfg), cfg)
+
+
+@torch.no_grad()
+def step64(sd, cfg, step: int, x: torch.Tensor):
+    """(stream after `step`, second output or None) in float64 from the step's input stream x (step 0: the planes).  `sd` from sd64."""
+    cfg = net_ref.full_cfg(cfg)
+    st = schedule(cfg)[step]
+    x = x.double()
+    if not st["run"]:
+        return x, None
+    k = st["kind"]
+    if k == "stem":                                            # resnet.py:314-318, 229-232
+        out = net_ref._act(net_ref._norm(F.conv2d(x, sd["stem.0.weight"], padding=1), sd, "stem.1", cfg), cfg)
+        if cfg["chess_features"]:
+            out = out + sd["chess_features.position_encoding"]
+    elif k == "pst":                                           # resnet.py:233-238
+        t = F.conv2d(x, sd["chess_features.pst_conv.weight"])
+        out = x + net_ref._act(net_ref._norm(t, sd, "chess_features.pst_norm", cfg), cfg)
+    elif k == "inter":                                         # resnet.py:239-244
+        t = F.conv2d(x, sd["chess_features.interaction_conv.weight"], padding=1)
+        out = x + net_ref._act(net_ref._norm(t, sd, "chess_features.interaction_norm", cfg), cfg)
+    elif k == "res":
+        out = net_ref._res_block(x, sd, st["prefix"], cfg)
+    else:
+        out = net_ref._attention(x, sd, st["prefix"], cfg, net_ref.attention_mask())
+    return out, _second(out, sd, cfg, st)
+
+
+@torch.no_grad()
+def heads64(sd, cfg, feats: torch.Tensor):
+    """(logits [B,4672], value [B], {task: ssl map}) in float64 from the last stream."""
+    cfg = net_ref.full_cfg(cfg)
+    return net_ref._heads(feats.double(), sd, cfg, True)
+
+
+# ---- the storage model ----------------------------------------------------------------------------------------------------
+def _gn_from(val, src, sd, prefix):
+    """GroupNorm16 of `val` with the statistics of `src`: a kernel that normalises a tensor it has already rounded to fp16 still
+    takes the sums from its fp32 values (conv_epilogue.h: EPI_PLAIN's out_stats; net_kernels.hip: ew_gn_channel)."""
+    B, C = src.shape[:2]
+    g = src.reshape(B, C // 16, -1)
+    mean = g.mean(-1)
+    rstd = torch.rsqrt(g.var(-1, unbiased=False) + 1e-5)
+    mean = mean.repeat_interleave(16, 1)[:, :, None, None]
+    rstd = rstd.repeat_interleave(16, 1)[:, :, None, None]
+    return (val - mean) * rstd * sd[prefix + ".weight"][None, :, None, None] + sd[prefix + ".bias"][None, :, None, None]
+
+
+def _model_second(y16, stats_src, sd, cfg, st):
+    # every writer of AA_ normalises the fp16 stream it has just stored and rounds the result: conv_tail.h tail_y2 (sums of the
+    # rounded y, tail_residual), net_kernels.hip ew_board step 5 and attn_block.hip ab_second_output (sums of the fp32 y)
+    if st["next_bn1"] is None:
+        return None
+    return _h(net_ref._act(_gn_from(y16, stats_src, sd, st["next_bn1"] + ".bn1"), cfg))
+
+
+def _model_conv_norm(x, sd, cfg, wkey, norm, pad, form, res=None, posenc=None):
+    """Net::conv_norm_act (net.hip): out = act(GroupNorm(conv(x))) [+ posenc] [+ res] in one of its three forms."""
+    t = F.conv2d(x, _h(sd[wkey]), padding=pad)                 # fp16 weights (net_pack.hip pack_gemm), fp16 operand x, fp32 sums
+    if form == "tail":
+        # conv_tail.h / conv_zs_tail.h, PRE: act(GroupNorm(t)) on the accumulators -> fp16 image; tail_residual: y = x + image as
+        # a packed fp16 add
+        return _h(res + _h(net_ref._act(_gn_from(t, t, sd, norm), cfg)))
+    if form == "epilogue":
+        # conv_epilogue.h EPI_GN / conv_zs_epilogue.h: GroupNorm + act (+ posenc) on the accumulators, one fp16 store
+        y = net_ref._act(_gn_from(t, t, sd, norm), cfg)
+        return _h(y if posenc is None else y + posenc)
+    # unfused: the raw conv is stored as fp16 (conv_epilogue.h EPI_PLAIN / EPI_ELEMENT) with fp32 statistics, then
+    # net_kernels.hip ew_board_kernel: act(GroupNorm(fp16 t)) + res + posenc in fp32, one fp16 store
+    y = net_ref._act(_gn_from(_h(t), t, sd, norm), cfg)
+    if res is not None:
+        y = y + res
+    if posenc is not None:
+        y = y + posenc
+    return _h(y)
+
+
+def _model_res_block(x, sd, cfg, st, plan):
+    p = st["prefix"]
+    # AA_ = act(bn1(x)) as the previous step stored it (fp16); recomputed here from the fp16 stream
+    a = _h(net_ref._act(_gn_from(x, x, sd, p + ".bn1"), cfg))
+    # conv1 + bn2 + act -> T1_: conv_zs_kernel EPI_GN on the 320-wide trunk, else conv + ew_board (net.hip conv_norm_act)
+    t1 = _model_conv_norm(a, sd, cfg, p + ".conv1.weight", p + ".bn2", 1, "epilogue" if plan["big"] else "unfused")
+    t = F.conv2d(t1, _h(sd[p + ".conv2.weight"]), padding=1)
+    if plan["fuse_tail"]:
+        gate = 1.0
+        if cfg["se"]:
+            # conv_zs_tail.h A-C: channel means and hidden units as fp16 hi + lo pairs (~fp32), W1 and W2 as fp16 fragments
+            w = t.mean(dim=(2, 3))
+            w = net_ref._act(F.linear(w, _h(sd[p + ".se_fc1.weight"]), sd[p + ".se_fc1.bias"]), cfg)
+            gate = torch.sigmoid(F.linear(w, _h(sd[p + ".se_fc2.weight"]), sd[p + ".se_fc2.bias"]))[:, :, None, None]
+        y = _h(x + _h(t * gate))                               # conv_zs_tail.h D: gate * t -> fp16 image; conv_tail.h tail_residual
+        return y, _model_second(y, y, sd, cfg, st)
+    t16 = _h(t)                                                # net.hip: conv2 -> T2_ (fp16) with fp32 sums in S2_
+    gate = 1.0
+    if cfg["se"]:
+        w = t.mean(dim=(2, 3))                                 # net_kernels.hip se_gate_kernel: fp32 weights, pool from S2_
+        w = net_ref._act(F.linear(w, sd[p + ".se_fc1.weight"], sd[p + ".se_fc1.bias"]), cfg)
+        gate = torch.sigmoid(F.linear(w, sd[p + ".se_fc2.weight"], sd[p + ".se_fc2.bias"]))[:, :, None, None]
+    yf = t16 * gate + x                                        # ew_board_kernel step 3
+    y = _h(yf)
+    return y, _model_second(y, yf, sd, cfg, st)
+
+
+def _model_attention(x, sd, cfg, st, plan):
+    p = st["prefix"]
+    B, C = x.shape[:2]
+    heads = int(cfg["attention_heads"])
+    D = C // heads
+    # qkv as fp16: QKV_ (net.hip, split path) / q, k, v in LDS (attn_block.hip ab_stage_qkv)
+    qkv = _h(F.conv2d(x, _h(sd[p + ".qkv.weight"]))).reshape(B, 3, heads, D, 64).permute(1, 0, 2, 4, 3)
+    q, k, v = qkv[0], qkv[1], qkv[2]
+    # attn_math.h attn_softmax_pv: scores in log2 units, fp32; rel_bias * log2(e) as fp16 (net_pack.hip pack_attn:
+    # attn_block_bias<_Float16>; attn_core.hip converts the same table into LDS)
+    s = torch.matmul(q, k.transpose(-2, -1)) * (LOG2E / math.sqrt(D))
+    if cfg["attention_relbias"]:
+        s = s + _h(sd[p + ".rel_bias"] * LOG2E)
+    e = torch.exp2(torch.clamp(s, -50.0 * LOG2E, 50.0 * LOG2E))          # no max subtraction: the clamp bounds the exponent
+    vis = net_ref.attention_mask().double()[None, None]
+    mix = float(cfg["attention_unmasked_mix"])
+    if 0.0 < mix < 1.0:                                        # attn_math.h attn_branch_weights
+        wm, wu = 1.0 - mix, 1.0 - (1.0 - mix)
+    elif mix >= 1.0:
+        wm, wu = 1.0, 0.0
+    else:
+        wm, wu = 0.0, 1.0
+    cu = wu / e.sum(-1, keepdim=True)
+    cm = wm / (e * vis).sum(-1, keepdim=True)
+    pf = _h(e * (vis * cm + cu))                               # attn_math.h: pf[u] = (_Float16)(e * (vs * cm + cu)), MFMA operand
+    o = _h(torch.matmul(pf, v))                                # attn_math.h attn_pack_o: O as fp16 (O_ / over Q in LDS)
+    o = o.transpose(1, 2).reshape(B, 64, C).transpose(1, 2).reshape(B, C, 8, 8)
+    t = F.conv2d(o, _h(sd[p + ".proj.weight"]))
+    if not plan["fuse_attn"]:
+        t = _h(t)                                              # net.hip split path: proj -> T1_ (fp16)
+    # attn_block.hip ab_residual_layernorm / ew_board_kernel: residual and LayerNorm in fp32, one fp16 store
+    yf = F.layer_norm((t + x).permute(0, 2, 3, 1), (C,), sd[p + ".norm.weight"], sd[p + ".norm.bias"], 1e-5).permute(0, 3, 1, 2)
+    y = _h(yf)
+    return y, _model_second(y, yf, sd, cfg, st)
+
+
+@torch.no_grad()
+def step_model(sd, cfg, step: int, x: torch.Tensor, plan: Optional[dict] = None):
+    """step64's results as the kernels' arithmetic gives them up to fp32 effects: float64 with fp16 rounding at the kernels'
+    storage points.  x is the fp16-exact input (a GPU tap, or a rounded float64 stream)."""
+    cfg = net_ref.full_cfg(cfg)
+    plan = plan or kernel_plan(cfg)
+    st = schedule(cfg)[step]
+    x = x.double()
+    if not st["run"]:
+        return x, None
+    k = st["kind"]
+    if k == "stem":
+        # planes_to_nhwc (net_kernels.hip) stores the planes as fp16; the stem runs conv_gemm_kernel<9> with the GroupNorm
+        # epilogue where the trunk is a multiple of 64 wide and nothing else is asked of it (net.hip conv_norm_act)
+        pe = sd["chess_features.position_encoding"] if cfg["chess_features"] else None
+        form = "epilogue" if plan["gn_small"] and st["next_bn1"] is None else "unfused"
+        y = _model_conv_norm(_h(x), sd, cfg, "stem.0.weight", "stem.1", 1, form, posenc=pe)
+    elif k in ("pst", "inter"):
+        form = "tail" if plan["fuse_tail"] else "unfused"      # conv_big_kernel / conv_zs_kernel EPI_TAIL_PRE, else conv + ew_board
+        y = _model_conv_norm(x, sd, cfg, st["prefix"] + "_conv.weight", st["prefix"] + "_norm", 0 if k == "pst" else 1, form, res=x)
+    elif k == "res":
+        return _model_res_block(x, sd, cfg, st, plan)
+    else:
+        return _model_attention(x, sd, cfg, st, plan)
+    # tail_y2 normalises the rounded y with its own sums; ew_board takes the sums of the fp32 y: the difference is far below
+    # one fp16 rounding, and the rounded y stands for both here
+    return y, _model_second(y, y, sd, cfg, st)
+
+
+@torch.no_grad()
+def heads_model(sd, cfg, feats: torch.Tensor, plan: Optional[dict] = None):
+    """heads64 with the kernels' fp16 points (net.hip, after the tower): every head conv and FC has fp16 weights and an fp16
+    output, except the logits and the value, which leave their GEMM as fp32."""
+    cfg = net_ref.full_cfg(cfg)
+    plan = plan or kernel_plan(cfg)
+    x = feats.double()
+    B = x.shape[0]
+    small = "epilogue" if plan["gn_small"] else "unfused"      # conv_gemm_kernel<1> EPI_GN for N = 32 / 64 / 128 / 160
+    ph = _model_conv_norm(x, sd, cfg, "policy_head.0.weight", "policy_head.1", 0, small)       # PH2_ (joint launch hv_)
+    pflat = ph.reshape(B, -1)
+    if int(cfg["policy_factor_rank"]) > 0:
+        f1 = _h(F.relu(F.linear(pflat, _h(sd["policy_fc1.weight"]), sd["policy_fc1.bias"])))   # F1_: EPI_ELEMENT, fp16
+        p_ = F.linear(f1, _h(sd["policy_fc2.weight"]), sd["policy_fc2.bias"])
+    else:
+        p_ = F.linear(pflat, _h(sd["policy_fc.weight"]), sd["policy_fc.bias"])
+    p_ = p_ * torch.clamp(F.softplus(sd["_policy_logit_scale_raw"]) + 1e-3, max=5.0)           # out_f32, out_scale
+    v = _model_conv_norm(x, sd, cfg, "value_head.0.weight", "value_head.1", 0, small)          # VH2_
+    v = _model_conv_norm(v, sd, cfg, "value_head.3.weight", "value_head.4", 0, small)          # VH_
+    v = v.reshape(B, -1)
+    v = _h(net_ref._value_act(F.linear(v, _h(sd["value_fc1.weight"]), sd["value_fc1.bias"]), cfg))     # F2_ (split-K sums in fp32)
+    v = _h(net_ref._value_act(F.linear(v, _h(sd["value_fc2.weight"]), sd["value_fc2.bias"]), cfg))     # F3_
+    v = _h(v * torch.sigmoid(F.linear(v, _h(sd["value_gate.0.weight"]), sd["value_gate.0.bias"])))     # F4_: GemmArgs::mul
+    v = torch.tanh(F.linear(v, _h(sd["value_fc3.weight"]), sd["value_fc3.bias"])).squeeze(-1)          # VAL_ fp32
+    ssl = {}
+    if cfg["self_supervised"]:
+        for task in cfg["ssl_tasks"]:
+            if task in net_ref.SSL_OUT:
+                h = f"ssl_heads.{task}"
+                t = _model_conv_norm(x, sd, cfg, h + ".0.weight", h + ".1", 0, small)          # SH2_
+                ssl[task] = _h(F.conv2d(t, _h(sd[h + ".3.weight"])))                           # SO_ fp16, widened by nhwc_to_nchw_f32
+    return p_, v, ssl
+
+
+# ---- inputs and weight regimes of the tests ------------------------------------------------------------------------------------
+def random_planes(B: int, seed: int) -> torch.Tensor:
+    """The input planes of tests/test_net_gpu.py: sparse piece planes, 0/1 flag planes, two counters in [0,1)."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.zeros(B, 19, 8, 8)
+    x[:, :12] = (torch.rand(B, 12, 8, 8, generator=g) < 0.08).float()
+    x[:, 12:17] = (torch.rand(B, 5, 1, 1, generator=g) < 0.5).float()
+    x[:, 17:] = torch.rand(B, 2, 1, 1, generator=g)
+    return x
+
+
+def sharpen(sd, cfg) -> dict:
+    """The "sharp" regime: in every attention layer the q and k rows of qkv.weight x4 and rel_bias x8 -- scores of a trained
+    network's size, so that the +-50 clamp binds, exp2 works without a max subtraction near the ends of its range and the fp16
+    bias table's quantisation matters."""
+    C = int(net_ref.full_cfg(cfg)["channels"])
+    out = dict(sd)
+    for kind, idx in net_ref.tower_layout(cfg):
+        if kind == "att":
+            w = sd[f"tower.{idx}.qkv.weight"].clone()
+            w[:2 * C] *= 4.0
+            out[f"tower.{idx}.qkv.weight"] = w
+            if f"tower.{idx}.rel_bias" in sd:
+                out[f"tower.{idx}.rel_bias"] = sd[f"tower.{idx}.rel_bias"] * 8.0
+    return out
+
+
+@torch.no_grad()
+def attention_stats(sd, cfg, step: int, x: torch.Tensor) -> dict:
+    """Of an attention step on input x, in float64: the scores' std, the fraction outside the +-50 clamp and the mean largest
+    probability of the unmasked softmax."""
+    cfg = net_ref.full_cfg(cfg)
+    p = schedule(cfg)[step]["prefix"]
+    B, C = x.shape[:2]
+    heads = int(cfg["attention_heads"])
+    D = C // heads
+    qkv = F.conv2d(x.double(), sd[p + ".qkv.weight"]).reshape(B, 3, heads, D, 64).permute(1, 0, 2, 4, 3)
+    s = torch.matmul(qkv[0], qkv[1].transpose(-2, -1)) / math.sqrt(D)
+    if cfg["attention_relbias"]:
+        s = s + sd[p + ".rel_bias"]
+    pr = F.softmax(torch.clamp(s, -50.0, 50.0), dim=-1)
+    return {"std": float(s.std()), "clamped": float((s.abs() > 50.0).double().mean()), "maxprob": float(pr.max(-1).values.mean())}
+
+
+@torch.no_grad()
+def chain64(sd, cfg, planes: torch.Tensor):
+    """Every step in turn, float64 all the way: [(input, stream, second)] per step."""
+    out, x = [], planes.double()
+    for s in range(len(schedule(cfg))):
+        y, y2 = step64(sd, cfg, s, x)
+        out.append((x, y, y2))
+        x = y
+    return out
+
+
+# ---- the comparator -------------------------------------------------------------------------------------------------------
+def metric(got: torch.Tensor, ref: torch.Tensor, maps: bool = True) -> dict:
+    """{'rel': max over (board, channel) of ||got - ref||_2 over the 64 squares / (||ref||_2 + 1e-3), 'abs': max |got - ref|};
+    maps=False (logits, value): 'abs' alone."""
+    got, ref = got.double(), ref.double()
+    out = {"abs": float((got - ref).abs().max())}
+    if maps:
+        d = (got - ref).flatten(2).norm(dim=-1)
+        out["rel"] = float((d / (ref.flatten(2).norm(dim=-1) + 1e-3)).max())
+    return out
+
+
+def compare(got: torch.Tensor, ref: torch.Tensor, model: torch.Tensor, maps: bool = True) -> dict:
+    """Errors of `got` and of the storage model against the float64 `ref`, their ratios, and ok = every error within
+    MARGIN x the model's."""
+    e, m = metric(got, ref, maps), metric(model, ref, maps)
+    ratio = {k: (e[k] / m[k] if m[k] > 0 else (0.0 if e[k] == 0 else math.inf)) for k in e}
+    return {"err": e, "model": m, "ratio": ratio, "ok": all(e[k] <= MARGIN * m[k] for k in e)}
+
+
+def worst(got: torch.Tensor, ref: torch.Tensor, n: int = 5):
+    """The n worst (board, channel, square, got, ref) of a map: the pattern of an error names its cause."""
+    d = (got.double() - ref.double()).abs().flatten(2)
+    idx = torch.topk(d.flatten(), min(n, d.numel())).indices.tolist()
+    C, S = d.shape[1], d.shape[2]
+    return [(i // (C * S), (i // S) % C, i % S, float(got.flatten()[i]), float(ref.flatten()[i])) for i in idx]

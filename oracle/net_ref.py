@@ -181,6 +181,14 @@ def forward(sd: Dict[str, torch.Tensor], cfg: dict, x: torch.Tensor, return_ssl:
                 continue
             x = _attention(x, sd, p, cfg, mask)
     feats = torch.nan_to_num(x, nan=0.0, posinf=0.0, neginf=0.0)
+    p_, v, ssl = _heads(feats, sd, cfg, return_ssl)
+    if return_feats:
+        return p_, v, ssl, feats
+    return p_, v, ssl
+
+
+def _heads(feats, sd, cfg, return_ssl):
+    """Policy, value and SSL heads over the tower's features (resnet.py:697-753), in the dtype of `feats` and `sd`."""
     # policy (resnet.py:699-711)
     pf = F.conv2d(feats, sd["policy_head.0.weight"])
     pf = _act(_norm(pf, sd, "policy_head.1", cfg), cfg)
@@ -213,8 +221,6 @@ def forward(sd: Dict[str, torch.Tensor], cfg: dict, x: torch.Tensor, return_ssl:
             t = F.conv2d(feats, sd[h + ".0.weight"])
             t = _act(_norm(t, sd, h + ".1", cfg), cfg)
             ssl[task] = F.conv2d(t, sd[h + ".3.weight"])
-    if return_feats:
-        return p_, v, ssl, feats
     return p_, v, ssl
 
 
