@@ -557,4 +557,6 @@ int m0_replay_games(int hip_device, const char* const* start_fens, const uint32_
 #endif
 /* live searches on an analysis engine (peek, stop, held trees, continue by moves): the calls a UCI front end needs */
 #include "m0_analysis_live.h"
+/* training loss of stored positions under a network, per row (no trainer, no gradient) */
+#include "m0_score.h"
 #endif /* M0_ENGINE_H */

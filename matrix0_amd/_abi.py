@@ -28,6 +28,11 @@ HALFMOVE_SATURATED, FULLMOVE_SATURATED, EP_FROM_MASK, NO_MASK = 1, 2, 4, 8
 REPLAY_STATUS = {0: "ok", 1: "illegal", 2: "ambiguous", 3: "too_long"}
 REPLAY_END_BITS = {"checkmate": 1, "stalemate": 2, "insufficient": 4, "white_to_move": 8}
 MOVE_UCI, MOVE_RAW = 0, 1
+# include/m0_score.h: how a row's support is chosen, its columns and the flag bits of the last one
+SCORE_MASK = {"legal": 0, "target": 1, "none": 2}
+SCORE_COLS = 8
+SCORE_COLUMNS = ("policy_loss", "entropy", "value_loss", "rank", "support_mass", "support_size", "value", "flags")
+SCORE_FLAGS = {"empty": 1, "nonfinite": 2, "uniform": 4}
 
 # ---- structs ----
 i32, i64, u8, u16, u32, u64, f32, f64 = (C.c_int, C.c_int64, C.c_uint8, C.c_uint16, C.c_uint32, C.c_uint64, C.c_float,
@@ -100,6 +105,10 @@ class AnalysisResult(C.Structure):
                 ("sims", i32), ("root_n", i32), ("evals", u64), ("value", f32), ("root_q", f64),
                 ("nlines", i32), ("lines", AnalysisLine * AN_MAX_LINES),
                 ("tb_dtm", i32), ("line_dtm", i32 * AN_MAX_LINES)]
+
+
+class ScoreOpts(C.Structure):
+    _fields_ = [("mask_mode", i32), ("label_smoothing", f32), ("value_loss", i32), ("huber_delta", f32)]
 
 
 STRUCTS = {"m0_net_cfg": NetCfg, "m0_selfplay_cfg": SelfplayCfg, "m0_selfplay_stats": SelfplayStats,
@@ -222,12 +231,21 @@ LIVE_FUNCTIONS = {
     "m0_analysis_held": (i32, [vp]),
 }
 
+# ---- include/m0_score.h (which m0_engine.h includes too): the training loss of stored rows, in that header's order;
+# tests/test_abi_score.py compares the two ----
+SCORE_STRUCTS = {"m0_score_opts": ScoreOpts}
+SCORE_FUNCTIONS = {
+    "m0_score_rows": (i32, [i32, vp, vp, vp, vp, vp, i32, P(ScoreOpts), vp]),
+    "m0_net_score": (i32, [vp, vp, vp, vp, vp, i32, P(ScoreOpts), vp]),
+    "m0_score_bench": (i32, [i32, i32, i32, P(f32), P(f64)]),
+}
+
 
 def bind(L) -> list:
-    """Set restype and argtypes of every function of FUNCTIONS and LIVE_FUNCTIONS on the loaded library; the names it does not
-    export."""
+    """Set restype and argtypes of every function of FUNCTIONS, LIVE_FUNCTIONS and SCORE_FUNCTIONS on the loaded library; the
+    names it does not export."""
     missing = []
-    for name, (restype, argtypes) in list(FUNCTIONS.items()) + list(LIVE_FUNCTIONS.items()):
+    for name, (restype, argtypes) in list(FUNCTIONS.items()) + list(LIVE_FUNCTIONS.items()) + list(SCORE_FUNCTIONS.items()):
         fn = getattr(L, name, None)
         if fn is None:
             missing.append(name)

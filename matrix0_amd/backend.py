@@ -17,7 +17,33 @@ from typing import Dict, Optional, Tuple
 
 import numpy as np
 
-from . import _lib
+from . import _abi, _lib
+
+
+def resolve_mask_mode(pi: np.ndarray, legal_mask, mask_mode: Optional[str]) -> str:
+    """The support rule of a score call: "legal" with a mask; without one the reference's rule on the arrays given
+    (train.py:454-460): every row one-hot -> "none" (imported games), otherwise "target" (soft search targets)."""
+    if mask_mode is not None:
+        if mask_mode not in _abi.SCORE_MASK:
+            raise ValueError(f"mask_mode must be one of {sorted(_abi.SCORE_MASK)} or None, got {mask_mode!r}")
+        return mask_mode
+    if legal_mask is not None:
+        return "legal"
+    return "none" if bool(((np.asarray(pi) > 0).sum(axis=1) == 1).all()) else "target"
+
+
+class NonFiniteScore(ValueError):
+    """M0Backend.score met non-finite network outputs; `rows` holds the columns all the same (flag 2 marks the rows)."""
+
+    def __init__(self, msg: str, rows: np.ndarray):
+        super().__init__(msg)
+        self.rows = rows
+
+
+def score_opts(mask_mode: str, label_smoothing: float, value_loss: str, huber_delta: float) -> "_abi.ScoreOpts":
+    if value_loss not in ("mse", "huber"):
+        raise ValueError(f"value_loss must be 'mse' or 'huber', got {value_loss!r}")
+    return _abi.ScoreOpts(_abi.SCORE_MASK[mask_mode], float(label_smoothing), int(value_loss == "huber"), float(huber_delta))
 
 
 class M0Backend:
@@ -123,6 +149,37 @@ class M0Backend:
         if tap_step is not None:
             return pol, val, out, stream, (second if has_second.value else None)
         return pol, val, out
+
+    # ---- training loss of stored rows --------------------------------------------------------
+    def score(self, s: np.ndarray, pi: np.ndarray, z: np.ndarray, legal_mask: Optional[np.ndarray] = None, *,
+              mask_mode: Optional[str] = None, label_smoothing: float = 0.0, value_loss: str = "mse",
+              huber_delta: float = 1.0) -> np.ndarray:
+        """f32 [B, 8]: the columns of include/m0_score.h (_abi.SCORE_COLUMNS) for the rows (s, pi, z, legal_mask) under this
+        network -- forward and loss on the device (m0_net_score), only the 8 columns come back.  mask_mode: "legal", "target",
+        "none", or None for resolve_mask_mode.  A non-finite network output raises NonFiniteScore (a ValueError, as infer_np
+        raises; it carries the rows)."""
+        if not self._finalized:
+            raise RuntimeError("weights not loaded")
+        a = np.ascontiguousarray(s, dtype=np.float32)
+        if a.ndim != 4 or a.shape[1:] != (self._cfg.planes, 8, 8):
+            raise ValueError(f"expected input [B,{self._cfg.planes},8,8], got {a.shape}")
+        B = a.shape[0]
+        pi = np.ascontiguousarray(pi, dtype=np.float32)
+        z = np.ascontiguousarray(np.asarray(z).reshape(-1), dtype=np.float32)
+        if pi.shape != (B, _lib.POLICY_SIZE) or z.shape != (B,):
+            raise ValueError(f"expected pi [{B},{_lib.POLICY_SIZE}] and z [{B}], got {pi.shape} and {z.shape}")
+        if legal_mask is not None:
+            legal_mask = np.ascontiguousarray(np.asarray(legal_mask).reshape(B, -1), dtype=np.uint8)
+            if legal_mask.shape != pi.shape:
+                raise ValueError(f"expected legal_mask [{B},{_lib.POLICY_SIZE}], got {legal_mask.shape}")
+        opts = score_opts(resolve_mask_mode(pi, legal_mask, mask_mode), label_smoothing, value_loss, huber_delta)
+        rows = np.empty((B, _abi.SCORE_COLS), dtype=np.float32)
+        rc = self._L.m0_net_score(self._h, _lib.ptr(a), _lib.ptr(pi), _lib.ptr(z), _lib.ptr(legal_mask), B, C.byref(opts),
+                                  _lib.ptr(rows))
+        if rc == _lib.M0_ERR_NONFINITE:
+            raise NonFiniteScore(f"m0_net_score failed ({rc}): {_lib.last_error()}", rows)
+        _lib.check(rc, "m0_net_score")
+        return rows
 
     # ---- measurement helpers ----------------------------------------------------------------
     def param_count(self) -> int:

@@ -8,6 +8,8 @@
 #include "../../include/m0_engine.h"
 #include "net.h"
 #include "capi_common.h"
+#include "score_core.h"
+#include "score_kernels.h"
 
 thread_local std::string g_m0_last_error;
 
@@ -24,6 +26,12 @@ struct m0_net {
     float* value_dev = nullptr;
     float* ssl_dev = nullptr;
     int cap = 0;
+    // staging buffers of m0_net_score: the stored targets in, the score columns out
+    float* score_pi_dev = nullptr;
+    float* score_z_dev = nullptr;
+    uint8_t* score_mask_dev = nullptr;
+    float* score_rows_dev = nullptr;
+    int score_cap = 0;
 };
 
 Net* m0_net_impl(m0_net* n) { return n ? n->net : nullptr; }
@@ -89,6 +97,10 @@ void m0_net_destroy(m0_net* n) {
     if (n->logits_dev) (void)hipFree(n->logits_dev);
     if (n->value_dev) (void)hipFree(n->value_dev);
     if (n->ssl_dev) (void)hipFree(n->ssl_dev);
+    if (n->score_pi_dev) (void)hipFree(n->score_pi_dev);
+    if (n->score_z_dev) (void)hipFree(n->score_z_dev);
+    if (n->score_mask_dev) (void)hipFree(n->score_mask_dev);
+    if (n->score_rows_dev) (void)hipFree(n->score_rows_dev);
     delete n->net;
     if (n->stream) (void)hipStreamDestroy(n->stream);
     delete n;
@@ -130,6 +142,27 @@ static int ensure_io(m0_net* n, int B) {
     M0_HIP(hs, hipMalloc((void**)&n->ssl_dev, (size_t)cap * (sslc > 0 ? sslc : 1) * 64 * 4));
     if (!hs.ok()) return m0_hip_error(hs, "hipMalloc failed for I/O staging");
     n->cap = cap;
+    return M0_OK;
+}
+
+// the staging of m0_net_score, grown as ensure_io grows the forward's
+static int ensure_score_io(m0_net* n, int B) {
+    if (B <= n->score_cap) return M0_OK;
+    HipStatus& hs = n->net->hip();
+    if (n->score_pi_dev) M0_HIP(hs, hipFree(n->score_pi_dev));
+    if (n->score_z_dev) M0_HIP(hs, hipFree(n->score_z_dev));
+    if (n->score_mask_dev) M0_HIP(hs, hipFree(n->score_mask_dev));
+    if (n->score_rows_dev) M0_HIP(hs, hipFree(n->score_rows_dev));
+    n->score_pi_dev = n->score_z_dev = n->score_rows_dev = nullptr;
+    n->score_mask_dev = nullptr;
+    n->score_cap = 0;
+    const int cap = B < 64 ? 64 : B;
+    M0_HIP(hs, hipMalloc((void**)&n->score_pi_dev, (size_t)cap * M0_POLICY_SIZE * 4));
+    M0_HIP(hs, hipMalloc((void**)&n->score_z_dev, (size_t)cap * 4));
+    M0_HIP(hs, hipMalloc((void**)&n->score_mask_dev, (size_t)cap * M0_POLICY_SIZE));
+    M0_HIP(hs, hipMalloc((void**)&n->score_rows_dev, (size_t)cap * M0_SCORE_COLS * 4));
+    if (!hs.ok()) return m0_hip_error(hs, "hipMalloc failed for score staging");
+    n->score_cap = cap;
     return M0_OK;
 }
 
@@ -181,6 +214,40 @@ int m0_net_infer(m0_net* n, const float* planes, int B, float* policy, float* va
     if (B <= 0) { m0_set_error("batch must be positive"); return M0_ERR_INVALID; }
     std::lock_guard<std::mutex> lk(n->mu);
     return infer_locked(n, planes, B, policy, value, ssl);
+}
+
+int m0_net_score(m0_net* n, const float* planes, const float* pi, const float* z, const uint8_t* legal_mask, int B,
+                 const m0_score_opts* opts, float* rows) {
+    if (!n || !planes || !pi || !z || !rows) { m0_set_error("null argument"); return M0_ERR_INVALID; }
+    if (B <= 0) { m0_set_error("batch must be positive"); return M0_ERR_INVALID; }
+    if (const char* why = m0score::bad_opts(opts, legal_mask != nullptr)) { m0_set_error(why); return M0_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(n->mu);
+    HipStatus& hs = n->net->hip();
+    if (!M0_HIP(hs, hipSetDevice(n->device))) return m0_hip_error(hs);       // also a network that has failed before
+    int rc = ensure_io(n, B);
+    if (rc == M0_OK) rc = ensure_score_io(n, B);
+    if (rc != M0_OK) return rc;
+    const bool masked = opts->mask_mode == M0_SCORE_MASK_LEGAL;
+    const size_t cells = (size_t)B * M0_POLICY_SIZE;
+    M0_HIP(hs, hipMemcpyAsync(n->planes_dev, planes, (size_t)B * n->net->cfg().planes * 64 * 4, hipMemcpyHostToDevice, n->stream));
+    M0_HIP(hs, hipMemcpyAsync(n->score_pi_dev, pi, cells * 4, hipMemcpyHostToDevice, n->stream));
+    M0_HIP(hs, hipMemcpyAsync(n->score_z_dev, z, (size_t)B * 4, hipMemcpyHostToDevice, n->stream));
+    if (masked) M0_HIP(hs, hipMemcpyAsync(n->score_mask_dev, legal_mask, cells, hipMemcpyHostToDevice, n->stream));
+    if (!hs.ok()) return m0_hip_error(hs, "H2D copy");
+    std::string err;
+    rc = n->net->forward(n->planes_dev, nullptr, B, n->logits_dev, n->value_dev, nullptr, n->stream, err);
+    if (rc != M0_OK) { m0_set_error(err); return rc; }
+    // the logits stay where the forward left them
+    M0_HIP(hs, launch_score_rows(n->logits_dev, n->value_dev, n->score_pi_dev, n->score_z_dev, masked ? n->score_mask_dev : nullptr,
+                                 B, *opts, n->score_rows_dev, n->stream));
+    M0_HIP(hs, hipMemcpyAsync(rows, n->score_rows_dev, (size_t)B * M0_SCORE_COLS * 4, hipMemcpyDeviceToHost, n->stream));
+    if (!M0_HIP(hs, hipStreamSynchronize(n->stream))) return m0_hip_error(hs, "forward and score failed");
+    for (int b = 0; b < B; ++b)
+        if ((int)rows[(size_t)b * M0_SCORE_COLS + 7] & M0_SCORE_FLAG_NONFINITE) {
+            m0_set_error("network produced non-finite outputs (row " + std::to_string(b) + ")");
+            return M0_ERR_NONFINITE;
+        }
+    return M0_OK;
 }
 
 int m0_net_tap_info(const m0_net* n, int* steps, int* width) {
