@@ -20,9 +20,11 @@ CFG = {"seed": 77,
                     "opening_random_plies": 4, "temperature_start": 1.2, "temperature_end": 0.3, "temperature_moves": 40}}
 
 
-def _play(be, eval_cache, **kw):
+def _play(be, eval_cache, cfg=CFG, openings=None, **kw):
     from matrix0_amd import engine as eng
-    e = eng.SelfplayEngine(be, eng.selfplay_cfg_from_dict(CFG, concurrent_games=6, total_games=8, eval_cache=eval_cache, **kw))
+    e = eng.SelfplayEngine(be, eng.selfplay_cfg_from_dict(cfg, concurrent_games=6, total_games=8, eval_cache=eval_cache, **kw))
+    if openings:
+        e.set_openings(openings)
     games = {}
     for _ in range(4000):
         e.step(4)
@@ -56,6 +58,35 @@ def test_games_are_identical_with_and_without_the_cache(mode):
     print(f"eval cache [{mode}]: {int(st_on['evals_cached'])} of {int(st_off['evals'])} leaf evaluations served from the cache "
           f"({100.0 * st_on['evals_cached'] / st_off['evals']:.1f} %)")
     assert st_on["evals_cached"] > 0.005 * st_off["evals"]
+
+
+def test_games_from_roots_at_the_cache_payload_boundary_are_identical():
+    """An entry holds the logits of at most 64 legal moves (M0_EC_MAXLEGAL): games that start on positions with 63, 64, 65 and 138
+    moves, where cached and uncached positions lie side by side in one tree, are the same games with the cache on and off."""
+    from matrix0_amd.backend import M0Backend
+    from oracle import chess_py as ch
+    from tests import rules_cases as rc
+    openings = [rc.WAVE_EDGE[63], rc.WAVE_EDGE[64], rc.WAVE_EDGE[65], rc.WIDE_138]
+    assert [len(ch.Board(f).legal_moves) for f in openings] == [63, 64, 65, 138]
+    assert not any(ch.Board(f).is_game_over() for f in openings)
+    # seed 117: the book draws of games 0..7 (the first number of each game's stream) put two games on every position
+    cfg = dict(CFG, seed=117, selfplay=dict(CFG["selfplay"], opening_random_plies=0, max_game_len=12))
+    be = M0Backend.from_state_dict(NET, net_ref.random_state_dict(NET, seed=9))
+    off, st_off = _play(be, False, cfg, openings)
+    on, st_on = _play(be, True, cfg, openings)
+    be.close()
+    assert sorted(off) == sorted(on) == list(range(8))
+    assert {off[i]["start_fen"] for i in range(8)} == set(openings)       # the draw of the book put a game on every one
+    for i in range(8):
+        a, b = off[i], on[i]
+        assert a["start_fen"] == b["start_fen"] and a["played"] == b["played"] and a["result"] == b["result"], i
+        for k in ("pi", "z", "s", "legal_mask", "search_values"):
+            assert np.array_equal(a[k], b[k]), (i, k)
+    print(f"eval cache [63/64/65/138-move roots]: {int(st_on['evals_cached'])} of {int(st_off['evals'])} leaf evaluations served "
+          f"from the cache, {int(st_off['plies'])} plies")
+    assert st_off["evals_cached"] == 0 and st_on["evals_cached"] > 0
+    assert st_on["sims"] == st_off["sims"] and st_on["plies"] == st_off["plies"]
+    assert st_on["evals"] + st_on["evals_cached"] == st_off["evals"]
 
 
 def test_cache_is_off_where_the_payload_cannot_serve_the_expansion():

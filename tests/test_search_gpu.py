@@ -8,7 +8,9 @@ import pytest
 
 from oracle import chess_py as ch
 from oracle import mcts_ref as ref
+from tests import rules_cases as rc
 from tests.fake_net import FakeNet
+from tests.hash_net import HashNet
 
 pytestmark = pytest.mark.gpu
 
@@ -25,11 +27,11 @@ FENS = [ch.START_FEN,
         "7k/5Q2/5K2/8/8/8/8/8 w - - 0 1"]               # stalemate / mate leaves near the root
 
 
-def _engine(G, L, sims, vl_active=True, legal_softmax=True, noise=True):
+def _engine(G, L, sims, vl_active=True, legal_softmax=True, noise=True, mcts=None, compat=None):
     from matrix0_amd import engine as eng
-    m = dict(MCTS, inference_batch_size=L, legal_softmax=legal_softmax, enable_entropy_noise=noise)
+    m = dict(MCTS, inference_batch_size=L, legal_softmax=legal_softmax, enable_entropy_noise=noise, **(mcts or {}))
     cfg = eng.selfplay_cfg_from_dict({"seed": 1234, "mcts": m, "selfplay": {"num_simulations": sims}},
-                                     concurrent_games=G, virtual_loss_active=vl_active)
+                                     concurrent_games=G, virtual_loss_active=vl_active, compat=compat)
     return eng.SelfplayEngine(None, cfg), m
 
 
@@ -45,9 +47,9 @@ def _run_engine_search(e, net, G):
     return [e.search_result(g) for g in range(G)]
 
 
-def _oracle(fen, uid, sims, L, net, m, vl_active, dirichlet, ply=0, numerics="engine"):
-    cfg = ref.MCTSConfig.from_dict(dict(m, use_tt=False, virtual_loss_active=vl_active, inference_batch_size=L,
-                                        dirichlet_plies=(30 if dirichlet else 0), numerics=numerics))
+def _oracle(fen, uid, sims, L, net, m, vl_active, dirichlet, ply=0, numerics="engine", **switches):
+    cfg = ref.MCTSConfig.from_dict({**dict(m, use_tt=False, virtual_loss_active=vl_active, inference_batch_size=L,
+                                           dirichlet_plies=(30 if dirichlet else 0), numerics=numerics), **switches})
     o = ref.MCTS(cfg, net.infer_np, seed=1234, game=uid)
     b = ch.Board(fen)
     vc, pi, rq = o.run(b, num_simulations=sims, ply=ply)
@@ -155,15 +157,17 @@ def test_tree_reuse_across_moves_matches_oracle():
 def test_expand_priors_vs_reference_numerics(sharp, legal_softmax):
     """Node._expand priors from the HIP kernel vs the reference-faithful float32 path (torch.softmax, numpy
     float32 sums): tolerance 1e-6 absolute, the bound tests/test_mcts_logits.py uses."""
-    G = len(FENS)
+    fens = FENS + [rc.WIDE_218, rc.WIDE_218_B, rc.WAVE_EDGE[129]]         # and move lists of four and of three rounds of 64
+    G = len(fens)
     e, m = _engine(G, 4, 1, legal_softmax=legal_softmax)
     net = FakeNet(seed=11, sharp=sharp)
-    for g, fen in enumerate(FENS):
+    for g, fen in enumerate(fens):
         e.search_begin(g, fen, 1, False, 300 + g)
     results = _run_engine_search(e, net, G)
-    for g, fen in enumerate(FENS):
+    for g, fen in enumerate(fens):
         b = ch.Board(fen)
         moves, idxs = ch.legal_moves_with_indices(b)
+        assert len(results[g]["prior"]) == len(moves)
         lg, _ = FakeNet(seed=11, sharp=sharp).infer_np(ch.encode_board(b)[None])
         noise = ref.Stream(ref.derive_seed(1234, 300 + g, ref.PURPOSE_NOISE))
         want = ref.legal_priors(lg[0], idxs, legal_softmax, True, noise, numerics="reference")
@@ -198,3 +202,138 @@ def test_pruning_config_is_validated():
         eng.selfplay_cfg_from_dict({"mcts": {"max_children": 1000}}, concurrent_games=1)
     with pytest.raises(ValueError, match="compat"):
         eng.selfplay_cfg_from_dict({}, concurrent_games=1, compat={"no_such_switch": True})
+
+
+# ---- nodes wider than one wave of 64 lanes: 218 and 138 legal moves at the root, well over a hundred two plies below it ----
+WIDE = [rc.WIDE_218, rc.WIDE_138]
+WIDE_SIMS, WIDE_L = 300, 16
+
+
+class _ShiftedNet:
+    """HashNet with a constant added to every logit: the raw-prior branch divides the legal logits by their sum, so the sign
+    of that sum decides between the division and the uniform fallback."""
+
+    def __init__(self, shift, **kw):
+        self.net, self.shift = HashNet(**kw), np.float32(shift)
+
+    def infer_np(self, planes):
+        lg, v = self.net.infer_np(planes)
+        return lg + self.shift, v
+
+
+def _tree(root):
+    """Every node below an oracle root once (with the position table the children are shared)."""
+    seen, stack, out = {id(root)}, [root], []
+    while stack:
+        node = stack.pop()
+        out.append(node)
+        for c in node.children.values():
+            if id(c) not in seen:
+                seen.add(id(c))
+                stack.append(c)
+    return out
+
+
+def _widest_below(root):
+    return max((len(n.children) for n in _tree(root) if n is not root), default=0)
+
+
+def _wide_searches(make_net, reached, *, vl_active=True, legal_softmax=True, mcts=None, compat=None, **switches):
+    """One search per WIDE root, 300 simulations in batches of 16 with Dirichlet noise.  The oracle runs first and `reached`, asked
+    of its tree of the 218-move root, says whether the search got to the shape the case is about: a case that did not fails."""
+    G = len(WIDE)
+    e, m = _engine(G, WIDE_L, WIDE_SIMS, vl_active=vl_active, legal_softmax=legal_softmax, mcts=mcts, compat=compat)
+    want = [_oracle(fen, 700 + g, WIDE_SIMS, WIDE_L, make_net(), m, vl_active, True, **switches) for g, fen in enumerate(WIDE)]
+    assert reached(want[0][0]._last_root), "the oracle's tree never reached the shape this case is about"
+    for g, fen in enumerate(WIDE):
+        e.search_begin(g, fen, WIDE_SIMS, True, 700 + g)
+    results = _run_engine_search(e, make_net(), G)
+    for g in range(G):
+        o, b, vc, pi, rq = want[g]
+        _compare(results[g], o, vc, rq)
+    return results, want
+
+
+def _wide_root_and_below(root):
+    return len(root.children) == 218 and _widest_below(root) > 128
+
+
+def test_wide_nodes_full_softmax_with_entropy_noise():
+    _wide_searches(lambda: HashNet(seed=31, sharp=6.0), _wide_root_and_below, legal_softmax=False)
+
+
+@pytest.mark.parametrize("shift", [1.5, -1.5])
+def test_wide_nodes_raw_legal_priors(shift):
+    """Legal logits over their sum below the root.  +1.5: every logit is positive, the float32 sum of more than 128 of them is
+    the pairwise one; -1.5: every sum is negative, the priors are uniform."""
+    net = lambda: _ShiftedNet(shift, seed=32, sharp=2.0)                  # noqa: E731  logits in shift +- 1
+    results, want = _wide_searches(net, _wide_root_and_below, compat={"raw_legal_priors": True}, raw_legal_priors=True)
+    wide = [n for n in _tree(want[0][0]._last_root) if n.parent is not None and len(n.children) > 128]
+    for n in wide:
+        pr = np.array([c.prior for c in n.children.values()])
+        assert (len(set(pr.tolist())) == 1) == (shift < 0)                 # uniform exactly where the sum is not positive
+
+
+def test_wide_nodes_pruned_children():
+    """MCTS._prune_children on lists of up to 218: the root keeps its 80 best, nodes below keep between 65 and 128."""
+    def reached(root):
+        kept = [len(n.children) for n in _tree(root) if n is not root]
+        return len(root.children) == 80 and any(64 < k <= 128 for k in kept)
+    results, _ = _wide_searches(lambda: HashNet(seed=33, sharp=6.0), reached, mcts={"max_children": 80, "min_child_prior": 0.002})
+    assert len(results[0]["n"]) == 80
+
+
+def test_wide_nodes_in_the_position_table():
+    _wide_searches(lambda: HashNet(seed=34, sharp=6.0), _wide_root_and_below, compat={"tt_merge": True}, use_tt=True)
+
+
+def test_wide_nodes_without_virtual_loss():
+    _wide_searches(lambda: HashNet(seed=35, sharp=6.0), _wide_root_and_below, vl_active=False)
+
+
+def _highest_visited_slot_that_goes_on(board, visits):
+    """The last root child with a visit whose move does not end the game (many of the queens' moves mate or stalemate): after
+    one that does there is nothing left to search."""
+    for slot in range(len(visits) - 1, -1, -1):
+        mv, n = visits[slot]
+        if n > 0:
+            board.push(mv)
+            over = board.is_game_over()
+            board.pop()
+            if not over:
+                return slot
+    raise AssertionError("every visited move ends the game")
+
+
+def test_tree_reuse_through_a_child_slot_past_the_first_wave():
+    """As test_tree_reuse_across_moves_matches_oracle, on the wide roots: the first move played is the visited root child with the
+    highest slot among those that do not end the game, which lies beyond slot 63; the searches of the next two plies start from
+    its subtree."""
+    G, L, sims = len(WIDE), WIDE_L, WIDE_SIMS
+    e, m = _engine(G, L, sims)
+    net = HashNet(seed=36, sharp=6.0)
+    oracles = []
+    for g, fen in enumerate(WIDE):
+        e.search_begin(g, fen, sims, True, 760 + g)
+        cfg = ref.MCTSConfig.from_dict(dict(m, use_tt=False, virtual_loss_active=True, inference_batch_size=L, numerics="engine"))
+        oracles.append((ref.MCTS(cfg, HashNet(seed=36, sharp=6.0).infer_np, seed=1234, game=760 + g), ch.Board(fen)))
+    for ply in range(3):
+        results = _run_engine_search(e, net, G)
+        for g in range(G):
+            o, b = oracles[g]
+            vc, pi, rq = o.run(b, num_simulations=sims, ply=ply)
+            _compare(results[g], o, vc, rq)
+            if ply == 2:
+                assert len(vc) > 128                                     # the third search stands on a wide node again
+                continue
+            n = results[g]["n"]
+            if ply == 0:
+                slot = _highest_visited_slot_that_goes_on(b, list(vc.items()))
+                assert slot >= 64 and n[slot] > 0, slot
+            else:
+                slot = int(np.argmax(n))
+            mv = ch.Move.from_uci(results[g]["moves"][slot])
+            o.note_move_played(mv)
+            b.push(mv)
+            assert not b.is_game_over()
+            e.search_advance(g, slot, sims, True)
