@@ -111,6 +111,10 @@ class ScoreOpts(C.Structure):
     _fields_ = [("mask_mode", i32), ("label_smoothing", f32), ("value_loss", i32), ("huber_delta", f32)]
 
 
+class GumbelCfg(C.Structure):
+    _fields_ = [("max_considered", i32), ("c_visit", f64), ("c_scale", f64)]
+
+
 STRUCTS = {"m0_net_cfg": NetCfg, "m0_selfplay_cfg": SelfplayCfg, "m0_selfplay_stats": SelfplayStats,
            "m0_game_record": GameRecord, "m0_analysis_opts": AnalysisOpts, "m0_analysis_line": AnalysisLine,
            "m0_analysis_result": AnalysisResult}
@@ -240,12 +244,23 @@ SCORE_FUNCTIONS = {
     "m0_score_bench": (i32, [i32, i32, i32, P(f32), P(f64)]),
 }
 
+# ---- include/m0_gumbel.h (which m0_engine.h includes too): the Gumbel root search, in that header's order;
+# tests/test_abi_gumbel.py compares the two ----
+GUMBEL_STRUCTS = {"m0_gumbel_cfg": GumbelCfg}
+GUMBEL_FUNCTIONS = {
+    "m0_selfplay_set_gumbel": (i32, [vp, P(GumbelCfg)]),
+    "m0_search_gumbel_result": (i32, [vp, i32, _pi32, P(f64), vp, vp, _pi32]),
+    "m0_gumbel_schedule": (i32, [i32, i32, vp, vp]),
+    "m0_gumbel_improve": (i32, [i32, vp, vp, vp, vp, f64, P(GumbelCfg), vp, P(f64), _pi32]),
+}
+
 
 def bind(L) -> list:
-    """Set restype and argtypes of every function of FUNCTIONS, LIVE_FUNCTIONS and SCORE_FUNCTIONS on the loaded library; the
-    names it does not export."""
+    """Set restype and argtypes of every function of FUNCTIONS, LIVE_FUNCTIONS, SCORE_FUNCTIONS and GUMBEL_FUNCTIONS on the loaded
+    library; the names it does not export."""
     missing = []
-    for name, (restype, argtypes) in list(FUNCTIONS.items()) + list(LIVE_FUNCTIONS.items()) + list(SCORE_FUNCTIONS.items()):
+    for name, (restype, argtypes) in (list(FUNCTIONS.items()) + list(LIVE_FUNCTIONS.items()) + list(SCORE_FUNCTIONS.items()) +
+                                      list(GUMBEL_FUNCTIONS.items())):
         fn = getattr(L, name, None)
         if fn is None:
             missing.append(name)

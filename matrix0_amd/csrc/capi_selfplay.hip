@@ -17,6 +17,8 @@ static void fill_tree_cfg(const m0_selfplay_cfg& c, bool match, TreeCfg& t) {
     t.virtual_loss_active = c.virtual_loss_active; t.leaves_per_step = c.inference_batch_size;
     t.tt_merge = c.tt_merge; t.raw_legal_priors = c.raw_legal_priors; t.max_children = c.max_children;
     t.min_child_prior = c.min_child_prior;
+    t.gumbel = 0;                          // m0_selfplay_set_gumbel turns it on
+    t.gumbel_cfg = m0_gumbel_cfg{0, 0.0, 0.0};
     // the cached payload is the LEGAL logits: only the legal-softmax expansion can be served from it
     t.eval_cache = ((match ? c.arena_eval_cache : c.eval_cache) && c.legal_softmax && !c.raw_legal_priors && !c.tt_merge) ? 1 : 0;
 }
@@ -367,6 +369,7 @@ int m0_search_begin(m0_selfplay* sp, int g, const char* fen, int sims, int diric
     if (parse_fen(fen, line.pos) != 0) { m0_set_error("bad FEN"); return M0_ERR_INVALID; }
     if (!sync_games_d2h(sp)) return m0_hip_error(sp->hip, "device sync failed");
     occupy_slot(sp, g, std::move(line), game_uid);
+    sp->search_begun = true;
     begin_search(sp, g, sims, dirichlet != 0, ROOT_FRESH);
     return apply_advances(sp);
 }
@@ -430,7 +433,7 @@ int m0_search_advance(m0_selfplay* sp, int g, int slot, int sims, int dirichlet)
     const RootResult& R = sp->hres[g];
     if (slot < 0 || slot >= R.nchild) { m0_set_error("child slot out of range"); return M0_ERR_INVALID; }
     sp->games[g].play(R.child_mv[slot]);
-    const bool fresh = sp->cfg.fresh_tree_per_move || sp->cfg.tt_merge;
+    const bool fresh = sp->cfg.fresh_tree_per_move || sp->cfg.tt_merge || sp->tc.gumbel;
     begin_search(sp, g, sims, dirichlet != 0, fresh ? ROOT_FRESH : slot);
     return apply_advances(sp);
 }

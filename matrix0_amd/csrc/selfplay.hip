@@ -29,7 +29,9 @@ static void seed_game_dev(GameDev& g, uint64_t base, int uid) {
     g.seed_jitter = derive_seed(base, uid, PURPOSE_JITTER);
     g.seed_noise = derive_seed(base, uid, PURPOSE_NOISE);
     g.seed_dir = derive_seed(base, uid, PURPOSE_DIRICHLET);
-    g.ctr_jitter = g.ctr_noise = g.ctr_dir = 0;
+    g.seed_gumbel = derive_seed(base, uid, PURPOSE_GUMBEL);
+    g.ctr_jitter = g.ctr_noise = g.ctr_dir = g.ctr_gumbel = 0;
+    g.gumbel_miss = 0;
 }
 
 bool sync_games_d2h(m0_selfplay* sp) {
@@ -52,7 +54,8 @@ static void arm_search(m0_selfplay* sp, int slot, const Pos& pos, const RepWindo
     GameDev& g = sp->hg[slot];
     g.root_pos = pos;
     g.active = 1; g.sims_done = 0; g.sims_target = sims;
-    g.need_dirichlet = dirichlet ? 1 : 0;
+    g.need_dirichlet = dirichlet && !sp->tc.gumbel ? 1 : 0;     // the Gumbel root takes no Dirichlet noise
+    g.gumbel_drawn = 0;
     g.root_q_from_v = 0;
     g.root_fresh = fresh ? 1 : 0;
     g.flip_root_v = (sp->cfg.value_from_white && pos.turn == BLACK) ? 1 : 0;
@@ -161,6 +164,7 @@ static void begin_move(m0_selfplay* sp, int slot, int child_slot) {
     int sims = playout_cap(c.num_simulations, c.playout_random_frac, cap_draws ? hgm.rng.next() : 0.0);
     hgm.cur_sims = sims;
     if (c.fresh_tree_per_move || c.tt_merge) root = ROOT_FRESH;   // tt_merge: the table lives for one search (see m0_engine.h)
+    if (sp->tc.gumbel) root = ROOT_FRESH;                          // the halving schedule assumes unvisited root children
     // ... except in a match engine, where each side's table lives for the whole game
     if (match && c.tt_merge) root = hgm.nstates == 0 ? ROOT_FIRST_OF_GAME : ROOT_FROM_SIDE_TABLE;
     const bool dir = c.dirichlet_plies < 0 || hgm.nstates < c.dirichlet_plies;
@@ -220,12 +224,15 @@ static void finish_search(m0_selfplay* sp, int slot) {
         return;
     }
     const double root_q = R.root_n > 0 ? R.root_q : g.root_v;
-    // policy target (mcts.py:828-837)
+    // Gumbel root search: the target is the improved policy and the move is the search's own pick (include/m0_gumbel.h)
+    const GumbelResult* GR = sp->tc.gumbel ? &sp->hgres[slot] : nullptr;
+    // a child's share of the policy target as recorded (mcts.py:828-837: visits over their sum)
+    auto target = [&](int i) { return GR ? (float)GR->pi[i] : (float)((double)R.child_n[i] / (double)total); };
     const size_t T = (size_t)hgm.nstates;
     if (c.record_games) {
         hgm.pis.resize((T + 1) * 4672, 0.f);
         float* pi = hgm.pis.data() + T * 4672;
-        for (int i = 0; i < k; ++i) pi[R.child_idx[i]] = (float)((double)R.child_n[i] / (double)total);
+        for (int i = 0; i < k; ++i) pi[R.child_idx[i]] = target(i);
         hgm.states.resize((T + 1) * 19 * 64);
         encode_planes_f32(hgm.pos, hgm.states.data() + T * 19 * 64);
         if (c.ssl_targets) hgm.rec_pos.push_back(hgm.pos);
@@ -243,7 +250,7 @@ static void finish_search(m0_selfplay* sp, int slot) {
     {
         double ent = 0.0;
         for (int i = 0; i < k; ++i) {
-            double p = (double)(float)((double)R.child_n[i] / (double)total);
+            double p = (double)target(i);
             if (p < 1e-12) p = 1e-12;
             ent -= p * log(p);
         }
@@ -257,7 +264,9 @@ static void finish_search(m0_selfplay* sp, int slot) {
     if (c.low_visit_threshold > 0 && maxv < c.low_visit_threshold && temp < 0.8) temp = 0.8;
     std::vector<int32_t> visits(R.child_n, R.child_n + k);
     int pick;
-    if (sp->kind == EngineKind::Match) {       // arena.py:73-106 (the uniform is drawn only on the sampling branch, as np.random.choice is)
+    if (GR) {                                  // no temperature, no low_visit_threshold: the Gumbel draw is the sampling
+        pick = GR->pick >= 0 && GR->pick < k ? GR->pick : 0;
+    } else if (sp->kind == EngineKind::Match) {       // arena.py:73-106 (the uniform is drawn only on the sampling branch, as np.random.choice is)
         const bool sampling = c.arena_temp > 1e-3 && hgm.nstates < c.arena_temp_plies;
         pick = arena_choose_move(visits.data(), k, c.arena_temp, hgm.nstates, c.arena_temp_plies, sampling ? hgm.rng.next() : 0.0);
     } else {
@@ -367,6 +376,8 @@ int refill(m0_selfplay* sp) {
 // The searches that the last expand finished become moves; games end, free slots start the next ones.
 static int harvest_games(m0_selfplay* sp) {
     if (!M0_HIP(sp->hip, hipMemcpy(sp->hres.data(), sp->d.results, sizeof(RootResult) * sp->G, hipMemcpyDeviceToHost)))
+        return m0_hip_error(sp->hip, "harvest failed");
+    if (sp->tc.gumbel && !M0_HIP(sp->hip, hipMemcpy(sp->hgres.data(), sp->d.gumbel_results, sizeof(GumbelResult) * sp->G, hipMemcpyDeviceToHost)))
         return m0_hip_error(sp->hip, "harvest failed");
     for (int s = 0; s < sp->G; ++s) {
         if (!(sp->hg[s].active && sp->hg[s].finished)) continue;

@@ -154,6 +154,9 @@ struct m0_selfplay {
                                           // m0_selfplay_set_search_tablebase), for a submitted root (analysis engines)
     int tb_max_pieces = 0;                // ... for positions with at most this many men (d.tb_set: the probe inside the search)
     uint64_t tb_adjudications = 0;        // games it ended
+    // Gumbel root search (m0_selfplay_set_gumbel; the switch itself is tc.gumbel)
+    std::vector<GumbelResult> hgres;      // host copies of d.gumbel_results, beside hres
+    bool search_begun = false;            // m0_search_begin was called: the mode can no longer be set
 };
 
 namespace m0 {
@@ -182,7 +185,8 @@ inline bool hip_ok(m0_selfplay* sp, const char* context) {
 //
 //   call                                                            accepted by
 //   m0_selfplay_step, _poll, _set_openings                          self-play, match
-//   m0_selfplay_ext_select, _ext_expand, m0_selfplay_set_tablebase  self-play
+//   m0_selfplay_ext_select, _ext_expand, m0_selfplay_set_tablebase,
+//   m0_selfplay_set_gumbel, m0_search_gumbel_result                 self-play
 //   m0_arena_ext_select, _ext_expand                                match
 //   m0_search_*                                                     self-play, match (a match engine is accepted as it always
 //                                                                   was, although nothing drives one this way)

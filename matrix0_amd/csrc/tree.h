@@ -9,10 +9,12 @@
 namespace m0 { struct TbSet; }   // tb_core.h
 // deliberate: the C ABI already fixes M0_POLICY_SIZE (logits per batch row) and M0_PLANES (input planes); one definition
 #include "../../include/m0_engine.h"
+#include "gumbel_core.h"
 
 #define M0_MAX_DEPTH 256      // path length cap (nodes)
 #define M0_HIST_CAP 192       // reversible-move history window (<= 150 by the 75-move rule)
 #define M0_MAX_CHILDREN 256
+static_assert(M0_MAX_CHILDREN == m0::M0_GUMBEL_MAX_K, "gumbel_core.h and include/m0_gumbel.h count on 256 root children at most");
 constexpr int M0_NHWC_C = 32;          // channel stride of the fp16 NHWC network input (M0_PLANES used, the rest zero)
 
 struct TreeCfg {              // MCTSConfig fields the kernels read (mcts.py:61-107)
@@ -38,6 +40,10 @@ struct TreeCfg {              // MCTSConfig fields the kernels read (mcts.py:61-
     double min_child_prior;
     int eval_cache;           // 1: leaf evaluations are looked up in / stored to the game's evaluation cache (EvalCache) and a leaf
                               //    reached twice in one pass shares one batch row
+    // Gumbel root search (m0_selfplay_set_gumbel, include/m0_gumbel.h): read by the Gumbel instantiation of select_kernel
+    // and by expand_kernel when a search finishes
+    int gumbel;               // 1: the root level is sequential halving over Gumbel scores (tree_gumbel.h)
+    m0_gumbel_cfg gumbel_cfg;
 };
 
 // Per-game evaluation cache: what the network said about a position (value + the logits of its legal moves, in generation
@@ -91,6 +97,11 @@ struct GameDev {
     int side_next[2];         // bump allocator of each side's half while the other side searches
     int root_found;           // advance_kernel: this search's root was found in the side's table (mcts.py:343, 359-371)
     uint64_t tb_leaves;       // leaves that select_kernel took from the endgame tablebases (TreeDev::tb_set), counted by lane 0
+    // Gumbel root search: the game's stream (k draws per search), whether this search has drawn, and how often no root child
+    // had the scheduled visit count (0 with a correct schedule)
+    uint64_t seed_gumbel, ctr_gumbel;
+    int gumbel_drawn;
+    int gumbel_miss;
 };
 
 enum SampleKind : int {
@@ -143,6 +154,13 @@ struct RootResult {           // written when a search finishes
     double child_q[M0_MAX_CHILDREN];
 };
 
+struct GumbelResult {         // Gumbel root search: written beside RootResult when a search finishes
+    int pick;                 // the move: index into RootResult's children
+    double v_mix;
+    double pi[M0_MAX_CHILDREN];   // improved policy over the root children
+    double gl[M0_MAX_CHILDREN];   // g + log(prior) of this search
+};
+
 struct TreeDev {
     TreeArrays t;
     GameDev* games;           // [G]
@@ -169,6 +187,8 @@ struct TreeDev {
     int L;
     const m0::TbSet* tb_set;  // endgame tablebases in device memory (m0_selfplay_set_search_tablebase); null = leaves are not probed
     int tb_max_pieces;        // ... for leaves with at most this many men
+    double* gumbel_gl;        // Gumbel root search: [G][M0_MAX_CHILDREN] g + log(prior) of the running search; null = mode off
+    GumbelResult* gumbel_results;   // [G]
 };
 
 hipError_t launch_select(const TreeDev& d, const TreeCfg& c, hipStream_t st);

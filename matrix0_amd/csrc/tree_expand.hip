@@ -2,6 +2,7 @@
 // (mcts.py:135-225), pruning, child block allocation, backup (mcts.py:946-953), evaluation-cache fill, virtual-loss
 // release, root result extraction.  The legal moves of every leaf come from select_kernel (TreeDev::leaf_moves).
 #include "tree_device.h"
+#include "tree_gumbel.h"
 #include "eval_cache.h"
 
 struct ExpandScratch {          // workgroup-shared staging of one expansion (raw priors / pruning only)
@@ -393,6 +394,7 @@ __global__ __launch_bounds__(64) void expand_kernel(TreeDev d, TreeCfg c) {
         gd->root_q = A.q[root];
     }
     if (fin) write_root_result(d.results + g, A, root, lane);
+    if (fin && c.gumbel) write_gumbel_result(d, c, A, gd, g, root, lane);   // beside it: the move and the improved policy
 }
 
 hipError_t launch_expand(const TreeDev& d, const TreeCfg& c, hipStream_t st) {

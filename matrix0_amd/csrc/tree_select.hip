@@ -6,6 +6,7 @@
 // terminal leaf with the table's value.  A position with a castling right left is no hit; the half-move clock is ignored,
 // as in adjudication (tb_core.h, tb_probe).
 #include "tree_device.h"
+#include "tree_gumbel.h"
 #include "tb_core.h"
 #include "eval_cache.h"
 #include "movegen_wave.h"
@@ -169,6 +170,11 @@ static_assert(sizeof(TopCache) == M0_SEL_CACHE_BYTES, "32 bytes of select fields
 // select_kernel measured 25 us (1.5 %) slower per call.
 #define TOP(f, hit, i) ((hit) ? TC->f[i] : A.f[i])
 
+// GUMBEL: the instantiation for the Gumbel root search (TreeCfg::gumbel, tree_gumbel.h).  Only the root level differs: no
+// Dirichlet noise, a pass that ends at the phase boundary of the halving schedule, and at depth 0 the pick by scheduled visit
+// count and Gumbel score in place of the PUCT scan (no jitter draw there).  A template parameter, not a field read in the scan:
+// the PUCT instantiation is the kernel it was.
+template <bool GUMBEL>
 __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
     extern __shared__ __attribute__((aligned(16))) char sel_cache[];
     TopCache* const TC = reinterpret_cast<TopCache*>(sel_cache);
@@ -191,12 +197,20 @@ __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
     const bool reinfer = gd->reinfer != 0;
 
     if (A.nch[root] < 0) { emit_root_init(d, gd, S, P, LM, root, reinfer, smoves, spseudo, lane); return; }
-    if (gd->need_dirichlet) {
+    if constexpr (GUMBEL) {
+        if (lane == 0) gd->need_dirichlet = 0;
+    } else if (gd->need_dirichlet) {
         apply_dirichlet(A, root, gd, c, sg, lane);
         if (lane == 0) gd->need_dirichlet = 0;
     }
     int nleaf = gd->sims_target - gd->sims_done;
     if (nleaf > d.L) nleaf = d.L;
+    // Gumbel: the pass ends with the phase of the halving schedule, where the next phase needs this one's values
+    const int g_done = gd->sims_done, g_n = gd->sims_target;
+    const int g_m = GUMBEL ? gumbel_m_eff(c.gumbel_cfg.max_considered, A.nch[root]) : 0;
+    if constexpr (GUMBEL) {
+        if (nleaf > 0) { const int left = gumbel_phase_end(g_m, g_n, g_done) - g_done; if (nleaf > left) nleaf = left; }
+    }
     if (nleaf < 0) nleaf = 0;
     // the top of the tree -> LDS (after the Dirichlet noise, which rewrites the root's priors)
     int ncached = 0;
@@ -207,6 +221,12 @@ __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
             TC->nch[i] = A.nch[i]; TC->mv[i] = A.mv[i];
         }
         __syncthreads();
+    }
+    int* gcnt = nullptr;                                   // Gumbel: the root children's visit counts as the pass goes
+    if constexpr (GUMBEL) {
+        __shared__ int gumbel_cnt[M0_MAX_CHILDREN];
+        gcnt = gumbel_cnt;
+        if (nleaf > 0) gumbel_pass_prologue(d, c, A, gd, g, root, sg, gcnt, lane);
     }
     uint64_t ctrj = gd->ctr_jitter;
     const uint64_t seedj = gd->seed_jitter;
@@ -235,31 +255,42 @@ __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
             int b_nch = 0, b_cb = 0, b_n = 0, b_vl = 0;
             double b_q = 0.0;
             Move b_mv = 0;
-            for (int i = lane; i < nc; i += 64) {
-                const int ci = cb + i;
-                const bool hit = ci < ncached;                  // the children of a node are one block: all lanes agree but at the edge
-                const int cn = TOP(n, hit, ci);
-                const double cq = TOP(q, hit, ci);
-                const int c_nch = TOP(nch, hit, ci), c_cb = TOP(cbase, hit, ci);
-                const Move m = TOP(mv, hit, ci);
-                const double cprior = TOP(prior, hit, ci);
-                const double qq = cn == 0 ? nq - c.fpu_reduction : cq;
-                const double u = eff * cprior * (sq / (1.0 + (double)cn));
-                double sc = qq + u;
-                if (c.no_instant_backtrack && depth >= 1) {
-                    if (mv_from(m) == prev_to && mv_to(m) == prev_from) sc -= 0.01;
+            bool root_rule = false;
+            if constexpr (GUMBEL) root_rule = depth == 0;
+            if (root_rule) {
+                // every lane loads the picked child's fields: the broadcast below then reads them from any lane
+                bi = gumbel_pick_child(gd, sg, gcnt, nc, gumbel_considered(g_m, g_n, g_done + s), lane);
+                const int ci = cb + bi;
+                const bool hit = ci < ncached;
+                b_n = TOP(n, hit, ci); b_q = TOP(q, hit, ci); b_nch = TOP(nch, hit, ci); b_cb = TOP(cbase, hit, ci);
+                b_mv = TOP(mv, hit, ci); b_vl = c.virtual_loss_active ? TOP(vl, hit, ci) : 0;
+            } else {
+                for (int i = lane; i < nc; i += 64) {
+                    const int ci = cb + i;
+                    const bool hit = ci < ncached;                  // the children of a node are one block: all lanes agree but at the edge
+                    const int cn = TOP(n, hit, ci);
+                    const double cq = TOP(q, hit, ci);
+                    const int c_nch = TOP(nch, hit, ci), c_cb = TOP(cbase, hit, ci);
+                    const Move m = TOP(mv, hit, ci);
+                    const double cprior = TOP(prior, hit, ci);
+                    const double qq = cn == 0 ? nq - c.fpu_reduction : cq;
+                    const double u = eff * cprior * (sq / (1.0 + (double)cn));
+                    double sc = qq + u;
+                    if (c.no_instant_backtrack && depth >= 1) {
+                        if (mv_from(m) == prev_to && mv_to(m) == prev_from) sc -= 0.01;
+                    }
+                    const int cvl = c.virtual_loss_active ? TOP(vl, hit, ci) : 0;
+                    if (c.virtual_loss_active && c.virtual_loss > 0.0) sc -= (double)cvl * c.virtual_loss;
+                    sc += (u01(seedj, ctrj + (uint64_t)i) - 0.5) * jit;
+                    if (sc > best) { best = sc; bi = i; b_nch = c_nch; b_cb = c_cb; b_n = cn; b_q = cq; b_mv = m; b_vl = cvl; }
                 }
-                const int cvl = c.virtual_loss_active ? TOP(vl, hit, ci) : 0;
-                if (c.virtual_loss_active && c.virtual_loss > 0.0) sc -= (double)cvl * c.virtual_loss;
-                sc += (u01(seedj, ctrj + (uint64_t)i) - 0.5) * jit;
-                if (sc > best) { best = sc; bi = i; b_nch = c_nch; b_cb = c_cb; b_n = cn; b_q = cq; b_mv = m; b_vl = cvl; }
+                for (int off = 32; off > 0; off >>= 1) {
+                    const double ob = __shfl_xor(best, off);
+                    const int oi = __shfl_xor(bi, off);
+                    if (oi >= 0 && (bi < 0 || ob > best || (ob == best && oi < bi))) { best = ob; bi = oi; }
+                }
+                ctrj += (uint64_t)nc;
             }
-            for (int off = 32; off > 0; off >>= 1) {
-                const double ob = __shfl_xor(best, off);
-                const int oi = __shfl_xor(bi, off);
-                if (oi >= 0 && (bi < 0 || ob > best || (ob == best && oi < bi))) { best = ob; bi = oi; }
-            }
-            ctrj += (uint64_t)nc;
             if (bi < 0) bi = 0;
             const int child = cb + bi;
             // the lane that scanned child bi (i = lane + 64 k) holds its fields iff its own best is bi
@@ -322,9 +353,14 @@ __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
 hipError_t launch_select(const TreeDev& d, const TreeCfg& c, hipStream_t st) {
     static DeviceOnce once;
     hipError_t e = once.run([] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(&select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, M0_SEL_CACHE_BYTES);
+        hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&select_kernel<false>),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, M0_SEL_CACHE_BYTES);
+        if (e1 != hipSuccess) return e1;
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(&select_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   M0_SEL_CACHE_BYTES);
     });
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(select_kernel, dim3(d.G), dim3(64), M0_SEL_CACHE_BYTES, st, d, c);
+    if (c.gumbel) hipLaunchKernelGGL(select_kernel<true>, dim3(d.G), dim3(64), M0_SEL_CACHE_BYTES, st, d, c);
+    else hipLaunchKernelGGL(select_kernel<false>, dim3(d.G), dim3(64), M0_SEL_CACHE_BYTES, st, d, c);
     return hipGetLastError();
 }

@@ -9,7 +9,7 @@ import numpy as np
 from . import _lib
 
 from ._abi import (AN_MAX_LINES, AN_MAX_PV, AnalysisLine, AnalysisOpts, AnalysisResult, GameRecord,  # noqa: F401
-                   SelfplayCfg, SelfplayStats)
+                   GumbelCfg, SelfplayCfg, SelfplayStats)
 from ._lib import ptr
 
 c_double, c_int = C.c_double, C.c_int
@@ -108,6 +108,39 @@ def selfplay_cfg_from_dict(cfg: dict, *, concurrent_games: int, total_games: int
     ts = ecfg.get("tail_split", False) if tail_split is None else tail_split
     c.tail_split = 2 if ts in ("halves", "half", 2) and ts is not True else int(bool(ts))
     return c
+
+
+GUMBEL_DEFAULTS = {"max_considered": 16, "c_visit": 50.0, "c_scale": 1.0}      # the paper's
+
+
+def gumbel_cfg_from_dict(cfg: dict) -> Optional[GumbelCfg]:
+    """`mcts.gumbel: {enabled, max_considered: 16, c_visit: 50.0, c_scale: 1.0}` of config.yaml as the library's struct (for
+    SelfplayEngine.set_gumbel); None without the block or with `enabled: false`.  A block that is present has to be right:
+    ValueError for anything but a mapping with a boolean `enabled`, for an unknown key, for a max_considered that is no integer
+    in 1..256, for a constant that is no finite number >= 0, and for the mode together with engine.compat.tt_merge."""
+    g = (cfg.get("mcts", {}) or {}).get("gumbel")
+    if g is None:
+        return None
+    if not isinstance(g, dict):
+        raise ValueError(f"mcts.gumbel must be a mapping, not {g!r}")
+    unknown = set(g) - {"enabled", *GUMBEL_DEFAULTS}
+    if unknown:
+        raise ValueError(f"unknown mcts.gumbel keys: {sorted(map(str, unknown))}")
+    if not isinstance(g.get("enabled"), bool):
+        raise ValueError("mcts.gumbel.enabled must be true or false")
+    v = dict(GUMBEL_DEFAULTS, **{k: x for k, x in g.items() if k != "enabled"})
+    m = v["max_considered"]
+    if isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= 256:
+        raise ValueError(f"mcts.gumbel.max_considered must be an integer in 1..256, not {m!r}")
+    for key in ("c_visit", "c_scale"):
+        x = v[key]
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not (0.0 <= float(x) < float("inf")):
+            raise ValueError(f"mcts.gumbel.{key} must be a finite number >= 0, not {x!r}")
+    if not g["enabled"]:
+        return None
+    if bool((((cfg.get("engine", {}) or {}).get("compat", {}) or {}).get("tt_merge", False))):
+        raise ValueError("mcts.gumbel does not go with engine.compat.tt_merge")
+    return GumbelCfg(int(m), float(v["c_visit"]), float(v["c_scale"]))
 
 
 def move_to_uci(m: int) -> str:
@@ -261,6 +294,26 @@ class SelfplayEngine:
         return {"finished": bool(fin.value), "n": cn[:k].copy(), "moves": [move_to_uci(int(x)) for x in mv[:k]],
                 "idx": idx[:k].copy(), "prior": pr[:k].copy(), "q": q[:k].copy(), "root_q": rq.value, "root_n": rn.value}
 
+    # ---- Gumbel root search (include/m0_gumbel.h)
+    def set_gumbel(self, gumbel: Optional[GumbelCfg] = None, *, max_considered: int = GUMBEL_DEFAULTS["max_considered"],
+                   c_visit: float = GUMBEL_DEFAULTS["c_visit"], c_scale: float = GUMBEL_DEFAULTS["c_scale"]) -> None:
+        """Turn the Gumbel root search on (a self-play engine, before the first step or search): `gumbel` as
+        gumbel_cfg_from_dict returns it, or the three numbers."""
+        g = gumbel if gumbel is not None else GumbelCfg(int(max_considered), float(c_visit), float(c_scale))
+        _lib.check(self._L.m0_selfplay_set_gumbel(self._h, C.byref(g)), "m0_selfplay_set_gumbel")
+        self.gumbel = g
+
+    def search_gumbel_result(self, g: int) -> dict:
+        """Beside search_result(g): `pick` (index into its children, -1 while the search runs), `v_mix`, `pi` and `gl` per root
+        child, and `miss` (0 unless the schedule found no child with the visit count it asked for)."""
+        k = c_int(0); pick = c_int(-1); miss = c_int(0); vm = c_double(0)
+        _lib.check(self._L.m0_search_result(self._h, g, C.byref(k), None, None, None, None, None, None, None, None),
+                   "m0_search_result")
+        pi, gl = np.zeros(256, np.float64), np.zeros(256, np.float64)
+        _lib.check(self._L.m0_search_gumbel_result(self._h, g, C.byref(pick), C.byref(vm), ptr(pi), ptr(gl), C.byref(miss)),
+                   "m0_search_gumbel_result")
+        return {"pick": pick.value, "v_mix": vm.value, "pi": pi[: k.value].copy(), "gl": gl[: k.value].copy(), "miss": miss.value}
+
     def search_advance(self, g: int, slot: int, sims: int, dirichlet: bool) -> None:
         _lib.check(self._L.m0_search_advance(self._h, g, slot, sims, int(dirichlet)), "m0_search_advance")
 
@@ -372,6 +425,30 @@ def sample_move_index(visits, temperature: float, u: float) -> int:
 
 def playout_cap(sims: int, frac: float, u: float) -> int:
     return int(_lib.lib().m0_playout_cap(int(sims), float(frac), float(u)))
+
+
+def gumbel_schedule(m_eff: int, n: int):
+    """(seq, phase_end), i32 [n] each: the visit count simulation s considers at the root and the first simulation after its
+    phase, for m_eff considered children and n simulations (include/m0_gumbel.h)."""
+    seq, end = np.zeros(int(n), np.int32), np.zeros(int(n), np.int32)
+    _lib.check(_lib.lib().m0_gumbel_schedule(int(m_eff), int(n), ptr(seq), ptr(end)), "m0_gumbel_schedule")
+    return seq, end
+
+
+def gumbel_improve(prior, q, n, gl, root_v: float, c_visit: float = GUMBEL_DEFAULTS["c_visit"],
+                   c_scale: float = GUMBEL_DEFAULTS["c_scale"]):
+    """(pi f64 [k], v_mix, pick) of a root's children from their prior, q, visits and gl (include/m0_gumbel.h)."""
+    pr, qq, gg = (np.ascontiguousarray(a, dtype=np.float64) for a in (prior, q, gl))
+    nn = np.ascontiguousarray(n, dtype=np.int32)
+    k = int(pr.shape[0])
+    if not (qq.shape == nn.shape == gg.shape == (k,)):
+        raise ValueError("prior, q, n and gl must have one entry per child")
+    pi = np.zeros(k, np.float64)
+    vm, pick = c_double(0), c_int(-1)
+    g = GumbelCfg(GUMBEL_DEFAULTS["max_considered"], float(c_visit), float(c_scale))
+    _lib.check(_lib.lib().m0_gumbel_improve(k, ptr(pr), ptr(qq), ptr(nn), ptr(gg), float(root_v), C.byref(g), ptr(pi),
+                                            C.byref(vm), C.byref(pick)), "m0_gumbel_improve")
+    return pi, vm.value, pick.value
 
 
 def temperature_for(fullmove: int, t_start: float, t_end: float, t_moves: int) -> float:

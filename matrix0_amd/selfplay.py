@@ -8,7 +8,7 @@ by orchestrator.py:494 and selfplay/__main__.py:68).  Same config dict, same que
 
 Instead of one game at a time with a Python MCTS, the games of this worker run concurrently on one MI355X inside
 libm0engine.so; `shared_memory_resource` (the reference's inference-server handle) is accepted and ignored: leaf
-batching happens in the engine.  New keys live under an `engine:` section only:
+batching happens in the engine.  New keys live under an `engine:` section:
     engine: {device_index: int, concurrent_games: int, leaves_per_step: int, virtual_loss_active: bool,
              first_game_index: int, compat: {fresh_tree_per_move, tt_merge, raw_legal_priors, root_reinfer},
              tablebase: {max_pieces: 3 | 4, cache: <path or null>, in_search: false | true}}
@@ -17,6 +17,9 @@ batching happens in the engine.  New keys live under an `engine:` section only:
 generated on the GPU (matrix0_amd/tablebase.py), or loaded from `cache`, and a game ends as soon as the position after a move
 is found in them.  With `in_search: true` the tables also live on the GPU and the search takes the exact value of every leaf
 found in them instead of a network evaluation.  `tablebases.enabled: true` is accepted only together with this key.
+
+The one new key outside `engine:` is `mcts.gumbel: {enabled, max_considered: 16, c_visit: 50.0, c_scale: 1.0}`: the Gumbel root
+search (sequential halving, improved-policy targets; engine.gumbel_cfg_from_dict) for small simulation budgets.
 
 The orchestrator hands the SAME cfg_dict to every worker (orchestrator.py:490-496), so what tells workers apart is
 proc_id alone: worker i runs on GPU  i % (visible MI355X)  and plays the global game indices [i*games, (i+1)*games) --
@@ -36,7 +39,7 @@ import numpy as np
 from . import encoding
 from .backend import M0Backend
 from .data_writer import ReplayShardWriter, SelfplayShardWriter
-from .engine import SelfplayEngine, SelfplayPool, selfplay_cfg_from_dict
+from .engine import SelfplayEngine, SelfplayPool, gumbel_cfg_from_dict, selfplay_cfg_from_dict
 from .pgn import START_FEN
 from .tablebase import Tablebase, probe_limit, tablebase_cfg
 from .weights import random_state_dict
@@ -130,6 +133,12 @@ def selfplay_worker(proc_id: int, cfg_dict: dict, ckpt_path: Optional[str], game
         book = load_opening_book(sp_book)
         logger.debug("worker %d: %d positions from opening book %s", proc_id, len(book), sp_book)
     engines = engine.engines if hasattr(engine, "engines") else [engine]
+    # mcts.gumbel: Gumbel root search (sequential halving, improved-policy targets) instead of the PUCT root
+    gumbel = gumbel_cfg_from_dict(cfg_dict)
+    if gumbel is not None:
+        for e in engines:
+            e.set_gumbel(gumbel)
+        logger.info("worker %d: Gumbel root search, %d considered moves", proc_id, gumbel.max_considered)
     if book:
         for e in engines:
             e.set_openings(book)
