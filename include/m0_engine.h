@@ -559,6 +559,8 @@ int m0_replay_games(int hip_device, const char* const* start_fens, const uint32_
 #include "m0_analysis_live.h"
 /* training loss of stored positions under a network, per row (no trainer, no gradient) */
 #include "m0_score.h"
+/* ... and its SSL term: the heads' losses per row, targets stored or taken from the stored planes */
+#include "m0_ssl_score.h"
 /* Gumbel root search for self-play engines: sequential halving and improved-policy targets (opt-in) */
 #include "m0_gumbel.h"
 #endif /* M0_ENGINE_H */

@@ -33,6 +33,12 @@ SCORE_MASK = {"legal": 0, "target": 1, "none": 2}
 SCORE_COLS = 8
 SCORE_COLUMNS = ("policy_loss", "entropy", "value_loss", "rank", "support_mass", "support_size", "value", "flags")
 SCORE_FLAGS = {"empty": 1, "nonfinite": 2, "uniform": 4}
+# include/m0_ssl_score.h: a row's columns and the flag bits of the last one
+SSL_SCORE_COLS = 16
+SSL_SCORE_COLUMNS = ("piece_loss", "threat_loss", "pin_loss", "fork_loss", "control_loss", "piece_hits", "piece_hits_occupied",
+                     "occupied", "threat_true_positive", "threat_predicted", "threat_actual", "fork_true_positive",
+                     "fork_predicted", "fork_actual", "control_hits", "flags")
+SSL_SCORE_FLAGS = {"planes": 1, "nonfinite": 2, "mismatch": 4}
 
 # ---- structs ----
 i32, i64, u8, u16, u32, u64, f32, f64 = (C.c_int, C.c_int64, C.c_uint8, C.c_uint16, C.c_uint32, C.c_uint64, C.c_float,
@@ -244,6 +250,15 @@ SCORE_FUNCTIONS = {
     "m0_score_bench": (i32, [i32, i32, i32, P(f32), P(f64)]),
 }
 
+# ---- include/m0_ssl_score.h (which m0_engine.h includes too): the SSL heads' losses of stored rows, in that header's order;
+# tests/test_abi_ssl_score.py compares the two ----
+SSL_SCORE_FUNCTIONS = {
+    "m0_ssl_score_rows": (i32, [i32, vp, i32, vp, vp, i32, vp]),
+    "m0_net_score_ssl": (i32, [vp, vp, vp, vp, vp, vp, i32, P(ScoreOpts), vp, vp]),
+    "m0_ssl_targets_planes": (i32, [i32, vp, i32, vp, vp]),
+    "m0_ssl_score_bench": (i32, [i32, i32, i32, i32, i32, P(f32), P(f64)]),
+}
+
 # ---- include/m0_gumbel.h (which m0_engine.h includes too): the Gumbel root search, in that header's order;
 # tests/test_abi_gumbel.py compares the two ----
 GUMBEL_STRUCTS = {"m0_gumbel_cfg": GumbelCfg}
@@ -256,11 +271,11 @@ GUMBEL_FUNCTIONS = {
 
 
 def bind(L) -> list:
-    """Set restype and argtypes of every function of FUNCTIONS, LIVE_FUNCTIONS, SCORE_FUNCTIONS and GUMBEL_FUNCTIONS on the loaded
-    library; the names it does not export."""
+    """Set restype and argtypes of every function of FUNCTIONS, LIVE_FUNCTIONS, SCORE_FUNCTIONS, SSL_SCORE_FUNCTIONS and
+    GUMBEL_FUNCTIONS on the loaded library; the names it does not export."""
     missing = []
     for name, (restype, argtypes) in (list(FUNCTIONS.items()) + list(LIVE_FUNCTIONS.items()) + list(SCORE_FUNCTIONS.items()) +
-                                      list(GUMBEL_FUNCTIONS.items())):
+                                      list(SSL_SCORE_FUNCTIONS.items()) + list(GUMBEL_FUNCTIONS.items())):
         fn = getattr(L, name, None)
         if fn is None:
             missing.append(name)

@@ -33,11 +33,13 @@ def resolve_mask_mode(pi: np.ndarray, legal_mask, mask_mode: Optional[str]) -> s
 
 
 class NonFiniteScore(ValueError):
-    """M0Backend.score met non-finite network outputs; `rows` holds the columns all the same (flag 2 marks the rows)."""
+    """M0Backend.score met non-finite network outputs; `rows` holds the columns all the same (flag 2 marks the rows), and after
+    score_ssl `ssl_rows` holds the SSL columns."""
 
-    def __init__(self, msg: str, rows: np.ndarray):
+    def __init__(self, msg: str, rows: np.ndarray, ssl_rows: Optional[np.ndarray] = None):
         super().__init__(msg)
         self.rows = rows
+        self.ssl_rows = ssl_rows
 
 
 def score_opts(mask_mode: str, label_smoothing: float, value_loss: str, huber_delta: float) -> "_abi.ScoreOpts":
@@ -151,13 +153,8 @@ class M0Backend:
         return pol, val, out
 
     # ---- training loss of stored rows --------------------------------------------------------
-    def score(self, s: np.ndarray, pi: np.ndarray, z: np.ndarray, legal_mask: Optional[np.ndarray] = None, *,
-              mask_mode: Optional[str] = None, label_smoothing: float = 0.0, value_loss: str = "mse",
-              huber_delta: float = 1.0) -> np.ndarray:
-        """f32 [B, 8]: the columns of include/m0_score.h (_abi.SCORE_COLUMNS) for the rows (s, pi, z, legal_mask) under this
-        network -- forward and loss on the device (m0_net_score), only the 8 columns come back.  mask_mode: "legal", "target",
-        "none", or None for resolve_mask_mode.  A non-finite network output raises NonFiniteScore (a ValueError, as infer_np
-        raises; it carries the rows)."""
+    def _score_inputs(self, s, pi, z, legal_mask):
+        """the rows of a score call as contiguous arrays of the types the library reads, their shapes checked"""
         if not self._finalized:
             raise RuntimeError("weights not loaded")
         a = np.ascontiguousarray(s, dtype=np.float32)
@@ -172,6 +169,17 @@ class M0Backend:
             legal_mask = np.ascontiguousarray(np.asarray(legal_mask).reshape(B, -1), dtype=np.uint8)
             if legal_mask.shape != pi.shape:
                 raise ValueError(f"expected legal_mask [{B},{_lib.POLICY_SIZE}], got {legal_mask.shape}")
+        return a, pi, z, legal_mask
+
+    def score(self, s: np.ndarray, pi: np.ndarray, z: np.ndarray, legal_mask: Optional[np.ndarray] = None, *,
+              mask_mode: Optional[str] = None, label_smoothing: float = 0.0, value_loss: str = "mse",
+              huber_delta: float = 1.0) -> np.ndarray:
+        """f32 [B, 8]: the columns of include/m0_score.h (_abi.SCORE_COLUMNS) for the rows (s, pi, z, legal_mask) under this
+        network -- forward and loss on the device (m0_net_score), only the 8 columns come back.  mask_mode: "legal", "target",
+        "none", or None for resolve_mask_mode.  A non-finite network output raises NonFiniteScore (a ValueError, as infer_np
+        raises; it carries the rows)."""
+        a, pi, z, legal_mask = self._score_inputs(s, pi, z, legal_mask)
+        B = a.shape[0]
         opts = score_opts(resolve_mask_mode(pi, legal_mask, mask_mode), label_smoothing, value_loss, huber_delta)
         rows = np.empty((B, _abi.SCORE_COLS), dtype=np.float32)
         rc = self._L.m0_net_score(self._h, _lib.ptr(a), _lib.ptr(pi), _lib.ptr(z), _lib.ptr(legal_mask), B, C.byref(opts),
@@ -180,6 +188,30 @@ class M0Backend:
             raise NonFiniteScore(f"m0_net_score failed ({rc}): {_lib.last_error()}", rows)
         _lib.check(rc, "m0_net_score")
         return rows
+
+    def score_ssl(self, s: np.ndarray, pi: np.ndarray, z: np.ndarray, legal_mask: Optional[np.ndarray] = None,
+                  ssl_targets: Optional[np.ndarray] = None, *, mask_mode: Optional[str] = None, label_smoothing: float = 0.0,
+                  value_loss: str = "mse", huber_delta: float = 1.0) -> Tuple[np.ndarray, np.ndarray]:
+        """(rows f32 [B, 8], ssl_rows f32 [B, 16]): `rows` as score gives them, `ssl_rows` the columns of include/m0_ssl_score.h
+        (_abi.SSL_SCORE_COLUMNS) for this network's SSL tasks -- one forward with the heads, both losses on the device
+        (m0_net_score_ssl).  ssl_targets f32 [B,17,8,8] (or [B,17,64]: piece one-hot, threat, pin, fork, control) as stored with
+        the rows, or None to take the targets from the planes.  A network without SSL heads is a ValueError; non-finite
+        outputs raise NonFiniteScore, which then carries `rows` and `ssl_rows`."""
+        a, pi, z, legal_mask = self._score_inputs(s, pi, z, legal_mask)
+        B = a.shape[0]
+        if ssl_targets is not None:
+            ssl_targets = np.ascontiguousarray(ssl_targets, dtype=np.float32)
+            if ssl_targets.size != B * 17 * 64 or ssl_targets.shape[:2] != (B, 17):
+                raise ValueError(f"expected ssl_targets [{B},17,8,8], got {ssl_targets.shape}")
+        opts = score_opts(resolve_mask_mode(pi, legal_mask, mask_mode), label_smoothing, value_loss, huber_delta)
+        rows = np.empty((B, _abi.SCORE_COLS), dtype=np.float32)
+        ssl_rows = np.empty((B, _abi.SSL_SCORE_COLS), dtype=np.float32)
+        rc = self._L.m0_net_score_ssl(self._h, _lib.ptr(a), _lib.ptr(pi), _lib.ptr(z), _lib.ptr(legal_mask), _lib.ptr(ssl_targets),
+                                      B, C.byref(opts), _lib.ptr(rows), _lib.ptr(ssl_rows))
+        if rc == _lib.M0_ERR_NONFINITE:
+            raise NonFiniteScore(f"m0_net_score_ssl failed ({rc}): {_lib.last_error()}", rows, ssl_rows)
+        _lib.check(rc, "m0_net_score_ssl")
+        return rows, ssl_rows
 
     # ---- measurement helpers ----------------------------------------------------------------
     def param_count(self) -> int:

@@ -10,6 +10,8 @@
 #include "capi_common.h"
 #include "score_core.h"
 #include "score_kernels.h"
+#include "ssl_score_core.h"
+#include "ssl_score_kernels.h"
 
 thread_local std::string g_m0_last_error;
 
@@ -32,6 +34,10 @@ struct m0_net {
     uint8_t* score_mask_dev = nullptr;
     float* score_rows_dev = nullptr;
     int score_cap = 0;
+    // ... and of m0_net_score_ssl: stored SSL targets in, the SSL score columns out
+    float* ssl_targets_dev = nullptr;
+    float* ssl_rows_dev = nullptr;
+    int ssl_score_cap = 0;
 };
 
 Net* m0_net_impl(m0_net* n) { return n ? n->net : nullptr; }
@@ -101,6 +107,8 @@ void m0_net_destroy(m0_net* n) {
     if (n->score_z_dev) (void)hipFree(n->score_z_dev);
     if (n->score_mask_dev) (void)hipFree(n->score_mask_dev);
     if (n->score_rows_dev) (void)hipFree(n->score_rows_dev);
+    if (n->ssl_targets_dev) (void)hipFree(n->ssl_targets_dev);
+    if (n->ssl_rows_dev) (void)hipFree(n->ssl_rows_dev);
     delete n->net;
     if (n->stream) (void)hipStreamDestroy(n->stream);
     delete n;
@@ -166,6 +174,22 @@ static int ensure_score_io(m0_net* n, int B) {
     return M0_OK;
 }
 
+// the staging of m0_net_score_ssl
+static int ensure_ssl_score_io(m0_net* n, int B) {
+    if (B <= n->ssl_score_cap) return M0_OK;
+    HipStatus& hs = n->net->hip();
+    if (n->ssl_targets_dev) M0_HIP(hs, hipFree(n->ssl_targets_dev));
+    if (n->ssl_rows_dev) M0_HIP(hs, hipFree(n->ssl_rows_dev));
+    n->ssl_targets_dev = n->ssl_rows_dev = nullptr;
+    n->ssl_score_cap = 0;
+    const int cap = B < 64 ? 64 : B;
+    M0_HIP(hs, hipMalloc((void**)&n->ssl_targets_dev, (size_t)cap * m0ssl::TARGET_CH * 64 * 4));
+    M0_HIP(hs, hipMalloc((void**)&n->ssl_rows_dev, (size_t)cap * M0_SSL_SCORE_COLS * 4));
+    if (!hs.ok()) return m0_hip_error(hs, "hipMalloc failed for SSL score staging");
+    n->ssl_score_cap = cap;
+    return M0_OK;
+}
+
 // The host-facing forward, under the network's lock.  tap_stream / tap_second (both or neither): the trunk tap's two buffers
 // after the forward, fp16 [B][64][width] widened to f32; the caller has armed the tap.
 static int infer_locked(m0_net* n, const float* planes, int B, float* policy, float* value, float* ssl,
@@ -216,16 +240,28 @@ int m0_net_infer(m0_net* n, const float* planes, int B, float* policy, float* va
     return infer_locked(n, planes, B, policy, value, ssl);
 }
 
-int m0_net_score(m0_net* n, const float* planes, const float* pi, const float* z, const uint8_t* legal_mask, int B,
-                 const m0_score_opts* opts, float* rows) {
+// m0_net_score and m0_net_score_ssl: one forward, then the score kernels on the buffers it left.  ssl_rows null: without the SSL
+// heads, as m0_net_score always ran.
+static int net_score(m0_net* n, const float* planes, const float* pi, const float* z, const uint8_t* legal_mask,
+                     const float* ssl_targets, int B, const m0_score_opts* opts, float* rows, float* ssl_rows) {
     if (!n || !planes || !pi || !z || !rows) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     if (B <= 0) { m0_set_error("batch must be positive"); return M0_ERR_INVALID; }
     if (const char* why = m0score::bad_opts(opts, legal_mask != nullptr)) { m0_set_error(why); return M0_ERR_INVALID; }
     std::lock_guard<std::mutex> lk(n->mu);
+    int tasks = 0;
+    if (ssl_rows) {
+        tasks = n->net->cfg().self_supervised ? n->net->cfg().ssl_tasks & m0sslscore::ALL_TASKS : 0;
+        if (n->net->ssl_channels_total() == 0 || n->net->ssl_channels_total() != m0sslscore::channels(tasks)) {
+            m0_set_error("the net has no SSL heads to score");
+            return M0_ERR_INVALID;
+        }
+        if (n->net->cfg().planes != M0_PLANES) { m0_set_error("SSL targets need the 19 planes of encode_board"); return M0_ERR_INVALID; }
+    }
     HipStatus& hs = n->net->hip();
     if (!M0_HIP(hs, hipSetDevice(n->device))) return m0_hip_error(hs);       // also a network that has failed before
     int rc = ensure_io(n, B);
     if (rc == M0_OK) rc = ensure_score_io(n, B);
+    if (rc == M0_OK && ssl_rows) rc = ensure_ssl_score_io(n, B);
     if (rc != M0_OK) return rc;
     const bool masked = opts->mask_mode == M0_SCORE_MASK_LEGAL;
     const size_t cells = (size_t)B * M0_POLICY_SIZE;
@@ -233,21 +269,40 @@ int m0_net_score(m0_net* n, const float* planes, const float* pi, const float* z
     M0_HIP(hs, hipMemcpyAsync(n->score_pi_dev, pi, cells * 4, hipMemcpyHostToDevice, n->stream));
     M0_HIP(hs, hipMemcpyAsync(n->score_z_dev, z, (size_t)B * 4, hipMemcpyHostToDevice, n->stream));
     if (masked) M0_HIP(hs, hipMemcpyAsync(n->score_mask_dev, legal_mask, cells, hipMemcpyHostToDevice, n->stream));
+    if (ssl_rows && ssl_targets)
+        M0_HIP(hs, hipMemcpyAsync(n->ssl_targets_dev, ssl_targets, (size_t)B * m0ssl::TARGET_CH * 64 * 4, hipMemcpyHostToDevice, n->stream));
     if (!hs.ok()) return m0_hip_error(hs, "H2D copy");
     std::string err;
-    rc = n->net->forward(n->planes_dev, nullptr, B, n->logits_dev, n->value_dev, nullptr, n->stream, err);
+    rc = n->net->forward(n->planes_dev, nullptr, B, n->logits_dev, n->value_dev, ssl_rows ? n->ssl_dev : nullptr, n->stream, err);
     if (rc != M0_OK) { m0_set_error(err); return rc; }
-    // the logits stay where the forward left them
+    // the logits and the head outputs stay where the forward left them
     M0_HIP(hs, launch_score_rows(n->logits_dev, n->value_dev, n->score_pi_dev, n->score_z_dev, masked ? n->score_mask_dev : nullptr,
                                  B, *opts, n->score_rows_dev, n->stream));
     M0_HIP(hs, hipMemcpyAsync(rows, n->score_rows_dev, (size_t)B * M0_SCORE_COLS * 4, hipMemcpyDeviceToHost, n->stream));
+    if (ssl_rows) {
+        M0_HIP(hs, launch_ssl_score(n->ssl_dev, tasks, n->planes_dev, ssl_targets ? n->ssl_targets_dev : nullptr, B, n->ssl_rows_dev,
+                                    n->stream));
+        M0_HIP(hs, hipMemcpyAsync(ssl_rows, n->ssl_rows_dev, (size_t)B * M0_SSL_SCORE_COLS * 4, hipMemcpyDeviceToHost, n->stream));
+    }
     if (!M0_HIP(hs, hipStreamSynchronize(n->stream))) return m0_hip_error(hs, "forward and score failed");
     for (int b = 0; b < B; ++b)
-        if ((int)rows[(size_t)b * M0_SCORE_COLS + 7] & M0_SCORE_FLAG_NONFINITE) {
+        if (((int)rows[(size_t)b * M0_SCORE_COLS + 7] & M0_SCORE_FLAG_NONFINITE) ||
+            (ssl_rows && ((int)ssl_rows[(size_t)b * M0_SSL_SCORE_COLS + 15] & M0_SSL_SCORE_FLAG_NONFINITE))) {
             m0_set_error("network produced non-finite outputs (row " + std::to_string(b) + ")");
             return M0_ERR_NONFINITE;
         }
     return M0_OK;
+}
+
+int m0_net_score(m0_net* n, const float* planes, const float* pi, const float* z, const uint8_t* legal_mask, int B,
+                 const m0_score_opts* opts, float* rows) {
+    return net_score(n, planes, pi, z, legal_mask, nullptr, B, opts, rows, nullptr);
+}
+
+int m0_net_score_ssl(m0_net* n, const float* planes, const float* pi, const float* z, const uint8_t* legal_mask,
+                     const float* ssl_targets, int B, const m0_score_opts* opts, float* rows, float* ssl_rows) {
+    if (!ssl_rows) { m0_set_error("null argument"); return M0_ERR_INVALID; }
+    return net_score(n, planes, pi, z, legal_mask, ssl_targets, B, opts, rows, ssl_rows);
 }
 
 int m0_net_tap_info(const m0_net* n, int* steps, int* width) {

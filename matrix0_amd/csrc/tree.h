@@ -238,6 +238,8 @@ hipError_t launch_policy_lines(const float* logits_dev, const float* values_dev,
 
 // SSL training targets for recorded positions: out f32 [n][17][64] (piece 13, threat, pin, fork, control)
 hipError_t launch_ssl_targets(const m0::Pos* pos_dev, int n, float* out_dev, hipStream_t st);
+// ... and for stored planes f32 [n][19][64]: status 0, or 1 for a row the targets cannot be taken from, whose `out` stays unwritten
+hipError_t launch_ssl_targets_planes(const float* planes_dev, int n, float* out_dev, int32_t* status_dev, hipStream_t st);
 
 // Replay of written games (replay_kernels.hip, patterns: san_match.h), one wave per game.  Game g owns rows offsets[g] ..
 // offsets[g+1] of patterns and of the per-ply outputs and writes the first plies[g] of them: the position before each resolved

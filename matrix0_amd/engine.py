@@ -495,6 +495,19 @@ def ssl_targets_fens(fens, device_index: int = 0) -> dict:
     return _lib.split_ssl(out)
 
 
+def ssl_targets_planes(planes, device_index: int = 0) -> dict:
+    """The same targets taken from stored planes f32 [n,19,8,8] (m0_ssl_targets_planes): the maps of ssl_targets_fens plus
+    "status" i32 [n], 0 or 1 for a row whose planes 0-12 do not describe a board (its maps are zero)."""
+    a = np.ascontiguousarray(planes, dtype=np.float32)
+    if a.ndim != 4 or a.shape[1:] != (19, 8, 8):
+        raise ValueError(f"expected planes [n,19,8,8], got {a.shape}")
+    n = a.shape[0]
+    out = np.zeros((n, 17, 8, 8), np.float32)
+    status = np.zeros(n, np.int32)
+    _lib.check(_lib.lib().m0_ssl_targets_planes(int(device_index), ptr(a), n, ptr(out), ptr(status)), "m0_ssl_targets_planes")
+    return dict(_lib.split_ssl(out), status=status)
+
+
 class ArenaEngine(SelfplayEngine):
     """Evaluation match engine (m0_arena_create): game i has `backend_a` as White when i is even; step / poll / stats as
     SelfplayEngine.  Records carry `played`, `result` (White's point of view) and `moves`, and `start_fen` when the game began

@@ -17,6 +17,22 @@ Command line: python -m matrix0_amd.score --config config.yaml --checkpoint A [-
 label_smoothing, value_loss and huber_delta default to training.policy_label_smoothing, training.value_loss and
 training.huber_delta of the config (the reference's keys).  One line per checkpoint; the exit status is 1 when any row had
 non-finite outputs.
+
+The SSL term (ssl=..., --ssl): the reference's loss is policy + value + ssl_weight * ssl_loss (train.py:551-677), and with
+ssl="auto" | "stored" | "planes" the same forward also scores the network's SSL heads (M0Backend.score_ssl -> m0_net_score_ssl,
+include/m0_ssl_score.h; 16 more floats per row).  "stored" takes the targets the shard holds (ssl_piece [N,13,8,8], ssl_threat /
+ssl_pin / ssl_fork / ssl_control [N,8,8]) and fails when a task of the network has no key; "planes" takes them from the stored
+planes and ignores the shard's; "auto" decides per shard: stored when the shard has every key, otherwise planes.  Stored
+targets are audited against the planes for free (flag "mismatch").  The report gains the key "ssl" (overall, per source, per
+shard): `loss` per task, `ssl_total` = piece + sum of ssl_<task>_weight * loss over the network's tasks (resnet.py:990),
+`total_with_ssl` = policy + value + ssl_weight * ssl_total, piece accuracy over all and over occupied squares, control accuracy,
+precision and recall of threat and fork, and the flag counts.  The reference leaves a task out of ssl_total when its loss is not
+finite or not > 0 (resnet.py:961-964, 988-996) PER TRAINING BATCH; here that rule is applied once, to the mean over the data set
+(`dropped` names such tasks).  training.ssl_target_weight other than 1 scales one-hot targets during training and has no meaning
+for a read-only score: it is refused.  Without ssl the report, the per-sample file and every call are what they were.
+    [--ssl [auto|stored|planes]] [--ssl-weight X] [--ssl-task-weight task=X ...]
+--ssl-weight defaults to training.ssl_weight (0.1 when absent, train.py:1306), a task's weight to model.ssl_<task>_weight (1).
+With --per-sample the 16 SSL columns are written under the key `ssl_columns`.
 """
 from __future__ import annotations
 
@@ -24,26 +40,66 @@ import argparse
 import json
 import sys
 from pathlib import Path
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Mapping, Optional, Sequence
 
 import numpy as np
 
-from ._abi import POLICY_SIZE, SCORE_COLS, SCORE_FLAGS
+from ._abi import POLICY_SIZE, SCORE_COLS, SCORE_FLAGS, SSL_BITS, SSL_SCORE_COLS, SSL_SCORE_FLAGS
 from .backend import NonFiniteScore, resolve_mask_mode
 from .npz_dataset import ReplayReader
 
 POLICY, ENTROPY, VALUE_LOSS, RANK, MASS, SUPPORT, VALUE, FLAGS = range(SCORE_COLS)
 _LEFT_OUT = SCORE_FLAGS["empty"] | SCORE_FLAGS["nonfinite"]
+SSL_MODES = ("auto", "stored", "planes")
+SSL_TASKS = tuple(SSL_BITS)                      # the order of the heads and of a row's target maps
+SSL_FLAGS_COL = SSL_SCORE_COLS - 1
 
 
-def score_arrays(backend, s, pi, z, legal_mask=None, *, batch: int = 4096, mask_mode: Optional[str] = None, **opts) -> np.ndarray:
+def pack_ssl_targets(arrays: Mapping[str, np.ndarray], n: int, tasks: Sequence[str]) -> np.ndarray:
+    """A shard's ssl_piece [n,13,8,8] and ssl_threat / ssl_pin / ssl_fork / ssl_control [n,8,8] as f32 [n,17,64], the layout of
+    m0_game_record.ssl.  KeyError when a task of `tasks` has no key; the map of a task that is not
+    asked for and not stored stays zero."""
+    out = np.zeros((n, 17, 64), np.float32)
+    for k, t in enumerate(SSL_TASKS):
+        a = arrays.get("ssl_" + t)
+        if a is None:
+            if t in tasks:
+                raise KeyError(f"stored SSL targets lack ssl_{t}")
+            continue
+        a = np.asarray(a)
+        if t == "piece":
+            out[:, :13] = a.reshape(n, 13, 64)
+        else:
+            out[:, 12 + k] = a.reshape(n, 64)
+    return out
+
+
+def score_arrays(backend, s, pi, z, legal_mask=None, *, batch: int = 4096, mask_mode: Optional[str] = None,
+                 ssl: Optional[str] = None, ssl_targets: Optional[np.ndarray] = None, **opts):
     """backend.score over the rows in chunks of `batch` (the last one partial): f32 [N, 8].  mask_mode None is resolved once,
-    on the arrays given, not per chunk.  Rows of non-finite network outputs come back with flag 2 set; nothing is raised."""
+    on the arrays given, not per chunk.  Rows of non-finite network outputs come back with flag 2 set; nothing is raised.
+    With ssl ("stored": ssl_targets f32 [N,17,64] as pack_ssl_targets makes them; "planes"; "auto": stored when targets are
+    given) the chunks go through backend.score_ssl and the result is (f32 [N, 8], f32 [N, 16])."""
     n = len(s)
     if batch <= 0:
         raise ValueError("batch must be positive")
     mode = resolve_mask_mode(pi, legal_mask, mask_mode)
     out = np.empty((n, SCORE_COLS), np.float32)
+    if ssl is not None:
+        if ssl not in SSL_MODES:
+            raise ValueError(f"ssl must be one of {SSL_MODES} or None, got {ssl!r}")
+        if ssl == "stored" and ssl_targets is None:
+            raise ValueError("ssl='stored' needs ssl_targets")
+        targets = None if ssl == "planes" else ssl_targets
+        ssl_out = np.empty((n, SSL_SCORE_COLS), np.float32)
+        for a in range(0, n, batch):
+            b = min(n, a + batch)
+            try:
+                out[a:b], ssl_out[a:b] = backend.score_ssl(s[a:b], pi[a:b], z[a:b], None if legal_mask is None else legal_mask[a:b],
+                                                           None if targets is None else targets[a:b], mask_mode=mode, **opts)
+            except NonFiniteScore as e:
+                out[a:b], ssl_out[a:b] = e.rows, e.ssl_rows
+        return out, ssl_out
     for a in range(0, n, batch):
         b = min(n, a + batch)
         try:
@@ -89,15 +145,83 @@ class Sums:
                 "flags": dict(self.flags)}
 
 
+class SslSums:
+    """float64 sums of SSL score columns (include/m0_ssl_score.h); report() turns them into the "ssl" block of the module's
+    docstring.  Rows whose columns the kernel zeroed (non-finite heads; unusable planes without stored targets) are counted
+    and left out."""
+
+    def __init__(self):
+        self.rows = 0
+        self.scored = 0
+        self.flags = dict.fromkeys(SSL_SCORE_FLAGS, 0)
+        self.sum = np.zeros(SSL_FLAGS_COL, np.float64)
+
+    def add(self, ssl_rows: np.ndarray, stored: bool) -> None:
+        r = np.asarray(ssl_rows, np.float64)
+        flags = r[:, SSL_FLAGS_COL].astype(np.int64)
+        for name, bit in SSL_SCORE_FLAGS.items():
+            self.flags[name] += int(((flags & bit) != 0).sum())
+        left_out = SSL_SCORE_FLAGS["nonfinite"] | (0 if stored else SSL_SCORE_FLAGS["planes"])
+        keep = (flags & left_out) == 0
+        self.rows += len(r)
+        self.scored += int(keep.sum())
+        self.sum += r[keep, :SSL_FLAGS_COL].sum(axis=0, dtype=np.float64)
+
+    def report(self, base: dict, tasks: Sequence[str], task_weights: Mapping[str, float], ssl_weight: float) -> dict:
+        n, s = self.scored, self.sum
+        ratio = lambda a, b: float(a / b) if b else None
+        loss = {t: ratio(s[SSL_TASKS.index(t)], n) for t in tasks}
+        counted = [t for t in tasks if loss[t] is not None and np.isfinite(loss[t]) and loss[t] > 0]
+        ssl_total = float(sum((1.0 if t == "piece" else float(task_weights.get(t, 1.0))) * loss[t] for t in counted)) if n else None
+        with_ssl = None
+        if ssl_total is not None and base["policy_loss"] is not None:
+            with_ssl = base["policy_loss"] + base["value_loss"] + float(ssl_weight) * ssl_total
+        out = {"rows": self.rows, "scored": n, "tasks": list(tasks), "loss": loss, "dropped": [t for t in tasks if t not in counted],
+               "ssl_total": ssl_total, "ssl_weight": float(ssl_weight), "total_with_ssl": with_ssl, "flags": dict(self.flags)}
+        if "piece" in tasks:
+            out["piece_accuracy"] = ratio(s[5], 64.0 * n)
+            out["piece_accuracy_occupied"] = ratio(s[6], s[7])
+        for t, c in (("threat", 8), ("fork", 11)):
+            if t in tasks:
+                out[t + "_precision"], out[t + "_recall"] = ratio(s[c], s[c + 1]), ratio(s[c], s[c + 2])
+        if "control" in tasks:
+            out["control_accuracy"] = ratio(s[14], 64.0 * n)
+        return out
+
+
+def _stored_ssl(path) -> Dict[str, np.ndarray]:
+    with np.load(path) as d:
+        return {k: d[k] for k in d.files if k.startswith("ssl_")}
+
+
 def score_shards(data_dir, backend, *, sources: Sequence[str] = ("selfplay", ""), batch: int = 4096,
-                 per_sample: Optional[str] = None, expected_planes: int = 19, **opts) -> dict:
+                 per_sample: Optional[str] = None, expected_planes: int = 19, ssl: Optional[str] = None,
+                 ssl_weight: float = 0.1, ssl_task_weights: Optional[Mapping[str, float]] = None,
+                 ssl_target_weight: float = 1.0, **opts) -> dict:
     """The report over every readable shard of `data_dir` whose source is in `sources`: the overall figures, "by_source",
     "by_shard" (keyed by file name, in the table's order, each with its "mask_mode") and "skipped" (shards that do not load
     or do not hold 4672 columns; nothing is marked in the table -- this tool only reads).  per_sample=PATH also writes
-    columns f32 [N, 8], shard_index i32 [N] into shards (file names) and row i32 [N], the row's index in its shard."""
+    columns f32 [N, 8], shard_index i32 [N] into shards (file names) and row i32 [N], the row's index in its shard.
+    ssl="auto" | "stored" | "planes" adds the "ssl" blocks of the module's docstring (a shard's also says its "targets":
+    "stored" or "planes") and ssl_columns f32 [N, 16] to the per-sample file; ssl_weight is training.ssl_weight (its default
+    there is 0.1, train.py:1306), ssl_task_weights {task: weight} defaults to backend.model_cfg's ssl_<task>_weight.  ssl=None
+    adds nothing."""
+    if ssl is not None:
+        if ssl not in SSL_MODES:
+            raise ValueError(f"ssl must be one of {SSL_MODES} or None, got {ssl!r}")
+        if float(ssl_target_weight) != 1.0:
+            raise ValueError("ssl_target_weight other than 1.0 scales the targets of a training step; a read-only score has no use for it")
+        tasks = list(backend.ssl_tasks)
+        if not tasks:
+            raise ValueError("the network has no SSL heads to score")
+        if ssl_task_weights is None:
+            model_cfg = getattr(backend, "model_cfg", {}) or {}
+            ssl_task_weights = {t: float(model_cfg.get(f"ssl_{t}_weight", 1.0)) for t in tasks}
+        ssl_report = lambda sums, base: sums.report(base, tasks, ssl_task_weights, ssl_weight)
     reader = ReplayReader(str(data_dir), expected_planes=expected_planes)
     total, by_source, by_shard, skipped = Sums(), {}, {}, []
-    keep: Dict[str, List[np.ndarray]] = {"columns": [], "shard_index": [], "row": []}
+    ssl_total, ssl_by_source = SslSums(), {}
+    keep: Dict[str, List[np.ndarray]] = {"columns": [], "shard_index": [], "row": [], "ssl_columns": []}
     for path, _, source, corrupted in reader.index.rows():
         source = source or ""
         if corrupted or source not in sources or not Path(path).exists():
@@ -111,21 +235,44 @@ def score_shards(data_dir, backend, *, sources: Sequence[str] = ("selfplay", "")
             continue
         s, pi, z, mask = got
         mode = resolve_mask_mode(pi, mask, opts.get("mask_mode"))
-        rows = score_arrays(backend, s, pi, z, mask, batch=batch, **dict(opts, mask_mode=mode))
+        if ssl is None:
+            rows = score_arrays(backend, s, pi, z, mask, batch=batch, **dict(opts, mask_mode=mode))
+        else:
+            have = {} if ssl == "planes" else _stored_ssl(path)
+            stored = ssl == "stored" or (ssl == "auto" and all("ssl_" + t in have for t in tasks))
+            try:
+                targets = pack_ssl_targets(have, len(s), tasks) if stored else None
+            except KeyError as e:
+                raise KeyError(f"{Path(path).name}: {e.args[0]} (ssl='stored')") from None
+            rows, ssl_rows = score_arrays(backend, s, pi, z, mask, batch=batch, ssl="stored" if stored else "planes",
+                                          ssl_targets=targets, **dict(opts, mask_mode=mode))
         one = Sums()
         for sums in (total, by_source.setdefault(source, Sums()), one):
             sums.add(rows, z)
         by_shard[Path(path).name] = dict(one.report(), source=source, mask_mode=mode)
+        if ssl is not None:
+            ssl_one = SslSums()
+            for sums in (ssl_total, ssl_by_source.setdefault(source, SslSums()), ssl_one):
+                sums.add(ssl_rows, stored)
+            by_shard[Path(path).name]["ssl"] = dict(ssl_report(ssl_one, one.report()), targets="stored" if stored else "planes")
         if per_sample:
             keep["columns"].append(rows)
             keep["shard_index"].append(np.full(len(rows), len(by_shard) - 1, np.int32))
             keep["row"].append(np.arange(len(rows), dtype=np.int32))
+            if ssl is not None:
+                keep["ssl_columns"].append(ssl_rows)
     if per_sample:
         cat = lambda key, dtype, shape: np.concatenate(keep[key]) if keep[key] else np.zeros(shape, dtype)
+        more = {} if ssl is None else {"ssl_columns": cat("ssl_columns", np.float32, (0, SSL_SCORE_COLS))}
         with open(per_sample, "wb") as f:
             np.savez(f, columns=cat("columns", np.float32, (0, SCORE_COLS)), shard_index=cat("shard_index", np.int32, (0,)),
-                     row=cat("row", np.int32, (0,)), shards=np.array(list(by_shard), dtype=str))
-    return dict(total.report(), by_source={k: v.report() for k, v in by_source.items()}, by_shard=by_shard, skipped=skipped)
+                     row=cat("row", np.int32, (0,)), shards=np.array(list(by_shard), dtype=str), **more)
+    report = dict(total.report(), by_source={k: v.report() for k, v in by_source.items()}, by_shard=by_shard, skipped=skipped)
+    if ssl is not None:
+        report["ssl"] = ssl_report(ssl_total, report)
+        for k, v in ssl_by_source.items():
+            report["by_source"][k]["ssl"] = ssl_report(v, report["by_source"][k])
+    return report
 
 
 def training_opts(cfg: dict, label_smoothing=None, value_loss=None, huber_delta=None) -> dict:
@@ -135,6 +282,29 @@ def training_opts(cfg: dict, label_smoothing=None, value_loss=None, huber_delta=
     return {"label_smoothing": float(tr.get("policy_label_smoothing", 0.0) if label_smoothing is None else label_smoothing),
             "value_loss": str(tr.get("value_loss", "mse") if value_loss is None else value_loss),
             "huber_delta": float(tr.get("huber_delta", 1.0) if huber_delta is None else huber_delta)}
+
+
+def ssl_opts(cfg: dict, tasks: Sequence[str] = SSL_TASKS, ssl_weight=None, task_weights: Optional[Mapping[str, float]] = None) -> dict:
+    """The SSL settings of a run: `training.ssl_weight` (train.py:1306, 0.1 when absent), `model.ssl_<task>_weight`
+    (resnet.py:990, 1 when absent) and `training.ssl_target_weight`; the arguments override the keys."""
+    tr, model = cfg.get("training", {}) or {}, cfg.get("model", {}) or {}
+    weights = {t: float(model.get(f"ssl_{t}_weight", 1.0)) for t in tasks if t != "piece"}
+    for t, w in (task_weights or {}).items():
+        if t not in weights:
+            raise ValueError(f"no SSL task weight for {t!r}: the weighted tasks are {sorted(weights)}")
+        weights[t] = float(w)
+    return {"ssl_weight": float(tr.get("ssl_weight", 0.1) if ssl_weight is None else ssl_weight), "ssl_task_weights": weights,
+            "ssl_target_weight": float(tr.get("ssl_target_weight", 1.0))}
+
+
+def ssl_summary_line(name: str, r: dict) -> str:
+    f = lambda x: "    n/a" if x is None else f"{x:7.4f}"
+    x = r["ssl"]
+    losses = "  ".join(f"{t} {f(v)}" for t, v in x["loss"].items())
+    return (f"{name}  ssl rows {x['rows']} scored {x['scored']}  {losses}  ssl_total {f(x['ssl_total'])}  "
+            f"total_with_ssl {f(x['total_with_ssl'])} (ssl_weight {x['ssl_weight']:g})  piece acc {f(x.get('piece_accuracy'))} "
+            f"occupied {f(x.get('piece_accuracy_occupied'))}  control acc {f(x.get('control_accuracy'))}  "
+            f"flags {x['flags']['planes']}/{x['flags']['nonfinite']}/{x['flags']['mismatch']}")
 
 
 def summary_line(name: str, r: dict) -> str:
@@ -158,6 +328,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--label-smoothing", type=float, default=None)
     ap.add_argument("--value-loss", choices=["mse", "huber"], default=None)
     ap.add_argument("--huber-delta", type=float, default=None)
+    ap.add_argument("--ssl", nargs="?", const="auto", default=None, choices=list(SSL_MODES),
+                    help="also score the SSL heads: targets as stored, from the planes, or per shard (auto, the default of --ssl)")
+    ap.add_argument("--ssl-weight", type=float, default=None, help="overrides training.ssl_weight")
+    ap.add_argument("--ssl-task-weight", action="append", default=[], metavar="TASK=X", help="overrides model.ssl_<task>_weight")
     ap.add_argument("--device", type=int, default=0)
     return ap
 
@@ -173,6 +347,10 @@ def main(argv: Optional[List[str]] = None) -> int:
     cfg = load_config(args.config)
     model_cfg = cfg.get("model", {}) or {}
     opts = training_opts(cfg, args.label_smoothing, args.value_loss, args.huber_delta)
+    more = {}
+    if args.ssl:
+        pairs = [w.partition("=") for w in args.ssl_task_weight]
+        more = dict(ssl_opts(cfg, ssl_weight=args.ssl_weight, task_weights={t: float(x) for t, _, x in pairs}), ssl=args.ssl)
     reports, nonfinite = {}, 0
     for k, ckpt in enumerate(args.checkpoint):
         per = args.per_sample
@@ -181,15 +359,19 @@ def main(argv: Optional[List[str]] = None) -> int:
         be = load_backend(model_cfg, ckpt, args.device)
         try:
             r = score_shards(args.data, be, sources=tuple(args.sources), batch=args.batch, per_sample=per,
-                             expected_planes=int(model_cfg.get("planes", 19)), **opts)
+                             expected_planes=int(model_cfg.get("planes", 19)), **opts, **more)
         finally:
             be.close()
         reports[ckpt] = r
         nonfinite += r["flags"]["nonfinite"]
         print(summary_line(ckpt, r), flush=True)
+        if args.ssl:
+            nonfinite += r["ssl"]["flags"]["nonfinite"]
+            print(ssl_summary_line(ckpt, r), flush=True)
     if args.json:
         with open(args.json, "w") as f:
-            json.dump({"options": opts, "sources": list(args.sources), "checkpoints": reports}, f, indent=1)
+            json.dump(dict({"options": opts, "sources": list(args.sources), "checkpoints": reports},
+                           **({"ssl_options": more} if args.ssl else {})), f, indent=1)
     return 1 if nonfinite else 0
 
 
