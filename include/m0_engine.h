@@ -184,7 +184,9 @@ typedef struct m0_selfplay_cfg {
     int concurrent_games;         /* trees resident on this GPU */
     int total_games;              /* games to play (<=0: unbounded, slots restart forever) */
     int first_game_index;         /* global index of this engine's first game (multi-GPU sharding) */
-    int arena_nodes;              /* nodes per arena half and game (0 = default) */
+    int arena_nodes;              /* nodes per arena half and game (0 = default: (1.3 * num_simulations + 64) * 96); a value
+                                     below 4096, the default included, is raised to 4096.  A search that needs more: see
+                                     "A full node arena" below */
     uint64_t seed;                /* cfg["seed"] (1234) */
     int virtual_loss_active;      /* 1 = apply mcts.py:889-890/922-923 as written (the reference never does) */
     int ssl_in_forward;           /* run the SSL heads in every leaf evaluation (BASELINE config 4) */
@@ -242,7 +244,9 @@ typedef struct m0_selfplay m0_selfplay;
 typedef struct m0_selfplay_stats {
     uint64_t steps, evals, sims, plies, games_finished, games_started;
     double ms_total, ms_net, ms_tree, ms_host;   /* accumulated wall (host) and device (HIP events) times */
-    uint64_t arena_overflows;
+    uint64_t arena_overflows;     /* searches that finished with a refused expansion ("A full node arena" below) or, in a game,
+                                     without a visit; counted once per search by every way of driving one (m0_selfplay_step,
+                                     m0_selfplay_ext_*, m0_search_expand, m0_analysis_*) */
     uint64_t ssl_dropped;         /* finished games emitted WITHOUT ssl_* targets because their staging buffers could not grow */
     uint64_t evals_cached;        /* leaf evaluations served by the evaluation cache (not counted in `evals`) */
     int active_games;
@@ -346,6 +350,25 @@ int m0_search_result(m0_selfplay* sp, int g, int* nchild, int32_t* child_n, uint
 /* play child slot `slot` of the finished search in g and keep its subtree (tree reuse across moves) */
 int m0_search_advance(m0_selfplay* sp, int g, int slot, int sims, int dirichlet);
 
+/* ---- A full node arena ----
+ * A slot's tree lives in one half of its arena: arena_nodes nodes (at least 4096).  The root is node 0; an expansion takes one
+ * block of consecutive nodes, one per child it keeps after pruning (max_children / min_child_prior), behind the last block.  A
+ * search over a kept subtree (tree reuse, m0_search_advance) starts with that subtree copied whole into the other half, children
+ * without visits included.
+ * An expansion whose block does not fit (nodes in use + block > arena_nodes) is refused.  The test is per expansion: a later
+ * leaf with a smaller block may still fit.  After a refusal
+ *   - the leaf stays an unexpanded leaf without children; a later descent that reaches it evaluates it and tries again;
+ *   - the sample is otherwise an ordinary one: its value is backed up along the path, the simulation counts (the root
+ *     children's visits still sum to the simulations run, the search still ends after `sims` of them) and the evaluation
+ *     counts in `evals` / `evals_cached`;
+ *   - whatever the priors drew from the game's entropy-noise stream before the refusal stays drawn, once per attempt -- with
+ *     the evaluation cache too, where a leaf reached again within the pass shares the first sample's row and tries again
+ *     from it: games are the same with the cache on and off in a full arena as well;
+ *   - the search's overflow flag is set.  It is per search: a fresh root and a kept subtree both clear it, and expansion goes
+ *     on in the other half.  It is what m0_analysis_result.overflow reports and what stats.arena_overflows counts.
+ * Nothing is written outside the half.  The root's own expansion always fits (1 + 218 < 4096).  The table mode (tt_merge in a
+ * match engine) starts a side's half over before a search that might not fit instead (arena_nodes above). */
+
 /* ---- batched position analysis (the reference's MCTS.run(board) for a list of arbitrary positions) ----
  * An analysis engine plays no games: positions are submitted with an id, searched in the engine's tree slots on the device
  * (select -> network -> expand, the kernels of m0_selfplay_step) and answered with the best root moves, the principal
@@ -353,7 +376,8 @@ int m0_search_advance(m0_selfplay* sp, int g, int slot, int sims, int dirichlet)
  * a result does not depend on the slot, the number of slots or what else is in flight.  (The streams take the low 32 bits
  * of id.)
  * cfg: concurrent_games = tree slots, inference_batch_size and the MCTS fields as a self-play engine reads them;
- * num_simulations sizes the node arenas (a submission with more simulations may report `overflow`).  The self-play, draw and
+ * num_simulations sizes the node arenas (a submission with more simulations may report `overflow`: "A full node arena"
+ * above; its lines, PVs -- which end at a refused leaf whatever its visits -- and `sims` are those of the search as it ran).  The self-play, draw and
  * arena fields, eval_cache and tail_split are ignored; tt_merge / raw_legal_priors are refused (NULL, the message starts with
  * "M0_ERR_UNSUPPORTED").  Destroy and stats with m0_selfplay_destroy / m0_selfplay_stats_get.  m0_selfplay_step, _poll,
  * _ext_*, _set_openings and m0_search_* on an analysis engine return M0_ERR_STATE, as m0_analysis_* do on any other engine. */

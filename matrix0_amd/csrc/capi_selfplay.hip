@@ -3,6 +3,7 @@
 #include <string.h>
 #include <algorithm>
 #include <memory>
+#include <vector>
 #include "selfplay_engine.h"
 
 using namespace m0;
@@ -394,9 +395,19 @@ int m0_search_expand(m0_selfplay* sp, const float* logits, const float* values, 
     if (rows != sp->last_rows || rows > sp->rows_max) { m0_set_error("rows does not match the last select"); return M0_ERR_INVALID; }
     if (rows > 0 && (!logits || !values)) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     upload_eval(sp, 0, logits, values, rows);
+    std::vector<uint8_t> was_finished(sp->G);
+    for (int g = 0; g < sp->G; ++g) was_finished[g] = sp->hg[g].finished ? 1 : 0;
     M0_HIP(sp->hip, launch_expand(sp->d, sp->tc, sp->stream));
     if (!sync_games_d2h(sp)) return m0_hip_error(sp->hip, "expand failed");
     sp->stats.evals += (uint64_t)rows;
+    // a search that this expand finished with a refused expansion behind it: counted once, as the fused step does (harvest_games)
+    for (int g = 0; g < sp->G; ++g)
+        if (sp->hg[g].active && sp->hg[g].finished && !was_finished[g] && sp->hg[g].overflow) sp->stats.arena_overflows++;
+    if (sp->tc.eval_cache) {               // as finish_step does
+        uint64_t h = 0;
+        for (int g = 0; g < sp->G; ++g) h += sp->hg[g].cache_hits;
+        sp->stats.evals_cached = h;
+    }
     return M0_OK;
 }
 

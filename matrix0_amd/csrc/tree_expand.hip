@@ -269,8 +269,8 @@ __device__ __forceinline__ bool expand_node(const ExpandEnv& E, const TreeCfg& c
 }
 
 // A leaf with a batch row of its own (SK_EVAL, or the unexpanded root SK_ROOT_INIT): expand it from the row's logits; a cacheable
-// leaf (SK_EVAL with a key set by select) also puts its evaluation into the cache.
-__device__ __forceinline__ void expand_evaluated(const TreeDev& d, const TreeCfg& c, const ExpandEnv& E, int g, const Sample& smp,
+// leaf (SK_EVAL with a key set by select) also puts its evaluation into the cache.  False: the node arena refused the child block.
+__device__ __forceinline__ bool expand_evaluated(const TreeDev& d, const TreeCfg& c, const ExpandEnv& E, int g, const Sample& smp,
                                                  const uint16_t* moves, const float* lg, float v, double q0) {
     const Arena& A = E.A;
     GameDev* gd = E.gd;
@@ -292,6 +292,23 @@ __device__ __forceinline__ void expand_evaluated(const TreeDev& d, const TreeCfg
     if (cw && lane == 0) {
         if (ok && !E.X->bad) ec_publish(d.ec, gd, ce, ckey, v, sig);
     }
+    return ok;
+}
+
+// An SK_SHARED sample whose leaf is still unexpanded: the expansion from its row was refused earlier in this pass (node arena
+// full).  Without the evaluation cache this sample would have been an SK_EVAL of its own and would have tried again, drawing
+// entropy noise again; the games are the same with the cache on and off only if it tries again here, from the same row.  Its
+// legal moves are those of the sample that owns the row (select stores them once).
+__device__ __forceinline__ bool retry_refused_shared(const TreeCfg& c, const ExpandEnv& E, const Sample* S, int s, const uint16_t* LM,
+                                                     const float* logits, const int* path) {
+    const int leaf = S[s].leaf, row = S[s].row;
+    int s0 = 0;
+    while (s0 < s && !(S[s0].kind == SK_EVAL && S[s0].row == row)) ++s0;
+    if (s0 >= s) return true;                       // (cannot happen: a pending row has an owner before every sharer)
+    const Pos pos = S[s].pos;
+    return expand_node(E, c, leaf, pos, LM + (size_t)s0 * M0_MAX_CHILDREN, S[s].nlegal,
+                       logits_of_row(logits + (size_t)row * M0_POLICY_SIZE, nullptr), false, true,
+                       child_seed_q(c, E.A, path, S[s].depth));
 }
 
 // release virtual losses of the whole batch (the reference's inflight dict dies with the batch)
@@ -335,12 +352,18 @@ __global__ __launch_bounds__(64) void expand_kernel(TreeDev d, TreeCfg c) {
     const bool may_repeat = c.tt_merge != 0;
     int sims = 0;
     uint64_t evals = 0, hits = 0;
+    bool refused = false;                        // the arena refused an expansion of this pass (wave-uniform)
     for (int s = 0; s < ns; ++s) {
         const int kind = S[s].kind;
         const int* path = P + (size_t)s * M0_MAX_DEPTH;
         const uint16_t* moves = LM + (size_t)s * M0_MAX_CHILDREN;
-        if (kind == SK_SHARED) {                 // its row's value, no second expansion
+        if (kind == SK_SHARED) {                 // its row's value, no second expansion ...
             const float v = d.values[S[s].row];
+            if (refused) {                       // ... unless the first was refused: see retry_refused_shared
+                // lane 0's stores of this launch (nch of a leaf that did get its block) before the wave reads them back
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+                if (A.nch[S[s].leaf] < 0) retry_refused_shared(c, E, S, s, LM, d.logits, path);
+            }
             backprop(A, path, S[s].depth, (double)v, lane, may_repeat, NoMirror{});
             ++sims; ++hits;
             __syncthreads();
@@ -350,7 +373,8 @@ __global__ __launch_bounds__(64) void expand_kernel(TreeDev d, TreeCfg c) {
             const float v = pay[EC_VALUE];
             if (A.nch[leaf] < 0) {
                 const Pos pos = S[s].pos;
-                expand_node(E, c, leaf, pos, moves, S[s].nlegal, logits_of_cache(pay), false, true, child_seed_q(c, A, path, depth));
+                refused |= !expand_node(E, c, leaf, pos, moves, S[s].nlegal, logits_of_cache(pay), false, true,
+                                        child_seed_q(c, A, path, depth));
             }
             backprop(A, path, depth, (double)v, lane, may_repeat, NoMirror{});
             ++sims; ++hits;
@@ -359,7 +383,7 @@ __global__ __launch_bounds__(64) void expand_kernel(TreeDev d, TreeCfg c) {
             const int leaf = S[s].leaf, depth = S[s].depth, row = S[s].row;
             const float* lg = d.logits + (size_t)row * M0_POLICY_SIZE;
             const float v = d.values[row];
-            if (A.nch[leaf] < 0) expand_evaluated(d, c, E, g, S[s], moves, lg, v, child_seed_q(c, A, path, depth));
+            if (A.nch[leaf] < 0) refused |= !expand_evaluated(d, c, E, g, S[s], moves, lg, v, child_seed_q(c, A, path, depth));
             ++evals;
             if (kind == SK_EVAL) {
                 backprop(A, path, depth, (double)v, lane, may_repeat, NoMirror{});

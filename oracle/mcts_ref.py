@@ -133,6 +133,9 @@ class MCTSConfig:
     use_tt: bool = True
     virtual_loss_active: bool = False
     numerics: str = "reference"   # "engine": see legal_priors
+    # the engine's node arena (csrc/tree_expand.hip write_children, tree_device.h reroot_*): nodes one search tree may hold,
+    # 0 = unlimited.  Tree-only structure (use_tt False); see MCTS.claim_nodes
+    node_cap: int = 0
 
     @classmethod
     def from_dict(cls, d):
@@ -213,6 +216,15 @@ class MCTS:
         self.evals = 0
         self._last_sims_run = 0
         self._last_root = None
+        # node arena (cfg.node_cap): `next` = nodes the tree holds (the root is node 0), `overflow` = an expansion of this
+        # search was refused, `attempts` = every expansion tried since the object was made, in order:
+        # (search, pass, node, block size, next before, fitted)
+        self.next = 0
+        self.next_at_start = 0                     # `next` as the current search found it: 1, or the size of the kept subtree
+        self.overflow = False
+        self.attempts: List[Tuple[int, int, Node, int, int, bool]] = []
+        self._search = -1
+        self._pass = -1
 
     # ---- pieces ----
     def cpuct_at(self, ply: int) -> float:
@@ -270,6 +282,24 @@ class MCTS:
             node.children[m] = c
         node.expanded = True
         self.prune_children(node)
+        if not self.claim_nodes(node, len(node.children)):
+            # refused (write_children returns false): the node stays an unexpanded leaf without children; what the priors
+            # drew from the noise stream stays drawn, and the caller backs the value up and counts the simulation as ever
+            node.children = {}
+            node.expanded = False
+
+    def claim_nodes(self, node: Node, nkeep: int) -> bool:
+        """The arena rule of write_children (csrc/tree_expand.hip): the block of the `nkeep` children left after pruning takes the
+        next `nkeep` nodes; with next + nkeep > cap the expansion is refused and the search's overflow flag is set.  The test is
+        per expansion: a later, smaller block may still fit."""
+        cap = int(self.cfg.node_cap)
+        ok = not (cap > 0 and self.next + nkeep > cap)
+        self.attempts.append((self._search, self._pass, node, nkeep, self.next, ok))
+        if ok:
+            self.next += nkeep
+        else:
+            self.overflow = True
+        return ok
 
     def register_children(self, node: Node, board: ch.Board) -> None:
         if not self.cfg.use_tt:
@@ -347,6 +377,7 @@ class MCTS:
         done = 0
         while done < sims:
             batch_n = min(L, sims - done)
+            self._pass += 1
             inflight = {} if self.cfg.virtual_loss_active else None
             samples = []
             for _ in range(batch_n):
@@ -372,9 +403,18 @@ class MCTS:
         cfg = self.cfg
         if board.is_game_over():
             return {}, np.zeros(4672, dtype=np.float32), self.terminal_value(board)
+        assert not (cfg.node_cap and cfg.use_tt), "the node cap restates the tree-only engine"
         key = board._transposition_key()
         root = self.tt.get(key) if cfg.use_tt else self._last_child_root(board)
         v = 0.0
+        # a new root for the slot (tree_device.h): a fresh root is node 0 and next = 1 (reroot_fresh); a kept subtree is copied
+        # whole into the other arena half, unvisited children included, and next is its size (reroot_keep_subtree).  Both clear
+        # the overflow flag: it is per search.
+        self._search += 1
+        self._pass = -1
+        self.overflow = False
+        self.next = 1 if root is None else (subtree_size(root) if not cfg.use_tt else 0)   # (the table's graph is no tree)
+        self.next_at_start = self.next
         if root is None:
             root = Node()
             logits, v = self._infer_one(board)
@@ -406,6 +446,8 @@ class MCTS:
             root.q = float(np.clip(v, -1.0, 1.0))
             if cfg.dirichlet_plies is None or ply is None or ply < int(cfg.dirichlet_plies):
                 pass  # reference applied Dirichlet before this expansion (no children then): no-op there
+        # the engine's smallest arena (4096 nodes) is above 1 + 218: the root's own expansion always fits
+        assert root.expanded, "node_cap is too small for the root's children"
         self.run_batched(board, root, sims)
         visit_counts = {m: c.n for m, c in root.children.items()}
         pi = np.zeros(4672, dtype=np.float32)
@@ -430,6 +472,16 @@ class MCTS:
 
     def note_move_played(self, move: ch.Move):
         self._last_move = move
+
+
+def subtree_size(root: Node) -> int:
+    """Nodes of the tree below and including `root` (tree-only structure: every node has one parent)."""
+    k, stack = 0, [root]
+    while stack:
+        node = stack.pop()
+        k += 1
+        stack.extend(node.children.values())
+    return k
 
 
 # ---- self-play decision functions (host logic of the engine mirrors these) ----

@@ -27,11 +27,12 @@ FENS = [ch.START_FEN,
         "7k/5Q2/5K2/8/8/8/8/8 w - - 0 1"]               # stalemate / mate leaves near the root
 
 
-def _engine(G, L, sims, vl_active=True, legal_softmax=True, noise=True, mcts=None, compat=None):
+def _engine(G, L, sims, vl_active=True, legal_softmax=True, noise=True, mcts=None, compat=None, **cfg_kw):
+    """cfg_kw: further keywords of selfplay_cfg_from_dict (arena_nodes, eval_cache)."""
     from matrix0_amd import engine as eng
     m = dict(MCTS, inference_batch_size=L, legal_softmax=legal_softmax, enable_entropy_noise=noise, **(mcts or {}))
     cfg = eng.selfplay_cfg_from_dict({"seed": 1234, "mcts": m, "selfplay": {"num_simulations": sims}},
-                                     concurrent_games=G, virtual_loss_active=vl_active, compat=compat)
+                                     concurrent_games=G, virtual_loss_active=vl_active, compat=compat, **cfg_kw)
     return eng.SelfplayEngine(None, cfg), m
 
 
