@@ -587,4 +587,6 @@ int m0_replay_games(int hip_device, const char* const* start_fens, const uint32_
 #include "m0_ssl_score.h"
 /* Gumbel root search for self-play engines: sequential halving and improved-policy targets (opt-in) */
 #include "m0_gumbel.h"
+/* the trainer's flip and rotate augmentations of stored rows on the device, and the training loss under them */
+#include "m0_augment.h"
 #endif /* M0_ENGINE_H */

@@ -1,7 +1,7 @@
 /* Training loss of stored positions, read-only: how well a network fits rows (s, pi, z, legal_mask) of the shard store, as the
  * reference's trainer measures it (azchess/training/train.py:436-549) but per row and without a trainer (m0_engine.h includes
- * this file: the calls here are part of the same C ABI and the same library).  No gradient, no WDL term, no augmentation; the
- * SSL term is m0_ssl_score.h.
+ * this file: the calls here are part of the same C ABI and the same library).  No gradient, no WDL term; the SSL term is
+ * m0_ssl_score.h, the trainer's flip and rotate augmentations are m0_augment.h (m0_net_score_aug).
  *
  * Per row, with pi >= 0 (4672 columns) and the network's logits and value v:
  *   support   M0_SCORE_MASK_LEGAL: legal_mask | (pi > 0)  (:444-449); _TARGET: pi > 0 (apply_policy_mask, :82); _NONE: every

@@ -39,6 +39,8 @@ SSL_SCORE_COLUMNS = ("piece_loss", "threat_loss", "pin_loss", "fork_loss", "cont
                      "occupied", "threat_true_positive", "threat_predicted", "threat_actual", "fork_true_positive",
                      "fork_predicted", "fork_actual", "control_hits", "flags")
 SSL_SCORE_FLAGS = {"planes": 1, "nonfinite": 2, "mismatch": 4}
+# include/m0_augment.h: the kinds of the trainer's augmentations
+AUGMENT_KINDS = {"none": 0, "hflip": 1, "rot180": 2}
 
 # ---- structs ----
 i32, i64, u8, u16, u32, u64, f32, f64 = (C.c_int, C.c_int64, C.c_uint8, C.c_uint16, C.c_uint32, C.c_uint64, C.c_float,
@@ -269,13 +271,22 @@ GUMBEL_FUNCTIONS = {
     "m0_gumbel_improve": (i32, [i32, vp, vp, vp, vp, f64, P(GumbelCfg), vp, P(f64), _pi32]),
 }
 
+# ---- include/m0_augment.h (which m0_engine.h includes too): the trainer's flip and rotate augmentations of stored rows, in that
+# header's order; tests/test_abi_augment.py compares the two ----
+AUGMENT_FUNCTIONS = {
+    "m0_augment_rows": (i32, [i32, vp, i32, vp, vp, vp, i32, vp, vp, vp]),
+    "m0_net_score_aug": (i32, [vp, vp, vp, vp, vp, vp, i32, P(ScoreOpts), vp]),
+    "m0_augment_bench": (i32, [i32, i32, i32, P(f32), P(f64)]),
+}
+
 
 def bind(L) -> list:
-    """Set restype and argtypes of every function of FUNCTIONS, LIVE_FUNCTIONS, SCORE_FUNCTIONS, SSL_SCORE_FUNCTIONS and
-    GUMBEL_FUNCTIONS on the loaded library; the names it does not export."""
+    """Set restype and argtypes of every function of FUNCTIONS, LIVE_FUNCTIONS, SCORE_FUNCTIONS, SSL_SCORE_FUNCTIONS,
+    GUMBEL_FUNCTIONS and AUGMENT_FUNCTIONS on the loaded library; the names it does not export."""
     missing = []
     for name, (restype, argtypes) in (list(FUNCTIONS.items()) + list(LIVE_FUNCTIONS.items()) + list(SCORE_FUNCTIONS.items()) +
-                                      list(SSL_SCORE_FUNCTIONS.items()) + list(GUMBEL_FUNCTIONS.items())):
+                                      list(SSL_SCORE_FUNCTIONS.items()) + list(GUMBEL_FUNCTIONS.items()) +
+                                      list(AUGMENT_FUNCTIONS.items())):
         fn = getattr(L, name, None)
         if fn is None:
             missing.append(name)

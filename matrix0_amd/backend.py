@@ -173,20 +173,30 @@ class M0Backend:
 
     def score(self, s: np.ndarray, pi: np.ndarray, z: np.ndarray, legal_mask: Optional[np.ndarray] = None, *,
               mask_mode: Optional[str] = None, label_smoothing: float = 0.0, value_loss: str = "mse",
-              huber_delta: float = 1.0) -> np.ndarray:
+              huber_delta: float = 1.0, augment=None) -> np.ndarray:
         """f32 [B, 8]: the columns of include/m0_score.h (_abi.SCORE_COLUMNS) for the rows (s, pi, z, legal_mask) under this
         network -- forward and loss on the device (m0_net_score), only the 8 columns come back.  mask_mode: "legal", "target",
         "none", or None for resolve_mask_mode.  A non-finite network output raises NonFiniteScore (a ValueError, as infer_np
-        raises; it carries the rows)."""
+        raises; it carries the rows).  augment: None for the rows as they are; "hflip", "rot180", "none" or a u8 [B] of
+        _abi.AUGMENT_KINDS' values scores every row under that trainer augmentation, transformed on the device after the one
+        upload (m0_net_score_aug, include/m0_augment.h); the mode is still resolved on the rows as given."""
         a, pi, z, legal_mask = self._score_inputs(s, pi, z, legal_mask)
         B = a.shape[0]
         opts = score_opts(resolve_mask_mode(pi, legal_mask, mask_mode), label_smoothing, value_loss, huber_delta)
         rows = np.empty((B, _abi.SCORE_COLS), dtype=np.float32)
-        rc = self._L.m0_net_score(self._h, _lib.ptr(a), _lib.ptr(pi), _lib.ptr(z), _lib.ptr(legal_mask), B, C.byref(opts),
-                                  _lib.ptr(rows))
+        if augment is None:
+            call = "m0_net_score"
+            rc = self._L.m0_net_score(self._h, _lib.ptr(a), _lib.ptr(pi), _lib.ptr(z), _lib.ptr(legal_mask), B, C.byref(opts),
+                                      _lib.ptr(rows))
+        else:
+            from .encoding import augment_kinds
+            call = "m0_net_score_aug"
+            kinds = augment_kinds(augment, B)
+            rc = self._L.m0_net_score_aug(self._h, _lib.ptr(a), _lib.ptr(pi), _lib.ptr(z), _lib.ptr(legal_mask), _lib.ptr(kinds), B,
+                                          C.byref(opts), _lib.ptr(rows))
         if rc == _lib.M0_ERR_NONFINITE:
-            raise NonFiniteScore(f"m0_net_score failed ({rc}): {_lib.last_error()}", rows)
-        _lib.check(rc, "m0_net_score")
+            raise NonFiniteScore(f"{call} failed ({rc}): {_lib.last_error()}", rows)
+        _lib.check(rc, call)
         return rows
 
     def score_ssl(self, s: np.ndarray, pi: np.ndarray, z: np.ndarray, legal_mask: Optional[np.ndarray] = None,

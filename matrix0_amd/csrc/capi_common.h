@@ -16,6 +16,9 @@ void m0_net_unlock(m0_net* n);
 // A non-blocking stream; when the environment variable env_name holds w0,w1,...,w7 (hex words, bit b = CU b in the driver's
 // numbering) the stream runs on those CUs only (hipExtStreamCreateWithCUMask).  Measurement switch; read at every call.
 hipError_t create_stream_cu_mask_env(const char* env_name, hipStream_t* stream);
+// The check m0_augment_rows and m0_net_score_aug share on kinds u8 [B] (include/m0_augment.h): nullptr when every row holds a kind,
+// otherwise why not (capi_augment.hip).
+const char* m0_bad_kinds(const uint8_t* kinds, int B);
 
 // device memory for the length of one call
 template <typename T>

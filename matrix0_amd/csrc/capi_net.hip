@@ -12,6 +12,7 @@
 #include "score_kernels.h"
 #include "ssl_score_core.h"
 #include "ssl_score_kernels.h"
+#include "augment_kernels.h"
 
 thread_local std::string g_m0_last_error;
 
@@ -38,6 +39,12 @@ struct m0_net {
     float* ssl_targets_dev = nullptr;
     float* ssl_rows_dev = nullptr;
     int ssl_score_cap = 0;
+    // ... and of m0_net_score_aug: the kinds in, the transformed planes, pi and mask that its forward and score kernel read
+    uint8_t* aug_kinds_dev = nullptr;
+    float* aug_planes_dev = nullptr;
+    float* aug_pi_dev = nullptr;
+    uint8_t* aug_mask_dev = nullptr;
+    int aug_cap = 0;
 };
 
 Net* m0_net_impl(m0_net* n) { return n ? n->net : nullptr; }
@@ -109,6 +116,10 @@ void m0_net_destroy(m0_net* n) {
     if (n->score_rows_dev) (void)hipFree(n->score_rows_dev);
     if (n->ssl_targets_dev) (void)hipFree(n->ssl_targets_dev);
     if (n->ssl_rows_dev) (void)hipFree(n->ssl_rows_dev);
+    if (n->aug_kinds_dev) (void)hipFree(n->aug_kinds_dev);
+    if (n->aug_planes_dev) (void)hipFree(n->aug_planes_dev);
+    if (n->aug_pi_dev) (void)hipFree(n->aug_pi_dev);
+    if (n->aug_mask_dev) (void)hipFree(n->aug_mask_dev);
     delete n->net;
     if (n->stream) (void)hipStreamDestroy(n->stream);
     delete n;
@@ -190,6 +201,27 @@ static int ensure_ssl_score_io(m0_net* n, int B) {
     return M0_OK;
 }
 
+// the staging of m0_net_score_aug
+static int ensure_aug_io(m0_net* n, int B) {
+    if (B <= n->aug_cap) return M0_OK;
+    HipStatus& hs = n->net->hip();
+    if (n->aug_kinds_dev) M0_HIP(hs, hipFree(n->aug_kinds_dev));
+    if (n->aug_planes_dev) M0_HIP(hs, hipFree(n->aug_planes_dev));
+    if (n->aug_pi_dev) M0_HIP(hs, hipFree(n->aug_pi_dev));
+    if (n->aug_mask_dev) M0_HIP(hs, hipFree(n->aug_mask_dev));
+    n->aug_kinds_dev = n->aug_mask_dev = nullptr;
+    n->aug_planes_dev = n->aug_pi_dev = nullptr;
+    n->aug_cap = 0;
+    const int cap = B < 64 ? 64 : B;
+    M0_HIP(hs, hipMalloc((void**)&n->aug_kinds_dev, (size_t)cap));
+    M0_HIP(hs, hipMalloc((void**)&n->aug_planes_dev, (size_t)cap * n->net->cfg().planes * 64 * 4));
+    M0_HIP(hs, hipMalloc((void**)&n->aug_pi_dev, (size_t)cap * M0_POLICY_SIZE * 4));
+    M0_HIP(hs, hipMalloc((void**)&n->aug_mask_dev, (size_t)cap * M0_POLICY_SIZE));
+    if (!hs.ok()) return m0_hip_error(hs, "hipMalloc failed for augmentation staging");
+    n->aug_cap = cap;
+    return M0_OK;
+}
+
 // The host-facing forward, under the network's lock.  tap_stream / tap_second (both or neither): the trunk tap's two buffers
 // after the forward, fp16 [B][64][width] widened to f32; the caller has armed the tap.
 static int infer_locked(m0_net* n, const float* planes, int B, float* policy, float* value, float* ssl,
@@ -240,13 +272,18 @@ int m0_net_infer(m0_net* n, const float* planes, int B, float* policy, float* va
     return infer_locked(n, planes, B, policy, value, ssl);
 }
 
-// m0_net_score and m0_net_score_ssl: one forward, then the score kernels on the buffers it left.  ssl_rows null: without the SSL
-// heads, as m0_net_score always ran.
+// m0_net_score, m0_net_score_ssl and m0_net_score_aug: one forward, then the score kernels on the buffers it left.  ssl_rows null:
+// without the SSL heads, as m0_net_score always ran.  kinds null (augmented false): the rows as they were uploaded, the launches
+// m0_net_score always made; otherwise augment_rows_kernel first moves them into the second staging set, and the forward and the
+// score kernel read that.
 static int net_score(m0_net* n, const float* planes, const float* pi, const float* z, const uint8_t* legal_mask,
-                     const float* ssl_targets, int B, const m0_score_opts* opts, float* rows, float* ssl_rows) {
+                     const float* ssl_targets, const uint8_t* kinds, bool augmented, int B, const m0_score_opts* opts, float* rows,
+                     float* ssl_rows) {
     if (!n || !planes || !pi || !z || !rows) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     if (B <= 0) { m0_set_error("batch must be positive"); return M0_ERR_INVALID; }
     if (const char* why = m0score::bad_opts(opts, legal_mask != nullptr)) { m0_set_error(why); return M0_ERR_INVALID; }
+    if (augmented)
+        if (const char* why = m0_bad_kinds(kinds, B)) { m0_set_error(why); return M0_ERR_INVALID; }
     std::lock_guard<std::mutex> lk(n->mu);
     int tasks = 0;
     if (ssl_rows) {
@@ -262,6 +299,7 @@ static int net_score(m0_net* n, const float* planes, const float* pi, const floa
     int rc = ensure_io(n, B);
     if (rc == M0_OK) rc = ensure_score_io(n, B);
     if (rc == M0_OK && ssl_rows) rc = ensure_ssl_score_io(n, B);
+    if (rc == M0_OK && augmented) rc = ensure_aug_io(n, B);
     if (rc != M0_OK) return rc;
     const bool masked = opts->mask_mode == M0_SCORE_MASK_LEGAL;
     const size_t cells = (size_t)B * M0_POLICY_SIZE;
@@ -271,13 +309,24 @@ static int net_score(m0_net* n, const float* planes, const float* pi, const floa
     if (masked) M0_HIP(hs, hipMemcpyAsync(n->score_mask_dev, legal_mask, cells, hipMemcpyHostToDevice, n->stream));
     if (ssl_rows && ssl_targets)
         M0_HIP(hs, hipMemcpyAsync(n->ssl_targets_dev, ssl_targets, (size_t)B * m0ssl::TARGET_CH * 64 * 4, hipMemcpyHostToDevice, n->stream));
+    if (augmented) M0_HIP(hs, hipMemcpyAsync(n->aug_kinds_dev, kinds, (size_t)B, hipMemcpyHostToDevice, n->stream));
     if (!hs.ok()) return m0_hip_error(hs, "H2D copy");
+    const float* planes_in = n->planes_dev;
+    const float* pi_in = n->score_pi_dev;
+    const uint8_t* mask_in = masked ? n->score_mask_dev : nullptr;
+    if (augmented) {
+        if (!M0_HIP(hs, launch_augment_rows(planes_in, pi_in, mask_in, n->aug_kinds_dev, M0_AUG_NONE, B, n->net->cfg().planes,
+                                            n->aug_planes_dev, n->aug_pi_dev, masked ? n->aug_mask_dev : nullptr, n->stream)))
+            return m0_hip_error(hs, "augment kernel");
+        planes_in = n->aug_planes_dev;
+        pi_in = n->aug_pi_dev;
+        if (masked) mask_in = n->aug_mask_dev;
+    }
     std::string err;
-    rc = n->net->forward(n->planes_dev, nullptr, B, n->logits_dev, n->value_dev, ssl_rows ? n->ssl_dev : nullptr, n->stream, err);
+    rc = n->net->forward(planes_in, nullptr, B, n->logits_dev, n->value_dev, ssl_rows ? n->ssl_dev : nullptr, n->stream, err);
     if (rc != M0_OK) { m0_set_error(err); return rc; }
     // the logits and the head outputs stay where the forward left them
-    M0_HIP(hs, launch_score_rows(n->logits_dev, n->value_dev, n->score_pi_dev, n->score_z_dev, masked ? n->score_mask_dev : nullptr,
-                                 B, *opts, n->score_rows_dev, n->stream));
+    M0_HIP(hs, launch_score_rows(n->logits_dev, n->value_dev, pi_in, n->score_z_dev, mask_in, B, *opts, n->score_rows_dev, n->stream));
     M0_HIP(hs, hipMemcpyAsync(rows, n->score_rows_dev, (size_t)B * M0_SCORE_COLS * 4, hipMemcpyDeviceToHost, n->stream));
     if (ssl_rows) {
         M0_HIP(hs, launch_ssl_score(n->ssl_dev, tasks, n->planes_dev, ssl_targets ? n->ssl_targets_dev : nullptr, B, n->ssl_rows_dev,
@@ -296,13 +345,18 @@ static int net_score(m0_net* n, const float* planes, const float* pi, const floa
 
 int m0_net_score(m0_net* n, const float* planes, const float* pi, const float* z, const uint8_t* legal_mask, int B,
                  const m0_score_opts* opts, float* rows) {
-    return net_score(n, planes, pi, z, legal_mask, nullptr, B, opts, rows, nullptr);
+    return net_score(n, planes, pi, z, legal_mask, nullptr, nullptr, false, B, opts, rows, nullptr);
+}
+
+int m0_net_score_aug(m0_net* n, const float* planes, const float* pi, const float* z, const uint8_t* legal_mask, const uint8_t* kinds,
+                     int B, const m0_score_opts* opts, float* rows) {
+    return net_score(n, planes, pi, z, legal_mask, nullptr, kinds, true, B, opts, rows, nullptr);
 }
 
 int m0_net_score_ssl(m0_net* n, const float* planes, const float* pi, const float* z, const uint8_t* legal_mask,
                      const float* ssl_targets, int B, const m0_score_opts* opts, float* rows, float* ssl_rows) {
     if (!ssl_rows) { m0_set_error("null argument"); return M0_ERR_INVALID; }
-    return net_score(n, planes, pi, z, legal_mask, ssl_targets, B, opts, rows, ssl_rows);
+    return net_score(n, planes, pi, z, legal_mask, ssl_targets, nullptr, false, B, opts, rows, ssl_rows);
 }
 
 int m0_net_tap_info(const m0_net* n, int* steps, int* width) {

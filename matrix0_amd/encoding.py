@@ -11,7 +11,7 @@ from typing import List, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._abi import (DECODE_MASK_MISMATCH, DECODE_OK, DECODE_STATUS, EP_FROM_MASK, FULLMOVE_SATURATED,  # noqa: F401
+from ._abi import (AUGMENT_KINDS, DECODE_MASK_MISMATCH, DECODE_OK, DECODE_STATUS, EP_FROM_MASK, FULLMOVE_SATURATED,  # noqa: F401
                    HALFMOVE_SATURATED, NO_MASK)
 from ._lib import ptr
 from .engine import move_to_uci
@@ -117,3 +117,42 @@ def build_rotate180_permutation() -> np.ndarray:
     for blk in (64, 67, 70):
         perm[blk + 1], perm[blk + 2] = perm[blk + 2], perm[blk + 1]
     return np.ascontiguousarray(perm, dtype=np.int64)
+
+
+def augment_kinds(kind, n: int) -> np.ndarray:
+    """`kind` as the u8 [n] the library reads: a name of AUGMENT_KINDS for every row, or one kind (0, 1, 2) per row."""
+    if isinstance(kind, str):
+        if kind not in AUGMENT_KINDS:
+            raise ValueError(f"augmentation must be one of {sorted(AUGMENT_KINDS)} or an array of kinds, got {kind!r}")
+        return np.full((n,), AUGMENT_KINDS[kind], np.uint8)
+    raw = np.asarray(kind)
+    if raw.shape != (n,) or raw.dtype.kind not in "iub" or ((raw < 0) | (raw > max(AUGMENT_KINDS.values()))).any():
+        raise ValueError(f"per-row augmentation kinds must be [{n}] integers in 0..{max(AUGMENT_KINDS.values())}")
+    return np.ascontiguousarray(raw, dtype=np.uint8)
+
+
+def augment(s, pi, legal_mask=None, kind="hflip", device_index: int = 0):
+    """The trainer's augmentation of rows (train.py:280-305): s f32 [n,P,8,8], pi f32 [n,4672], legal_mask [n,4672] or None ->
+    (s', pi', legal_mask') of the same shapes (legal_mask' u8, or None), transformed on the device (m0_augment_rows,
+    include/m0_augment.h).  kind: "hflip" (files mirrored, build_horizontal_flip_permutation on the move types), "rot180" (ranks
+    and files, build_rotate180_permutation), "none" (a copy), or one kind of AUGMENT_KINDS' values per row.  Values travel as their
+    bits.  This is the trainer's transform, not a symmetry of chess: see DESIGN.md section 8."""
+    a = np.ascontiguousarray(s, dtype=np.float32)
+    if a.ndim != 4 or a.shape[2:] != (8, 8) or a.shape[1] <= 0:
+        raise ValueError(f"expected planes [n,P,8,8], got {a.shape}")
+    n = int(a.shape[0])
+    p = np.ascontiguousarray(pi, dtype=np.float32)
+    if p.shape != (n, LEGACY_POLICY_SIZE):
+        raise ValueError(f"expected pi [{n},{LEGACY_POLICY_SIZE}], got {p.shape}")
+    m = None
+    if legal_mask is not None:
+        m = np.ascontiguousarray(np.asarray(legal_mask).reshape(n, -1), dtype=np.uint8)
+        if m.shape != p.shape:
+            raise ValueError(f"expected legal_mask [{n},{LEGACY_POLICY_SIZE}], got {m.shape}")
+    kinds = augment_kinds(kind, n)
+    s_out, pi_out = np.empty_like(a), np.empty_like(p)
+    m_out = None if m is None else np.empty_like(m)
+    if n:
+        _lib.check(_lib.lib().m0_augment_rows(int(device_index), ptr(a), int(a.shape[1]), ptr(p), ptr(m), ptr(kinds), n, ptr(s_out),
+                                              ptr(pi_out), ptr(m_out)), "m0_augment_rows")
+    return s_out, pi_out, m_out

@@ -33,6 +33,21 @@ for a read-only score: it is refused.  Without ssl the report, the per-sample fi
     [--ssl [auto|stored|planes]] [--ssl-weight X] [--ssl-task-weight task=X ...]
 --ssl-weight defaults to training.ssl_weight (0.1 when absent, train.py:1306), a task's weight to model.ssl_<task>_weight (1).
 With --per-sample the 16 SSL columns are written under the key `ssl_columns`.
+
+The trainer's augmentations (augment=..., --augment): the reference's trainer (train.py:280-305, augment=True by default) draws one
+r per batch and mirrors the files of s, pi and legal_mask when r < 0.5, rotates them by 180 degrees when 0.5 <= r < 0.75 and
+training.augment_rotate180 holds (default true), and otherwise leaves them alone -- so what it optimises is mostly the loss on
+transformed rows.  augment="none" | "hflip" | "rot180" scores every row under that kind (M0Backend.score(augment=...) ->
+m0_net_score_aug, include/m0_augment.h: one upload, the transform on the device) and the report says which under "augment".
+augment="trainer" scores every row under all three kinds (three forwards) and adds the block "augment" to the report, overall and
+per shard: `by_kind` (the figures above for each kind), `weights` and `expected` = the policy loss, value loss and total the
+trainer's draw gives in expectation, 0.5 hflip + 0.25 rot180 + 0.25 none, or 0.5 hflip + 0.5 none with
+training.augment_rotate180: false (the elif chain of train.py:284-295), and `symmetry_gap`: the mean and the largest per-row
+absolute difference of policy loss and value loss between "none" and "hflip", over the rows scored under both.  The figures
+at the top of the report are then those of "none".  With --per-sample every kind's columns are written under
+`columns_<kind>`.  The trainer leaves stored SSL targets untransformed, and targets taken from rotated planes are not positions the
+decoder accepts: ssl together with an augmentation other than "none" is refused.  Without augment nothing changes.
+    [--augment none|hflip|rot180|trainer]
 """
 from __future__ import annotations
 
@@ -44,7 +59,7 @@ from typing import Dict, List, Mapping, Optional, Sequence
 
 import numpy as np
 
-from ._abi import POLICY_SIZE, SCORE_COLS, SCORE_FLAGS, SSL_BITS, SSL_SCORE_COLS, SSL_SCORE_FLAGS
+from ._abi import AUGMENT_KINDS, POLICY_SIZE, SCORE_COLS, SCORE_FLAGS, SSL_BITS, SSL_SCORE_COLS, SSL_SCORE_FLAGS
 from .backend import NonFiniteScore, resolve_mask_mode
 from .npz_dataset import ReplayReader
 
@@ -53,6 +68,22 @@ _LEFT_OUT = SCORE_FLAGS["empty"] | SCORE_FLAGS["nonfinite"]
 SSL_MODES = ("auto", "stored", "planes")
 SSL_TASKS = tuple(SSL_BITS)                      # the order of the heads and of a row's target maps
 SSL_FLAGS_COL = SSL_SCORE_COLS - 1
+AUGMENT_MODES = tuple(AUGMENT_KINDS) + ("trainer",)
+
+
+def trainer_weights(augment_rotate180: bool = True) -> Dict[str, float]:
+    """The share of batches the trainer's one draw r gives each kind (train.py:282-295): r < 0.5 mirrors, 0.5 <= r < 0.75 rotates
+    when augment_rotate180, everything else stays."""
+    rot = 0.25 if augment_rotate180 else 0.0
+    return {"hflip": 0.5, "rot180": rot, "none": 0.5 - rot}
+
+
+def _check_augment(augment, ssl) -> None:
+    if isinstance(augment, str) and augment not in AUGMENT_MODES:
+        raise ValueError(f"augment must be one of {AUGMENT_MODES}, a per-row array of kinds or None, got {augment!r}")
+    if ssl is not None and augment is not None and not (isinstance(augment, str) and augment == "none"):
+        raise ValueError("ssl cannot be combined with an augmentation other than 'none': the trainer leaves stored SSL targets "
+                         "untransformed, and targets taken from rotated planes are not positions the decoder accepts")
 
 
 def pack_ssl_targets(arrays: Mapping[str, np.ndarray], n: int, tasks: Sequence[str]) -> np.ndarray:
@@ -75,15 +106,26 @@ def pack_ssl_targets(arrays: Mapping[str, np.ndarray], n: int, tasks: Sequence[s
 
 
 def score_arrays(backend, s, pi, z, legal_mask=None, *, batch: int = 4096, mask_mode: Optional[str] = None,
-                 ssl: Optional[str] = None, ssl_targets: Optional[np.ndarray] = None, **opts):
+                 ssl: Optional[str] = None, ssl_targets: Optional[np.ndarray] = None, augment=None, **opts):
     """backend.score over the rows in chunks of `batch` (the last one partial): f32 [N, 8].  mask_mode None is resolved once,
     on the arrays given, not per chunk.  Rows of non-finite network outputs come back with flag 2 set; nothing is raised.
     With ssl ("stored": ssl_targets f32 [N,17,64] as pack_ssl_targets makes them; "planes"; "auto": stored when targets are
-    given) the chunks go through backend.score_ssl and the result is (f32 [N, 8], f32 [N, 16])."""
+    given) the chunks go through backend.score_ssl and the result is (f32 [N, 8], f32 [N, 16]).
+    augment: None for the rows as they are (backend.score is called as ever); "none", "hflip", "rot180" or a per-row u8 [N] of
+    AUGMENT_KINDS' values for the rows under that trainer augmentation (backend.score(augment=...)); "trainer" for all three,
+    f32 [3, N, 8] in AUGMENT_KINDS' order.  With ssl only None and "none" are accepted."""
     n = len(s)
     if batch <= 0:
         raise ValueError("batch must be positive")
+    _check_augment(augment, ssl)
     mode = resolve_mask_mode(pi, legal_mask, mask_mode)
+    if isinstance(augment, str) and augment == "trainer":
+        return np.stack([score_arrays(backend, s, pi, z, legal_mask, batch=batch, mask_mode=mode, augment=k, **opts)
+                         for k in AUGMENT_KINDS])
+    per_row = None if augment is None or isinstance(augment, str) else np.asarray(augment)
+    if per_row is not None and per_row.shape != (n,):
+        raise ValueError(f"per-row augmentation kinds must be [{n}], got {per_row.shape}")
+    more = lambda a, b: {} if augment is None or ssl is not None else {"augment": augment if per_row is None else per_row[a:b]}
     out = np.empty((n, SCORE_COLS), np.float32)
     if ssl is not None:
         if ssl not in SSL_MODES:
@@ -103,7 +145,8 @@ def score_arrays(backend, s, pi, z, legal_mask=None, *, batch: int = 4096, mask_
     for a in range(0, n, batch):
         b = min(n, a + batch)
         try:
-            out[a:b] = backend.score(s[a:b], pi[a:b], z[a:b], None if legal_mask is None else legal_mask[a:b], mask_mode=mode, **opts)
+            out[a:b] = backend.score(s[a:b], pi[a:b], z[a:b], None if legal_mask is None else legal_mask[a:b], mask_mode=mode, **opts,
+                                     **more(a, b))
         except NonFiniteScore as e:
             out[a:b] = e.rows
     return out
@@ -189,6 +232,43 @@ class SslSums:
         return out
 
 
+class AugmentSums:
+    """Sums per kind of rows scored under all three, and of the per-row gap between "none" and "hflip"; report() gives the
+    "augment" block of the module's docstring."""
+
+    def __init__(self):
+        self.kind = {k: Sums() for k in AUGMENT_KINDS}
+        self.gap_rows = 0
+        self.gap_sum = {"policy_loss": 0.0, "value_loss": 0.0}
+        self.gap_max = {"policy_loss": 0.0, "value_loss": 0.0}
+
+    def add(self, rows3: np.ndarray, z: np.ndarray) -> None:
+        for k, rows in zip(AUGMENT_KINDS, rows3):
+            self.kind[k].add(rows, z)
+        a = np.asarray(rows3[AUGMENT_KINDS["none"]], np.float64)
+        b = np.asarray(rows3[AUGMENT_KINDS["hflip"]], np.float64)
+        both = ((a[:, FLAGS].astype(np.int64) | b[:, FLAGS].astype(np.int64)) & _LEFT_OUT) == 0
+        self.gap_rows += int(both.sum())
+        for key, col in (("policy_loss", POLICY), ("value_loss", VALUE_LOSS)):
+            d = np.abs(a[both, col] - b[both, col])
+            self.gap_sum[key] += float(d.sum(dtype=np.float64))
+            if len(d):
+                self.gap_max[key] = max(self.gap_max[key], float(d.max()))
+
+    def report(self, weights: Mapping[str, float]) -> dict:
+        by_kind = {k: v.report() for k, v in self.kind.items()}
+        used = [k for k in AUGMENT_KINDS if weights[k] > 0]
+        expected = {}
+        for key in ("policy_loss", "value_loss", "total"):
+            parts = [by_kind[k][key] for k in used]
+            expected[key] = None if any(x is None for x in parts) else float(sum(weights[k] * x for k, x in zip(used, parts)))
+        n = self.gap_rows
+        gap = {key: {"mean": self.gap_sum[key] / n if n else None, "max": self.gap_max[key] if n else None}
+               for key in ("policy_loss", "value_loss")}
+        return {"mode": "trainer", "weights": {k: float(weights[k]) for k in AUGMENT_KINDS}, "by_kind": by_kind,
+                "expected": expected, "symmetry_gap": dict(gap, rows=n)}
+
+
 def _stored_ssl(path) -> Dict[str, np.ndarray]:
     with np.load(path) as d:
         return {k: d[k] for k in d.files if k.startswith("ssl_")}
@@ -197,7 +277,7 @@ def _stored_ssl(path) -> Dict[str, np.ndarray]:
 def score_shards(data_dir, backend, *, sources: Sequence[str] = ("selfplay", ""), batch: int = 4096,
                  per_sample: Optional[str] = None, expected_planes: int = 19, ssl: Optional[str] = None,
                  ssl_weight: float = 0.1, ssl_task_weights: Optional[Mapping[str, float]] = None,
-                 ssl_target_weight: float = 1.0, **opts) -> dict:
+                 ssl_target_weight: float = 1.0, augment: Optional[str] = None, augment_rotate180: bool = True, **opts) -> dict:
     """The report over every readable shard of `data_dir` whose source is in `sources`: the overall figures, "by_source",
     "by_shard" (keyed by file name, in the table's order, each with its "mask_mode") and "skipped" (shards that do not load
     or do not hold 4672 columns; nothing is marked in the table -- this tool only reads).  per_sample=PATH also writes
@@ -205,7 +285,16 @@ def score_shards(data_dir, backend, *, sources: Sequence[str] = ("selfplay", "")
     ssl="auto" | "stored" | "planes" adds the "ssl" blocks of the module's docstring (a shard's also says its "targets":
     "stored" or "planes") and ssl_columns f32 [N, 16] to the per-sample file; ssl_weight is training.ssl_weight (its default
     there is 0.1, train.py:1306), ssl_task_weights {task: weight} defaults to backend.model_cfg's ssl_<task>_weight.  ssl=None
-    adds nothing."""
+    adds nothing.  augment="none" | "hflip" | "rot180" scores the rows under that trainer augmentation and names it under
+    "augment"; augment="trainer" scores them under all three and adds the "augment" block of the module's docstring (overall and
+    per shard), weighted by trainer_weights(augment_rotate180); the per-sample file gains columns_<kind>.  augment=None adds
+    nothing."""
+    if augment is not None and not isinstance(augment, str):
+        raise ValueError("score_shards takes an augmentation by name")
+    _check_augment(augment, ssl)
+    trainer = augment == "trainer"
+    weights = trainer_weights(augment_rotate180)
+    aug_total = AugmentSums()
     if ssl is not None:
         if ssl not in SSL_MODES:
             raise ValueError(f"ssl must be one of {SSL_MODES} or None, got {ssl!r}")
@@ -222,6 +311,7 @@ def score_shards(data_dir, backend, *, sources: Sequence[str] = ("selfplay", "")
     total, by_source, by_shard, skipped = Sums(), {}, {}, []
     ssl_total, ssl_by_source = SslSums(), {}
     keep: Dict[str, List[np.ndarray]] = {"columns": [], "shard_index": [], "row": [], "ssl_columns": []}
+    keep.update({"columns_" + k: [] for k in AUGMENT_KINDS})
     for path, _, source, corrupted in reader.index.rows():
         source = source or ""
         if corrupted or source not in sources or not Path(path).exists():
@@ -235,8 +325,13 @@ def score_shards(data_dir, backend, *, sources: Sequence[str] = ("selfplay", "")
             continue
         s, pi, z, mask = got
         mode = resolve_mask_mode(pi, mask, opts.get("mask_mode"))
-        if ssl is None:
-            rows = score_arrays(backend, s, pi, z, mask, batch=batch, **dict(opts, mask_mode=mode))
+        rows3 = None
+        if trainer:
+            rows3 = score_arrays(backend, s, pi, z, mask, batch=batch, augment="trainer", **dict(opts, mask_mode=mode))
+            rows = rows3[AUGMENT_KINDS["none"]]
+        elif ssl is None:
+            rows = score_arrays(backend, s, pi, z, mask, batch=batch, **dict(opts, mask_mode=mode),
+                                **({} if augment is None else {"augment": augment}))
         else:
             have = {} if ssl == "planes" else _stored_ssl(path)
             stored = ssl == "stored" or (ssl == "auto" and all("ssl_" + t in have for t in tasks))
@@ -250,6 +345,11 @@ def score_shards(data_dir, backend, *, sources: Sequence[str] = ("selfplay", "")
         for sums in (total, by_source.setdefault(source, Sums()), one):
             sums.add(rows, z)
         by_shard[Path(path).name] = dict(one.report(), source=source, mask_mode=mode)
+        if trainer:
+            aug_one = AugmentSums()
+            for sums in (aug_total, aug_one):
+                sums.add(rows3, z)
+            by_shard[Path(path).name]["augment"] = aug_one.report(weights)
         if ssl is not None:
             ssl_one = SslSums()
             for sums in (ssl_total, ssl_by_source.setdefault(source, SslSums()), ssl_one):
@@ -261,13 +361,24 @@ def score_shards(data_dir, backend, *, sources: Sequence[str] = ("selfplay", "")
             keep["row"].append(np.arange(len(rows), dtype=np.int32))
             if ssl is not None:
                 keep["ssl_columns"].append(ssl_rows)
+            if trainer:
+                for k, r3 in zip(AUGMENT_KINDS, rows3):
+                    keep["columns_" + k].append(r3)
+            elif augment is not None:
+                keep["columns_" + augment].append(rows)
     if per_sample:
         cat = lambda key, dtype, shape: np.concatenate(keep[key]) if keep[key] else np.zeros(shape, dtype)
         more = {} if ssl is None else {"ssl_columns": cat("ssl_columns", np.float32, (0, SSL_SCORE_COLS))}
+        for k in (AUGMENT_KINDS if trainer else () if augment is None else (augment,)):
+            more["columns_" + k] = cat("columns_" + k, np.float32, (0, SCORE_COLS))
         with open(per_sample, "wb") as f:
             np.savez(f, columns=cat("columns", np.float32, (0, SCORE_COLS)), shard_index=cat("shard_index", np.int32, (0,)),
                      row=cat("row", np.int32, (0,)), shards=np.array(list(by_shard), dtype=str), **more)
     report = dict(total.report(), by_source={k: v.report() for k, v in by_source.items()}, by_shard=by_shard, skipped=skipped)
+    if trainer:
+        report["augment"] = aug_total.report(weights)
+    elif augment is not None:
+        report["augment"] = {"mode": augment}
     if ssl is not None:
         report["ssl"] = ssl_report(ssl_total, report)
         for k, v in ssl_by_source.items():
@@ -307,6 +418,19 @@ def ssl_summary_line(name: str, r: dict) -> str:
             f"flags {x['flags']['planes']}/{x['flags']['nonfinite']}/{x['flags']['mismatch']}")
 
 
+def augment_summary_line(name: str, r: dict) -> str:
+    f = lambda x: "    n/a" if x is None else f"{x:7.4f}"
+    x = r["augment"]
+    if x["mode"] != "trainer":
+        return f"{name}  augment {x['mode']}: the figures above are those of the rows under it"
+    kinds = "  ".join(f"{k} policy {f(v['policy_loss'])} value {f(v['value_loss'])} total {f(v['total'])}" for k, v in x["by_kind"].items())
+    w, e, g = x["weights"], x["expected"], x["symmetry_gap"]
+    return (f"{name}  augment trainer  {kinds}  expected ({w['hflip']:g} hflip + {w['rot180']:g} rot180 + {w['none']:g} none) "
+            f"policy {f(e['policy_loss'])} value {f(e['value_loss'])} total {f(e['total'])}  symmetry gap none/hflip over {g['rows']} rows: "
+            f"policy mean {f(g['policy_loss']['mean'])} max {f(g['policy_loss']['max'])}  value mean {f(g['value_loss']['mean'])} "
+            f"max {f(g['value_loss']['max'])}")
+
+
 def summary_line(name: str, r: dict) -> str:
     f = lambda x: "    n/a" if x is None else f"{x:7.4f}"
     return (f"{name}  rows {r['rows']} scored {r['scored']}  policy {f(r['policy_loss'])}  kl {f(r['kl'])}  value {f(r['value_loss'])}  "
@@ -332,6 +456,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="also score the SSL heads: targets as stored, from the planes, or per shard (auto, the default of --ssl)")
     ap.add_argument("--ssl-weight", type=float, default=None, help="overrides training.ssl_weight")
     ap.add_argument("--ssl-task-weight", action="append", default=[], metavar="TASK=X", help="overrides model.ssl_<task>_weight")
+    ap.add_argument("--augment", default=None, choices=list(AUGMENT_MODES),
+                    help="score the rows under a trainer augmentation; trainer: under all three, with the loss the trainer's draw "
+                         "expects (training.augment_rotate180 of the config decides the weights) and the none/hflip symmetry gap")
     ap.add_argument("--device", type=int, default=0)
     return ap
 
@@ -343,7 +470,11 @@ def load_backend(model_cfg: dict, checkpoint: str, device: int):
 
 def main(argv: Optional[List[str]] = None) -> int:
     from .analysis import load_config
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.ssl and args.augment not in (None, "none"):
+        parser.error("--ssl cannot be combined with --augment other than none: the trainer leaves stored SSL targets untransformed, "
+                     "and targets taken from rotated planes are not positions the decoder accepts")
     cfg = load_config(args.config)
     model_cfg = cfg.get("model", {}) or {}
     opts = training_opts(cfg, args.label_smoothing, args.value_loss, args.huber_delta)
@@ -351,6 +482,9 @@ def main(argv: Optional[List[str]] = None) -> int:
     if args.ssl:
         pairs = [w.partition("=") for w in args.ssl_task_weight]
         more = dict(ssl_opts(cfg, ssl_weight=args.ssl_weight, task_weights={t: float(x) for t, _, x in pairs}), ssl=args.ssl)
+    aug = {}
+    if args.augment:
+        aug = {"augment": args.augment, "augment_rotate180": bool((cfg.get("training", {}) or {}).get("augment_rotate180", True))}
     reports, nonfinite = {}, 0
     for k, ckpt in enumerate(args.checkpoint):
         per = args.per_sample
@@ -359,7 +493,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         be = load_backend(model_cfg, ckpt, args.device)
         try:
             r = score_shards(args.data, be, sources=tuple(args.sources), batch=args.batch, per_sample=per,
-                             expected_planes=int(model_cfg.get("planes", 19)), **opts, **more)
+                             expected_planes=int(model_cfg.get("planes", 19)), **opts, **more, **aug)
         finally:
             be.close()
         reports[ckpt] = r
@@ -368,10 +502,15 @@ def main(argv: Optional[List[str]] = None) -> int:
         if args.ssl:
             nonfinite += r["ssl"]["flags"]["nonfinite"]
             print(ssl_summary_line(ckpt, r), flush=True)
+        if args.augment:
+            if args.augment == "trainer":
+                nonfinite += sum(v["flags"]["nonfinite"] for k, v in r["augment"]["by_kind"].items() if k != "none")
+            print(augment_summary_line(ckpt, r), flush=True)
     if args.json:
         with open(args.json, "w") as f:
             json.dump(dict({"options": opts, "sources": list(args.sources), "checkpoints": reports},
-                           **({"ssl_options": more} if args.ssl else {})), f, indent=1)
+                           **({"ssl_options": more} if args.ssl else {}), **({"augment_options": aug} if args.augment else {})),
+                      f, indent=1)
     return 1 if nonfinite else 0
 
 
