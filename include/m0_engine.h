@@ -589,4 +589,6 @@ int m0_replay_games(int hip_device, const char* const* start_fens, const uint32_
 #include "m0_gumbel.h"
 /* the trainer's flip and rotate augmentations of stored rows on the device, and the training loss under them */
 #include "m0_augment.h"
+/* proof search: exact wins, losses and draws backed up the search tree (opt-in) */
+#include "m0_proof.h"
 #endif /* M0_ENGINE_H */

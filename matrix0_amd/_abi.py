@@ -119,6 +119,10 @@ class ScoreOpts(C.Structure):
     _fields_ = [("mask_mode", i32), ("label_smoothing", f32), ("value_loss", i32), ("huber_delta", f32)]
 
 
+class ProofLines(C.Structure):
+    _fields_ = [("proof", i32), ("proof_plies", i32), ("line_proof", i32 * AN_MAX_LINES), ("line_proof_plies", i32 * AN_MAX_LINES)]
+
+
 class GumbelCfg(C.Structure):
     _fields_ = [("max_considered", i32), ("c_visit", f64), ("c_scale", f64)]
 
@@ -279,14 +283,24 @@ AUGMENT_FUNCTIONS = {
     "m0_augment_bench": (i32, [i32, i32, i32, P(f32), P(f64)]),
 }
 
+# ---- include/m0_proof.h (which m0_engine.h includes too): the proof search, in that header's order;
+# tests/test_abi_proof.py compares the two ----
+PROOF_STRUCTS = {"m0_proof_lines": ProofLines}
+PROOF_FUNCTIONS = {
+    "m0_selfplay_set_proof": (i32, [vp, i32]),
+    "m0_search_proof_result": (i32, [vp, i32, _pi32, _pi32, vp, vp, _pi32]),
+    "m0_analysis_last_proof": (i32, [vp, P(ProofLines)]),
+    "m0_proof_combine": (i32, [i32, vp, vp, i32, _pi32, _pi32]),
+}
+
 
 def bind(L) -> list:
     """Set restype and argtypes of every function of FUNCTIONS, LIVE_FUNCTIONS, SCORE_FUNCTIONS, SSL_SCORE_FUNCTIONS,
-    GUMBEL_FUNCTIONS and AUGMENT_FUNCTIONS on the loaded library; the names it does not export."""
+    GUMBEL_FUNCTIONS, AUGMENT_FUNCTIONS and PROOF_FUNCTIONS on the loaded library; the names it does not export."""
     missing = []
     for name, (restype, argtypes) in (list(FUNCTIONS.items()) + list(LIVE_FUNCTIONS.items()) + list(SCORE_FUNCTIONS.items()) +
                                       list(SSL_SCORE_FUNCTIONS.items()) + list(GUMBEL_FUNCTIONS.items()) +
-                                      list(AUGMENT_FUNCTIONS.items())):
+                                      list(AUGMENT_FUNCTIONS.items()) + list(PROOF_FUNCTIONS.items())):
         fn = getattr(L, name, None)
         if fn is None:
             missing.append(name)

@@ -48,7 +48,7 @@ class Analyzer:
 
     def __init__(self, backend, cfg_dict: dict, *, slots: int = 256, multipv: int = 1, pv_len: int = 8, dirichlet: bool = False,
                  leaves_per_step: Optional[int] = None, max_sims: Optional[int] = None, seed: Optional[int] = None,
-                 tablebase=None, tb_men: int = 4):
+                 tablebase=None, tb_men: int = 4, prove: bool = False):
         if not 1 <= int(multipv) <= eng.AN_MAX_LINES or not 1 <= int(pv_len) <= eng.AN_MAX_PV:
             raise ValueError(f"multipv must be in [1, {eng.AN_MAX_LINES}] and pv_len in [1, {eng.AN_MAX_PV}]")
         self.multipv = int(multipv)
@@ -59,6 +59,8 @@ class Analyzer:
         self.cfg = cfg
         self.engine = self._make_engine(backend, cfg, multipv=self.multipv, pv_len=int(pv_len), dirichlet=bool(dirichlet))
         self._tb_owned = None
+        if prove:                                   # the proof search: results carry `proof` / `proof_plies`, proven lines rank first
+            self.engine.set_proof()
         if tablebase is not None:
             try:
                 if isinstance(tablebase, (str, os.PathLike)):        # a cache file: loaded here, closed with the analyzer
@@ -198,6 +200,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--tablebase", default=None, metavar="PATH", help="cache file of generated endgame tables (matrix0_amd.tablebase)")
     ap.add_argument("--tb-men", type=int, default=4, help="probe positions with at most this many men (default 4)")
+    ap.add_argument("--prove", action="store_true",
+                    help="proof search: exact wins, losses and draws are backed up the tree, a proven root ends its search, and "
+                         "the output carries proof / proof_plies for the root and every line")
     return ap
 
 
@@ -211,8 +216,8 @@ def load_config(path: str) -> dict:
 
 def result_line(r: dict) -> str:
     """The JSON object the command line prints for one position."""
-    keys = ("fen", "moves", "status", "nlegal", "sims", "root_n", "root_q", "value", "evals", "lines")
-    return json.dumps({k: r[k] for k in keys})
+    keys = ("fen", "moves", "status", "nlegal", "sims", "root_n", "root_q", "value", "evals", "lines", "proof", "proof_plies")
+    return json.dumps({k: r[k] for k in keys if k in r})
 
 
 def main(argv: Optional[List[str]] = None) -> int:
@@ -226,6 +231,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         kw["max_sims"] = args.sims
     if args.tablebase:
         kw.update(tablebase=args.tablebase, tb_men=args.tb_men)
+    if args.prove:
+        kw["prove"] = True
     with Analyzer(be, cfg, **kw) as an:
         results = an.evaluate(positions) if args.sims == 0 else an.analyse(positions, args.sims)
     for r in results:

@@ -128,7 +128,9 @@ def play_match(backend_a, backend_b, games: int, cfg: dict, seed: Optional[int] 
     games 2k and 2k+1 from the same one; `max_moves` then counts the plies played from there.  Details of the last match
     (W/L/D, win rate, Wilson interval, Elo, evaluations made and served from the cache, the records with their `start_fen`) are
     left in `last_match_stats`.  `tablebase` (a Tablebase) or `engine.tablebase` with `in_search: true` in `cfg`: the endgame tables
-    are probed inside the searches and end a game that enters them, with their result."""
+    are probed inside the searches and end a game that enters them, with their result.  `engine.proof_search: true` in `cfg`: the
+    proof search (SelfplayEngine.set_proof) -- a proven mate is played, a move that is proven lost is not, a search ends once
+    its root is proven."""
     global last_match_stats
     if games <= 0:
         return 0.0
@@ -169,6 +171,8 @@ def play_match(backend_a, backend_b, games: int, cfg: dict, seed: Optional[int] 
             e.set_openings(book)
         if tb is not None:
             e.set_search_tablebase(tb, tb_limit)
+        if bool(ecfg.get("proof_search", False)):
+            e.set_proof()                       # exact wins, losses and draws are backed up the tree; the engine plays the search's pick
         while e.running():
             e.step(8)
             while (r := e.poll()) is not None:

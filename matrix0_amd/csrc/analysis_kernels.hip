@@ -29,8 +29,20 @@ __device__ __forceinline__ void pad_pv(m0_analysis_line* L, int from) {
     for (int i = from; i < M0_AN_MAX_PV; ++i) L->pv[i] = 0;
 }
 
+// A root child's rank key in the proof search's ranking, larger first: a child that is LOSS for its own mover is a winning move
+// (fewest plies first), one that is WIN a losing move (most plies first), the others go by visits in between.
+__device__ __forceinline__ int proof_rank_key(int16_t child, int n) {
+    const int s = proof_state(child);
+    if (s == PROOF_LOSS) return (2 << 24) + (PROOF_MAX_PLIES - proof_plies(child));
+    if (s == PROOF_WIN) return proof_plies(child);
+    return (1 << 24) + (n < (1 << 24) - 1 ? n : (1 << 24) - 1);
+}
+
+// PROOF: the instantiation for engines that run the proof search (launch_analysis_lines with proof_dev); the other one is the
+// kernel it was.
+template <bool PROOF>
 __global__ __launch_bounds__(64) void analysis_lines_kernel(TreeDev d, const int* slots, int multipv, int pv_len,
-                                                            m0_analysis_line* lines, int* nlines) {
+                                                            m0_analysis_line* lines, int* nlines, m0_proof_lines* proofs) {
     const int j = blockIdx.x, l = blockIdx.y, lane = threadIdx.x;
     const int g = slots[j];
     const GameDev* gd = &d.games[g];
@@ -40,10 +52,20 @@ __global__ __launch_bounds__(64) void analysis_lines_kernel(TreeDev d, const int
     const int cb = A.cbase[root];
     const int nl = multipv < nc ? multipv : nc;
     if (l == 0 && lane == 0) nlines[j] = nl;
+    if constexpr (PROOF) {                                             // the root's proof, and NONE for the lines nobody writes
+        m0_proof_lines* PL = proofs + j;
+        if (l == 0 && lane == 0) { PL->proof = proof_state(A.proof[root]); PL->proof_plies = proof_plies(A.proof[root]); }
+        if (l == 0 && lane >= multipv && lane < M0_AN_MAX_LINES) { PL->line_proof[lane] = 0; PL->line_proof_plies[lane] = 0; }
+        if (l >= nl && lane == 0) { PL->line_proof[l] = 0; PL->line_proof_plies[l] = 0; }
+    }
     if (l >= nl) return;                                               // lines beyond the root's children are not written
     int cn[CPL], rank[CPL];
 #pragma unroll
-    for (int k = 0; k < CPL; ++k) { const int i = lane + 64 * k; cn[k] = i < nc ? A.n[cb + i] : -1; }
+    for (int k = 0; k < CPL; ++k) {
+        const int i = lane + 64 * k;
+        cn[k] = i < nc ? A.n[cb + i] : -1;
+        if constexpr (PROOF) { if (i < nc) cn[k] = proof_rank_key(A.proof[cb + i], cn[k]); }
+    }
     rank_descending(cn, nc, lane, rank);
     int mine = -1;                                                     // exactly one (lane, k) holds rank l
 #pragma unroll
@@ -56,18 +78,34 @@ __global__ __launch_bounds__(64) void analysis_lines_kernel(TreeDev d, const int
         L->move = A.mv[node]; L->policy_index = A.midx[node]; L->visits = A.n[node];
         L->prior = (float)A.prior[node]; L->q = A.q[node];
         L->pv[0] = A.mv[node];
+        if constexpr (PROOF) {                                         // the line's proof from the root mover's view
+            const int16_t cp = A.proof[node];
+            const int cs = proof_state(cp);
+            proofs[j].line_proof[l] = cs == PROOF_LOSS ? PROOF_WIN : (cs == PROOF_WIN ? PROOF_LOSS : cs);
+            proofs[j].line_proof_plies[l] = cs == PROOF_LOSS || cs == PROOF_WIN ? proof_plies(cp) + 1 : 0;
+        }
     }
     // the most visited line from there: one round of dependent loads per level (the scan of a node's children also fetches
     // each child's own child block, the winner's is passed round)
     int len = 1;
     int nch = A.nch[node], cbn = A.cbase[node];
+    int ns = PROOF_NONE;                                               // proof search: the state of the node the line stands at
+    if constexpr (PROOF) ns = proof_state(A.proof[node]);
     while (len < pv_len && nch > 0) {
         int bn = -1, bi = -1, b_nch = -1, b_cb = -1;
         Move b_mv = 0;
         for (int i = lane; i < nch; i += 64) {
             const int c = cbn + i;
-            const int n = A.n[c], c_nch = A.nch[c], c_cb = A.cbase[c];
+            int n = A.n[c];
+            const int c_nch = A.nch[c], c_cb = A.cbase[c];
             const Move m = A.mv[c];
+            if constexpr (PROOF) {                                     // at a proven node: the move the proof search picks there
+                if (ns != PROOF_NONE) {
+                    const int16_t cp = A.proof[c];
+                    if (!proof_pick_eligible(ns, cp, true)) continue;
+                    n = (1 << 20) + proof_pick_key(ns, cp, n < (1 << 19) ? n : (1 << 19));     // above 0: `wn <= 0` is for visits
+                }
+            }
             if (n > bn) { bn = n; bi = i; b_nch = c_nch; b_cb = c_cb; b_mv = m; }
         }
         int wn = bn, wi = bi;
@@ -78,6 +116,7 @@ __global__ __launch_bounds__(64) void analysis_lines_kernel(TreeDev d, const int
         if (wn <= 0) break;                                            // no child was visited
         const int wl = wi & 63;                                        // the lane that scanned child wi holds it as its best
         const Move m = (Move)__shfl((int)b_mv, wl);
+        if constexpr (PROOF) ns = proof_state(A.proof[cbn + wi]);
         nch = __shfl(b_nch, wl); cbn = __shfl(b_cb, wl);
         if (lane == 0) L->pv[len] = m;
         ++len;
@@ -86,9 +125,13 @@ __global__ __launch_bounds__(64) void analysis_lines_kernel(TreeDev d, const int
 }
 
 hipError_t launch_analysis_lines(const TreeDev& d, const int* slots_dev, int count, int multipv, int pv_len,
-                                 m0_analysis_line* lines_dev, int* nlines_dev, hipStream_t st) {
+                                 m0_analysis_line* lines_dev, int* nlines_dev, hipStream_t st, m0_proof_lines* proof_dev) {
     if (count <= 0) return hipSuccess;
-    hipLaunchKernelGGL(analysis_lines_kernel, dim3(count, multipv), dim3(64), 0, st, d, slots_dev, multipv, pv_len, lines_dev, nlines_dev);
+    if (proof_dev && !d.t.proof) return hipErrorInvalidValue;
+    if (proof_dev) hipLaunchKernelGGL(analysis_lines_kernel<true>, dim3(count, multipv), dim3(64), 0, st, d, slots_dev, multipv, pv_len,
+                                      lines_dev, nlines_dev, proof_dev);
+    else hipLaunchKernelGGL(analysis_lines_kernel<false>, dim3(count, multipv), dim3(64), 0, st, d, slots_dev, multipv, pv_len, lines_dev,
+                            nlines_dev, proof_dev);
     return hipGetLastError();
 }
 

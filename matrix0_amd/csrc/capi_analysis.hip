@@ -33,9 +33,20 @@ static m0_analysis_result blank_result(const AnalysisJob& job) {
 }
 
 // A result joins the answered ones with its root children ((policy index, visits) pairs, empty unless a harvest kept them).
-static void answer(Analysis& a, const m0_analysis_result& r, std::vector<int32_t>&& children = std::vector<int32_t>()) {
+static void answer(Analysis& a, const m0_analysis_result& r, std::vector<int32_t>&& children = std::vector<int32_t>(),
+                   const m0_proof_lines& proof = m0_proof_lines{}) {
     a.done.push_back(r);
     a.done_children.push_back(std::move(children));
+    a.done_proof.push_back(proof);
+}
+// the result kernel's proof output, where the engine runs the proof search
+static m0_proof_lines* proof_out(const m0_selfplay* sp) { return sp->tc.proof ? sp->an->proof_dev : nullptr; }
+// the front of the answered results leaves: its proofs are what m0_analysis_last_proof returns from now on
+static void pop_done(Analysis& a) {
+    a.last_proof = a.done_proof.front();
+    a.done.pop_front();
+    a.done_children.pop_front();
+    a.done_proof.pop_front();
 }
 
 // What m0_analysis_submit does with a position once it stands in job.line and job.nlegal is known: roots without legal moves
@@ -101,9 +112,12 @@ int analysis_harvest(m0_selfplay* sp) {
     if (nf == 0) return M0_OK;
     HipStatus& hs = sp->hip;
     M0_HIP(hs, hipMemcpyAsync(sp->ids_dev, a.finished.data(), (size_t)nf * 4, hipMemcpyHostToDevice, sp->stream));
-    M0_HIP(hs, launch_analysis_lines(sp->d, sp->ids_dev, nf, a.opts.multipv, a.opts.pv_len, a.lines_dev, a.nlines_dev, sp->stream));
+    M0_HIP(hs, launch_analysis_lines(sp->d, sp->ids_dev, nf, a.opts.multipv, a.opts.pv_len, a.lines_dev, a.nlines_dev, sp->stream,
+                                     proof_out(sp)));
     M0_HIP(hs, hipMemcpyAsync(a.hlines.data(), a.lines_dev, sizeof(m0_analysis_line) * M0_AN_MAX_LINES * nf, hipMemcpyDeviceToHost, sp->stream));
     M0_HIP(hs, hipMemcpyAsync(a.hnlines.data(), a.nlines_dev, (size_t)nf * 4, hipMemcpyDeviceToHost, sp->stream));
+    if (proof_out(sp))
+        M0_HIP(hs, hipMemcpyAsync(a.hproof.data(), a.proof_dev, sizeof(m0_proof_lines) * nf, hipMemcpyDeviceToHost, sp->stream));
     if (a.keep_visits) {           // the root children of the same searches, in the same trip
         M0_HIP(hs, launch_root_children(sp->d, sp->ids_dev, nf, a.child_idx_dev, a.child_n_dev, a.nchild_dev, sp->stream));
         M0_HIP(hs, hipMemcpyAsync(a.hchild_idx.data(), a.child_idx_dev, (size_t)nf * M0_MAX_CHILDREN * 4, hipMemcpyDeviceToHost, sp->stream));
@@ -128,7 +142,7 @@ int analysis_harvest(m0_selfplay* sp) {
             children.assign(ci, ci + k);
             children.insert(children.end(), cn, cn + k);
         }
-        answer(a, r, std::move(children));
+        answer(a, r, std::move(children), proof_out(sp) ? a.hproof[j] : m0_proof_lines{});
         g.active = 0; g.finished = 0;
         leave_slot(sp, s);
     }
@@ -197,11 +211,14 @@ template <typename Q> static typename Q::iterator queued(Q& q, int64_t id) {
 
 // The result of the search in slot s as it stands: the lines from the result kernel on that one slot (it reads the tree, not
 // the block a finished search writes), the rest from the slot's control block, read back first.
-static int live_result(m0_selfplay* sp, int s, m0_analysis_result& r) {
+static int live_result(m0_selfplay* sp, int s, m0_analysis_result& r, m0_proof_lines& proof) {
     Analysis& a = *sp->an;
     HipStatus& hs = sp->hip;
+    proof = m0_proof_lines{};
     M0_HIP(hs, hipMemcpyAsync(sp->ids_dev, &s, 4, hipMemcpyHostToDevice, sp->stream));
-    M0_HIP(hs, launch_analysis_lines(sp->d, sp->ids_dev, 1, a.opts.multipv, a.opts.pv_len, a.lines_dev, a.nlines_dev, sp->stream));
+    M0_HIP(hs, launch_analysis_lines(sp->d, sp->ids_dev, 1, a.opts.multipv, a.opts.pv_len, a.lines_dev, a.nlines_dev, sp->stream,
+                                     proof_out(sp)));
+    if (proof_out(sp)) M0_HIP(hs, hipMemcpyAsync(&proof, a.proof_dev, sizeof(m0_proof_lines), hipMemcpyDeviceToHost, sp->stream));
     M0_HIP(hs, hipMemcpyAsync(a.hlines.data(), a.lines_dev, sizeof(m0_analysis_line) * M0_AN_MAX_LINES, hipMemcpyDeviceToHost, sp->stream));
     M0_HIP(hs, hipMemcpyAsync(a.hnlines.data(), a.nlines_dev, 4, hipMemcpyDeviceToHost, sp->stream));
     if (!sync_games_d2h(sp)) return m0_hip_error(hs, "reading a running search failed");
@@ -376,8 +393,7 @@ int m0_analysis_poll(m0_selfplay* sp, m0_analysis_result* out) {
     if (!out) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     if (sp->an->done.empty()) return 0;
     *out = sp->an->done.front();
-    sp->an->done.pop_front();
-    sp->an->done_children.pop_front();
+    pop_done(*sp->an);
     return 1;
 }
 
@@ -392,9 +408,16 @@ int m0_analysis_poll_visits(m0_selfplay* sp, m0_analysis_result* out, int32_t* n
     const int k = (int)(ch.size() / 2);
     *nchild = k;
     if (k > 0) { memcpy(policy_idx, ch.data(), (size_t)k * 4); memcpy(visits, ch.data() + k, (size_t)k * 4); }
-    sp->an->done.pop_front();
-    sp->an->done_children.pop_front();
+    pop_done(*sp->an);
     return 1;
+}
+
+int m0_analysis_last_proof(m0_selfplay* sp, m0_proof_lines* out) {
+    M0_ENGINE_CALL(sp, "m0_analysis_last_proof", KIND_ANALYSIS, false);
+    if (!out) { m0_set_error("null argument"); return M0_ERR_INVALID; }
+    if (!sp->tc.proof) { m0_set_error("m0_analysis_last_proof: the proof search is not set on this engine"); return M0_ERR_STATE; }
+    *out = sp->an->last_proof;
+    return M0_OK;
 }
 
 int m0_analysis_pending(m0_selfplay* sp) {
@@ -423,7 +446,7 @@ int m0_analysis_peek(m0_selfplay* sp, int64_t id, m0_analysis_result* out) {
         return M0_ERR_INVALID;
     }
     m0_analysis_result r;
-    const int rc = live_result(sp, s, r);
+    const int rc = live_result(sp, s, r, a.last_proof);
     if (rc != M0_OK) return rc;
     *out = r;
     return 1;
@@ -444,10 +467,11 @@ int m0_analysis_stop(m0_selfplay* sp, int64_t id) {
         return M0_OK;
     }
     m0_analysis_result r;
-    const int rc = live_result(sp, s, r);
+    m0_proof_lines proof;
+    const int rc = live_result(sp, s, r, proof);
     if (rc != M0_OK) return rc;
     if (r.overflow) sp->stats.arena_overflows++;
-    answer(a, r);
+    answer(a, r, std::vector<int32_t>(), proof);
     sp->hg[s].active = 0; sp->hg[s].finished = 0;
     leave_slot(sp, s);
     sync_games_h2d(sp);

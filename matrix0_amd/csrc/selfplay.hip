@@ -264,8 +264,13 @@ static void finish_search(m0_selfplay* sp, int slot) {
     if (c.low_visit_threshold > 0 && maxv < c.low_visit_threshold && temp < 0.8) temp = 0.8;
     std::vector<int32_t> visits(R.child_n, R.child_n + k);
     int pick;
+    // proof search (include/m0_proof.h): a match engine plays the search's own move -- the shortest proven win, the longest
+    // defence, never a move that is proven lost while another is not; with nothing proven it is the most visited move
+    const ProofResult* PR = sp->tc.proof && sp->kind == EngineKind::Match ? &sp->hpres[slot] : nullptr;
     if (GR) {                                  // no temperature, no low_visit_threshold: the Gumbel draw is the sampling
         pick = GR->pick >= 0 && GR->pick < k ? GR->pick : 0;
+    } else if (PR && (PR->state != PROOF_NONE || !(c.arena_temp > 1e-3 && hgm.nstates < c.arena_temp_plies))) {
+        pick = PR->pick >= 0 && PR->pick < k ? PR->pick : 0;      // (a sampled opening ply stays sampled while nothing is proven)
     } else if (sp->kind == EngineKind::Match) {       // arena.py:73-106 (the uniform is drawn only on the sampling branch, as np.random.choice is)
         const bool sampling = c.arena_temp > 1e-3 && hgm.nstates < c.arena_temp_plies;
         pick = arena_choose_move(visits.data(), k, c.arena_temp, hgm.nstates, c.arena_temp_plies, sampling ? hgm.rng.next() : 0.0);
@@ -378,6 +383,8 @@ static int harvest_games(m0_selfplay* sp) {
     if (!M0_HIP(sp->hip, hipMemcpy(sp->hres.data(), sp->d.results, sizeof(RootResult) * sp->G, hipMemcpyDeviceToHost)))
         return m0_hip_error(sp->hip, "harvest failed");
     if (sp->tc.gumbel && !M0_HIP(sp->hip, hipMemcpy(sp->hgres.data(), sp->d.gumbel_results, sizeof(GumbelResult) * sp->G, hipMemcpyDeviceToHost)))
+        return m0_hip_error(sp->hip, "harvest failed");
+    if (sp->tc.proof && !M0_HIP(sp->hip, hipMemcpy(sp->hpres.data(), sp->d.proof_results, sizeof(ProofResult) * sp->G, hipMemcpyDeviceToHost)))
         return m0_hip_error(sp->hip, "harvest failed");
     for (int s = 0; s < sp->G; ++s) {
         if (!(sp->hg[s].active && sp->hg[s].finished)) continue;

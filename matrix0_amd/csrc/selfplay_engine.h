@@ -75,6 +75,12 @@ struct Analysis {
     std::deque<AnalysisJob> policy_queue;  // submitted policy-mode positions (sims = 0)
     std::deque<m0_analysis_result> done;   // answered, not yet polled
     std::deque<std::vector<int32_t>> done_children;   // beside `done`: the root children of each (answer(), capi_analysis.hip)
+    // proof search (m0_selfplay_set_proof on an analysis engine): beside `done` the proofs of each, the proofs of the result
+    // handed out last (m0_analysis_last_proof), and the result kernel's output for them
+    std::deque<m0_proof_lines> done_proof;
+    m0_proof_lines last_proof = {};
+    m0_proof_lines* proof_dev = nullptr;   // [G]
+    std::vector<m0_proof_lines> hproof;
     std::vector<AnalysisJob> slot_job;     // per slot: what it searches (the Line lives in games[slot])
     // A HELD slot (include/m0_analysis_live.h): its search was answered (finished or stopped) and its tree stays for
     // m0_analysis_continue: games[slot].in_use, hg[slot].active == 0, held[slot]; slot_job[slot].id is the held id.
@@ -157,6 +163,8 @@ struct m0_selfplay {
     // Gumbel root search (m0_selfplay_set_gumbel; the switch itself is tc.gumbel)
     std::vector<GumbelResult> hgres;      // host copies of d.gumbel_results, beside hres
     bool search_begun = false;            // m0_search_begin was called: the mode can no longer be set
+    // proof search (m0_selfplay_set_proof; the switch itself is tc.proof)
+    std::vector<ProofResult> hpres;       // host copies of d.proof_results, beside hres
 };
 
 namespace m0 {
@@ -191,8 +199,10 @@ inline bool hip_ok(m0_selfplay* sp, const char* context) {
 //   m0_search_*                                                     self-play, match (a match engine is accepted as it always
 //                                                                   was, although nothing drives one this way)
 //   m0_analysis_*                                                   analysis
+//   m0_search_proof_result                                          self-play, match
 //   m0_selfplay_stats_get, _running, _last_batch_nhwc,
-//   _set_search_tablebase, _tb_leaves, _tb_adjudications            every kind
+//   _set_search_tablebase, _tb_leaves, _tb_adjudications,
+//   m0_selfplay_set_proof                                           every kind
 bool kind_accepted(const m0_selfplay* sp, const char* what, unsigned kinds);   // false: the error string is set
 #define M0_ENGINE_CALL_OR(null_result, sp, what, kinds, on_device)                    \
     if (!(sp)) { m0_set_error(what ": sp is null"); return null_result; }             \

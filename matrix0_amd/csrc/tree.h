@@ -10,6 +10,7 @@ namespace m0 { struct TbSet; }   // tb_core.h
 // deliberate: the C ABI already fixes M0_POLICY_SIZE (logits per batch row) and M0_PLANES (input planes); one definition
 #include "../../include/m0_engine.h"
 #include "gumbel_core.h"
+#include "proof_core.h"
 
 #define M0_MAX_DEPTH 256      // path length cap (nodes)
 #define M0_HIST_CAP 192       // reversible-move history window (<= 150 by the 75-move rule)
@@ -44,6 +45,9 @@ struct TreeCfg {              // MCTSConfig fields the kernels read (mcts.py:61-
     // and by expand_kernel when a search finishes
     int gumbel;               // 1: the root level is sequential halving over Gumbel scores (tree_gumbel.h)
     m0_gumbel_cfg gumbel_cfg;
+    // proof search (m0_selfplay_set_proof, include/m0_proof.h): read by launch_select, which then runs the proof instantiation
+    // of select_kernel, and by expand_kernel when it decides whether a search has finished
+    int proof;                // 1: proven wins, losses and draws are backed up the tree (tree_proof.h)
 };
 
 // Per-game evaluation cache: what the network said about a position (value + the logits of its legal moves, in generation
@@ -140,6 +144,7 @@ struct TreeArrays {           // each [G][2*cap]
     uint16_t* mv;
     uint16_t* midx;
     int cap;                  // nodes per arena half
+    int16_t* proof;           // proof search: state and plies packed (proof_core.h), 0 = not proven; null = mode off
 };
 
 struct RootResult {           // written when a search finishes
@@ -159,6 +164,12 @@ struct GumbelResult {         // Gumbel root search: written beside RootResult w
     double v_mix;
     double pi[M0_MAX_CHILDREN];   // improved policy over the root children
     double gl[M0_MAX_CHILDREN];   // g + log(prior) of this search
+};
+
+struct ProofResult {          // proof search: written beside RootResult when a search finishes
+    int state, plies;         // the root's, from the view of its side to move
+    int pick;                 // the move: index into RootResult's children
+    int16_t child[M0_MAX_CHILDREN];   // every root child's state and plies, packed, from the view of the child's side to move
 };
 
 struct TreeDev {
@@ -189,6 +200,7 @@ struct TreeDev {
     int tb_max_pieces;        // ... for leaves with at most this many men
     double* gumbel_gl;        // Gumbel root search: [G][M0_MAX_CHILDREN] g + log(prior) of the running search; null = mode off
     GumbelResult* gumbel_results;   // [G]
+    ProofResult* proof_results;     // proof search: [G]; null = mode off
 };
 
 hipError_t launch_select(const TreeDev& d, const TreeCfg& c, hipStream_t st);
@@ -224,8 +236,11 @@ hipError_t launch_decode_planes(const float* planes_dev, const uint8_t* mask_dev
 // Results of the analysis engine (analysis_kernels.hip).  lines: M0_AN_MAX_LINES per entry, nlines: lines written per entry.
 // launch_analysis_lines: entry j = the finished search of slot slots_dev[j]: its root children by visits (ties by move order)
 // with the most-visited line behind each, at most pv_len moves.
+// proof_dev (proof search; null: the ranking above): per entry a m0_proof_lines -- the lines are then ranked as
+// m0_tb_root_lines ranks table roots (winning moves, shortest first; unproven and drawn moves by visits; losing moves, longest
+// first) and the variation behind a line follows the proof search's pick at every proven node.
 hipError_t launch_analysis_lines(const TreeDev& d, const int* slots_dev, int count, int multipv, int pv_len,
-                                 m0_analysis_line* lines_dev, int* nlines_dev, hipStream_t st);
+                                 m0_analysis_line* lines_dev, int* nlines_dev, hipStream_t st, m0_proof_lines* proof_dev = nullptr);
 // launch_root_children: entry j = the finished search of slot slots_dev[j]: (policy index, visits) of every root child in
 // move-generation order from the slot's RootResult, zero-padded to M0_MAX_CHILDREN, and their number.
 hipError_t launch_root_children(const TreeDev& d, const int* slots_dev, int count, int32_t* policy_idx_dev, int32_t* visits_dev,

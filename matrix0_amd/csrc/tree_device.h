@@ -41,23 +41,27 @@ static __device__ double gamma_draw(uint64_t seed, uint64_t& ctr, double a) {   
 
 struct Arena {
     double* prior; double* w; double* q; int* n; int* vl; int* cbase; int16_t* nch; uint16_t* mv; uint16_t* midx;
+    int16_t* proof;           // null unless the engine runs the proof search (TreeArrays::proof)
 };
 __device__ __forceinline__ Arena arena_of(const TreeArrays& t, int g, int half) {
     size_t b = ((size_t)g * 2 + half) * (size_t)t.cap;
     Arena a;
     a.prior = t.prior + b; a.w = t.w + b; a.q = t.q + b; a.n = t.n + b; a.vl = t.vl + b;
     a.cbase = t.cbase + b; a.nch = t.nch + b; a.mv = t.mv + b; a.midx = t.midx + b;
+    a.proof = t.proof ? t.proof + b : nullptr;
     return a;
 }
 // a new, unexpanded, unvisited node
 __device__ __forceinline__ void node_reset(const Arena& A, int i, double prior, Move mv, uint16_t midx) {
     A.prior[i] = prior; A.w[i] = 0.0; A.q[i] = 0.0; A.n[i] = 0; A.vl[i] = 0;
     A.cbase[i] = -1; A.nch[i] = -1; A.mv[i] = mv; A.midx[i] = midx;
+    if (A.proof) A.proof[i] = 0;
 }
 // node so of S -> node dn of D, without its in-flight count; the child base is still the one in S
 __device__ __forceinline__ void node_copy(const Arena& D, int dn, const Arena& S, int so) {
     D.prior[dn] = S.prior[so]; D.w[dn] = S.w[so]; D.q[dn] = S.q[so]; D.n[dn] = S.n[so]; D.vl[dn] = 0;
     D.cbase[dn] = S.cbase[so]; D.nch[dn] = S.nch[so]; D.mv[dn] = S.mv[so]; D.midx[dn] = S.midx[so];
+    if (D.proof) D.proof[dn] = S.proof[so];      // a kept subtree keeps its proofs
 }
 
 __device__ __forceinline__ float wave_max_f(float v) {

@@ -3,6 +3,7 @@
 // release, root result extraction.  The legal moves of every leaf come from select_kernel (TreeDev::leaf_moves).
 #include "tree_device.h"
 #include "tree_gumbel.h"
+#include "tree_proof.h"
 #include "eval_cache.h"
 
 struct ExpandScratch {          // workgroup-shared staging of one expansion (raw priors / pruning only)
@@ -344,8 +345,11 @@ __global__ __launch_bounds__(64) void expand_kernel(TreeDev d, TreeCfg c) {
     int* TN = c.tt_merge ? d.tt_nodes + tt_table_of(d, g, gd) : nullptr;
     const uint16_t* LM = d.leaf_moves + (size_t)g * (d.L + 1) * M0_MAX_CHILDREN;
     const int ns = gd->nsamples;
-    if (ns <= 0) return;
     const Arena A = arena_of(d.t, g, gd->arena);
+    // proof search: a search whose root is proven has finished, whatever is left of its budget -- also one that select_kernel
+    // gave no sample because its root was proven when it started (the subtree it took over)
+    const bool proven = c.proof && A.proof[gd->root] != 0;
+    if (ns <= 0 && !(proven && !gd->finished)) return;
     const ExpandEnv E{A, d.t.cap, gd, TK, TN, d.tt_cap, &X, lane};
     const Sample* S = d.samples + (size_t)g * (d.L + 1);
     const int* P = d.paths + (size_t)g * (d.L + 1) * M0_MAX_DEPTH;
@@ -408,7 +412,7 @@ __global__ __launch_bounds__(64) void expand_kernel(TreeDev d, TreeCfg c) {
     __syncthreads();
     const int done = gd->sims_done + sims;
     const int root = gd->root;
-    const bool fin = (A.nch[root] >= 0 || gd->overflow) && done >= gd->sims_target;
+    const bool fin = ((A.nch[root] >= 0 || gd->overflow) && done >= gd->sims_target) || proven;
     if (lane == 0) {
         gd->sims_done = done;
         gd->evals += evals;
@@ -419,6 +423,7 @@ __global__ __launch_bounds__(64) void expand_kernel(TreeDev d, TreeCfg c) {
     }
     if (fin) write_root_result(d.results + g, A, root, lane);
     if (fin && c.gumbel) write_gumbel_result(d, c, A, gd, g, root, lane);   // beside it: the move and the improved policy
+    if (fin && c.proof) write_proof_result(d, A, g, root, lane);            // ... or what the search proved, and the move
 }
 
 hipError_t launch_expand(const TreeDev& d, const TreeCfg& c, hipStream_t st) {

@@ -7,6 +7,7 @@
 // as in adjudication (tb_core.h, tb_probe).
 #include "tree_device.h"
 #include "tree_gumbel.h"
+#include "tree_proof.h"
 #include "tb_core.h"
 #include "eval_cache.h"
 #include "movegen_wave.h"
@@ -174,7 +175,12 @@ static_assert(sizeof(TopCache) == M0_SEL_CACHE_BYTES, "32 bytes of select fields
 // Dirichlet noise, a pass that ends at the phase boundary of the halving schedule, and at depth 0 the pick by scheduled visit
 // count and Gumbel score in place of the PUCT scan (no jitter draw there).  A template parameter, not a field read in the scan:
 // the PUCT instantiation is the kernel it was.
-template <bool GUMBEL>
+// PROOF: the instantiation for the proof search (TreeCfg::proof, tree_proof.h, include/m0_proof.h).  The nodes' proofs are read
+// through PRF: the tree top's from an LDS copy beside TopCache, the others from the arena.  A terminal leaf is proven at its
+// first visit and the proof is combined up its path; a descent stops at a proven node; the scan passes over children that
+// are won for their own mover; a pass ends once the root is proven.  While no node is proven it is the PUCT search, draw by draw.
+#define PRF(i) ((i) < ncached ? TP[i] : A.proof[i])
+template <bool GUMBEL, bool PROOF>
 __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
     extern __shared__ __attribute__((aligned(16))) char sel_cache[];
     TopCache* const TC = reinterpret_cast<TopCache*>(sel_cache);
@@ -196,6 +202,11 @@ __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
     const int* TN = c.tt_merge ? d.tt_nodes + tt_table_of(d, g, gd) : nullptr;
     const bool reinfer = gd->reinfer != 0;
 
+    if constexpr (PROOF) {
+        // a root that is proven -- by an earlier pass of this search, or in the subtree the search took over -- is searched no
+        // further: no sample, no evaluation; expand_kernel declares the search finished
+        if (A.proof[root] != 0) { if (lane == 0) { gd->nsamples = 0; gd->reinfer = 0; } return; }
+    }
     if (A.nch[root] < 0) { emit_root_init(d, gd, S, P, LM, root, reinfer, smoves, spseudo, lane); return; }
     if constexpr (GUMBEL) {
         if (lane == 0) gd->need_dirichlet = 0;
@@ -214,11 +225,17 @@ __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
     if (nleaf < 0) nleaf = 0;
     // the top of the tree -> LDS (after the Dirichlet noise, which rewrites the root's priors)
     int ncached = 0;
+    int16_t* TP = nullptr;                                 // proof search: the proofs of the cached nodes
+    if constexpr (PROOF) {
+        __shared__ int16_t top_proof[M0_SEL_CACHE];
+        TP = top_proof;
+    }
     if (!c.tt_merge && nleaf > 0) {
         ncached = gd->next < M0_SEL_CACHE ? gd->next : M0_SEL_CACHE;
         for (int i = lane; i < ncached; i += 64) {
             TC->prior[i] = A.prior[i]; TC->q[i] = A.q[i]; TC->n[i] = A.n[i]; TC->vl[i] = A.vl[i]; TC->cbase[i] = A.cbase[i];
             TC->nch[i] = A.nch[i]; TC->mv[i] = A.mv[i];
+            if constexpr (PROOF) TP[i] = A.proof[i];
         }
         __syncthreads();
     }
@@ -233,6 +250,14 @@ __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
     const double jit = c.selection_jitter > 0.0 ? c.selection_jitter : 0.001;
     const int hist_len = gd->hist_len;
     const uint64_t* H = d.hist + (size_t)g * M0_HIST_CAP;
+    // proof search: step 2 of the rule needs a node's children to be all of its legal moves
+    const bool proof_complete = c.max_children <= 0 && !(c.min_child_prior > 0.0);
+    // a node becomes proven: the arena, the LDS copy, and the store made visible to the loads of later descents (see the fence
+    // after the terminal backup below)
+    auto set_proof = [&](int nd, int16_t pv) {
+        if (lane == 0) { A.proof[nd] = pv; if (nd < ncached) TP[nd] = pv; }
+    };
+    int made = nleaf;                                      // samples of this pass: fewer once the root is proven
 
     for (int s = 0; s < nleaf; ++s) {
         Pos pos = gd->root_pos;
@@ -246,6 +271,7 @@ __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
         const bool rh = node < ncached;
         int nc = TOP(nch, rh, node), cb = TOP(cbase, rh, node), nn = TOP(n, rh, node);
         double nq = TOP(q, rh, node);
+        int16_t stop_proof = 0;                            // proof search: the proven node this descent arrived at
         while (true) {
             if (nc <= 0 || depth >= M0_MAX_DEPTH - 1) break;
             const double sq = sqrt((double)(nn > 1 ? nn : 1));
@@ -257,6 +283,12 @@ __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
             Move b_mv = 0;
             bool root_rule = false;
             if constexpr (GUMBEL) root_rule = depth == 0;
+            bool skip_won = false;                         // proof search: some child is not won for its mover -- those that are
+            if constexpr (PROOF) {                         // cannot be the arg-max
+                bool notwin = false;
+                for (int i = lane; i < nc; i += 64) notwin = notwin || proof_state(PRF(cb + i)) != PROOF_WIN;
+                skip_won = __any(notwin);
+            }
             if (root_rule) {
                 // every lane loads the picked child's fields: the broadcast below then reads them from any lane
                 bi = gumbel_pick_child(gd, sg, gcnt, nc, gumbel_considered(g_m, g_n, g_done + s), lane);
@@ -268,6 +300,7 @@ __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
                 for (int i = lane; i < nc; i += 64) {
                     const int ci = cb + i;
                     const bool hit = ci < ncached;                  // the children of a node are one block: all lanes agree but at the edge
+                    if constexpr (PROOF) { if (skip_won && proof_state(PRF(ci)) == PROOF_WIN) continue; }    // no draw is consumed
                     const int cn = TOP(n, hit, ci);
                     const double cq = TOP(q, hit, ci);
                     const int c_nch = TOP(nch, hit, ci), c_cb = TOP(cbase, hit, ci);
@@ -318,12 +351,19 @@ __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
                 if (lane == 0) epath[depth] = child;
             }
             if (lane == 0) path[depth] = node;
+            if constexpr (PROOF) { stop_proof = PRF(node); if (stop_proof != 0) break; }
         }
         __syncthreads();
-        const int nlegal = gen_legal_wave(pos, smoves, spseudo, lane);
-        double tv;
-        bool tb_hit;
-        const bool term = leaf_terminal(d, c, pos, nlegal, depth, pkey, pirr, H, hist_len, lane, tv, tb_hit);
+        int nlegal = 0;
+        double tv = 0.0;
+        bool tb_hit = false, term = false;
+        if (PROOF && stop_proof != 0) {                  // a terminal sample with the value a table hit of that outcome has
+            term = true;
+            tv = proof_value(proof_state(stop_proof), c.draw_penalty);
+        } else {
+            nlegal = gen_legal_wave(pos, smoves, spseudo, lane);
+            term = leaf_terminal(d, c, pos, nlegal, depth, pkey, pirr, H, hist_len, lane, tv, tb_hit);
+        }
         if (tb_hit && lane == 0) gd->tb_leaves++;
         uint64_t ckey = 0;
         bool cached = false;
@@ -338,29 +378,47 @@ __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
             backprop(A, path, depth, tv, lane, c.tt_merge != 0, [&](int nd, int nn, double qq) {
                 if (nd < ncached) { TC->n[nd] = nn; TC->q[nd] = qq; }
             });
+            if constexpr (PROOF) {
+                // the first visit of a terminal leaf (a proven one is never reached again): its proof, then its ancestors'
+                const int16_t pv = stop_proof != 0 ? (int16_t)0 : leaf_proof(d, pos, nlegal, tb_hit);
+                if (pv != 0) {
+                    set_proof(node, pv);
+                    proof_combine_up(A, path, depth, pv, proof_complete, lane, [&](int i) { return PRF(i); }, set_proof);
+                }
+            }
             __syncthreads();
             // Later descents of this launch read these nodes' statistics again, the uncached ones from the arena: drop this CU's
             // vector-L1 lines so that they come from L2, where the stores above are.  (Round 4: a load of the same addresses
             // issued right after the barrier returned the OLD values from time to time -- the lines were resident from the
             // children scan and a store does not refresh them at once; seen as run-to-run differences in whole games.)
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            if constexpr (PROOF) {
+                if (PRF(root) != 0) { made = s + 1; break; }    // the root is proven: the search ends with this sample
+            }
         }
     }
-    if (reinfer) emit_root_value(d, gd, S, nleaf, root, lane);
-    if (lane == 0) { gd->ctr_jitter = ctrj; gd->nsamples = nleaf + (reinfer ? 1 : 0); }
+    if (reinfer) emit_root_value(d, gd, S, made, root, lane);
+    if (lane == 0) { gd->ctr_jitter = ctrj; gd->nsamples = made + (reinfer ? 1 : 0); }
 }
+#undef PRF
 
 hipError_t launch_select(const TreeDev& d, const TreeCfg& c, hipStream_t st) {
     static DeviceOnce once;
     hipError_t e = once.run([] {
-        hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&select_kernel<false>),
+        hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&select_kernel<false, false>),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, M0_SEL_CACHE_BYTES);
         if (e1 != hipSuccess) return e1;
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(&select_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&select_kernel<false, true>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, M0_SEL_CACHE_BYTES);
+        if (e1 != hipSuccess) return e1;
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(&select_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    M0_SEL_CACHE_BYTES);
     });
     if (e != hipSuccess) return e;
-    if (c.gumbel) hipLaunchKernelGGL(select_kernel<true>, dim3(d.G), dim3(64), M0_SEL_CACHE_BYTES, st, d, c);
-    else hipLaunchKernelGGL(select_kernel<false>, dim3(d.G), dim3(64), M0_SEL_CACHE_BYTES, st, d, c);
+    // the modes exclude each other (m0_selfplay_set_gumbel, m0_selfplay_set_proof); a proof search needs its node array
+    if (c.proof && (c.gumbel || !d.t.proof || !d.proof_results)) return hipErrorInvalidValue;
+    if (c.gumbel) hipLaunchKernelGGL((select_kernel<true, false>), dim3(d.G), dim3(64), M0_SEL_CACHE_BYTES, st, d, c);
+    else if (c.proof) hipLaunchKernelGGL((select_kernel<false, true>), dim3(d.G), dim3(64), M0_SEL_CACHE_BYTES, st, d, c);
+    else hipLaunchKernelGGL((select_kernel<false, false>), dim3(d.G), dim3(64), M0_SEL_CACHE_BYTES, st, d, c);
     return hipGetLastError();
 }

@@ -9,7 +9,7 @@ import numpy as np
 from . import _lib
 
 from ._abi import (AN_MAX_LINES, AN_MAX_PV, AnalysisLine, AnalysisOpts, AnalysisResult, GameRecord,  # noqa: F401
-                   GumbelCfg, SelfplayCfg, SelfplayStats)
+                   GumbelCfg, ProofLines, SelfplayCfg, SelfplayStats)
 from ._lib import ptr
 
 c_double, c_int = C.c_double, C.c_int
@@ -314,6 +314,25 @@ class SelfplayEngine:
                    "m0_search_gumbel_result")
         return {"pick": pick.value, "v_mix": vm.value, "pi": pi[: k.value].copy(), "gl": gl[: k.value].copy(), "miss": miss.value}
 
+    # ---- proof search (include/m0_proof.h)
+    def set_proof(self, on: bool = True) -> None:
+        """Turn the proof search on or off (before the first step or search): exact wins, losses and draws are backed up the
+        tree, a search whose root is proven ends.  Not on a self-play engine that plays games with its own network."""
+        _lib.check(self._L.m0_selfplay_set_proof(self._h, int(bool(on))), "m0_selfplay_set_proof")
+        self.proof = bool(on)
+
+    def search_proof_result(self, g: int) -> dict:
+        """Beside search_result(g): the root's `state` (PROOF_STATES) and `plies`, `child_state` and `child_plies` per root child
+        (from the view of the child's side to move) and `pick` (index into its children, -1 while the search runs)."""
+        k = c_int(0); pick = c_int(-1); st = c_int(0); pl = c_int(0)
+        _lib.check(self._L.m0_search_result(self._h, g, C.byref(k), None, None, None, None, None, None, None, None),
+                   "m0_search_result")
+        cs, cp = np.zeros(256, np.int32), np.zeros(256, np.int32)
+        _lib.check(self._L.m0_search_proof_result(self._h, g, C.byref(st), C.byref(pl), ptr(cs), ptr(cp), C.byref(pick)),
+                   "m0_search_proof_result")
+        return {"state": PROOF_STATES[st.value], "plies": pl.value, "pick": pick.value,
+                "child_state": [PROOF_STATES[int(x)] for x in cs[: k.value]], "child_plies": cp[: k.value].copy()}
+
     def search_advance(self, g: int, slot: int, sims: int, dirichlet: bool) -> None:
         _lib.check(self._L.m0_search_advance(self._h, g, slot, sims, int(dirichlet)), "m0_search_advance")
 
@@ -451,6 +470,22 @@ def gumbel_improve(prior, q, n, gl, root_v: float, c_visit: float = GUMBEL_DEFAU
     return pi, vm.value, pick.value
 
 
+PROOF_STATES = ["none", "win", "loss", "draw"]                 # M0_PROOF_* of include/m0_proof.h, by value
+
+
+def proof_combine(states, plies, complete: bool):
+    """(state, plies) of a parent from its children's (names of PROOF_STATES, or their values) by the rule of the proof search
+    (include/m0_proof.h); `complete`: the children are all of the parent's legal moves."""
+    ss = np.ascontiguousarray([PROOF_STATES.index(s) if isinstance(s, str) else int(s) for s in states], dtype=np.int32)
+    pp = np.ascontiguousarray(plies, dtype=np.int32)
+    if ss.shape != pp.shape:
+        raise ValueError("states and plies must have one entry per child")
+    st, pl = c_int(0), c_int(0)
+    _lib.check(_lib.lib().m0_proof_combine(int(ss.shape[0]), ptr(ss), ptr(pp), int(bool(complete)), C.byref(st), C.byref(pl)),
+               "m0_proof_combine")
+    return PROOF_STATES[st.value], pl.value
+
+
 def temperature_for(fullmove: int, t_start: float, t_end: float, t_moves: int) -> float:
     return float(_lib.lib().m0_temperature_for(int(fullmove), float(t_start), float(t_end), int(t_moves)))
 
@@ -536,10 +571,12 @@ class ArenaExtEngine(SelfplayEngine):
 ANALYSIS_STATUS = {0: "ok", 1: "checkmate", 2: "stalemate", 3: "tablebase"}
 
 
-def analysis_result_to_dict(r: AnalysisResult) -> dict:
+def analysis_result_to_dict(r: AnalysisResult, proof: Optional[ProofLines] = None) -> dict:
     """One m0_analysis_result as plain Python: moves and principal variations as UCI strings.  A result from the endgame
     tablebases (status "tablebase") also carries `dtm`, the root's distance to mate in plies (0: a draw), and per line the
-    `dtm` of the position after its move; its root_q is the exact wdl."""
+    `dtm` of the position after its move; its root_q is the exact wdl.  With `proof` (an engine in the proof search,
+    m0_analysis_last_proof) it carries `proof` (a name of PROOF_STATES) and `proof_plies` of the root and, per line, of the
+    root's side to move after that line's move."""
     from_tb = int(r.status) == 3
     lines = []
     for i in range(r.nlines):
@@ -554,6 +591,10 @@ def analysis_result_to_dict(r: AnalysisResult) -> dict:
            "value": float(r.value), "root_q": float(r.root_q), "lines": lines}
     if from_tb:
         out["dtm"] = int(r.tb_dtm)
+    if proof is not None:
+        out["proof"], out["proof_plies"] = PROOF_STATES[int(proof.proof)], int(proof.proof_plies)
+        for i, ln in enumerate(lines):
+            ln["proof"], ln["proof_plies"] = PROOF_STATES[int(proof.line_proof[i])], int(proof.line_proof_plies[i])
     return out
 
 
@@ -586,11 +627,19 @@ class AnalysisEngine(SelfplayEngine):
         rc = _lib.count(self._L.m0_analysis_peek(self._h, int(id), C.byref(r)), "m0_analysis_peek")
         return r if rc == 1 else None
 
+    def _last_proof(self) -> Optional[ProofLines]:
+        """The proofs of the result handed out last, on an engine in the proof search (set_proof); None otherwise."""
+        if not getattr(self, "proof", False):
+            return None
+        p = ProofLines()
+        _lib.check(self._L.m0_analysis_last_proof(self._h, C.byref(p)), "m0_analysis_last_proof")
+        return p
+
     def peek(self, id: int) -> Optional[dict]:
         """The result of the running search `id` as it stands (`sims`: simulations done so far), None while it is queued.
         Reads only."""
         r = self.peek_raw(id)
-        return None if r is None else analysis_result_to_dict(r)
+        return None if r is None else analysis_result_to_dict(r, self._last_proof())
 
     def stop(self, id: int) -> None:
         """Answer the search `id` now (its result, equal to a peek, comes through `poll`); a queued one is answered with zeros."""
@@ -656,13 +705,13 @@ class AnalysisEngine(SelfplayEngine):
         r = AnalysisResult()
         if not visits:
             rc = _lib.count(self._L.m0_analysis_poll(self._h, C.byref(r)), "m0_analysis_poll")
-            return analysis_result_to_dict(r) if rc == 1 else None
+            return analysis_result_to_dict(r, self._last_proof()) if rc == 1 else None
         k = C.c_int32(0)
         idx, cn = np.zeros(256, np.int32), np.zeros(256, np.int32)
         rc = self._L.m0_analysis_poll_visits(self._h, C.byref(r), C.byref(k), ptr(idx), ptr(cn), 256)
         if _lib.count(rc, "m0_analysis_poll_visits") != 1:
             return None
-        out = analysis_result_to_dict(r)
+        out = analysis_result_to_dict(r, self._last_proof())
         out["policy_idx"], out["visits"] = idx[: k.value].copy(), cn[: k.value].copy()
         return out
 

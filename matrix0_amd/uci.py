@@ -15,7 +15,10 @@ that nothing ends earlier; it sizes the node arenas), Leaves 1..96 (leaves per p
 Tablebase (cache file of matrix0_amd.tablebase) and TablebaseMen.  MaxNodes, Leaves and the tablebase options rebuild the engine
 before the next search.  Handled `go` arguments: nodes, movetime, wtime btime winc binc movestogo, infinite; depth, mate,
 searchmoves and ponder are ignored with an `info string` each.  `go nodes N` is the only fully deterministic mode: every
-other one ends on the clock.  `score mate` is printed for results from the endgame tables only.
+other one ends on the clock.  `score mate` is printed for results from the endgame tables and, with the option ProveMates
+(true / false, default false; `--prove` starts with it on; accepted by `setoption`, not listed by `uci`), for lines that the
+proof search has proven (include/m0_proof.h): the search then ends as soon as its root is proven, and `go mate N` is honoured --
+it ends once the root is a win in at most 2N-1 plies, or at its other limits -- instead of being ignored.
 
 The command-line loop reads standard input on a thread into a queue and drains it between passes; every GPU call stays on the
 main thread, so `isready` is answered during a search and `stop` / `quit` take effect between two passes."""
@@ -50,7 +53,11 @@ OPTIONS = {        # name -> (type, default, min, max)
     "Tablebase": ("string", "", None, None),
     "TablebaseMen": ("spin", 4, 3, 4),
 }
-REBUILD_OPTIONS = ("MaxNodes", "Leaves", "Tablebase", "TablebaseMen")
+# ProveMates (check, default false): the proof search.  Proven lines print `score mate N` and `go mate N` is honoured.  It is
+# accepted by setoption and is not in the list that `uci` prints (that list is pinned at six options): start the engine with
+# --prove, or send `setoption name ProveMates value true`.
+UNLISTED_OPTIONS = {"ProveMates": ("check", False, None, None)}
+REBUILD_OPTIONS = ("MaxNodes", "Leaves", "Tablebase", "TablebaseMen", "ProveMates")
 IGNORED_GO = ("depth", "mate", "searchmoves", "ponder")
 GO_INT = ("nodes", "movetime", "wtime", "btime", "winc", "binc", "movestogo", "depth", "mate")
 GO_WORDS = GO_INT + ("infinite", "ponder", "searchmoves")
@@ -132,6 +139,7 @@ class UciEngine:
             fen_after = eng.fen_after
         self.fen_after = fen_after
         self.options = {k: v[1] for k, v in OPTIONS.items()}
+        self.unlisted = {k: v[1] for k, v in UNLISTED_OPTIONS.items()}      # beside `options`, which holds the listed ones
         sims = int((cfg.get("selfplay", {}) or {}).get("num_simulations", 0) or 0)
         leaves = int((cfg.get("mcts", {}) or {}).get("inference_batch_size", 0) or 0)
         if sims > 0:
@@ -180,12 +188,18 @@ class UciEngine:
         j = rest.index("value") if "value" in rest else len(rest)
         name = " ".join(rest[i + 1:j])
         value = " ".join(rest[j + 1:])
-        key = {k.lower(): k for k in OPTIONS}.get(name.lower())
+        every = {**OPTIONS, **UNLISTED_OPTIONS}
+        key = {k.lower(): k for k in every}.get(name.lower())
         if key is None:
             self.out(f"info string unknown option: {name}")
             return
-        kind, _, lo, hi = OPTIONS[key]
-        if kind == "spin":
+        kind, _, lo, hi = every[key]
+        if kind == "check":
+            if value.lower() not in ("true", "false"):
+                self.out(f"info string option {key} needs true or false")
+                return
+            v = value.lower() == "true"
+        elif kind == "spin":
             try:
                 v = int(value)
             except ValueError:
@@ -199,9 +213,10 @@ class UciEngine:
         if self.search is not None and key in REBUILD_OPTIONS:
             self.out(f"info string option {key} cannot change during a search")
             return
-        if self.options[key] != v and key in REBUILD_OPTIONS:
+        held_in = self.unlisted if key in UNLISTED_OPTIONS else self.options
+        if held_in[key] != v and key in REBUILD_OPTIONS:
             self.dirty = True
-        self.options[key] = v
+        held_in[key] = v
 
     def _release(self):
         if self.held is not None:
@@ -243,13 +258,14 @@ class UciEngine:
         args, bad = parse_go(rest)
         for name in bad:
             self.out(f"info string go: cannot read {name}")
+        prove = bool(self.unlisted["ProveMates"])
         for name in IGNORED_GO:
-            if name in args:
+            if name in args and not (name == "mate" and prove):
                 self.out(f"info string go {name} is not supported and ignored")
         if self.dirty and self.rebuild is not None:
             self.held = None                                # the tree goes with its engine
             self.engine.close()
-            self.engine, self.step = self.rebuild(dict(self.options))
+            self.engine, self.step = self.rebuild(dict(self.options, **self.unlisted))
         self.dirty = False
         max_nodes = int(self.options["MaxNodes"])
         sims = max(1, min(int(args["nodes"]), max_nodes)) if "nodes" in args else max_nodes
@@ -275,6 +291,9 @@ class UciEngine:
         now = self.clock()
         self.search = {"id": sid, "t0": now, "budget": budget, "last_info": now, "longest": 0.0, "stopping": False,
                        "base": self.base, "moves": list(self.moves),
+                       # go mate N with ProveMates: the search ends once the root is a win in at most 2N-1 plies (a search
+                       # whose root is proven ends by itself, whatever the distance), or at its other limits
+                       "mate": int(args["mate"]) if prove and "mate" in args else None,
                        # simulations a continued search may still add before its tree is REUSE_TOTAL_FACTOR x MaxNodes visits
                        "room": REUSE_TOTAL_FACTOR * max_nodes - self.last_reused if self.last_reused else None}
         self._collect()                                     # mate, stalemate, a root inside the tables: answered at once
@@ -328,6 +347,8 @@ class UciEngine:
         for k, ln in enumerate(r["lines"][: int(self.options["MultiPV"])]):
             if r["status"] == "tablebase" and ln["q"] != 0:
                 score = f"mate {mate_score(ln['dtm'] + 1, ln['q'] < 0)}"     # ln["dtm"]: of the position after the move
+            elif ln.get("proof") in ("win", "loss"):                         # ProveMates: a proven line
+                score = f"mate {mate_score(ln['proof_plies'], ln['proof'] == 'loss')}"
             else:
                 score = f"cp {cp_from_q(ln['q'])}"
             self.out(f"info depth {len(ln['pv'])} multipv {k + 1} score {score} nodes {r['root_n']} nps {nps} "
@@ -369,8 +390,13 @@ class UciEngine:
         self._pass()
         if self._collect():
             return False
-        if (self.clock() - s["last_info"]) * 1000.0 >= INFO_INTERVAL_MS:
+        pk = None
+        if s["mate"] is not None:                           # go mate N: found?
             pk = self.engine.peek(s["id"])
+            if pk is not None and pk.get("proof") == "win" and pk["proof_plies"] <= 2 * s["mate"] - 1:
+                s["stopping"] = True
+        if (self.clock() - s["last_info"]) * 1000.0 >= INFO_INTERVAL_MS:
+            pk = pk if pk is not None else self.engine.peek(s["id"])
             if pk is not None:
                 self._info(pk)
         return True
@@ -396,6 +422,8 @@ def make_engine(backend, cfg: dict, options: dict):
     kw = dict(slots=1, multipv=8, pv_len=16, leaves_per_step=int(options["Leaves"]), max_sims=int(options["MaxNodes"]))
     if options.get("Tablebase"):
         kw.update(tablebase=options["Tablebase"], tb_men=int(options["TablebaseMen"]))
+    if options.get("ProveMates"):
+        kw["prove"] = True
     e = _OwnedEngine(Analyzer(backend, cfg, **kw))
     return e, (lambda: e.step(1))
 
@@ -405,6 +433,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--config", required=True, help="config.yaml (or .json) of the run: model, mcts sections")
     ap.add_argument("--checkpoint", required=True)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--prove", action="store_true", help="start with the option ProveMates on (the proof search)")
     return ap
 
 
@@ -420,7 +449,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         sys.stdout.flush()
 
     u = UciEngine(None, cfg, out=out, rebuild=lambda opts: make_engine(be, cfg, opts))
-    u.engine, u.step = make_engine(be, cfg, u.options)
+    u.unlisted["ProveMates"] = bool(args.prove)
+    u.engine, u.step = make_engine(be, cfg, dict(u.options, **u.unlisted))
     lines: "queue.Queue[Optional[str]]" = queue.Queue()
 
     def reader():                          # standard input only; every GPU call stays on the main thread
