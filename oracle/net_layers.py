@@ -64,13 +64,29 @@ def schedule(cfg: dict) -> List[dict]:
 
 
 def kernel_plan(cfg: dict, fuse_tail: bool = True, fuse_attn: bool = True) -> dict:
-    """The kernel forms Net::make_plan picks (net_pack.hip:208-216); fuse_tail / fuse_attn False = M0_FUSE_TAIL=0 / M0_FUSE_ATTN=0."""
+    """The kernel forms Net::make_plan picks (net_pack.hip:208-216) and, per head conv, Net::conv_norm_act (net.hip:253-254);
+    fuse_tail / fuse_attn False = M0_FUSE_TAIL=0 / M0_FUSE_ATTN=0.
+
+      big          the trunk convs take the 320-column tile: conv_gemm_tile_n(Cp, Cp) == 320 (conv_gemm.hip:205-207), 320 alone
+      gn_small     the small tile's GroupNorm epilogue is in use (trunk % 64 == 0): the stem (taps == 9, Cin == 32, net.hip:254),
+                   the joint policy_head.0 / value_head.0 launch (N = 64 + 128, net.hip:397-402) and value_head.3 (N = 128)
+      ssl_epilogue the SSL head conv has that epilogue too: gn_small AND its packed width Cs = ceil32(max(16, C / 2))
+                   (net.hip:57) one of 32 / 64 / 128 / 160 (net.hip:254; conv_gemm.hip:195-198 has no other instance).  False at
+                   192 (N = 96) and 384 (N = 192), where the conv is stored raw and ew_board normalises it.
+    value_fc1 on the split-K path (widths 160 and 320, net.hip:218-228) sums its eight fp32 partial tiles in fp32 and rounds once,
+    after bias and activation (splitk_reduce): no storage point of its own, so the plan has no entry for it.
+
+    Before the widths other than 64 and 320 were run, heads_model applied gn_small to every head conv: wrong for the SSL
+    heads at 192 and 384 (modelled as fused, run unfused).  The joint head launch, value_head.3 and value_fc1 were right at every
+    width."""
     cfg = net_ref.full_cfg(cfg)
     C = int(cfg["channels"])
     Cp = 320 if 256 < C < 320 else C                           # net.hip: Cp_
     big = Cp % 320 == 0                                        # conv_gemm.hip: conv_gemm_tile_n(Cp, Cp) == 320
     hidden = max(8, int(C * float(cfg["se_ratio"])))
-    return dict(big=big, gn_small=Cp % 64 == 0, fuse_attn=big and fuse_attn,
+    gn_small = Cp % 64 == 0
+    Cs = -(-max(16, C // 2) // 32) * 32                        # net.hip:57 Cs_
+    return dict(big=big, gn_small=gn_small, ssl_epilogue=gn_small and Cs in (32, 64, 128, 160), fuse_attn=big and fuse_attn,
                 fuse_tail=big and fuse_tail and (not cfg["se"] or (hidden <= 96 and hidden % 4 == 0)))
 
 
@@ -154,10 +170,13 @@ def _model_conv_norm(x, sd, cfg, wkey, norm, pad, form, res=None, posenc=None):
     return _h(y)
 
 
-def _model_res_block(x, sd, cfg, st, plan):
+def _model_res_block(x, sd, cfg, st, plan, block_in=None):
     p = st["prefix"]
-    # AA_ = act(bn1(x)) as the previous step stored it (fp16); recomputed here from the fp16 stream
-    a = _h(net_ref._act(_gn_from(x, x, sd, p + ".bn1"), cfg))
+    # conv1 reads AA_ = act(bn1(x)) as the previous step stored it (fp16; net.hip:345): `block_in` where the caller has that
+    # tensor (the previous step's tapped second output), else recomputed here from the fp16 stream.  The recomputation takes the
+    # statistics of the rounded stream where the writer took them of its fp32 values, which moves ~3 % of AA_ by one fp16 step
+    # and, through the two convs, ~20 % of the block's output (measured at 256 wide); with AA_ itself 0.7 % remain.
+    a = block_in.double() if block_in is not None else _h(net_ref._act(_gn_from(x, x, sd, p + ".bn1"), cfg))
     # conv1 + bn2 + act -> T1_: conv_zs_kernel EPI_GN on the 320-wide trunk, else conv + ew_board (net.hip conv_norm_act)
     t1 = _model_conv_norm(a, sd, cfg, p + ".conv1.weight", p + ".bn2", 1, "epilogue" if plan["big"] else "unfused")
     t = F.conv2d(t1, _h(sd[p + ".conv2.weight"]), padding=1)
@@ -218,9 +237,10 @@ def _model_attention(x, sd, cfg, st, plan):
 
 
 @torch.no_grad()
-def step_model(sd, cfg, step: int, x: torch.Tensor, plan: Optional[dict] = None):
+def step_model(sd, cfg, step: int, x: torch.Tensor, plan: Optional[dict] = None, block_in: Optional[torch.Tensor] = None):
     """step64's results as the kernels' arithmetic gives them up to fp32 effects: float64 with fp16 rounding at the kernels'
-    storage points.  x is the fp16-exact input (a GPU tap, or a rounded float64 stream)."""
+    storage points.  x is the fp16-exact input (a GPU tap, or a rounded float64 stream); block_in, for a residual block, its
+    second input AA_ as the step before wrote it (that step's second output), where the caller has it."""
     cfg = net_ref.full_cfg(cfg)
     plan = plan or kernel_plan(cfg)
     st = schedule(cfg)[step]
@@ -238,7 +258,7 @@ def step_model(sd, cfg, step: int, x: torch.Tensor, plan: Optional[dict] = None)
         form = "tail" if plan["fuse_tail"] else "unfused"      # conv_big_kernel / conv_zs_kernel EPI_TAIL_PRE, else conv + ew_board
         y = _model_conv_norm(x, sd, cfg, st["prefix"] + "_conv.weight", st["prefix"] + "_norm", 0 if k == "pst" else 1, form, res=x)
     elif k == "res":
-        return _model_res_block(x, sd, cfg, st, plan)
+        return _model_res_block(x, sd, cfg, st, plan, block_in)
     else:
         return _model_attention(x, sd, cfg, st, plan)
     # tail_y2 normalises the rounded y with its own sums; ew_board takes the sums of the fp32 y: the difference is far below
@@ -254,8 +274,12 @@ def heads_model(sd, cfg, feats: torch.Tensor, plan: Optional[dict] = None):
     plan = plan or kernel_plan(cfg)
     x = feats.double()
     B = x.shape[0]
-    small = "epilogue" if plan["gn_small"] else "unfused"      # conv_gemm_kernel<1> EPI_GN for N = 32 / 64 / 128 / 160
-    ph = _model_conv_norm(x, sd, cfg, "policy_head.0.weight", "policy_head.1", 0, small)       # PH2_ (joint launch hv_)
+    # conv_gemm_kernel<1> EPI_GN: policy_head.0 and value_head.0 in the joint launch (net.hip:397-402), value_head.3 with N = 128
+    # (net.hip:254, 416); without it (trunk % 64 != 0) each is conv + ew_board (net.hip:404, 413, 259-266)
+    small = "epilogue" if plan["gn_small"] else "unfused"
+    # the SSL head conv has N = C / 2: the epilogue exists for 32 / 64 / 128 / 160 alone (net.hip:254, 431)
+    ssl_form = "epilogue" if plan["ssl_epilogue"] else "unfused"
+    ph =_model_conv_norm(x, sd, cfg, "policy_head.0.weight", "policy_head.1", 0, small)       # PH2_ (joint launch hv_)
     pflat = ph.reshape(B, -1)
     if int(cfg["policy_factor_rank"]) > 0:
         f1 = _h(F.relu(F.linear(pflat, _h(sd["policy_fc1.weight"]), sd["policy_fc1.bias"])))   # F1_: EPI_ELEMENT, fp16
@@ -275,7 +299,7 @@ def heads_model(sd, cfg, feats: torch.Tensor, plan: Optional[dict] = None):
         for task in cfg["ssl_tasks"]:
             if task in net_ref.SSL_OUT:
                 h = f"ssl_heads.{task}"
-                t = _model_conv_norm(x, sd, cfg, h + ".0.weight", h + ".1", 0, small)          # SH2_
+                t = _model_conv_norm(x, sd, cfg, h + ".0.weight", h + ".1", 0, ssl_form)       # SH2_
                 ssl[task] = _h(F.conv2d(t, _h(sd[h + ".3.weight"])))                           # SO_ fp16, widened by nhwc_to_nchw_f32
     return p_, v, ssl
 

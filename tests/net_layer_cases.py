@@ -24,6 +24,46 @@ def planes():
     return nl.random_planes(B, PLANES_SEED)
 
 
+# ---- one network per supported trunk width that is neither 64 nor 320 (tests/test_net_widths_gpu.py, tests/test_net_layers.py) ----
+# Four blocks: res, res, res, att, res -- an attention block that writes the next block's second output, a last block that
+# writes none.  C / 16 heads, group norm, preact and the five SSL tasks on every row; the remaining switches are spread so that
+# each is met off 64 and 320 once (the "switch" column).
+#
+#   C    switch                               what the width is there for
+#   32   --                                   one 32-column tile, ew_board in one wave, two dead attention waves, SE hidden 8,
+#                                             SSL width 16 padded to 32
+#   96   value_activation="leaky_relu"        no multiple of 64, H = 6, the LayerNorm loop ends mid-pass, SE hidden 24, SSL 48 -> 64
+#   160  policy_factor_rank=0 (dense FC)      no multiple of 64, H = 10, value_fc1 on the big-tile split-K path, SSL width 80 -> 96
+#   192  attention_relbias=False              GroupNorm epilogues with an unfused SSL conv (N = 96)
+#   256  activation="relu", se=False          widest unpadded trunk under the padded band, SSL N = 128 in the two-wave-group epilogue
+#   352  --                                   above 320 and no multiple of 64: 704 threads, H = 22, SE hidden 88
+#   384  --                                   the upper bound: both launch bounds, the largest LDS, SSL N = 192 unfused
+WIDE_B = 17      # five 4-board tiles (three padded boards), three se_gate groups (the last ragged), two attn_core board groups
+LONG_B = 257     # two 256-row FC tiles, 17 attention board groups: on the 32 and 96 rows only
+
+
+def width_cfg(C, **kw):
+    return dict(dict(planes=19, channels=C, blocks=4, attention_heads=C // 16, policy_size=4672, norm="group", activation="silu",
+                     preact=True, policy_factor_rank=32, self_supervised=True, ssl_tasks=SSL5), **kw)
+
+
+WIDTHS = [
+    (32, width_cfg(32)),
+    (96, width_cfg(96, value_activation="leaky_relu")),
+    (160, width_cfg(160, policy_factor_rank=0)),
+    (192, width_cfg(192, attention_relbias=False)),
+    (256, width_cfg(256, activation="relu", se=False)),
+    (352, width_cfg(352)),
+    (384, width_cfg(384)),
+]
+WIDTH_IDS = [str(c) for c, _ in WIDTHS]
+LONG_WIDTHS = [w for w in WIDTHS if w[0] in (32, 96)]
+
+
+def wide_planes(b=WIDE_B):
+    return nl.random_planes(b, PLANES_SEED)
+
+
 def weights(cfg, seed=0, sharp=False):
     sd = net_ref.random_state_dict(cfg, seed)
     return nl.sharpen(sd, cfg) if sharp else sd
@@ -68,3 +108,36 @@ MUTATIONS = [
     # visible in the second output alone: the next block's bn1, applied by the step that writes the stream
     ("next block's bn1 gamma/beta of channels 3 and 4 swapped", 16, _mut(lambda sd: _swap_norm(sd, "tower.14.bn1"))),
 ]
+
+
+# ---- one-layer mutations of a WIDTHS row: the same kinds, at the layers of the four-block tower -------------------------------
+W_RES = "tower.1"      # step 4: a residual block that writes the next block's second output
+W_ATT = "tower.3"      # step 6: the attention block
+SE_FC1_ROW = 352       # the neighbour of the se=False row drops se_fc1.bias where the others drop se_fc2.bias
+
+
+def _swap_across_groups(sd):
+    """Channels 15 and 16: the last of GroupNorm group 0 and the first of group 1."""
+    _swap(sd, W_RES + ".bn2.weight", 15, 16)
+    _swap(sd, W_RES + ".bn2.bias", 15, 16)
+
+
+def width_mutations(C, cfg):
+    """[(name, step, mutate)] for one row of WIDTHS: three mutations, each of one parameter set of one layer."""
+    full = net_ref.full_cfg(cfg)
+    out = [("bn2 gamma/beta of channels 15 and 16 swapped", 4, _mut(_swap_across_groups))]
+    if not full["se"]:
+        out.append(("corner tap of conv2 zeroed on 16 channels", 4, _mut(_zero(W_RES + ".conv2.weight", (slice(0, 16), slice(None), 0, 0)))))
+    elif C == SE_FC1_ROW:
+        out.append(("se_fc1 bias dropped", 4, _mut(_zero(W_RES + ".se_fc1.bias", slice(None)))))
+    else:
+        out.append(("se_fc2 bias dropped", 4, _mut(_zero(W_RES + ".se_fc2.bias", slice(None)))))
+    if full["attention_relbias"]:
+        out.append((f"rel_bias of head {C // 16 - 1} dropped", 6, _mut(_zero(W_ATT + ".rel_bias", (0, C // 16 - 1)))))
+    else:
+        out.append((f"LayerNorm beta of channel {C - 1} dropped", 6, _mut(_zero(W_ATT + ".norm.bias", C - 1))))
+    return out
+
+
+WIDTH_MUTATIONS = [(C, cfg, *m) for C, cfg in WIDTHS for m in width_mutations(C, cfg)]
+WIDTH_MUTATION_IDS = [f"{m[0]}:{m[2]}" for m in WIDTH_MUTATIONS]
