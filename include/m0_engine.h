@@ -591,4 +591,6 @@ int m0_replay_games(int hip_device, const char* const* start_fens, const uint32_
 #include "m0_augment.h"
 /* proof search: exact wins, losses and draws backed up the search tree (opt-in) */
 #include "m0_proof.h"
+/* packed training rows: bitboards and sparse policies, expanded on the device */
+#include "m0_rowpack.h"
 #endif /* M0_ENGINE_H */

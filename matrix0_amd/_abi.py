@@ -41,6 +41,10 @@ SSL_SCORE_COLUMNS = ("piece_loss", "threat_loss", "pin_loss", "fork_loss", "cont
 SSL_SCORE_FLAGS = {"planes": 1, "nonfinite": 2, "mismatch": 4}
 # include/m0_augment.h: the kinds of the trainer's augmentations
 AUGMENT_KINDS = {"none": 0, "hflip": 1, "rot180": 2}
+# include/m0_rowpack.h: the format's version, the kinds of a packed row and of its mask
+ROWPACK_VERSION = 1
+ROWPACK_ROW_KINDS = {"packed": 0, "raw": 1}
+ROWPACK_MASK_KINDS = {"none": 0, "legal": 1, "list": 2}
 
 # ---- structs ----
 i32, i64, u8, u16, u32, u64, f32, f64 = (C.c_int, C.c_int64, C.c_uint8, C.c_uint16, C.c_uint32, C.c_uint64, C.c_float,
@@ -121,6 +125,17 @@ class ScoreOpts(C.Structure):
 
 class ProofLines(C.Structure):
     _fields_ = [("proof", i32), ("proof_plies", i32), ("line_proof", i32 * AN_MAX_LINES), ("line_proof_plies", i32 * AN_MAX_LINES)]
+
+
+class RowpackPos(C.Structure):
+    _fields_ = [("men", u64 * 12), ("turn", u8), ("castling", u8), ("ep", u8), ("halfmove", u8), ("fullmove", u8),
+                ("row_kind", u8), ("mask_kind", u8), ("reserved", u8)]
+
+
+class RowpackArrays(C.Structure):
+    _fields_ = [("n", i64), ("pi_n", i64), ("mask_n", i64), ("raw_n", i64), ("pos", vp), ("z", vp), ("pi_off", vp),
+                ("pi_idx", vp), ("pi_val", vp), ("mask_off", vp), ("mask_idx", vp), ("raw_planes", vp), ("raw_pi", vp),
+                ("raw_mask", vp)]
 
 
 class GumbelCfg(C.Structure):
@@ -293,14 +308,28 @@ PROOF_FUNCTIONS = {
     "m0_proof_combine": (i32, [i32, vp, vp, i32, _pi32, _pi32]),
 }
 
+# ---- include/m0_rowpack.h (which m0_engine.h includes too): packed training rows, in that header's order;
+# tests/test_abi_rowpack.py compares the two ----
+ROWPACK_STRUCTS = {"m0_rowpack_pos": RowpackPos, "m0_rowpack_arrays": RowpackArrays}
+ROWPACK_FUNCTIONS = {
+    "m0_rowpack_pack": (i32, [i32, vp, vp, vp, vp, i32, P(RowpackArrays), vp]),
+    "m0_rowpack_unpack": (i32, [i32, P(RowpackArrays), vp, vp, vp, vp]),
+    "m0_rowpack_pack_host": (i32, [vp, vp, vp, vp, i32, P(RowpackArrays), vp]),
+    "m0_rowpack_unpack_host": (i32, [P(RowpackArrays), vp, vp, vp, vp]),
+    "m0_net_score_packed": (i32, [vp, P(RowpackArrays), P(ScoreOpts), vp]),
+    "m0_rowpack_bench": (i32, [i32, i32, i32, P(f32), P(f32), P(f64)]),
+}
+
 
 def bind(L) -> list:
     """Set restype and argtypes of every function of FUNCTIONS, LIVE_FUNCTIONS, SCORE_FUNCTIONS, SSL_SCORE_FUNCTIONS,
-    GUMBEL_FUNCTIONS, AUGMENT_FUNCTIONS and PROOF_FUNCTIONS on the loaded library; the names it does not export."""
+    GUMBEL_FUNCTIONS, AUGMENT_FUNCTIONS, PROOF_FUNCTIONS and ROWPACK_FUNCTIONS on the loaded library; the names it does not
+    export."""
     missing = []
     for name, (restype, argtypes) in (list(FUNCTIONS.items()) + list(LIVE_FUNCTIONS.items()) + list(SCORE_FUNCTIONS.items()) +
                                       list(SSL_SCORE_FUNCTIONS.items()) + list(GUMBEL_FUNCTIONS.items()) +
-                                      list(AUGMENT_FUNCTIONS.items()) + list(PROOF_FUNCTIONS.items())):
+                                      list(AUGMENT_FUNCTIONS.items()) + list(PROOF_FUNCTIONS.items()) +
+                                      list(ROWPACK_FUNCTIONS.items())):
         fn = getattr(L, name, None)
         if fn is None:
             missing.append(name)

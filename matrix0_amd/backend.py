@@ -171,15 +171,21 @@ class M0Backend:
                 raise ValueError(f"expected legal_mask [{B},{_lib.POLICY_SIZE}], got {legal_mask.shape}")
         return a, pi, z, legal_mask
 
-    def score(self, s: np.ndarray, pi: np.ndarray, z: np.ndarray, legal_mask: Optional[np.ndarray] = None, *,
-              mask_mode: Optional[str] = None, label_smoothing: float = 0.0, value_loss: str = "mse",
-              huber_delta: float = 1.0, augment=None) -> np.ndarray:
+    def score(self, s: Optional[np.ndarray] = None, pi: Optional[np.ndarray] = None, z: Optional[np.ndarray] = None,
+              legal_mask: Optional[np.ndarray] = None, *, mask_mode: Optional[str] = None, label_smoothing: float = 0.0,
+              value_loss: str = "mse", huber_delta: float = 1.0, augment=None, packed=None) -> np.ndarray:
         """f32 [B, 8]: the columns of include/m0_score.h (_abi.SCORE_COLUMNS) for the rows (s, pi, z, legal_mask) under this
         network -- forward and loss on the device (m0_net_score), only the 8 columns come back.  mask_mode: "legal", "target",
         "none", or None for resolve_mask_mode.  A non-finite network output raises NonFiniteScore (a ValueError, as infer_np
         raises; it carries the rows).  augment: None for the rows as they are; "hflip", "rot180", "none" or a u8 [B] of
         _abi.AUGMENT_KINDS' values scores every row under that trainer augmentation, transformed on the device after the one
-        upload (m0_net_score_aug, include/m0_augment.h); the mode is still resolved on the rows as given."""
+        upload (m0_net_score_aug, include/m0_augment.h); the mode is still resolved on the rows as given.  packed: a
+        rowpack.PackedRows instead of s, pi, z and legal_mask -- the packed arrays are what is uploaded, the rows are unpacked
+        on the device (m0_net_score_packed, include/m0_rowpack.h) and the columns are those of the dense rows bit for bit."""
+        if packed is not None:
+            return self._score_packed(packed, mask_mode, label_smoothing, value_loss, huber_delta, s, pi, z, legal_mask, augment)
+        if s is None or pi is None or z is None:
+            raise ValueError("score needs s, pi and z, or packed rows")
         a, pi, z, legal_mask = self._score_inputs(s, pi, z, legal_mask)
         B = a.shape[0]
         opts = score_opts(resolve_mask_mode(pi, legal_mask, mask_mode), label_smoothing, value_loss, huber_delta)
@@ -197,6 +203,21 @@ class M0Backend:
         if rc == _lib.M0_ERR_NONFINITE:
             raise NonFiniteScore(f"{call} failed ({rc}): {_lib.last_error()}", rows)
         _lib.check(rc, call)
+        return rows
+
+    def _score_packed(self, packed, mask_mode, label_smoothing, value_loss, huber_delta, *dense) -> np.ndarray:
+        if not self._finalized:
+            raise RuntimeError("weights not loaded")
+        if any(d is not None for d in dense):
+            raise ValueError("packed rows come instead of s, pi, z and legal_mask, and are not augmented")
+        from .rowpack import mask_mode_of
+        opts = score_opts(resolve_mask_mode(None, None, mask_mode_of(packed, mask_mode)), label_smoothing, value_loss, huber_delta)
+        rows = np.empty((packed.n, _abi.SCORE_COLS), dtype=np.float32)
+        arrays = packed.c_arrays()
+        rc = self._L.m0_net_score_packed(self._h, C.byref(arrays), C.byref(opts), _lib.ptr(rows))
+        if rc == _lib.M0_ERR_NONFINITE:
+            raise NonFiniteScore(f"m0_net_score_packed failed ({rc}): {_lib.last_error()}", rows)
+        _lib.check(rc, "m0_net_score_packed")
         return rows
 
     def score_ssl(self, s: np.ndarray, pi: np.ndarray, z: np.ndarray, legal_mask: Optional[np.ndarray] = None,

@@ -19,6 +19,11 @@ hipError_t create_stream_cu_mask_env(const char* env_name, hipStream_t* stream);
 // The check m0_augment_rows and m0_net_score_aug share on kinds u8 [B] (include/m0_augment.h): nullptr when every row holds a kind,
 // otherwise why not (capi_augment.hip).
 const char* m0_bad_kinds(const uint8_t* kinds, int B);
+// Packed rows (include/m0_rowpack.h) checked, uploaded and unpacked on `st` into device arrays planes f32 [n][19][64],
+// pi f32 [n][4672] and mask u8 [n][4672] (null: no mask wanted); returns with the stream drained.  M0_ERR_INVALID with nothing
+// launched for arrays that fail the checks (capi_rowpack.hip).
+int m0_rowpack_unpack_to_device(HipStatus& hs, const m0_rowpack_arrays* in, float* planes_dev, float* pi_dev, uint8_t* mask_dev,
+                                hipStream_t st);
 
 // device memory for the length of one call
 template <typename T>

@@ -1,5 +1,6 @@
 // extern "C" entry points of the network seam (include/m0_engine.h).
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <math.h>
 #include <string.h>
 #include <mutex>
@@ -275,13 +276,16 @@ int m0_net_infer(m0_net* n, const float* planes, int B, float* policy, float* va
 // m0_net_score, m0_net_score_ssl and m0_net_score_aug: one forward, then the score kernels on the buffers it left.  ssl_rows null:
 // without the SSL heads, as m0_net_score always ran.  kinds null (augmented false): the rows as they were uploaded, the launches
 // m0_net_score always made; otherwise augment_rows_kernel first moves them into the second staging set, and the forward and the
-// score kernel read that.
+// score kernel read that.  packed (m0_net_score_packed; planes, pi and legal_mask null then): the staging buffers that the dense
+// rows would be copied into are filled by unpacking on the stream instead, and everything behind them is the same.
 static int net_score(m0_net* n, const float* planes, const float* pi, const float* z, const uint8_t* legal_mask,
                      const float* ssl_targets, const uint8_t* kinds, bool augmented, int B, const m0_score_opts* opts, float* rows,
-                     float* ssl_rows) {
-    if (!n || !planes || !pi || !z || !rows) { m0_set_error("null argument"); return M0_ERR_INVALID; }
+                     float* ssl_rows, const m0_rowpack_arrays* packed = nullptr) {
+    if (!n || (!packed && (!planes || !pi)) || !z || !rows) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     if (B <= 0) { m0_set_error("batch must be positive"); return M0_ERR_INVALID; }
-    if (const char* why = m0score::bad_opts(opts, legal_mask != nullptr)) { m0_set_error(why); return M0_ERR_INVALID; }
+    const bool have_mask = packed ? packed->pos[0].mask_kind != M0_ROWPACK_MASK_NONE : legal_mask != nullptr;
+    if (const char* why = m0score::bad_opts(opts, have_mask)) { m0_set_error(why); return M0_ERR_INVALID; }
+    if (packed && n->net->cfg().planes != M0_PLANES) { m0_set_error("packed rows need the 19 planes of encode_board"); return M0_ERR_INVALID; }
     if (augmented)
         if (const char* why = m0_bad_kinds(kinds, B)) { m0_set_error(why); return M0_ERR_INVALID; }
     std::lock_guard<std::mutex> lk(n->mu);
@@ -303,10 +307,16 @@ static int net_score(m0_net* n, const float* planes, const float* pi, const floa
     if (rc != M0_OK) return rc;
     const bool masked = opts->mask_mode == M0_SCORE_MASK_LEGAL;
     const size_t cells = (size_t)B * M0_POLICY_SIZE;
-    M0_HIP(hs, hipMemcpyAsync(n->planes_dev, planes, (size_t)B * n->net->cfg().planes * 64 * 4, hipMemcpyHostToDevice, n->stream));
-    M0_HIP(hs, hipMemcpyAsync(n->score_pi_dev, pi, cells * 4, hipMemcpyHostToDevice, n->stream));
-    M0_HIP(hs, hipMemcpyAsync(n->score_z_dev, z, (size_t)B * 4, hipMemcpyHostToDevice, n->stream));
-    if (masked) M0_HIP(hs, hipMemcpyAsync(n->score_mask_dev, legal_mask, cells, hipMemcpyHostToDevice, n->stream));
+    if (packed) {
+        rc = m0_rowpack_unpack_to_device(hs, packed, n->planes_dev, n->score_pi_dev, masked ? n->score_mask_dev : nullptr, n->stream);
+        if (rc != M0_OK) return rc;
+        M0_HIP(hs, hipMemcpyAsync(n->score_z_dev, z, (size_t)B * 4, hipMemcpyHostToDevice, n->stream));
+    } else {
+        M0_HIP(hs, hipMemcpyAsync(n->planes_dev, planes, (size_t)B * n->net->cfg().planes * 64 * 4, hipMemcpyHostToDevice, n->stream));
+        M0_HIP(hs, hipMemcpyAsync(n->score_pi_dev, pi, cells * 4, hipMemcpyHostToDevice, n->stream));
+        M0_HIP(hs, hipMemcpyAsync(n->score_z_dev, z, (size_t)B * 4, hipMemcpyHostToDevice, n->stream));
+        if (masked) M0_HIP(hs, hipMemcpyAsync(n->score_mask_dev, legal_mask, cells, hipMemcpyHostToDevice, n->stream));
+    }
     if (ssl_rows && ssl_targets)
         M0_HIP(hs, hipMemcpyAsync(n->ssl_targets_dev, ssl_targets, (size_t)B * m0ssl::TARGET_CH * 64 * 4, hipMemcpyHostToDevice, n->stream));
     if (augmented) M0_HIP(hs, hipMemcpyAsync(n->aug_kinds_dev, kinds, (size_t)B, hipMemcpyHostToDevice, n->stream));
@@ -346,6 +356,11 @@ static int net_score(m0_net* n, const float* planes, const float* pi, const floa
 int m0_net_score(m0_net* n, const float* planes, const float* pi, const float* z, const uint8_t* legal_mask, int B,
                  const m0_score_opts* opts, float* rows) {
     return net_score(n, planes, pi, z, legal_mask, nullptr, nullptr, false, B, opts, rows, nullptr);
+}
+
+int m0_net_score_packed(m0_net* n, const m0_rowpack_arrays* in, const m0_score_opts* opts, float* rows) {
+    if (!in || !in->pos || !in->z || in->n <= 0 || in->n > INT_MAX) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
+    return net_score(n, nullptr, nullptr, in->z, nullptr, nullptr, nullptr, false, (int)in->n, opts, rows, nullptr, in);
 }
 
 int m0_net_score_aug(m0_net* n, const float* planes, const float* pi, const float* z, const uint8_t* legal_mask, const uint8_t* kinds,

@@ -114,8 +114,12 @@ class RowBuffer:
 
 
 class SelfplayShardWriter:
-    def __init__(self, base_dir: str = "data"):
+    """packed=True writes every shard in the packed form of rowpack.py (packed on the CPU: the writer owns no device); the
+    table's rows and everything else are as for dense shards, and ReplayReader reads either."""
+
+    def __init__(self, base_dir: str = "data", packed: bool = False):
         self.base_dir = Path(base_dir)
+        self.packed = bool(packed)
         self.selfplay_dir = self.base_dir / "selfplay"
         self.selfplay_dir.mkdir(parents=True, exist_ok=True)
         self.index = ShardIndex(self.base_dir)
@@ -131,8 +135,12 @@ class SelfplayShardWriter:
         """<dir>/<dir name>_<timestamp>_<uuid8>.npz and its row (source "selfplay": the replay shards carry it too)."""
         ts = datetime.now().strftime("%Y%m%d_%H%M%S")
         path = dir_path / f"{dir_path.name}_{ts}_{uuid.uuid4().hex[:8]}.npz"
+        rows = int(np.asarray(data["s"]).shape[0]) if "s" in data else 0
+        if self.packed and rows:
+            from .rowpack import pack_dict
+            data = pack_dict(data, device="host")
         write_npz(path, data)
-        self.index.add(path, int(np.asarray(data["s"]).shape[0]) if "s" in data else 0, "selfplay")
+        self.index.add(path, rows, "selfplay")
         return str(path)
 
     def add_selfplay_data(self, data: Dict[str, np.ndarray], worker_id: int, game_id: int) -> str:
@@ -150,8 +158,8 @@ class ReplayShardWriter(SelfplayShardWriter):
     name order (sources are moved to `<base>/backups/`, their rows dropped); `add_game()` takes finished games directly
     from the engine (no per-game file at all) -- call `close()` to flush the tail."""
 
-    def __init__(self, base_dir: str = "data", max_shards: int = 128, shard_size: int = 16384):
-        super().__init__(base_dir)
+    def __init__(self, base_dir: str = "data", max_shards: int = 128, shard_size: int = 16384, packed: bool = False):
+        super().__init__(base_dir, packed=packed)
         self.replays_dir = self.base_dir / "replays"
         self.backups_dir = self.base_dir / "backups"
         self.replays_dir.mkdir(parents=True, exist_ok=True)

@@ -139,8 +139,9 @@ class _ShardWriter:
     """Collects sample arrays (data_writer.RowBuffer) and writes <prefix>_<index:06d>.npz with exactly shard_size samples each
     (the tail is shorter) through data_writer.write_npz; no row in the shard index."""
 
-    def __init__(self, out_dir: str, prefix: str, shard_size: int):
+    def __init__(self, out_dir: str, prefix: str, shard_size: int, packed: bool = False, device_index: int = 0):
         self.out_dir, self.prefix, self.shard_size = out_dir, prefix, int(shard_size)
+        self.packed, self.device_index = bool(packed), int(device_index)
         self.buf = RowBuffer()
         self.shards = 0
         self.seconds = 0.0
@@ -158,9 +159,15 @@ class _ShardWriter:
     def _write(self, n: int) -> None:
         t0 = time.perf_counter()
         arrays = self.buf.take(n)
-        pi = np.zeros((n, 4672), np.float32)
-        pi[np.arange(n), arrays.pop("_pi_idx")] = 1.0
-        arrays["pi"] = pi
+        if self.packed:                                     # (rowpack.py) the one-hot pi is never built
+            from . import rowpack
+            rows = rowpack.pack_rows_onehot(arrays.pop("s"), arrays.pop("_pi_idx"), arrays.pop("z"), arrays.pop("legal_mask", None),
+                                            device=self.device_index)
+            arrays = rowpack.packed_to_dict(rows, arrays)
+        else:
+            pi = np.zeros((n, 4672), np.float32)
+            pi[np.arange(n), arrays.pop("_pi_idx")] = 1.0
+            arrays["pi"] = pi
         write_npz(os.path.join(self.out_dir, f"{self.prefix}_{self.shards:06d}.npz"), arrays)
         self.shards += 1
         self.seconds += time.perf_counter() - t0
@@ -170,7 +177,7 @@ def import_pgn(path, out_dir: str, *, min_elo: int = 0, require_normal_terminati
                max_games: Optional[int] = None, shard_size: int = 8192, legal_mask: bool = True, ssl_tasks: Sequence[str] = (),
                result_source: str = "header", on_error: str = "truncate", prefix: str = "import", lichess: bool = False,
                device_index: int = 0, max_plies: int = 1024, max_positions_per_launch: int = 16384,
-               games_per_call: int = 1024, timings: Optional[dict] = None) -> dict:
+               games_per_call: int = 1024, timings: Optional[dict] = None, packed: bool = False) -> dict:
     """PGN file (or text) -> NPZ shards of training samples, as the reference's process_game makes them: per ply `s` = the
     position before the move, `pi` one-hot at the move's index, `z` = the game's result from the side to move's point of view
     (what the engine's own records hold), plus `legal_mask` and `ssl_<task>` (the worker's channel split: piece [N,13,8,8], the
@@ -181,6 +188,8 @@ def import_pgn(path, out_dir: str, *, min_elo: int = 0, require_normal_terminati
     on_error: "truncate" keeps the plies before the first token that does not resolve (python-chess ends the line there),
     "drop" leaves such a game out.  result_source: "header" trusts the Result tag as the reference does; "board" takes the result
     from the final position when it is checkmate or stalemate and the header otherwise.  max_games caps the games kept.
+    packed=True writes packed shards (rowpack.py: bitboards and the one move per row; rowpack.load_shard and the readers of this
+    package give the same dense arrays back, `python -m matrix0_amd.rowpack unpack` dense files for the reference's reader).
     Returns the summary: games_read, games_kept, games_filtered, games_truncated, games_dropped, samples, shards,
     result_mismatches (kept games whose final position is checkmate while the header names another result; "*" names none)."""
     if result_source not in ("header", "board"):
@@ -201,7 +210,7 @@ def import_pgn(path, out_dir: str, *, min_elo: int = 0, require_normal_terminati
     summary = {"games_read": 0, "games_kept": 0, "games_filtered": 0, "games_truncated": 0, "games_dropped": 0, "samples": 0,
                "shards": 0, "result_mismatches": 0}
     tm = {"parse": 0.0, "device": 0.0, "compress": 0.0}
-    writer = _ShardWriter(out_dir, prefix, shard_size)
+    writer = _ShardWriter(out_dir, prefix, shard_size, packed=packed, device_index=device_index)
 
     def flush(batch: List[Tuple[dict, List[str]]]) -> None:
         t0 = time.perf_counter()

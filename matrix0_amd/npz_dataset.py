@@ -14,6 +14,7 @@ from typing import Iterator, List, Optional, Tuple
 import numpy as np
 
 from .data_writer import ShardIndex
+from .rowpack import load_shard
 
 
 class ReplayReader:
@@ -32,11 +33,12 @@ class ReplayReader:
 
     # -- validation (data_manager.py _validate_shapes / _validate_dtypes_and_ranges) ------------------------------------
     def _load(self, path: str):
-        with np.load(path) as d:
-            if not all(k in d.files for k in ("s", "pi", "z")):
-                return None
-            s, pi, z = d["s"], d["pi"], d["z"]
-            lm = d["legal_mask"] if "legal_mask" in d.files else None
+        # dense or packed (rowpack.py): the same arrays either way, and of a dense file only these four keys are read
+        d = load_shard(path, device="host", keys=("s", "pi", "z", "legal_mask"))
+        if not all(k in d for k in ("s", "pi", "z")):
+            return None
+        s, pi, z = d["s"], d["pi"], d["z"]
+        lm = d.get("legal_mask")
         if z.ndim == 2 and z.shape[1] == 1:
             z = z.reshape(z.shape[0])
         ok = (s.dtype == np.float32 and pi.dtype == np.float32 and z.dtype == np.float32 and s.ndim == 4 and

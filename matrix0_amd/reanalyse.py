@@ -37,6 +37,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .encoding import DECODE_MASK_MISMATCH, DECODE_STATUS
+from .rowpack import load_shard
 
 _EPS = 1e-12
 REPORT_NAME = "reanalyse_report.json"
@@ -209,8 +210,7 @@ def reanalyse_shards(in_dir, out_dir, *, analyzer, sims: int, value_mix: float =
     next_id = int(first_id)
     reports, shards = [], []
     for k, f in enumerate(files):
-        with np.load(f, allow_pickle=False) as d:
-            data = {key: d[key] for key in d.files}
+        data = load_shard(f, device="host")                  # dense or packed (rowpack.py)
         if not {"s", "pi", "z"} <= set(data):
             shards.append({"source": str(f), "skipped": "no s / pi / z"})
             continue

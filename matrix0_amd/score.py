@@ -11,6 +11,8 @@ no masking; otherwise the support is pi > 0).  The report sums in float64 over a
 means of policy loss, KL (policy loss - target entropy), value loss and total (policy + value, train.py:675), top-1/3/5 hit
 rates of the target's best move, the mean soft-max mass on the support, the sign agreement of v with z over rows with z != 0,
 and the count of each flag.  Rows with an empty support or non-finite network outputs are counted and left out of the means.
+A packed shard (rowpack.py) is handed to M0Backend.score(packed=...) as it is and unpacked on the device -- the same columns and
+the same report as for the dense shard; with ssl or augment it is unpacked on the host first.
 
 Command line: python -m matrix0_amd.score --config config.yaml --checkpoint A [--checkpoint B ...] --data DIR [--sources ...]
     [--batch N] [--json OUT] [--per-sample OUT.npz] [--label-smoothing X] [--value-loss mse|huber] [--huber-delta X]
@@ -274,6 +276,31 @@ def _stored_ssl(path) -> Dict[str, np.ndarray]:
         return {k: d[k] for k in d.files if k.startswith("ssl_")}
 
 
+def _packed_rows(path, expected_planes: int):
+    """The rows of a packed shard (rowpack.py) that the reader would accept, still packed; None for any other file, of which
+    nothing but the names in it is read here."""
+    from . import rowpack
+    try:
+        packed, _ = rowpack.read_shard(path, keys=())
+        if packed is not None:
+            packed.validate()
+    except Exception:
+        return None
+    if packed is None or expected_planes != rowpack.PLANES:
+        return None
+    finite = all(bool(np.isfinite(a).all()) for a in (packed.pi_val, packed.z, packed.raw_planes, packed.raw_pi))
+    return packed if finite else None
+
+
+def _score_packed(backend, packed, batch: int, **opts) -> np.ndarray:
+    """score_arrays of packed rows: chunks of M0Backend.score(packed=...), unpacked on the device"""
+    out = np.empty((packed.n, SCORE_COLS), np.float32)
+    for a in range(0, packed.n, batch):
+        b = min(a + batch, packed.n)
+        out[a:b] = backend.score(packed=packed.rows(a, b), **opts)
+    return out
+
+
 def score_shards(data_dir, backend, *, sources: Sequence[str] = ("selfplay", ""), batch: int = 4096,
                  per_sample: Optional[str] = None, expected_planes: int = 19, ssl: Optional[str] = None,
                  ssl_weight: float = 0.1, ssl_task_weights: Optional[Mapping[str, float]] = None,
@@ -316,31 +343,44 @@ def score_shards(data_dir, backend, *, sources: Sequence[str] = ("selfplay", "")
         source = source or ""
         if corrupted or source not in sources or not Path(path).exists():
             continue
+        # a packed shard goes to the device as it is when nothing but the rows' own columns is wanted
+        packed = _packed_rows(path, expected_planes) if ssl is None and augment is None else None
         try:
-            got = reader._load(path)
+            got = reader._load(path) if packed is None else None
         except Exception:
             got = None
-        if got is None or got[1].shape[1] != POLICY_SIZE:          # the only policy layout the engine has
+        if packed is None and (got is None or got[1].shape[1] != POLICY_SIZE):          # the only policy layout the engine has
             skipped.append(Path(path).name)
             continue
-        s, pi, z, mask = got
-        mode = resolve_mask_mode(pi, mask, opts.get("mask_mode"))
         rows3 = None
-        if trainer:
-            rows3 = score_arrays(backend, s, pi, z, mask, batch=batch, augment="trainer", **dict(opts, mask_mode=mode))
-            rows = rows3[AUGMENT_KINDS["none"]]
-        elif ssl is None:
-            rows = score_arrays(backend, s, pi, z, mask, batch=batch, **dict(opts, mask_mode=mode),
-                                **({} if augment is None else {"augment": augment}))
-        else:
-            have = {} if ssl == "planes" else _stored_ssl(path)
-            stored = ssl == "stored" or (ssl == "auto" and all("ssl_" + t in have for t in tasks))
+        if packed is not None:
+            from .rowpack import mask_mode_of
+            z, mode = packed.z, mask_mode_of(packed, opts.get("mask_mode"))
             try:
-                targets = pack_ssl_targets(have, len(s), tasks) if stored else None
-            except KeyError as e:
-                raise KeyError(f"{Path(path).name}: {e.args[0]} (ssl='stored')") from None
-            rows, ssl_rows = score_arrays(backend, s, pi, z, mask, batch=batch, ssl="stored" if stored else "planes",
-                                          ssl_targets=targets, **dict(opts, mask_mode=mode))
+                rows = _score_packed(backend, packed, batch, **dict(opts, mask_mode=mode))
+            except NonFiniteScore:
+                raise
+            except ValueError:                                      # arrays that do not hold together: as an unreadable dense shard
+                skipped.append(Path(path).name)
+                continue
+        else:
+            s, pi, z, mask = got
+            mode = resolve_mask_mode(pi, mask, opts.get("mask_mode"))
+            if trainer:
+                rows3 = score_arrays(backend, s, pi, z, mask, batch=batch, augment="trainer", **dict(opts, mask_mode=mode))
+                rows = rows3[AUGMENT_KINDS["none"]]
+            elif ssl is None:
+                rows = score_arrays(backend, s, pi, z, mask, batch=batch, **dict(opts, mask_mode=mode),
+                                    **({} if augment is None else {"augment": augment}))
+            else:
+                have = {} if ssl == "planes" else _stored_ssl(path)
+                stored = ssl == "stored" or (ssl == "auto" and all("ssl_" + t in have for t in tasks))
+                try:
+                    targets = pack_ssl_targets(have, len(s), tasks) if stored else None
+                except KeyError as e:
+                    raise KeyError(f"{Path(path).name}: {e.args[0]} (ssl='stored')") from None
+                rows, ssl_rows = score_arrays(backend, s, pi, z, mask, batch=batch, ssl="stored" if stored else "planes",
+                                              ssl_targets=targets, **dict(opts, mask_mode=mode))
         one = Sums()
         for sums in (total, by_source.setdefault(source, Sums()), one):
             sums.add(rows, z)

@@ -78,6 +78,17 @@ def check_unsupported_sections(cfg_dict: dict) -> None:
                                   "set engine.tablebase: {max_pieces: 3 | 4, cache: <path>} or tablebases.enabled: false")
 
 
+def shard_writer(cfg_dict: dict, eng_cfg: dict):
+    """The worker's writer.  engine.replay_shards: emit replay-buffer shards directly (ReplayShardWriter: what the orchestrator's
+    compact_selfplay_to_replay would make of the per-game files) instead of one NPZ per game; "packed" writes them in the
+    packed form of rowpack.py (true keeps meaning dense)."""
+    replay = eng_cfg.get("replay_shards", False)
+    if not replay:
+        return SelfplayShardWriter(base_dir=cfg_dict.get("data_dir", "data"))
+    return ReplayShardWriter(base_dir=cfg_dict.get("data_dir", "data"), max_shards=int(eng_cfg.get("max_shards", 128)),
+                             shard_size=int(eng_cfg.get("shard_size", 16384)), packed=replay == "packed")
+
+
 def selfplay_worker(proc_id: int, cfg_dict: dict, ckpt_path: Optional[str], games: int, q=None,
                     shared_memory_resource: Optional[Dict[str, Any]] = None) -> None:
     logger = logging.getLogger(f"selfplay_worker_{proc_id}")
@@ -152,14 +163,8 @@ def selfplay_worker(proc_id: int, cfg_dict: dict, ckpt_path: Optional[str], game
             (e.set_search_tablebase if searched else e.set_tablebase)(tablebase, probe_limit(cfg_dict))
         logger.info("worker %d: endgame tables up to %d men attached (probing up to %d%s)", proc_id, tablebase.max_men,
                     probe_limit(cfg_dict), ", inside the search too" if searched else "")
-    # engine.replay_shards: emit replay-buffer shards directly (ReplayShardWriter: what the orchestrator's
-    # compact_selfplay_to_replay would make of the per-game files) instead of one NPZ per game
-    direct_replay = bool(eng_cfg.get("replay_shards", False))
-    if direct_replay:
-        writer = ReplayShardWriter(base_dir=cfg_dict.get("data_dir", "data"),
-                                   max_shards=int(eng_cfg.get("max_shards", 128)), shard_size=int(eng_cfg.get("shard_size", 16384)))
-    else:
-        writer = SelfplayShardWriter(base_dir=cfg_dict.get("data_dir", "data"))
+    writer = shard_writer(cfg_dict, eng_cfg)
+    direct_replay = isinstance(writer, ReplayShardWriter)
     last_hb = time.perf_counter()
     done = 0
     overflows = 0
