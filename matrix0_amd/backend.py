@@ -186,24 +186,34 @@ class M0Backend:
             return self._score_packed(packed, mask_mode, label_smoothing, value_loss, huber_delta, s, pi, z, legal_mask, augment)
         if s is None or pi is None or z is None:
             raise ValueError("score needs s, pi and z, or packed rows")
-        a, pi, z, legal_mask = self._score_inputs(s, pi, z, legal_mask)
-        B = a.shape[0]
-        opts = score_opts(resolve_mask_mode(pi, legal_mask, mask_mode), label_smoothing, value_loss, huber_delta)
-        rows = np.empty((B, _abi.SCORE_COLS), dtype=np.float32)
-        if augment is None:
-            call = "m0_net_score"
-            rc = self._L.m0_net_score(self._h, _lib.ptr(a), _lib.ptr(pi), _lib.ptr(z), _lib.ptr(legal_mask), B, C.byref(opts),
-                                      _lib.ptr(rows))
+        dense = self._score_inputs(s, pi, z, legal_mask)
+        mode = resolve_mask_mode(dense[1], dense[3], mask_mode)
+        call = "m0_net_score" if augment is None else "m0_net_score_aug"
+        return self._net_score(call, len(dense[0]), (mode, label_smoothing, value_loss, huber_delta), dense, augment=augment)[0]
+
+    def _net_score(self, call: str, B: int, loss: tuple, dense=(), *, augment=None, packed=None, ssl_targets=None):
+        """The one way into m0_net_score and its _aug, _packed and _ssl variants: the options (loss: score_opts' arguments), the
+        output arrays [rows] or [rows, ssl_rows], the call, and NonFiniteScore with those arrays or _lib.check for its answer."""
+        opts = score_opts(*loss)
+        out = [np.empty((B, _abi.SCORE_COLS), dtype=np.float32)]
+        if call == "m0_net_score_packed":
+            arrays = packed.c_arrays()
+            args = [C.byref(arrays)]
         else:
-            from .encoding import augment_kinds
-            call = "m0_net_score_aug"
-            kinds = augment_kinds(augment, B)
-            rc = self._L.m0_net_score_aug(self._h, _lib.ptr(a), _lib.ptr(pi), _lib.ptr(z), _lib.ptr(legal_mask), _lib.ptr(kinds), B,
-                                          C.byref(opts), _lib.ptr(rows))
+            args = [_lib.ptr(x) for x in dense]
+            if call == "m0_net_score_aug":
+                from .encoding import augment_kinds
+                kinds = augment_kinds(augment, B)
+                args.append(_lib.ptr(kinds))
+            elif call == "m0_net_score_ssl":
+                out.append(np.empty((B, _abi.SSL_SCORE_COLS), dtype=np.float32))
+                args.append(_lib.ptr(ssl_targets))
+            args.append(B)
+        rc = getattr(self._L, call)(self._h, *args, C.byref(opts), *[_lib.ptr(x) for x in out])
         if rc == _lib.M0_ERR_NONFINITE:
-            raise NonFiniteScore(f"{call} failed ({rc}): {_lib.last_error()}", rows)
+            raise NonFiniteScore(f"{call} failed ({rc}): {_lib.last_error()}", *out)
         _lib.check(rc, call)
-        return rows
+        return out
 
     def _score_packed(self, packed, mask_mode, label_smoothing, value_loss, huber_delta, *dense) -> np.ndarray:
         if not self._finalized:
@@ -211,14 +221,8 @@ class M0Backend:
         if any(d is not None for d in dense):
             raise ValueError("packed rows come instead of s, pi, z and legal_mask, and are not augmented")
         from .rowpack import mask_mode_of
-        opts = score_opts(resolve_mask_mode(None, None, mask_mode_of(packed, mask_mode)), label_smoothing, value_loss, huber_delta)
-        rows = np.empty((packed.n, _abi.SCORE_COLS), dtype=np.float32)
-        arrays = packed.c_arrays()
-        rc = self._L.m0_net_score_packed(self._h, C.byref(arrays), C.byref(opts), _lib.ptr(rows))
-        if rc == _lib.M0_ERR_NONFINITE:
-            raise NonFiniteScore(f"m0_net_score_packed failed ({rc}): {_lib.last_error()}", rows)
-        _lib.check(rc, "m0_net_score_packed")
-        return rows
+        mode = resolve_mask_mode(None, None, mask_mode_of(packed, mask_mode))
+        return self._net_score("m0_net_score_packed", packed.n, (mode, label_smoothing, value_loss, huber_delta), packed=packed)[0]
 
     def score_ssl(self, s: np.ndarray, pi: np.ndarray, z: np.ndarray, legal_mask: Optional[np.ndarray] = None,
                   ssl_targets: Optional[np.ndarray] = None, *, mask_mode: Optional[str] = None, label_smoothing: float = 0.0,
@@ -228,21 +232,14 @@ class M0Backend:
         (m0_net_score_ssl).  ssl_targets f32 [B,17,8,8] (or [B,17,64]: piece one-hot, threat, pin, fork, control) as stored with
         the rows, or None to take the targets from the planes.  A network without SSL heads is a ValueError; non-finite
         outputs raise NonFiniteScore, which then carries `rows` and `ssl_rows`."""
-        a, pi, z, legal_mask = self._score_inputs(s, pi, z, legal_mask)
-        B = a.shape[0]
+        dense = self._score_inputs(s, pi, z, legal_mask)
+        B = len(dense[0])
         if ssl_targets is not None:
             ssl_targets = np.ascontiguousarray(ssl_targets, dtype=np.float32)
             if ssl_targets.size != B * 17 * 64 or ssl_targets.shape[:2] != (B, 17):
                 raise ValueError(f"expected ssl_targets [{B},17,8,8], got {ssl_targets.shape}")
-        opts = score_opts(resolve_mask_mode(pi, legal_mask, mask_mode), label_smoothing, value_loss, huber_delta)
-        rows = np.empty((B, _abi.SCORE_COLS), dtype=np.float32)
-        ssl_rows = np.empty((B, _abi.SSL_SCORE_COLS), dtype=np.float32)
-        rc = self._L.m0_net_score_ssl(self._h, _lib.ptr(a), _lib.ptr(pi), _lib.ptr(z), _lib.ptr(legal_mask), _lib.ptr(ssl_targets),
-                                      B, C.byref(opts), _lib.ptr(rows), _lib.ptr(ssl_rows))
-        if rc == _lib.M0_ERR_NONFINITE:
-            raise NonFiniteScore(f"m0_net_score_ssl failed ({rc}): {_lib.last_error()}", rows, ssl_rows)
-        _lib.check(rc, "m0_net_score_ssl")
-        return rows, ssl_rows
+        loss = (resolve_mask_mode(dense[1], dense[3], mask_mode), label_smoothing, value_loss, huber_delta)
+        return tuple(self._net_score("m0_net_score_ssl", B, loss, dense, ssl_targets=ssl_targets))
 
     # ---- measurement helpers ----------------------------------------------------------------
     def param_count(self) -> int:

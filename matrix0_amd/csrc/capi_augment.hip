@@ -30,19 +30,13 @@ int m0_augment_rows(int hip_device, const float* planes, int P, const float* pi,
         return M0_ERR_INVALID;
     }
     if (const char* why = m0_bad_kinds(kinds, B)) { m0_set_error(why); return M0_ERR_INVALID; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { m0_set_error("no HIP device available (no CPU fallback)"); return M0_ERR_HIP; }
     HipStatus hs;
-    if (!M0_HIP(hs, hipSetDevice(hip_device))) return m0_hip_error(hs);
+    if (const int rc = m0_select_device(hs, hip_device)) return rc;
     const size_t cells = (size_t)B * COLS, pcells = (size_t)B * P * SQUARES;
     DevBuf<float> ds, dp, dso, dpo;
     DevBuf<uint8_t> dm, dmo, dk;
-    if (!ds.alloc(hs, pcells) || !dso.alloc(hs, pcells) || !dp.alloc(hs, cells) || !dpo.alloc(hs, cells) || !dk.alloc(hs, B) ||
-        (legal_mask && (!dm.alloc(hs, cells) || !dmo.alloc(hs, cells)))) return m0_hip_error(hs, "hipMalloc failed");
-    M0_HIP(hs, hipMemcpy(ds.p, planes, pcells * 4, hipMemcpyHostToDevice));
-    M0_HIP(hs, hipMemcpy(dp.p, pi, cells * 4, hipMemcpyHostToDevice));
-    M0_HIP(hs, hipMemcpy(dk.p, kinds, (size_t)B, hipMemcpyHostToDevice));
-    if (legal_mask) M0_HIP(hs, hipMemcpy(dm.p, legal_mask, cells, hipMemcpyHostToDevice));
+    if (!ds.upload(hs, planes, pcells) || !dso.alloc(hs, pcells) || !dp.upload(hs, pi, cells) || !dpo.alloc(hs, cells) || !dk.upload(hs, kinds, B) ||
+        (legal_mask && (!dm.upload(hs, legal_mask, cells) || !dmo.alloc(hs, cells)))) return m0_hip_error(hs, "hipMalloc failed");
     M0_HIP(hs, launch_augment_rows(ds.p, dp.p, dm.p, dk.p, M0_AUG_NONE, B, P, dso.p, dpo.p, dmo.p, nullptr));
     M0_HIP(hs, hipDeviceSynchronize());
     if (!hs.ok()) return m0_hip_error(hs, "augment kernel failed");          // the outputs stay untouched
@@ -55,42 +49,27 @@ int m0_augment_rows(int hip_device, const float* planes, int P, const float* pi,
 
 int m0_augment_bench(int hip_device, int B, int iters, float* us_per_launch, double* bytes_per_launch) {
     if (B <= 0 || iters <= 0 || !us_per_launch || !bytes_per_launch) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { m0_set_error("no HIP device available (no CPU fallback)"); return M0_ERR_HIP; }
     HipStatus hs;
-    if (!M0_HIP(hs, hipSetDevice(hip_device))) return m0_hip_error(hs);
+    if (const int rc = m0_select_device(hs, hip_device)) return rc;
     // what is moved does not depend on the values: seeded floats and bytes, the three kinds in turn
     const int P = M0_PLANES;
     const size_t cells = (size_t)B * COLS, pcells = (size_t)B * P * SQUARES;
     std::vector<float> hp(cells), hplanes(pcells);
     std::vector<uint8_t> hm(cells), hk(B);
-    uint64_t s = 0x9E3779B97F4A7C15ull;
-    auto next = [&]() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return s; };
-    for (auto& x : hp) x = (float)((double)(next() % 16384) / 16384.0);
-    for (auto& x : hplanes) x = (float)(next() % 2);
-    for (auto& x : hm) x = (uint8_t)(next() % 128 == 0);
+    BenchRng rng;
+    for (auto& x : hp) x = (float)((double)(rng.next() % 16384) / 16384.0);
+    for (auto& x : hplanes) x = (float)(rng.next() % 2);
+    for (auto& x : hm) x = (uint8_t)(rng.next() % 128 == 0);
     for (int b = 0; b < B; ++b) hk[b] = (uint8_t)(b % KINDS);
     DevBuf<float> ds, dp, dso, dpo;
     DevBuf<uint8_t> dm, dmo, dk;
-    if (!ds.alloc(hs, pcells) || !dso.alloc(hs, pcells) || !dp.alloc(hs, cells) || !dpo.alloc(hs, cells) || !dk.alloc(hs, B) ||
-        !dm.alloc(hs, cells) || !dmo.alloc(hs, cells)) return m0_hip_error(hs, "hipMalloc failed");
-    M0_HIP(hs, hipMemcpy(ds.p, hplanes.data(), pcells * 4, hipMemcpyHostToDevice));
-    M0_HIP(hs, hipMemcpy(dp.p, hp.data(), cells * 4, hipMemcpyHostToDevice));
-    M0_HIP(hs, hipMemcpy(dm.p, hm.data(), cells, hipMemcpyHostToDevice));
-    M0_HIP(hs, hipMemcpy(dk.p, hk.data(), (size_t)B, hipMemcpyHostToDevice));
-    M0_HIP(hs, launch_augment_rows(ds.p, dp.p, dm.p, dk.p, M0_AUG_NONE, B, P, dso.p, dpo.p, dmo.p, nullptr));     // warm-up
-    struct Events {                          // destroyed on every way out
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-    } ev;
-    M0_HIP(hs, hipEventCreate(&ev.e0)); M0_HIP(hs, hipEventCreate(&ev.e1));
-    M0_HIP(hs, hipEventRecord(ev.e0, nullptr));
-    for (int i = 0; i < iters; ++i) M0_HIP(hs, launch_augment_rows(ds.p, dp.p, dm.p, dk.p, M0_AUG_NONE, B, P, dso.p, dpo.p, dmo.p, nullptr));
-    M0_HIP(hs, hipEventRecord(ev.e1, nullptr));
-    M0_HIP(hs, hipEventSynchronize(ev.e1));
-    float ms = 0.f;
-    if (!M0_HIP(hs, hipEventElapsedTime(&ms, ev.e0, ev.e1))) return m0_hip_error(hs, "augment bench failed");
-    *us_per_launch = ms * 1000.f / (float)iters;
+    if (!ds.upload(hs, hplanes.data(), pcells) || !dso.alloc(hs, pcells) || !dp.upload(hs, hp.data(), cells) || !dpo.alloc(hs, cells) ||
+        !dk.upload(hs, hk.data(), B) || !dm.upload(hs, hm.data(), cells) || !dmo.alloc(hs, cells)) return m0_hip_error(hs, "hipMalloc failed");
+    auto launch = [&]() { return M0_HIP(hs, launch_augment_rows(ds.p, dp.p, dm.p, dk.p, M0_AUG_NONE, B, P, dso.p, dpo.p, dmo.p, nullptr)); };
+    launch();                                                                           // warm-up
+    const float ms = m0_time_iterations(hs, nullptr, iters, launch);
+    if (!hs.ok()) return m0_hip_error(hs, "augment bench failed");
+    *us_per_launch = ms * 1000.f;
     *bytes_per_launch = (double)B * (2.0 * ((double)COLS * (4 + 1) + (double)P * SQUARES * 4) + 1.0);
     return M0_OK;
 }

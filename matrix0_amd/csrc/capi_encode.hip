@@ -16,9 +16,7 @@ namespace {
 
 // selects the device, parses the n FENs and puts the positions on it
 int upload_fens(HipStatus& hs, int hip_device, const char* const* fens, int n, DevBuf<Pos>& dp) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { m0_set_error("no HIP device available (no CPU fallback)"); return M0_ERR_HIP; }
-    if (!M0_HIP(hs, hipSetDevice(hip_device))) return m0_hip_error(hs);
+    if (const int rc = m0_select_device(hs, hip_device)) return rc;
     std::vector<Pos> hp(n);
     for (int i = 0; i < n; ++i)
         if (!fens[i] || parse_fen(fens[i], hp[i]) != 0) { m0_set_error(std::string("bad FEN at index ") + std::to_string(i)); return M0_ERR_INVALID; }
@@ -80,16 +78,12 @@ int m0_ssl_targets_fens(int hip_device, const char* const* fens, int n, float* o
 int m0_decode_planes(int hip_device, const float* planes, const uint8_t* mask, int n, int32_t* status, int32_t* flags,
                      int32_t* nlegal, char* fens, int fen_stride) {
     if (!planes || n <= 0 || (fens && fen_stride < 96)) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { m0_set_error("no HIP device available (no CPU fallback)"); return M0_ERR_HIP; }
     HipStatus hs;
-    if (!M0_HIP(hs, hipSetDevice(hip_device))) return m0_hip_error(hs);
+    if (const int rc = m0_select_device(hs, hip_device)) return rc;
     const size_t N = (size_t)n;
     DevBuf<float> dpl; DevBuf<uint8_t> dm; DevBuf<Pos> dp; DevBuf<int32_t> dst, dfl, dnl;
-    if (!dpl.alloc(hs, N * M0_PLANES * 64) || (mask && !dm.alloc(hs, N * M0_POLICY_SIZE)) || !dp.alloc(hs, N) || !dst.alloc(hs, N) ||
+    if (!dpl.upload(hs, planes, N * M0_PLANES * 64) || (mask && !dm.upload(hs, mask, N * M0_POLICY_SIZE)) || !dp.alloc(hs, N) || !dst.alloc(hs, N) ||
         !dfl.alloc(hs, N) || !dnl.alloc(hs, N)) return m0_hip_error(hs, "hipMalloc failed");
-    M0_HIP(hs, hipMemcpy(dpl.p, planes, N * M0_PLANES * 64 * sizeof(float), hipMemcpyHostToDevice));
-    if (mask) M0_HIP(hs, hipMemcpy(dm.p, mask, N * M0_POLICY_SIZE, hipMemcpyHostToDevice));
     M0_HIP(hs, launch_decode_planes(dpl.p, dm.p, n, dp.p, dst.p, dfl.p, dnl.p, nullptr));
     if (!M0_HIP(hs, hipDeviceSynchronize())) return m0_hip_error(hs, "decode kernel failed");
     std::vector<int32_t> hst(N);

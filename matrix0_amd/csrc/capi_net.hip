@@ -19,33 +19,48 @@ thread_local std::string g_m0_last_error;
 
 void m0_set_error(const std::string& s) { g_m0_last_error = s; }
 
+// One staging array of a network handle: where its device pointer lives and how many bytes a row takes.
+struct StagedArray {
+    void** p;
+    size_t row_bytes;
+    template <typename T>
+    StagedArray(T*& ptr, size_t per_row) : p((void**)&ptr), row_bytes(per_row * sizeof(T)) {}
+};
+
+// The arrays of a group grow together and share one capacity; a call reserves only the groups it uses.
+enum { STAGE_IO, STAGE_SCORE, STAGE_SSL_SCORE, STAGE_AUG, STAGE_GROUPS };
+static const char* const STAGE_GROW_ERROR[STAGE_GROUPS] = {"hipMalloc failed for I/O staging", "hipMalloc failed for score staging",
+                                                           "hipMalloc failed for SSL score staging",
+                                                           "hipMalloc failed for augmentation staging"};
+
 struct m0_net {
     Net* net = nullptr;
     int device = 0;
     hipStream_t stream = nullptr;
     std::mutex mu;
-    // staging buffers for the host-facing infer call
-    float* planes_dev = nullptr;
-    float* logits_dev = nullptr;
-    float* value_dev = nullptr;
-    float* ssl_dev = nullptr;
-    int cap = 0;
-    // staging buffers of m0_net_score: the stored targets in, the score columns out
-    float* score_pi_dev = nullptr;
-    float* score_z_dev = nullptr;
+    int cap[STAGE_GROUPS] = {0, 0, 0, 0};               // rows every array of the group holds; 0 after a failed growth
+    // STAGE_IO: the host-facing infer call
+    float *planes_dev = nullptr, *logits_dev = nullptr, *value_dev = nullptr, *ssl_dev = nullptr;
+    // STAGE_SCORE, m0_net_score: the stored targets in, the score columns out
+    float *score_pi_dev = nullptr, *score_z_dev = nullptr, *score_rows_dev = nullptr;
     uint8_t* score_mask_dev = nullptr;
-    float* score_rows_dev = nullptr;
-    int score_cap = 0;
-    // ... and of m0_net_score_ssl: stored SSL targets in, the SSL score columns out
-    float* ssl_targets_dev = nullptr;
-    float* ssl_rows_dev = nullptr;
-    int ssl_score_cap = 0;
-    // ... and of m0_net_score_aug: the kinds in, the transformed planes, pi and mask that its forward and score kernel read
-    uint8_t* aug_kinds_dev = nullptr;
-    float* aug_planes_dev = nullptr;
-    float* aug_pi_dev = nullptr;
-    uint8_t* aug_mask_dev = nullptr;
-    int aug_cap = 0;
+    // STAGE_SSL_SCORE, m0_net_score_ssl: stored SSL targets in, the SSL score columns out
+    float *ssl_targets_dev = nullptr, *ssl_rows_dev = nullptr;
+    // STAGE_AUG, m0_net_score_aug: the kinds in, the transformed planes, pi and mask that its forward and score kernel read
+    uint8_t *aug_kinds_dev = nullptr, *aug_mask_dev = nullptr;
+    float *aug_planes_dev = nullptr, *aug_pi_dev = nullptr;
+
+    // a group as (array, elements per row); a staging array is listed here and nowhere else
+    std::vector<StagedArray> staging(int group) {
+        const size_t planes = (size_t)net->cfg().planes * 64, sslc = net->ssl_channels_total() > 0 ? net->ssl_channels_total() : 1;
+        switch (group) {
+        case STAGE_IO: return {{planes_dev, planes}, {logits_dev, M0_POLICY_SIZE}, {value_dev, 1}, {ssl_dev, sslc * 64}};
+        case STAGE_SCORE: return {{score_pi_dev, M0_POLICY_SIZE}, {score_z_dev, 1}, {score_mask_dev, M0_POLICY_SIZE}, {score_rows_dev, M0_SCORE_COLS}};
+        case STAGE_SSL_SCORE: return {{ssl_targets_dev, (size_t)m0ssl::TARGET_CH * 64}, {ssl_rows_dev, M0_SSL_SCORE_COLS}};
+        case STAGE_AUG: return {{aug_kinds_dev, 1}, {aug_planes_dev, planes}, {aug_pi_dev, M0_POLICY_SIZE}, {aug_mask_dev, M0_POLICY_SIZE}};
+        }
+        return {};
+    }
 };
 
 Net* m0_net_impl(m0_net* n) { return n ? n->net : nullptr; }
@@ -66,6 +81,29 @@ hipError_t create_stream_cu_mask_env(const char* env_name, hipStream_t* stream) 
         q = (*end == ',') ? end + 1 : end;
     }
     return hipExtStreamCreateWithCUMask(stream, 8, words);
+}
+
+// Frees a group: through the network's status when it regrows, with the results dropped (hs null) at teardown.
+static void release_staging(m0_net* n, int group, HipStatus* hs) {
+    for (const StagedArray& a : n->staging(group)) {
+        if (*a.p && hs) M0_HIP(*hs, hipFree(*a.p));
+        else if (*a.p) (void)hipFree(*a.p);
+        *a.p = nullptr;
+    }
+    n->cap[group] = 0;
+}
+
+// Room for B rows in a group.  It grows only past its capacity, to max(B, 64) rows, and the old arrays are freed before the new
+// ones are allocated, so the peak does not double.
+static int reserve_staging(m0_net* n, int group, int B) {
+    if (B <= n->cap[group]) return M0_OK;
+    HipStatus& hs = n->net->hip();
+    release_staging(n, group, &hs);
+    const int rows = B < 64 ? 64 : B;
+    for (const StagedArray& a : n->staging(group)) M0_HIP(hs, hipMalloc(a.p, (size_t)rows * a.row_bytes));
+    if (!hs.ok()) return m0_hip_error(hs, STAGE_GROW_ERROR[group]);
+    n->cap[group] = rows;
+    return M0_OK;
 }
 
 extern "C" {
@@ -107,20 +145,7 @@ void m0_net_destroy(m0_net* n) {
     if (!n) return;
     (void)hipSetDevice(n->device);
     if (n->stream) { (void)hipStreamSynchronize(n->stream); }
-    if (n->planes_dev) (void)hipFree(n->planes_dev);
-    if (n->logits_dev) (void)hipFree(n->logits_dev);
-    if (n->value_dev) (void)hipFree(n->value_dev);
-    if (n->ssl_dev) (void)hipFree(n->ssl_dev);
-    if (n->score_pi_dev) (void)hipFree(n->score_pi_dev);
-    if (n->score_z_dev) (void)hipFree(n->score_z_dev);
-    if (n->score_mask_dev) (void)hipFree(n->score_mask_dev);
-    if (n->score_rows_dev) (void)hipFree(n->score_rows_dev);
-    if (n->ssl_targets_dev) (void)hipFree(n->ssl_targets_dev);
-    if (n->ssl_rows_dev) (void)hipFree(n->ssl_rows_dev);
-    if (n->aug_kinds_dev) (void)hipFree(n->aug_kinds_dev);
-    if (n->aug_planes_dev) (void)hipFree(n->aug_planes_dev);
-    if (n->aug_pi_dev) (void)hipFree(n->aug_pi_dev);
-    if (n->aug_mask_dev) (void)hipFree(n->aug_mask_dev);
+    for (int g = 0; g < STAGE_GROUPS; ++g) release_staging(n, g, nullptr);
     delete n->net;
     if (n->stream) (void)hipStreamDestroy(n->stream);
     delete n;
@@ -145,91 +170,13 @@ int m0_net_finalize(m0_net* n) {
     return rc;
 }
 
-static int ensure_io(m0_net* n, int B) {
-    if (B <= n->cap) return M0_OK;
-    HipStatus& hs = n->net->hip();
-    for (float** p : {&n->planes_dev, &n->logits_dev, &n->value_dev, &n->ssl_dev}) {
-        if (*p) M0_HIP(hs, hipFree(*p));
-        *p = nullptr;
-    }
-    n->cap = 0;
-    int cap = B < 64 ? 64 : B;
-    const int P = n->net->cfg().planes;
-    int sslc = n->net->ssl_channels_total();
-    M0_HIP(hs, hipMalloc((void**)&n->planes_dev, (size_t)cap * P * 64 * 4));
-    M0_HIP(hs, hipMalloc((void**)&n->logits_dev, (size_t)cap * M0_POLICY_SIZE * 4));
-    M0_HIP(hs, hipMalloc((void**)&n->value_dev, (size_t)cap * 4));
-    M0_HIP(hs, hipMalloc((void**)&n->ssl_dev, (size_t)cap * (sslc > 0 ? sslc : 1) * 64 * 4));
-    if (!hs.ok()) return m0_hip_error(hs, "hipMalloc failed for I/O staging");
-    n->cap = cap;
-    return M0_OK;
-}
-
-// the staging of m0_net_score, grown as ensure_io grows the forward's
-static int ensure_score_io(m0_net* n, int B) {
-    if (B <= n->score_cap) return M0_OK;
-    HipStatus& hs = n->net->hip();
-    if (n->score_pi_dev) M0_HIP(hs, hipFree(n->score_pi_dev));
-    if (n->score_z_dev) M0_HIP(hs, hipFree(n->score_z_dev));
-    if (n->score_mask_dev) M0_HIP(hs, hipFree(n->score_mask_dev));
-    if (n->score_rows_dev) M0_HIP(hs, hipFree(n->score_rows_dev));
-    n->score_pi_dev = n->score_z_dev = n->score_rows_dev = nullptr;
-    n->score_mask_dev = nullptr;
-    n->score_cap = 0;
-    const int cap = B < 64 ? 64 : B;
-    M0_HIP(hs, hipMalloc((void**)&n->score_pi_dev, (size_t)cap * M0_POLICY_SIZE * 4));
-    M0_HIP(hs, hipMalloc((void**)&n->score_z_dev, (size_t)cap * 4));
-    M0_HIP(hs, hipMalloc((void**)&n->score_mask_dev, (size_t)cap * M0_POLICY_SIZE));
-    M0_HIP(hs, hipMalloc((void**)&n->score_rows_dev, (size_t)cap * M0_SCORE_COLS * 4));
-    if (!hs.ok()) return m0_hip_error(hs, "hipMalloc failed for score staging");
-    n->score_cap = cap;
-    return M0_OK;
-}
-
-// the staging of m0_net_score_ssl
-static int ensure_ssl_score_io(m0_net* n, int B) {
-    if (B <= n->ssl_score_cap) return M0_OK;
-    HipStatus& hs = n->net->hip();
-    if (n->ssl_targets_dev) M0_HIP(hs, hipFree(n->ssl_targets_dev));
-    if (n->ssl_rows_dev) M0_HIP(hs, hipFree(n->ssl_rows_dev));
-    n->ssl_targets_dev = n->ssl_rows_dev = nullptr;
-    n->ssl_score_cap = 0;
-    const int cap = B < 64 ? 64 : B;
-    M0_HIP(hs, hipMalloc((void**)&n->ssl_targets_dev, (size_t)cap * m0ssl::TARGET_CH * 64 * 4));
-    M0_HIP(hs, hipMalloc((void**)&n->ssl_rows_dev, (size_t)cap * M0_SSL_SCORE_COLS * 4));
-    if (!hs.ok()) return m0_hip_error(hs, "hipMalloc failed for SSL score staging");
-    n->ssl_score_cap = cap;
-    return M0_OK;
-}
-
-// the staging of m0_net_score_aug
-static int ensure_aug_io(m0_net* n, int B) {
-    if (B <= n->aug_cap) return M0_OK;
-    HipStatus& hs = n->net->hip();
-    if (n->aug_kinds_dev) M0_HIP(hs, hipFree(n->aug_kinds_dev));
-    if (n->aug_planes_dev) M0_HIP(hs, hipFree(n->aug_planes_dev));
-    if (n->aug_pi_dev) M0_HIP(hs, hipFree(n->aug_pi_dev));
-    if (n->aug_mask_dev) M0_HIP(hs, hipFree(n->aug_mask_dev));
-    n->aug_kinds_dev = n->aug_mask_dev = nullptr;
-    n->aug_planes_dev = n->aug_pi_dev = nullptr;
-    n->aug_cap = 0;
-    const int cap = B < 64 ? 64 : B;
-    M0_HIP(hs, hipMalloc((void**)&n->aug_kinds_dev, (size_t)cap));
-    M0_HIP(hs, hipMalloc((void**)&n->aug_planes_dev, (size_t)cap * n->net->cfg().planes * 64 * 4));
-    M0_HIP(hs, hipMalloc((void**)&n->aug_pi_dev, (size_t)cap * M0_POLICY_SIZE * 4));
-    M0_HIP(hs, hipMalloc((void**)&n->aug_mask_dev, (size_t)cap * M0_POLICY_SIZE));
-    if (!hs.ok()) return m0_hip_error(hs, "hipMalloc failed for augmentation staging");
-    n->aug_cap = cap;
-    return M0_OK;
-}
-
 // The host-facing forward, under the network's lock.  tap_stream / tap_second (both or neither): the trunk tap's two buffers
 // after the forward, fp16 [B][64][width] widened to f32; the caller has armed the tap.
 static int infer_locked(m0_net* n, const float* planes, int B, float* policy, float* value, float* ssl,
                         float* tap_stream = nullptr, float* tap_second = nullptr, int* has_second = nullptr) {
     HipStatus& hs = n->net->hip();
     if (!M0_HIP(hs, hipSetDevice(n->device))) return m0_hip_error(hs);       // also a network that has failed before
-    int rc = ensure_io(n, B);
+    int rc = reserve_staging(n, STAGE_IO, B);
     if (rc != M0_OK) return rc;
     const int P = n->net->cfg().planes;
     const int sslc = n->net->ssl_channels_total();
@@ -273,24 +220,38 @@ int m0_net_infer(m0_net* n, const float* planes, int B, float* policy, float* va
     return infer_locked(n, planes, B, policy, value, ssl);
 }
 
-// m0_net_score, m0_net_score_ssl and m0_net_score_aug: one forward, then the score kernels on the buffers it left.  ssl_rows null:
-// without the SSL heads, as m0_net_score always ran.  kinds null (augmented false): the rows as they were uploaded, the launches
-// m0_net_score always made; otherwise augment_rows_kernel first moves them into the second staging set, and the forward and the
-// score kernel read that.  packed (m0_net_score_packed; planes, pi and legal_mask null then): the staging buffers that the dense
-// rows would be copied into are filled by unpacking on the stream instead, and everything behind them is the same.
-static int net_score(m0_net* n, const float* planes, const float* pi, const float* z, const uint8_t* legal_mask,
-                     const float* ssl_targets, const uint8_t* kinds, bool augmented, int B, const m0_score_opts* opts, float* rows,
-                     float* ssl_rows, const m0_rowpack_arrays* packed = nullptr) {
-    if (!n || (!packed && (!planes || !pi)) || !z || !rows) { m0_set_error("null argument"); return M0_ERR_INVALID; }
+// What m0_net_score, m0_net_score_packed, m0_net_score_aug and m0_net_score_ssl ask of net_score: one forward, then the score
+// kernels on the buffers it left.  ssl_rows null: without the SSL heads, as m0_net_score always ran.  augmented false: the rows as
+// they were uploaded, the launches m0_net_score always made; otherwise augment_rows_kernel first moves them into the second staging
+// set, and the forward and the score kernel read that.  packed (planes, pi and legal_mask null then): the staging buffers that
+// the dense rows would be copied into are filled by unpacking on the stream instead, and everything behind them is the same.
+struct ScoreRequest {
+    const float* planes = nullptr;                      // the rows: dense planes, pi and legal_mask (may be null) ...
+    const float* pi = nullptr;
+    const uint8_t* legal_mask = nullptr;
+    const m0_rowpack_arrays* packed = nullptr;          // ... or packed
+    const float* z = nullptr;
+    int B = 0;
+    const m0_score_opts* opts = nullptr;
+    float* rows = nullptr;
+    bool augmented = false;
+    const uint8_t* kinds = nullptr;
+    float* ssl_rows = nullptr;
+    const float* ssl_targets = nullptr;
+};
+
+static int net_score(m0_net* n, const ScoreRequest& q) {
+    const int B = q.B;
+    if (!n || (!q.packed && (!q.planes || !q.pi)) || !q.z || !q.rows) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     if (B <= 0) { m0_set_error("batch must be positive"); return M0_ERR_INVALID; }
-    const bool have_mask = packed ? packed->pos[0].mask_kind != M0_ROWPACK_MASK_NONE : legal_mask != nullptr;
-    if (const char* why = m0score::bad_opts(opts, have_mask)) { m0_set_error(why); return M0_ERR_INVALID; }
-    if (packed && n->net->cfg().planes != M0_PLANES) { m0_set_error("packed rows need the 19 planes of encode_board"); return M0_ERR_INVALID; }
-    if (augmented)
-        if (const char* why = m0_bad_kinds(kinds, B)) { m0_set_error(why); return M0_ERR_INVALID; }
+    const bool have_mask = q.packed ? q.packed->pos[0].mask_kind != M0_ROWPACK_MASK_NONE : q.legal_mask != nullptr;
+    if (const char* why = m0score::bad_opts(q.opts, have_mask)) { m0_set_error(why); return M0_ERR_INVALID; }
+    if (q.packed && n->net->cfg().planes != M0_PLANES) { m0_set_error("packed rows need the 19 planes of encode_board"); return M0_ERR_INVALID; }
+    if (q.augmented)
+        if (const char* why = m0_bad_kinds(q.kinds, B)) { m0_set_error(why); return M0_ERR_INVALID; }
     std::lock_guard<std::mutex> lk(n->mu);
     int tasks = 0;
-    if (ssl_rows) {
+    if (q.ssl_rows) {
         tasks = n->net->cfg().self_supervised ? n->net->cfg().ssl_tasks & m0sslscore::ALL_TASKS : 0;
         if (n->net->ssl_channels_total() == 0 || n->net->ssl_channels_total() != m0sslscore::channels(tasks)) {
             m0_set_error("the net has no SSL heads to score");
@@ -300,31 +261,31 @@ static int net_score(m0_net* n, const float* planes, const float* pi, const floa
     }
     HipStatus& hs = n->net->hip();
     if (!M0_HIP(hs, hipSetDevice(n->device))) return m0_hip_error(hs);       // also a network that has failed before
-    int rc = ensure_io(n, B);
-    if (rc == M0_OK) rc = ensure_score_io(n, B);
-    if (rc == M0_OK && ssl_rows) rc = ensure_ssl_score_io(n, B);
-    if (rc == M0_OK && augmented) rc = ensure_aug_io(n, B);
+    int rc = reserve_staging(n, STAGE_IO, B);
+    if (rc == M0_OK) rc = reserve_staging(n, STAGE_SCORE, B);
+    if (rc == M0_OK && q.ssl_rows) rc = reserve_staging(n, STAGE_SSL_SCORE, B);
+    if (rc == M0_OK && q.augmented) rc = reserve_staging(n, STAGE_AUG, B);
     if (rc != M0_OK) return rc;
-    const bool masked = opts->mask_mode == M0_SCORE_MASK_LEGAL;
+    const bool masked = q.opts->mask_mode == M0_SCORE_MASK_LEGAL;
     const size_t cells = (size_t)B * M0_POLICY_SIZE;
-    if (packed) {
-        rc = m0_rowpack_unpack_to_device(hs, packed, n->planes_dev, n->score_pi_dev, masked ? n->score_mask_dev : nullptr, n->stream);
+    if (q.packed) {
+        rc = m0_rowpack_unpack_to_device(hs, q.packed, n->planes_dev, n->score_pi_dev, masked ? n->score_mask_dev : nullptr, n->stream);
         if (rc != M0_OK) return rc;
-        M0_HIP(hs, hipMemcpyAsync(n->score_z_dev, z, (size_t)B * 4, hipMemcpyHostToDevice, n->stream));
+        M0_HIP(hs, hipMemcpyAsync(n->score_z_dev, q.z, (size_t)B * 4, hipMemcpyHostToDevice, n->stream));
     } else {
-        M0_HIP(hs, hipMemcpyAsync(n->planes_dev, planes, (size_t)B * n->net->cfg().planes * 64 * 4, hipMemcpyHostToDevice, n->stream));
-        M0_HIP(hs, hipMemcpyAsync(n->score_pi_dev, pi, cells * 4, hipMemcpyHostToDevice, n->stream));
-        M0_HIP(hs, hipMemcpyAsync(n->score_z_dev, z, (size_t)B * 4, hipMemcpyHostToDevice, n->stream));
-        if (masked) M0_HIP(hs, hipMemcpyAsync(n->score_mask_dev, legal_mask, cells, hipMemcpyHostToDevice, n->stream));
+        M0_HIP(hs, hipMemcpyAsync(n->planes_dev, q.planes, (size_t)B * n->net->cfg().planes * 64 * 4, hipMemcpyHostToDevice, n->stream));
+        M0_HIP(hs, hipMemcpyAsync(n->score_pi_dev, q.pi, cells * 4, hipMemcpyHostToDevice, n->stream));
+        M0_HIP(hs, hipMemcpyAsync(n->score_z_dev, q.z, (size_t)B * 4, hipMemcpyHostToDevice, n->stream));
+        if (masked) M0_HIP(hs, hipMemcpyAsync(n->score_mask_dev, q.legal_mask, cells, hipMemcpyHostToDevice, n->stream));
     }
-    if (ssl_rows && ssl_targets)
-        M0_HIP(hs, hipMemcpyAsync(n->ssl_targets_dev, ssl_targets, (size_t)B * m0ssl::TARGET_CH * 64 * 4, hipMemcpyHostToDevice, n->stream));
-    if (augmented) M0_HIP(hs, hipMemcpyAsync(n->aug_kinds_dev, kinds, (size_t)B, hipMemcpyHostToDevice, n->stream));
+    if (q.ssl_rows && q.ssl_targets)
+        M0_HIP(hs, hipMemcpyAsync(n->ssl_targets_dev, q.ssl_targets, (size_t)B * m0ssl::TARGET_CH * 64 * 4, hipMemcpyHostToDevice, n->stream));
+    if (q.augmented) M0_HIP(hs, hipMemcpyAsync(n->aug_kinds_dev, q.kinds, (size_t)B, hipMemcpyHostToDevice, n->stream));
     if (!hs.ok()) return m0_hip_error(hs, "H2D copy");
     const float* planes_in = n->planes_dev;
     const float* pi_in = n->score_pi_dev;
     const uint8_t* mask_in = masked ? n->score_mask_dev : nullptr;
-    if (augmented) {
+    if (q.augmented) {
         if (!M0_HIP(hs, launch_augment_rows(planes_in, pi_in, mask_in, n->aug_kinds_dev, M0_AUG_NONE, B, n->net->cfg().planes,
                                             n->aug_planes_dev, n->aug_pi_dev, masked ? n->aug_mask_dev : nullptr, n->stream)))
             return m0_hip_error(hs, "augment kernel");
@@ -333,45 +294,59 @@ static int net_score(m0_net* n, const float* planes, const float* pi, const floa
         if (masked) mask_in = n->aug_mask_dev;
     }
     std::string err;
-    rc = n->net->forward(planes_in, nullptr, B, n->logits_dev, n->value_dev, ssl_rows ? n->ssl_dev : nullptr, n->stream, err);
+    rc = n->net->forward(planes_in, nullptr, B, n->logits_dev, n->value_dev, q.ssl_rows ? n->ssl_dev : nullptr, n->stream, err);
     if (rc != M0_OK) { m0_set_error(err); return rc; }
     // the logits and the head outputs stay where the forward left them
-    M0_HIP(hs, launch_score_rows(n->logits_dev, n->value_dev, pi_in, n->score_z_dev, mask_in, B, *opts, n->score_rows_dev, n->stream));
-    M0_HIP(hs, hipMemcpyAsync(rows, n->score_rows_dev, (size_t)B * M0_SCORE_COLS * 4, hipMemcpyDeviceToHost, n->stream));
-    if (ssl_rows) {
-        M0_HIP(hs, launch_ssl_score(n->ssl_dev, tasks, n->planes_dev, ssl_targets ? n->ssl_targets_dev : nullptr, B, n->ssl_rows_dev,
+    M0_HIP(hs, launch_score_rows(n->logits_dev, n->value_dev, pi_in, n->score_z_dev, mask_in, B, *q.opts, n->score_rows_dev, n->stream));
+    M0_HIP(hs, hipMemcpyAsync(q.rows, n->score_rows_dev, (size_t)B * M0_SCORE_COLS * 4, hipMemcpyDeviceToHost, n->stream));
+    if (q.ssl_rows) {
+        M0_HIP(hs, launch_ssl_score(n->ssl_dev, tasks, n->planes_dev, q.ssl_targets ? n->ssl_targets_dev : nullptr, B, n->ssl_rows_dev,
                                     n->stream));
-        M0_HIP(hs, hipMemcpyAsync(ssl_rows, n->ssl_rows_dev, (size_t)B * M0_SSL_SCORE_COLS * 4, hipMemcpyDeviceToHost, n->stream));
+        M0_HIP(hs, hipMemcpyAsync(q.ssl_rows, n->ssl_rows_dev, (size_t)B * M0_SSL_SCORE_COLS * 4, hipMemcpyDeviceToHost, n->stream));
     }
     if (!M0_HIP(hs, hipStreamSynchronize(n->stream))) return m0_hip_error(hs, "forward and score failed");
     for (int b = 0; b < B; ++b)
-        if (((int)rows[(size_t)b * M0_SCORE_COLS + 7] & M0_SCORE_FLAG_NONFINITE) ||
-            (ssl_rows && ((int)ssl_rows[(size_t)b * M0_SSL_SCORE_COLS + 15] & M0_SSL_SCORE_FLAG_NONFINITE))) {
+        if (((int)q.rows[(size_t)b * M0_SCORE_COLS + 7] & M0_SCORE_FLAG_NONFINITE) ||
+            (q.ssl_rows && ((int)q.ssl_rows[(size_t)b * M0_SSL_SCORE_COLS + 15] & M0_SSL_SCORE_FLAG_NONFINITE))) {
             m0_set_error("network produced non-finite outputs (row " + std::to_string(b) + ")");
             return M0_ERR_NONFINITE;
         }
     return M0_OK;
 }
 
+// the dense rows and what every score call gives
+static ScoreRequest dense_request(const float* planes, const float* pi, const float* z, const uint8_t* legal_mask, int B,
+                                  const m0_score_opts* opts, float* rows) {
+    ScoreRequest q;
+    q.planes = planes; q.pi = pi; q.z = z; q.legal_mask = legal_mask; q.B = B; q.opts = opts; q.rows = rows;
+    return q;
+}
+
 int m0_net_score(m0_net* n, const float* planes, const float* pi, const float* z, const uint8_t* legal_mask, int B,
                  const m0_score_opts* opts, float* rows) {
-    return net_score(n, planes, pi, z, legal_mask, nullptr, nullptr, false, B, opts, rows, nullptr);
+    return net_score(n, dense_request(planes, pi, z, legal_mask, B, opts, rows));
 }
 
 int m0_net_score_packed(m0_net* n, const m0_rowpack_arrays* in, const m0_score_opts* opts, float* rows) {
     if (!in || !in->pos || !in->z || in->n <= 0 || in->n > INT_MAX) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
-    return net_score(n, nullptr, nullptr, in->z, nullptr, nullptr, nullptr, false, (int)in->n, opts, rows, nullptr, in);
+    ScoreRequest q;
+    q.packed = in; q.z = in->z; q.B = (int)in->n; q.opts = opts; q.rows = rows;
+    return net_score(n, q);
 }
 
 int m0_net_score_aug(m0_net* n, const float* planes, const float* pi, const float* z, const uint8_t* legal_mask, const uint8_t* kinds,
                      int B, const m0_score_opts* opts, float* rows) {
-    return net_score(n, planes, pi, z, legal_mask, nullptr, kinds, true, B, opts, rows, nullptr);
+    ScoreRequest q = dense_request(planes, pi, z, legal_mask, B, opts, rows);
+    q.augmented = true; q.kinds = kinds;
+    return net_score(n, q);
 }
 
 int m0_net_score_ssl(m0_net* n, const float* planes, const float* pi, const float* z, const uint8_t* legal_mask,
                      const float* ssl_targets, int B, const m0_score_opts* opts, float* rows, float* ssl_rows) {
     if (!ssl_rows) { m0_set_error("null argument"); return M0_ERR_INVALID; }
-    return net_score(n, planes, pi, z, legal_mask, ssl_targets, nullptr, false, B, opts, rows, ssl_rows);
+    ScoreRequest q = dense_request(planes, pi, z, legal_mask, B, opts, rows);
+    q.ssl_rows = ssl_rows; q.ssl_targets = ssl_targets;
+    return net_score(n, q);
 }
 
 int m0_net_tap_info(const m0_net* n, int* steps, int* width) {
@@ -430,7 +405,7 @@ int m0_net_bench_forward(m0_net* n, int B, int iters, int with_ssl, float* ms_pe
     std::lock_guard<std::mutex> lk(n->mu);
     HipStatus& hs = n->net->hip();
     if (!M0_HIP(hs, hipSetDevice(n->device))) return m0_hip_error(hs);
-    int rc = ensure_io(n, B);
+    int rc = reserve_staging(n, STAGE_IO, B);
     if (rc != M0_OK) return rc;
     std::string err;
     // synthetic resident input: sparse 0/1 piece planes + constant planes (with_ssl bit 1: keep the input of the previous call
@@ -438,9 +413,9 @@ int m0_net_bench_forward(m0_net* n, int B, int iters, int with_ssl, float* ms_pe
     if (!(with_ssl & 2)) {
         const int P = n->net->cfg().planes;
         std::vector<float> h((size_t)B * P * 64, 0.f);
-        uint64_t s = 0x9E3779B97F4A7C15ull;
+        BenchRng rng;
         for (size_t i = 0; i < h.size(); ++i) {
-            s ^= s << 13; s ^= s >> 7; s ^= s << 17;
+            const uint64_t s = rng.next();
             int p = (int)((i / 64) % P);
             if (p < 12) h[i] = ((s >> 20) % 100) < 8 ? 1.f : 0.f;
             else h[i] = (float)((((i / 64 / P) * 7 + p) % 10) / 10.0);
@@ -450,21 +425,13 @@ int m0_net_bench_forward(m0_net* n, int B, int iters, int with_ssl, float* ms_pe
     float* ssl = ((with_ssl & 1) && n->net->ssl_channels_total() > 0) ? n->ssl_dev : nullptr;
     rc = n->net->forward(n->planes_dev, nullptr, B, n->logits_dev, n->value_dev, ssl, n->stream, err);   // warm-up
     if (rc != M0_OK) { m0_set_error(err); return rc; }
-    struct Events {                          // destroyed on every way out
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-    } ev;
-    M0_HIP(hs, hipEventCreate(&ev.e0)); M0_HIP(hs, hipEventCreate(&ev.e1));
-    M0_HIP(hs, hipEventRecord(ev.e0, n->stream));
-    for (int i = 0; i < iters && hs.ok(); ++i) {
+    const float ms = m0_time_iterations(hs, n->stream, iters, [&]() {
         rc = n->net->forward(n->planes_dev, nullptr, B, n->logits_dev, n->value_dev, ssl, n->stream, err);
-        if (rc != M0_OK) { m0_set_error(err); return rc; }
-    }
-    M0_HIP(hs, hipEventRecord(ev.e1, n->stream));
-    M0_HIP(hs, hipEventSynchronize(ev.e1));
-    float ms = 0.f;
-    if (!M0_HIP(hs, hipEventElapsedTime(&ms, ev.e0, ev.e1))) return m0_hip_error(hs, "bench forward failed");
-    *ms_per_forward = ms / iters;
+        return rc == M0_OK;
+    });
+    if (rc != M0_OK) { m0_set_error(err); return rc; }
+    if (!hs.ok()) return m0_hip_error(hs, "bench forward failed");
+    *ms_per_forward = ms;
     n->net->harvest_profile();
     return M0_OK;
 }

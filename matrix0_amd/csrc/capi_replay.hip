@@ -72,10 +72,8 @@ int m0_replay_games(int hip_device, const char* const* start_fens, const uint32_
         const char* fen = start_fens && start_fens[g] ? start_fens[g] : START_FEN;
         if (parse_fen(fen, hstart[g]) != 0) { m0_set_error(std::string("bad FEN at index ") + std::to_string(g)); return M0_ERR_INVALID; }
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { m0_set_error("no HIP device available (no CPU fallback)"); return M0_ERR_HIP; }
     HipStatus hs;
-    if (!M0_HIP(hs, hipSetDevice(hip_device))) return m0_hip_error(hs);
+    if (const int rc = m0_select_device(hs, hip_device)) return rc;
 
     // A game puts min(tokens, max_plies + 1) rows on the device: the tokens it may resolve, and one more for a game past the
     // cap so that the kernel sees it is longer.  A launch takes whole games while they fit; a game larger than the limit goes alone.

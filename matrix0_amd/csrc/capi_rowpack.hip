@@ -14,18 +14,6 @@ using namespace m0rowpack;
 
 namespace {
 
-template <typename T>
-bool upload(HipStatus& hs, DevBuf<T>& d, const T* host, size_t count, hipStream_t st) {
-    if (!d.alloc(hs, count ? count : 1)) return false;
-    return count == 0 || M0_HIP(hs, hipMemcpyAsync(d.p, host, count * sizeof(T), hipMemcpyHostToDevice, st));
-}
-
-int select_device(HipStatus& hs, int hip_device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { m0_set_error("no HIP device available (use the _host call)"); return M0_ERR_HIP; }
-    return M0_HIP(hs, hipSetDevice(hip_device)) ? M0_OK : m0_hip_error(hs);
-}
-
 int invalid(const std::string& why) { m0_set_error(why); return M0_ERR_INVALID; }
 
 }  // namespace
@@ -45,17 +33,17 @@ int m0_rowpack_unpack_to_device(HipStatus& hs, const m0_rowpack_arrays* in, floa
     DevBuf<float> dpv, drs, drp;
     DevBuf<uint8_t> drm;
     DevBuf<int32_t> dslot;
-    upload(hs, dpos, positions.data(), n, st);
-    upload(hs, dq, in->pos, n, st);
-    upload(hs, dpo, in->pi_off, n + 1, st);
-    upload(hs, dmo, in->mask_off, n + 1, st);
-    upload(hs, dpi, in->pi_idx, (size_t)in->pi_n, st);
-    upload(hs, dpv, in->pi_val, (size_t)in->pi_n, st);
-    upload(hs, dmi, in->mask_idx, mask_dev ? (size_t)in->mask_n : 0, st);
-    upload(hs, dslot, raw_slot.data(), n, st);
-    upload(hs, drs, in->raw_planes, raw * PLANE_FLOATS, st);
-    upload(hs, drp, in->raw_pi, raw * COLS, st);
-    upload(hs, drm, in->raw_mask, mask_dev ? raw * COLS : 0, st);
+    dpos.upload(hs, positions.data(), n, st);
+    dq.upload(hs, in->pos, n, st);
+    dpo.upload(hs, in->pi_off, n + 1, st);
+    dmo.upload(hs, in->mask_off, n + 1, st);
+    dpi.upload(hs, in->pi_idx, (size_t)in->pi_n, st);
+    dpv.upload(hs, in->pi_val, (size_t)in->pi_n, st);
+    dmi.upload(hs, in->mask_idx, mask_dev ? (size_t)in->mask_n : 0, st);
+    dslot.upload(hs, raw_slot.data(), n, st);
+    drs.upload(hs, in->raw_planes, raw * PLANE_FLOATS, st);
+    drp.upload(hs, in->raw_pi, raw * COLS, st);
+    drm.upload(hs, in->raw_mask, mask_dev ? raw * COLS : 0, st);
     if (!hs.ok()) return m0_hip_error(hs, "packed rows upload failed");
     M0_HIP(hs, launch_encode_positions(dpos.p, (int)n, planes_dev, nullptr, mask_dev, nullptr, nullptr, nullptr, st));
     M0_HIP(hs, launch_rowpack_unpack(dq.p, dpo.p, dpi.p, dpv.p, dmo.p, dmi.p, dslot.p, drs.p, drp.p, drm.p, (int)n, planes_dev, pi_dev,
@@ -89,7 +77,7 @@ int m0_rowpack_pack(int hip_device, const float* planes, const float* pi, const 
                     m0_rowpack_arrays* out, int64_t* sizes) {
     if (!planes || !z || !out || !sizes || n <= 0) return invalid("invalid argument");
     HipStatus hs;
-    const int rc = select_device(hs, hip_device);
+    const int rc = m0_select_device(hs, hip_device, "use the _host call");
     if (rc != M0_OK) return rc;
     const size_t N = (size_t)n;
     DevBuf<float> dpl, dpi;
@@ -97,9 +85,9 @@ int m0_rowpack_pack(int hip_device, const float* planes, const float* pi, const 
     DevBuf<Pos> dpos;
     DevBuf<int32_t> dst, dfl, dnl, dcnt;
     DevBuf<m0_rowpack_pos> dq;
-    upload(hs, dpl, planes, N * PLANE_FLOATS, nullptr);
-    if (pi) upload(hs, dpi, pi, N * COLS, nullptr);
-    if (legal_mask) upload(hs, dm, legal_mask, N * COLS, nullptr);
+    dpl.upload(hs, planes, N * PLANE_FLOATS);
+    if (pi) dpi.upload(hs, pi, N * COLS);
+    if (legal_mask) dm.upload(hs, legal_mask, N * COLS);
     if (!dpos.alloc(hs, N) || !dst.alloc(hs, N) || !dfl.alloc(hs, N) || !dnl.alloc(hs, N) || !dcnt.alloc(hs, 2 * N) || !dq.alloc(hs, N))
         return m0_hip_error(hs, "hipMalloc or upload failed");
     M0_HIP(hs, launch_decode_planes(dpl.p, dm.p, n, dpos.p, dst.p, dfl.p, dnl.p, nullptr));
@@ -120,9 +108,9 @@ int m0_rowpack_pack(int hip_device, const float* planes, const float* pi, const 
     DevBuf<float> dval, drs, drp;
     DevBuf<uint8_t> drm;
     const size_t npi = (size_t)sizes[0], nmk = (size_t)sizes[1], raw = (size_t)sizes[2];
-    upload(hs, dpo, pi_off.data(), N + 1, nullptr);
-    upload(hs, dmo, mask_off.data(), N + 1, nullptr);
-    upload(hs, dslot, raw_slot.data(), N, nullptr);
+    dpo.upload(hs, pi_off.data(), N + 1);
+    dmo.upload(hs, mask_off.data(), N + 1);
+    dslot.upload(hs, raw_slot.data(), N);
     if (!didx.alloc(hs, npi + 1) || !dval.alloc(hs, npi + 1) || !dmidx.alloc(hs, nmk + 1) || !drs.alloc(hs, raw * PLANE_FLOATS + 1) ||
         !drp.alloc(hs, raw * COLS + 1) || !drm.alloc(hs, raw * COLS + 1)) return m0_hip_error(hs, "hipMalloc or upload failed");
     M0_HIP(hs, launch_rowpack_fill(dpl.p, dpi.p, dm.p, dq.p, dpo.p, dmo.p, dslot.p, n, didx.p, dval.p, dmidx.p, drs.p, drp.p, drm.p, nullptr));
@@ -154,7 +142,7 @@ int m0_rowpack_unpack(int hip_device, const m0_rowpack_arrays* in, float* planes
     if (in->n <= 0 || !in->pos) return invalid("packed rows: the number of rows must be positive");
     if ((legal_mask != nullptr) != has_masks(*in)) return invalid("packed rows: the mask output must be given exactly for rows with masks");
     HipStatus hs;
-    int rc = select_device(hs, hip_device);
+    int rc = m0_select_device(hs, hip_device, "use the _host call");
     if (rc != M0_OK) return rc;
     const size_t N = (size_t)in->n;
     DevBuf<float> dpl, dpi;
@@ -174,13 +162,12 @@ int m0_rowpack_unpack(int hip_device, const m0_rowpack_arrays* in, float* planes
 int m0_rowpack_bench(int hip_device, int B, int iters, float* pack_us, float* unpack_us, double* dense_bytes) {
     if (B <= 0 || iters <= 0 || !pack_us || !unpack_us || !dense_bytes) return invalid("invalid argument");
     HipStatus hs;
-    int rc = select_device(hs, hip_device);
+    int rc = m0_select_device(hs, hip_device, "use the _host call");
     if (rc != M0_OK) return rc;
     const size_t N = (size_t)B;
     std::vector<float> planes(N * PLANE_FLOATS), pi(N * COLS, 0.f), z(N, 0.f);
     std::vector<uint8_t> mask(N * COLS, 0);
-    uint64_t s = 0x9E3779B97F4A7C15ull;
-    auto next = [&]() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return s; };
+    BenchRng rng;
     const char* start = "rnbqkbnr/pppppppp/8/8/8/8/PPPPPPPP/RNBQKBNR w KQkq - 0 1";
     Pos p;
     m0::parse_fen(start, p);
@@ -193,10 +180,10 @@ int m0_rowpack_bench(int hip_device, int B, int iters, float* pack_us, float* un
         for (int j = 0; j < k; ++j) {
             const int idx = m0::move_to_index(p, mv[j]);
             mask[i * COLS + idx] = 1;
-            if (next() % 3 || j == 0) sum += pi[i * COLS + idx] = (float)(1 + next() % 100);
+            if (rng.next() % 3 || j == 0) sum += pi[i * COLS + idx] = (float)(1 + rng.next() % 100);
         }
         for (int j = 0; j < k; ++j) pi[i * COLS + m0::move_to_index(p, mv[j])] /= sum;
-        m0::make_move(p, mv[next() % k]);
+        m0::make_move(p, mv[rng.next() % k]);
     }
     // the packed form of these rows, once, for the offsets of the fill pass and as the input of unpacking
     int64_t sizes[3];
@@ -222,48 +209,37 @@ int m0_rowpack_bench(int hip_device, int B, int iters, float* pack_us, float* un
     DevBuf<m0_rowpack_pos> dq;
     DevBuf<int64_t> dpo, dmo;
     DevBuf<uint16_t> didx, dmidx;
-    upload(hs, dpl, planes.data(), N * PLANE_FLOATS, nullptr);
-    upload(hs, dpi, pi.data(), N * COLS, nullptr);
-    upload(hs, dm, mask.data(), N * COLS, nullptr);
-    upload(hs, dpo, hpo.data(), N + 1, nullptr);
-    upload(hs, dmo, hmo.data(), N + 1, nullptr);
-    upload(hs, dslot, raw_slot.data(), N, nullptr);
+    dpl.upload(hs, planes.data(), N * PLANE_FLOATS);
+    dpi.upload(hs, pi.data(), N * COLS);
+    dm.upload(hs, mask.data(), N * COLS);
+    dpo.upload(hs, hpo.data(), N + 1);
+    dmo.upload(hs, hmo.data(), N + 1);
+    dslot.upload(hs, raw_slot.data(), N);
     if (!dpos.alloc(hs, N) || !dst.alloc(hs, N) || !dfl.alloc(hs, N) || !dnl.alloc(hs, N) || !dcnt.alloc(hs, 2 * N) || !dq.alloc(hs, N) ||
         !didx.alloc(hs, hidx.size() + 1) || !dval.alloc(hs, hidx.size() + 1) || !dmidx.alloc(hs, 1) || !opl.alloc(hs, N * PLANE_FLOATS) ||
         !opi.alloc(hs, N * COLS) || !om.alloc(hs, N * COLS)) return m0_hip_error(hs, "hipMalloc or upload failed");
     auto pack = [&]() {
         M0_HIP(hs, launch_decode_planes(dpl.p, dm.p, B, dpos.p, dst.p, dfl.p, dnl.p, nullptr));
         M0_HIP(hs, launch_rowpack_count(dpi.p, dm.p, dpos.p, dst.p, B, dq.p, dcnt.p, nullptr));
-        M0_HIP(hs, launch_rowpack_fill(dpl.p, dpi.p, dm.p, dq.p, dpo.p, dmo.p, dslot.p, B, didx.p, dval.p, dmidx.p, nullptr, nullptr,
-                                       nullptr, nullptr));
+        return M0_HIP(hs, launch_rowpack_fill(dpl.p, dpi.p, dm.p, dq.p, dpo.p, dmo.p, dslot.p, B, didx.p, dval.p, dmidx.p, nullptr,
+                                              nullptr, nullptr, nullptr));
     };
     auto unpack = [&]() {
         M0_HIP(hs, launch_encode_positions(dpos.p, B, opl.p, nullptr, om.p, nullptr, nullptr, nullptr, nullptr));
-        M0_HIP(hs, launch_rowpack_unpack(dq.p, dpo.p, didx.p, dval.p, dmo.p, dmidx.p, dslot.p, nullptr, nullptr, nullptr, B, opl.p,
-                                         opi.p, om.p, nullptr));
+        return M0_HIP(hs, launch_rowpack_unpack(dq.p, dpo.p, didx.p, dval.p, dmo.p, dmidx.p, dslot.p, nullptr, nullptr, nullptr, B,
+                                                opl.p, opi.p, om.p, nullptr));
     };
     pack(); unpack();                                                                   // warm-up
-    struct Events {                          // destroyed on every way out
-        hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-        ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-    } ev;
-    for (hipEvent_t& x : ev.e) M0_HIP(hs, hipEventCreate(&x));
-    M0_HIP(hs, hipEventRecord(ev.e[0], nullptr));
-    for (int i = 0; i < iters; ++i) pack();
-    M0_HIP(hs, hipEventRecord(ev.e[1], nullptr));
-    for (int i = 0; i < iters; ++i) unpack();
-    M0_HIP(hs, hipEventRecord(ev.e[2], nullptr));
-    M0_HIP(hs, hipEventSynchronize(ev.e[2]));
-    float ms_pack = 0.f, ms_unpack = 0.f;
-    M0_HIP(hs, hipEventElapsedTime(&ms_pack, ev.e[0], ev.e[1]));
-    if (!M0_HIP(hs, hipEventElapsedTime(&ms_unpack, ev.e[1], ev.e[2]))) return m0_hip_error(hs, "rowpack bench failed");
+    const float ms_pack = m0_time_iterations(hs, nullptr, iters, pack);
+    const float ms_unpack = m0_time_iterations(hs, nullptr, iters, unpack);
+    if (!hs.ok()) return m0_hip_error(hs, "rowpack bench failed");
     // what the kernels wrote last is what the host packs and unpacks
     std::vector<float> back(N * COLS);
     opi.download(hs, back.data(), N * COLS);
     if (!hs.ok()) return m0_hip_error(hs, "download failed");
     if (memcmp(back.data(), pi.data(), N * COLS * sizeof(float)) != 0) return invalid("the bench rows did not come back");
-    *pack_us = ms_pack * 1000.f / (float)iters;
-    *unpack_us = ms_unpack * 1000.f / (float)iters;
+    *pack_us = ms_pack * 1000.f;
+    *unpack_us = ms_unpack * 1000.f;
     *dense_bytes = (double)B * (PLANE_FLOATS * 4.0 + COLS * 4.0 + COLS);
     return M0_OK;
 }

@@ -56,6 +56,7 @@ from __future__ import annotations
 import argparse
 import json
 import sys
+from collections import namedtuple
 from pathlib import Path
 from typing import Dict, List, Mapping, Optional, Sequence
 
@@ -80,12 +81,22 @@ def trainer_weights(augment_rotate180: bool = True) -> Dict[str, float]:
     return {"hflip": 0.5, "rot180": rot, "none": 0.5 - rot}
 
 
+_SSL_AUG = "the trainer leaves stored SSL targets untransformed, and targets taken from rotated planes are not positions the decoder accepts"
+
+
 def _check_augment(augment, ssl) -> None:
     if isinstance(augment, str) and augment not in AUGMENT_MODES:
         raise ValueError(f"augment must be one of {AUGMENT_MODES}, a per-row array of kinds or None, got {augment!r}")
     if ssl is not None and augment is not None and not (isinstance(augment, str) and augment == "none"):
-        raise ValueError("ssl cannot be combined with an augmentation other than 'none': the trainer leaves stored SSL targets "
-                         "untransformed, and targets taken from rotated planes are not positions the decoder accepts")
+        raise ValueError("ssl cannot be combined with an augmentation other than 'none': " + _SSL_AUG)
+    if ssl is not None and ssl not in SSL_MODES:
+        raise ValueError(f"ssl must be one of {SSL_MODES} or None, got {ssl!r}")
+
+
+def _chunks(n: int, batch: int):
+    """(a, b) of every chunk of `batch` rows out of n, the last one partial"""
+    for a in range(0, n, batch):
+        yield a, min(n, a + batch)
 
 
 def pack_ssl_targets(arrays: Mapping[str, np.ndarray], n: int, tasks: Sequence[str]) -> np.ndarray:
@@ -128,30 +139,33 @@ def score_arrays(backend, s, pi, z, legal_mask=None, *, batch: int = 4096, mask_
     if per_row is not None and per_row.shape != (n,):
         raise ValueError(f"per-row augmentation kinds must be [{n}], got {per_row.shape}")
     more = lambda a, b: {} if augment is None or ssl is not None else {"augment": augment if per_row is None else per_row[a:b]}
-    out = np.empty((n, SCORE_COLS), np.float32)
-    if ssl is not None:
-        if ssl not in SSL_MODES:
-            raise ValueError(f"ssl must be one of {SSL_MODES} or None, got {ssl!r}")
-        if ssl == "stored" and ssl_targets is None:
-            raise ValueError("ssl='stored' needs ssl_targets")
-        targets = None if ssl == "planes" else ssl_targets
-        ssl_out = np.empty((n, SSL_SCORE_COLS), np.float32)
-        for a in range(0, n, batch):
-            b = min(n, a + batch)
-            try:
-                out[a:b], ssl_out[a:b] = backend.score_ssl(s[a:b], pi[a:b], z[a:b], None if legal_mask is None else legal_mask[a:b],
-                                                           None if targets is None else targets[a:b], mask_mode=mode, **opts)
-            except NonFiniteScore as e:
-                out[a:b], ssl_out[a:b] = e.rows, e.ssl_rows
-        return out, ssl_out
-    for a in range(0, n, batch):
-        b = min(n, a + batch)
+    cut = lambda x, a, b: None if x is None else x[a:b]
+    if ssl == "stored" and ssl_targets is None:
+        raise ValueError("ssl='stored' needs ssl_targets")
+    targets = None if ssl == "planes" else ssl_targets
+    outs = [np.empty((n, cols), np.float32) for cols in ((SCORE_COLS,) if ssl is None else (SCORE_COLS, SSL_SCORE_COLS))]
+    for a, b in _chunks(n, batch):
+        dense = (s[a:b], pi[a:b], z[a:b], cut(legal_mask, a, b))
         try:
-            out[a:b] = backend.score(s[a:b], pi[a:b], z[a:b], None if legal_mask is None else legal_mask[a:b], mask_mode=mode, **opts,
-                                     **more(a, b))
+            if ssl is None:
+                got = (backend.score(*dense, mask_mode=mode, **opts, **more(a, b)),)
+            else:
+                got = backend.score_ssl(*dense, cut(targets, a, b), mask_mode=mode, **opts)
         except NonFiniteScore as e:
-            out[a:b] = e.rows
-    return out
+            got = (e.rows, e.ssl_rows)
+        for out, rows in zip(outs, got):
+            out[a:b] = rows
+    return outs[0] if ssl is None else tuple(outs)
+
+
+def _count_flags(sums, flags: np.ndarray, bits: Mapping[str, int], left_out: int) -> np.ndarray:
+    """counts a batch's flags, rows and scored rows into a Sums or SslSums; returns the rows to sum: those with no flag of left_out"""
+    for name, bit in bits.items():
+        sums.flags[name] += int(((flags & bit) != 0).sum())
+    keep = (flags & left_out) == 0
+    sums.rows += len(flags)
+    sums.scored += int(keep.sum())
+    return keep
 
 
 class Sums:
@@ -166,13 +180,8 @@ class Sums:
 
     def add(self, rows: np.ndarray, z: np.ndarray) -> None:
         r = np.asarray(rows, np.float64)
-        flags = r[:, FLAGS].astype(np.int64)
-        for name, bit in SCORE_FLAGS.items():
-            self.flags[name] += int(((flags & bit) != 0).sum())
-        keep = (flags & _LEFT_OUT) == 0
+        keep = _count_flags(self, r[:, FLAGS].astype(np.int64), SCORE_FLAGS, _LEFT_OUT)
         r, zz = r[keep], np.asarray(z, np.float64).reshape(-1)[keep]
-        self.rows += len(rows)
-        self.scored += len(r)
         signed = zz != 0
         for key, x in (("policy_loss", r[:, POLICY]), ("entropy", r[:, ENTROPY]), ("value_loss", r[:, VALUE_LOSS]),
                        ("top1", r[:, RANK] < 1), ("top3", r[:, RANK] < 3), ("top5", r[:, RANK] < 5), ("support_mass", r[:, MASS]),
@@ -203,13 +212,8 @@ class SslSums:
 
     def add(self, ssl_rows: np.ndarray, stored: bool) -> None:
         r = np.asarray(ssl_rows, np.float64)
-        flags = r[:, SSL_FLAGS_COL].astype(np.int64)
-        for name, bit in SSL_SCORE_FLAGS.items():
-            self.flags[name] += int(((flags & bit) != 0).sum())
         left_out = SSL_SCORE_FLAGS["nonfinite"] | (0 if stored else SSL_SCORE_FLAGS["planes"])
-        keep = (flags & left_out) == 0
-        self.rows += len(r)
-        self.scored += int(keep.sum())
+        keep = _count_flags(self, r[:, SSL_FLAGS_COL].astype(np.int64), SSL_SCORE_FLAGS, left_out)
         self.sum += r[keep, :SSL_FLAGS_COL].sum(axis=0, dtype=np.float64)
 
     def report(self, base: dict, tasks: Sequence[str], task_weights: Mapping[str, float], ssl_weight: float) -> dict:
@@ -295,10 +299,60 @@ def _packed_rows(path, expected_planes: int):
 def _score_packed(backend, packed, batch: int, **opts) -> np.ndarray:
     """score_arrays of packed rows: chunks of M0Backend.score(packed=...), unpacked on the device"""
     out = np.empty((packed.n, SCORE_COLS), np.float32)
-    for a in range(0, packed.n, batch):
-        b = min(a + batch, packed.n)
+    for a, b in _chunks(packed.n, batch):
         out[a:b] = backend.score(packed=packed.rows(a, b), **opts)
     return out
+
+
+# _score_shard's answer; ssl_rows and stored (the targets were the shard's own) with ssl, rows3 (every kind's columns) with "trainer"
+ShardScore = namedtuple("ShardScore", "rows z mode ssl_rows stored rows3", defaults=(None, False, None))
+
+
+def _score_shard(backend, reader, path, batch, expected_planes, ssl, tasks, augment, opts) -> Optional[ShardScore]:
+    """One shard scored as score_shards was asked to; None when it does not load, does not hold 4672 columns or, packed, does not
+    hold together.  A packed shard goes to the device as it is when nothing but the rows' own columns is wanted."""
+    packed = _packed_rows(path, expected_planes) if ssl is None and augment is None else None
+    if packed is not None:
+        from .rowpack import mask_mode_of
+        mode = mask_mode_of(packed, opts.get("mask_mode"))
+        try:
+            return ShardScore(_score_packed(backend, packed, batch, **dict(opts, mask_mode=mode)), packed.z, mode)
+        except NonFiniteScore:
+            raise
+        except ValueError:                                          # as an unreadable dense shard
+            return None
+    try:
+        s, pi, z, mask = reader._load(path)                         # None for a shard the reader refuses: that fails here as well
+    except Exception:
+        return None
+    if pi.shape[1] != POLICY_SIZE:                                  # the only policy layout the engine has
+        return None
+    mode = resolve_mask_mode(pi, mask, opts.get("mask_mode"))
+    opts = dict(opts, mask_mode=mode)
+    if ssl is None:
+        rows = score_arrays(backend, s, pi, z, mask, batch=batch, augment=augment, **opts)
+        return ShardScore(rows[AUGMENT_KINDS["none"]], z, mode, rows3=rows) if augment == "trainer" else ShardScore(rows, z, mode)
+    have = {} if ssl == "planes" else _stored_ssl(path)
+    stored = ssl == "stored" or (ssl == "auto" and all("ssl_" + t in have for t in tasks))
+    try:
+        targets = pack_ssl_targets(have, len(s), tasks) if stored else None
+    except KeyError as e:
+        raise KeyError(f"{Path(path).name}: {e.args[0]} (ssl='stored')") from None
+    rows, ssl_rows = score_arrays(backend, s, pi, z, mask, batch=batch, ssl="stored" if stored else "planes", ssl_targets=targets, **opts)
+    return ShardScore(rows, z, mode, ssl_rows, stored)
+
+
+def _write_per_sample(path, kept: Sequence[ShardScore], shards: Sequence[str], ssl: Optional[str], augment: Optional[str]) -> None:
+    """The per-row columns of every scored shard, in the order of `shards`, as the .npz of score_shards' docstring."""
+    cat = lambda parts, dtype=np.float32, shape=(0, SCORE_COLS): np.concatenate(parts) if parts else np.zeros(shape, dtype)
+    more = {} if ssl is None else {"ssl_columns": cat([x.ssl_rows for x in kept], np.float32, (0, SSL_SCORE_COLS))}
+    for k in (AUGMENT_KINDS if augment == "trainer" else () if augment is None else (augment,)):
+        more["columns_" + k] = cat([x.rows3[AUGMENT_KINDS[k]] if augment == "trainer" else x.rows for x in kept])
+    with open(path, "wb") as f:
+        np.savez(f, columns=cat([x.rows for x in kept]),
+                 shard_index=cat([np.full(len(x.rows), i, np.int32) for i, x in enumerate(kept)], np.int32, (0,)),
+                 row=cat([np.arange(len(x.rows), dtype=np.int32) for x in kept], np.int32, (0,)),
+                 shards=np.array(list(shards), dtype=str), **more)
 
 
 def score_shards(data_dir, backend, *, sources: Sequence[str] = ("selfplay", ""), batch: int = 4096,
@@ -321,10 +375,8 @@ def score_shards(data_dir, backend, *, sources: Sequence[str] = ("selfplay", "")
     _check_augment(augment, ssl)
     trainer = augment == "trainer"
     weights = trainer_weights(augment_rotate180)
-    aug_total = AugmentSums()
+    tasks: List[str] = []
     if ssl is not None:
-        if ssl not in SSL_MODES:
-            raise ValueError(f"ssl must be one of {SSL_MODES} or None, got {ssl!r}")
         if float(ssl_target_weight) != 1.0:
             raise ValueError("ssl_target_weight other than 1.0 scales the targets of a training step; a read-only score has no use for it")
         tasks = list(backend.ssl_tasks)
@@ -336,84 +388,34 @@ def score_shards(data_dir, backend, *, sources: Sequence[str] = ("selfplay", "")
         ssl_report = lambda sums, base: sums.report(base, tasks, ssl_task_weights, ssl_weight)
     reader = ReplayReader(str(data_dir), expected_planes=expected_planes)
     total, by_source, by_shard, skipped = Sums(), {}, {}, []
-    ssl_total, ssl_by_source = SslSums(), {}
-    keep: Dict[str, List[np.ndarray]] = {"columns": [], "shard_index": [], "row": [], "ssl_columns": []}
-    keep.update({"columns_" + k: [] for k in AUGMENT_KINDS})
+    ssl_total, ssl_by_source, aug_total, kept = SslSums(), {}, AugmentSums(), []
     for path, _, source, corrupted in reader.index.rows():
         source = source or ""
         if corrupted or source not in sources or not Path(path).exists():
             continue
-        # a packed shard goes to the device as it is when nothing but the rows' own columns is wanted
-        packed = _packed_rows(path, expected_planes) if ssl is None and augment is None else None
-        try:
-            got = reader._load(path) if packed is None else None
-        except Exception:
-            got = None
-        if packed is None and (got is None or got[1].shape[1] != POLICY_SIZE):          # the only policy layout the engine has
-            skipped.append(Path(path).name)
+        name = Path(path).name
+        got = _score_shard(backend, reader, path, batch, expected_planes, ssl, tasks, augment, opts)
+        if got is None:
+            skipped.append(name)
             continue
-        rows3 = None
-        if packed is not None:
-            from .rowpack import mask_mode_of
-            z, mode = packed.z, mask_mode_of(packed, opts.get("mask_mode"))
-            try:
-                rows = _score_packed(backend, packed, batch, **dict(opts, mask_mode=mode))
-            except NonFiniteScore:
-                raise
-            except ValueError:                                      # arrays that do not hold together: as an unreadable dense shard
-                skipped.append(Path(path).name)
-                continue
-        else:
-            s, pi, z, mask = got
-            mode = resolve_mask_mode(pi, mask, opts.get("mask_mode"))
-            if trainer:
-                rows3 = score_arrays(backend, s, pi, z, mask, batch=batch, augment="trainer", **dict(opts, mask_mode=mode))
-                rows = rows3[AUGMENT_KINDS["none"]]
-            elif ssl is None:
-                rows = score_arrays(backend, s, pi, z, mask, batch=batch, **dict(opts, mask_mode=mode),
-                                    **({} if augment is None else {"augment": augment}))
-            else:
-                have = {} if ssl == "planes" else _stored_ssl(path)
-                stored = ssl == "stored" or (ssl == "auto" and all("ssl_" + t in have for t in tasks))
-                try:
-                    targets = pack_ssl_targets(have, len(s), tasks) if stored else None
-                except KeyError as e:
-                    raise KeyError(f"{Path(path).name}: {e.args[0]} (ssl='stored')") from None
-                rows, ssl_rows = score_arrays(backend, s, pi, z, mask, batch=batch, ssl="stored" if stored else "planes",
-                                              ssl_targets=targets, **dict(opts, mask_mode=mode))
         one = Sums()
         for sums in (total, by_source.setdefault(source, Sums()), one):
-            sums.add(rows, z)
-        by_shard[Path(path).name] = dict(one.report(), source=source, mask_mode=mode)
+            sums.add(got.rows, got.z)
+        by_shard[name] = dict(one.report(), source=source, mask_mode=got.mode)
         if trainer:
             aug_one = AugmentSums()
             for sums in (aug_total, aug_one):
-                sums.add(rows3, z)
-            by_shard[Path(path).name]["augment"] = aug_one.report(weights)
+                sums.add(got.rows3, got.z)
+            by_shard[name]["augment"] = aug_one.report(weights)
         if ssl is not None:
             ssl_one = SslSums()
             for sums in (ssl_total, ssl_by_source.setdefault(source, SslSums()), ssl_one):
-                sums.add(ssl_rows, stored)
-            by_shard[Path(path).name]["ssl"] = dict(ssl_report(ssl_one, one.report()), targets="stored" if stored else "planes")
+                sums.add(got.ssl_rows, got.stored)
+            by_shard[name]["ssl"] = dict(ssl_report(ssl_one, one.report()), targets="stored" if got.stored else "planes")
         if per_sample:
-            keep["columns"].append(rows)
-            keep["shard_index"].append(np.full(len(rows), len(by_shard) - 1, np.int32))
-            keep["row"].append(np.arange(len(rows), dtype=np.int32))
-            if ssl is not None:
-                keep["ssl_columns"].append(ssl_rows)
-            if trainer:
-                for k, r3 in zip(AUGMENT_KINDS, rows3):
-                    keep["columns_" + k].append(r3)
-            elif augment is not None:
-                keep["columns_" + augment].append(rows)
+            kept.append(got)
     if per_sample:
-        cat = lambda key, dtype, shape: np.concatenate(keep[key]) if keep[key] else np.zeros(shape, dtype)
-        more = {} if ssl is None else {"ssl_columns": cat("ssl_columns", np.float32, (0, SSL_SCORE_COLS))}
-        for k in (AUGMENT_KINDS if trainer else () if augment is None else (augment,)):
-            more["columns_" + k] = cat("columns_" + k, np.float32, (0, SCORE_COLS))
-        with open(per_sample, "wb") as f:
-            np.savez(f, columns=cat("columns", np.float32, (0, SCORE_COLS)), shard_index=cat("shard_index", np.int32, (0,)),
-                     row=cat("row", np.int32, (0,)), shards=np.array(list(by_shard), dtype=str), **more)
+        _write_per_sample(per_sample, kept, by_shard, ssl, augment)
     report = dict(total.report(), by_source={k: v.report() for k, v in by_source.items()}, by_shard=by_shard, skipped=skipped)
     if trainer:
         report["augment"] = aug_total.report(weights)
@@ -448,34 +450,34 @@ def ssl_opts(cfg: dict, tasks: Sequence[str] = SSL_TASKS, ssl_weight=None, task_
             "ssl_target_weight": float(tr.get("ssl_target_weight", 1.0))}
 
 
+_f = lambda x: "    n/a" if x is None else f"{x:7.4f}"              # a figure of the summary lines
+
+
 def ssl_summary_line(name: str, r: dict) -> str:
-    f = lambda x: "    n/a" if x is None else f"{x:7.4f}"
     x = r["ssl"]
-    losses = "  ".join(f"{t} {f(v)}" for t, v in x["loss"].items())
-    return (f"{name}  ssl rows {x['rows']} scored {x['scored']}  {losses}  ssl_total {f(x['ssl_total'])}  "
-            f"total_with_ssl {f(x['total_with_ssl'])} (ssl_weight {x['ssl_weight']:g})  piece acc {f(x.get('piece_accuracy'))} "
-            f"occupied {f(x.get('piece_accuracy_occupied'))}  control acc {f(x.get('control_accuracy'))}  "
+    losses = "  ".join(f"{t} {_f(v)}" for t, v in x["loss"].items())
+    return (f"{name}  ssl rows {x['rows']} scored {x['scored']}  {losses}  ssl_total {_f(x['ssl_total'])}  "
+            f"total_with_ssl {_f(x['total_with_ssl'])} (ssl_weight {x['ssl_weight']:g})  piece acc {_f(x.get('piece_accuracy'))} "
+            f"occupied {_f(x.get('piece_accuracy_occupied'))}  control acc {_f(x.get('control_accuracy'))}  "
             f"flags {x['flags']['planes']}/{x['flags']['nonfinite']}/{x['flags']['mismatch']}")
 
 
 def augment_summary_line(name: str, r: dict) -> str:
-    f = lambda x: "    n/a" if x is None else f"{x:7.4f}"
     x = r["augment"]
     if x["mode"] != "trainer":
         return f"{name}  augment {x['mode']}: the figures above are those of the rows under it"
-    kinds = "  ".join(f"{k} policy {f(v['policy_loss'])} value {f(v['value_loss'])} total {f(v['total'])}" for k, v in x["by_kind"].items())
+    kinds = "  ".join(f"{k} policy {_f(v['policy_loss'])} value {_f(v['value_loss'])} total {_f(v['total'])}" for k, v in x["by_kind"].items())
     w, e, g = x["weights"], x["expected"], x["symmetry_gap"]
     return (f"{name}  augment trainer  {kinds}  expected ({w['hflip']:g} hflip + {w['rot180']:g} rot180 + {w['none']:g} none) "
-            f"policy {f(e['policy_loss'])} value {f(e['value_loss'])} total {f(e['total'])}  symmetry gap none/hflip over {g['rows']} rows: "
-            f"policy mean {f(g['policy_loss']['mean'])} max {f(g['policy_loss']['max'])}  value mean {f(g['value_loss']['mean'])} "
-            f"max {f(g['value_loss']['max'])}")
+            f"policy {_f(e['policy_loss'])} value {_f(e['value_loss'])} total {_f(e['total'])}  symmetry gap none/hflip over {g['rows']} rows: "
+            f"policy mean {_f(g['policy_loss']['mean'])} max {_f(g['policy_loss']['max'])}  value mean {_f(g['value_loss']['mean'])} "
+            f"max {_f(g['value_loss']['max'])}")
 
 
 def summary_line(name: str, r: dict) -> str:
-    f = lambda x: "    n/a" if x is None else f"{x:7.4f}"
-    return (f"{name}  rows {r['rows']} scored {r['scored']}  policy {f(r['policy_loss'])}  kl {f(r['kl'])}  value {f(r['value_loss'])}  "
-            f"total {f(r['total'])}  top1 {f(r['top1'])}  top3 {f(r['top3'])}  top5 {f(r['top5'])}  mass {f(r['support_mass'])}  "
-            f"sign {f(r['value_sign_agreement'])}  flags {r['flags']['empty']}/{r['flags']['nonfinite']}/{r['flags']['uniform']}")
+    return (f"{name}  rows {r['rows']} scored {r['scored']}  policy {_f(r['policy_loss'])}  kl {_f(r['kl'])}  value {_f(r['value_loss'])}  "
+            f"total {_f(r['total'])}  top1 {_f(r['top1'])}  top3 {_f(r['top3'])}  top5 {_f(r['top5'])}  mass {_f(r['support_mass'])}  "
+            f"sign {_f(r['value_sign_agreement'])}  flags {r['flags']['empty']}/{r['flags']['nonfinite']}/{r['flags']['uniform']}")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -513,8 +515,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     parser = build_parser()
     args = parser.parse_args(argv)
     if args.ssl and args.augment not in (None, "none"):
-        parser.error("--ssl cannot be combined with --augment other than none: the trainer leaves stored SSL targets untransformed, "
-                     "and targets taken from rotated planes are not positions the decoder accepts")
+        parser.error("--ssl cannot be combined with --augment other than none: " + _SSL_AUG)
     cfg = load_config(args.config)
     model_cfg = cfg.get("model", {}) or {}
     opts = training_opts(cfg, args.label_smoothing, args.value_loss, args.huber_delta)
