@@ -593,4 +593,6 @@ int m0_replay_games(int hip_device, const char* const* start_fens, const uint32_
 #include "m0_proof.h"
 /* packed training rows: bitboards and sparse policies, expanded on the device */
 #include "m0_rowpack.h"
+/* a resident store of packed rows: training batches gathered, expanded and augmented on the device in one launch */
+#include "m0_batch.h"
 #endif /* M0_ENGINE_H */

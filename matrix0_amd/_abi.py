@@ -320,16 +320,31 @@ ROWPACK_FUNCTIONS = {
     "m0_rowpack_bench": (i32, [i32, i32, i32, P(f32), P(f32), P(f64)]),
 }
 
+# ---- include/m0_batch.h (which m0_engine.h includes too): the resident store of packed rows and its batches, in that header's
+# order; tests/test_abi_batch.py compares the two ----
+ROWSTORE_HOST = -1
+ROWSTORE_INFO = ("rows", "first_row", "next_row", "segments", "raw_rows", "bytes")
+BATCH_FUNCTIONS = {
+    "m0_rowstore_create": (vp, [i32, i32]),
+    "m0_rowstore_destroy": (None, [vp]),
+    "m0_rowstore_append": (i32, [vp, P(RowpackArrays), P(i64)]),
+    "m0_rowstore_evict": (i32, [vp, i64]),
+    "m0_rowstore_info": (i32, [vp, vp]),
+    "m0_rowstore_batch": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, i32, vp]),
+    "m0_rowstore_batch_host": (i32, [P(RowpackArrays), vp, vp, i32, vp, vp, vp, vp]),
+    "m0_rowstore_bench": (i32, [i32, i32, i32, vp, vp, P(f64)]),
+}
+
 
 def bind(L) -> list:
     """Set restype and argtypes of every function of FUNCTIONS, LIVE_FUNCTIONS, SCORE_FUNCTIONS, SSL_SCORE_FUNCTIONS,
-    GUMBEL_FUNCTIONS, AUGMENT_FUNCTIONS, PROOF_FUNCTIONS and ROWPACK_FUNCTIONS on the loaded library; the names it does not
-    export."""
+    GUMBEL_FUNCTIONS, AUGMENT_FUNCTIONS, PROOF_FUNCTIONS, ROWPACK_FUNCTIONS and BATCH_FUNCTIONS on the loaded library; the
+    names it does not export."""
     missing = []
     for name, (restype, argtypes) in (list(FUNCTIONS.items()) + list(LIVE_FUNCTIONS.items()) + list(SCORE_FUNCTIONS.items()) +
                                       list(SSL_SCORE_FUNCTIONS.items()) + list(GUMBEL_FUNCTIONS.items()) +
                                       list(AUGMENT_FUNCTIONS.items()) + list(PROOF_FUNCTIONS.items()) +
-                                      list(ROWPACK_FUNCTIONS.items())):
+                                      list(ROWPACK_FUNCTIONS.items()) + list(BATCH_FUNCTIONS.items())):
         fn = getattr(L, name, None)
         if fn is None:
             missing.append(name)

@@ -1,0 +1,11 @@
+// Launcher of batch_kernels.hip: a training batch gathered from resident packed rows, expanded and augmented in one launch
+// (include/m0_batch.h).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "batch_core.h"
+
+// refs [B] in device memory, each naming a row of a resident device segment (the host has checked row < n and kind <= 2) ->
+// planes f32 [B][19][64], pi f32 [B][4672], z f32 [B], mask u8 [B][4672] (null: a store without masks), all device memory with
+// planes, pi and mask on 16-byte boundaries.  One wave per output row; every byte of planes, pi and mask is written once.
+hipError_t launch_batch_rows(const m0batch::RowRef* refs, int B, float* planes, float* pi, float* z, uint8_t* mask, hipStream_t st);

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>
+#include <vector>
 #include "../../include/m0_engine.h"
 #include "hip_check.h"
 
@@ -24,6 +25,9 @@ const char* m0_bad_kinds(const uint8_t* kinds, int B);
 // launched for arrays that fail the checks (capi_rowpack.hip).
 int m0_rowpack_unpack_to_device(HipStatus& hs, const m0_rowpack_arrays* in, float* planes_dev, float* pi_dev, uint8_t* mask_dev,
                                 hipStream_t st);
+// The seeded rows that m0_rowpack_bench and m0_rowstore_bench run on: planes f32 [N][19][64], pi f32 [N][4672], mask u8 [N][4672];
+// every row packs as a position with a LEGAL mask (capi_rowpack.hip).
+void m0_rowpack_bench_rows(size_t N, std::vector<float>& planes, std::vector<float>& pi, std::vector<uint8_t>& mask);
 
 // What every stateless device call does first: M0_OK with hip_device current, or M0_ERR_HIP and the error string set.
 inline int m0_select_device(HipStatus& hs, int hip_device, const char* hint = "no CPU fallback") {

@@ -53,6 +53,32 @@ int m0_rowpack_unpack_to_device(HipStatus& hs, const m0_rowpack_arrays* in, floa
     return M0_OK;
 }
 
+// The rows the *_bench calls of the packed rows run on (capi_common.h): N positions of seeded legal play from the start position,
+// soft pi on about two thirds of each one's legal moves, the legal moves as mask.
+void m0_rowpack_bench_rows(size_t N, std::vector<float>& planes, std::vector<float>& pi, std::vector<uint8_t>& mask) {
+    planes.assign(N * PLANE_FLOATS, 0.f);
+    pi.assign(N * COLS, 0.f);
+    mask.assign(N * COLS, 0);
+    BenchRng rng;
+    const char* start = "rnbqkbnr/pppppppp/8/8/8/8/PPPPPPPP/RNBQKBNR w KQkq - 0 1";
+    Pos p;
+    m0::parse_fen(start, p);
+    for (size_t i = 0; i < N; ++i) {
+        m0::Move mv[M0_MAX_MOVES];
+        int k = m0::gen_legal(p, mv);
+        if (k == 0 || p.halfmove > 90 || p.fullmove > 150) { m0::parse_fen(start, p); k = m0::gen_legal(p, mv); }
+        m0::encode_planes_f32(p, &planes[i * PLANE_FLOATS]);
+        float sum = 0.f;
+        for (int j = 0; j < k; ++j) {
+            const int idx = m0::move_to_index(p, mv[j]);
+            mask[i * COLS + idx] = 1;
+            if (rng.next() % 3 || j == 0) sum += pi[i * COLS + idx] = (float)(1 + rng.next() % 100);
+        }
+        for (int j = 0; j < k; ++j) pi[i * COLS + m0::move_to_index(p, mv[j])] /= sum;
+        m0::make_move(p, mv[rng.next() % k]);
+    }
+}
+
 extern "C" {
 
 int m0_rowpack_pack_host(const float* planes, const float* pi, const float* z, const uint8_t* legal_mask, int n,
@@ -165,26 +191,9 @@ int m0_rowpack_bench(int hip_device, int B, int iters, float* pack_us, float* un
     int rc = m0_select_device(hs, hip_device, "use the _host call");
     if (rc != M0_OK) return rc;
     const size_t N = (size_t)B;
-    std::vector<float> planes(N * PLANE_FLOATS), pi(N * COLS, 0.f), z(N, 0.f);
-    std::vector<uint8_t> mask(N * COLS, 0);
-    BenchRng rng;
-    const char* start = "rnbqkbnr/pppppppp/8/8/8/8/PPPPPPPP/RNBQKBNR w KQkq - 0 1";
-    Pos p;
-    m0::parse_fen(start, p);
-    for (size_t i = 0; i < N; ++i) {
-        m0::Move mv[M0_MAX_MOVES];
-        int k = m0::gen_legal(p, mv);
-        if (k == 0 || p.halfmove > 90 || p.fullmove > 150) { m0::parse_fen(start, p); k = m0::gen_legal(p, mv); }
-        m0::encode_planes_f32(p, &planes[i * PLANE_FLOATS]);
-        float sum = 0.f;
-        for (int j = 0; j < k; ++j) {
-            const int idx = m0::move_to_index(p, mv[j]);
-            mask[i * COLS + idx] = 1;
-            if (rng.next() % 3 || j == 0) sum += pi[i * COLS + idx] = (float)(1 + rng.next() % 100);
-        }
-        for (int j = 0; j < k; ++j) pi[i * COLS + m0::move_to_index(p, mv[j])] /= sum;
-        m0::make_move(p, mv[rng.next() % k]);
-    }
+    std::vector<float> planes, pi, z(N, 0.f);
+    std::vector<uint8_t> mask;
+    m0_rowpack_bench_rows(N, planes, pi, mask);
     // the packed form of these rows, once, for the offsets of the fill pass and as the input of unpacking
     int64_t sizes[3];
     m0_rowpack_arrays a = {};
