@@ -12,6 +12,9 @@ stream next, to the block's pre-activated input act(GroupNorm(stream; bn1)) -- t
   compare                   the per-tensor metric and the bound MARGIN x (model error) that tests/test_net_layers_gpu.py applies
                             to the GPU's steps, and tests/test_net_layers.py to mutated float64 steps (a test of the test)
 
+  trained_like / regime_stats   the "trained" weight regime (sizes, signs and offsets of a checkpoint) and the conditions it meets
+                            on the float64 chain (tests/test_net_regimes.py, tests/test_net_regimes_gpu.py); sharpen: the "sharp" one
+
 Which kernel form a step takes (fused epilogue or conv + ew_board) decides where it rounds: kernel_plan restates the choices of
 Net::make_plan (net_pack.hip) and Net::conv_norm_act (net.hip)."""
 from __future__ import annotations
@@ -32,8 +35,13 @@ def sd64(sd) -> Dict[str, torch.Tensor]:
     return {k: torch.as_tensor(v).double() for k, v in sd.items()}
 
 
+_PEAKS: Optional[List[float]] = None          # regime_stats: the largest magnitude at every rounding point, before it rounds
+
+
 def _h(t: torch.Tensor) -> torch.Tensor:
     """Round to nearest fp16 (a kernel's fp16 store or MFMA operand)."""
+    if _PEAKS is not None:
+        _PEAKS.append(float(t.abs().max()) if bool(torch.isfinite(t).all()) else math.inf)
     return t.to(torch.float16).to(torch.float64)
 
 
@@ -346,6 +354,195 @@ def attention_stats(sd, cfg, step: int, x: torch.Tensor) -> dict:
         s = s + sd[p + ".rel_bias"]
     pr = F.softmax(torch.clamp(s, -50.0, 50.0), dim=-1)
     return {"std": float(s.std()), "clamped": float((s.abs() > 50.0).double().mean()), "maxprob": float(pr.max(-1).values.mean())}
+
+
+def _attn_parts(sd, cfg, p, x):
+    """q, k, v [B,H,64,D], the scores before the clamp and the mixed heads before proj [B,C,8,8] of attention layer p, float64."""
+    B, C = x.shape[:2]
+    heads = int(cfg["attention_heads"])
+    D = C // heads
+    qkv = F.conv2d(x.double(), sd[p + ".qkv.weight"]).reshape(B, 3, heads, D, 64).permute(1, 0, 2, 4, 3)
+    q, k, v = qkv[0], qkv[1], qkv[2]
+    s = torch.matmul(q, k.transpose(-2, -1)) / math.sqrt(D)
+    if cfg["attention_relbias"]:
+        s = s + sd[p + ".rel_bias"]
+    c = torch.clamp(s, -50.0, 50.0)
+    mix = float(cfg["attention_unmasked_mix"])
+    pm = F.softmax(c.masked_fill(~net_ref.attention_mask()[None, None], -1e4), dim=-1)
+    pu = F.softmax(c, dim=-1)
+    pr = (1.0 - mix) * pm + mix * pu if 0.0 < mix < 1.0 else (pm if mix >= 1.0 else pu)
+    o = torch.matmul(pr, v).transpose(1, 2).reshape(B, 64, C).transpose(1, 2).reshape(B, C, 8, 8)
+    return q, k, v, s, o
+
+
+def _res_parts(sd, cfg, p, x):
+    """Of residual block p (preact) on the stream x, float64: bn2's output before the activation, and the squeeze-excite hidden
+    units after theirs (None without squeeze-excite)."""
+    a = net_ref._act(net_ref._norm(x.double(), sd, p + ".bn1", cfg), cfg)
+    pre = net_ref._norm(F.conv2d(a, sd[p + ".conv1.weight"], padding=1), sd, p + ".bn2", cfg)
+    if not cfg["se"]:
+        return pre, None
+    w = F.conv2d(net_ref._act(pre, cfg), sd[p + ".conv2.weight"], padding=1).mean(dim=(2, 3))
+    return pre, net_ref._act(F.linear(w, sd[p + ".se_fc1.weight"], sd[p + ".se_fc1.bias"]), cfg)
+
+
+def _rms(t):
+    return float(t.double().pow(2).mean().sqrt())
+
+
+@torch.no_grad()
+def trained_like(sd, cfg, seed: int = 0, planes: Optional[torch.Tensor] = None) -> dict:
+    """The "trained" regime: a random_state_dict of any supported width (group norm) given the sizes, signs and offsets of a
+    trained checkpoint, everything at once, so that every place where a kernel could be wrong only off O(1) is exercised:
+
+      GroupNorm gains    lognormal, median 2; one in ten negative; per layer one channel at +64 and one at -64 (a normalised value
+                         stays within sqrt(1023) ~ 32 of zero, so the activation meets inputs beyond +-88.8, where fp32 exp
+                         overflows); biases uniform in +-1.5
+      position_encoding  x30 plus a level per 16-channel group: groups whose mean is many times their standard deviation
+      residual blocks    conv2.weight x6; se_fc2.weight scaled to gate logits of rms 3 around biases uniform in +-3: a good part
+                         of the gates saturated, the rest anywhere in between
+      attention          norm.weight x12, one in ten negative; norm.bias a per-channel offset plus a per-group level; rel_bias x6;
+                         the q and k rows of qkv.weight scaled to rms 3.5, the v rows to rms 4 and proj.weight so that the
+                         attention branch has twice the rms of the stream it joins -- peaked softmaxes with |q|, |k|, |v| <= 64,
+                         and an attention branch that the stream and the LayerNorm do not drown
+      heads              value_gate x4; value_fc3 and its bias such that on `planes` one board's value is tanh(0.2) and the
+                         farthest board's pre-activation is 0.2 +- 3 (|value| > 0.99); the policy logit scale at its 5.0 clamp
+
+    The attention and value scales are set on the float64 chain over `planes` (default random_planes(6, seed)) as it is built,
+    step by step, so the function is deterministic in (sd, cfg, seed, planes) and needs nothing but torch.  regime_stats reports
+    the conditions the result meets."""
+    full = net_ref.full_cfg(cfg)
+    assert full["norm"] == "group"
+    g = torch.Generator().manual_seed(7919 + seed)
+    out = {k: torch.as_tensor(v).clone().float() for k, v in sd.items()}
+    planes = random_planes(6, seed) if planes is None else planes
+
+    def randn(*s):
+        return torch.randn(*s, generator=g)
+
+    def rand(*s):
+        return torch.rand(*s, generator=g)
+
+    def levels(n, scale):                                      # one level per 16-channel group: +-scale x [0.5, 1.5)
+        m = max(1, n // 16)
+        return (scale * torch.sign(randn(m)) * (0.5 + rand(m))).repeat_interleave(16)[:n]
+
+    att_norms = {f"tower.{i}.norm" for kind, i in net_ref.tower_layout(full) if kind == "att"}
+    for key in sorted(k for k in sd if k.endswith(".weight") and out[k].dim() == 1):
+        prefix, n = key[:-len(".weight")], out[key].numel()
+        if prefix in att_norms:
+            w = 12.0 * out[key]
+            out[key] = torch.where(rand(n) < 0.1, -w, w)
+            out[prefix + ".bias"] = 4.0 * randn(n) + levels(n, 40.0)
+            continue
+        w = 2.0 * torch.exp(0.5 * randn(n))
+        w = torch.where(rand(n) < 0.1, -w, w)
+        i, j = torch.randperm(n, generator=g)[:2].tolist()
+        w[i], w[j] = 64.0, -64.0
+        out[key] = w
+        out[prefix + ".bias"] = 3.0 * rand(n) - 1.5
+    if full["chess_features"]:
+        pe = out["chess_features.position_encoding"]
+        out["chess_features.position_encoding"] = 30.0 * pe + levels(pe.shape[1], 25.0)[None, :, None, None]
+    out["_policy_logit_scale_raw"] = torch.tensor(10.0)         # softplus(10) + 1e-3 > 5: the clamp binds
+    out["value_gate.0.weight"] = 4.0 * out["value_gate.0.weight"]
+    C = int(full["channels"])
+    x = planes.double()
+    for s, st in enumerate(schedule(full)):
+        p = st["prefix"]
+        if st["kind"] == "res":
+            out[p + ".conv2.weight"] = 6.0 * out[p + ".conv2.weight"]
+            if full["se"]:
+                out[p + ".se_fc2.bias"] = 6.0 * rand(C) - 3.0
+                if st["run"]:
+                    hid = _res_parts(sd64(out), full, p, x)[1]
+                    out[p + ".se_fc2.weight"] *= 3.0 / _rms(F.linear(hid, out[p + ".se_fc2.weight"].double()))
+        elif st["kind"] == "att":
+            if full["attention_relbias"]:
+                out[p + ".rel_bias"] = 6.0 * out[p + ".rel_bias"]
+            if st["run"]:
+                q, k, v, _, _ = _attn_parts(sd64(out), full, p, x)
+                w = out[p + ".qkv.weight"]
+                w[:C] *= 3.5 / _rms(q)
+                w[C:2 * C] *= 3.5 / _rms(k)
+                w[2 * C:] *= 4.0 / _rms(v)
+                o = _attn_parts(sd64(out), full, p, x)[4]
+                out[p + ".proj.weight"] *= 2.0 * _rms(x) / _rms(F.conv2d(o, out[p + ".proj.weight"].double()))
+        if st["run"]:
+            x = step64(sd64(out), full, s, x)[0]
+    # the value head: z = value_fc3.weight . (gated features) per board, then an affine map of z
+    # (read through heads64 with the weight shrunk until tanh is the identity to float64)
+    probe = sd64(out)
+    probe["value_fc3.weight"], probe["value_fc3.bias"] = probe["value_fc3.weight"] * 1e-9, torch.zeros(1, dtype=torch.float64)
+    z = heads64(probe, full, x)[1] * 1e9
+    j = int(torch.argsort(z)[len(z) // 2])
+    scale = 3.0 / float((z - z[j]).abs().max())
+    out["value_fc3.weight"] = out["value_fc3.weight"] * scale
+    out["value_fc3.bias"] = torch.tensor([0.2 - scale * float(z[j])])
+    return out
+
+
+@torch.no_grad()
+def regime_stats(sd, cfg, planes: torch.Tensor, chain=None) -> dict:
+    """What a weight regime does to the float64 chain over `planes` (sd from sd64), and how far the storage model stays from the
+    fp16 range on those inputs:
+
+      stream_max, first_block_in   max |stream| over all steps; at the input of the first residual block
+      group_mean_over_std          largest |mean| / std of a (board, 16-channel group) of a stream that feeds a second output
+      bn2_pre, second_pre          over residual blocks (over second outputs) the largest m such that one block's bn2 output (one
+                                   second output's GroupNorm output) has a value <= -m and a value >= m
+      se_outside                   largest fraction, over blocks, of squeeze-excite gates outside [0.02, 0.98]
+      attention                    attention_stats of every attention step that runs;  qkv_max: max |q|, |k|, |v| over them
+      neg_gains                    fraction of negative norm gains
+      values, logit_scale          the value per board; the policy logit scale after its clamp
+      finite, peak                 every tensor of step_model (both kernel plans) and heads_model is finite; the largest
+                                   magnitude at any of their fp16 rounding points, before it rounds"""
+    global _PEAKS
+    full = net_ref.full_cfg(cfg)
+    chain = chain if chain is not None else chain64(sd, full, planes)
+    sched = schedule(full)
+    out = dict(stream_max=max(float(y.abs().max()) for _, y, _ in chain), group_mean_over_std=0.0, bn2_pre=0.0, second_pre=0.0,
+               se_outside=0.0, attention=[], qkv_max=0.0)
+    first_res = [s for s, st in enumerate(sched) if st["kind"] == "res"][0]
+    out["first_block_in"] = float(chain[first_res][0].abs().max())
+
+    def both_sides(t):
+        return min(float(t.max()), -float(t.min()))
+
+    for s, st in enumerate(sched):
+        if not st["run"]:
+            continue
+        x, y, _ = chain[s]
+        if st["next_bn1"] is not None:
+            grp = y.reshape(y.shape[0], y.shape[1] // 16, -1)
+            out["group_mean_over_std"] = max(out["group_mean_over_std"], float((grp.mean(-1).abs() / grp.std(-1, unbiased=False)).max()))
+            out["second_pre"] = max(out["second_pre"], both_sides(net_ref._norm(y, sd, st["next_bn1"] + ".bn1", full)))
+        p = st["prefix"]
+        if st["kind"] == "res":
+            pre, hid = _res_parts(sd, full, p, x)
+            out["bn2_pre"] = max(out["bn2_pre"], both_sides(pre))
+            if full["se"]:
+                gate = torch.sigmoid(F.linear(hid, sd[p + ".se_fc2.weight"], sd[p + ".se_fc2.bias"]))
+                out["se_outside"] = max(out["se_outside"], float(((gate < 0.02) | (gate > 0.98)).double().mean()))
+        elif st["kind"] == "att":
+            out["attention"].append(attention_stats(sd, full, s, x))
+            out["qkv_max"] = max(out["qkv_max"], *(float(t.abs().max()) for t in _attn_parts(sd, full, p, x)[:3]))
+    gains = torch.cat([v.flatten() for k, v in sd.items() if k.endswith(".weight") and v.dim() == 1])
+    out["neg_gains"] = float((gains < 0).double().mean())
+    out["values"] = heads64(sd, full, chain[-1][1])[1].tolist()
+    out["logit_scale"] = float(torch.clamp(F.softplus(sd["_policy_logit_scale_raw"]) + 1e-3, max=5.0))
+    _PEAKS, finite = [], True
+    try:
+        for plan in (kernel_plan(full), kernel_plan(full, fuse_tail=False, fuse_attn=False)):
+            for s in range(len(sched)):
+                finite &= all(bool(torch.isfinite(t).all()) for t in step_model(sd, full, s, _h(chain[s][0]), plan) if t is not None)
+            pm, vm, sslm = heads_model(sd, full, _h(chain[-1][1]), plan)
+            finite &= all(bool(torch.isfinite(t).all()) for t in (pm, vm, *(sslm or {}).values()))
+        out["peak"] = max(_PEAKS)
+    finally:
+        _PEAKS = None
+    out["finite"] = finite and math.isfinite(out["peak"])
+    return out
 
 
 @torch.no_grad()

@@ -64,8 +64,11 @@ def wide_planes(b=WIDE_B):
     return nl.random_planes(b, PLANES_SEED)
 
 
-def weights(cfg, seed=0, sharp=False):
+def weights(cfg, seed=0, sharp=False, trained=False, on=None):
+    """trained: the regime of nl.trained_like, its attention and value scales set on the boards `on` (default planes())."""
     sd = net_ref.random_state_dict(cfg, seed)
+    if trained:
+        return nl.trained_like(sd, cfg, seed, planes() if on is None else on)
     return nl.sharpen(sd, cfg) if sharp else sd
 
 
@@ -141,3 +144,50 @@ def width_mutations(C, cfg):
 
 WIDTH_MUTATIONS = [(C, cfg, *m) for C, cfg in WIDTHS for m in width_mutations(C, cfg)]
 WIDTH_MUTATION_IDS = [f"{m[0]}:{m[2]}" for m in WIDTH_MUTATIONS]
+
+
+# ---- the "trained" regime (nl.trained_like): its networks and its mutations of 320 x 6 ----------------------------------------
+# 320 x 6 and every WIDTHS row have the same first five tower layers (res, res, res, att, res), so W_RES and W_ATT and the
+# steps of width_mutations hold for 320 x 6 too.
+REGIME_WIDTHS = (96, 192, 352)
+
+
+def regime_networks():
+    """name -> (cfg, boards): the networks tests/test_net_regimes_gpu.py runs, each with the boards its scales are set on."""
+    nets = {"320x6": (r24_cfg(blocks=6), planes()),
+            "288in320": (r24_cfg(channels=288, attention_heads=18, blocks=6, infer_attention_stride=2), planes())}
+    for C in REGIME_WIDTHS:
+        nets[f"width_{C}"] = (dict(WIDTHS)[C], wide_planes())
+    return nets
+
+
+def regime_weights(name):
+    cfg, x = regime_networks()[name]
+    return weights(cfg, trained=True, on=x)
+
+
+def _flip_negative_gain(sd):
+    """The first negative bn2 gain that is not the -64 one changes its sign."""
+    w = sd[W_RES + ".bn2.weight"]
+    i = int(((w < 0) & (w > -64)).nonzero()[0])
+    w[i] = -w[i]
+
+
+def _halve_largest_gain(sd):
+    w = sd[W_RES + ".bn2.weight"]
+    i = int(w.argmax())
+    assert float(w[i]) == 64.0
+    w[i] = 32.0
+
+
+def regime_mutations(cfg):
+    """[(name, step, mutate)] on 320 x 6 in the trained regime: the three of width_mutations, the remaining kinds of MUTATIONS at
+    the same two layers, and two that mean something in this regime alone."""
+    return width_mutations(320, cfg) + [
+        ("rel_bias row of query square 63 dropped", 6, _mut(_zero(W_ATT + ".rel_bias", (0, slice(None), 63)))),
+        ("one LayerNorm beta dropped", 6, _mut(_zero(W_ATT + ".norm.bias", 0))),
+        ("corner tap of conv2 zeroed on 16 channels", 4, _mut(_zero(W_RES + ".conv2.weight", (slice(0, 16), slice(None), 0, 0)))),
+        ("next block's bn1 gamma/beta of channels 3 and 4 swapped", 4, _mut(lambda sd: _swap_norm(sd, "tower.2.bn1"))),
+        ("sign of one negative bn2 gain flipped", 4, _mut(_flip_negative_gain)),
+        ("the +64 bn2 gain replaced by +32", 4, _mut(_halve_largest_gain)),
+    ]
