@@ -595,4 +595,6 @@ int m0_replay_games(int hip_device, const char* const* start_fens, const uint32_
 #include "m0_rowpack.h"
 /* a resident store of packed rows: training batches gathered, expanded and augmented on the device in one launch */
 #include "m0_batch.h"
+/* self-play budget mix: full and fast searches, forced playouts and policy-target pruning (opt-in) */
+#include "m0_budget.h"
 #endif /* M0_ENGINE_H */

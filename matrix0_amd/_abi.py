@@ -142,6 +142,10 @@ class GumbelCfg(C.Structure):
     _fields_ = [("max_considered", i32), ("c_visit", f64), ("c_scale", f64)]
 
 
+class BudgetCfg(C.Structure):
+    _fields_ = [("full_prob", f64), ("fast_simulations", i32), ("forced_k", f64), ("prune_targets", i32)]
+
+
 STRUCTS = {"m0_net_cfg": NetCfg, "m0_selfplay_cfg": SelfplayCfg, "m0_selfplay_stats": SelfplayStats,
            "m0_game_record": GameRecord, "m0_analysis_opts": AnalysisOpts, "m0_analysis_line": AnalysisLine,
            "m0_analysis_result": AnalysisResult}
@@ -335,16 +339,30 @@ BATCH_FUNCTIONS = {
     "m0_rowstore_bench": (i32, [i32, i32, i32, vp, vp, P(f64)]),
 }
 
+# ---- include/m0_budget.h (which m0_engine.h includes too): the self-play budget mix, in that header's order;
+# tests/test_abi_budget.py compares the two ----
+BUDGET_STRUCTS = {"m0_budget_cfg": BudgetCfg}
+BUDGET_FUNCTIONS = {
+    "m0_selfplay_set_budget": (i32, [vp, P(BudgetCfg)]),
+    "m0_search_budget_result": (i32, [vp, i32, vp, vp, _pi32]),
+    "m0_game_record_budget": (i32, [P(GameRecord), P(P(u8)), P(P(i32))]),
+    "m0_selfplay_budget_stats": (i32, [vp, vp]),
+    "m0_budget_is_full": (i32, [u64, i32, i32, f64, _pi32]),
+    "m0_budget_forced": (i32, [f64, f64, i64, P(f64)]),
+    "m0_budget_prune": (i32, [i32, vp, vp, vp, i32, f64, f64, vp, vp, _pi32]),
+}
+
 
 def bind(L) -> list:
     """Set restype and argtypes of every function of FUNCTIONS, LIVE_FUNCTIONS, SCORE_FUNCTIONS, SSL_SCORE_FUNCTIONS,
-    GUMBEL_FUNCTIONS, AUGMENT_FUNCTIONS, PROOF_FUNCTIONS, ROWPACK_FUNCTIONS and BATCH_FUNCTIONS on the loaded library; the
-    names it does not export."""
+    GUMBEL_FUNCTIONS, AUGMENT_FUNCTIONS, PROOF_FUNCTIONS, ROWPACK_FUNCTIONS, BATCH_FUNCTIONS and BUDGET_FUNCTIONS on the loaded
+    library; the names it does not export."""
     missing = []
     for name, (restype, argtypes) in (list(FUNCTIONS.items()) + list(LIVE_FUNCTIONS.items()) + list(SCORE_FUNCTIONS.items()) +
                                       list(SSL_SCORE_FUNCTIONS.items()) + list(GUMBEL_FUNCTIONS.items()) +
                                       list(AUGMENT_FUNCTIONS.items()) + list(PROOF_FUNCTIONS.items()) +
-                                      list(ROWPACK_FUNCTIONS.items()) + list(BATCH_FUNCTIONS.items())):
+                                      list(ROWPACK_FUNCTIONS.items()) + list(BATCH_FUNCTIONS.items()) +
+                                      list(BUDGET_FUNCTIONS.items())):
         fn = getattr(L, name, None)
         if fn is None:
             missing.append(name)

@@ -21,6 +21,7 @@ int m0_selfplay_set_gumbel(m0_selfplay* sp, const m0_gumbel_cfg* cfg) {
     if (const char* bad = gumbel_bad_constants(cfg)) { m0_set_error(bad); return M0_ERR_INVALID; }
     if (sp->cfg.tt_merge) { m0_set_error("the Gumbel root search does not go with compat.tt_merge"); return M0_ERR_INVALID; }
     if (sp->tc.proof) { m0_set_error("the Gumbel root search does not go with the proof search"); return M0_ERR_INVALID; }
+    if (sp->tc.budget) { m0_set_error("the Gumbel root search does not go with the self-play budget mix"); return M0_ERR_INVALID; }
     if (!sp->d.gumbel_gl) {
         double* gl = dalloc<double>(sp, (size_t)sp->G * M0_MAX_CHILDREN);
         GumbelResult* res = dalloc<GumbelResult>(sp, sp->G);

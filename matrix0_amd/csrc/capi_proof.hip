@@ -21,6 +21,7 @@ int m0_selfplay_set_proof(m0_selfplay* sp, int on) {
     }
     if (sp->cfg.tt_merge) { m0_set_error("the proof search does not go with compat.tt_merge"); return M0_ERR_INVALID; }
     if (sp->tc.gumbel) { m0_set_error("the proof search does not go with the Gumbel root search"); return M0_ERR_INVALID; }
+    if (sp->tc.budget) { m0_set_error("the proof search does not go with the self-play budget mix"); return M0_ERR_INVALID; }
     if (on && !sp->d.t.proof) {
         int16_t* proof = dalloc<int16_t>(sp, (size_t)sp->G * 2 * sp->cap);       // zeroed: nothing is proven
         ProofResult* res = dalloc<ProofResult>(sp, sp->G);

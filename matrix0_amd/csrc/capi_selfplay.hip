@@ -21,6 +21,8 @@ static void fill_tree_cfg(const m0_selfplay_cfg& c, bool match, TreeCfg& t) {
     t.gumbel = 0;                          // m0_selfplay_set_gumbel turns it on
     t.gumbel_cfg = m0_gumbel_cfg{0, 0.0, 0.0};
     t.proof = 0;                           // m0_selfplay_set_proof turns it on
+    t.budget = 0;                          // m0_selfplay_set_budget turns it on
+    t.forced_k = 0.0;
     // the cached payload is the LEGAL logits: only the legal-softmax expansion can be served from it
     t.eval_cache = ((match ? c.arena_eval_cache : c.eval_cache) && c.legal_softmax && !c.raw_legal_priors && !c.tt_merge) ? 1 : 0;
 }

@@ -56,6 +56,8 @@ static void arm_search(m0_selfplay* sp, int slot, const Pos& pos, const RepWindo
     g.active = 1; g.sims_done = 0; g.sims_target = sims;
     g.need_dirichlet = dirichlet && !sp->tc.gumbel ? 1 : 0;     // the Gumbel root takes no Dirichlet noise
     g.gumbel_drawn = 0;
+    // budget mix: forced playouts at the root of a full search (every split-step search of such an engine is a full one)
+    g.forced = sp->tc.budget && sp->budget.forced_k > 0.0 && sp->games[slot].cur_full ? 1 : 0;
     g.root_q_from_v = 0;
     g.root_fresh = fresh ? 1 : 0;
     g.flip_root_v = (sp->cfg.value_from_white && pos.turn == BLACK) ? 1 : 0;
@@ -105,6 +107,7 @@ static void finish_game(m0_selfplay* sp, int slot, bool resigned, int resigner, 
         o->z.resize(hgm.nstates);
         for (int i = 0; i < hgm.nstates; ++i) o->z[i] = z * (float)hgm.turns[i];
         o->played.assign(hgm.history.begin(), hgm.history.end());
+        if (sp->tc.budget) { o->budget = true; o->full = hgm.full; o->sims.assign(hgm.sims_used.begin(), hgm.sims_used.end()); }
         if (hgm.book_index >= 0) o->start_fen = sp->book_fens[hgm.book_index];
         if (c.ssl_targets && (int)hgm.rec_pos.size() == hgm.nstates) {
             // targets for all plies of the game in one launch on the engine stream
@@ -161,13 +164,17 @@ static void begin_move(m0_selfplay* sp, int slot, int child_slot) {
     }
     // mcts.py:378-387 draws random.randint only when the cap is configured
     const bool cap_draws = c.playout_random_frac > 0.0 && c.num_simulations > 0;
-    int sims = playout_cap(c.num_simulations, c.playout_random_frac, cap_draws ? hgm.rng.next() : 0.0);
+    // budget mix (include/m0_budget.h): the ply's draw of the game's budget stream decides between a full and a fast search
+    hgm.cur_full = !sp->tc.budget || budget_is_full(c.seed, hgm.game_index, hgm.nstates, sp->budget.full_prob);
+    if (sp->tc.budget) ++(hgm.cur_full ? sp->budget_full : sp->budget_fast);
+    const int budget = hgm.cur_full ? c.num_simulations : sp->budget.fast_simulations;
+    int sims = playout_cap(budget, c.playout_random_frac, cap_draws ? hgm.rng.next() : 0.0);
     hgm.cur_sims = sims;
     if (c.fresh_tree_per_move || c.tt_merge) root = ROOT_FRESH;   // tt_merge: the table lives for one search (see m0_engine.h)
     if (sp->tc.gumbel) root = ROOT_FRESH;                          // the halving schedule assumes unvisited root children
     // ... except in a match engine, where each side's table lives for the whole game
     if (match && c.tt_merge) root = hgm.nstates == 0 ? ROOT_FIRST_OF_GAME : ROOT_FROM_SIDE_TABLE;
-    const bool dir = c.dirichlet_plies < 0 || hgm.nstates < c.dirichlet_plies;
+    const bool dir = (c.dirichlet_plies < 0 || hgm.nstates < c.dirichlet_plies) && hgm.cur_full;   // a fast search takes no noise
     begin_search(sp, slot, sims, dir, root);
 }
 
@@ -219,15 +226,27 @@ static void finish_search(m0_selfplay* sp, int slot) {
         sp->stats.arena_overflows++;   // in stats.arena_overflows, which the worker logs
         hgm.nstates = 0;               // no rows -> finish_game emits no training record
         hgm.states.clear(); hgm.pis.clear(); hgm.masks.clear(); hgm.search_values.clear(); hgm.turns.clear();
-        hgm.sims_used.clear(); hgm.rec_pos.clear();
+        hgm.sims_used.clear(); hgm.full.clear(); hgm.rec_pos.clear();
         finish_game(sp, slot, false, 0, true, 0.f);
         return;
     }
     const double root_q = R.root_n > 0 ? R.root_q : g.root_v;
     // Gumbel root search: the target is the improved policy and the move is the search's own pick (include/m0_gumbel.h)
     const GumbelResult* GR = sp->tc.gumbel ? &sp->hgres[slot] : nullptr;
+    // budget mix, a full search with forced playouts and target pruning: the visits that only the forcing brought are taken out
+    // of the target again, and the move is sampled from what is left (include/m0_budget.h)
+    const bool pruned = sp->tc.budget && hgm.cur_full && sp->budget.prune_targets && sp->budget.forced_k > 0.0;
+    std::vector<int32_t> visits(R.child_n, R.child_n + k);
+    std::vector<double> pruned_pi;
+    if (pruned) {
+        pruned_pi.resize(k);
+        sp->budget_pruned += (uint64_t)budget_prune(k, R.child_prior, R.child_q, R.child_n, R.root_n, cpuct_at_root(sp->tc),
+                                                    sp->budget.forced_k, visits.data(), pruned_pi.data(), nullptr);
+    }
     // a child's share of the policy target as recorded (mcts.py:828-837: visits over their sum)
-    auto target = [&](int i) { return GR ? (float)GR->pi[i] : (float)((double)R.child_n[i] / (double)total); };
+    auto target = [&](int i) {
+        return GR ? (float)GR->pi[i] : pruned ? (float)pruned_pi[i] : (float)((double)R.child_n[i] / (double)total);
+    };
     const size_t T = (size_t)hgm.nstates;
     if (c.record_games) {
         hgm.pis.resize((T + 1) * 4672, 0.f);
@@ -262,7 +281,6 @@ static void finish_search(m0_selfplay* sp, int slot) {
     // temperature + move choice (internal.py:386-394, 418-427, 690-735)
     double temp = temperature_for(hgm.pos.fullmove, c.temperature_start, c.temperature_end, c.temperature_moves);
     if (c.low_visit_threshold > 0 && maxv < c.low_visit_threshold && temp < 0.8) temp = 0.8;
-    std::vector<int32_t> visits(R.child_n, R.child_n + k);
     int pick;
     // proof search (include/m0_proof.h): a match engine plays the search's own move -- the shortest proven win, the longest
     // defence, never a move that is proven lost while another is not; with nothing proven it is the most visited move
@@ -281,6 +299,7 @@ static void finish_search(m0_selfplay* sp, int slot) {
     hgm.search_values.push_back((float)root_q);
     hgm.turns.push_back(hgm.pos.turn == WHITE ? 1 : -1);
     hgm.sims_used.push_back(hgm.cur_sims);
+    hgm.full.push_back(hgm.cur_full ? 1 : 0);
     hgm.nstates++;
     sp->stats.plies++;
     // resign (internal.py:507-536)

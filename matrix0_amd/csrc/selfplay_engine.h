@@ -27,6 +27,10 @@ struct GameRecordOwner {
     std::vector<uint8_t> legal_mask;
     std::vector<uint16_t> played;
     std::string start_fen;
+    // self-play budget mix (m0_game_record_budget): per recorded ply; `budget` false = a record of an engine without the mode
+    bool budget = false;
+    std::vector<uint8_t> full;
+    std::vector<int32_t> sims;
 };
 
 struct HostGame : Line {                  // pos, win, history (all moves incl. opening plies)
@@ -45,6 +49,8 @@ struct HostGame : Line {                  // pos, win, history (all moves incl. 
     HStream rng;                          // PURPOSE_GAME stream: opening plies, playout cap, move sampling
     double t0 = 0.0;
     int cur_sims = 0;
+    bool cur_full = true;                 // self-play budget mix: the running search is a full one
+    std::vector<uint8_t> full;            // ... and cur_full of every recorded ply, beside sims_used
     bool a_is_white = true;               // arena
     int book_index = -1;                  // the opening-book position the game started from, -1 = the initial position
 };
@@ -165,6 +171,9 @@ struct m0_selfplay {
     bool search_begun = false;            // m0_search_begin was called: the mode can no longer be set
     // proof search (m0_selfplay_set_proof; the switch itself is tc.proof)
     std::vector<ProofResult> hpres;       // host copies of d.proof_results, beside hres
+    // self-play budget mix (m0_selfplay_set_budget; the switch itself is tc.budget)
+    m0_budget_cfg budget = {1.0, 1, 0.0, 0};
+    uint64_t budget_full = 0, budget_fast = 0, budget_pruned = 0;   // searches of either kind, visits pruned from targets
 };
 
 namespace m0 {
@@ -194,7 +203,9 @@ inline bool hip_ok(m0_selfplay* sp, const char* context) {
 //   call                                                            accepted by
 //   m0_selfplay_step, _poll, _set_openings                          self-play, match
 //   m0_selfplay_ext_select, _ext_expand, m0_selfplay_set_tablebase,
-//   m0_selfplay_set_gumbel, m0_search_gumbel_result                 self-play
+//   m0_selfplay_set_gumbel, m0_search_gumbel_result,
+//   m0_selfplay_set_budget, m0_search_budget_result,
+//   m0_selfplay_budget_stats                                        self-play
 //   m0_arena_ext_select, _ext_expand                                match
 //   m0_search_*                                                     self-play, match (a match engine is accepted as it always
 //                                                                   was, although nothing drives one this way)

@@ -11,11 +11,13 @@ namespace m0 { struct TbSet; }   // tb_core.h
 #include "../../include/m0_engine.h"
 #include "gumbel_core.h"
 #include "proof_core.h"
+#include "budget_core.h"
 
 #define M0_MAX_DEPTH 256      // path length cap (nodes)
 #define M0_HIST_CAP 192       // reversible-move history window (<= 150 by the 75-move rule)
 #define M0_MAX_CHILDREN 256
 static_assert(M0_MAX_CHILDREN == m0::M0_GUMBEL_MAX_K, "gumbel_core.h and include/m0_gumbel.h count on 256 root children at most");
+static_assert(M0_MAX_CHILDREN == m0::M0_BUDGET_MAX_K, "budget_core.h and include/m0_budget.h count on 256 root children at most");
 constexpr int M0_NHWC_C = 32;          // channel stride of the fp16 NHWC network input (M0_PLANES used, the rest zero)
 
 struct TreeCfg {              // MCTSConfig fields the kernels read (mcts.py:61-107)
@@ -48,7 +50,17 @@ struct TreeCfg {              // MCTSConfig fields the kernels read (mcts.py:61-
     // proof search (m0_selfplay_set_proof, include/m0_proof.h): read by launch_select, which then runs the proof instantiation
     // of select_kernel, and by expand_kernel when it decides whether a search has finished
     int proof;                // 1: proven wins, losses and draws are backed up the tree (tree_proof.h)
+    // self-play budget mix (m0_selfplay_set_budget, include/m0_budget.h): read by launch_select, which then runs the forced
+    // instantiation of select_kernel, and by that instantiation at the root of a search with GameDev::forced
+    int budget;               // 1: the engine has the mode
+    double forced_k;          // forced playouts bring a visited root child up to sqrt(forced_k * prior * sum n) visits
 };
+
+// select_kernel's cpuct_at (tree_select.hip) at depth 0, for the host: the constant the root's children were scored with
+inline double cpuct_at_root(const TreeCfg& c) {
+    if (c.use_c_base) return c.cpuct_c_init + log((1.0 + c.cpuct_c_base) / c.cpuct_c_base);
+    return c.cpuct_plies <= 0 ? c.cpuct : c.cpuct_start;
+}
 
 // Per-game evaluation cache: what the network said about a position (value + the logits of its legal moves, in generation
 // order), keyed by everything the network input and the expansion depend on (pieces, turn, castling rights, legal
@@ -106,6 +118,10 @@ struct GameDev {
     uint64_t seed_gumbel, ctr_gumbel;
     int gumbel_drawn;
     int gumbel_miss;
+    // self-play budget mix: this search is a full one with forced playouts at its root (arm_search), and the descents the
+    // forcing rule has decided in this slot, counted by lane 0
+    int forced;
+    uint64_t forced_descents;
 };
 
 enum SampleKind : int {

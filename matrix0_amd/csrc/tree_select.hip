@@ -8,6 +8,7 @@
 #include "tree_device.h"
 #include "tree_gumbel.h"
 #include "tree_proof.h"
+#include "tree_forced.h"
 #include "tb_core.h"
 #include "eval_cache.h"
 #include "movegen_wave.h"
@@ -179,8 +180,12 @@ static_assert(sizeof(TopCache) == M0_SEL_CACHE_BYTES, "32 bytes of select fields
 // through PRF: the tree top's from an LDS copy beside TopCache, the others from the arena.  A terminal leaf is proven at its
 // first visit and the proof is combined up its path; a descent stops at a proven node; the scan passes over children that
 // are won for their own mover; a pass ends once the root is proven.  While no node is proven it is the PUCT search, draw by draw.
+// FORCED: the instantiation for the self-play budget mix (TreeCfg::budget, tree_forced.h, include/m0_budget.h).  The rule is per
+// game: in a search with GameDev::forced (a full search with forced playouts; full and fast searches of different games share a
+// launch) a descent takes, at depth 0, the lowest root child in deficit where there is one.  A search without the flag is the
+// PUCT search, draw by draw.
 #define PRF(i) ((i) < ncached ? TP[i] : A.proof[i])
-template <bool GUMBEL, bool PROOF>
+template <bool GUMBEL, bool PROOF, bool FORCED>
 __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
     extern __shared__ __attribute__((aligned(16))) char sel_cache[];
     TopCache* const TC = reinterpret_cast<TopCache*>(sel_cache);
@@ -250,6 +255,7 @@ __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
     const double jit = c.selection_jitter > 0.0 ? c.selection_jitter : 0.001;
     const int hist_len = gd->hist_len;
     const uint64_t* H = d.hist + (size_t)g * M0_HIST_CAP;
+    const bool forced_search = FORCED && gd->forced != 0;  // wave-uniform
     // proof search: step 2 of the rule needs a node's children to be all of its legal moves
     const bool proof_complete = c.max_children <= 0 && !(c.min_child_prior > 0.0);
     // a node becomes proven: the arena, the LDS copy, and the store made visible to the loads of later descents (see the fence
@@ -283,6 +289,16 @@ __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
             Move b_mv = 0;
             bool root_rule = false;
             if constexpr (GUMBEL) root_rule = depth == 0;
+            bool forced_root = false;                      // forced playouts: this level is the root of a search with the rule
+            int n_sum = 0;                                 // ... and the root children's completed visits
+            if constexpr (FORCED) {
+                forced_root = forced_search && depth == 0;
+                if (forced_root) {
+                    int part = 0;
+                    for (int i = lane; i < nc; i += 64) { const int ci = cb + i; part += TOP(n, ci < ncached, ci); }
+                    n_sum = wave_sum_i(part);
+                }
+            }
             bool skip_won = false;                         // proof search: some child is not won for its mover -- those that are
             if constexpr (PROOF) {                         // cannot be the arg-max
                 bool notwin = false;
@@ -315,6 +331,7 @@ __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
                     const int cvl = c.virtual_loss_active ? TOP(vl, hit, ci) : 0;
                     if (c.virtual_loss_active && c.virtual_loss > 0.0) sc -= (double)cvl * c.virtual_loss;
                     sc += (u01(seedj, ctrj + (uint64_t)i) - 0.5) * jit;
+                    if constexpr (FORCED) { if (forced_root) sc = forced_root_score(c.forced_k, cprior, cn, cvl, n_sum, i, sc); }
                     if (sc > best) { best = sc; bi = i; b_nch = c_nch; b_cb = c_cb; b_n = cn; b_q = cq; b_mv = m; b_vl = cvl; }
                 }
                 for (int off = 32; off > 0; off >>= 1) {
@@ -323,6 +340,7 @@ __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
                     if (oi >= 0 && (bi < 0 || ob > best || (ob == best && oi < bi))) { best = ob; bi = oi; }
                 }
                 ctrj += (uint64_t)nc;
+                if constexpr (FORCED) { if (forced_root && lane == 0 && budget_score_is_forced(best)) gd->forced_descents++; }
             }
             if (bi < 0) bi = 0;
             const int child = cb + bi;
@@ -405,20 +423,26 @@ __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
 hipError_t launch_select(const TreeDev& d, const TreeCfg& c, hipStream_t st) {
     static DeviceOnce once;
     hipError_t e = once.run([] {
-        hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&select_kernel<false, false>),
+        hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&select_kernel<false, false, false>),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, M0_SEL_CACHE_BYTES);
         if (e1 != hipSuccess) return e1;
-        e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&select_kernel<false, true>),
+        e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&select_kernel<false, true, false>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, M0_SEL_CACHE_BYTES);
         if (e1 != hipSuccess) return e1;
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(&select_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   M0_SEL_CACHE_BYTES);
+        e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&select_kernel<false, false, true>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, M0_SEL_CACHE_BYTES);
+        if (e1 != hipSuccess) return e1;
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(&select_kernel<true, false, false>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, M0_SEL_CACHE_BYTES);
     });
     if (e != hipSuccess) return e;
-    // the modes exclude each other (m0_selfplay_set_gumbel, m0_selfplay_set_proof); a proof search needs its node array
+    // the modes exclude each other (m0_selfplay_set_gumbel, m0_selfplay_set_proof, m0_selfplay_set_budget); a proof search needs
+    // its node array
     if (c.proof && (c.gumbel || !d.t.proof || !d.proof_results)) return hipErrorInvalidValue;
-    if (c.gumbel) hipLaunchKernelGGL((select_kernel<true, false>), dim3(d.G), dim3(64), M0_SEL_CACHE_BYTES, st, d, c);
-    else if (c.proof) hipLaunchKernelGGL((select_kernel<false, true>), dim3(d.G), dim3(64), M0_SEL_CACHE_BYTES, st, d, c);
-    else hipLaunchKernelGGL((select_kernel<false, false>), dim3(d.G), dim3(64), M0_SEL_CACHE_BYTES, st, d, c);
+    if (c.budget && (c.gumbel || c.proof || c.tt_merge)) return hipErrorInvalidValue;
+    if (c.gumbel) hipLaunchKernelGGL((select_kernel<true, false, false>), dim3(d.G), dim3(64), M0_SEL_CACHE_BYTES, st, d, c);
+    else if (c.proof) hipLaunchKernelGGL((select_kernel<false, true, false>), dim3(d.G), dim3(64), M0_SEL_CACHE_BYTES, st, d, c);
+    else if (c.budget) hipLaunchKernelGGL((select_kernel<false, false, true>), dim3(d.G), dim3(64), M0_SEL_CACHE_BYTES, st, d, c);
+    else hipLaunchKernelGGL((select_kernel<false, false, false>), dim3(d.G), dim3(64), M0_SEL_CACHE_BYTES, st, d, c);
     return hipGetLastError();
 }

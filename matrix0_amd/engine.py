@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _lib
 
-from ._abi import (AN_MAX_LINES, AN_MAX_PV, AnalysisLine, AnalysisOpts, AnalysisResult, GameRecord,  # noqa: F401
+from ._abi import (AN_MAX_LINES, AN_MAX_PV, AnalysisLine, AnalysisOpts, AnalysisResult, BudgetCfg, GameRecord,  # noqa: F401
                    GumbelCfg, ProofLines, SelfplayCfg, SelfplayStats)
 from ._lib import ptr
 
@@ -143,6 +143,53 @@ def gumbel_cfg_from_dict(cfg: dict) -> Optional[GumbelCfg]:
     return GumbelCfg(int(m), float(v["c_visit"]), float(v["c_scale"]))
 
 
+BUDGET_DEFAULTS = {"full_prob": 0.25, "fast_simulations": 100, "forced_k": 2.0, "prune_targets": True}   # KataGo's forced_k
+BUDGET_STATS = ("full_searches", "fast_searches", "forced_descents", "pruned_visits")
+
+
+def budget_cfg_from_dict(cfg: dict) -> Optional[BudgetCfg]:
+    """`mcts.budget: {enabled, full_prob: 0.25, fast_simulations: 100, forced_k: 2.0, prune_targets: true}` of config.yaml as the
+    library's struct (for SelfplayEngine.set_budget); None without the block or with `enabled: false`.  A block that is present
+    has to be right: ValueError for anything but a mapping with a boolean `enabled`, for an unknown key, for a full_prob that is
+    no number in (0, 1], a fast_simulations that is no integer >= 1, a forced_k that is no finite number >= 0, a prune_targets
+    that is no boolean, and for the mode together with mcts.gumbel, engine.proof_search or engine.compat.tt_merge."""
+    b = (cfg.get("mcts", {}) or {}).get("budget")
+    if b is None:
+        return None
+    if not isinstance(b, dict):
+        raise ValueError(f"mcts.budget must be a mapping, not {b!r}")
+    unknown = set(b) - {"enabled", *BUDGET_DEFAULTS}
+    if unknown:
+        raise ValueError(f"unknown mcts.budget keys: {sorted(map(str, unknown))}")
+    if not isinstance(b.get("enabled"), bool):
+        raise ValueError("mcts.budget.enabled must be true or false")
+    v = dict(BUDGET_DEFAULTS, **{k: x for k, x in b.items() if k != "enabled"})
+
+    def number(x):
+        return not isinstance(x, bool) and isinstance(x, (int, float))
+
+    p, fast, fk, prune = v["full_prob"], v["fast_simulations"], v["forced_k"], v["prune_targets"]
+    if not number(p) or not 0.0 < float(p) <= 1.0:
+        raise ValueError(f"mcts.budget.full_prob must be a number in (0, 1], not {p!r}")
+    if isinstance(fast, bool) or not isinstance(fast, int) or fast < 1:
+        raise ValueError(f"mcts.budget.fast_simulations must be an integer >= 1, not {fast!r}")
+    if not number(fk) or not 0.0 <= float(fk) < float("inf"):
+        raise ValueError(f"mcts.budget.forced_k must be a finite number >= 0, not {fk!r}")
+    if not isinstance(prune, bool):
+        raise ValueError(f"mcts.budget.prune_targets must be true or false, not {prune!r}")
+    if not b["enabled"]:
+        return None
+    ecfg = cfg.get("engine", {}) or {}
+    if bool(((ecfg.get("compat", {}) or {}).get("tt_merge", False))):
+        raise ValueError("mcts.budget does not go with engine.compat.tt_merge")
+    if bool(ecfg.get("proof_search", False)):
+        raise ValueError("mcts.budget does not go with engine.proof_search")
+    g = (cfg.get("mcts", {}) or {}).get("gumbel")
+    if isinstance(g, dict) and g.get("enabled") is True:
+        raise ValueError("mcts.budget does not go with mcts.gumbel")
+    return BudgetCfg(float(p), int(fast), float(fk), int(prune))
+
+
 def move_to_uci(m: int) -> str:
     f, t, p = m & 63, (m >> 6) & 63, (m >> 12) & 7
     s = "abcdefgh"[f & 7] + str((f >> 3) + 1) + "abcdefgh"[t & 7] + str((t >> 3) + 1)
@@ -222,6 +269,12 @@ class SelfplayEngine:
                 out["search_values"] = np.ctypeslib.as_array(r.search_values, shape=(T,)).copy()
             if r.ssl:
                 out["ssl"] = _lib.split_ssl(np.ctypeslib.as_array(r.ssl, shape=(T, 17, 8, 8)).copy())
+            if getattr(self, "budget", None) is not None:      # budget mix: which plies were searched in full, and with how much
+                full, sims = C.POINTER(C.c_uint8)(), C.POINTER(C.c_int)()
+                _lib.check(self._L.m0_game_record_budget(C.byref(r), C.byref(full), C.byref(sims)), "m0_game_record_budget")
+                have = bool(full) and bool(sims) and T > 0
+                out["full"] = np.ctypeslib.as_array(full, shape=(T,)).astype(bool) if have else np.zeros(0, bool)
+                out["sims"] = np.ctypeslib.as_array(sims, shape=(T,)).astype(np.int32) if have else np.zeros(0, np.int32)
         finally:
             self._L.m0_game_record_free(C.byref(r))
         return out
@@ -313,6 +366,35 @@ class SelfplayEngine:
         _lib.check(self._L.m0_search_gumbel_result(self._h, g, C.byref(pick), C.byref(vm), ptr(pi), ptr(gl), C.byref(miss)),
                    "m0_search_gumbel_result")
         return {"pick": pick.value, "v_mix": vm.value, "pi": pi[: k.value].copy(), "gl": gl[: k.value].copy(), "miss": miss.value}
+
+    # ---- self-play budget mix (include/m0_budget.h)
+    def set_budget(self, budget: Optional[BudgetCfg] = None, *, full_prob: float = BUDGET_DEFAULTS["full_prob"],
+                   fast_simulations: int = BUDGET_DEFAULTS["fast_simulations"], forced_k: float = BUDGET_DEFAULTS["forced_k"],
+                   prune_targets: bool = BUDGET_DEFAULTS["prune_targets"]) -> None:
+        """Turn the budget mix on (a self-play engine, before the first step or search): `budget` as budget_cfg_from_dict
+        returns it, or the four values.  Most moves then get a fast search without noise, a random share of `full_prob` the full
+        one with forced playouts at the root and a pruned policy target; `poll()` adds `full` and `sims` per ply."""
+        b = budget if budget is not None else BudgetCfg(float(full_prob), int(fast_simulations), float(forced_k),
+                                                        int(bool(prune_targets)))
+        _lib.check(self._L.m0_selfplay_set_budget(self._h, C.byref(b)), "m0_selfplay_set_budget")
+        self.budget = b
+
+    def search_budget_result(self, g: int) -> dict:
+        """Beside search_result(g): `pruned_n` and `pi` per root child (the plain visits and shares with forced_k = 0 or without
+        prune_targets) and `forced_descents`, the descents the forcing rule has decided in the slot; zeros and -1 while the
+        search runs."""
+        k = c_int(0); fd = c_int(-1)
+        _lib.check(self._L.m0_search_result(self._h, g, C.byref(k), None, None, None, None, None, None, None, None),
+                   "m0_search_result")
+        pn, pi = np.zeros(256, np.int32), np.zeros(256, np.float64)
+        _lib.check(self._L.m0_search_budget_result(self._h, g, ptr(pn), ptr(pi), C.byref(fd)), "m0_search_budget_result")
+        return {"pruned_n": pn[: k.value].copy(), "pi": pi[: k.value].copy(), "forced_descents": fd.value}
+
+    def budget_stats(self) -> Dict[str, int]:
+        """Full searches, fast searches, descents decided by the forcing rule and visits pruned from targets so far."""
+        out = np.zeros(4, np.uint64)
+        _lib.check(self._L.m0_selfplay_budget_stats(self._h, ptr(out)), "m0_selfplay_budget_stats")
+        return {k: int(x) for k, x in zip(BUDGET_STATS, out)}
 
     # ---- proof search (include/m0_proof.h)
     def set_proof(self, on: bool = True) -> None:
@@ -424,6 +506,23 @@ class SelfplayPool:
             out[k] = v / len(sts) if k.startswith("ms_") or k == "steps" else v
         return out
 
+    # ---- self-play budget mix: every engine of the pool, in slot order
+    def set_budget(self, *args, **kw) -> None:
+        for e in self.engines:
+            e.set_budget(*args, **kw)
+
+    def search_budget_result(self, g: int) -> dict:
+        """Slot g counted over the engines in order (engine 0's slots first)."""
+        for e in self.engines:
+            if g < e.cfg.concurrent_games:
+                return e.search_budget_result(g)
+            g -= e.cfg.concurrent_games
+        raise IndexError("slot out of range")
+
+    def budget_stats(self) -> Dict[str, int]:
+        sts = [e.budget_stats() for e in self.engines]
+        return {k: sum(s[k] for s in sts) for k in sts[0]}
+
     def close(self):
         for e in getattr(self, "engines", []):
             e.close()
@@ -468,6 +567,34 @@ def gumbel_improve(prior, q, n, gl, root_v: float, c_visit: float = GUMBEL_DEFAU
     _lib.check(_lib.lib().m0_gumbel_improve(k, ptr(pr), ptr(qq), ptr(nn), ptr(gg), float(root_v), C.byref(g), ptr(pi),
                                             C.byref(vm), C.byref(pick)), "m0_gumbel_improve")
     return pi, vm.value, pick.value
+
+
+def budget_is_full(seed: int, game_index: int, ply: int, full_prob: float) -> bool:
+    """Whether searched ply `ply` of game `game_index` gets the full search (include/m0_budget.h)."""
+    full = c_int(0)
+    _lib.check(_lib.lib().m0_budget_is_full(int(seed), int(game_index), int(ply), float(full_prob), C.byref(full)),
+               "m0_budget_is_full")
+    return bool(full.value)
+
+
+def budget_forced(forced_k: float, prior: float, n_sum: int) -> float:
+    """sqrt(forced_k * prior * n_sum): the visits forced playouts bring a visited root child up to."""
+    out = c_double(0)
+    _lib.check(_lib.lib().m0_budget_forced(float(forced_k), float(prior), int(n_sum), C.byref(out)), "m0_budget_forced")
+    return out.value
+
+
+def budget_prune(prior, q, n, root_n: int, cpuct: float, forced_k: float = BUDGET_DEFAULTS["forced_k"]):
+    """(pruned_n i32 [k], pi f64 [k], best) of a root's children from their prior, q and visits (include/m0_budget.h)."""
+    pr, qq = (np.ascontiguousarray(a, dtype=np.float64) for a in (prior, q))
+    nn = np.ascontiguousarray(n, dtype=np.int32)
+    k = int(pr.shape[0])
+    if not (qq.shape == nn.shape == (k,)):
+        raise ValueError("prior, q and n must have one entry per child")
+    pn, pi, best = np.zeros(k, np.int32), np.zeros(k, np.float64), c_int(-1)
+    _lib.check(_lib.lib().m0_budget_prune(k, ptr(pr), ptr(qq), ptr(nn), int(root_n), float(cpuct), float(forced_k), ptr(pn),
+                                          ptr(pi), C.byref(best)), "m0_budget_prune")
+    return pn, pi, best.value
 
 
 PROOF_STATES = ["none", "win", "loss", "draw"]                 # M0_PROOF_* of include/m0_proof.h, by value

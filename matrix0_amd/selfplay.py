@@ -20,6 +20,9 @@ found in them instead of a network evaluation.  `tablebases.enabled: true` is ac
 
 The one new key outside `engine:` is `mcts.gumbel: {enabled, max_considered: 16, c_visit: 50.0, c_scale: 1.0}`: the Gumbel root
 search (sequential halving, improved-policy targets; engine.gumbel_cfg_from_dict) for small simulation budgets.
+Another is `mcts.budget: {enabled, full_prob: 0.25, fast_simulations: 100, forced_k: 2.0, prune_targets: true}`: playout-cap
+randomisation with forced playouts and policy-target pruning (engine.budget_cfg_from_dict).  A shard then holds the plies that
+were searched in full, with `meta_plies` and `meta_full_rows`; a game without one writes no shard and is still reported.
 
 The orchestrator hands the SAME cfg_dict to every worker (orchestrator.py:490-496), so what tells workers apart is
 proc_id alone: worker i runs on GPU  i % (visible MI355X)  and plays the global game indices [i*games, (i+1)*games) --
@@ -39,7 +42,7 @@ import numpy as np
 from . import encoding
 from .backend import M0Backend
 from .data_writer import ReplayShardWriter, SelfplayShardWriter
-from .engine import SelfplayEngine, SelfplayPool, gumbel_cfg_from_dict, selfplay_cfg_from_dict
+from .engine import SelfplayEngine, SelfplayPool, budget_cfg_from_dict, gumbel_cfg_from_dict, selfplay_cfg_from_dict
 from .pgn import START_FEN
 from .tablebase import Tablebase, probe_limit, tablebase_cfg
 from .weights import random_state_dict
@@ -87,6 +90,21 @@ def shard_writer(cfg_dict: dict, eng_cfg: dict):
         return SelfplayShardWriter(base_dir=cfg_dict.get("data_dir", "data"))
     return ReplayShardWriter(base_dir=cfg_dict.get("data_dir", "data"), max_shards=int(eng_cfg.get("max_shards", 128)),
                              shard_size=int(eng_cfg.get("shard_size", 16384)), packed=replay == "packed")
+
+
+def keep_full_rows(game_data: dict, full) -> dict:
+    """Budget mix (mcts.budget): the shard of a game holds the plies that were searched in full, in order -- every per-row array
+    (s, pi, z, legal_mask, ssl_*) filtered alike -- with `meta_plies` (plies searched) and `meta_full_rows` (rows kept) beside
+    the game's other metadata, which still describes the whole game."""
+    keep = np.asarray(full, dtype=bool)
+    rows = int(keep.shape[0])
+    out = {}
+    for key, a in game_data.items():
+        per_row = not key.startswith("meta_") and getattr(a, "ndim", 0) >= 1 and a.shape[0] == rows
+        out[key] = a[keep] if per_row else a
+    out["meta_plies"] = np.array([rows], dtype=np.int32)
+    out["meta_full_rows"] = np.array([int(keep.sum())], dtype=np.int32)
+    return out
 
 
 def selfplay_worker(proc_id: int, cfg_dict: dict, ckpt_path: Optional[str], games: int, q=None,
@@ -150,6 +168,13 @@ def selfplay_worker(proc_id: int, cfg_dict: dict, ckpt_path: Optional[str], game
         for e in engines:
             e.set_gumbel(gumbel)
         logger.info("worker %d: Gumbel root search, %d considered moves", proc_id, gumbel.max_considered)
+    # mcts.budget: most moves get a fast search, a random share the full one; only those become training rows
+    budget = budget_cfg_from_dict(cfg_dict)
+    if budget is not None:
+        for e in engines:
+            e.set_budget(budget)
+        logger.info("worker %d: budget mix, full searches with probability %.3f, fast searches of %d simulations", proc_id,
+                    budget.full_prob, budget.fast_simulations)
     if book:
         for e in engines:
             e.set_openings(book)
@@ -192,9 +217,16 @@ def selfplay_worker(proc_id: int, cfg_dict: dict, ckpt_path: Optional[str], game
                     if "ssl" in rec and task in rec["ssl"]:
                         game_data[f"ssl_{task}"] = rec["ssl"][task].astype(np.float32)
                 filepath = None
-                if T > 0 and direct_replay:
+                rows = T                                            # rows the shard gets: with the budget mix the full plies
+                if budget is not None and T > 0:
+                    game_data = keep_full_rows(game_data, rec["full"])
+                    rows = int(game_data["meta_full_rows"][0])
+                    if rows == 0:
+                        logger.info("worker %d: game %d has no full search among its %d plies, no shard written", proc_id,
+                                    rec["game_index"], T)
+                if rows > 0 and direct_replay:
                     writer.add_game(game_data)
-                elif T > 0:
+                elif rows > 0:
                     filepath = writer.add_selfplay_data(game_data, worker_id=proc_id, game_id=rec["game_index"])
                 done += 1
                 if q is not None:                                   # internal.py:665-679
