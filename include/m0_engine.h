@@ -595,6 +595,8 @@ int m0_replay_games(int hip_device, const char* const* start_fens, const uint32_
 #include "m0_rowpack.h"
 /* a resident store of packed rows: training batches gathered, expanded and augmented on the device in one launch */
 #include "m0_batch.h"
+/* ... and the SSL target maps of the augmented rows, written by the same launch */
+#include "m0_batch_ssl.h"
 /* self-play budget mix: full and fast searches, forced playouts and policy-target pruning (opt-in) */
 #include "m0_budget.h"
 #endif /* M0_ENGINE_H */

@@ -339,6 +339,15 @@ BATCH_FUNCTIONS = {
     "m0_rowstore_bench": (i32, [i32, i32, i32, vp, vp, P(f64)]),
 }
 
+# ---- include/m0_batch_ssl.h (which m0_engine.h includes behind m0_batch.h): batches with the SSL target maps of their rows, in
+# that header's order; tests/test_abi_batch_ssl.py compares the two ----
+BATCH_SSL_CH = 17
+BATCH_SSL_FUNCTIONS = {
+    "m0_rowstore_batch_ssl": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp]),
+    "m0_rowstore_batch_ssl_host": (i32, [P(RowpackArrays), vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+    "m0_rowstore_bench_ssl": (i32, [i32, i32, i32, vp, vp, P(f64)]),
+}
+
 # ---- include/m0_budget.h (which m0_engine.h includes too): the self-play budget mix, in that header's order;
 # tests/test_abi_budget.py compares the two ----
 BUDGET_STRUCTS = {"m0_budget_cfg": BudgetCfg}
@@ -355,14 +364,14 @@ BUDGET_FUNCTIONS = {
 
 def bind(L) -> list:
     """Set restype and argtypes of every function of FUNCTIONS, LIVE_FUNCTIONS, SCORE_FUNCTIONS, SSL_SCORE_FUNCTIONS,
-    GUMBEL_FUNCTIONS, AUGMENT_FUNCTIONS, PROOF_FUNCTIONS, ROWPACK_FUNCTIONS, BATCH_FUNCTIONS and BUDGET_FUNCTIONS on the loaded
-    library; the names it does not export."""
+    GUMBEL_FUNCTIONS, AUGMENT_FUNCTIONS, PROOF_FUNCTIONS, ROWPACK_FUNCTIONS, BATCH_FUNCTIONS, BATCH_SSL_FUNCTIONS and
+    BUDGET_FUNCTIONS on the loaded library; the names it does not export."""
     missing = []
     for name, (restype, argtypes) in (list(FUNCTIONS.items()) + list(LIVE_FUNCTIONS.items()) + list(SCORE_FUNCTIONS.items()) +
                                       list(SSL_SCORE_FUNCTIONS.items()) + list(GUMBEL_FUNCTIONS.items()) +
                                       list(AUGMENT_FUNCTIONS.items()) + list(PROOF_FUNCTIONS.items()) +
                                       list(ROWPACK_FUNCTIONS.items()) + list(BATCH_FUNCTIONS.items()) +
-                                      list(BUDGET_FUNCTIONS.items())):
+                                      list(BATCH_SSL_FUNCTIONS.items()) + list(BUDGET_FUNCTIONS.items())):
         fn = getattr(L, name, None)
         if fn is None:
             missing.append(name)

@@ -73,23 +73,48 @@ inline void rebase_segment(SegBlock& block, const uint8_t* base) {
     memcpy(block.bytes.data(), &v, sizeof(SegView));
 }
 
-// One output row on the CPU: what batch_rows_kernel writes for the same reference.  mask null: not written.
-inline void batch_row_host(const SegView& g, int row, int kind, float* planes, float* pi, float* z, uint8_t* mask) {
+// The maps of one output row from the pieces of its 64 output cells (batch_core.h): status 0; an unusable row: zeros, status 1
+inline void ssl_row_host(const int* cells, bool usable, bool stm_white, float* ssl, int32_t* ssl_status) {
+    m0ssl::Board4 board;
+    for (int t = 0; t < 64; ++t) board.set(t, cells[t]);
+    for (int t = 0; t < 64; ++t) {
+        if (usable) target_cell(board, t, stm_white, ssl);
+        else zero_cell(ssl, t);
+    }
+    *ssl_status = usable ? 0 : 1;
+}
+
+// One output row on the CPU: what batch_rows_kernel writes for the same reference.  mask null: not written; ssl and ssl_status
+// both null: not written.
+inline void batch_row_host(const SegView& g, int row, int kind, float* planes, float* pi, float* z, uint8_t* mask, float* ssl = nullptr,
+                           int32_t* ssl_status = nullptr) {
     *z = g.z[row];
     const uint8_t meta = g.meta[row];
+    int cells[64];
     if (meta_raw(meta)) {
         const size_t slot = (size_t)g.raw_slot[row];
-        m0aug::augment_row(kind, (const uint32_t*)(g.raw_planes + slot * PLANE_FLOATS), M0_PLANES, (const uint32_t*)(g.raw_pi + slot * COLS),
+        const float* stored = g.raw_planes + slot * PLANE_FLOATS;
+        m0aug::augment_row(kind, (const uint32_t*)stored, M0_PLANES, (const uint32_t*)(g.raw_pi + slot * COLS),
                            mask ? g.raw_mask + slot * COLS : nullptr, (uint32_t*)planes, (uint32_t*)pi, mask);
+        if (ssl) {
+            bool unusable = false;
+            for (int t = 0; t < 64; ++t) {
+                bool bad;
+                cells[t] = raw_cell(stored, kind, t, &bad);
+                unusable = unusable || bad;
+            }
+            ssl_row_host(cells, !unusable, raw_white(stored, kind), ssl, ssl_status);
+        }
         return;
     }
     const Pos& p = g.pos[row];
     float c7[7];
     m0::plane_consts(p, c7);
     for (int t = 0; t < 64; ++t) {
-        const int pl = m0::piece_plane(p, cell_square(kind, t));
+        const int pl = cells[t] = m0::piece_plane(p, cell_square(kind, t));
         for (int k = 0; k < M0_PLANES; ++k) planes[k * 64 + t] = plane_cell(pl, c7, k);
     }
+    if (ssl) ssl_row_host(cells, true, p.turn == m0::WHITE, ssl, ssl_status);
     memset(pi, 0, COLS * sizeof(float));
     for (int64_t e = g.pi_off[row]; e < g.pi_off[row + 1]; ++e) pi[dest_column(kind, g.pi_idx[e])] = g.pi_val[e];
     if (!mask) return;
@@ -106,11 +131,13 @@ inline void batch_row_host(const SegView& g, int row, int kind, float* planes, f
     }
 }
 
-// refs [B] -> the dense outputs
-inline void batch_rows_host(const RowRef* refs, int B, float* planes, float* pi, float* z, uint8_t* mask) {
+// refs [B] -> the dense outputs; ssl [B][17][64] and ssl_status [B], or both null
+inline void batch_rows_host(const RowRef* refs, int B, float* planes, float* pi, float* z, uint8_t* mask, float* ssl = nullptr,
+                            int32_t* ssl_status = nullptr) {
     for (int b = 0; b < B; ++b)
         batch_row_host(*refs[b].seg, refs[b].row, refs[b].kind, planes + (size_t)b * PLANE_FLOATS, pi + (size_t)b * COLS, z + b,
-                       mask ? mask + (size_t)b * COLS : nullptr);
+                       mask ? mask + (size_t)b * COLS : nullptr, ssl ? ssl + (size_t)b * SSL_FLOATS : nullptr,
+                       ssl ? ssl_status + b : nullptr);
 }
 
 }  // namespace m0batch

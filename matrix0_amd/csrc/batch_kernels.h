@@ -9,3 +9,8 @@
 // planes f32 [B][19][64], pi f32 [B][4672], z f32 [B], mask u8 [B][4672] (null: a store without masks), all device memory with
 // planes, pi and mask on 16-byte boundaries.  One wave per output row; every byte of planes, pi and mask is written once.
 hipError_t launch_batch_rows(const m0batch::RowRef* refs, int B, float* planes, float* pi, float* z, uint8_t* mask, hipStream_t st);
+// The same launch with the SSL target maps of the output planes (include/m0_batch_ssl.h): ssl f32 [B][17][64] and ssl_status
+// i32 [B], device memory, each map stored as one 256-byte row by the wave of its output row; the other outputs bit for bit those
+// of launch_batch_rows.
+hipError_t launch_batch_rows_ssl(const m0batch::RowRef* refs, int B, float* planes, float* pi, float* z, uint8_t* mask, float* ssl,
+                                 int32_t* ssl_status, hipStream_t st);

@@ -16,10 +16,21 @@
 // nothing shared between waves: a row's bytes depend on (seg, row, kind) alone.  LDS: 18 688 + 4 672 + 2 x 512 bytes a workgroup,
 // six workgroups on a CU's 160 KB.
 //
+// SSL = true (include/m0_batch_ssl.h) is the same body with two more outputs, the target maps of the row's output planes and
+// their status (the rule: batch_core.h); SSL = false compiles to the kernel without them.  Lane t owns output cell t:
+//   PACKED  four ballots of the piece plane the lane already holds make the board (m0ssl::Board4); the side to move is the
+//           position's.  No LDS, no global read.
+//   RAW     the lane reads its cell of planes 0-12 of the stored row by the read-side rule (raw_cell); one __any decides for the
+//           wave whether the row is usable.  An unusable row gets zeros.
+// A wave stores each of the 17 maps as one whole 256-byte row (lane t the dword of cell t), so every byte of ssl[b] is written
+// exactly once; ssl_status[b] is one dword from lane 0.  No LDS is added.
+//
 // Bounds: the host has checked b < B, row < seg->n and kind <= 2.  check_arrays has run over every segment: an entry's column is
 // below 4672, dest_column maps [0, 4672) onto itself, so a scatter stays inside the workgroup's own LDS arrays; a row reads
 // [off[row], off[row + 1]) of its segment's entries only; raw_slot of a RAW row is below the segment's RAW rows.  A move index is
-// bounded before it is used.  Global stores go to pieces below PLANE_PIECES, PI_PIECES and MASK_PIECES of row b.
+// bounded before it is used.  Global stores go to pieces below PLANE_PIECES, PI_PIECES and MASK_PIECES of row b.  The maps go to
+// ssl + b * 17 * 64 + k * 64 + lane with k < 17 and lane < 64; raw_cell reads planes 0-12 of the RAW row's own slot at squares
+// below 64 (map_square maps [0, 64) onto itself).
 #include <hip/hip_runtime.h>
 #include "batch_core.h"
 #include "batch_kernels.h"
@@ -33,8 +44,10 @@ using m0rowpack::PLANE_PIECES;
 
 namespace {
 
+template <bool SSL>
 __global__ __launch_bounds__(LANES) void batch_rows_kernel(const RowRef* __restrict__ refs, int B, float* __restrict__ planes,
-                                                          float* __restrict__ pi, float* __restrict__ z, uint8_t* __restrict__ mask) {
+                                                          float* __restrict__ pi, float* __restrict__ z, uint8_t* __restrict__ mask,
+                                                          float* __restrict__ ssl, int32_t* __restrict__ ssl_status) {
     __shared__ __attribute__((aligned(16))) uint32_t spi[COLS];
     __shared__ __attribute__((aligned(16))) uint8_t smask[COLS];
     __shared__ Move smoves[M0_MAX_MOVES];
@@ -54,6 +67,21 @@ __global__ __launch_bounds__(LANES) void batch_rows_kernel(const RowRef* __restr
         const size_t slot = (size_t)g.raw_slot[row];
         const uint32_t* rs = reinterpret_cast<const uint32_t*>(g.raw_planes + slot * PLANE_FLOATS);
         const uint32_t* rp = reinterpret_cast<const uint32_t*>(g.raw_pi + slot * COLS);
+        if constexpr (SSL) {
+            const float* stored = g.raw_planes + slot * PLANE_FLOATS;
+            float* maps = ssl + (size_t)b * SSL_FLOATS;
+            bool bad;
+            const int piece = raw_cell(stored, kind, lane, &bad);
+            const bool unusable = __any(bad) != 0;                        // once per wave
+            if (lane == 0) ssl_status[b] = unusable ? 1 : 0;
+            if (unusable) {
+                zero_cell(maps, lane);
+            } else {
+                m0ssl::Board4 board;
+                for (int j = 0; j < 4; ++j) board.w[j] = __ballot(((piece + 1) >> j) & 1);
+                target_cell(board, lane, raw_white(stored, kind), maps);
+            }
+        }
         for (int j = lane; j < PLANE_PIECES; j += LANES) {
             const uint32_t* src = rs + (j >> 4) * 64;
             const int t = (j & 15) * 4;
@@ -85,6 +113,12 @@ __global__ __launch_bounds__(LANES) void batch_rows_kernel(const RowRef* __restr
         float c7[7];
         plane_consts(p, c7);
         const int pl = piece_plane(p, cell_square(kind, lane));
+        if constexpr (SSL) {
+            m0ssl::Board4 board;
+            for (int j = 0; j < 4; ++j) board.w[j] = __ballot(((pl + 1) >> j) & 1);
+            target_cell(board, lane, p.turn == WHITE, ssl + (size_t)b * SSL_FLOATS);
+            if (lane == 0) ssl_status[b] = 0;
+        }
         int pl4[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) pl4[i] = __shfl(pl, (lane & 15) * 4 + i);
@@ -124,6 +158,13 @@ __global__ __launch_bounds__(LANES) void batch_rows_kernel(const RowRef* __restr
 
 hipError_t launch_batch_rows(const RowRef* refs, int B, float* planes, float* pi, float* z, uint8_t* mask, hipStream_t st) {
     if (!refs || !planes || !pi || !z || B <= 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(batch_rows_kernel, dim3(B), dim3(LANES), 0, st, refs, B, planes, pi, z, mask);
+    hipLaunchKernelGGL(batch_rows_kernel<false>, dim3(B), dim3(LANES), 0, st, refs, B, planes, pi, z, mask, nullptr, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_rows_ssl(const RowRef* refs, int B, float* planes, float* pi, float* z, uint8_t* mask, float* ssl,
+                                 int32_t* ssl_status, hipStream_t st) {
+    if (!refs || !planes || !pi || !z || !ssl || !ssl_status || B <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(batch_rows_kernel<true>, dim3(B), dim3(LANES), 0, st, refs, B, planes, pi, z, mask, ssl, ssl_status);
     return hipGetLastError();
 }

@@ -1,4 +1,5 @@
-// extern "C" entry points of the resident row store (include/m0_batch.h).  A store owns its segments (one allocation each, a
+// extern "C" entry points of the resident row store (include/m0_batch.h) and of its batches with SSL target maps
+// (include/m0_batch_ssl.h: the same path with two more outputs and the SSL instantiation of the kernel).  A store owns its segments (one allocation each, a
 // SegView in front: batch_host.h), a ring of descriptor slots, and the staging outputs of batches that go to host memory.
 //
 // A batch resolves its ids to row references on the host, writes them into a slot's pinned buffer, copies them to the slot's
@@ -64,6 +65,10 @@ struct m0_rowstore {
     float* o_z = nullptr;
     uint8_t* o_mask = nullptr;
     int o_cap = 0;
+    // ... and of its SSL target maps, from the first batch that asks for them (m0_rowstore_batch_ssl)
+    float* o_ssl = nullptr;
+    int32_t* o_status = nullptr;
+    int o_ssl_cap = 0;
 
     bool on_device() const { return device >= 0; }
     int64_t resident() const { return segs.empty() ? 0 : segs.back().first + segs.back().rows - segs.front().first; }
@@ -82,6 +87,18 @@ void free_outputs(m0_rowstore* s) {
     (void)hipFree(s->o_planes); (void)hipFree(s->o_pi); (void)hipFree(s->o_z); (void)hipFree(s->o_mask);
     s->o_planes = s->o_pi = s->o_z = nullptr; s->o_mask = nullptr; s->o_cap = 0;
 }
+
+void free_ssl_outputs(m0_rowstore* s) {
+    (void)hipFree(s->o_ssl); (void)hipFree(s->o_status);
+    s->o_ssl = nullptr; s->o_status = nullptr; s->o_ssl_cap = 0;
+}
+
+// the two outputs m0_rowstore_batch_ssl adds; `asked` false: a batch without them
+struct SslOut {
+    bool asked = false;
+    float* maps = nullptr;
+    int32_t* status = nullptr;
+};
 
 // the slot of this batch, free and holding B references
 Slot* take_slot(m0_rowstore* s, int B) {
@@ -117,9 +134,9 @@ bool resolve(const m0_rowstore* s, const int64_t* rows, const uint8_t* kinds, in
 
 // the argument checks of a batch that need no store
 int check_batch(const int64_t* rows, const uint8_t* kinds, int B, const float* planes, const float* pi, const float* z, const uint8_t* mask,
-                bool with_mask) {
+                bool with_mask, const SslOut& ssl = SslOut()) {
     if (B <= 0) return invalid("batch must be positive");
-    if (!rows || !planes || !pi || !z) return invalid("null argument");
+    if (!rows || !planes || !pi || !z || (ssl.asked && (!ssl.maps || !ssl.status))) return invalid("null argument");
     if ((mask != nullptr) != with_mask) return invalid(with_mask ? "the rows have masks: a mask output is required" : "the rows have no masks: no mask output");
     if (kinds)
         if (const char* why = m0_bad_kinds(kinds, B)) return invalid(why);
@@ -127,7 +144,7 @@ int check_batch(const int64_t* rows, const uint8_t* kinds, int B, const float* p
 }
 
 int device_batch(m0_rowstore* s, const int64_t* rows, const uint8_t* kinds, int B, float* planes, float* pi, float* z, uint8_t* mask,
-                 bool outputs_on_device, hipStream_t stream) {
+                 const SslOut& ssl, bool outputs_on_device, hipStream_t stream) {
     if (!M0_HIP(s->hs, hipSetDevice(s->device))) return m0_hip_error(s->hs);
     if (!outputs_on_device) stream = nullptr;
     Slot* sl = take_slot(s, B);
@@ -136,6 +153,19 @@ int device_batch(m0_rowstore* s, const int64_t* rows, const uint8_t* kinds, int 
     if (!resolve(s, rows, kinds, B, sl->pinned, &missing)) return invalid("row " + std::to_string(missing) + " is not resident");
     float *dpl = planes, *dpi = pi, *dz = z;
     uint8_t* dm = mask;
+    float* dssl = ssl.maps;
+    int32_t* dst = ssl.status;
+    if (!outputs_on_device && ssl.asked) {
+        if (s->o_ssl_cap < B) {
+            drain(s);
+            free_ssl_outputs(s);
+            M0_HIP(s->hs, hipMalloc((void**)&s->o_ssl, (size_t)B * SSL_FLOATS * sizeof(float)));
+            M0_HIP(s->hs, hipMalloc((void**)&s->o_status, (size_t)B * sizeof(int32_t)));
+            if (!s->hs.ok()) return m0_hip_error(s->hs, "hipMalloc failed");
+            s->o_ssl_cap = B;
+        }
+        dssl = s->o_ssl; dst = s->o_status;
+    }
     if (!outputs_on_device) {
         if (s->o_cap < B) {
             drain(s);
@@ -151,7 +181,8 @@ int device_batch(m0_rowstore* s, const int64_t* rows, const uint8_t* kinds, int 
         dpl = s->o_planes; dpi = s->o_pi; dz = s->o_z; dm = s->o_mask;
     }
     M0_HIP(s->hs, hipMemcpyAsync(sl->dev, sl->pinned, (size_t)B * sizeof(RowRef), hipMemcpyHostToDevice, stream));
-    M0_HIP(s->hs, launch_batch_rows(sl->dev, B, dpl, dpi, dz, dm, stream));
+    M0_HIP(s->hs, ssl.asked ? launch_batch_rows_ssl(sl->dev, B, dpl, dpi, dz, dm, dssl, dst, stream)
+                            : launch_batch_rows(sl->dev, B, dpl, dpi, dz, dm, stream));
     if (M0_HIP(s->hs, hipEventRecord(sl->done, stream))) sl->busy = true;
     if (!s->hs.ok()) return m0_hip_error(s->hs, "batch launch failed");
     if (outputs_on_device) return M0_OK;
@@ -163,8 +194,96 @@ int device_batch(m0_rowstore* s, const int64_t* rows, const uint8_t* kinds, int 
     M0_HIP(s->hs, hipMemcpy(pi, dpi, N * COLS * sizeof(float), hipMemcpyDeviceToHost));
     M0_HIP(s->hs, hipMemcpy(z, dz, N * sizeof(float), hipMemcpyDeviceToHost));
     if (mask) M0_HIP(s->hs, hipMemcpy(mask, dm, N * COLS, hipMemcpyDeviceToHost));
+    if (ssl.asked) {
+        M0_HIP(s->hs, hipMemcpy(ssl.maps, dssl, N * SSL_FLOATS * sizeof(float), hipMemcpyDeviceToHost));
+        M0_HIP(s->hs, hipMemcpy(ssl.status, dst, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
     return s->hs.ok() ? M0_OK : m0_hip_error(s->hs, "download failed");
 }
+
+// m0_rowstore_batch and m0_rowstore_batch_ssl
+int store_batch(m0_rowstore* s, const int64_t* rows, const uint8_t* kinds, int B, float* planes, float* pi, float* z, uint8_t* mask,
+                const SslOut& ssl, int outputs_on_device, void* stream) {
+    if (!s) return invalid("null handle");
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!s->hs.ok()) return m0_hip_error(s->hs);
+    if (const int rc = check_batch(rows, kinds, B, planes, pi, z, mask, s->with_mask, ssl)) return rc;
+    if (outputs_on_device && !s->on_device()) return invalid("a host store fills host memory");
+    if (outputs_on_device && (((uintptr_t)planes | (uintptr_t)pi | (uintptr_t)mask | (uintptr_t)ssl.maps) & 15) != 0)
+        return invalid("device outputs must lie on 16-byte boundaries");
+    if (s->on_device()) return device_batch(s, rows, kinds, B, planes, pi, z, mask, ssl, outputs_on_device != 0, (hipStream_t)stream);
+    s->refs.resize((size_t)B);
+    int64_t missing = 0;
+    if (!resolve(s, rows, kinds, B, s->refs.data(), &missing)) return invalid("row " + std::to_string(missing) + " is not resident");
+    batch_rows_host(s->refs.data(), B, planes, pi, z, mask, ssl.maps, ssl.status);
+    return M0_OK;
+}
+
+// m0_rowstore_batch_host and m0_rowstore_batch_ssl_host
+int arrays_batch(const m0_rowpack_arrays* in, const int64_t* rows, const uint8_t* kinds, int B, float* planes, float* pi, float* z,
+                 uint8_t* mask, const SslOut& ssl) {
+    if (!in) return invalid("null argument");
+    if (B <= 0) return invalid("batch must be positive");
+    SegBlock block;
+    const std::string why = build_segment(in, mask != nullptr, block);
+    if (!why.empty()) return invalid("packed rows: " + why);
+    if (const int rc = check_batch(rows, kinds, B, planes, pi, z, mask, mask != nullptr, ssl)) return rc;
+    const SegView* view = reinterpret_cast<const SegView*>(block.bytes.data());
+    std::vector<RowRef> refs((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        if (rows[b] < 0 || rows[b] >= in->n) return invalid("row " + std::to_string(rows[b]) + " is not one of the packed rows");
+        refs[b] = RowRef{view, (int32_t)rows[b], kinds ? (int32_t)kinds[b] : M0_AUG_NONE};
+    }
+    batch_rows_host(refs.data(), B, planes, pi, z, mask, ssl.maps, ssl.status);
+    return M0_OK;
+}
+
+// The rows of the two benches: those of m0_rowpack_bench (every row PACKED with a LEGAL mask) in their packed form, a store of its
+// own that holds them, and the references of a batch of all B of them, kinds 0, 1, 2 in turn, in order and in a seeded shuffle.
+struct BenchRows {
+    std::vector<m0_rowpack_pos> hq;
+    std::vector<int64_t> hpo, hmo;
+    std::vector<uint16_t> hidx;
+    std::vector<float> hval, hz;
+    std::vector<Pos> positions;
+    std::vector<int32_t> raw_slot;
+    std::vector<uint8_t> hk;
+    m0_rowstore* store = nullptr;
+    DevBuf<RowRef> dorder, dshuffled;
+
+    ~BenchRows() { m0_rowstore_destroy(store); }
+
+    int build(HipStatus& hs, int hip_device, int B) {
+        const size_t N = (size_t)B;
+        std::vector<float> planes, pi, z(N, 0.f);
+        std::vector<uint8_t> mask;
+        m0_rowpack_bench_rows(N, planes, pi, mask);
+        // their packed form: the sizes first, then the arrays
+        int64_t sizes[3];
+        m0_rowpack_arrays a = {};
+        a.n = B;
+        (void)pack_host(planes.data(), pi.data(), z.data(), mask.data(), N, &a, sizes);
+        hq.resize(N); hpo.resize(N + 1); hmo.resize(N + 1); hidx.resize((size_t)sizes[0]); hval.resize((size_t)sizes[0]); hz.resize(N);
+        a.pi_n = sizes[0]; a.pos = hq.data(); a.z = hz.data(); a.pi_off = hpo.data(); a.mask_off = hmo.data(); a.pi_idx = hidx.data();
+        a.pi_val = hval.data();
+        if (sizes[1] != 0 || sizes[2] != 0 || !pack_host(planes.data(), pi.data(), z.data(), mask.data(), N, &a, sizes).empty())
+            return invalid("the bench rows did not pack as positions with legal masks");
+        const std::string why = check_arrays(&a, positions, raw_slot);
+        if (!why.empty()) return invalid(why);
+        store = m0_rowstore_create(hip_device, 1);
+        int64_t first = 0;
+        if (!store) return M0_ERR_HIP;
+        if (const int rc = m0_rowstore_append(store, &a, &first)) return rc;
+        std::vector<RowRef> order(N), shuffled(N);
+        hk.resize(N);
+        BenchRng rng;
+        for (size_t i = 0; i < N; ++i) { hk[i] = (uint8_t)(i % m0aug::KINDS); order[i] = RowRef{store->segs.back().view(), (int32_t)i, (int32_t)hk[i]}; }
+        shuffled = order;
+        for (size_t i = N - 1; i > 0; --i) std::swap(shuffled[i].row, shuffled[rng.next() % (i + 1)].row);
+        dorder.upload(hs, order.data(), N); dshuffled.upload(hs, shuffled.data(), N);
+        return hs.ok() ? M0_OK : m0_hip_error(hs, "upload failed");
+    }
+};
 
 }  // namespace
 
@@ -193,6 +312,7 @@ void m0_rowstore_destroy(m0_rowstore* s) {
             if (sl.dev) (void)hipFree(sl.dev);
         }
         free_outputs(s);
+        free_ssl_outputs(s);
         for (Segment& g : s->segs) (void)hipFree(g.dev);
     }
     delete s;
@@ -260,36 +380,22 @@ int m0_rowstore_info(m0_rowstore* s, int64_t* info) {
 
 int m0_rowstore_batch(m0_rowstore* s, const int64_t* rows, const uint8_t* kinds, int B, float* planes, float* pi, float* z, uint8_t* mask,
                       int outputs_on_device, void* stream) {
-    if (!s) return invalid("null handle");
-    std::lock_guard<std::mutex> lk(s->mu);
-    if (!s->hs.ok()) return m0_hip_error(s->hs);
-    if (const int rc = check_batch(rows, kinds, B, planes, pi, z, mask, s->with_mask)) return rc;
-    if (outputs_on_device && !s->on_device()) return invalid("a host store fills host memory");
-    if (outputs_on_device && (((uintptr_t)planes | (uintptr_t)pi | (uintptr_t)mask) & 15) != 0) return invalid("device outputs must lie on 16-byte boundaries");
-    if (s->on_device()) return device_batch(s, rows, kinds, B, planes, pi, z, mask, outputs_on_device != 0, (hipStream_t)stream);
-    s->refs.resize((size_t)B);
-    int64_t missing = 0;
-    if (!resolve(s, rows, kinds, B, s->refs.data(), &missing)) return invalid("row " + std::to_string(missing) + " is not resident");
-    batch_rows_host(s->refs.data(), B, planes, pi, z, mask);
-    return M0_OK;
+    return store_batch(s, rows, kinds, B, planes, pi, z, mask, SslOut(), outputs_on_device, stream);
+}
+
+int m0_rowstore_batch_ssl(m0_rowstore* s, const int64_t* rows, const uint8_t* kinds, int B, float* planes, float* pi, float* z,
+                          uint8_t* mask, float* ssl, int32_t* ssl_status, int outputs_on_device, void* stream) {
+    return store_batch(s, rows, kinds, B, planes, pi, z, mask, SslOut{true, ssl, ssl_status}, outputs_on_device, stream);
 }
 
 int m0_rowstore_batch_host(const m0_rowpack_arrays* in, const int64_t* rows, const uint8_t* kinds, int B, float* planes, float* pi,
                            float* z, uint8_t* mask) {
-    if (!in) return invalid("null argument");
-    if (B <= 0) return invalid("batch must be positive");
-    SegBlock block;
-    const std::string why = build_segment(in, mask != nullptr, block);
-    if (!why.empty()) return invalid("packed rows: " + why);
-    if (const int rc = check_batch(rows, kinds, B, planes, pi, z, mask, mask != nullptr)) return rc;
-    const SegView* view = reinterpret_cast<const SegView*>(block.bytes.data());
-    std::vector<RowRef> refs((size_t)B);
-    for (int b = 0; b < B; ++b) {
-        if (rows[b] < 0 || rows[b] >= in->n) return invalid("row " + std::to_string(rows[b]) + " is not one of the packed rows");
-        refs[b] = RowRef{view, (int32_t)rows[b], kinds ? (int32_t)kinds[b] : M0_AUG_NONE};
-    }
-    batch_rows_host(refs.data(), B, planes, pi, z, mask);
-    return M0_OK;
+    return arrays_batch(in, rows, kinds, B, planes, pi, z, mask, SslOut());
+}
+
+int m0_rowstore_batch_ssl_host(const m0_rowpack_arrays* in, const int64_t* rows, const uint8_t* kinds, int B, float* planes,
+                               float* pi, float* z, uint8_t* mask, float* ssl, int32_t* ssl_status) {
+    return arrays_batch(in, rows, kinds, B, planes, pi, z, mask, SslOut{true, ssl, ssl_status});
 }
 
 int m0_rowstore_bench(int hip_device, int B, int iters, float* fused_us, float* chain_us, double* dense_bytes) {
@@ -297,41 +403,9 @@ int m0_rowstore_bench(int hip_device, int B, int iters, float* fused_us, float* 
     HipStatus hs;
     if (const int rc = m0_select_device(hs, hip_device)) return rc;
     const size_t N = (size_t)B;
-    std::vector<float> planes, pi, z(N, 0.f);
-    std::vector<uint8_t> mask;
-    m0_rowpack_bench_rows(N, planes, pi, mask);
-    // their packed form: the sizes first, then the arrays
-    int64_t sizes[3];
-    m0_rowpack_arrays a = {};
-    a.n = B;
-    (void)pack_host(planes.data(), pi.data(), z.data(), mask.data(), N, &a, sizes);
-    std::vector<m0_rowpack_pos> hq(N);
-    std::vector<int64_t> hpo(N + 1), hmo(N + 1);
-    std::vector<uint16_t> hidx((size_t)sizes[0]);
-    std::vector<float> hval((size_t)sizes[0]), hz(N);
-    a.pi_n = sizes[0]; a.pos = hq.data(); a.z = hz.data(); a.pi_off = hpo.data(); a.mask_off = hmo.data(); a.pi_idx = hidx.data();
-    a.pi_val = hval.data();
-    if (sizes[1] != 0 || sizes[2] != 0 || !pack_host(planes.data(), pi.data(), z.data(), mask.data(), N, &a, sizes).empty())
-        return invalid("the bench rows did not pack as positions with legal masks");
-    std::vector<Pos> positions;
-    std::vector<int32_t> raw_slot;
-    const std::string why = check_arrays(&a, positions, raw_slot);
-    if (!why.empty()) return invalid(why);
-    // the store and the references of a shuffled batch of its rows; the chain's inputs beside it
-    struct Store {
-        m0_rowstore* s;
-        ~Store() { m0_rowstore_destroy(s); }
-    } store{m0_rowstore_create(hip_device, 1)};
-    int64_t first = 0;
-    if (!store.s) return M0_ERR_HIP;
-    if (const int rc = m0_rowstore_append(store.s, &a, &first)) return rc;
-    std::vector<RowRef> order(N), shuffled(N);
-    std::vector<uint8_t> hk(N);
-    BenchRng rng;
-    for (size_t i = 0; i < N; ++i) { hk[i] = (uint8_t)(i % m0aug::KINDS); order[i] = RowRef{store.s->segs.back().view(), (int32_t)i, (int32_t)hk[i]}; }
-    shuffled = order;
-    for (size_t i = N - 1; i > 0; --i) std::swap(shuffled[i].row, shuffled[rng.next() % (i + 1)].row);
-    DevBuf<RowRef> dorder, dshuffled;
+    BenchRows r;
+    if (const int rc = r.build(hs, hip_device, B)) return rc;
+    // the chain's inputs beside the store
     DevBuf<Pos> dpos;
     DevBuf<m0_rowpack_pos> dq;
     DevBuf<int64_t> dpo, dmo;
@@ -339,15 +413,14 @@ int m0_rowstore_bench(int hip_device, int B, int iters, float* fused_us, float* 
     DevBuf<int32_t> dslot;
     DevBuf<uint8_t> dk, um, cm, fm;
     DevBuf<float> dval, upl, upi, cpl, cpi, fpl, fpi, fz;
-    dorder.upload(hs, order.data(), N); dshuffled.upload(hs, shuffled.data(), N);
-    dpos.upload(hs, positions.data(), N); dq.upload(hs, hq.data(), N);
-    dpo.upload(hs, hpo.data(), N + 1); dmo.upload(hs, hmo.data(), N + 1);
-    didx.upload(hs, hidx.data(), hidx.size()); dval.upload(hs, hval.data(), hval.size()); dmidx.upload(hs, nullptr, 0);
-    dslot.upload(hs, raw_slot.data(), N); dk.upload(hs, hk.data(), N);
-    if (!hs.ok() || !upl.alloc(hs, N * PLANE_FLOATS) || !upi.alloc(hs, N * COLS) || !um.alloc(hs, N * COLS) || !cpl.alloc(hs, N * PLANE_FLOATS) ||
+    dpos.upload(hs, r.positions.data(), N); dq.upload(hs, r.hq.data(), N);
+    dpo.upload(hs, r.hpo.data(), N + 1); dmo.upload(hs, r.hmo.data(), N + 1);
+    didx.upload(hs, r.hidx.data(), r.hidx.size()); dval.upload(hs, r.hval.data(), r.hval.size()); dmidx.upload(hs, nullptr, 0);
+    dslot.upload(hs, r.raw_slot.data(), N); dk.upload(hs, r.hk.data(), N);
+    if (!hs.ok() ||!upl.alloc(hs, N * PLANE_FLOATS) || !upi.alloc(hs, N * COLS) || !um.alloc(hs, N * COLS) || !cpl.alloc(hs, N * PLANE_FLOATS) ||
         !cpi.alloc(hs, N * COLS) || !cm.alloc(hs, N * COLS) || !fpl.alloc(hs, N * PLANE_FLOATS) || !fpi.alloc(hs, N * COLS) ||
         !fm.alloc(hs, N * COLS) || !fz.alloc(hs, N)) return m0_hip_error(hs, "hipMalloc or upload failed");
-    const RowRef* refs = dorder.p;
+    const RowRef* refs = r.dorder.p;
     auto fused = [&]() { return M0_HIP(hs, launch_batch_rows(refs, B, fpl.p, fpi.p, fz.p, fm.p, nullptr)); };
     auto chain = [&]() {
         M0_HIP(hs, launch_encode_positions(dpos.p, B, upl.p, nullptr, um.p, nullptr, nullptr, nullptr, nullptr));
@@ -366,7 +439,7 @@ int m0_rowstore_bench(int hip_device, int B, int iters, float* fused_us, float* 
         if (!hs.ok()) return m0_hip_error(hs, "row store bench failed");
         if (memcmp(got.data(), want.data(), o.bytes) != 0) return invalid("the fused batch is not the chain's");
     }
-    refs = dshuffled.p;
+    refs = r.dshuffled.p;
     fused();
     for (int run = 0; run < 2; ++run) {
         fused_us[run] = m0_time_iterations(hs, nullptr, iters, fused) * 1000.f;
@@ -374,6 +447,47 @@ int m0_rowstore_bench(int hip_device, int B, int iters, float* fused_us, float* 
     }
     if (!M0_HIP(hs, hipDeviceSynchronize())) return m0_hip_error(hs, "row store bench failed");
     *dense_bytes = (double)B * (PLANE_FLOATS * 4.0 + COLS * 4.0 + COLS + 4.0);
+    return M0_OK;
+}
+
+int m0_rowstore_bench_ssl(int hip_device, int B, int iters, float* fused_us, float* chain_us, double* dense_bytes) {
+    if (B <= 0 || iters <= 0 || !fused_us || !chain_us || !dense_bytes) return invalid("invalid argument");
+    HipStatus hs;
+    if (const int rc = m0_select_device(hs, hip_device)) return rc;
+    const size_t N = (size_t)B;
+    BenchRows r;
+    if (const int rc = r.build(hs, hip_device, B)) return rc;
+    // one set of outputs for the launch with the maps (f), one for the launch without them and the targets kernel behind it (c)
+    DevBuf<uint8_t> fm, cm;
+    DevBuf<float> fpl, fpi, fz, fssl, cpl, cpi, cz, cssl;
+    DevBuf<int32_t> fst, cst;
+    if (!fpl.alloc(hs, N * PLANE_FLOATS) || !fpi.alloc(hs, N * COLS) || !fm.alloc(hs, N * COLS) || !fz.alloc(hs, N) || !fssl.alloc(hs, N * SSL_FLOATS) ||
+        !fst.alloc(hs, N) || !cpl.alloc(hs, N * PLANE_FLOATS) || !cpi.alloc(hs, N * COLS) || !cm.alloc(hs, N * COLS) || !cz.alloc(hs, N) ||
+        !cssl.alloc(hs, N * SSL_FLOATS) || !cst.alloc(hs, N)) return m0_hip_error(hs, "hipMalloc failed");
+    const RowRef* refs = r.dshuffled.p;
+    auto fused = [&]() { return M0_HIP(hs, launch_batch_rows_ssl(refs, B, fpl.p, fpi.p, fz.p, fm.p, fssl.p, fst.p, nullptr)); };
+    auto chain = [&]() {
+        M0_HIP(hs, launch_batch_rows(refs, B, cpl.p, cpi.p, cz.p, cm.p, nullptr));
+        return M0_HIP(hs, launch_ssl_targets_planes(cpl.p, B, cssl.p, cst.p, nullptr));
+    };
+    // the warm-up is the check: both give the same bytes (every row is a position, so the targets kernel writes every map)
+    fused(); chain();
+    std::vector<uint8_t> got(N * COLS * sizeof(float)), want(N * COLS * sizeof(float));
+    const struct { const void* f; const void* c; size_t bytes; } outs[6] = {
+        {fpl.p, cpl.p, N * PLANE_FLOATS * sizeof(float)}, {fpi.p, cpi.p, N * COLS * sizeof(float)}, {fm.p, cm.p, N * COLS},
+        {fz.p, cz.p, N * sizeof(float)}, {fssl.p, cssl.p, N * SSL_FLOATS * sizeof(float)}, {fst.p, cst.p, N * sizeof(int32_t)}};
+    for (const auto& o : outs) {
+        M0_HIP(hs, hipMemcpy(got.data(), o.f, o.bytes, hipMemcpyDeviceToHost));
+        M0_HIP(hs, hipMemcpy(want.data(), o.c, o.bytes, hipMemcpyDeviceToHost));
+        if (!hs.ok()) return m0_hip_error(hs, "row store bench failed");
+        if (memcmp(got.data(), want.data(), o.bytes) != 0) return invalid("the batch with the maps is not the chain's");
+    }
+    for (int run = 0; run < 2; ++run) {
+        fused_us[run] = m0_time_iterations(hs, nullptr, iters, fused) * 1000.f;
+        chain_us[run] = m0_time_iterations(hs, nullptr, iters, chain) * 1000.f;
+    }
+    if (!M0_HIP(hs, hipDeviceSynchronize())) return m0_hip_error(hs, "row store bench failed");
+    *dense_bytes = (double)B * (PLANE_FLOATS * 4.0 + COLS * 4.0 + COLS + 4.0 + SSL_FLOATS * 4.0 + 4.0);
     return M0_OK;
 }
 

@@ -10,6 +10,8 @@ the ids and kinds of a batch cross from the host.
     store = DeviceReplay(device="host")                                      # the same calls on a machine without a GPU
     first = store.append(packed)                                             # range of the new rows' ids
     s, pi, z, legal_mask = store.batch(ids, kinds)                           # numpy
+    s, pi, z, legal_mask, ssl, ssl_status = store.batch(ids, kinds, ssl=True)   # with the SSL target maps of s
+    targets = ssl_targets(ssl)                                               # {"piece": [B,13,8,8], "threat": [B,8,8], ...}
 
     python -m matrix0_amd.device_replay info DIR
 
@@ -26,7 +28,7 @@ from typing import Iterator, List, Optional, Sequence
 import numpy as np
 
 from . import _lib, rowpack
-from ._abi import AUGMENT_KINDS, POLICY_SIZE, ROWSTORE_HOST, ROWSTORE_INFO
+from ._abi import AUGMENT_KINDS, BATCH_SSL_CH, POLICY_SIZE, ROWSTORE_HOST, ROWSTORE_INFO
 from .rowpack import DENSE_ROW_BYTES, PLANES, PackedRows
 
 AUGMENT_MODES = ("trainer",) + tuple(AUGMENT_KINDS)
@@ -135,20 +137,28 @@ class DeviceReplay:
             kinds = np.ascontiguousarray(kinds, dtype=np.uint8)
         return rows, kinds
 
-    def batch(self, rows, kinds=None):
+    def batch(self, rows, kinds=None, ssl: bool = False):
         """numpy (s f32 [B,19,8,8], pi f32 [B,4672], z f32 [B], legal_mask u8 [B,4672]) of the rows with these ids under these
-        kinds (None: untransformed; one number: every row), or (s, pi, z) for a store without masks."""
+        kinds (None: untransformed; one number: every row), or (s, pi, z) for a store without masks.  ssl=True appends the SSL
+        target maps of s (ssl f32 [B,17,8,8]) and their status (ssl_status i32 [B]: 1 for a row whose planes give no targets,
+        whose maps are zero), written by the same launch (include/m0_batch_ssl.h; ssl_targets splits the maps by task)."""
         rows, kinds = self._ids_kinds(rows, kinds)
         B = len(rows)
         s, pi, z = np.empty((B, PLANES, 8, 8), np.float32), np.empty((B, POLICY_SIZE), np.float32), np.empty(B, np.float32)
         mask = np.empty((B, POLICY_SIZE), np.uint8) if self.with_mask else None
-        _lib.check(self._L.m0_rowstore_batch(self._h, _lib.ptr(rows), _lib.ptr(kinds), B, _lib.ptr(s), _lib.ptr(pi), _lib.ptr(z),
-                                             _lib.ptr(mask), 0, None), "m0_rowstore_batch")
-        return (s, pi, z, mask) if self.with_mask else (s, pi, z)
+        got = (s, pi, z, mask) if self.with_mask else (s, pi, z)
+        if not ssl:
+            _lib.check(self._L.m0_rowstore_batch(self._h, _lib.ptr(rows), _lib.ptr(kinds), B, _lib.ptr(s), _lib.ptr(pi), _lib.ptr(z),
+                                                 _lib.ptr(mask), 0, None), "m0_rowstore_batch")
+            return got
+        maps, status = np.empty((B, BATCH_SSL_CH, 8, 8), np.float32), np.empty(B, np.int32)
+        _lib.check(self._L.m0_rowstore_batch_ssl(self._h, _lib.ptr(rows), _lib.ptr(kinds), B, _lib.ptr(s), _lib.ptr(pi), _lib.ptr(z),
+                                                 _lib.ptr(mask), _lib.ptr(maps), _lib.ptr(status), 0, None), "m0_rowstore_batch_ssl")
+        return (*got, maps, status)
 
-    def batch_torch(self, rows, kinds=None, out=None):
+    def batch_torch(self, rows, kinds=None, out=None, ssl: bool = False):
         """The same batch as torch tensors on cuda:<device>, filled on torch's current stream without a wait: work enqueued on
-        that stream afterwards sees them filled.  out: the tensors of an earlier call, to be written again."""
+        that stream afterwards sees them filled.  out: the tensors of an earlier call (with the same ssl), to be written again."""
         import torch
         if self.device == ROWSTORE_HOST:
             raise ValueError("a host store has no device tensors: use batch()")
@@ -158,16 +168,20 @@ class DeviceReplay:
         want = [((B, PLANES, 8, 8), torch.float32), ((B, POLICY_SIZE), torch.float32), ((B,), torch.float32)]
         if self.with_mask:
             want.append(((B, POLICY_SIZE), torch.uint8))
+        if ssl:
+            want += [((B, BATCH_SSL_CH, 8, 8), torch.float32), ((B,), torch.int32)]
         if out is None:
             out = tuple(torch.empty(shape, dtype=dtype, device=dev) for shape, dtype in want)
         out = tuple(out)
         if len(out) != len(want) or any(tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous()
                                         for t, (shape, dtype) in zip(out, want)):
             raise ValueError(f"out must be contiguous tensors on {dev} of {want}")
-        ptrs = [C.c_void_p(t.data_ptr()) for t in out] + ([] if self.with_mask else [None])
+        ptrs = [C.c_void_p(t.data_ptr()) for t in out]
+        if not self.with_mask:
+            ptrs.insert(3, None)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(self._L.m0_rowstore_batch(self._h, _lib.ptr(rows), _lib.ptr(kinds), B, *ptrs, 1, C.c_void_p(stream)),
-                   "m0_rowstore_batch")
+        name = "m0_rowstore_batch_ssl" if ssl else "m0_rowstore_batch"
+        _lib.check(getattr(self._L, name)(self._h, _lib.ptr(rows), _lib.ptr(kinds), B, *ptrs, 1, C.c_void_p(stream)), name)
         return out
 
     def plan(self, epoch: int, batch_size: int, seed: int = 0, augment: str = "trainer", rotate180: bool = True):
@@ -184,10 +198,11 @@ class DeviceReplay:
         return ids[: n * int(batch_size)].reshape(n, int(batch_size)), np.array(kinds, np.uint8)
 
     def batches(self, batch_size: int, epochs: Optional[int] = None, seed: int = 0, augment: str = "trainer", rotate180: bool = True,
-                torch: bool = False) -> Iterator[tuple]:
+                torch: bool = False, ssl: bool = False) -> Iterator[tuple]:
         """Full batches, epoch after epoch (None: without end): (s, pi, z, legal_mask, ids, kind) -- without legal_mask for a store
-        without masks -- as batch() or, with torch=True, batch_torch() gives them.  Batch j of epoch e is a function of (seed, e, j)
-        and the resident rows alone (plan); ids and kind say what it holds, so a run can be replayed."""
+        without masks, and with ssl=True (s, pi, z, legal_mask, ssl, ssl_status, ids, kind) -- as batch() or, with torch=True,
+        batch_torch() gives them.  Batch j of epoch e is a function of (seed, e, j) and the resident rows alone (plan); ids and
+        kind say what it holds, so a run can be replayed."""
         if int(batch_size) <= 0:
             raise ValueError("batch_size must be positive")
         epoch = 0
@@ -196,9 +211,17 @@ class DeviceReplay:
             if len(ids) == 0:
                 return
             for rows, kind in zip(ids, kinds):
-                got = self.batch_torch(rows, int(kind)) if torch else self.batch(rows, int(kind))
+                got = self.batch_torch(rows, int(kind), ssl=ssl) if torch else self.batch(rows, int(kind), ssl=ssl)
                 yield (*got, rows, int(kind))
             epoch += 1
+
+
+def ssl_targets(ssl) -> dict:
+    """The maps of a batch (numpy array or torch tensor [B,17,8,8]) as the trainer's dictionary: piece [B,13,8,8], threat, pin, fork
+    and control [B,8,8], views of `ssl` without a copy (_lib.split_ssl)."""
+    if ssl.ndim != 4 or tuple(ssl.shape[1:]) != (BATCH_SSL_CH, 8, 8):
+        raise ValueError(f"ssl must be [B,{BATCH_SSL_CH},8,8]")
+    return _lib.split_ssl(ssl)
 
 
 def info(base_dir, sources: Sequence[str] = ("selfplay", ""), window_rows: Optional[int] = None) -> dict:
