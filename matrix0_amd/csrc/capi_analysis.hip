@@ -40,7 +40,7 @@ static void answer(Analysis& a, const m0_analysis_result& r, std::vector<int32_t
     a.done_proof.push_back(proof);
 }
 // the result kernel's proof output, where the engine runs the proof search
-static m0_proof_lines* proof_out(const m0_selfplay* sp) { return sp->tc.proof ? sp->an->proof_dev : nullptr; }
+static m0_proof_lines* proof_out(const m0_selfplay* sp) { return is_proof(sp->tc) ? sp->an->proof_dev : nullptr; }
 // the front of the answered results leaves: its proofs are what m0_analysis_last_proof returns from now on
 static void pop_done(Analysis& a) {
     a.last_proof = a.done_proof.front();
@@ -415,7 +415,7 @@ int m0_analysis_poll_visits(m0_selfplay* sp, m0_analysis_result* out, int32_t* n
 int m0_analysis_last_proof(m0_selfplay* sp, m0_proof_lines* out) {
     M0_ENGINE_CALL(sp, "m0_analysis_last_proof", KIND_ANALYSIS, false);
     if (!out) { m0_set_error("null argument"); return M0_ERR_INVALID; }
-    if (!sp->tc.proof) { m0_set_error("m0_analysis_last_proof: the proof search is not set on this engine"); return M0_ERR_STATE; }
+    if (!is_proof(sp->tc)) { m0_set_error("m0_analysis_last_proof: the proof search is not set on this engine"); return M0_ERR_STATE; }
     *out = sp->an->last_proof;
     return M0_OK;
 }

@@ -11,28 +11,20 @@ extern "C" {
 int m0_selfplay_set_budget(m0_selfplay* sp, const m0_budget_cfg* cfg) {
     if (!sp || !cfg) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     M0_ENGINE_CALL(sp, "m0_selfplay_set_budget", KIND_SELFPLAY, false);
-    if (sp->stats.games_started != 0 || sp->search_begun) {
-        m0_set_error("set the self-play budget mix before the first step or search");
-        return M0_ERR_STATE;
-    }
+    if (const int rc = mode_settable(sp, MODE_BUDGET, "the self-play budget mix")) return rc;
     if (const char* bad = budget_bad_cfg(cfg)) { m0_set_error(bad); return M0_ERR_INVALID; }
-    if (sp->cfg.tt_merge) { m0_set_error("the self-play budget mix does not go with compat.tt_merge"); return M0_ERR_INVALID; }
-    if (sp->tc.gumbel) { m0_set_error("the self-play budget mix does not go with the Gumbel root search"); return M0_ERR_INVALID; }
-    if (sp->tc.proof) { m0_set_error("the self-play budget mix does not go with the proof search"); return M0_ERR_INVALID; }
-    sp->tc.budget = 1;
+    sp->tc.mode = MODE_BUDGET;
     sp->tc.forced_k = cfg->forced_k;
     sp->budget = *cfg;
     return M0_OK;
 }
 
 int m0_search_budget_result(m0_selfplay* sp, int g, int32_t* pruned_n, double* pi, int* forced_descents) {
-    if (!sp || g < 0 || g >= sp->G) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
     M0_ENGINE_CALL(sp, "m0_search_budget_result", KIND_SELFPLAY, true);
-    if (!sp->tc.budget) { m0_set_error("m0_search_budget_result: the self-play budget mix is not set on this engine"); return M0_ERR_STATE; }
+    bool finished;
+    if (const int rc = mode_result_fetch(sp, g, MODE_BUDGET, "m0_search_budget_result", &finished)) return rc;
     if (forced_descents) *forced_descents = -1;
-    if (!sp->hg[g].finished) return M0_OK;
-    if (!M0_HIP(sp->hip, hipMemcpy(&sp->hres[g], sp->d.results + g, sizeof(RootResult), hipMemcpyDeviceToHost)))
-        return m0_hip_error(sp->hip, "result copy failed");
+    if (!finished) return M0_OK;
     const RootResult& R = sp->hres[g];
     const bool prune = sp->budget.prune_targets && sp->budget.forced_k > 0.0;
     budget_prune(R.nchild, R.child_prior, R.child_q, R.child_n, R.root_n, cpuct_at_root(sp->tc), prune ? sp->budget.forced_k : 0.0,
@@ -53,7 +45,7 @@ int m0_game_record_budget(const m0_game_record* rec, const uint8_t** full, const
 int m0_selfplay_budget_stats(m0_selfplay* sp, uint64_t* out) {
     if (!sp || !out) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     M0_ENGINE_CALL(sp, "m0_selfplay_budget_stats", KIND_SELFPLAY, false);
-    if (!sp->tc.budget) { m0_set_error("m0_selfplay_budget_stats: the self-play budget mix is not set on this engine"); return M0_ERR_STATE; }
+    if (!is_budget(sp->tc)) { m0_set_error("m0_selfplay_budget_stats: the self-play budget mix is not set on this engine"); return M0_ERR_STATE; }
     uint64_t forced = 0;
     for (const GameDev& g : sp->hg) forced += g.forced_descents;      // the mirror the last step copied
     out[0] = sp->budget_full; out[1] = sp->budget_fast; out[2] = forced; out[3] = sp->budget_pruned;

@@ -10,18 +10,12 @@ extern "C" {
 int m0_selfplay_set_gumbel(m0_selfplay* sp, const m0_gumbel_cfg* cfg) {
     if (!sp || !cfg) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     M0_ENGINE_CALL(sp, "m0_selfplay_set_gumbel", KIND_SELFPLAY, true);
-    if (sp->stats.games_started != 0 || sp->search_begun) {
-        m0_set_error("set the Gumbel root search before the first step or search");
-        return M0_ERR_STATE;
-    }
+    if (const int rc = mode_settable(sp, MODE_GUMBEL, "the Gumbel root search")) return rc;
     if (cfg->max_considered < 1 || cfg->max_considered > M0_MAX_CHILDREN) {
         m0_set_error("max_considered must be in 1 .. 256");
         return M0_ERR_INVALID;
     }
     if (const char* bad = gumbel_bad_constants(cfg)) { m0_set_error(bad); return M0_ERR_INVALID; }
-    if (sp->cfg.tt_merge) { m0_set_error("the Gumbel root search does not go with compat.tt_merge"); return M0_ERR_INVALID; }
-    if (sp->tc.proof) { m0_set_error("the Gumbel root search does not go with the proof search"); return M0_ERR_INVALID; }
-    if (sp->tc.budget) { m0_set_error("the Gumbel root search does not go with the self-play budget mix"); return M0_ERR_INVALID; }
     if (!sp->d.gumbel_gl) {
         double* gl = dalloc<double>(sp, (size_t)sp->G * M0_MAX_CHILDREN);
         GumbelResult* res = dalloc<GumbelResult>(sp, sp->G);
@@ -31,21 +25,18 @@ int m0_selfplay_set_gumbel(m0_selfplay* sp, const m0_gumbel_cfg* cfg) {
         sp->d.gumbel_results = res;
         sp->hgres.resize(sp->G);
     }
-    sp->tc.gumbel = 1;
+    sp->tc.mode = MODE_GUMBEL;
     sp->tc.gumbel_cfg = *cfg;
     return M0_OK;
 }
 
 int m0_search_gumbel_result(m0_selfplay* sp, int g, int* pick, double* v_mix, double* pi, double* gl, int* miss) {
-    if (!sp || g < 0 || g >= sp->G) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
     M0_ENGINE_CALL(sp, "m0_search_gumbel_result", KIND_SELFPLAY, true);
-    if (!sp->tc.gumbel) { m0_set_error("m0_search_gumbel_result: the Gumbel root search is not set on this engine"); return M0_ERR_STATE; }
+    bool finished;
+    if (const int rc = mode_result_fetch(sp, g, MODE_GUMBEL, "m0_search_gumbel_result", &finished)) return rc;
     if (miss) *miss = sp->hg[g].gumbel_miss;
     if (pick) *pick = -1;
-    if (!sp->hg[g].finished) return M0_OK;
-    if (!M0_HIP(sp->hip, hipMemcpy(&sp->hres[g], sp->d.results + g, sizeof(RootResult), hipMemcpyDeviceToHost)) ||
-        !M0_HIP(sp->hip, hipMemcpy(&sp->hgres[g], sp->d.gumbel_results + g, sizeof(GumbelResult), hipMemcpyDeviceToHost)))
-        return m0_hip_error(sp->hip, "result copy failed");
+    if (!finished) return M0_OK;
     const GumbelResult& R = sp->hgres[g];
     const int k = sp->hres[g].nchild;
     if (pick) *pick = R.pick;

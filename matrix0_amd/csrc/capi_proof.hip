@@ -10,18 +10,13 @@ extern "C" {
 
 int m0_selfplay_set_proof(m0_selfplay* sp, int on) {
     M0_ENGINE_CALL(sp, "m0_selfplay_set_proof", KIND_ANY, true);
-    if (sp->stats.games_started != 0 || sp->stats.steps != 0 || sp->search_begun) {
-        m0_set_error("set the proof search before the first step or search");
-        return M0_ERR_STATE;
-    }
     if (sp->kind == EngineKind::SelfPlay && sp->net) {
         m0_set_error("m0_selfplay_set_proof: not on a self-play engine that plays games with its own network "
                      "(searches that end early would change the policy targets)");
         return M0_ERR_STATE;
     }
-    if (sp->cfg.tt_merge) { m0_set_error("the proof search does not go with compat.tt_merge"); return M0_ERR_INVALID; }
-    if (sp->tc.gumbel) { m0_set_error("the proof search does not go with the Gumbel root search"); return M0_ERR_INVALID; }
-    if (sp->tc.budget) { m0_set_error("the proof search does not go with the self-play budget mix"); return M0_ERR_INVALID; }
+    // turning it off asks the same: an engine in another mode answers that the proof search does not go with it
+    if (const int rc = mode_settable(sp, MODE_PROOF, "the proof search")) return rc;
     if (on && !sp->d.t.proof) {
         int16_t* proof = dalloc<int16_t>(sp, (size_t)sp->G * 2 * sp->cap);       // zeroed: nothing is proven
         ProofResult* res = dalloc<ProofResult>(sp, sp->G);
@@ -37,21 +32,18 @@ int m0_selfplay_set_proof(m0_selfplay* sp, int on) {
             sp->an->hproof.resize(sp->G);
         }
     }
-    sp->tc.proof = on ? 1 : 0;
+    sp->tc.mode = on ? MODE_PROOF : MODE_PUCT;
     return M0_OK;
 }
 
 int m0_search_proof_result(m0_selfplay* sp, int g, int* state, int* plies, int32_t* child_state, int32_t* child_plies, int* pick) {
-    if (!sp || g < 0 || g >= sp->G) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
     M0_ENGINE_CALL(sp, "m0_search_proof_result", KIND_GAMES, true);
-    if (!sp->tc.proof) { m0_set_error("m0_search_proof_result: the proof search is not set on this engine"); return M0_ERR_STATE; }
+    bool finished;
+    if (const int rc = mode_result_fetch(sp, g, MODE_PROOF, "m0_search_proof_result", &finished)) return rc;
     if (pick) *pick = -1;
     if (state) *state = M0_PROOF_NONE;
     if (plies) *plies = 0;
-    if (!sp->hg[g].finished) return M0_OK;
-    if (!M0_HIP(sp->hip, hipMemcpy(&sp->hres[g], sp->d.results + g, sizeof(RootResult), hipMemcpyDeviceToHost)) ||
-        !M0_HIP(sp->hip, hipMemcpy(&sp->hpres[g], sp->d.proof_results + g, sizeof(ProofResult), hipMemcpyDeviceToHost)))
-        return m0_hip_error(sp->hip, "result copy failed");
+    if (!finished) return M0_OK;
     const ProofResult& R = sp->hpres[g];
     const int k = sp->hres[g].nchild;
     if (pick) *pick = R.pick;

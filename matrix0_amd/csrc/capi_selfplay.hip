@@ -18,11 +18,8 @@ static void fill_tree_cfg(const m0_selfplay_cfg& c, bool match, TreeCfg& t) {
     t.virtual_loss_active = c.virtual_loss_active; t.leaves_per_step = c.inference_batch_size;
     t.tt_merge = c.tt_merge; t.raw_legal_priors = c.raw_legal_priors; t.max_children = c.max_children;
     t.min_child_prior = c.min_child_prior;
-    t.gumbel = 0;                          // m0_selfplay_set_gumbel turns it on
-    t.gumbel_cfg = m0_gumbel_cfg{0, 0.0, 0.0};
-    t.proof = 0;                           // m0_selfplay_set_proof turns it on
-    t.budget = 0;                          // m0_selfplay_set_budget turns it on
-    t.forced_k = 0.0;
+    t.mode = MODE_PUCT;                    // m0_selfplay_set_gumbel / _set_proof / _set_budget set another, with its parameters
+    t.gumbel_cfg = m0_gumbel_cfg{0, 0.0, 0.0}; t.forced_k = 0.0;
     // the cached payload is the LEGAL logits: only the legal-softmax expansion can be served from it
     t.eval_cache = ((match ? c.arena_eval_cache : c.eval_cache) && c.legal_softmax && !c.raw_legal_priors && !c.tt_merge) ? 1 : 0;
 }
@@ -447,7 +444,7 @@ int m0_search_advance(m0_selfplay* sp, int g, int slot, int sims, int dirichlet)
     const RootResult& R = sp->hres[g];
     if (slot < 0 || slot >= R.nchild) { m0_set_error("child slot out of range"); return M0_ERR_INVALID; }
     sp->games[g].play(R.child_mv[slot]);
-    const bool fresh = sp->cfg.fresh_tree_per_move || sp->cfg.tt_merge || sp->tc.gumbel;
+    const bool fresh = sp->cfg.fresh_tree_per_move || sp->cfg.tt_merge || is_gumbel(sp->tc);
     begin_search(sp, g, sims, dirichlet != 0, fresh ? ROOT_FRESH : slot);
     return apply_advances(sp);
 }

@@ -5,6 +5,7 @@
 // The engine's C-ABI (creation, step, poll, external evaluators, split-step search) is capi_selfplay.hip.
 #include <math.h>
 #include <string.h>
+#include <algorithm>
 #include <atomic>
 #include "selfplay_engine.h"
 #include "tb.h"
@@ -49,15 +50,46 @@ static void push_hist(m0_selfplay* sp, int slot, const RepWindow& w) {
     if (n > 0) M0_HIP(sp->hip, hipMemcpyAsync(sp->d.hist + (size_t)slot * M0_HIST_CAP, src, (size_t)n * 8, hipMemcpyHostToDevice, sp->stream));
 }
 
+static const char* const MODE_NAMES[] = {"the PUCT search", "the Gumbel root search", "the proof search", "the self-play budget mix"};
+int mode_settable(m0_selfplay* sp, SearchMode wanted, const char* name) {
+    // stats.steps counts for the engines that start no games (analysis); where games are played one has started before a step ends
+    if (sp->stats.games_started != 0 || sp->stats.steps != 0 || sp->search_begun) {
+        m0_set_error(std::string("set ") + name + " before the first step or search"); return M0_ERR_STATE;
+    }
+    const char* other = sp->cfg.tt_merge ? "compat.tt_merge"
+                        : sp->tc.mode != MODE_PUCT && sp->tc.mode != wanted ? MODE_NAMES[sp->tc.mode] : nullptr;
+    if (other) { m0_set_error(std::string(name) + " does not go with " + other); return M0_ERR_INVALID; }
+    return M0_OK;
+}
+// The results of slots [first, first + count), device -> host mirrors: RootResult and what the engine's mode writes beside it when a
+// search finishes, described by its device array, host mirror and element size (PUCT and the budget mix write nothing more).
+static bool results_d2h(m0_selfplay* sp, int first, int count) {
+    struct { const void* dev; void* host; size_t size; } m = {nullptr, nullptr, 0};
+    if (is_gumbel(sp->tc)) m = {sp->d.gumbel_results, sp->hgres.data(), sizeof(GumbelResult)};
+    if (is_proof(sp->tc)) m = {sp->d.proof_results, sp->hpres.data(), sizeof(ProofResult)};
+    return M0_HIP(sp->hip, hipMemcpy(&sp->hres[first], sp->d.results + first, sizeof(RootResult) * count, hipMemcpyDeviceToHost)) &&
+           (!m.size || M0_HIP(sp->hip, hipMemcpy((char*)m.host + first * m.size, (const char*)m.dev + first * m.size, m.size * count,
+                                                 hipMemcpyDeviceToHost)));
+}
+int mode_result_fetch(m0_selfplay* sp, int g, SearchMode mode, const char* what, bool* finished) {
+    *finished = false;
+    if (g < 0 || g >= sp->G) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
+    if (sp->tc.mode != mode) { m0_set_error(std::string(what) + ": " + MODE_NAMES[mode] + " is not set on this engine"); return M0_ERR_STATE; }
+    if (!sp->hg[g].finished) return M0_OK;
+    if (!results_d2h(sp, g, 1)) return m0_hip_error(sp->hip, "result copy failed");
+    *finished = true;
+    return M0_OK;
+}
+
 // configure a search on slot for the host position (MCTS.run prologue, mcts.py:342-396)
 static void arm_search(m0_selfplay* sp, int slot, const Pos& pos, const RepWindow& win, int sims, bool dirichlet, bool fresh) {
     GameDev& g = sp->hg[slot];
     g.root_pos = pos;
     g.active = 1; g.sims_done = 0; g.sims_target = sims;
-    g.need_dirichlet = dirichlet && !sp->tc.gumbel ? 1 : 0;     // the Gumbel root takes no Dirichlet noise
+    g.need_dirichlet = dirichlet && !is_gumbel(sp->tc) ? 1 : 0;    // the Gumbel root takes no Dirichlet noise
     g.gumbel_drawn = 0;
     // budget mix: forced playouts at the root of a full search (every split-step search of such an engine is a full one)
-    g.forced = sp->tc.budget && sp->budget.forced_k > 0.0 && sp->games[slot].cur_full ? 1 : 0;
+    g.forced = is_budget(sp->tc) && sp->budget.forced_k > 0.0 && sp->games[slot].cur_full ? 1 : 0;
     g.root_q_from_v = 0;
     g.root_fresh = fresh ? 1 : 0;
     g.flip_root_v = (sp->cfg.value_from_white && pos.turn == BLACK) ? 1 : 0;
@@ -107,7 +139,7 @@ static void finish_game(m0_selfplay* sp, int slot, bool resigned, int resigner, 
         o->z.resize(hgm.nstates);
         for (int i = 0; i < hgm.nstates; ++i) o->z[i] = z * (float)hgm.turns[i];
         o->played.assign(hgm.history.begin(), hgm.history.end());
-        if (sp->tc.budget) { o->budget = true; o->full = hgm.full; o->sims.assign(hgm.sims_used.begin(), hgm.sims_used.end()); }
+        if (is_budget(sp->tc)) { o->budget = true; o->full = hgm.full; o->sims.assign(hgm.sims_used.begin(), hgm.sims_used.end()); }
         if (hgm.book_index >= 0) o->start_fen = sp->book_fens[hgm.book_index];
         if (c.ssl_targets && (int)hgm.rec_pos.size() == hgm.nstates) {
             // targets for all plies of the game in one launch on the engine stream
@@ -165,13 +197,13 @@ static void begin_move(m0_selfplay* sp, int slot, int child_slot) {
     // mcts.py:378-387 draws random.randint only when the cap is configured
     const bool cap_draws = c.playout_random_frac > 0.0 && c.num_simulations > 0;
     // budget mix (include/m0_budget.h): the ply's draw of the game's budget stream decides between a full and a fast search
-    hgm.cur_full = !sp->tc.budget || budget_is_full(c.seed, hgm.game_index, hgm.nstates, sp->budget.full_prob);
-    if (sp->tc.budget) ++(hgm.cur_full ? sp->budget_full : sp->budget_fast);
+    hgm.cur_full = !is_budget(sp->tc) || budget_is_full(c.seed, hgm.game_index, hgm.nstates, sp->budget.full_prob);
+    if (is_budget(sp->tc)) ++(hgm.cur_full ? sp->budget_full : sp->budget_fast);
     const int budget = hgm.cur_full ? c.num_simulations : sp->budget.fast_simulations;
     int sims = playout_cap(budget, c.playout_random_frac, cap_draws ? hgm.rng.next() : 0.0);
     hgm.cur_sims = sims;
     if (c.fresh_tree_per_move || c.tt_merge) root = ROOT_FRESH;   // tt_merge: the table lives for one search (see m0_engine.h)
-    if (sp->tc.gumbel) root = ROOT_FRESH;                          // the halving schedule assumes unvisited root children
+    if (is_gumbel(sp->tc)) root = ROOT_FRESH;                      // the halving schedule assumes unvisited root children
     // ... except in a match engine, where each side's table lives for the whole game
     if (match && c.tt_merge) root = hgm.nstates == 0 ? ROOT_FIRST_OF_GAME : ROOT_FROM_SIDE_TABLE;
     const bool dir = (c.dirichlet_plies < 0 || hgm.nstates < c.dirichlet_plies) && hgm.cur_full;   // a fast search takes no noise
@@ -212,46 +244,44 @@ static void start_game(m0_selfplay* sp, int slot) {
     begin_move(sp, slot, ROOT_FRESH);
 }
 
-// MCTS.run epilogue + the rest of the per-ply loop body (mcts.py:431-507, internal.py:408-539)
-static void finish_search(m0_selfplay* sp, int slot) {
-    HostGame& hgm = sp->games[slot];
-    const m0_selfplay_cfg& c = sp->cfg;
+// What a finished search gives the game loop -- the only part of a ply's end that knows the search modes.
+// target: per root child its share of the policy target (recorded as float); visits: the counts the move is sampled from; pick: the
+// move the search picked itself (index into the root children), -1: it is sampled
+struct SearchOutcome { std::vector<double> target; std::vector<int32_t> visits; int pick; };
+static SearchOutcome search_outcome(m0_selfplay* sp, int slot, long total) {
+    const HostGame& hgm = sp->games[slot];
     const RootResult& R = sp->hres[slot];
-    const GameDev& g = sp->hg[slot];
     const int k = R.nchild;
-    long total = 0;
-    int maxv = 0;
-    for (int i = 0; i < k; ++i) { total += R.child_n[i]; if (R.child_n[i] > maxv) maxv = R.child_n[i]; }
-    if (k <= 0 || total <= 0) {        // mcts.py:435-463 raises RuntimeError: the game is dropped (no record), counted
-        sp->stats.arena_overflows++;   // in stats.arena_overflows, which the worker logs
-        hgm.nstates = 0;               // no rows -> finish_game emits no training record
-        hgm.states.clear(); hgm.pis.clear(); hgm.masks.clear(); hgm.search_values.clear(); hgm.turns.clear();
-        hgm.sims_used.clear(); hgm.full.clear(); hgm.rec_pos.clear();
-        finish_game(sp, slot, false, 0, true, 0.f);
-        return;
-    }
-    const double root_q = R.root_n > 0 ? R.root_q : g.root_v;
-    // Gumbel root search: the target is the improved policy and the move is the search's own pick (include/m0_gumbel.h)
-    const GumbelResult* GR = sp->tc.gumbel ? &sp->hgres[slot] : nullptr;
-    // budget mix, a full search with forced playouts and target pruning: the visits that only the forcing brought are taken out
-    // of the target again, and the move is sampled from what is left (include/m0_budget.h)
-    const bool pruned = sp->tc.budget && hgm.cur_full && sp->budget.prune_targets && sp->budget.forced_k > 0.0;
-    std::vector<int32_t> visits(R.child_n, R.child_n + k);
-    std::vector<double> pruned_pi;
-    if (pruned) {
-        pruned_pi.resize(k);
+    SearchOutcome out{std::vector<double>(k), std::vector<int32_t>(R.child_n, R.child_n + k), -1};
+    for (int i = 0; i < k; ++i) out.target[i] = (double)R.child_n[i] / (double)total;     // mcts.py:828-837: visits over their sum
+    auto own = [k](int pick) { return pick >= 0 && pick < k ? pick : 0; };
+    if (is_gumbel(sp->tc)) {
+        // the improved policy and the search's own pick: no temperature, no low_visit_threshold, the Gumbel draw is the sampling
+        out.target.assign(sp->hgres[slot].pi, sp->hgres[slot].pi + k);
+        out.pick = own(sp->hgres[slot].pick);
+    } else if (is_budget(sp->tc) && hgm.cur_full && sp->budget.prune_targets && sp->budget.forced_k > 0.0) {
+        // a full search with forced playouts and target pruning: the visits that only the forcing brought are taken out of the
+        // target again, and the move is sampled from what is left (include/m0_budget.h)
         sp->budget_pruned += (uint64_t)budget_prune(k, R.child_prior, R.child_q, R.child_n, R.root_n, cpuct_at_root(sp->tc),
-                                                    sp->budget.forced_k, visits.data(), pruned_pi.data(), nullptr);
+                                                    sp->budget.forced_k, out.visits.data(), out.target.data(), nullptr);
+    } else if (is_proof(sp->tc) && sp->kind == EngineKind::Match) {
+        // a match engine plays the search's own move -- the shortest proven win, the longest defence, never a move that is proven
+        // lost while another is not; most visits with nothing proven -- but a sampled opening ply stays sampled till then
+        const ProofResult& PR = sp->hpres[slot];
+        if (PR.state != PROOF_NONE || !(sp->cfg.arena_temp > 1e-3 && hgm.nstates < sp->cfg.arena_temp_plies)) out.pick = own(PR.pick);
     }
-    // a child's share of the policy target as recorded (mcts.py:828-837: visits over their sum)
-    auto target = [&](int i) {
-        return GR ? (float)GR->pi[i] : pruned ? (float)pruned_pi[i] : (float)((double)R.child_n[i] / (double)total);
-    };
+    return out;
+}
+
+// The searched position becomes a row of the game's record (planes, policy target, legal mask) and an entry of its entropy window.
+static void record_ply(m0_selfplay* sp, HostGame& hgm, const RootResult& R, const std::vector<double>& target) {
+    const m0_selfplay_cfg& c = sp->cfg;
+    const int k = R.nchild;
     const size_t T = (size_t)hgm.nstates;
     if (c.record_games) {
         hgm.pis.resize((T + 1) * 4672, 0.f);
         float* pi = hgm.pis.data() + T * 4672;
-        for (int i = 0; i < k; ++i) pi[R.child_idx[i]] = target(i);
+        for (int i = 0; i < k; ++i) pi[R.child_idx[i]] = (float)target[i];
         hgm.states.resize((T + 1) * 19 * 64);
         encode_planes_f32(hgm.pos, hgm.states.data() + T * 19 * 64);
         if (c.ssl_targets) hgm.rec_pos.push_back(hgm.pos);
@@ -266,58 +296,62 @@ static void finish_search(m0_selfplay* sp, int slot) {
         }
     }
     // entropy of pi (internal.py:430-436)
-    {
-        double ent = 0.0;
-        for (int i = 0; i < k; ++i) {
-            double p = (double)target(i);
-            if (p < 1e-12) p = 1e-12;
-            ent -= p * log(p);
-        }
-        ent -= (double)(4672 - k) * (1e-12 * log(1e-12));
-        hgm.entropy_sum += ent; hgm.entropy_count++;
-        hgm.resign.recent_entropies.push_back(ent);
-        if ((int)hgm.resign.recent_entropies.size() > c.resign_window) hgm.resign.recent_entropies.erase(hgm.resign.recent_entropies.begin());
+    double ent = 0.0;
+    for (int i = 0; i < k; ++i) { const double p = std::max((double)(float)target[i], 1e-12); ent -= p * log(p); }   // of the recorded share
+    ent -= (double)(4672 - k) * (1e-12 * log(1e-12));
+    hgm.entropy_sum += ent; hgm.entropy_count++;
+    hgm.resign.recent_entropies.push_back(ent);
+    if ((int)hgm.resign.recent_entropies.size() > c.resign_window) hgm.resign.recent_entropies.erase(hgm.resign.recent_entropies.begin());
+}
+
+// MCTS.run epilogue + the rest of the per-ply loop body (mcts.py:431-507, internal.py:408-539): search_outcome, record_ply, then --
+// here, knowing no mode -- the move (the search's own or sampled), resignation, the tablebase verdict and the next search.
+static void finish_search(m0_selfplay* sp, int slot) {
+    HostGame& hgm = sp->games[slot];
+    const m0_selfplay_cfg& c = sp->cfg;
+    const RootResult& R = sp->hres[slot];
+    const int k = R.nchild;
+    long total = 0;
+    for (int i = 0; i < k; ++i) total += R.child_n[i];
+    if (k <= 0 || total <= 0) {        // mcts.py:435-463 raises RuntimeError: the game is dropped (no record), counted
+        sp->stats.arena_overflows++;   // in stats.arena_overflows, which the worker logs
+        hgm.nstates = 0;               // no rows -> finish_game emits no training record
+        hgm.states.clear(); hgm.pis.clear(); hgm.masks.clear(); hgm.search_values.clear(); hgm.turns.clear();
+        hgm.sims_used.clear(); hgm.full.clear(); hgm.rec_pos.clear();
+        finish_game(sp, slot, false, 0, true, 0.f);
+        return;
     }
+    const SearchOutcome out = search_outcome(sp, slot, total);
+    record_ply(sp, hgm, R, out.target);
     // temperature + move choice (internal.py:386-394, 418-427, 690-735)
-    double temp = temperature_for(hgm.pos.fullmove, c.temperature_start, c.temperature_end, c.temperature_moves);
-    if (c.low_visit_threshold > 0 && maxv < c.low_visit_threshold && temp < 0.8) temp = 0.8;
-    int pick;
-    // proof search (include/m0_proof.h): a match engine plays the search's own move -- the shortest proven win, the longest
-    // defence, never a move that is proven lost while another is not; with nothing proven it is the most visited move
-    const ProofResult* PR = sp->tc.proof && sp->kind == EngineKind::Match ? &sp->hpres[slot] : nullptr;
-    if (GR) {                                  // no temperature, no low_visit_threshold: the Gumbel draw is the sampling
-        pick = GR->pick >= 0 && GR->pick < k ? GR->pick : 0;
-    } else if (PR && (PR->state != PROOF_NONE || !(c.arena_temp > 1e-3 && hgm.nstates < c.arena_temp_plies))) {
-        pick = PR->pick >= 0 && PR->pick < k ? PR->pick : 0;      // (a sampled opening ply stays sampled while nothing is proven)
-    } else if (sp->kind == EngineKind::Match) {       // arena.py:73-106 (the uniform is drawn only on the sampling branch, as np.random.choice is)
+    int pick = out.pick;
+    if (pick < 0 && sp->kind == EngineKind::Match) {  // arena.py:73-106 (the uniform is drawn only on the sampling branch, as np.random.choice is)
         const bool sampling = c.arena_temp > 1e-3 && hgm.nstates < c.arena_temp_plies;
-        pick = arena_choose_move(visits.data(), k, c.arena_temp, hgm.nstates, c.arena_temp_plies, sampling ? hgm.rng.next() : 0.0);
-    } else {
-        pick = sample_move_index(visits.data(), k, temp, sample_move_draws(visits.data(), k, temp) ? hgm.rng.next() : 0.0);
+        pick = arena_choose_move(out.visits.data(), k, c.arena_temp, hgm.nstates, c.arena_temp_plies, sampling ? hgm.rng.next() : 0.0);
+    } else if (pick < 0) {
+        double temp = temperature_for(hgm.pos.fullmove, c.temperature_start, c.temperature_end, c.temperature_moves);
+        const int maxv = *std::max_element(R.child_n, R.child_n + k);
+        if (c.low_visit_threshold > 0 && maxv < c.low_visit_threshold && temp < 0.8) temp = 0.8;
+        pick = sample_move_index(out.visits.data(), k, temp, sample_move_draws(out.visits.data(), k, temp) ? hgm.rng.next() : 0.0);
     }
-    const Move mv = R.child_mv[pick];
-    hgm.search_values.push_back((float)root_q);
-    hgm.turns.push_back(hgm.pos.turn == WHITE ? 1 : -1);
-    hgm.sims_used.push_back(hgm.cur_sims);
-    hgm.full.push_back(hgm.cur_full ? 1 : 0);
-    hgm.nstates++;
-    sp->stats.plies++;
+    const double root_q = R.root_n > 0 ? R.root_q : sp->hg[slot].root_v;
+    hgm.search_values.push_back((float)root_q); hgm.turns.push_back(hgm.pos.turn == WHITE ? 1 : -1);
+    hgm.sims_used.push_back(hgm.cur_sims); hgm.full.push_back(hgm.cur_full ? 1 : 0);
+    hgm.nstates++; sp->stats.plies++;
     // resign (internal.py:507-536)
     if (sp->kind != EngineKind::Match && resign_update(hgm.resign, root_q, hgm.nstates, c)) {
         const bool white = hgm.pos.turn == WHITE;
         finish_game(sp, slot, true, white ? 1 : 2, true, white ? -1.f : 1.f);
         return;
     }
-    hgm.play(mv);
+    hgm.play(R.child_mv[pick]);
     // tablebase hit after the move (internal.py:559-581): the game ends with the table's verdict, from White's point of view
     // (a match engine too, once the tables are attached through m0_selfplay_set_search_tablebase)
-    if (sp->tb) {
-        int wdl = 0, dtm = 0;
-        if (tb_probe(sp->tb->set, hgm.pos, sp->tb_max_pieces, wdl, dtm)) {
-            sp->tb_adjudications++;
-            finish_game(sp, slot, false, 0, true, (float)(hgm.pos.turn == WHITE ? wdl : -wdl));
-            return;
-        }
+    int wdl = 0, dtm = 0;
+    if (sp->tb && tb_probe(sp->tb->set, hgm.pos, sp->tb_max_pieces, wdl, dtm)) {
+        sp->tb_adjudications++;
+        finish_game(sp, slot, false, 0, true, (float)(hgm.pos.turn == WHITE ? wdl : -wdl));
+        return;
     }
     begin_move(sp, slot, pick);
 }
@@ -399,12 +433,7 @@ int refill(m0_selfplay* sp) {
 
 // The searches that the last expand finished become moves; games end, free slots start the next ones.
 static int harvest_games(m0_selfplay* sp) {
-    if (!M0_HIP(sp->hip, hipMemcpy(sp->hres.data(), sp->d.results, sizeof(RootResult) * sp->G, hipMemcpyDeviceToHost)))
-        return m0_hip_error(sp->hip, "harvest failed");
-    if (sp->tc.gumbel && !M0_HIP(sp->hip, hipMemcpy(sp->hgres.data(), sp->d.gumbel_results, sizeof(GumbelResult) * sp->G, hipMemcpyDeviceToHost)))
-        return m0_hip_error(sp->hip, "harvest failed");
-    if (sp->tc.proof && !M0_HIP(sp->hip, hipMemcpy(sp->hpres.data(), sp->d.proof_results, sizeof(ProofResult) * sp->G, hipMemcpyDeviceToHost)))
-        return m0_hip_error(sp->hip, "harvest failed");
+    if (!results_d2h(sp, 0, sp->G)) return m0_hip_error(sp->hip, "harvest failed");
     for (int s = 0; s < sp->G; ++s) {
         if (!(sp->hg[s].active && sp->hg[s].finished)) continue;
         if (sp->hg[s].overflow) sp->stats.arena_overflows++;

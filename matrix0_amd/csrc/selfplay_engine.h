@@ -166,12 +166,9 @@ struct m0_selfplay {
                                           // m0_selfplay_set_search_tablebase), for a submitted root (analysis engines)
     int tb_max_pieces = 0;                // ... for positions with at most this many men (d.tb_set: the probe inside the search)
     uint64_t tb_adjudications = 0;        // games it ended
-    // Gumbel root search (m0_selfplay_set_gumbel; the switch itself is tc.gumbel)
+    bool search_begun = false;            // m0_search_begin was called: the mode (tc.mode, mode_settable) can no longer be set
     std::vector<GumbelResult> hgres;      // host copies of d.gumbel_results, beside hres
-    bool search_begun = false;            // m0_search_begin was called: the mode can no longer be set
-    // proof search (m0_selfplay_set_proof; the switch itself is tc.proof)
     std::vector<ProofResult> hpres;       // host copies of d.proof_results, beside hres
-    // self-play budget mix (m0_selfplay_set_budget; the switch itself is tc.budget)
     m0_budget_cfg budget = {1.0, 1, 0.0, 0};
     uint64_t budget_full = 0, budget_fast = 0, budget_pruned = 0;   // searches of either kind, visits pruned from targets
 };
@@ -202,18 +199,17 @@ inline bool hip_ok(m0_selfplay* sp, const char* context) {
 //
 //   call                                                            accepted by
 //   m0_selfplay_step, _poll, _set_openings                          self-play, match
-//   m0_selfplay_ext_select, _ext_expand, m0_selfplay_set_tablebase,
-//   m0_selfplay_set_gumbel, m0_search_gumbel_result,
-//   m0_selfplay_set_budget, m0_search_budget_result,
-//   m0_selfplay_budget_stats                                        self-play
+//   m0_selfplay_ext_select, _ext_expand, m0_selfplay_set_tablebase   self-play
 //   m0_arena_ext_select, _ext_expand                                match
 //   m0_search_*                                                     self-play, match (a match engine is accepted as it always
 //                                                                   was, although nothing drives one this way)
 //   m0_analysis_*                                                   analysis
-//   m0_search_proof_result                                          self-play, match
 //   m0_selfplay_stats_get, _running, _last_batch_nhwc,
-//   _set_search_tablebase, _tb_leaves, _tb_adjudications,
+//   _set_search_tablebase, _tb_leaves, _tb_adjudications            every kind
+//   m0_selfplay_set_gumbel, m0_search_gumbel_result,
+//   m0_selfplay_set_budget, m0_search_budget_result, _budget_stats  self-play
 //   m0_selfplay_set_proof                                           every kind
+//   m0_search_proof_result                                          self-play, match
 bool kind_accepted(const m0_selfplay* sp, const char* what, unsigned kinds);   // false: the error string is set
 #define M0_ENGINE_CALL_OR(null_result, sp, what, kinds, on_device)                    \
     if (!(sp)) { m0_set_error(what ": sp is null"); return null_result; }             \
@@ -236,6 +232,12 @@ void begin_search(m0_selfplay* sp, int slot, int sims, bool dirichlet, int root)
 void arm_slot_search(m0_selfplay* sp, int slot, int sims, bool dirichlet, bool fresh);
 int apply_advances(m0_selfplay* sp);            // control blocks -> device, advance_kernel over sp->adv, which is empty afterwards
 int run_select(m0_selfplay* sp, int* rows_out);
+// The search mode (sp->tc.mode).  The guard of the three mode setters: M0_OK when `wanted`, which the messages call `name`, may be
+// set or taken back now -- no game or search has started, no compat.tt_merge, no other mode on; else M0_ERR_STATE / _INVALID.
+int mode_settable(m0_selfplay* sp, SearchMode wanted, const char* name);
+// The shared part of the m0_search_<mode>_result calls: a bad slot g, M0_ERR_STATE with "`what`: <the mode> is not set on this engine",
+// M0_OK and *finished false while the search runs; else slot g's RootResult and mode result are copied to their host mirrors.
+int mode_result_fetch(m0_selfplay* sp, int g, SearchMode mode, const char* what, bool* finished);
 int refill(m0_selfplay* sp);                    // before select: the first games (lazily, at the first step) / queued analyses
 int one_step(m0_selfplay* sp);                  // select -> network -> finish_step
 // second half of a step: expand / backup on the device, the counters, then the harvest of the finished searches

@@ -20,6 +20,10 @@ static_assert(M0_MAX_CHILDREN == m0::M0_GUMBEL_MAX_K, "gumbel_core.h and include
 static_assert(M0_MAX_CHILDREN == m0::M0_BUDGET_MAX_K, "budget_core.h and include/m0_budget.h count on 256 root children at most");
 constexpr int M0_NHWC_C = 32;          // channel stride of the fp16 NHWC network input (M0_PLANES used, the rest zero)
 
+// The searches an engine can run: PUCT, the Gumbel root search (tree_gumbel.h), the proof search (tree_proof.h) and the self-play
+// budget mix (tree_forced.h; at the root of a search with GameDev::forced).  All but MODE_PUCT exclude compat.tt_merge.
+enum SearchMode : int { MODE_PUCT = 0, MODE_GUMBEL, MODE_PROOF, MODE_BUDGET };
+
 struct TreeCfg {              // MCTSConfig fields the kernels read (mcts.py:61-107)
     double fpu_reduction;
     double draw_penalty;
@@ -43,18 +47,14 @@ struct TreeCfg {              // MCTSConfig fields the kernels read (mcts.py:61-
     double min_child_prior;
     int eval_cache;           // 1: leaf evaluations are looked up in / stored to the game's evaluation cache (EvalCache) and a leaf
                               //    reached twice in one pass shares one batch row
-    // Gumbel root search (m0_selfplay_set_gumbel, include/m0_gumbel.h): read by the Gumbel instantiation of select_kernel
-    // and by expand_kernel when a search finishes
-    int gumbel;               // 1: the root level is sequential halving over Gumbel scores (tree_gumbel.h)
-    m0_gumbel_cfg gumbel_cfg;
-    // proof search (m0_selfplay_set_proof, include/m0_proof.h): read by launch_select, which then runs the proof instantiation
-    // of select_kernel, and by expand_kernel when it decides whether a search has finished
-    int proof;                // 1: proven wins, losses and draws are backed up the tree (tree_proof.h)
-    // self-play budget mix (m0_selfplay_set_budget, include/m0_budget.h): read by launch_select, which then runs the forced
-    // instantiation of select_kernel, and by that instantiation at the root of a search with GameDev::forced
-    int budget;               // 1: the engine has the mode
-    double forced_k;          // forced playouts bring a visited root child up to sqrt(forced_k * prior * sum n) visits
+    SearchMode mode;          // set through mode_settable (selfplay_engine.h); launch_select runs its select_kernel, expand_kernel reads it
+    m0_gumbel_cfg gumbel_cfg; // MODE_GUMBEL: the halving schedule's width and the constants of the improved policy
+    double forced_k;          // MODE_BUDGET: forced playouts bring a visited root child up to sqrt(forced_k * prior * sum n) visits
 };
+
+M0_HD bool is_gumbel(const TreeCfg& c) { return c.mode == MODE_GUMBEL; }
+M0_HD bool is_proof(const TreeCfg& c) { return c.mode == MODE_PROOF; }
+M0_HD bool is_budget(const TreeCfg& c) { return c.mode == MODE_BUDGET; }
 
 // select_kernel's cpuct_at (tree_select.hip) at depth 0, for the host: the constant the root's children were scored with
 inline double cpuct_at_root(const TreeCfg& c) {

@@ -348,7 +348,7 @@ __global__ __launch_bounds__(64) void expand_kernel(TreeDev d, TreeCfg c) {
     const Arena A = arena_of(d.t, g, gd->arena);
     // proof search: a search whose root is proven has finished, whatever is left of its budget -- also one that select_kernel
     // gave no sample because its root was proven when it started (the subtree it took over)
-    const bool proven = c.proof && A.proof[gd->root] != 0;
+    const bool proven = is_proof(c) && A.proof[gd->root] != 0;
     if (ns <= 0 && !(proven && !gd->finished)) return;
     const ExpandEnv E{A, d.t.cap, gd, TK, TN, d.tt_cap, &X, lane};
     const Sample* S = d.samples + (size_t)g * (d.L + 1);
@@ -422,8 +422,8 @@ __global__ __launch_bounds__(64) void expand_kernel(TreeDev d, TreeCfg c) {
         gd->root_q = A.q[root];
     }
     if (fin) write_root_result(d.results + g, A, root, lane);
-    if (fin && c.gumbel) write_gumbel_result(d, c, A, gd, g, root, lane);   // beside it: the move and the improved policy
-    if (fin && c.proof) write_proof_result(d, A, g, root, lane);            // ... or what the search proved, and the move
+    if (fin && is_gumbel(c)) write_gumbel_result(d, c, A, gd, g, root, lane);   // beside it: the move and the improved policy
+    if (fin && is_proof(c)) write_proof_result(d, A, g, root, lane);            // ... or what the search proved, and the move
 }
 
 hipError_t launch_expand(const TreeDev& d, const TreeCfg& c, hipStream_t st) {

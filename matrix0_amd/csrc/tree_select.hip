@@ -172,21 +172,22 @@ static_assert(sizeof(TopCache) == M0_SEL_CACHE_BYTES, "32 bytes of select fields
 // select_kernel measured 25 us (1.5 %) slower per call.
 #define TOP(f, hit, i) ((hit) ? TC->f[i] : A.f[i])
 
-// GUMBEL: the instantiation for the Gumbel root search (TreeCfg::gumbel, tree_gumbel.h).  Only the root level differs: no
+// GUMBEL: the instantiation for the Gumbel root search (MODE_GUMBEL, tree_gumbel.h).  Only the root level differs: no
 // Dirichlet noise, a pass that ends at the phase boundary of the halving schedule, and at depth 0 the pick by scheduled visit
 // count and Gumbel score in place of the PUCT scan (no jitter draw there).  A template parameter, not a field read in the scan:
 // the PUCT instantiation is the kernel it was.
-// PROOF: the instantiation for the proof search (TreeCfg::proof, tree_proof.h, include/m0_proof.h).  The nodes' proofs are read
+// PROOF: the instantiation for the proof search (MODE_PROOF, tree_proof.h, include/m0_proof.h).  The nodes' proofs are read
 // through PRF: the tree top's from an LDS copy beside TopCache, the others from the arena.  A terminal leaf is proven at its
 // first visit and the proof is combined up its path; a descent stops at a proven node; the scan passes over children that
 // are won for their own mover; a pass ends once the root is proven.  While no node is proven it is the PUCT search, draw by draw.
-// FORCED: the instantiation for the self-play budget mix (TreeCfg::budget, tree_forced.h, include/m0_budget.h).  The rule is per
+// FORCED: the instantiation for the self-play budget mix (MODE_BUDGET, tree_forced.h, include/m0_budget.h).  The rule is per
 // game: in a search with GameDev::forced (a full search with forced playouts; full and fast searches of different games share a
 // launch) a descent takes, at depth 0, the lowest root child in deficit where there is one.  A search without the flag is the
 // PUCT search, draw by draw.
 #define PRF(i) ((i) < ncached ? TP[i] : A.proof[i])
-template <bool GUMBEL, bool PROOF, bool FORCED>
+template <SearchMode MODE>
 __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
+    constexpr bool GUMBEL = MODE == MODE_GUMBEL, PROOF = MODE == MODE_PROOF, FORCED = MODE == MODE_BUDGET;
     extern __shared__ __attribute__((aligned(16))) char sel_cache[];
     TopCache* const TC = reinterpret_cast<TopCache*>(sel_cache);
     __shared__ uint64_t pkey[M0_MAX_DEPTH];
@@ -420,29 +421,23 @@ __global__ __launch_bounds__(64) void select_kernel(TreeDev d, TreeCfg c) {
 }
 #undef PRF
 
+// one instantiation per TreeCfg::mode, by SearchMode: the list both the dynamic-LDS attribute and the launch are taken from
+using SelectKernel = void (*)(TreeDev, TreeCfg);
+static constexpr SelectKernel SELECT_KERNELS[] = {select_kernel<MODE_PUCT>, select_kernel<MODE_GUMBEL>, select_kernel<MODE_PROOF>, select_kernel<MODE_BUDGET>};
+
 hipError_t launch_select(const TreeDev& d, const TreeCfg& c, hipStream_t st) {
     static DeviceOnce once;
     hipError_t e = once.run([] {
-        hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&select_kernel<false, false, false>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, M0_SEL_CACHE_BYTES);
-        if (e1 != hipSuccess) return e1;
-        e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&select_kernel<false, true, false>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, M0_SEL_CACHE_BYTES);
-        if (e1 != hipSuccess) return e1;
-        e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&select_kernel<false, false, true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, M0_SEL_CACHE_BYTES);
-        if (e1 != hipSuccess) return e1;
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(&select_kernel<true, false, false>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, M0_SEL_CACHE_BYTES);
+        for (SelectKernel k : SELECT_KERNELS) {
+            hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                M0_SEL_CACHE_BYTES);
+            if (e1 != hipSuccess) return e1;
+        }
+        return hipSuccess;
     });
     if (e != hipSuccess) return e;
-    // the modes exclude each other (m0_selfplay_set_gumbel, m0_selfplay_set_proof, m0_selfplay_set_budget); a proof search needs
-    // its node array
-    if (c.proof && (c.gumbel || !d.t.proof || !d.proof_results)) return hipErrorInvalidValue;
-    if (c.budget && (c.gumbel || c.proof || c.tt_merge)) return hipErrorInvalidValue;
-    if (c.gumbel) hipLaunchKernelGGL((select_kernel<true, false, false>), dim3(d.G), dim3(64), M0_SEL_CACHE_BYTES, st, d, c);
-    else if (c.proof) hipLaunchKernelGGL((select_kernel<false, true, false>), dim3(d.G), dim3(64), M0_SEL_CACHE_BYTES, st, d, c);
-    else if (c.budget) hipLaunchKernelGGL((select_kernel<false, false, true>), dim3(d.G), dim3(64), M0_SEL_CACHE_BYTES, st, d, c);
-    else hipLaunchKernelGGL((select_kernel<false, false, false>), dim3(d.G), dim3(64), M0_SEL_CACHE_BYTES, st, d, c);
+    if ((unsigned)c.mode >= sizeof(SELECT_KERNELS) / sizeof(SELECT_KERNELS[0])) return hipErrorInvalidValue;
+    if (is_proof(c) && (!d.t.proof || !d.proof_results)) return hipErrorInvalidValue;   // a proof search needs its node array
+    hipLaunchKernelGGL(SELECT_KERNELS[c.mode], dim3(d.G), dim3(64), M0_SEL_CACHE_BYTES, st, d, c);
     return hipGetLastError();
 }

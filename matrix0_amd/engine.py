@@ -113,34 +113,64 @@ def selfplay_cfg_from_dict(cfg: dict, *, concurrent_games: int, total_games: int
 GUMBEL_DEFAULTS = {"max_considered": 16, "c_visit": 50.0, "c_scale": 1.0}      # the paper's
 
 
+def _number(x) -> bool:
+    return not isinstance(x, bool) and isinstance(x, (int, float))
+
+
+def _integer(x) -> bool:
+    return not isinstance(x, bool) and isinstance(x, int)
+
+
+def _finite_nonneg(x) -> bool:
+    return _number(x) and 0.0 <= float(x) < float("inf")
+
+
+def _check_mode_config(cfg: dict, asking: str) -> None:
+    """The modes that `cfg` turns on, by their config keys, must go with `asking`, the one whose block is being read:
+    ValueError for engine.compat.tt_merge beside it and, where the budget mix is asked for, for another mode beside it."""
+    mcts, ecfg = cfg.get("mcts", {}) or {}, cfg.get("engine", {}) or {}
+    on = [name for name, is_on in (
+        ("engine.proof_search", bool(ecfg.get("proof_search", False))),
+        *((f"mcts.{k}", isinstance(mcts.get(k), dict) and mcts[k].get("enabled") is True) for k in ("gumbel", "budget"))) if is_on]
+    others = ["engine.compat.tt_merge"] if bool((ecfg.get("compat", {}) or {}).get("tt_merge", False)) else []
+    if asking == "mcts.budget":
+        others += [name for name in on if name != asking]
+    if others:
+        raise ValueError(f"{asking} does not go with {others[0]}")
+
+
+def _mode_block(cfg: dict, key: str, defaults: dict, checks: dict) -> Optional[dict]:
+    """`mcts.<key>` of config.yaml with `defaults` merged in; None without the block or with `enabled: false`.  A block that is
+    present has to be right: ValueError for anything but a mapping with a boolean `enabled`, for an unknown key, for a value
+    that fails its entry of `checks` (field: (predicate, what it must be)), and for a mode that does not go with the others."""
+    b = (cfg.get("mcts", {}) or {}).get(key)
+    if b is None:
+        return None
+    if not isinstance(b, dict):
+        raise ValueError(f"mcts.{key} must be a mapping, not {b!r}")
+    unknown = set(b) - {"enabled", *defaults}
+    if unknown:
+        raise ValueError(f"unknown mcts.{key} keys: {sorted(map(str, unknown))}")
+    if not isinstance(b.get("enabled"), bool):
+        raise ValueError(f"mcts.{key}.enabled must be true or false")
+    v = dict(defaults, **{k: x for k, x in b.items() if k != "enabled"})
+    for field, (ok, must_be) in checks.items():
+        if not ok(v[field]):
+            raise ValueError(f"mcts.{key}.{field} must be {must_be}, not {v[field]!r}")
+    if not b["enabled"]:
+        return None
+    _check_mode_config(cfg, f"mcts.{key}")
+    return v
+
+
 def gumbel_cfg_from_dict(cfg: dict) -> Optional[GumbelCfg]:
     """`mcts.gumbel: {enabled, max_considered: 16, c_visit: 50.0, c_scale: 1.0}` of config.yaml as the library's struct (for
-    SelfplayEngine.set_gumbel); None without the block or with `enabled: false`.  A block that is present has to be right:
-    ValueError for anything but a mapping with a boolean `enabled`, for an unknown key, for a max_considered that is no integer
-    in 1..256, for a constant that is no finite number >= 0, and for the mode together with engine.compat.tt_merge."""
-    g = (cfg.get("mcts", {}) or {}).get("gumbel")
-    if g is None:
-        return None
-    if not isinstance(g, dict):
-        raise ValueError(f"mcts.gumbel must be a mapping, not {g!r}")
-    unknown = set(g) - {"enabled", *GUMBEL_DEFAULTS}
-    if unknown:
-        raise ValueError(f"unknown mcts.gumbel keys: {sorted(map(str, unknown))}")
-    if not isinstance(g.get("enabled"), bool):
-        raise ValueError("mcts.gumbel.enabled must be true or false")
-    v = dict(GUMBEL_DEFAULTS, **{k: x for k, x in g.items() if k != "enabled"})
-    m = v["max_considered"]
-    if isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= 256:
-        raise ValueError(f"mcts.gumbel.max_considered must be an integer in 1..256, not {m!r}")
-    for key in ("c_visit", "c_scale"):
-        x = v[key]
-        if isinstance(x, bool) or not isinstance(x, (int, float)) or not (0.0 <= float(x) < float("inf")):
-            raise ValueError(f"mcts.gumbel.{key} must be a finite number >= 0, not {x!r}")
-    if not g["enabled"]:
-        return None
-    if bool((((cfg.get("engine", {}) or {}).get("compat", {}) or {}).get("tt_merge", False))):
-        raise ValueError("mcts.gumbel does not go with engine.compat.tt_merge")
-    return GumbelCfg(int(m), float(v["c_visit"]), float(v["c_scale"]))
+    SelfplayEngine.set_gumbel); None without the block or with `enabled: false`.  A block that is present has to be right
+    (_mode_block): max_considered an integer in 1..256, the constants finite numbers >= 0, no engine.compat.tt_merge beside it."""
+    v = _mode_block(cfg, "gumbel", GUMBEL_DEFAULTS, {
+        "max_considered": (lambda m: _integer(m) and 1 <= m <= 256, "an integer in 1..256"),
+        "c_visit": (_finite_nonneg, "a finite number >= 0"), "c_scale": (_finite_nonneg, "a finite number >= 0")})
+    return None if v is None else GumbelCfg(int(v["max_considered"]), float(v["c_visit"]), float(v["c_scale"]))
 
 
 BUDGET_DEFAULTS = {"full_prob": 0.25, "fast_simulations": 100, "forced_k": 2.0, "prune_targets": True}   # KataGo's forced_k
@@ -150,44 +180,15 @@ BUDGET_STATS = ("full_searches", "fast_searches", "forced_descents", "pruned_vis
 def budget_cfg_from_dict(cfg: dict) -> Optional[BudgetCfg]:
     """`mcts.budget: {enabled, full_prob: 0.25, fast_simulations: 100, forced_k: 2.0, prune_targets: true}` of config.yaml as the
     library's struct (for SelfplayEngine.set_budget); None without the block or with `enabled: false`.  A block that is present
-    has to be right: ValueError for anything but a mapping with a boolean `enabled`, for an unknown key, for a full_prob that is
-    no number in (0, 1], a fast_simulations that is no integer >= 1, a forced_k that is no finite number >= 0, a prune_targets
-    that is no boolean, and for the mode together with mcts.gumbel, engine.proof_search or engine.compat.tt_merge."""
-    b = (cfg.get("mcts", {}) or {}).get("budget")
-    if b is None:
-        return None
-    if not isinstance(b, dict):
-        raise ValueError(f"mcts.budget must be a mapping, not {b!r}")
-    unknown = set(b) - {"enabled", *BUDGET_DEFAULTS}
-    if unknown:
-        raise ValueError(f"unknown mcts.budget keys: {sorted(map(str, unknown))}")
-    if not isinstance(b.get("enabled"), bool):
-        raise ValueError("mcts.budget.enabled must be true or false")
-    v = dict(BUDGET_DEFAULTS, **{k: x for k, x in b.items() if k != "enabled"})
-
-    def number(x):
-        return not isinstance(x, bool) and isinstance(x, (int, float))
-
-    p, fast, fk, prune = v["full_prob"], v["fast_simulations"], v["forced_k"], v["prune_targets"]
-    if not number(p) or not 0.0 < float(p) <= 1.0:
-        raise ValueError(f"mcts.budget.full_prob must be a number in (0, 1], not {p!r}")
-    if isinstance(fast, bool) or not isinstance(fast, int) or fast < 1:
-        raise ValueError(f"mcts.budget.fast_simulations must be an integer >= 1, not {fast!r}")
-    if not number(fk) or not 0.0 <= float(fk) < float("inf"):
-        raise ValueError(f"mcts.budget.forced_k must be a finite number >= 0, not {fk!r}")
-    if not isinstance(prune, bool):
-        raise ValueError(f"mcts.budget.prune_targets must be true or false, not {prune!r}")
-    if not b["enabled"]:
-        return None
-    ecfg = cfg.get("engine", {}) or {}
-    if bool(((ecfg.get("compat", {}) or {}).get("tt_merge", False))):
-        raise ValueError("mcts.budget does not go with engine.compat.tt_merge")
-    if bool(ecfg.get("proof_search", False)):
-        raise ValueError("mcts.budget does not go with engine.proof_search")
-    g = (cfg.get("mcts", {}) or {}).get("gumbel")
-    if isinstance(g, dict) and g.get("enabled") is True:
-        raise ValueError("mcts.budget does not go with mcts.gumbel")
-    return BudgetCfg(float(p), int(fast), float(fk), int(prune))
+    has to be right (_mode_block): full_prob a number in (0, 1], fast_simulations an integer >= 1, forced_k a finite number >= 0,
+    prune_targets a boolean, and no mcts.gumbel, engine.proof_search or engine.compat.tt_merge beside it."""
+    v = _mode_block(cfg, "budget", BUDGET_DEFAULTS, {
+        "full_prob": (lambda p: _number(p) and 0.0 < float(p) <= 1.0, "a number in (0, 1]"),
+        "fast_simulations": (lambda n: _integer(n) and n >= 1, "an integer >= 1"),
+        "forced_k": (_finite_nonneg, "a finite number >= 0"),
+        "prune_targets": (lambda x: isinstance(x, bool), "true or false")})
+    return None if v is None else BudgetCfg(float(v["full_prob"]), int(v["fast_simulations"]), float(v["forced_k"]),
+                                            int(v["prune_targets"]))
 
 
 def move_to_uci(m: int) -> str:
@@ -347,6 +348,15 @@ class SelfplayEngine:
         return {"finished": bool(fin.value), "n": cn[:k].copy(), "moves": [move_to_uci(int(x)) for x in mv[:k]],
                 "idx": idx[:k].copy(), "prior": pr[:k].copy(), "q": q[:k].copy(), "root_q": rq.value, "root_n": rn.value}
 
+    def _mode_result(self, g: int, name: str, *out):
+        """A search mode's result call `name` for slot g, beside search_result(g): `out` are its outputs in the call's order, a
+        ctypes scalar or an array of 256 per root child.  Their values: a scalar's, an array's first k (the root's children)."""
+        k = c_int(0)
+        _lib.check(self._L.m0_search_result(self._h, g, C.byref(k), None, None, None, None, None, None, None, None),
+                   "m0_search_result")
+        _lib.check(getattr(self._L, name)(self._h, g, *[ptr(o) if isinstance(o, np.ndarray) else C.byref(o) for o in out]), name)
+        return [o[: k.value].copy() if isinstance(o, np.ndarray) else o.value for o in out]
+
     # ---- Gumbel root search (include/m0_gumbel.h)
     def set_gumbel(self, gumbel: Optional[GumbelCfg] = None, *, max_considered: int = GUMBEL_DEFAULTS["max_considered"],
                    c_visit: float = GUMBEL_DEFAULTS["c_visit"], c_scale: float = GUMBEL_DEFAULTS["c_scale"]) -> None:
@@ -359,13 +369,9 @@ class SelfplayEngine:
     def search_gumbel_result(self, g: int) -> dict:
         """Beside search_result(g): `pick` (index into its children, -1 while the search runs), `v_mix`, `pi` and `gl` per root
         child, and `miss` (0 unless the schedule found no child with the visit count it asked for)."""
-        k = c_int(0); pick = c_int(-1); miss = c_int(0); vm = c_double(0)
-        _lib.check(self._L.m0_search_result(self._h, g, C.byref(k), None, None, None, None, None, None, None, None),
-                   "m0_search_result")
-        pi, gl = np.zeros(256, np.float64), np.zeros(256, np.float64)
-        _lib.check(self._L.m0_search_gumbel_result(self._h, g, C.byref(pick), C.byref(vm), ptr(pi), ptr(gl), C.byref(miss)),
-                   "m0_search_gumbel_result")
-        return {"pick": pick.value, "v_mix": vm.value, "pi": pi[: k.value].copy(), "gl": gl[: k.value].copy(), "miss": miss.value}
+        pick, v_mix, pi, gl, miss = self._mode_result(g, "m0_search_gumbel_result", c_int(-1), c_double(0),
+                                                      np.zeros(256, np.float64), np.zeros(256, np.float64), c_int(0))
+        return {"pick": pick, "v_mix": v_mix, "pi": pi, "gl": gl, "miss": miss}
 
     # ---- self-play budget mix (include/m0_budget.h)
     def set_budget(self, budget: Optional[BudgetCfg] = None, *, full_prob: float = BUDGET_DEFAULTS["full_prob"],
@@ -383,12 +389,9 @@ class SelfplayEngine:
         """Beside search_result(g): `pruned_n` and `pi` per root child (the plain visits and shares with forced_k = 0 or without
         prune_targets) and `forced_descents`, the descents the forcing rule has decided in the slot; zeros and -1 while the
         search runs."""
-        k = c_int(0); fd = c_int(-1)
-        _lib.check(self._L.m0_search_result(self._h, g, C.byref(k), None, None, None, None, None, None, None, None),
-                   "m0_search_result")
-        pn, pi = np.zeros(256, np.int32), np.zeros(256, np.float64)
-        _lib.check(self._L.m0_search_budget_result(self._h, g, ptr(pn), ptr(pi), C.byref(fd)), "m0_search_budget_result")
-        return {"pruned_n": pn[: k.value].copy(), "pi": pi[: k.value].copy(), "forced_descents": fd.value}
+        pruned_n, pi, fd = self._mode_result(g, "m0_search_budget_result", np.zeros(256, np.int32), np.zeros(256, np.float64),
+                                             c_int(-1))
+        return {"pruned_n": pruned_n, "pi": pi, "forced_descents": fd}
 
     def budget_stats(self) -> Dict[str, int]:
         """Full searches, fast searches, descents decided by the forcing rule and visits pruned from targets so far."""
@@ -406,14 +409,10 @@ class SelfplayEngine:
     def search_proof_result(self, g: int) -> dict:
         """Beside search_result(g): the root's `state` (PROOF_STATES) and `plies`, `child_state` and `child_plies` per root child
         (from the view of the child's side to move) and `pick` (index into its children, -1 while the search runs)."""
-        k = c_int(0); pick = c_int(-1); st = c_int(0); pl = c_int(0)
-        _lib.check(self._L.m0_search_result(self._h, g, C.byref(k), None, None, None, None, None, None, None, None),
-                   "m0_search_result")
-        cs, cp = np.zeros(256, np.int32), np.zeros(256, np.int32)
-        _lib.check(self._L.m0_search_proof_result(self._h, g, C.byref(st), C.byref(pl), ptr(cs), ptr(cp), C.byref(pick)),
-                   "m0_search_proof_result")
-        return {"state": PROOF_STATES[st.value], "plies": pl.value, "pick": pick.value,
-                "child_state": [PROOF_STATES[int(x)] for x in cs[: k.value]], "child_plies": cp[: k.value].copy()}
+        st, plies, cs, cp, pick = self._mode_result(g, "m0_search_proof_result", c_int(0), c_int(0), np.zeros(256, np.int32),
+                                                    np.zeros(256, np.int32), c_int(-1))
+        return {"state": PROOF_STATES[st], "plies": plies, "pick": pick,
+                "child_state": [PROOF_STATES[int(x)] for x in cs], "child_plies": cp}
 
     def search_advance(self, g: int, slot: int, sims: int, dirichlet: bool) -> None:
         _lib.check(self._L.m0_search_advance(self._h, g, slot, sims, int(dirichlet)), "m0_search_advance")
