@@ -597,6 +597,8 @@ int m0_replay_games(int hip_device, const char* const* start_fens, const uint32_
 #include "m0_batch.h"
 /* ... and the SSL target maps of the augmented rows, written by the same launch */
 #include "m0_batch_ssl.h"
+/* ... and a weight per resident row: rows drawn in proportion to it and gathered on the device, a prioritised replay buffer */
+#include "m0_batch_weighted.h"
 /* self-play budget mix: full and fast searches, forced playouts and policy-target pruning (opt-in) */
 #include "m0_budget.h"
 #endif /* M0_ENGINE_H */

@@ -146,6 +146,10 @@ class BudgetCfg(C.Structure):
     _fields_ = [("full_prob", f64), ("fast_simulations", i32), ("forced_k", f64), ("prune_targets", i32)]
 
 
+class WeightRule(C.Structure):
+    _fields_ = [("policy", f32), ("kl", f32), ("value", f32), ("floor", f32), ("cap", f32)]
+
+
 STRUCTS = {"m0_net_cfg": NetCfg, "m0_selfplay_cfg": SelfplayCfg, "m0_selfplay_stats": SelfplayStats,
            "m0_game_record": GameRecord, "m0_analysis_opts": AnalysisOpts, "m0_analysis_line": AnalysisLine,
            "m0_analysis_result": AnalysisResult}
@@ -348,6 +352,25 @@ BATCH_SSL_FUNCTIONS = {
     "m0_rowstore_bench_ssl": (i32, [i32, i32, i32, vp, vp, P(f64)]),
 }
 
+# ---- include/m0_batch_weighted.h (which m0_engine.h includes behind m0_batch_ssl.h): a weight per resident row, draws in proportion
+# to it and the batches of the drawn rows, in that header's order; tests/test_abi_batch_weighted.py compares the two ----
+WEIGHT_MAX = 65536
+WEIGHT_ONE_TICKS = 1 << 24
+WEIGHT_ROWS_MAX = 1 << 23
+WEIGHTS_INFO = ("total_ticks", "rows_with_ticks", "sanitised_or_skipped", "degenerate_draws")
+BATCH_WEIGHTED_STRUCTS = {"m0_weight_rule": WeightRule}
+BATCH_WEIGHTED_FUNCTIONS = {
+    "m0_rowstore_set_weights": (i32, [vp, vp, vp, i64, i32, vp]),
+    "m0_rowstore_fill_weights": (i32, [vp, i64, i64, f32]),
+    "m0_rowstore_scale_weights": (i32, [vp, f32]),
+    "m0_rowstore_get_weights": (i32, [vp, vp, i64, vp]),
+    "m0_rowstore_weights_info": (i32, [vp, vp]),
+    "m0_rowstore_sample": (i32, [vp, i32, u64, u64, i32, vp, vp, i32, vp]),
+    "m0_rowstore_batch_sampled": (i32, [vp, i32, u64, u64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
+    "m0_net_score_resident": (i32, [vp, vp, vp, vp, i32, P(ScoreOpts), vp, P(WeightRule)]),
+    "m0_weight_from_score": (i32, [vp, i32, P(WeightRule), vp]),
+}
+
 # ---- include/m0_budget.h (which m0_engine.h includes too): the self-play budget mix, in that header's order;
 # tests/test_abi_budget.py compares the two ----
 BUDGET_STRUCTS = {"m0_budget_cfg": BudgetCfg}
@@ -364,14 +387,15 @@ BUDGET_FUNCTIONS = {
 
 def bind(L) -> list:
     """Set restype and argtypes of every function of FUNCTIONS, LIVE_FUNCTIONS, SCORE_FUNCTIONS, SSL_SCORE_FUNCTIONS,
-    GUMBEL_FUNCTIONS, AUGMENT_FUNCTIONS, PROOF_FUNCTIONS, ROWPACK_FUNCTIONS, BATCH_FUNCTIONS, BATCH_SSL_FUNCTIONS and
-    BUDGET_FUNCTIONS on the loaded library; the names it does not export."""
+    GUMBEL_FUNCTIONS, AUGMENT_FUNCTIONS, PROOF_FUNCTIONS, ROWPACK_FUNCTIONS, BATCH_FUNCTIONS, BATCH_SSL_FUNCTIONS,
+    BATCH_WEIGHTED_FUNCTIONS and BUDGET_FUNCTIONS on the loaded library; the names it does not export."""
     missing = []
     for name, (restype, argtypes) in (list(FUNCTIONS.items()) + list(LIVE_FUNCTIONS.items()) + list(SCORE_FUNCTIONS.items()) +
                                       list(SSL_SCORE_FUNCTIONS.items()) + list(GUMBEL_FUNCTIONS.items()) +
                                       list(AUGMENT_FUNCTIONS.items()) + list(PROOF_FUNCTIONS.items()) +
                                       list(ROWPACK_FUNCTIONS.items()) + list(BATCH_FUNCTIONS.items()) +
-                                      list(BATCH_SSL_FUNCTIONS.items()) + list(BUDGET_FUNCTIONS.items())):
+                                      list(BATCH_SSL_FUNCTIONS.items()) + list(BATCH_WEIGHTED_FUNCTIONS.items()) +
+                                      list(BUDGET_FUNCTIONS.items())):
         fn = getattr(L, name, None)
         if fn is None:
             missing.append(name)

@@ -191,6 +191,27 @@ class M0Backend:
         call = "m0_net_score" if augment is None else "m0_net_score_aug"
         return self._net_score(call, len(dense[0]), (mode, label_smoothing, value_loss, huber_delta), dense, augment=augment)[0]
 
+    def score_resident(self, store, ids, kinds=None, rule=None, *, mask_mode: Optional[str] = None, label_smoothing: float = 0.0,
+                       value_loss: str = "mse", huber_delta: float = 1.0) -> np.ndarray:
+        """f32 [B, 8]: score()'s columns for rows that are resident in a device_replay.DeviceReplay on this network's device --
+        the store's batch kernel fills the network's staging buffers from ids (and kinds: None, one kind or u8 [B], as
+        store.batch takes them), nothing but the ids goes up and the columns come back (m0_net_score_resident,
+        include/m0_batch_weighted.h).  The columns are those of score(packed=...) for the same rows bit for bit.  rule: a
+        device_replay.weight_rule(...); every scored row then gets the rule's weight of its columns in the store, on the device.
+        mask_mode None: "legal" for a store with masks, "target" for one without."""
+        if not self._finalized:
+            raise RuntimeError("weights not loaded")
+        ids, kinds = store._ids_kinds(ids, kinds)
+        mode = resolve_mask_mode(None, None, mask_mode or ("legal" if store.with_mask else "target"))
+        opts = score_opts(mode, label_smoothing, value_loss, huber_delta)
+        rows = np.empty((len(ids), _abi.SCORE_COLS), dtype=np.float32)
+        rc = self._L.m0_net_score_resident(self._h, store._h, _lib.ptr(ids), _lib.ptr(kinds), len(ids), C.byref(opts), _lib.ptr(rows),
+                                           C.byref(rule) if rule is not None else None)
+        if rc == _lib.M0_ERR_NONFINITE:
+            raise NonFiniteScore(f"m0_net_score_resident failed ({rc}): {_lib.last_error()}", rows)
+        _lib.check(rc, "m0_net_score_resident")
+        return rows
+
     def _net_score(self, call: str, B: int, loss: tuple, dense=(), *, augment=None, packed=None, ssl_targets=None):
         """The one way into m0_net_score and its _aug, _packed and _ssl variants: the options (loss: score_opts' arguments), the
         output arrays [rows] or [rows, ssl_rows], the call, and NonFiniteScore with those arrays or _lib.check for its answer."""

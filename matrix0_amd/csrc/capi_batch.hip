@@ -19,69 +19,15 @@
 #include "batch_host.h"
 #include "batch_kernels.h"
 #include "capi_common.h"
+#include "rowstore.h"
 #include "rowpack_kernels.h"
 #include "tree.h"
 
 using namespace m0batch;
+using namespace m0store;
 using m0rowpack::pack_host;
 
 namespace {
-
-constexpr int SLOTS = 4;
-
-int invalid(const std::string& why) { m0_set_error(why); return M0_ERR_INVALID; }
-
-struct Segment {
-    int64_t first = 0, rows = 0, raw_rows = 0;
-    size_t bytes = 0;
-    uint8_t* dev = nullptr;               // a device store's copy of the block
-    SegBlock host;                        // a host store's block
-    const SegView* view() const { return reinterpret_cast<const SegView*>(dev ? dev : host.bytes.data()); }
-};
-
-struct Slot {
-    RowRef* pinned = nullptr;
-    RowRef* dev = nullptr;
-    int cap = 0;
-    hipEvent_t done = nullptr;
-    bool busy = false;
-};
-
-}  // namespace
-
-struct m0_rowstore {
-    int device = M0_ROWSTORE_HOST;
-    bool with_mask = false;
-    HipStatus hs;
-    std::mutex mu;
-    std::deque<Segment> segs;
-    int64_t next_id = 0;
-    Slot slots[SLOTS];
-    unsigned turn = 0;
-    std::vector<RowRef> refs;             // a host store's descriptor
-    // outputs of a batch that goes to host memory
-    float* o_planes = nullptr;
-    float* o_pi = nullptr;
-    float* o_z = nullptr;
-    uint8_t* o_mask = nullptr;
-    int o_cap = 0;
-    // ... and of its SSL target maps, from the first batch that asks for them (m0_rowstore_batch_ssl)
-    float* o_ssl = nullptr;
-    int32_t* o_status = nullptr;
-    int o_ssl_cap = 0;
-
-    bool on_device() const { return device >= 0; }
-    int64_t resident() const { return segs.empty() ? 0 : segs.back().first + segs.back().rows - segs.front().first; }
-};
-
-namespace {
-
-// every batch enqueued so far has finished
-bool drain(m0_rowstore* s) {
-    for (Slot& sl : s->slots)
-        if (sl.busy) { M0_HIP(s->hs, hipEventSynchronize(sl.done)); sl.busy = false; }
-    return s->hs.ok();
-}
 
 void free_outputs(m0_rowstore* s) {
     (void)hipFree(s->o_planes); (void)hipFree(s->o_pi); (void)hipFree(s->o_z); (void)hipFree(s->o_mask);
@@ -93,14 +39,19 @@ void free_ssl_outputs(m0_rowstore* s) {
     s->o_ssl = nullptr; s->o_status = nullptr; s->o_ssl_cap = 0;
 }
 
-// the two outputs m0_rowstore_batch_ssl adds; `asked` false: a batch without them
-struct SslOut {
-    bool asked = false;
-    float* maps = nullptr;
-    int32_t* status = nullptr;
-};
+}  // namespace
 
-// the slot of this batch, free and holding B references
+// ---- what capi_batch_weighted.hip uses too (rowstore.h) ----
+namespace m0store {
+
+int invalid(const std::string& why) { m0_set_error(why); return M0_ERR_INVALID; }
+
+bool drain(m0_rowstore* s) {
+    for (Slot& sl : s->slots)
+        if (sl.busy) { M0_HIP(s->hs, hipEventSynchronize(sl.done)); sl.busy = false; }
+    return s->hs.ok();
+}
+
 Slot* take_slot(m0_rowstore* s, int B) {
     if (s->slots[0].cap < B) {                                            // a larger batch than any before: all slots grow at once
         drain(s);
@@ -120,7 +71,6 @@ Slot* take_slot(m0_rowstore* s, int B) {
     return s->hs.ok() ? &sl : nullptr;
 }
 
-// refs [B] of the ids, or the first id that is not resident in *missing
 bool resolve(const m0_rowstore* s, const int64_t* rows, const uint8_t* kinds, int B, RowRef* refs, int64_t* missing) {
     for (int b = 0; b < B; ++b) {
         const int64_t id = rows[b];
@@ -131,6 +81,59 @@ bool resolve(const m0_rowstore* s, const int64_t* rows, const uint8_t* kinds, in
     }
     return true;
 }
+
+int stage_outputs(m0_rowstore* s, int B, bool outputs_on_device, BatchOut& dev) {
+    if (outputs_on_device) return M0_OK;
+    if (dev.ssl.asked) {
+        if (s->o_ssl_cap < B) {
+            drain(s);
+            free_ssl_outputs(s);
+            M0_HIP(s->hs, hipMalloc((void**)&s->o_ssl, (size_t)B * SSL_FLOATS * sizeof(float)));
+            M0_HIP(s->hs, hipMalloc((void**)&s->o_status, (size_t)B * sizeof(int32_t)));
+            if (!s->hs.ok()) return m0_hip_error(s->hs, "hipMalloc failed");
+            s->o_ssl_cap = B;
+        }
+        dev.ssl.maps = s->o_ssl; dev.ssl.status = s->o_status;
+    }
+    if (s->o_cap < B) {
+        drain(s);
+        free_outputs(s);
+        const size_t N = (size_t)B;
+        M0_HIP(s->hs, hipMalloc((void**)&s->o_planes, N * PLANE_FLOATS * sizeof(float)));
+        M0_HIP(s->hs, hipMalloc((void**)&s->o_pi, N * COLS * sizeof(float)));
+        M0_HIP(s->hs, hipMalloc((void**)&s->o_z, N * sizeof(float)));
+        if (s->with_mask) M0_HIP(s->hs, hipMalloc((void**)&s->o_mask, N * COLS));
+        if (!s->hs.ok()) return m0_hip_error(s->hs, "hipMalloc failed");
+        s->o_cap = B;
+    }
+    dev.planes = s->o_planes; dev.pi = s->o_pi; dev.z = s->o_z; dev.mask = s->o_mask;
+    return M0_OK;
+}
+
+int finish_batch(m0_rowstore* s, Slot* sl, int B, const BatchOut& dev, const BatchOut& user, bool outputs_on_device, hipStream_t stream) {
+    M0_HIP(s->hs, dev.ssl.asked ? launch_batch_rows_ssl(sl->dev, B, dev.planes, dev.pi, dev.z, dev.mask, dev.ssl.maps, dev.ssl.status, stream)
+                                : launch_batch_rows(sl->dev, B, dev.planes, dev.pi, dev.z, dev.mask, stream));
+    if (M0_HIP(s->hs, hipEventRecord(sl->done, stream))) sl->busy = true;
+    if (!s->hs.ok()) return m0_hip_error(s->hs, "batch launch failed");
+    if (outputs_on_device) return M0_OK;
+    // into the caller's arrays only when the kernel has run: a failure leaves them untouched
+    if (!M0_HIP(s->hs, hipEventSynchronize(sl->done))) return m0_hip_error(s->hs, "batch kernel failed");
+    sl->busy = false;
+    const size_t N = (size_t)B;
+    M0_HIP(s->hs, hipMemcpy(user.planes, dev.planes, N * PLANE_FLOATS * sizeof(float), hipMemcpyDeviceToHost));
+    M0_HIP(s->hs, hipMemcpy(user.pi, dev.pi, N * COLS * sizeof(float), hipMemcpyDeviceToHost));
+    M0_HIP(s->hs, hipMemcpy(user.z, dev.z, N * sizeof(float), hipMemcpyDeviceToHost));
+    if (user.mask) M0_HIP(s->hs, hipMemcpy(user.mask, dev.mask, N * COLS, hipMemcpyDeviceToHost));
+    if (user.ssl.asked) {
+        M0_HIP(s->hs, hipMemcpy(user.ssl.maps, dev.ssl.maps, N * SSL_FLOATS * sizeof(float), hipMemcpyDeviceToHost));
+        M0_HIP(s->hs, hipMemcpy(user.ssl.status, dev.ssl.status, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    return s->hs.ok() ? M0_OK : m0_hip_error(s->hs, "download failed");
+}
+
+}  // namespace m0store
+
+namespace {
 
 // the argument checks of a batch that need no store
 int check_batch(const int64_t* rows, const uint8_t* kinds, int B, const float* planes, const float* pi, const float* z, const uint8_t* mask,
@@ -151,54 +154,11 @@ int device_batch(m0_rowstore* s, const int64_t* rows, const uint8_t* kinds, int 
     if (!sl) return m0_hip_error(s->hs, "row store staging failed");
     int64_t missing = 0;
     if (!resolve(s, rows, kinds, B, sl->pinned, &missing)) return invalid("row " + std::to_string(missing) + " is not resident");
-    float *dpl = planes, *dpi = pi, *dz = z;
-    uint8_t* dm = mask;
-    float* dssl = ssl.maps;
-    int32_t* dst = ssl.status;
-    if (!outputs_on_device && ssl.asked) {
-        if (s->o_ssl_cap < B) {
-            drain(s);
-            free_ssl_outputs(s);
-            M0_HIP(s->hs, hipMalloc((void**)&s->o_ssl, (size_t)B * SSL_FLOATS * sizeof(float)));
-            M0_HIP(s->hs, hipMalloc((void**)&s->o_status, (size_t)B * sizeof(int32_t)));
-            if (!s->hs.ok()) return m0_hip_error(s->hs, "hipMalloc failed");
-            s->o_ssl_cap = B;
-        }
-        dssl = s->o_ssl; dst = s->o_status;
-    }
-    if (!outputs_on_device) {
-        if (s->o_cap < B) {
-            drain(s);
-            free_outputs(s);
-            const size_t N = (size_t)B;
-            M0_HIP(s->hs, hipMalloc((void**)&s->o_planes, N * PLANE_FLOATS * sizeof(float)));
-            M0_HIP(s->hs, hipMalloc((void**)&s->o_pi, N * COLS * sizeof(float)));
-            M0_HIP(s->hs, hipMalloc((void**)&s->o_z, N * sizeof(float)));
-            if (s->with_mask) M0_HIP(s->hs, hipMalloc((void**)&s->o_mask, N * COLS));
-            if (!s->hs.ok()) return m0_hip_error(s->hs, "hipMalloc failed");
-            s->o_cap = B;
-        }
-        dpl = s->o_planes; dpi = s->o_pi; dz = s->o_z; dm = s->o_mask;
-    }
+    const BatchOut user{planes, pi, z, mask, ssl};
+    BatchOut dev = user;
+    if (const int rc = stage_outputs(s, B, outputs_on_device, dev)) return rc;
     M0_HIP(s->hs, hipMemcpyAsync(sl->dev, sl->pinned, (size_t)B * sizeof(RowRef), hipMemcpyHostToDevice, stream));
-    M0_HIP(s->hs, ssl.asked ? launch_batch_rows_ssl(sl->dev, B, dpl, dpi, dz, dm, dssl, dst, stream)
-                            : launch_batch_rows(sl->dev, B, dpl, dpi, dz, dm, stream));
-    if (M0_HIP(s->hs, hipEventRecord(sl->done, stream))) sl->busy = true;
-    if (!s->hs.ok()) return m0_hip_error(s->hs, "batch launch failed");
-    if (outputs_on_device) return M0_OK;
-    // into the caller's arrays only when the kernel has run: a failure leaves them untouched
-    if (!M0_HIP(s->hs, hipEventSynchronize(sl->done))) return m0_hip_error(s->hs, "batch kernel failed");
-    sl->busy = false;
-    const size_t N = (size_t)B;
-    M0_HIP(s->hs, hipMemcpy(planes, dpl, N * PLANE_FLOATS * sizeof(float), hipMemcpyDeviceToHost));
-    M0_HIP(s->hs, hipMemcpy(pi, dpi, N * COLS * sizeof(float), hipMemcpyDeviceToHost));
-    M0_HIP(s->hs, hipMemcpy(z, dz, N * sizeof(float), hipMemcpyDeviceToHost));
-    if (mask) M0_HIP(s->hs, hipMemcpy(mask, dm, N * COLS, hipMemcpyDeviceToHost));
-    if (ssl.asked) {
-        M0_HIP(s->hs, hipMemcpy(ssl.maps, dssl, N * SSL_FLOATS * sizeof(float), hipMemcpyDeviceToHost));
-        M0_HIP(s->hs, hipMemcpy(ssl.status, dst, N * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
-    return s->hs.ok() ? M0_OK : m0_hip_error(s->hs, "download failed");
+    return finish_batch(s, sl, B, dev, user, outputs_on_device, stream);
 }
 
 // m0_rowstore_batch and m0_rowstore_batch_ssl
@@ -313,6 +273,7 @@ void m0_rowstore_destroy(m0_rowstore* s) {
         }
         free_outputs(s);
         free_ssl_outputs(s);
+        weights_destroy(s);
         for (Segment& g : s->segs) (void)hipFree(g.dev);
     }
     delete s;
@@ -338,9 +299,15 @@ int m0_rowstore_append(m0_rowstore* s, const m0_rowpack_arrays* in, int64_t* fir
         }
         g.host = SegBlock();
     }
-    *first_row = g.first;
-    s->next_id += g.rows;
+    const int64_t rows = g.rows;
     s->segs.push_back(std::move(g));
+    if (const int rc = weights_append(s)) {                               // a weighted store: the new rows get weight 1
+        if (s->segs.back().dev) (void)hipFree(s->segs.back().dev);
+        s->segs.pop_back();
+        return rc;
+    }
+    *first_row = s->next_id;
+    s->next_id += rows;
     return M0_OK;
 }
 
@@ -357,10 +324,11 @@ int m0_rowstore_evict(m0_rowstore* s, int64_t keep_rows) {
         if (!M0_HIP(s->hs, hipSetDevice(s->device)) || !drain(s)) return m0_hip_error(s->hs, "waiting for the batches in flight failed");
     }
     for (size_t i = 0; i < drop; ++i) {
+        weights_free_segment(s, s->segs.front());
         if (s->segs.front().dev) (void)hipFree(s->segs.front().dev);
         s->segs.pop_front();
     }
-    return M0_OK;
+    return weights_evicted(s);
 }
 
 int m0_rowstore_info(m0_rowstore* s, int64_t* info) {

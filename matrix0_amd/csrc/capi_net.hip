@@ -14,6 +14,7 @@
 #include "ssl_score_core.h"
 #include "ssl_score_kernels.h"
 #include "augment_kernels.h"
+#include "rowstore.h"
 
 thread_local std::string g_m0_last_error;
 
@@ -225,6 +226,9 @@ int m0_net_infer(m0_net* n, const float* planes, int B, float* policy, float* va
 // they were uploaded, the launches m0_net_score always made; otherwise augment_rows_kernel first moves them into the second staging
 // set, and the forward and the score kernel read that.  packed (planes, pi and legal_mask null then): the staging buffers that
 // the dense rows would be copied into are filled by unpacking on the stream instead, and everything behind them is the same.
+// store (planes, pi, legal_mask, packed and z null then; include/m0_batch_weighted.h): those staging buffers are filled by the
+// batch kernel of a resident row store from ids and kinds, on the network's stream; with a rule, one more kernel behind the score
+// kernel turns each row's columns into its weight in the store.  The store's mutex is taken behind the network's.
 struct ScoreRequest {
     const float* planes = nullptr;                      // the rows: dense planes, pi and legal_mask (may be null) ...
     const float* pi = nullptr;
@@ -238,18 +242,30 @@ struct ScoreRequest {
     const uint8_t* kinds = nullptr;
     float* ssl_rows = nullptr;
     const float* ssl_targets = nullptr;
+    m0_rowstore* store = nullptr;                       // ... or resident: ids [B], kinds [B] or null
+    const int64_t* ids = nullptr;
+    const m0_weight_rule* rule = nullptr;
 };
 
 static int net_score(m0_net* n, const ScoreRequest& q) {
     const int B = q.B;
-    if (!n || (!q.packed && (!q.planes || !q.pi)) || !q.z || !q.rows) { m0_set_error("null argument"); return M0_ERR_INVALID; }
+    if (!n || (q.store ? !q.ids : (!q.packed && (!q.planes || !q.pi)) || !q.z) || !q.rows) { m0_set_error("null argument"); return M0_ERR_INVALID; }
     if (B <= 0) { m0_set_error("batch must be positive"); return M0_ERR_INVALID; }
-    const bool have_mask = q.packed ? q.packed->pos[0].mask_kind != M0_ROWPACK_MASK_NONE : q.legal_mask != nullptr;
+    const bool have_mask = q.store ? q.store->with_mask : q.packed ? q.packed->pos[0].mask_kind != M0_ROWPACK_MASK_NONE : q.legal_mask != nullptr;
     if (const char* why = m0score::bad_opts(q.opts, have_mask)) { m0_set_error(why); return M0_ERR_INVALID; }
-    if (q.packed && n->net->cfg().planes != M0_PLANES) { m0_set_error("packed rows need the 19 planes of encode_board"); return M0_ERR_INVALID; }
-    if (q.augmented)
+    if ((q.packed || q.store) && n->net->cfg().planes != M0_PLANES) { m0_set_error("packed rows need the 19 planes of encode_board"); return M0_ERR_INVALID; }
+    if (q.augmented || (q.store && q.kinds))
         if (const char* why = m0_bad_kinds(q.kinds, B)) { m0_set_error(why); return M0_ERR_INVALID; }
+    if (q.store) {
+        if (!q.store->on_device()) { m0_set_error("a host store has no rows on a device to score"); return M0_ERR_INVALID; }
+        if (q.store->device != n->device) { m0_set_error("the store is on another device than the network"); return M0_ERR_INVALID; }
+        if (q.rule)
+            if (const char* why = m0sample::bad_rule(q.rule)) { m0_set_error(why); return M0_ERR_INVALID; }
+    }
     std::lock_guard<std::mutex> lk(n->mu);
+    std::unique_lock<std::mutex> store_lk;                                    // network first, then store
+    if (q.store) store_lk = std::unique_lock<std::mutex>(q.store->mu);
+    m0store::Slot* slot = nullptr;
     int tasks = 0;
     if (q.ssl_rows) {
         tasks = n->net->cfg().self_supervised ? n->net->cfg().ssl_tasks & m0sslscore::ALL_TASKS : 0;
@@ -268,7 +284,11 @@ static int net_score(m0_net* n, const ScoreRequest& q) {
     if (rc != M0_OK) return rc;
     const bool masked = q.opts->mask_mode == M0_SCORE_MASK_LEGAL;
     const size_t cells = (size_t)B * M0_POLICY_SIZE;
-    if (q.packed) {
+    if (q.store) {
+        rc = m0store::score_gather(q.store, q.ids, q.kinds, B, n->planes_dev, n->score_pi_dev, n->score_z_dev,
+                                   have_mask ? n->score_mask_dev : nullptr, q.rule != nullptr, n->stream, &slot);
+        if (rc != M0_OK) return rc;
+    } else if (q.packed) {
         rc = m0_rowpack_unpack_to_device(hs, q.packed, n->planes_dev, n->score_pi_dev, masked ? n->score_mask_dev : nullptr, n->stream);
         if (rc != M0_OK) return rc;
         M0_HIP(hs, hipMemcpyAsync(n->score_z_dev, q.z, (size_t)B * 4, hipMemcpyHostToDevice, n->stream));
@@ -299,6 +319,10 @@ static int net_score(m0_net* n, const ScoreRequest& q) {
     // the logits and the head outputs stay where the forward left them
     M0_HIP(hs, launch_score_rows(n->logits_dev, n->value_dev, pi_in, n->score_z_dev, mask_in, B, *q.opts, n->score_rows_dev, n->stream));
     M0_HIP(hs, hipMemcpyAsync(q.rows, n->score_rows_dev, (size_t)B * M0_SCORE_COLS * 4, hipMemcpyDeviceToHost, n->stream));
+    if (q.store && q.rule && hs.ok()) {
+        rc = m0store::score_weights(q.store, slot, B, n->score_rows_dev, *q.rule, n->stream);
+        if (rc != M0_OK) return rc;
+    }
     if (q.ssl_rows) {
         M0_HIP(hs, launch_ssl_score(n->ssl_dev, tasks, n->planes_dev, q.ssl_targets ? n->ssl_targets_dev : nullptr, B, n->ssl_rows_dev,
                                     n->stream));
@@ -331,6 +355,14 @@ int m0_net_score_packed(m0_net* n, const m0_rowpack_arrays* in, const m0_score_o
     if (!in || !in->pos || !in->z || in->n <= 0 || in->n > INT_MAX) { m0_set_error("invalid argument"); return M0_ERR_INVALID; }
     ScoreRequest q;
     q.packed = in; q.z = in->z; q.B = (int)in->n; q.opts = opts; q.rows = rows;
+    return net_score(n, q);
+}
+
+int m0_net_score_resident(m0_net* n, m0_rowstore* store, const int64_t* ids, const uint8_t* kinds, int B, const m0_score_opts* opts,
+                          float* rows, const m0_weight_rule* rule) {
+    if (!store) { m0_set_error("null argument"); return M0_ERR_INVALID; }
+    ScoreRequest q;
+    q.store = store; q.ids = ids; q.kinds = kinds; q.B = B; q.opts = opts; q.rows = rows; q.rule = rule;
     return net_score(n, q);
 }
 
